@@ -14,7 +14,9 @@ flat gradient per epoch when N > 1).  value = K * T * n_envs_total / wall, the r
 policy, seeded goals).  Default: weak scaling, every GPU owns its own 4096-env shard (no data-path collective; the units
 are independent envs).  `--scaling strong` keeps 4096 envs IN TOTAL (SURVEY.md 8d(i) read literally): shards of 4096 / N.
 
-Besides the contract fields, rank 0 adds
+A plain run only sets up, warms up, times the K steps and prints the line.  `--dump-outputs DIR` writes what the last timed step
+computed (see dump_outputs) to DIR/<name>.npy before the line is printed; the inputs are seeded, so two builds compare output for
+output.  With `--full` (and without `--no-extras`) rank 0 adds
   roofline            the ray-cast run of BASELINE configs[2] (16384 envs, per-env stage_2 segment buffers, S=128) through the entry
                       point the north star names: navsim_step (step_kernel), ONE launch per env step, 64 launches per graph replay:
                       algorithmic bytes (134 + 16*S per env-step) x envs / mean launch duration from HIP events.
@@ -648,6 +650,32 @@ def env_n1_step_us(budget_s=1.5):
     return round(dt / (n - n0) * 1e6, 2)
 
 
+DUMP_ROWS = 65536   # rows of the rollout buffers dumped: a fixed, seeded sample (the full configs[1] buffers are ~170 MB)
+TIMING_KEYS = ("rollout_time", "update_time", "iter_time", "steps_per_sec", "rollout_steps_per_sec")
+
+
+def dump_outputs(trainer, lg, out_dir):
+    """What the timed path (PPOTrainer.iteration) computed in its last step, as DIR/<name>.npy: the updated actor + critic
+    parameters (params: the flat float32 buffer, all of it), the rollout rows the update ran on (obs, actions, log_probs, rewards,
+    rewards_to_go, ended: the same DUMP_ROWS seeded row indices of the T x N rows, float32) and every scalar the iteration returns
+    except its wall-clock timings (stat_<key>, float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    cfg, N, D = trainer.cfg, trainer.env.N, trainer.env.D
+    n = cfg.rollout_len * N
+    rows = np.arange(n) if n <= DUMP_ROWS else np.sort(np.random.default_rng(0).choice(n, DUMP_ROWS, replace=False))
+    idx = torch.from_numpy(rows).to(trainer.device)
+    bufs = dict(obs=trainer.obs_buf[:cfg.rollout_len].reshape(n, D), actions=trainer.act_buf.reshape(n, 2),
+                log_probs=trainer.logp_buf.reshape(n), rewards=trainer.rew_buf.reshape(n), rewards_to_go=trainer.rtg_buf.reshape(n),
+                ended=trainer.ended_buf.reshape(n))
+    arrays = {k: v.index_select(0, idx).float().cpu().numpy() for k, v in bufs.items()}
+    arrays["params"] = trainer.updater.fp.flat.float().cpu().numpy()
+    for k, v in lg.items():
+        if k not in TIMING_KEYS and isinstance(v, (int, float)):
+            arrays["stat_" + k] = np.asarray(v, dtype=np.float64)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+
+
 def dist_diagnostics(ctx, trainer, roll_ms, upd_ms, epochs=20):
     """N > 1: what a scaling run needs to be read in one shot -- every rank takes part, rank 0 reports.
       rollout_ms / update_ms    min and max over the ranks of the timed region's split (a straggler shows as max >> min)
@@ -847,7 +875,11 @@ def main():
     ap.add_argument("--epochs", type=int, default=50)
     ap.add_argument("--policy", default="mlp64x2")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip roofline / cpu_baseline legs")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other leg of the line (rooflines under rocprofv3, shards, resmlp512, time to reward, CPU baselines)")
+    ap.add_argument("--no-extras", action="store_true", help="skip roofline / cpu_baseline legs even with --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--with-pmc-file", default=None,
                     help="pmc_traffic.json recorded by tools/pmc_traffic.py in the same gpurun call (roofline.traffic comes from it)")
     ap.add_argument("--update-arith", choices=["bf16x3", "f32"], default="bf16x3",
@@ -918,6 +950,8 @@ def main():
     dt = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device=ctx.device)
     ctx.all_reduce_max(dt)
     dt = float(dt.item())
+    if args.dump_outputs and ctx.rank == 0:
+        dump_outputs(trainer, lg, args.dump_outputs)
     diag = dist_diagnostics(ctx, trainer, roll_t / args.steps * 1e3, upd_t / args.steps * 1e3) if ctx.enabled else None
 
     out = None
@@ -946,7 +980,7 @@ def main():
             "rollout_ms": round(roll_t / K * 1e3, 3), "update_ms": round(upd_t / K * 1e3, 3), "dist": diag,
             "last_iter": {k: lg[k] for k in ("avg_ep_rews", "success_rate", "episodes", "actor_loss", "critic_loss", "approx_kl")},
         }
-    if not args.no_extras and ctx.rank == 0:   # rank 0 only (the other ranks wait at the barrier below)
+    if args.full and not args.no_extras and ctx.rank == 0:   # rank 0 only (the other ranks wait at the barrier below)
         # GPU legs first and long enough (several seconds in total) for an outside utilisation sampler to see them
         prof, prof_src = rocprof_legs(["--envs-per-gpu", str(n_local), "--rollout", str(args.rollout), "--epochs", str(args.epochs), "--policy", args.policy,
                                        "--update-arith", args.update_arith])

@@ -451,7 +451,7 @@ def test_bench_two_ranks_share_one_gpu_over_gloo():
     env = dict(os.environ, NAVBOT_DIST_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(__import__("_ranks").free_port()), os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1",
-           "--envs-per-gpu", "512", "--rollout", "64", "--epochs", "3"]
+           "--envs-per-gpu", "512", "--rollout", "64", "--epochs", "3", "--full"]
     out = subprocess.run(cmd, env=env, cwd=repo, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -469,6 +469,37 @@ def test_bench_two_ranks_share_one_gpu_over_gloo():
     assert 0 < d["rollout_ms_min"] <= d["rollout_ms_max"] and 0 < d["update_ms_min"] <= d["update_ms_max"]
     assert d["allreduce_us"] > 0 and d["epoch_us_with_allreduce"] > 0 and d["epoch_us_local"] > 0
     assert d["allreduce_cost_in_epoch_us"] == pytest.approx(d["epoch_us_with_allreduce"] - d["epoch_us_local"], abs=0.02)
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_one(tmp_path):
+    """`bench.py --gpus 1` without --full: the contract line and nothing else (no extra legs), `--steps` timed steps, and
+    `--dump-outputs` writes the last timed step's results as float32 / float64 .npy files that are the same from run to run."""
+    import json
+    import subprocess
+    import sys
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        cmd = [sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--envs-per-gpu", "512",
+               "--rollout", "64", "--epochs", "3", "--dump-outputs", str(d)]
+        out = subprocess.run(cmd, cwd=repo, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, out.stdout
+        js = json.loads(lines[0])
+        assert js["metric"] == "env_steps_per_sec" and js["unit"] == "env-steps/s" and js["higher_is_better"] is True and js["dtype"] == "f32"
+        assert js["steps"] == 3 and js["value"] == pytest.approx(3 * 64 * 512 / (js["ms_per_step"] * 3e-3), rel=1e-3)
+        assert not {"roofline", "update_roofline", "cpu_baseline", "resmlp512", "time_to_reward_s"} & set(js)
+        files = {f.name: np.load(f) for f in d.iterdir()}
+        assert {"params.npy", "obs.npy", "actions.npy", "log_probs.npy", "rewards_to_go.npy", "stat_actor_loss.npy"} <= set(files)
+        assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+        assert sum(f.stat().st_size for f in d.iterdir()) <= 64 << 20
+        assert files["obs.npy"].shape == (64 * 512, 16) and np.isfinite(files["params.npy"]).all()
+        dumps.append(files)
+    assert dumps[0].keys() == dumps[1].keys()
+    for name in dumps[0]:
+        np.testing.assert_array_equal(dumps[0][name], dumps[1][name], err_msg=name)
 
 
 def test_bench_refuses_a_multi_rank_run_that_is_not_over_rccl():

@@ -6,8 +6,8 @@ mkdir -p $O
 echo "$PROF_RUN_ID" > $O/run_id.txt
 # counters first: bench.py --with-pmc-file quotes THIS call's file (same kernels: the file carries the sha256 of csrc/navsim.hip)
 python tools/pmc_traffic.py > $O/pmc_traffic.log 2>&1
-python bench.py --with-pmc-file $O/pmc_traffic.json > $O/bench_final.json 2> $O/bench_final.err
-tools/prof_stats.sh bench_final -- python bench.py --with-pmc-file $O/pmc_traffic.json > $O/bench_final_under_rocprof.log 2>&1
+python bench.py --full --with-pmc-file $O/pmc_traffic.json > $O/bench_final.json 2> $O/bench_final.err
+tools/prof_stats.sh bench_final -- python bench.py --full --with-pmc-file $O/pmc_traffic.json > $O/bench_final_under_rocprof.log 2>&1
 # the three forms of the step body at configs[2], at the Infinity Cache size and at 2x it
 for s in cfg3 s=1024 s=2048; do n=${s/=/}; n=${n/cfg3/cfg3}
   tools/prof_stats.sh step_$n -- python tools/time_step.py --$s > $O/step_${n}_rocprof.log 2>&1
