@@ -274,6 +274,43 @@ int navsim_rollout_resmlp512(navsim_t* h, const float* actor_params_dev, void* o
                              const uint32_t* step_base_dev, int32_t n_steps, void* stream);
 
 /*
+ * The evaluation loop (project_ppo/src/main.py:135-252) for the (B + 6)-64-64 actor in ONE launch: the workgroup of
+ * navsim_rollout_mlp64 (16 envs on 8 waves, env state and observation tile on chip) with the DETERMINISTIC action
+ * a = (clamp(mu0, 0, 1), clamp(mu1, -1, 1)) (main.py:197-199: no noise is drawn, no log-prob computed), no [n_steps, N, .] rows,
+ * and an episode quota kept on chip: every env plays its episodes back to back (auto_reset) and the first `quota` of them are
+ * recorded, one record each, in slot 0, 1, .. of the episode table; later episodes of that env are simulated but not recorded.
+ * A workgroup leaves the step loop once all its envs have met the quota, at the latest after n_steps steps.
+ *   actor_params_dev  as for navsim_rollout_mlp64
+ *   obs0_dev      [N, B + 6] f32 (f16 if cfg.obs_f16): the observations the episodes start from (navsim_reset), read as
+ *                 navsim_rollout_mlp64 reads row 0 of its obs_buf_dev
+ *   quota >= 1, n_steps >= 1 (quota * max_episode_steps is always enough: every episode ends by its time-out)
+ *   ep_flags_dev  [quota, N] u8   bit 0 success (arrive), bit 1 collision (done and not arrive), bit 2 timeout (ended, neither)
+ *   ep_length_dev [quota, N] i32  ep_return_dev [quota, N] f32   ep_path_dev [quota, N] f32   as navsim_step's ep_* outputs
+ *   count_dev     [N] i32         episodes recorded for env i (== quota unless n_steps ran out)
+ *   steps_dev     [ceil(N / 16)] i32   env steps workgroup k (envs 16 k .. 16 k + 15) executed before it left the loop
+ * Slots that were not reached keep what the caller put there.  Every record is bit-identical to what a loop of navppo_mlp64_act
+ * (noise_dev = zeros) / navsim_step calls yields.  The handle's env state is written back after the loop as by the rollouts, but
+ * is otherwise unspecified (the envs kept running after their quota): call navsim_reset before the handle is used again.
+ * NAVSIM_E_ARG, before anything is launched: a null handle or pointer, quota < 1, n_steps < 1, a handle without auto_reset or
+ * with max_episode_steps == 0 (an episode could never end), more than 4096 envs (only the 16-env workgroup shape has an
+ * evaluation form; navsim_set_shape has no effect here), n_beams other than 10 or 36, actor_params_dev / obs0_dev not 16-byte
+ * aligned.  The tile-box cast and the sensor-fidelity options are picked as for the rollout.
+ */
+int navsim_evaluate_mlp64(navsim_t* h, const float* actor_params_dev, const void* obs0_dev, int32_t quota, int32_t n_steps,
+                          uint8_t* ep_flags_dev, int32_t* ep_length_dev, float* ep_return_dev, float* ep_path_dev,
+                          int32_t* count_dev, int32_t* steps_dev, void* stream);
+
+/*
+ * The same with the reference's ACTIVE actor (NetActor, two residual blocks of 512 hidden units): the workgroup of
+ * navsim_rollout_resmlp512, records bit-identical to a loop of navppo_resmlp512_act (noise_dev = zeros) / navsim_step calls.
+ * Arguments, outputs and errors as for navsim_evaluate_mlp64; actor_params_dev as for navsim_rollout_resmlp512; needs
+ * n_beams == 10 (NAVSIM_E_ARG otherwise).
+ */
+int navsim_evaluate_resmlp512(navsim_t* h, const float* actor_params_dev, const void* obs0_dev, int32_t quota, int32_t n_steps,
+                              uint8_t* ep_flags_dev, int32_t* ep_length_dev, float* ep_return_dev, float* ep_path_dev,
+                              int32_t* count_dev, int32_t* steps_dev, void* stream);
+
+/*
  * n_steps calls of navsim_step with the actions of a tape, in ONE launch: the step loop of PPO.rollout (ppo.py:505-594) or of the
  * evaluation loop (main.py:176-235) when the actions do not depend on the observations being produced -- a recorded tape, a
  * scripted or random policy, an open-loop controller.  A workgroup keeps its envs for the whole tape (their state stays on chip

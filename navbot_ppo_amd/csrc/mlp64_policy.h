@@ -189,6 +189,17 @@ __device__ __forceinline__ PolicyOut policy_finish_pre(const float* __restrict__
     o.logp = -0.5f * ((d0 * d0 + d1 * d1) / var) - 1.8378770664093453f - log_var;  // ppo.py:704
     return o;
 }
+// The evaluation action (main.py:197-199): the clamped mean, no noise and no log-prob.  `+ 0.f` is policy_finish_pre's
+// fmaf(sd, 0, mu) -- a product of exactly +0 added to mu -- so the action equals that of a sampled step whose noise is zero
+// bit for bit (a mean of -0 becomes +0 on both paths).
+template <class L>
+__device__ __forceinline__ float2 policy_finish_mean(const float* __restrict__ params, const float (&pz3)[4], const float (&pz4)[4]) {
+    const float z3 = (((pz3[0] + pz3[1]) + pz3[2]) + pz3[3]) + params[L::OFF_B3];
+    const float z4 = (((pz4[0] + pz4[1]) + pz4[2]) + pz4[3]) + params[L::OFF_B4];
+    const float mu0 = 1.0f / (1.0f + expf(-z3));
+    const float mu1 = tanhf(z4);
+    return make_float2(fminf(fmaxf(mu0 + 0.f, 0.f), 1.f), fminf(fmaxf(mu1 + 0.f, -1.f), 1.f));
+}
 template <class L>
 __device__ __forceinline__ PolicyOut policy_finish(const float* __restrict__ params, const float (&pz3)[4], const float (&pz4)[4],
                                                    const float var, const float e0, const float e1) {

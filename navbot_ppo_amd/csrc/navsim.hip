@@ -465,6 +465,17 @@ struct StepIO {
     int32_t* ep_length;
     float* ep_path_out;
 };
+// EvalIO: what the evaluation kernels (evaluate_kernel, evaluate_resmlp_kernel) pass as `io` instead: no [T, N, .] rows and no
+// observation store; the rules lane of an env whose episode ends records it in slot cnt_l[env] of the [quota, N] episode table
+// while that count is below the quota.  (The StepIO base is all null: nothing of it is read in the PERSIST form.)
+struct EvalIO : StepIO {
+    int* cnt_l;          // LDS, [EPB]: episodes recorded per env (absent envs of a tail workgroup: quota)
+    int quota;
+    uint8_t* rec_flags;   // [quota, N]: 1 success (arrive), 2 collision (done and not arrive), 4 timeout (ended, neither)
+    int32_t* rec_length;  // [quota, N]
+    float* rec_return;    // [quota, N]
+    float* rec_path;      // [quota, N]
+};
 // Hook: called by EVERY wave right behind barrier B2 (the observation rows are complete but for a reset, which the rules lanes of
 // wave 0 work out next): the persistent rollout kernels run the policy of the NEXT step there, on waves that would otherwise
 // wait for the rules, reading the rows through next_obs_n below.  NoHook: nothing (step_kernel, steps_kernel).
@@ -478,6 +489,8 @@ __device__ __forceinline__ void step_body(PRef P, StepSmem<NB, EPB, NW>& sm, int
     static_assert(EPB <= 64 && EPB >= 4 && NB % 2 == 0, "EPB / NB");
     static_assert(!(PAIR && BOXES), "tile boxes describe 64-segment tiles");
     constexpr int kThreads = 64 * NW;
+    constexpr bool kEval = std::is_same<typename std::remove_cv<typename std::remove_reference<IORef>::type>::type, EvalIO>::value;
+    static_assert(!kEval || PERSIST, "the episode table is the persistent evaluation kernels' output");
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -1253,14 +1266,28 @@ __device__ __forceinline__ void step_body(PRef P, StepSmem<NB, EPB, NW>& sm, int
         double ret = ret0 + r;
         const bool timeout = (P.max_ep_steps > 0) && ((int)step >= P.max_ep_steps);  // ppo.py:552
         const bool end = d || a || timeout;
-        io.reward[row0 + i] = (float)r;
-        io.done[row0 + i] = d ? 1 : 0;
-        io.arrive[row0 + i] = a ? 1 : 0;
-        if (io.ended) io.ended[row0 + i] = end ? 1 : 0;
-        if (end) {
-            if (io.ep_return) io.ep_return[row0 + i] = (float)ret;
-            if (io.ep_length) io.ep_length[row0 + i] = (int32_t)step;
-            if (io.ep_path_out) io.ep_path_out[row0 + i] = (float)path;   // ppo.py:533-537: the final step's displacement is never added
+        if constexpr (kEval) {   // main.py:206-231: the env's first `quota` episodes, one record each; later ones are only simulated
+            if (end) {
+                const int c = io.cnt_l[e];
+                if (c < io.quota) {
+                    const size_t s = (size_t)c * (size_t)P.N + (size_t)i;
+                    io.rec_flags[s] = a ? 1 : (d ? 2 : 4);
+                    io.rec_length[s] = (int32_t)step;
+                    io.rec_return[s] = (float)ret;
+                    io.rec_path[s] = (float)path;   // ppo.py:533-537: the final step's displacement is never added
+                    io.cnt_l[e] = c + 1;
+                }
+            }
+        } else {
+            io.reward[row0 + i] = (float)r;
+            io.done[row0 + i] = d ? 1 : 0;
+            io.arrive[row0 + i] = a ? 1 : 0;
+            if (io.ended) io.ended[row0 + i] = end ? 1 : 0;
+            if (end) {
+                if (io.ep_return) io.ep_return[row0 + i] = (float)ret;
+                if (io.ep_length) io.ep_length[row0 + i] = (int32_t)step;
+                if (io.ep_path_out) io.ep_path_out[row0 + i] = (float)path;   // ppo.py:533-537: the final step's displacement is never added
+            }
         }
         path += sm.sv_d[11][e];
         float2 next_pact = act;  // ppo.py:543
@@ -1307,7 +1334,8 @@ __device__ __forceinline__ void step_body(PRef P, StepSmem<NB, EPB, NW>& sm, int
     }
     __syncthreads();  // barrier C: observation tile complete in LDS
 
-    // ---------------- coalesced store of the block's observation tile
+    // ---------------- coalesced store of the block's observation tile (the evaluation kernels keep it in LDS only)
+    if constexpr (kEval) return;
     const int n_out = nloc * D;
     if (P.obs_f16) {
         __half* o = reinterpret_cast<__half*>(io.obs_out) + (row0 + (size_t)base) * D;
@@ -1649,6 +1677,213 @@ __global__ __launch_bounds__(64 * 8) void rollout_resmlp_kernel(Params P, Rollou
         step_body<NB, EPB, SENS, true, NW, false, 0, const Params&, const StepIO&, decltype(hook)>(P, sm, next_env, io, t == R.T - 1, 0, hook);
         __syncthreads();   // the observation tile of step t + 1 is complete in sm.obs (the tile store only reads it)
     }
+}
+
+// ---------------------------------------------------------------- the evaluation form of the two persistent rollouts
+// main.evaluate (main.py:135-252) in ONE launch: rollout_kernel's / rollout_resmlp_kernel's workgroup (16 envs on 8 waves, env
+// state and observation tile in LDS) with
+//   - the deterministic action a = (clamp(mu0, 0, 1), clamp(mu1, -1, 1)) (main.py:197-199): no Philox draw, no Box-Muller, no
+//     log-prob, no noise wave and no pol_eps exchange;
+//   - no [T, N, .] rows at all: the only global stores of a step are an episode record (EvalIO, written by the env's rules lane)
+//     when an episode ends and the env's count is still below the quota -- later episodes are simulated but not recorded;
+//   - an early exit: behind barrier C of every step each wave reads the 16 counts from LDS and the workgroup leaves the loop once
+//     every env has met the quota (absent envs of a tail workgroup start at the quota).  The counts are written by wave 0 in
+//     front of barrier C and not again before barriers A / B / B2 of the next step, which no wave passes before every wave has
+//     read them: all waves of a workgroup see the same 16 values and take the same branch.  The loop is bounded by n_steps.
+// Same device functions on the same inputs as the per-step entry points (navppo_*_act with zero noise + navsim_step): the table
+// keeps their bits.  The env state goes back to HBM after the loop (the envs ran on past their quota: callers reset before reuse).
+struct EvalArgs {
+    const float* params;      // actor parameters (mlp64 / resmlp512 layout)
+    const void* obs0;         // [N, B + 6] f32 (f16: navsim_cfg.obs_f16): the reset observations
+    uint8_t* ep_flags;        // [quota, N]
+    int32_t* ep_length;       // [quota, N]
+    float* ep_return;         // [quota, N]
+    float* ep_path;           // [quota, N]
+    int32_t* count;           // [N]
+    int32_t* steps;           // [ceil(N / 16)]
+    int quota;
+    int T;
+};
+
+// what both kernels do around their step loops (tid < nloc: the env's lane)
+template <int NB, int EPB, int NW>
+__device__ __forceinline__ void eval_stage_state(const Params& P, StepSmem<NB, EPB, NW>& sm, const int e, const int i) {
+    sm.st_d[0][e] = P.x[i]; sm.st_d[1][e] = P.y[i]; sm.st_d[2][e] = P.th[i]; sm.st_d[3][e] = P.gx[i]; sm.st_d[4][e] = P.gy[i];
+    sm.st_d[5][e] = P.past_dist[i]; sm.st_d[6][e] = P.ep_ret[i]; sm.st_d[7][e] = P.ep_path[i];
+    sm.st_pact[e] = P.past_action[i];
+    sm.st_step[e] = (uint32_t)P.ep_step[i];
+    sm.st_ctr[e] = P.rng_ctr[i];
+}
+template <int NB, int EPB, int NW>
+__device__ __forceinline__ void eval_store_state(const Params& P, const StepSmem<NB, EPB, NW>& sm, const int e, const int i) {
+    P.x[i] = sm.st_d[0][e]; P.y[i] = sm.st_d[1][e]; P.th[i] = sm.st_d[2][e]; P.gx[i] = sm.st_d[3][e]; P.gy[i] = sm.st_d[4][e];
+    P.past_dist[i] = sm.st_d[5][e]; P.ep_ret[i] = sm.st_d[6][e]; P.ep_path[i] = sm.st_d[7][e];
+    P.past_action[i] = sm.st_pact[e];
+    P.ep_step[i] = (int32_t)sm.st_step[e];
+    P.rng_ctr[i] = sm.st_ctr[e];
+}
+// behind a barrier that follows the rules lanes' count updates: true on every wave of the workgroup, or on none
+template <int EPB>
+__device__ __forceinline__ bool eval_quota_met(const int* ep_cnt, const int lane, const int quota) {
+    return __builtin_amdgcn_ballot_w64(ep_cnt[lane & (EPB - 1)] < quota) == 0ull;
+}
+
+template <int NB, bool SENS, bool BOXES>
+__global__ __launch_bounds__(64 * 8) void evaluate_kernel(Params P, EvalArgs R) {
+    constexpr int EPB = 16, NW = 8, D = NB + 6, DP = D + 1, kThreads = 64 * NW;
+    using PL = mlp64::Layout<D>;
+    constexpr int KS = PL::KS;
+    __shared__ StepSmem<NB, EPB, NW> sm;
+    __shared__ int next_env;
+    __shared__ __attribute__((aligned(16))) float wts[PL::P_ACTOR + 2];   // the actor, staged once for the whole launch
+    __shared__ float2 pol_z[4][16];   // policy phase: per-tile partial sums of the two output units
+    __shared__ unsigned pol_cnt;      // arrivals of the in-step policy's four tile waves (the last one finishes)
+    __shared__ int ep_cnt[EPB];       // episodes recorded per env
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int base = blockIdx.x * EPB;
+    const int nloc = min(EPB, P.N - base);
+    for (int k = tid; k < PL::P_ACTOR; k += kThreads) wts[k] = R.params[k];
+    if (tid < nloc) eval_stage_state<NB, EPB, NW>(P, sm, tid, base + tid);
+    if (tid < EPB) ep_cnt[tid] = (tid < nloc) ? 0 : R.quota;
+    const bool half_rows = P.obs_f16 != 0;
+    for (int k = tid; k < nloc * D; k += kThreads)
+        sm.obs[(k / D) * DP + (k % D)] = half_rows ? __half2float(reinterpret_cast<const __half*>(R.obs0)[(size_t)base * D + k])
+                                                   : reinterpret_cast<const float*>(R.obs0)[(size_t)base * D + k];
+    for (int k = tid; k < 2 * NB; k += kThreads) sm.beam[k] = P.beam_cs[k];
+    for (int k = tid; k < (int)(sizeof(Rects) / 8); k += kThreads)
+        reinterpret_cast<uint64_t*>(&sm.rects)[k] = reinterpret_cast<const uint64_t*>(P.rects)[k];
+    if (tid == 0) pol_cnt = 0u;
+    __syncthreads();
+    const float sigma = SENS ? P.sigma : 0.f;
+    const int below_min = SENS ? P.below_min_mode : 0;
+    auto tile_part = [&](const int t2, auto in_step) __attribute__((always_inline)) {   // as in rollout_kernel
+        const int e = lane & 15, kk = lane >> 4;
+        const bool valid = e < nloc;
+        float xs[KS];
+        if constexpr (decltype(in_step)::value) {
+            next_obs_n<NB, EPB, NW, SENS, KS, const Params&>(P, sm, min(e, nloc - 1), KS * kk, sigma, below_min, xs);
+            if (half_rows) {
+#pragma unroll
+                for (int j = 0; j < KS; ++j) xs[j] = __half2float(__float2half_rn(xs[j]));
+            }
+        } else {
+            mlp64::policy_row<PL>(sm.obs + min(e, nloc - 1) * DP, kk, half_rows, xs);
+        }
+        if (!valid) {
+#pragma unroll
+            for (int j = 0; j < KS; ++j) xs[j] = 0.f;
+        }
+        mlp64::f32x4 c1[4];
+        mlp64::policy_hidden1<PL>(wts, xs, lane, c1);
+        float pz3, pz4;
+        mlp64::policy_tile2<PL>(wts, c1, lane, t2, pz3, pz4);
+        if (kk == 0) pol_z[t2][e] = make_float2(pz3, pz4);
+    };
+    auto finish = [&]() __attribute__((always_inline)) {   // any wave, lane = env
+        const int e = lane;
+        const float pz3[4] = {pol_z[0][e].x, pol_z[1][e].x, pol_z[2][e].x, pol_z[3][e].x};
+        const float pz4[4] = {pol_z[0][e].y, pol_z[1][e].y, pol_z[2][e].y, pol_z[3][e].y};
+        sm.act_l[e] = mlp64::policy_finish_mean<PL>(wts, pz3, pz4);
+    };
+    // the action of step 0, from the reset observations
+    if (wave < 4) tile_part(wave, std::false_type{});
+    __syncthreads();
+    if (wave == 0 && lane < nloc) finish();
+    __syncthreads();
+    EvalIO io;
+    io.action = nullptr; io.past_override = nullptr; io.obs_out = nullptr; io.reward = nullptr; io.done = nullptr;
+    io.arrive = nullptr; io.ended = nullptr; io.ep_return = nullptr; io.ep_length = nullptr; io.ep_path_out = nullptr;
+    io.cnt_l = ep_cnt; io.quota = R.quota; io.rec_flags = R.ep_flags; io.rec_length = R.ep_length; io.rec_return = R.ep_return;
+    io.rec_path = R.ep_path;
+    int n_done = 0;   // env steps executed
+    for (int t = 0; t < R.T; ++t) {
+        asm volatile("" ::: "memory");   // keeps the weight reads of the policy phase inside the loop (registers are scarce)
+        // the policy of step t + 1 inside step t, behind barrier B2 (see rollout_kernel): waves 1-4 run the tile parts and the last
+        // of the four to arrive finishes, all before barrier C
+        const bool more = t + 1 < R.T;
+        auto hook = [&](const int wv, const int ln) __attribute__((always_inline)) {
+            if (more && wv >= 1 && wv <= 4) {
+                tile_part(wv - 1, std::true_type{});
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                unsigned old = 0u;
+                if (ln == 0) old = atomicAdd(&pol_cnt, 1u);
+                if (__builtin_amdgcn_readfirstlane(old) == 3u) {   // the last of the four
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+                    if (ln == 0) pol_cnt = 0u;
+                    if (ln < nloc) finish();
+                }
+            }
+        };
+        step_body<NB, EPB, SENS, true, NW, BOXES, 0, const Params&, const EvalIO&, decltype(hook)>(P, sm, next_env, io, false, 0, hook);
+        n_done = t + 1;
+        if (eval_quota_met<EPB>(ep_cnt, lane, R.quota)) break;   // behind barrier C: workgroup-uniform (see above)
+    }
+    if (tid < nloc) {
+        eval_store_state<NB, EPB, NW>(P, sm, tid, base + tid);
+        R.count[base + tid] = ep_cnt[tid];
+    }
+    if (tid == 0) R.steps[blockIdx.x] = n_done;
+}
+
+template <bool SENS>
+__global__ __launch_bounds__(64 * 8) void evaluate_resmlp_kernel(Params P, EvalArgs R) {
+    constexpr int NB = 10, EPB = 16, NW = 8, D = NB + 6, DP = D + 1, kThreads = 64 * NW;
+    static_assert(D == resmlp::rp::D && EPB == resmlp::kPolEnvs && NW == resmlp::kPolWaves, "the policy step's workgroup");
+    __shared__ StepSmem<NB, EPB, NW> sm;
+    __shared__ int next_env;
+    __shared__ __attribute__((aligned(16))) resmlp::PolicySmem ps;
+    __shared__ __attribute__((aligned(16))) resmlp::Block1Smem bs;   // block 1's weights + the small tail of the parameters
+    __shared__ int ep_cnt[EPB];       // episodes recorded per env
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int base = blockIdx.x * EPB;
+    const int nloc = min(EPB, P.N - base);
+    if (tid < nloc) eval_stage_state<NB, EPB, NW>(P, sm, tid, base + tid);
+    if (tid < EPB) ep_cnt[tid] = (tid < nloc) ? 0 : R.quota;
+    const bool half_rows = P.obs_f16 != 0;
+    for (int k = tid; k < nloc * D; k += kThreads)
+        sm.obs[(k / D) * DP + (k % D)] = half_rows ? __half2float(reinterpret_cast<const __half*>(R.obs0)[(size_t)base * D + k])
+                                                   : reinterpret_cast<const float*>(R.obs0)[(size_t)base * D + k];
+    for (int k = tid; k < 2 * NB; k += kThreads) sm.beam[k] = P.beam_cs[k];
+    for (int k = tid; k < (int)(sizeof(Rects) / 8); k += kThreads)
+        reinterpret_cast<uint64_t*>(&sm.rects)[k] = reinterpret_cast<const uint64_t*>(P.rects)[k];
+    const int l15 = lane & 15, q = lane >> 4;
+    const bool valid = l15 < nloc;
+    resmlp::Weights W;
+    resmlp::stage_block1(R.params, lane, wave, bs);
+    __syncthreads();
+    EvalIO io;
+    io.action = nullptr; io.past_override = nullptr; io.obs_out = nullptr; io.reward = nullptr; io.done = nullptr;
+    io.arrive = nullptr; io.ended = nullptr; io.ep_return = nullptr; io.ep_length = nullptr; io.ep_path_out = nullptr;
+    io.cnt_l = ep_cnt; io.quota = R.quota; io.rec_flags = R.ep_flags; io.rec_length = R.ep_length; io.rec_return = R.ep_return;
+    io.rec_path = R.ep_path;
+    int n_done = 0;   // env steps executed
+    for (int t = 0; t < R.T; ++t) {
+        // ---- the mean of PPO.get_action (ppo.py:673-697) on the observation tile the previous step (or the reset) left in LDS
+        resmlp::f32x4 xq = resmlp::zero4();
+        if (valid) {
+            const float* row = sm.obs + l15 * DP + 4 * q;
+            xq = resmlp::f32x4{row[0], row[1], row[2], row[3]};
+            if (half_rows) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) xq[j] = __half2float(__float2half_rn(xq[j]));
+            }
+        }
+        float z3, z4;
+        resmlp::load_weights_b(R.params, lane, wave, W);   // requested first: in flight while block 1 runs out of LDS
+        resmlp::load_weights_a_lds(bs, lane, wave, W);
+        resmlp::policy_preact_w(W, bs.b2a, bs.tail, xq, lane, wave, ps, z3, z4);
+        if (wave == 0 && q == 0 && valid) sm.act_l[l15] = resmlp::policy_finish_mean(bs.tail, z3, z4);
+        __syncthreads();
+        // ---- the env step
+        step_body<NB, EPB, SENS, true, NW, false, 0, const Params&, const EvalIO&>(P, sm, next_env, io, false, 0);
+        n_done = t + 1;    // (behind barrier C: the observation tile of step t + 1 is complete in sm.obs)
+        if (eval_quota_met<EPB>(ep_cnt, lane, R.quota)) break;   // workgroup-uniform (see above)
+    }
+    if (tid < nloc) {
+        eval_store_state<NB, EPB, NW>(P, sm, tid, base + tid);
+        R.count[base + tid] = ep_cnt[tid];
+    }
+    if (tid == 0) R.steps[blockIdx.x] = n_done;
 }
 
 // ---------------------------------------------------------------- n steps of an action tape in ONE launch (navsim_step_seq)
@@ -2748,6 +2983,74 @@ int navsim_rollout_resmlp512(navsim_t* h, const float* actor_params_dev, void* o
     const dim3 grid((h->P.N + 15) / 16), block(64 * 8);
     if (sens) hipLaunchKernelGGL(rollout_resmlp_kernel<true>, grid, block, 0, (hipStream_t)stream, h->P, R);
     else hipLaunchKernelGGL(rollout_resmlp_kernel<false>, grid, block, 0, (hipStream_t)stream, h->P, R);
+    HIP_TRY(hipGetLastError());
+    return NAVSIM_OK;
+}
+
+// what both evaluation entry points check before anything is launched; `beams_ok`: the policy has an instantiation for P.B
+static int eval_check(const navsim* h, const char* fn, const float* params, const void* obs0, int32_t quota, int32_t n_steps,
+                      const void* flags, const void* length, const void* ret, const void* path, const void* count, const void* steps,
+                      bool (*beams_ok)(int), const char* beams_msg) {
+    const std::string f = std::string(fn) + ": ";
+    if (!h) return fail(NAVSIM_E_ARG, f + "null handle");
+    if (!params || !obs0 || !flags || !length || !ret || !path || !count || !steps) return fail(NAVSIM_E_ARG, f + "null pointer");
+    if (quota < 1) return fail(NAVSIM_E_ARG, f + "quota must be at least 1");
+    if (n_steps < 1) return fail(NAVSIM_E_ARG, f + "n_steps must be at least 1");
+    if (!h->P.auto_reset) return fail(NAVSIM_E_ARG, f + "the handle needs auto_reset (an env plays its episodes back to back)");
+    if (h->P.max_ep_steps <= 0) return fail(NAVSIM_E_ARG, f + "max_episode_steps == 0: an episode could never end");
+    if (h->P.N > 16 * 256)
+        return fail(NAVSIM_E_ARG, f + "more than 4096 envs (only the 16-env workgroup shape has an evaluation form)");
+    if (!beams_ok(h->P.B)) return fail(NAVSIM_E_ARG, f + beams_msg);
+    if (((uintptr_t)params & 15) || ((uintptr_t)obs0 & 15)) return fail(NAVSIM_E_ARG, f + "params and obs0 must be 16-byte aligned");
+    if (((uintptr_t)length & 3) || ((uintptr_t)ret & 3) || ((uintptr_t)path & 3) || ((uintptr_t)count & 3) || ((uintptr_t)steps & 3))
+        return fail(NAVSIM_E_ARG, f + "ep_length, ep_return, ep_path, count and steps must be 4-byte aligned");
+    if (!h->has_map) return fail(NAVSIM_E_STATE, f + "call navsim_set_map first");
+    return NAVSIM_OK;
+}
+
+int navsim_evaluate_mlp64(navsim_t* h, const float* actor_params_dev, const void* obs0_dev, int32_t quota, int32_t n_steps,
+                          uint8_t* ep_flags_dev, int32_t* ep_length_dev, float* ep_return_dev, float* ep_path_dev,
+                          int32_t* count_dev, int32_t* steps_dev, void* stream) {
+    const int rc = eval_check(h, "navsim_evaluate_mlp64", actor_params_dev, obs0_dev, quota, n_steps, ep_flags_dev, ep_length_dev,
+                              ep_return_dev, ep_path_dev, count_dev, steps_dev, [](int b) { return b == 10 || b == 36; },
+                              "the (B + 6)-64-64 policy needs 10 or 36 beams");
+    if (rc != NAVSIM_OK) return rc;
+    const EvalArgs R = {actor_params_dev, obs0_dev, ep_flags_dev, ep_length_dev, ep_return_dev, ep_path_dev, count_dev, steps_dev,
+                        quota, n_steps};
+    const bool sens = h->P.sigma > 0.f || h->P.below_min_mode != 0;
+    const bool boxes = h->P.tile_box != nullptr;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((h->P.N + 15) / 16), block(64 * 8);
+#define NAVSIM_EVAL(NB_)                                                                                                \
+    do {                                                                                                                \
+        if (boxes) {                                                                                                    \
+            if (sens) hipLaunchKernelGGL((evaluate_kernel<NB_, true, true>), grid, block, 0, st, h->P, R);              \
+            else hipLaunchKernelGGL((evaluate_kernel<NB_, false, true>), grid, block, 0, st, h->P, R);                  \
+        } else {                                                                                                        \
+            if (sens) hipLaunchKernelGGL((evaluate_kernel<NB_, true, false>), grid, block, 0, st, h->P, R);             \
+            else hipLaunchKernelGGL((evaluate_kernel<NB_, false, false>), grid, block, 0, st, h->P, R);                 \
+        }                                                                                                               \
+    } while (0)
+    if (h->P.B == 36) NAVSIM_EVAL(36);
+    else NAVSIM_EVAL(10);
+#undef NAVSIM_EVAL
+    HIP_TRY(hipGetLastError());
+    return NAVSIM_OK;
+}
+
+int navsim_evaluate_resmlp512(navsim_t* h, const float* actor_params_dev, const void* obs0_dev, int32_t quota, int32_t n_steps,
+                              uint8_t* ep_flags_dev, int32_t* ep_length_dev, float* ep_return_dev, float* ep_path_dev,
+                              int32_t* count_dev, int32_t* steps_dev, void* stream) {
+    const int rc = eval_check(h, "navsim_evaluate_resmlp512", actor_params_dev, obs0_dev, quota, n_steps, ep_flags_dev,
+                              ep_length_dev, ep_return_dev, ep_path_dev, count_dev, steps_dev, [](int b) { return b == 10; },
+                              "the reference's nets read 16-wide observations (10 beams)");
+    if (rc != NAVSIM_OK) return rc;
+    const EvalArgs R = {actor_params_dev, obs0_dev, ep_flags_dev, ep_length_dev, ep_return_dev, ep_path_dev, count_dev, steps_dev,
+                        quota, n_steps};
+    const bool sens = h->P.sigma > 0.f || h->P.below_min_mode != 0;
+    const dim3 grid((h->P.N + 15) / 16), block(64 * 8);
+    if (sens) hipLaunchKernelGGL(evaluate_resmlp_kernel<true>, grid, block, 0, (hipStream_t)stream, h->P, R);
+    else hipLaunchKernelGGL(evaluate_resmlp_kernel<false>, grid, block, 0, (hipStream_t)stream, h->P, R);
     HIP_TRY(hipGetLastError());
     return NAVSIM_OK;
 }

@@ -222,4 +222,14 @@ __device__ __forceinline__ Action policy_finish(const float* __restrict__ tail, 
     return o;
 }
 
+// The evaluation action (main.py:197-199): the clamped mean, no noise and no log-prob; bit for bit policy_finish's action when
+// its noise is zero (`+ 0.f` is its fmaf(sd, 0, mu)).
+__device__ __forceinline__ float2 policy_finish_mean(const float* __restrict__ tail, float z3, float z4) {
+    z3 += tail[rp::BO1 - rp::B2B];
+    z4 += tail[rp::BO2 - rp::B2B];
+    const float mu0 = 1.0f / (1.0f + expf(-z3));
+    const float mu1 = tanhf(z4);
+    return make_float2(fminf(fmaxf(mu0 + 0.f, 0.f), 1.f), fminf(fmaxf(mu1 + 0.f, -1.f), 1.f));
+}
+
 }  // namespace resmlp

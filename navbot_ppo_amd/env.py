@@ -299,6 +299,10 @@ class VecEnv:
                  seed=0, env_id_base=0, per_env_map=False, map_seed=0, obs_f16=False, device=None, sampler=None,
                  lidar_below_min="clamp", lidar_noise_sigma=0.0, respawn_on_arrive=False, envs_per_workgroup=None, pair_cast=None):
         thr = 0.2 if is_training else 0.4  # environment_new.py:44-47
+        # what a sibling env on the same world is built from (PPOTrainer's evaluation env: same map / beams / row type / sensor)
+        self.world_args = dict(map=map, n_beams=n_beams, per_env_map=per_env_map, map_seed=map_seed, obs_f16=obs_f16,
+                               sampler=sampler, lidar_below_min=lidar_below_min, lidar_noise_sigma=lidar_noise_sigma,
+                               respawn_on_arrive=respawn_on_arrive)
         self.sim = NavSim(n_envs, n_beams=n_beams, max_episode_steps=max_episode_steps, auto_reset=auto_reset,
                           respawn_on_arrive=respawn_on_arrive, seed=seed, env_id_base=env_id_base, threshold_arrive=thr,
                           obs_f16=obs_f16, device=device, lidar_below_min=lidar_below_min,
@@ -390,6 +394,60 @@ class VecEnv:
                                              int(seed) & 0xFFFFFFFFFFFFFFFF, p(base_t), T,
                                              C.c_void_p(torch.cuda.current_stream().cuda_stream)), "navsim_rollout_mlp64")
             torch.cuda.current_stream().synchronize()   # var_t / base_t / prm may be temporaries of this call
+        return out
+
+    EVAL_POLICIES = {"mlp64x2": "navsim_evaluate_mlp64", "resmlp512": "navsim_evaluate_resmlp512"}
+
+    def evaluate_policy(self, actor_params, quota, n_steps=None, policy="mlp64x2", fill=0):
+        """The evaluation loop (main.py:135-252) in ONE launch (navsim_evaluate_mlp64 / navsim_evaluate_resmlp512): a fresh
+        reset, then every env plays whole episodes back to back with the DETERMINISTIC action (the clamped mean of the actor,
+        main.py:197-199) and records its first ``quota`` of them; a workgroup of 16 envs stops once all of its envs are done,
+        at the latest after ``n_steps`` steps (default quota * max_episode_steps: always enough, every episode ends by its
+        time-out).  actor_params: the flat float32 actor as for rollout_mlp64 (policy "mlp64x2") or the [50290] 512-wide one
+        ("resmlp512", 10 beams).  Returns a namespace: flags [quota, N] uint8 (1 success, 2 collision, 4 timeout), length
+        [quota, N] int32, ret / path [quota, N] float32, count [N] int32 (episodes recorded), steps [ceil(N / 16)] int32 (steps
+        each workgroup executed); slots that were not reached hold ``fill``.  The env state afterwards is unspecified (the envs
+        ran on past their quota): reset before stepping this env again."""
+        import ctypes as C
+        from ._native import check, lib
+        if policy not in self.EVAL_POLICIES:
+            raise ValueError(f"evaluate_policy: no evaluation kernel for policy {policy!r} (have {sorted(self.EVAL_POLICIES)})")
+        if policy == "resmlp512" and self.B != 10:
+            raise ValueError("evaluate_policy: the 512-wide actor reads 16-wide observations (10 beams): no evaluation kernel "
+                             f"for {self.B} beams")
+        if policy == "mlp64x2" and self.B not in (10, 36):
+            raise ValueError(f"evaluate_policy: the (B + 6)-64-64 actor has evaluation kernels for 10 and 36 beams, not {self.B}")
+        N, D, dev, sim = self.N, self.D, self.device, self.sim
+        quota = int(quota)
+        n_steps = quota * int(sim.cfg.max_episode_steps) if n_steps is None else int(n_steps)
+        n_actor = 50290 if policy == "resmlp512" else 64 * D + 64 + 64 * 64 + 64 + 2 * (64 + 1)
+        if not torch.is_tensor(actor_params):
+            raise NavsimError("evaluate_policy: actor_params: expected a tensor")
+        prm = actor_params.detach().to(device=dev, dtype=torch.float32).contiguous()
+        if prm.numel() < n_actor or prm.data_ptr() % 16:
+            raise NavsimError(f"evaluate_policy: actor_params: at least {n_actor} float32 values, 16-byte aligned")
+        q = max(quota, 1)   # (quota < 1 is refused by the library, with its message)
+        out = types.SimpleNamespace(
+            flags=torch.full((q, N), int(fill), dtype=torch.uint8, device=dev),
+            length=torch.full((q, N), int(fill), dtype=torch.int32, device=dev),
+            ret=torch.full((q, N), float(fill), dtype=torch.float32, device=dev),
+            path=torch.full((q, N), float(fill), dtype=torch.float32, device=dev),
+            count=torch.zeros(N, dtype=torch.int32, device=dev),
+            steps=torch.zeros((N + 15) // 16, dtype=torch.int32, device=dev))
+        obs0 = torch.empty((N, D), dtype=sim.obs_dtype, device=dev)
+        sim._chk("evaluate_policy: actor_params", prm, torch.float32, prm.numel())
+        sim._chk("evaluate_policy: flags", out.flags, torch.uint8, q * N)
+        sim._chk("evaluate_policy: length", out.length, torch.int32, q * N)
+        sim._chk("evaluate_policy: ret", out.ret, torch.float32, q * N)
+        sim._chk("evaluate_policy: path", out.path, torch.float32, q * N)
+        sim.reset(obs0)
+        p = lambda x: C.c_void_p(x.data_ptr())
+        with torch.cuda.device(dev):
+            check(getattr(lib(), self.EVAL_POLICIES[policy])(
+                sim._h, p(prm), p(obs0), quota, n_steps, p(out.flags), p(out.length), p(out.ret), p(out.path), p(out.count),
+                p(out.steps), C.c_void_p(torch.cuda.current_stream().cuda_stream)), self.EVAL_POLICIES[policy])
+            if prm.data_ptr() != actor_params.data_ptr():
+                torch.cuda.current_stream().synchronize()   # prm is a temporary of this call
         return out
 
 

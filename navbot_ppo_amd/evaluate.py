@@ -38,19 +38,59 @@ def load_actor(path, device):
     return actor.to(device).eval(), policy
 
 
+def persistent_policy(actor, n_beams=10):
+    """(policy name, flat float32 actor in the layout of include/navppo.h) for VecEnv.evaluate_policy; ValueError if the actor
+    or the beam count has no evaluation kernel -- ``evaluate(persistent=True)`` never falls back to the stepping loop."""
+    if isinstance(actor, nets.MLP64Actor):
+        policy, beams = "mlp64x2", (10, 36)
+    elif isinstance(actor, nets.ResMLPActor):
+        policy, beams = "resmlp512", (10,)
+    else:
+        raise ValueError(f"evaluate(persistent=True): no evaluation kernel for an actor of type {type(actor).__name__} "
+                         "(navsim_evaluate_mlp64 runs nets.MLP64Actor, navsim_evaluate_resmlp512 nets.ResMLPActor)")
+    in_dim = (actor.rb1.fc1.weight if policy == "resmlp512" else actor.layer1.weight).shape[1]
+    if n_beams not in beams or in_dim != n_beams + 6:
+        raise ValueError(f"evaluate(persistent=True): no evaluation kernel for policy {policy} with {in_dim}-wide observations on "
+                         f"{n_beams} beams (instantiated for {' / '.join(str(b) for b in beams)} beams)")
+    return policy, nets.flat_actor_params(actor)
+
+
 @torch.no_grad()
 def evaluate(actor, num_episodes=100, max_timesteps_per_episode=500, map="stage_1", n_parallel=None, seed=0, device=None,
-             output_dir="", method_name="baseline", log=print):
+             output_dir="", method_name="baseline", log=print, persistent=False, timing=None):
     """Every env plays a FIXED quota of q = ceil(num_episodes / n_parallel) whole episodes (its first q; later ones are
     ignored) and stepping continues until every env has met it, so which episodes are reported does not depend on how
     long they last -- taking "the first num_episodes to finish" would over-sample short episodes (early collisions) and
     under-report timeouts.  Rows are ordered episode-slot-major (slot 0 of every env, then slot 1, ...) and cut to
-    num_episodes.  Everything stays on the device; the host looks at a counter every 16 steps."""
+    num_episodes.  Everything stays on the device; the host looks at a counter every 16 steps.
+
+    persistent=True replaces the stepping loop by ONE launch (VecEnv.evaluate_policy: the HIP actor and the env step alternate
+    inside the kernel, the quota is kept on chip, a workgroup stops when its envs are done); rows, order, CSV, summary and log
+    line come from the same code.  The ``time`` column is then length x (wall clock / the most steps any workgroup ran).  An
+    actor or beam count without an evaluation kernel raises ValueError.  timing: a dict that receives ``seconds`` (wall clock
+    of the stepping alone) and ``steps`` (env steps behind it)."""
     n_par = int(n_parallel or min(num_episodes, 1024))
     quota = -(-int(num_episodes) // n_par)
+    if persistent:
+        policy, flat_actor = persistent_policy(actor)
     env = VecEnv(n_par, map=map, max_episode_steps=max_timesteps_per_episode, auto_reset=True, is_training=False, seed=seed,
                  device=device)
     dev = env.device
+    if persistent:
+        flat_actor = flat_actor.to(dev)
+        torch.cuda.synchronize(dev)
+        t0 = time.time()
+        tab = env.evaluate_policy(flat_actor, quota, policy=policy)
+        torch.cuda.synchronize(dev)
+        seconds = time.time() - t0
+        if int(tab.count.min()) < quota:
+            raise RuntimeError("evaluate(persistent=True): an env did not finish its quota of episodes")
+        steps = int(tab.steps.max())
+        env.close()
+        fl = tab.flags
+        res = torch.stack([(fl & 1).double(), ((fl >> 1) & 1).double(), ((fl >> 2) & 1).double(), tab.length.double(),
+                           tab.ret.double(), tab.path.double()], 2)
+        return _report(res, quota, n_par, num_episodes, seconds, steps, output_dir, method_name, log, timing)
     actor = actor.to(dev).eval()
     obs = env.reset()
     count = torch.zeros(n_par, dtype=torch.int64, device=dev)
@@ -76,8 +116,16 @@ def evaluate(actor, num_episodes=100, max_timesteps_per_episode=500, map="stage_
         if steps % 16 == 0 and bool((count >= quota).all()):
             break
     torch.cuda.synchronize(dev)
-    sec_per_step = (time.time() - t0) / max(steps, 1)
+    seconds = time.time() - t0
     env.close()
+    return _report(res, quota, n_par, num_episodes, seconds, steps, output_dir, method_name, log, timing)
+
+
+def _report(res, quota, n_par, num_episodes, seconds, steps, output_dir, method_name, log, timing):
+    """rows, CSV, summary and log line of evaluate() from the [quota, n_par, 6] episode table of either stepping path"""
+    sec_per_step = seconds / max(steps, 1)
+    if timing is not None:
+        timing.update(seconds=seconds, steps=steps)
     flat = res.reshape(quota * n_par, 6)[:num_episodes].cpu().numpy()
     rows = [[k, int(r[0]), int(r[1]), int(r[2]), int(r[3]), float(r[4]), float(r[5]), float(r[3]) * sec_per_step]
             for k, r in enumerate(flat)]

@@ -10,7 +10,8 @@ Same flag names and defaults; what they mean on the batched simulator:
   --max_timesteps         training budget, counted like the reference over COMPLETED episodes (ppo.py:258)
   --tiny_debug_run        20-step episodes / 40-step batches / 400 total steps (arguments.py:58-65)
   --use_external_sampler  start/goal from the curated GoalSpawnSampler tables (parsed but never wired in the reference)
-Additions (not in the reference): --n_envs, --policy, --map, --seed.  Vision flags are accepted and refused (the camera
+Additions (not in the reference): --n_envs, --policy, --map, --seed, --eval_persistent (with --eval: one launch instead of the
+stepping loop), --eval_every K (training: a persistent evaluation of --eval_episodes episodes every K iterations).  Vision flags are accepted and refused (the camera
 modality is outside the LiDAR hot path); --mode test maps to --eval (the reference's test path is broken).
 """
 import argparse
@@ -42,6 +43,11 @@ def get_args(argv=None):
     p.add_argument("--policy", type=str, default="resmlp512", choices=["resmlp512", "mlp64x2"])
     p.add_argument("--map", type=str, default="stage_1")
     p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--eval_persistent", action="store_true", default=False,
+                   help="--eval: the whole evaluation in ONE launch (HIP actor + env step on chip) instead of the stepping loop")
+    p.add_argument("--eval_every", type=int, default=0,
+                   help="training: every this many iterations, a persistent deterministic evaluation of --eval_episodes episodes "
+                        "(arrival threshold 0.4) on a second set of envs; 0 = off")
     args = p.parse_args(argv)
     if args.output_dir is None:
         args.output_dir = os.path.join(os.getcwd(), "runs")
@@ -80,7 +86,7 @@ def main(argv=None):
         print(f"Loading actor: {path}", flush=True)
         actor, _ = ev.load_actor(path, "cuda")
         s = ev.evaluate(actor, num_episodes=args.eval_episodes, max_timesteps_per_episode=args.timesteps_per_episode, map=args.map,
-                        seed=args.seed, output_dir=args.output_dir, method_name=args.method_name)
+                        seed=args.seed, output_dir=args.output_dir, method_name=args.method_name, persistent=args.eval_persistent)
         return 0 if s["episodes"] == args.eval_episodes else 1
 
     ctx = ppo.DistCtx()
@@ -99,7 +105,8 @@ def main(argv=None):
     env = VecEnv(hi - lo, map=args.map, max_episode_steps=args.timesteps_per_episode, auto_reset=True, is_training=True,
                  seed=args.seed, env_id_base=lo, device=ctx.device, sampler=sampler)
     cfg = ppo.PPOConfig(rollout_len=rollout, max_episode_steps=args.timesteps_per_episode, policy=args.policy, seed=args.seed,
-                        save_freq=args.save_every_iterations, output_dir=args.output_dir, method_name=args.method_name)
+                        save_freq=args.save_every_iterations, output_dir=args.output_dir, method_name=args.method_name,
+                        eval_every=args.eval_every, eval_episodes=args.eval_episodes)
     trainer = ppo.PPOTrainer(env, cfg, ctx)
     if args.resume or args.actor_model:  # main.py:52-89
         pa = args.actor_model or ev.find_latest_checkpoint(args.output_dir, args.method_name, "actor")

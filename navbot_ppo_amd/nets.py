@@ -153,3 +153,10 @@ def make_policy(name, obs_dim=16, act_dim=2):
         raise KeyError(f"unknown policy {name!r}; have {sorted(POLICIES)}")
     a, c = POLICIES[name]
     return a(obs_dim, act_dim), c(obs_dim, 1)
+
+
+def flat_actor_params(actor):
+    """The actor as one flat float32 tensor in the layout of include/navppo.h: nn.Module.named_parameters() order without the
+    BatchNorm entries the 512-wide nets' forward never uses."""
+    ps = [p for k, p in actor.named_parameters() if ".bn" not in "." + k and not k.startswith("bn")]
+    return torch.cat([p.detach().reshape(-1).float() for p in ps]).contiguous()

@@ -65,6 +65,11 @@ class PPOConfig:
     episode_csv_rows: int = 2000           # per-iteration cap on rows appended to <method>_train_episodes.csv (0 = off)
     tb_episode_rows: int = 256             # per-iteration cap on Episode_Rewards/train points in the TensorBoard file (0 = off)
     method_name: str = "baseline"
+    # periodic evaluation while training: every eval_every iterations (0 = off) one persistent launch (VecEnv.evaluate_policy)
+    # plays eval_episodes episodes with the DETERMINISTIC mean action at the evaluation arrival threshold 0.4 -- the success rate
+    # the reference's users quote (main.py:135-252), not that of the noisy training rollouts -- on a second set of envs
+    eval_every: int = 0
+    eval_episodes: int = 100
 
 
 # --------------------------------------------------------------------------- distributed context
@@ -764,6 +769,8 @@ class PPOTrainer:
                            rollout_time=t1 - t0, update_time=t2 - t1, iter_time=t2 - t0,
                            steps_per_sec=T * N * world / (t2 - t0),                      # ppo.py:855
                            rollout_steps_per_sec=T * N * world / (t1 - t0), var=self.var_host)
+        if cfg.eval_every > 0 and self.i_so_far % cfg.eval_every == 0 and (self.ctx is None or self.ctx.rank == 0):
+            self.logger.update(self.evaluate_now())   # rank 0 alone, no collective: the other ranks go on to their next rollout
         if cfg.output_dir and (self.ctx is None or self.ctx.rank == 0):
             if self.i_so_far % cfg.save_freq == 0:
                 self.save_checkpoint()
@@ -775,6 +782,71 @@ class PPOTrainer:
                 self.write_episode_csv(cfg.episode_csv_rows)
             self.write_tensorboard()
         return self.logger
+
+    # ---- periodic evaluation (PPOConfig.eval_every)
+    EVAL_HISTORY_HEADER = ["iteration", "timesteps", "episodes", "success_rate", "collision_rate", "timeout_rate", "mean_length",
+                           "mean_return", "mean_path_length"]
+
+    @property
+    def stats(self):
+        """the last iteration's figures (what iteration() returned)"""
+        return self.logger
+
+    def _make_eval_env(self):
+        from .env import VecEnv
+        w = dict(getattr(self.env, "world_args", None) or {})
+        if not w:
+            raise ValueError("PPOConfig.eval_every: the training env does not describe its world (VecEnv.world_args)")
+        if torch.is_tensor(w["map"]) and w["map"].dim() == 3:
+            raise ValueError("PPOConfig.eval_every: a per-env segment tensor cannot be reused for the evaluation envs; pass a map "
+                             "name or a shared [S, 4] map (per_env_map=True replicates it)")
+        n_par = min(int(self.cfg.eval_episodes), 1024)
+        if n_par < 1:
+            raise ValueError("PPOConfig.eval_episodes must be at least 1")
+        seed = (int(self.cfg.seed) * 1000003 + 7919) & 0xFFFFFFFF   # its own goal / spawn stream, derived from cfg.seed
+        return VecEnv(n_par, max_episode_steps=self.cfg.max_episode_steps, auto_reset=True, is_training=False, seed=seed,
+                      device=self.device, **w)
+
+    def evaluate_now(self):
+        """eval_episodes episodes of the current actor in ONE launch on the evaluation envs (created at the first call): the
+        deterministic mean action, arrival threshold 0.4, a fixed quota of whole episodes per env, rows cut slot-major to
+        eval_episodes as evaluate() does.  Reads the flat parameter buffer the update writes and nothing of the training env
+        (its state, RNG counters, the noise counter and the captured graph are untouched).  Returns the eval_* figures and
+        appends one row to <method>_eval_history.csv."""
+        cfg = self.cfg
+        if not (self.updater.fused_mlp64 or self.updater.fused_resmlp512):
+            raise ValueError(f"PPOConfig.eval_every: no evaluation kernel for policy {cfg.policy!r} on this update path "
+                             "(it needs the fused HIP update's flat parameter layout)")
+        if getattr(self, "_eval_env", None) is None:
+            self._eval_env = self._make_eval_env()
+        env = self._eval_env
+        n_ep = int(cfg.eval_episodes)
+        quota = -(-n_ep // env.N)
+        t0 = time.time()
+        tab = env.evaluate_policy(self.updater.fp.flat, quota, policy="resmlp512" if self.updater.fused_resmlp512 else "mlp64x2")
+        cut = lambda x: x.reshape(-1)[:n_ep]
+        fl = cut(tab.flags)
+        sums = torch.stack([(fl & 1).sum().double(), ((fl >> 1) & 1).sum().double(), ((fl >> 2) & 1).sum().double(),
+                            cut(tab.length).double().sum(), cut(tab.ret).double().sum(), cut(tab.path).double().sum(),
+                            tab.count.min().double(), tab.steps.max().double()]).cpu().numpy()   # the one host sync
+        if int(sums[6]) < quota:
+            raise RuntimeError("evaluate_now: an env did not finish its quota of episodes")
+        sums = [float(v) for v in sums]
+        out = dict(eval_episodes=n_ep, eval_success=sums[0] / n_ep, eval_collision=sums[1] / n_ep, eval_timeout=sums[2] / n_ep,
+                   eval_length=sums[3] / n_ep, eval_return=sums[4] / n_ep, eval_path_length=sums[5] / n_ep,
+                   eval_steps=int(sums[7]), eval_time=time.time() - t0)
+        if cfg.output_dir:
+            import csv
+            os.makedirs(self.log_dir(), exist_ok=True)
+            path = os.path.join(self.log_dir(), f"{cfg.method_name}_eval_history.csv")
+            new = not os.path.exists(path)
+            with open(path, "a", newline="") as f:
+                w = csv.writer(f)
+                if new:
+                    w.writerow(self.EVAL_HISTORY_HEADER)
+                w.writerow([self.i_so_far, self.t_so_far, n_ep, out["eval_success"], out["eval_collision"], out["eval_timeout"],
+                            out["eval_length"], out["eval_return"], out["eval_path_length"]])
+        return out
 
     # ---- logging surface of the reference: per-episode CSV (ppo.py:159-163,739-746) and the TensorBoard scalar names
     #      (ppo.py:892-939) written as one JSON object per iteration (tensorboardX is not a dependency here)
@@ -833,7 +905,10 @@ class PPOTrainer:
                 "ppo/entropy": 1.0 + LOG_2PI + math.log(max(var, 1e-30)),   # MultivariateNormal(mean, var I).entropy(), 2-D
                 "ppo/clip_frac": lg.get("clip_frac"), "ppo/actor_grad_norm": lg.get("actor_grad_norm"),
                 "ppo/critic_grad_norm": lg.get("critic_grad_norm"), "ppo/actor_param_delta": lg.get("actor_param_delta"),
-                "ppo/critic_param_delta": lg.get("critic_param_delta")}
+                "ppo/critic_param_delta": lg.get("critic_param_delta"),
+                **({"eval/success_rate": lg["eval_success"], "eval/collision_rate": lg["eval_collision"],
+                    "eval/timeout_rate": lg["eval_timeout"], "eval/mean_return": lg["eval_return"],
+                    "eval/mean_ep_length": lg["eval_length"], "time/eval": lg["eval_time"]} if "eval_success" in lg else {})}
 
     def tb_dir(self):
         return os.path.join(self.cfg.output_dir, self.cfg.method_name, "tb")   # ppo.py:66
@@ -881,7 +956,10 @@ class PPOTrainer:
                 log(f"[iter {lg['iteration']:4d}] t={lg['t_so_far']:>10d} mean_ep_rew={lg['avg_ep_rews']:8.2f} "
                     f"succ={lg['success_rate']:.3f} ep_len={lg['avg_ep_lens']:6.1f} a_loss={lg['actor_loss']:.4f} "
                     f"c_loss={lg['critic_loss']:.2f} kl={lg['approx_kl']:.4f} steps/s={lg['steps_per_sec']:.0f} "
-                    f"(rollout {lg['rollout_time']:.3f}s update {lg['update_time']:.3f}s)")
+                    f"(rollout {lg['rollout_time']:.3f}s update {lg['update_time']:.3f}s)"
+                    + (f" eval: succ={lg['eval_success']:.3f} coll={lg['eval_collision']:.3f} tmo={lg['eval_timeout']:.3f} "
+                       f"ret={lg['eval_return']:.2f} len={lg['eval_length']:.1f} ({lg['eval_time']:.3f}s)"
+                       if "eval_success" in lg else ""))
         return self.logger
 
     # ---- ppo.py:452-457 file naming; state_dict keys match the reference's nets for policy resmlp512
