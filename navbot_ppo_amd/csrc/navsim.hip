@@ -1449,9 +1449,130 @@ struct RolloutArgs {
     int T;
 };
 
+// ---- what the persistent kernels (rollout_kernel, rollout_resmlp_kernel, evaluate_kernel, evaluate_resmlp_kernel, steps_kernel,
+// rollout_big_kernel) do around step_body.  A workgroup owns envs base .. base + nloc - 1; PRef as in step_body.
+
+// The state of env i (local e) between HBM (Params) and LDS (sm.st_*): in before the first step, out after the last.
+template <int NB, int EPB, int NW, class PRef>
+__device__ __forceinline__ void load_state(PRef P, StepSmem<NB, EPB, NW>& sm, const int e, const int i) {
+    sm.st_d[0][e] = P.x[i]; sm.st_d[1][e] = P.y[i]; sm.st_d[2][e] = P.th[i]; sm.st_d[3][e] = P.gx[i]; sm.st_d[4][e] = P.gy[i];
+    sm.st_d[5][e] = P.past_dist[i]; sm.st_d[6][e] = P.ep_ret[i]; sm.st_d[7][e] = P.ep_path[i];
+    sm.st_pact[e] = P.past_action[i];
+    sm.st_step[e] = (uint32_t)P.ep_step[i];
+    sm.st_ctr[e] = P.rng_ctr[i];
+}
+template <int NB, int EPB, int NW>
+__device__ __forceinline__ void store_state(const Params& P, const StepSmem<NB, EPB, NW>& sm, const int e, const int i) {
+    P.x[i] = sm.st_d[0][e]; P.y[i] = sm.st_d[1][e]; P.th[i] = sm.st_d[2][e]; P.gx[i] = sm.st_d[3][e]; P.gy[i] = sm.st_d[4][e];
+    P.past_dist[i] = sm.st_d[5][e]; P.ep_ret[i] = sm.st_d[6][e]; P.ep_path[i] = sm.st_d[7][e];
+    P.past_action[i] = sm.st_pact[e];
+    P.ep_step[i] = (int32_t)sm.st_step[e];
+    P.rng_ctr[i] = sm.st_ctr[e];
+}
+
+// The workgroup's rows of an [N, B + 6] observation buffer (f32; f16 if half_rows) -> the observation tile sm.obs
+template <int NB, int EPB, int NW>
+__device__ __forceinline__ void load_obs_tile(StepSmem<NB, EPB, NW>& sm, const void* obs, const int base, const int nloc,
+                                              const bool half_rows) {
+    constexpr int D = NB + 6, DP = D + 1;
+    for (int k = threadIdx.x; k < nloc * D; k += 64 * NW)
+        sm.obs[(k / D) * DP + (k % D)] = half_rows ? __half2float(reinterpret_cast<const __half*>(obs)[(size_t)base * D + k])
+                                                   : reinterpret_cast<const float*>(obs)[(size_t)base * D + k];
+}
+
+// The beam table and the goal rejection rectangles -> LDS, once for all steps of the launch
+template <int NB, int EPB, int NW, class PRef>
+__device__ __forceinline__ void load_tables(PRef P, StepSmem<NB, EPB, NW>& sm) {
+    for (int k = threadIdx.x; k < 2 * NB; k += 64 * NW) sm.beam[k] = P.beam_cs[k];
+    for (int k = threadIdx.x; k < (int)(sizeof(Rects) / 8); k += 64 * NW)
+        reinterpret_cast<uint64_t*>(&sm.rects)[k] = reinterpret_cast<const uint64_t*>(P.rects)[k];
+}
+
+template <int KS>
+struct ObsRow {
+    float x[KS];
+};
+// The input of lane (env e, kk) of a 16-env mlp64 policy tile: obs[e][KS kk .. KS kk + KS - 1].  IN_STEP: inside a step, behind
+// barrier B2, the row the step will leave (next_obs_n), rounded as the f16 buffer holds it; else the row in sm.obs (policy_row).
+// An absent env (e >= nloc) feeds zeros.  (Returned by value: with the row as an output argument instead, rollout_kernel<10, 4 | 8,
+// false, 8> took 169 VGPRs, one SIMD occupancy step below the 167 of the row written out in the kernel.)
+template <int NB, int EPB, int NW, bool SENS, bool IN_STEP, class PRef>
+__device__ __forceinline__ ObsRow<mlp64::Layout<NB + 6>::KS> mlp64_obs_row(PRef P, const StepSmem<NB, EPB, NW>& sm, const int e,
+                                                                        const int kk, const int nloc, const bool half_rows,
+                                                                        const float sigma, const int below_min) {
+    using PL = mlp64::Layout<NB + 6>;
+    constexpr int KS = PL::KS, DP = NB + 7;
+    const bool valid = e < nloc;
+    ObsRow<KS> r;
+    float (&xs)[KS] = r.x;
+    if constexpr (IN_STEP) {
+        next_obs_n<NB, EPB, NW, SENS, KS, PRef>(P, sm, min(e, nloc - 1), KS * kk, sigma, below_min, xs);
+        if (half_rows) {
+#pragma unroll
+            for (int j = 0; j < KS; ++j) xs[j] = __half2float(__float2half_rn(xs[j]));
+        }
+    } else {
+        mlp64::policy_row<PL>(sm.obs + min(e, nloc - 1) * DP, kk, half_rows, xs);
+    }
+    if (!valid) {
+#pragma unroll
+        for (int j = 0; j < KS; ++j) xs[j] = 0.f;
+    }
+    return r;
+}
+
+// Each of K waves calls this once its part of a phase is in LDS; the wave that arrives last resets the counter for the next phase
+// and runs finish(): an LDS counter -- a wave's LDS operations are performed in order, so the one that reads K - 1 sees what the
+// other waves wrote.
+template <unsigned K, class Finish>
+__device__ __forceinline__ void last_arrival(unsigned& cnt, const int lane, Finish finish) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    unsigned old = 0u;
+    if (lane == 0) old = atomicAdd(&cnt, 1u);
+    if (__builtin_amdgcn_readfirstlane(old) == K - 1) {
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        if (lane == 0) cnt = 0u;
+        finish();
+    }
+}
+
+// The resmlp512 policy step (resmlp_policy.h) on the observation tile in LDS, all eight waves, up to the pre-activations z3, z4 of
+// the two output units (valid on wave 0: lane (env lane & 15, q = 0)).  Lane (env l15, q) feeds obs[l15][4 q .. 4 q + 3].
+template <int NB, int EPB, int NW>
+__device__ __forceinline__ void resmlp_preact(const float* params, const StepSmem<NB, EPB, NW>& sm, const resmlp::Block1Smem& bs,
+                                              resmlp::PolicySmem& ps, const int lane, const int wave, const int nloc,
+                                              const bool half_rows, float& z3, float& z4) {
+    constexpr int DP = NB + 7;
+    const int l15 = lane & 15, q = lane >> 4;
+    resmlp::f32x4 xq = resmlp::zero4();
+    if (l15 < nloc) {
+        const float* row = sm.obs + l15 * DP + 4 * q;
+        xq = resmlp::f32x4{row[0], row[1], row[2], row[3]};
+        if (half_rows) {   // (the tile in LDS is float32; the row in the buffer -- what navppo_resmlp512_act would read -- is its rounding to half)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) xq[j] = __half2float(__float2half_rn(xq[j]));
+        }
+    }
+    resmlp::Weights W;
+    resmlp::load_weights_b(params, lane, wave, W);   // requested first: in flight while block 1 runs out of LDS
+    resmlp::load_weights_a_lds(bs, lane, wave, W);
+    resmlp::policy_preact_w(W, bs.b2a, bs.tail, xq, lane, wave, ps, z3, z4);
+}
+
+// The I/O of rollout step t (tn = t N): row t + 1 of the [T + 1, N, D] observation buffer (f16 if half_rows), row t of the [T, N]
+// buffers (the statistics nullable).  rollout_big_kernel takes the one of step 0 and reaches row t through step_body's row0.
+__host__ __device__ __forceinline__ StepIO rollout_io(const RolloutArgs& R, const size_t N, const size_t D, const size_t tn,
+                                                      const bool half_rows) {
+    void* const obs_row = half_rows ? (void*)(reinterpret_cast<__half*>(R.obs_buf) + (tn + N) * D)
+                                    : (void*)(reinterpret_cast<float*>(R.obs_buf) + (tn + N) * D);
+    return StepIO{nullptr, nullptr, obs_row, R.reward + tn, R.done + tn, R.arrive + tn, R.ended + tn,
+                  R.ep_return ? R.ep_return + tn : nullptr, R.ep_length ? R.ep_length + tn : nullptr,
+                  R.ep_path ? R.ep_path + tn : nullptr};
+}
+
 template <int NB, int EPB, bool SENS, int NW, bool BOXES = false>
 __global__ __launch_bounds__(64 * NW) void rollout_kernel(Params P, RolloutArgs R) {
-    constexpr int D = NB + 6, DP = D + 1, kThreads = 64 * NW;
+    constexpr int D = NB + 6, kThreads = 64 * NW;
     using PL = mlp64::Layout<D>;   // the (B + 6)-64-64 policy: 16-wide rows with 10 beams, 42-wide with 36
     constexpr int KS = PL::KS;
     __shared__ StepSmem<NB, EPB, NW> sm;
@@ -1466,21 +1587,10 @@ __global__ __launch_bounds__(64 * NW) void rollout_kernel(Params P, RolloutArgs 
     const int nloc = min(EPB, P.N - base);
     const size_t N = (size_t)P.N;
     for (int k = tid; k < PL::P_ACTOR; k += kThreads) wts[k] = R.params[k];
-    if (tid < nloc) {   // the envs' state: HBM -> LDS for the whole rollout
-        const int e = tid, i = base + e;
-        sm.st_d[0][e] = P.x[i]; sm.st_d[1][e] = P.y[i]; sm.st_d[2][e] = P.th[i]; sm.st_d[3][e] = P.gx[i]; sm.st_d[4][e] = P.gy[i];
-        sm.st_d[5][e] = P.past_dist[i]; sm.st_d[6][e] = P.ep_ret[i]; sm.st_d[7][e] = P.ep_path[i];
-        sm.st_pact[e] = P.past_action[i];
-        sm.st_step[e] = (uint32_t)P.ep_step[i];
-        sm.st_ctr[e] = P.rng_ctr[i];
-    }
+    if (tid < nloc) load_state<NB, EPB, NW, const Params&>(P, sm, tid, base + tid);   // the envs' state for the whole rollout
     const bool half_rows = P.obs_f16 != 0;   // float16 observation buffers: the policy reads what a reader of the buffers would
-    for (int k = tid; k < nloc * D; k += kThreads)
-        sm.obs[(k / D) * DP + (k % D)] = half_rows ? __half2float(reinterpret_cast<const __half*>(R.obs_buf)[(size_t)base * D + k])
-                                                   : reinterpret_cast<const float*>(R.obs_buf)[(size_t)base * D + k];
-    for (int k = tid; k < 2 * NB; k += kThreads) sm.beam[k] = P.beam_cs[k];
-    for (int k = tid; k < (int)(sizeof(Rects) / 8); k += kThreads)   // the goal rejection rectangles, for all T steps
-        reinterpret_cast<uint64_t*>(&sm.rects)[k] = reinterpret_cast<const uint64_t*>(P.rects)[k];
+    load_obs_tile<NB, EPB, NW>(sm, R.obs_buf, base, nloc, half_rows);
+    load_tables<NB, EPB, NW, const Params&>(P, sm);
     const uint32_t step0 = R.step_base ? *R.step_base : 0u;
     const float var = *R.var_ptr;
     if (tid == 0) pol_cnt = 0u;
@@ -1491,22 +1601,10 @@ __global__ __launch_bounds__(64 * NW) void rollout_kernel(Params P, RolloutArgs 
     const float sigma = SENS ? P.sigma : 0.f;
     const int below_min = SENS ? P.below_min_mode : 0;
     auto tile_part = [&](const int t2, auto in_step) __attribute__((always_inline)) {
-        const int e = lane & 15, kk = lane >> 4;   // lane (env, kk) feeds obs[env][KS kk .. KS kk + KS - 1]
-        const bool valid = e < nloc;
-        float xs[KS];
-        if constexpr (decltype(in_step)::value) {   // inside a step, behind barrier B2: the rows the step will leave
-            next_obs_n<NB, EPB, NW, SENS, KS, const Params&>(P, sm, min(e, nloc - 1), KS * kk, sigma, below_min, xs);
-            if (half_rows) {
-#pragma unroll
-                for (int j = 0; j < KS; ++j) xs[j] = __half2float(__float2half_rn(xs[j]));
-            }
-        } else {
-            mlp64::policy_row<PL>(sm.obs + min(e, nloc - 1) * DP, kk, half_rows, xs);
-        }
-        if (!valid) {
-#pragma unroll
-            for (int j = 0; j < KS; ++j) xs[j] = 0.f;
-        }
+        const int e = lane & 15, kk = lane >> 4;
+        const auto row = mlp64_obs_row<NB, EPB, NW, SENS, decltype(in_step)::value, const Params&>(P, sm, e, kk, nloc, half_rows,
+                                                                                                 sigma, below_min);
+        const float (&xs)[KS] = row.x;
         mlp64::f32x4 c1[4];
         mlp64::policy_hidden1<PL>(wts, xs, lane, c1);
         float pz3, pz4;
@@ -1538,16 +1636,11 @@ __global__ __launch_bounds__(64 * NW) void rollout_kernel(Params P, RolloutArgs 
     for (int t = 0; t < R.T; ++t) {
         const size_t tn = (size_t)t * N;
         asm volatile("" ::: "memory");   // keeps the weight reads of the policy phase inside the loop (registers are scarce)
-        void* const obs_row = half_rows ? (void*)(reinterpret_cast<__half*>(R.obs_buf) + (tn + N) * D)
-                                        : (void*)(reinterpret_cast<float*>(R.obs_buf) + (tn + N) * D);
-        const StepIO io = {nullptr, nullptr, obs_row, R.reward + tn, R.done + tn, R.arrive + tn, R.ended + tn,
-                           R.ep_return ? R.ep_return + tn : nullptr, R.ep_length ? R.ep_length + tn : nullptr,
-                           R.ep_path ? R.ep_path + tn : nullptr};
+        const StepIO io = rollout_io(R, N, D, tn, half_rows);
         // The policy of step t + 1 runs INSIDE step t, behind barrier B2.  Wave 0 works through the rules there (a float64 latency
         // chain, 0.85 us) and every other wave would only wait for it at barrier C; instead waves 1-4 run the tile parts, wave 5
-        // draws the noise, and whichever of the five arrives last (an LDS counter: a wave's LDS operations are performed in order,
-        // so the one that reads 4 sees what the other four wrote) finishes and publishes the action -- all before barrier C,
-        // so the next step starts right behind this one.  What the rules still have to decide about the observation tile --
+        // draws the noise, and whichever of the five arrives last (last_arrival) finishes and publishes the action -- all before
+        // barrier C, so the next step starts right behind this one.  What the rules still have to decide about the observation tile --
         // whether an env's row is replaced by its reset observation -- the tile waves work out themselves from the values that
         // are final at B2 (next_obs_n), so they read exactly the rows the step leaves: same device functions on the same inputs,
         // the buffers keep their bits.  Round 3 ran the phase between the steps with the whole workgroup waiting (5.2 us per
@@ -1559,14 +1652,9 @@ __global__ __launch_bounds__(64 * NW) void rollout_kernel(Params P, RolloutArgs 
             if (more && wv >= 1 && wv <= 5) {
                 if (wv <= 4) tile_part(wv - 1, std::true_type{});
                 else if (ln < nloc) draw_noise(step0 + (uint32_t)(t + 1));
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                unsigned old = 0u;
-                if (ln == 0) old = atomicAdd(&pol_cnt, 1u);
-                if (__builtin_amdgcn_readfirstlane(old) == 4u) {   // the last of the five
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-                    if (ln == 0) pol_cnt = 0u;
+                last_arrival<5>(pol_cnt, ln, [&]() __attribute__((always_inline)) {
                     if (ln < nloc) finish(tn + N);
-                }
+                });
             }
         };
         step_body<NB, EPB, SENS, true, NW, BOXES, 0, const Params&, const StepIO&, decltype(hook)>(P, sm, next_env, io,
@@ -1595,7 +1683,7 @@ __global__ __launch_bounds__(64 * NW) void rollout_kernel(Params P, RolloutArgs 
 // both blocks on one CU is 2.6), sum + finish 1.3, env step 4.0.
 template <bool SENS>
 __global__ __launch_bounds__(64 * 8) void rollout_resmlp_kernel(Params P, RolloutArgs R) {
-    constexpr int NB = 10, EPB = 16, NW = 8, D = NB + 6, DP = D + 1, kThreads = 64 * NW;
+    constexpr int NB = 10, EPB = 16, NW = 8, D = NB + 6;
     static_assert(D == resmlp::rp::D && EPB == resmlp::kPolEnvs && NW == resmlp::kPolWaves, "the policy step's workgroup");
     __shared__ StepSmem<NB, EPB, NW> sm;
     __shared__ int next_env;
@@ -1606,21 +1694,10 @@ __global__ __launch_bounds__(64 * 8) void rollout_resmlp_kernel(Params P, Rollou
     const int base = blockIdx.x * EPB;
     const int nloc = min(EPB, P.N - base);
     const size_t N = (size_t)P.N;
-    if (tid < nloc) {   // the envs' state: HBM -> LDS for the whole rollout
-        const int e = tid, i = base + e;
-        sm.st_d[0][e] = P.x[i]; sm.st_d[1][e] = P.y[i]; sm.st_d[2][e] = P.th[i]; sm.st_d[3][e] = P.gx[i]; sm.st_d[4][e] = P.gy[i];
-        sm.st_d[5][e] = P.past_dist[i]; sm.st_d[6][e] = P.ep_ret[i]; sm.st_d[7][e] = P.ep_path[i];
-        sm.st_pact[e] = P.past_action[i];
-        sm.st_step[e] = (uint32_t)P.ep_step[i];
-        sm.st_ctr[e] = P.rng_ctr[i];
-    }
+    if (tid < nloc) load_state<NB, EPB, NW, const Params&>(P, sm, tid, base + tid);   // the envs' state for the whole rollout
     const bool half_rows = P.obs_f16 != 0;   // float16 observation buffers (BASELINE configs[4]): the policy reads what a reader of the buffers would
-    for (int k = tid; k < nloc * D; k += kThreads)
-        sm.obs[(k / D) * DP + (k % D)] = half_rows ? __half2float(reinterpret_cast<const __half*>(R.obs_buf)[(size_t)base * D + k])
-                                                   : reinterpret_cast<const float*>(R.obs_buf)[(size_t)base * D + k];
-    for (int k = tid; k < 2 * NB; k += kThreads) sm.beam[k] = P.beam_cs[k];
-    for (int k = tid; k < (int)(sizeof(Rects) / 8); k += kThreads)
-        reinterpret_cast<uint64_t*>(&sm.rects)[k] = reinterpret_cast<const uint64_t*>(P.rects)[k];
+    load_obs_tile<NB, EPB, NW>(sm, R.obs_buf, base, nloc, half_rows);
+    load_tables<NB, EPB, NW, const Params&>(P, sm);
     const uint32_t step0 = R.step_base ? *R.step_base : 0u;
     const float var = *R.var_ptr;
     const int l15 = lane & 15, q = lane >> 4;
@@ -1633,26 +1710,14 @@ __global__ __launch_bounds__(64 * 8) void rollout_resmlp_kernel(Params P, Rollou
     // The weights of a policy step (this wave's 64 hidden units: 128 registers) are REQUESTED inside the env step in front of it --
     // behind barrier B2, where every wave but wave 0 only waits for the rules -- and arrive during the step's tail: the L2 round
     // trip of 197 KB per workgroup and step is off the critical path.  (They cannot simply stay in registers: the step body needs them.)
-    resmlp::Weights W;
     resmlp::stage_block1(R.params, lane, wave, bs);
     if (wave == 5 && lane < nloc) draw_noise(step0);
     __syncthreads();
     for (int t = 0; t < R.T; ++t) {
         const size_t tn = (size_t)t * N;
         // ---- PPO.get_action (ppo.py:673-706) on the observation tile the previous step (or the reset) left in LDS
-        resmlp::f32x4 xq = resmlp::zero4();
-        if (valid) {
-            const float* row = sm.obs + l15 * DP + 4 * q;
-            xq = resmlp::f32x4{row[0], row[1], row[2], row[3]};
-            if (half_rows) {   // (the tile in LDS is float32; the row in the buffer -- what navppo_resmlp512_act would read -- is its rounding to half)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) xq[j] = __half2float(__float2half_rn(xq[j]));
-            }
-        }
         float z3, z4;
-        resmlp::load_weights_b(R.params, lane, wave, W);   // requested first: in flight while block 1 runs out of LDS
-        resmlp::load_weights_a_lds(bs, lane, wave, W);
-        resmlp::policy_preact_w(W, bs.b2a, bs.tail, xq, lane, wave, ps, z3, z4);
+        resmlp_preact<NB, EPB, NW>(R.params, sm, bs, ps, lane, wave, nloc, half_rows, z3, z4);
         if (wave == 0 && q == 0 && valid) {
             const float2 eps = pol_eps[l15];
             const resmlp::Action o = resmlp::policy_finish(bs.tail, z3, z4, var, eps.x, eps.y);
@@ -1663,11 +1728,7 @@ __global__ __launch_bounds__(64 * 8) void rollout_resmlp_kernel(Params P, Rollou
         __syncthreads();
         // ---- the env step: the same step body as every other entry point; behind its barrier B2 the next policy step's weights are
         // requested and its noise is drawn
-        void* const obs_row = half_rows ? (void*)(reinterpret_cast<__half*>(R.obs_buf) + (tn + N) * D)
-                                        : (void*)(reinterpret_cast<float*>(R.obs_buf) + (tn + N) * D);
-        const StepIO io = {nullptr, nullptr, obs_row, R.reward + tn, R.done + tn, R.arrive + tn,
-                           R.ended + tn, R.ep_return ? R.ep_return + tn : nullptr, R.ep_length ? R.ep_length + tn : nullptr,
-                           R.ep_path ? R.ep_path + tn : nullptr};
+        const StepIO io = rollout_io(R, N, D, tn, half_rows);
         const bool more = t + 1 < R.T;
         auto hook = [&](const int wv, const int ln) __attribute__((always_inline)) {
             if (more) {
@@ -1705,22 +1766,9 @@ struct EvalArgs {
     int T;
 };
 
-// what both kernels do around their step loops (tid < nloc: the env's lane)
-template <int NB, int EPB, int NW>
-__device__ __forceinline__ void eval_stage_state(const Params& P, StepSmem<NB, EPB, NW>& sm, const int e, const int i) {
-    sm.st_d[0][e] = P.x[i]; sm.st_d[1][e] = P.y[i]; sm.st_d[2][e] = P.th[i]; sm.st_d[3][e] = P.gx[i]; sm.st_d[4][e] = P.gy[i];
-    sm.st_d[5][e] = P.past_dist[i]; sm.st_d[6][e] = P.ep_ret[i]; sm.st_d[7][e] = P.ep_path[i];
-    sm.st_pact[e] = P.past_action[i];
-    sm.st_step[e] = (uint32_t)P.ep_step[i];
-    sm.st_ctr[e] = P.rng_ctr[i];
-}
-template <int NB, int EPB, int NW>
-__device__ __forceinline__ void eval_store_state(const Params& P, const StepSmem<NB, EPB, NW>& sm, const int e, const int i) {
-    P.x[i] = sm.st_d[0][e]; P.y[i] = sm.st_d[1][e]; P.th[i] = sm.st_d[2][e]; P.gx[i] = sm.st_d[3][e]; P.gy[i] = sm.st_d[4][e];
-    P.past_dist[i] = sm.st_d[5][e]; P.ep_ret[i] = sm.st_d[6][e]; P.ep_path[i] = sm.st_d[7][e];
-    P.past_action[i] = sm.st_pact[e];
-    P.ep_step[i] = (int32_t)sm.st_step[e];
-    P.rng_ctr[i] = sm.st_ctr[e];
+// the episode table of a launch, counted in cnt_l (LDS)
+__device__ __forceinline__ EvalIO eval_io(const EvalArgs& R, int* cnt_l) {
+    return EvalIO{StepIO{}, cnt_l, R.quota, R.ep_flags, R.ep_length, R.ep_return, R.ep_path};
 }
 // behind a barrier that follows the rules lanes' count updates: true on every wave of the workgroup, or on none
 template <int EPB>
@@ -1730,7 +1778,7 @@ __device__ __forceinline__ bool eval_quota_met(const int* ep_cnt, const int lane
 
 template <int NB, bool SENS, bool BOXES>
 __global__ __launch_bounds__(64 * 8) void evaluate_kernel(Params P, EvalArgs R) {
-    constexpr int EPB = 16, NW = 8, D = NB + 6, DP = D + 1, kThreads = 64 * NW;
+    constexpr int EPB = 16, NW = 8, D = NB + 6, kThreads = 64 * NW;
     using PL = mlp64::Layout<D>;
     constexpr int KS = PL::KS;
     __shared__ StepSmem<NB, EPB, NW> sm;
@@ -1743,36 +1791,20 @@ __global__ __launch_bounds__(64 * 8) void evaluate_kernel(Params P, EvalArgs R) 
     const int base = blockIdx.x * EPB;
     const int nloc = min(EPB, P.N - base);
     for (int k = tid; k < PL::P_ACTOR; k += kThreads) wts[k] = R.params[k];
-    if (tid < nloc) eval_stage_state<NB, EPB, NW>(P, sm, tid, base + tid);
+    if (tid < nloc) load_state<NB, EPB, NW, const Params&>(P, sm, tid, base + tid);
     if (tid < EPB) ep_cnt[tid] = (tid < nloc) ? 0 : R.quota;
     const bool half_rows = P.obs_f16 != 0;
-    for (int k = tid; k < nloc * D; k += kThreads)
-        sm.obs[(k / D) * DP + (k % D)] = half_rows ? __half2float(reinterpret_cast<const __half*>(R.obs0)[(size_t)base * D + k])
-                                                   : reinterpret_cast<const float*>(R.obs0)[(size_t)base * D + k];
-    for (int k = tid; k < 2 * NB; k += kThreads) sm.beam[k] = P.beam_cs[k];
-    for (int k = tid; k < (int)(sizeof(Rects) / 8); k += kThreads)
-        reinterpret_cast<uint64_t*>(&sm.rects)[k] = reinterpret_cast<const uint64_t*>(P.rects)[k];
+    load_obs_tile<NB, EPB, NW>(sm, R.obs0, base, nloc, half_rows);
+    load_tables<NB, EPB, NW, const Params&>(P, sm);
     if (tid == 0) pol_cnt = 0u;
     __syncthreads();
     const float sigma = SENS ? P.sigma : 0.f;
     const int below_min = SENS ? P.below_min_mode : 0;
     auto tile_part = [&](const int t2, auto in_step) __attribute__((always_inline)) {   // as in rollout_kernel
         const int e = lane & 15, kk = lane >> 4;
-        const bool valid = e < nloc;
-        float xs[KS];
-        if constexpr (decltype(in_step)::value) {
-            next_obs_n<NB, EPB, NW, SENS, KS, const Params&>(P, sm, min(e, nloc - 1), KS * kk, sigma, below_min, xs);
-            if (half_rows) {
-#pragma unroll
-                for (int j = 0; j < KS; ++j) xs[j] = __half2float(__float2half_rn(xs[j]));
-            }
-        } else {
-            mlp64::policy_row<PL>(sm.obs + min(e, nloc - 1) * DP, kk, half_rows, xs);
-        }
-        if (!valid) {
-#pragma unroll
-            for (int j = 0; j < KS; ++j) xs[j] = 0.f;
-        }
+        const auto row = mlp64_obs_row<NB, EPB, NW, SENS, decltype(in_step)::value, const Params&>(P, sm, e, kk, nloc, half_rows,
+                                                                                                 sigma, below_min);
+        const float (&xs)[KS] = row.x;
         mlp64::f32x4 c1[4];
         mlp64::policy_hidden1<PL>(wts, xs, lane, c1);
         float pz3, pz4;
@@ -1790,11 +1822,7 @@ __global__ __launch_bounds__(64 * 8) void evaluate_kernel(Params P, EvalArgs R) 
     __syncthreads();
     if (wave == 0 && lane < nloc) finish();
     __syncthreads();
-    EvalIO io;
-    io.action = nullptr; io.past_override = nullptr; io.obs_out = nullptr; io.reward = nullptr; io.done = nullptr;
-    io.arrive = nullptr; io.ended = nullptr; io.ep_return = nullptr; io.ep_length = nullptr; io.ep_path_out = nullptr;
-    io.cnt_l = ep_cnt; io.quota = R.quota; io.rec_flags = R.ep_flags; io.rec_length = R.ep_length; io.rec_return = R.ep_return;
-    io.rec_path = R.ep_path;
+    const EvalIO io = eval_io(R, ep_cnt);
     int n_done = 0;   // env steps executed
     for (int t = 0; t < R.T; ++t) {
         asm volatile("" ::: "memory");   // keeps the weight reads of the policy phase inside the loop (registers are scarce)
@@ -1804,14 +1832,9 @@ __global__ __launch_bounds__(64 * 8) void evaluate_kernel(Params P, EvalArgs R) 
         auto hook = [&](const int wv, const int ln) __attribute__((always_inline)) {
             if (more && wv >= 1 && wv <= 4) {
                 tile_part(wv - 1, std::true_type{});
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                unsigned old = 0u;
-                if (ln == 0) old = atomicAdd(&pol_cnt, 1u);
-                if (__builtin_amdgcn_readfirstlane(old) == 3u) {   // the last of the four
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-                    if (ln == 0) pol_cnt = 0u;
+                last_arrival<4>(pol_cnt, ln, [&]() __attribute__((always_inline)) {
                     if (ln < nloc) finish();
-                }
+                });
             }
         };
         step_body<NB, EPB, SENS, true, NW, BOXES, 0, const Params&, const EvalIO&, decltype(hook)>(P, sm, next_env, io, false, 0, hook);
@@ -1819,12 +1842,15 @@ __global__ __launch_bounds__(64 * 8) void evaluate_kernel(Params P, EvalArgs R) 
         if (eval_quota_met<EPB>(ep_cnt, lane, R.quota)) break;   // behind barrier C: workgroup-uniform (see above)
     }
     if (tid < nloc) {
-        eval_store_state<NB, EPB, NW>(P, sm, tid, base + tid);
+        store_state<NB, EPB, NW>(P, sm, tid, base + tid);
         R.count[base + tid] = ep_cnt[tid];
     }
     if (tid == 0) R.steps[blockIdx.x] = n_done;
 }
 
+// (evaluate_resmlp_kernel keeps the parent commit's form of the staging, the policy phase and the EvalIO set-up: through
+// load_obs_tile / load_tables / resmlp_preact / eval_io it took 5.503 instead of 5.482-5.498 ms per launch, profiles/
+// persistent_refactor_ab.txt)
 template <bool SENS>
 __global__ __launch_bounds__(64 * 8) void evaluate_resmlp_kernel(Params P, EvalArgs R) {
     constexpr int NB = 10, EPB = 16, NW = 8, D = NB + 6, DP = D + 1, kThreads = 64 * NW;
@@ -1837,7 +1863,7 @@ __global__ __launch_bounds__(64 * 8) void evaluate_resmlp_kernel(Params P, EvalA
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int base = blockIdx.x * EPB;
     const int nloc = min(EPB, P.N - base);
-    if (tid < nloc) eval_stage_state<NB, EPB, NW>(P, sm, tid, base + tid);
+    if (tid < nloc) load_state<NB, EPB, NW, const Params&>(P, sm, tid, base + tid);
     if (tid < EPB) ep_cnt[tid] = (tid < nloc) ? 0 : R.quota;
     const bool half_rows = P.obs_f16 != 0;
     for (int k = tid; k < nloc * D; k += kThreads)
@@ -1880,7 +1906,7 @@ __global__ __launch_bounds__(64 * 8) void evaluate_resmlp_kernel(Params P, EvalA
         if (eval_quota_met<EPB>(ep_cnt, lane, R.quota)) break;   // workgroup-uniform (see above)
     }
     if (tid < nloc) {
-        eval_store_state<NB, EPB, NW>(P, sm, tid, base + tid);
+        store_state<NB, EPB, NW>(P, sm, tid, base + tid);
         R.count[base + tid] = ep_cnt[tid];
     }
     if (tid == 0) R.steps[blockIdx.x] = n_done;
@@ -1916,7 +1942,8 @@ __global__ __launch_bounds__(64 * NW, min_waves_per_simd(NB, EPB, NW, PAIR, true
     // parameters through the kernarg segment pointer, as in step_kernel (scalar loads at each use, no spilled SGPRs)
     SeqKArgsPtr A = (SeqKArgsPtr)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(A));
-    const Params __attribute__((address_space(4)))& P = A->P;
+    using PRef = const Params __attribute__((address_space(4)))&;
+    PRef P = A->P;
     const SeqArgs __attribute__((address_space(4)))& R = A->R;
     const int tid = threadIdx.x;
     const int base = blockIdx.x * EPB;
@@ -1926,15 +1953,9 @@ __global__ __launch_bounds__(64 * NW, min_waves_per_simd(NB, EPB, NW, PAIR, true
     if (tid < nloc) {   // the envs' state: HBM -> LDS for the whole tape; the first action
         const int e = tid, i = base + e;
         a_next = R.io.action[i];
-        sm.st_d[0][e] = P.x[i]; sm.st_d[1][e] = P.y[i]; sm.st_d[2][e] = P.th[i]; sm.st_d[3][e] = P.gx[i]; sm.st_d[4][e] = P.gy[i];
-        sm.st_d[5][e] = P.past_dist[i]; sm.st_d[6][e] = P.ep_ret[i]; sm.st_d[7][e] = P.ep_path[i];
-        sm.st_pact[e] = P.past_action[i];
-        sm.st_step[e] = (uint32_t)P.ep_step[i];
-        sm.st_ctr[e] = P.rng_ctr[i];
+        load_state<NB, EPB, NW, PRef>(P, sm, e, i);
     }
-    for (int k = tid; k < 2 * NB; k += 64 * NW) sm.beam[k] = P.beam_cs[k];
-    for (int k = tid; k < (int)(sizeof(Rects) / 8); k += 64 * NW)
-        reinterpret_cast<uint64_t*>(&sm.rects)[k] = reinterpret_cast<const uint64_t*>(P.rects)[k];
+    load_tables<NB, EPB, NW, PRef>(P, sm);
     for (int t = 0; t < T; ++t) {
         const size_t N = (size_t)P.N;
         const size_t tn = (size_t)t * N;
@@ -1943,8 +1964,8 @@ __global__ __launch_bounds__(64 * NW, min_waves_per_simd(NB, EPB, NW, PAIR, true
             if (t + 1 < T) a_next = R.io.action[tn + N + base + tid];   // lands under this step
         }
         __syncthreads();
-        step_body<NB, EPB, SENS, true, NW, BOXES, PAIR, const Params __attribute__((address_space(4)))&,
-                  const StepIO __attribute__((address_space(4)))&>(P, sm, next_env, R.io, t == T - 1, tn);
+        step_body<NB, EPB, SENS, true, NW, BOXES, PAIR, PRef, const StepIO __attribute__((address_space(4)))&>(P, sm, next_env, R.io,
+                                                                                                           t == T - 1, tn);
     }
 }
 
@@ -1982,7 +2003,8 @@ __global__ __launch_bounds__(64 * NW) void rollout_big_kernel(BigKArgs) {   // t
     __shared__ float2 pol_eps[2][EPB];   // action noise of this step and of the next one
     BigKArgsPtr A = (BigKArgsPtr)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(A));
-    const Params __attribute__((address_space(4)))& P = A->P;
+    using PRef = const Params __attribute__((address_space(4)))&;
+    PRef P = A->P;
     const RolloutArgs __attribute__((address_space(4)))& R = A->R;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int base = blockIdx.x * EPB;
@@ -1992,24 +2014,10 @@ __global__ __launch_bounds__(64 * NW) void rollout_big_kernel(BigKArgs) {   // t
         const float* const prm = R.params;
         for (int k = tid; k < mlp64::P_ACTOR; k += kThreads) wts[k] = prm[k];
     }
-    if (tid < nloc) {   // the envs' state: HBM -> LDS for the whole rollout
-        const int e = tid, i = base + e;
-        sm.st_d[0][e] = P.x[i]; sm.st_d[1][e] = P.y[i]; sm.st_d[2][e] = P.th[i]; sm.st_d[3][e] = P.gx[i]; sm.st_d[4][e] = P.gy[i];
-        sm.st_d[5][e] = P.past_dist[i]; sm.st_d[6][e] = P.ep_ret[i]; sm.st_d[7][e] = P.ep_path[i];
-        sm.st_pact[e] = P.past_action[i];
-        sm.st_step[e] = (uint32_t)P.ep_step[i];
-        sm.st_ctr[e] = P.rng_ctr[i];
-    }
+    if (tid < nloc) load_state<NB, EPB, NW, PRef>(P, sm, tid, base + tid);   // the envs' state for the whole rollout
     const bool half_rows = P.obs_f16 != 0;   // float16 observation buffers: the policy reads what a reader of the buffers would
-    {
-        const void* const ob = R.obs_buf;
-        for (int k = tid; k < nloc * D; k += kThreads)
-            sm.obs[(k / D) * DP + (k % D)] = half_rows ? __half2float(reinterpret_cast<const __half*>(ob)[(size_t)base * D + k])
-                                                       : reinterpret_cast<const float*>(ob)[(size_t)base * D + k];
-    }
-    for (int k = tid; k < 2 * NB; k += kThreads) sm.beam[k] = P.beam_cs[k];
-    for (int k = tid; k < (int)(sizeof(Rects) / 8); k += kThreads)
-        reinterpret_cast<uint64_t*>(&sm.rects)[k] = reinterpret_cast<const uint64_t*>(P.rects)[k];
+    load_obs_tile<NB, EPB, NW>(sm, R.obs_buf, base, nloc, half_rows);
+    load_tables<NB, EPB, NW, PRef>(P, sm);
     const uint32_t step0 = R.step_base ? *R.step_base : 0u;
     const float var = *R.var_ptr;
     const uint64_t seed = R.seed, gid = P.env_id_base + (uint64_t)(base + lane);
@@ -2024,10 +2032,11 @@ __global__ __launch_bounds__(64 * NW) void rollout_big_kernel(BigKArgs) {   // t
     auto tile_policy = [&](const int k, const size_t tn, const int eps_row, auto in_step) __attribute__((always_inline)) {
         const int e = 16 * k + (lane & 15), kk = lane >> 4;   // lane (env, kk) feeds obs[env][4 kk .. 4 kk + 3]
         const bool valid = e < nloc;
+        // (mlp64_obs_row's code, written out: through the helper the SENS instantiations with the 128-segment passes spill 28 instead
+        // of 20 bytes of scratch)
         float xs[KS];
         if constexpr (decltype(in_step)::value) {   // inside a step, behind barrier B2: the rows the step will leave
-            next_obs_n<NB, EPB, NW, SENS, KS, const Params __attribute__((address_space(4)))&>(P, sm, min(e, nloc - 1), KS * kk, sigma,
-                                                                                               below_min, xs);
+            next_obs_n<NB, EPB, NW, SENS, KS, PRef>(P, sm, min(e, nloc - 1), KS * kk, sigma, below_min, xs);
             if (half_rows) {
 #pragma unroll
                 for (int j = 0; j < KS; ++j) xs[j] = __half2float(__float2half_rn(xs[j]));
@@ -2082,8 +2091,8 @@ __global__ __launch_bounds__(64 * NW) void rollout_big_kernel(BigKArgs) {   // t
                 else if (wv == kNoiseWave && ln < nloc && t + 2 < T) draw_noise(t + 2);   // row (t + 2) & 1: not the one being read
             }
         };
-        step_body<NB, EPB, SENS, true, NW, BOXES, PAIR, const Params __attribute__((address_space(4)))&,
-                  const StepIO __attribute__((address_space(4)))&, decltype(hook)>(P, sm, next_env, A->io, t == T - 1, tn, hook);
+        step_body<NB, EPB, SENS, true, NW, BOXES, PAIR, PRef, const StepIO __attribute__((address_space(4)))&, decltype(hook)>(
+            P, sm, next_env, A->io, t == T - 1, tn, hook);
         // the observation tile of step t + 1 is in sm.obs (its store only reads it) and its action in sm.act_l
     }
 }
@@ -2429,24 +2438,26 @@ static ShapePick pick_shape(const navsim* h, bool tape) {
     return sp;
 }
 
+// Run-time choices -> template arguments: f(std::true_type) or f(std::false_type), so that f's body can name an instantiation
+// with the flag (`kernel<..., S, ...>`, `if constexpr (S)`).  Nested calls combine flags.
+template <class F>
+static void with_flag(const bool b, F&& f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+
+// The SENS flag of a handle's instantiations: the sensor-fidelity options (range noise, -inf below range_min) are on
+static bool sens_on(const navsim* h) { return h->P.sigma > 0.f || h->P.below_min_mode != 0; }
+
 // KERNEL: step_kernel | steps_kernel; `go(kernel, epb, waves)` launches
-#define NAVSIM_DISPATCH_CAST(KERNEL, EPB_, NW_)                                                            \
-    do {                                                                                                   \
-        if (sp.cast == 3) {                                                                                \
-            if (sens) go(KERNEL<NB, EPB_, true, NW_, true>, EPB_, NW_);                                    \
-            else go(KERNEL<NB, EPB_, false, NW_, true>, EPB_, NW_);                                        \
-        } else if (sp.cast == 2) {                                                                         \
-            constexpr int kNT = (NB == 10 && EPB_ >= 32) ? 2 : 1;   /* the streaming variant exists for the big shapes */ \
-            if (sens) go(KERNEL<NB, EPB_, true, NW_, false, kNT>, EPB_, NW_);                              \
-            else go(KERNEL<NB, EPB_, false, NW_, false, kNT>, EPB_, NW_);                                  \
-        } else if (sp.cast == 1) {                                                                         \
-            if (sens) go(KERNEL<NB, EPB_, true, NW_, false, 1>, EPB_, NW_);                                \
-            else go(KERNEL<NB, EPB_, false, NW_, false, 1>, EPB_, NW_);                                    \
-        } else {                                                                                           \
-            if (sens) go(KERNEL<NB, EPB_, true, NW_, false>, EPB_, NW_);                                   \
-            else go(KERNEL<NB, EPB_, false, NW_, false>, EPB_, NW_);                                       \
-        }                                                                                                  \
-    } while (0)
+#define NAVSIM_DISPATCH_CAST(KERNEL, EPB_, NW_)                                                                            \
+    with_flag(sens_on(h), [&](auto S) {                                                                                    \
+        if (sp.cast == 3) go(KERNEL<NB, EPB_, S, NW_, true>, EPB_, NW_);                                                   \
+        else if (sp.cast == 2) /* the streaming variant exists for the big shapes */                                       \
+            go(KERNEL<NB, EPB_, S, NW_, false, (NB == 10 && EPB_ >= 32) ? 2 : 1>, EPB_, NW_);                              \
+        else if (sp.cast == 1) go(KERNEL<NB, EPB_, S, NW_, false, 1>, EPB_, NW_);                                          \
+        else go(KERNEL<NB, EPB_, S, NW_, false>, EPB_, NW_);                                                               \
+    })
 #define NAVSIM_DISPATCH_SHAPE(KERNEL)                                              \
     do {                                                                           \
         if (sp.epb == 8) NAVSIM_DISPATCH_CAST(KERNEL, 8, 8);                       \
@@ -2462,7 +2473,6 @@ template <int NB>
 static void launch_step(const navsim* h, const float* action, const float* past, void* obs, float* reward, uint8_t* done,
                         uint8_t* arrive, uint8_t* ended, float* ep_ret, int32_t* ep_len, float* ep_path, hipStream_t st,
                         hipFuncAttributes* query = nullptr) {
-    const bool sens = h->P.sigma > 0.f || h->P.below_min_mode != 0;
     const StepKArgs ka = {h->P, StepIO{(const float2*)action, (const float2*)past, obs, reward, done, arrive, ended, ep_ret, ep_len,
                                        ep_path}};
     auto go = [&](auto kernel, int epb, int nw) {
@@ -2476,7 +2486,6 @@ static void launch_step(const navsim* h, const float* action, const float* past,
 // navsim_step_seq: the same shapes and cast variants, all steps of the tape in one launch
 template <int NB>
 static void launch_steps(const navsim* h, const SeqArgs& R, hipStream_t st, hipFuncAttributes* query = nullptr) {
-    const bool sens = h->P.sigma > 0.f || h->P.below_min_mode != 0;
     const SeqKArgs ka = {h->P, R};
     auto go = [&](auto kernel, int epb, int nw) {
         if (query) (void)hipFuncGetAttributes(query, reinterpret_cast<const void*>(kernel));
@@ -2882,80 +2891,61 @@ int navsim_step(navsim_t* h, const float* action_dev, const float* past_action_d
     return NAVSIM_OK;
 }
 
+// what both rollout entry points check before anything is launched, and the RolloutArgs they pass; `beams_ok`: the policy has an
+// instantiation for P.B.  NAVSIM_OK with n_steps == 0: nothing to launch.
+static int rollout_args(const navsim* h, const char* fn, bool (*beams_ok)(int), const char* beams_msg, RolloutArgs& R,
+                        const float* params, void* obs_buf, float* act_buf, float* logp_buf, float* reward, uint8_t* done,
+                        uint8_t* arrive, uint8_t* ended, float* ep_return, int32_t* ep_length, float* ep_path, const float* var,
+                        uint64_t seed, const uint32_t* step_base, int32_t n_steps) {
+    const std::string f = std::string(fn) + ": ";
+    if (!h || !params || !obs_buf || !act_buf || !logp_buf || !reward || !done || !arrive || !ended || !var || n_steps < 0)
+        return fail(NAVSIM_E_ARG, f + "bad argument");
+    if (!h->has_map) return fail(NAVSIM_E_STATE, f + "call navsim_set_map first");
+    if (!beams_ok(h->P.B)) return fail(NAVSIM_E_ARG, f + beams_msg);
+    if (((uintptr_t)params & 15) || ((uintptr_t)act_buf & 7) || ((uintptr_t)obs_buf & 15))
+        return fail(NAVSIM_E_ARG, f + "params and obs must be 16-byte, act 8-byte aligned");
+    R = RolloutArgs{params, obs_buf, act_buf, logp_buf, reward, done, arrive, ended, ep_return, ep_length, ep_path, var, step_base,
+                    seed, n_steps};
+    return NAVSIM_OK;
+}
+
 int navsim_rollout_mlp64(navsim_t* h, const float* actor_params_dev, void* obs_buf_dev, float* act_buf_dev,
                          float* logp_buf_dev, float* reward_dev, uint8_t* done_dev, uint8_t* arrive_dev, uint8_t* ended_dev,
                          float* ep_return_dev, int32_t* ep_length_dev, float* ep_path_dev, const float* var_dev,
                          uint64_t act_seed, const uint32_t* step_base_dev, int32_t n_steps, void* stream) {
-    if (!h || !actor_params_dev || !obs_buf_dev || !act_buf_dev || !logp_buf_dev || !reward_dev || !done_dev || !arrive_dev ||
-        !ended_dev || !var_dev || n_steps < 0)
-        return fail(NAVSIM_E_ARG, "navsim_rollout_mlp64: bad argument");
-    if (!h->has_map) return fail(NAVSIM_E_STATE, "navsim_rollout_mlp64: call navsim_set_map first");
-    const RolloutPick rp = pick_rollout(h);
-    if (rp.kind == 0) return fail(NAVSIM_E_ARG, "navsim_rollout_mlp64: the (B + 6)-64-64 policy needs 10 or 36 beams");
-    if (((uintptr_t)actor_params_dev & 15) || ((uintptr_t)act_buf_dev & 7) || ((uintptr_t)obs_buf_dev & 15))
-        return fail(NAVSIM_E_ARG, "navsim_rollout_mlp64: params and obs must be 16-byte, act 8-byte aligned");
-    if (n_steps == 0) return NAVSIM_OK;
     RolloutArgs R;
-    R.params = actor_params_dev; R.obs_buf = obs_buf_dev; R.act_buf = act_buf_dev; R.logp_buf = logp_buf_dev;
-    R.reward = reward_dev; R.done = done_dev; R.arrive = arrive_dev; R.ended = ended_dev; R.ep_return = ep_return_dev;
-    R.ep_length = ep_length_dev; R.ep_path = ep_path_dev; R.var_ptr = var_dev; R.step_base = step_base_dev;
-    R.seed = act_seed; R.T = n_steps;
-    const bool sens = h->P.sigma > 0.f || h->P.below_min_mode != 0;
+    const int rc = rollout_args(h, "navsim_rollout_mlp64", [](int b) { return b == 10 || b == 36; },
+                                "the (B + 6)-64-64 policy needs 10 or 36 beams", R, actor_params_dev, obs_buf_dev, act_buf_dev,
+                                logp_buf_dev, reward_dev, done_dev, arrive_dev, ended_dev, ep_return_dev, ep_length_dev, ep_path_dev,
+                                var_dev, act_seed, step_base_dev, n_steps);
+    if (rc != NAVSIM_OK || n_steps == 0) return rc;
+    const RolloutPick rp = pick_rollout(h);
     hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((h->P.N + rp.epb - 1) / rp.epb), block(64 * rp.waves);
     if (rp.kind == 2) {   // 64 envs on 16 waves, the cast variants of launch_step (see pick_rollout)
-        const size_t D = (size_t)h->P.B + 6;
-        StepIO io;
-        io.action = nullptr; io.past_override = nullptr;
-        io.obs_out = h->P.obs_f16 ? (void*)(reinterpret_cast<__half*>(obs_buf_dev) + (size_t)h->P.N * D)
-                                  : (void*)(reinterpret_cast<float*>(obs_buf_dev) + (size_t)h->P.N * D);
-        io.reward = reward_dev; io.done = done_dev; io.arrive = arrive_dev; io.ended = ended_dev;
-        io.ep_return = ep_return_dev; io.ep_length = ep_length_dev; io.ep_path_out = ep_path_dev;
-        const dim3 grid((h->P.N + rp.epb - 1) / rp.epb), block(64 * rp.waves);
-        const BigKArgs ka = {h->P, R, io};
-#define NAVSIM_BIG(BOXES_, PAIR_)                                                                                         \
-    do {                                                                                                                  \
-        if (sens) hipLaunchKernelGGL((rollout_big_kernel<64, true, 16, BOXES_, PAIR_>), grid, block, 0, st, ka);   \
-        else hipLaunchKernelGGL((rollout_big_kernel<64, false, 16, BOXES_, PAIR_>), grid, block, 0, st, ka);       \
-    } while (0)
-        if (rp.epb == 32) {   // (tile boxes; forced: any map without the 128-segment passes)
-            if (rp.cast == 3) {
-                if (sens) hipLaunchKernelGGL((rollout_big_kernel<32, true, 8, true, 0>), grid, block, 0, st, ka);
-                else hipLaunchKernelGGL((rollout_big_kernel<32, false, 8, true, 0>), grid, block, 0, st, ka);
-            } else {
-                if (sens) hipLaunchKernelGGL((rollout_big_kernel<32, true, 8, false, 0>), grid, block, 0, st, ka);
-                else hipLaunchKernelGGL((rollout_big_kernel<32, false, 8, false, 0>), grid, block, 0, st, ka);
-            }
-        } else if (rp.cast == 3) NAVSIM_BIG(true, 0);
-        else if (rp.cast == 2) NAVSIM_BIG(false, 2);
-        else if (rp.cast == 1) NAVSIM_BIG(false, 1);
-        else NAVSIM_BIG(false, 0);
-#undef NAVSIM_BIG
-        HIP_TRY(hipGetLastError());
-        return NAVSIM_OK;
-    }
-    // 8 waves per workgroup: more ray waves shorten the cast
-    constexpr int kRollWaves = 8;
-    const dim3 grid((h->P.N + rp.epb - 1) / rp.epb), block(64 * kRollWaves);
-    if (h->P.B == 36) {
-        if (rp.cast == 3) {
-            if (sens) hipLaunchKernelGGL((rollout_kernel<36, 16, true, kRollWaves, true>), grid, block, 0, st, h->P, R);
-            else hipLaunchKernelGGL((rollout_kernel<36, 16, false, kRollWaves, true>), grid, block, 0, st, h->P, R);
-        } else {
-            if (sens) hipLaunchKernelGGL((rollout_kernel<36, 16, true, kRollWaves>), grid, block, 0, st, h->P, R);
-            else hipLaunchKernelGGL((rollout_kernel<36, 16, false, kRollWaves>), grid, block, 0, st, h->P, R);
-        }
-    } else if (rp.cast == 3) {
-        if (sens) hipLaunchKernelGGL((rollout_kernel<10, 16, true, kRollWaves, true>), grid, block, 0, st, h->P, R);
-        else hipLaunchKernelGGL((rollout_kernel<10, 16, false, kRollWaves, true>), grid, block, 0, st, h->P, R);
-    } else if (rp.epb == 4) {
-        if (sens) hipLaunchKernelGGL((rollout_kernel<10, 4, true, kRollWaves>), grid, block, 0, st, h->P, R);
-        else hipLaunchKernelGGL((rollout_kernel<10, 4, false, kRollWaves>), grid, block, 0, st, h->P, R);
-    } else if (rp.epb == 8) {
-        if (sens) hipLaunchKernelGGL((rollout_kernel<10, 8, true, kRollWaves>), grid, block, 0, st, h->P, R);
-        else hipLaunchKernelGGL((rollout_kernel<10, 8, false, kRollWaves>), grid, block, 0, st, h->P, R);
-    } else {
-        if (sens) hipLaunchKernelGGL((rollout_kernel<10, 16, true, kRollWaves>), grid, block, 0, st, h->P, R);
-        else hipLaunchKernelGGL((rollout_kernel<10, 16, false, kRollWaves>), grid, block, 0, st, h->P, R);
+        const BigKArgs ka = {h->P, R, rollout_io(R, (size_t)h->P.N, (size_t)h->P.B + 6, 0, h->P.obs_f16 != 0)};
+        auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, st, ka); };
+        with_flag(sens_on(h), [&](auto S) {
+            if (rp.epb == 32) {   // (tile boxes; forced: any map without the 128-segment passes)
+                if (rp.cast == 3) go(rollout_big_kernel<32, S, 8, true, 0>);
+                else go(rollout_big_kernel<32, S, 8, false, 0>);
+            } else if (rp.cast == 3) go(rollout_big_kernel<64, S, 16, true, 0>);
+            else if (rp.cast == 2) go(rollout_big_kernel<64, S, 16, false, 2>);
+            else if (rp.cast == 1) go(rollout_big_kernel<64, S, 16, false, 1>);
+            else go(rollout_big_kernel<64, S, 16, false, 0>);
+        });
+    } else {   // 8 waves per workgroup (pick_rollout): more ray waves shorten the cast
+        constexpr int kRollWaves = 8;
+        auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, st, h->P, R); };
+        with_flag(sens_on(h), [&](auto S) {
+            if (h->P.B == 36) {
+                if (rp.cast == 3) go(rollout_kernel<36, 16, S, kRollWaves, true>);
+                else go(rollout_kernel<36, 16, S, kRollWaves>);
+            } else if (rp.cast == 3) go(rollout_kernel<10, 16, S, kRollWaves, true>);
+            else if (rp.epb == 4) go(rollout_kernel<10, 4, S, kRollWaves>);
+            else if (rp.epb == 8) go(rollout_kernel<10, 8, S, kRollWaves>);
+            else go(rollout_kernel<10, 16, S, kRollWaves>);
+        });
     }
     HIP_TRY(hipGetLastError());
     return NAVSIM_OK;
@@ -2965,24 +2955,16 @@ int navsim_rollout_resmlp512(navsim_t* h, const float* actor_params_dev, void* o
                              float* reward_dev, uint8_t* done_dev, uint8_t* arrive_dev, uint8_t* ended_dev, float* ep_return_dev,
                              int32_t* ep_length_dev, float* ep_path_dev, const float* var_dev, uint64_t act_seed,
                              const uint32_t* step_base_dev, int32_t n_steps, void* stream) {
-    if (!h || !actor_params_dev || !obs_buf_dev || !act_buf_dev || !logp_buf_dev || !reward_dev || !done_dev || !arrive_dev ||
-        !ended_dev || !var_dev || n_steps < 0)
-        return fail(NAVSIM_E_ARG, "navsim_rollout_resmlp512: bad argument");
-    if (!h->has_map) return fail(NAVSIM_E_STATE, "navsim_rollout_resmlp512: call navsim_set_map first");
-    if (h->P.B != 10)
-        return fail(NAVSIM_E_ARG, "navsim_rollout_resmlp512: the reference's nets read 16-wide observations (10 beams)");
-    if (((uintptr_t)actor_params_dev & 15) || ((uintptr_t)act_buf_dev & 7) || ((uintptr_t)obs_buf_dev & 15))
-        return fail(NAVSIM_E_ARG, "navsim_rollout_resmlp512: params and obs must be 16-byte, act 8-byte aligned");
-    if (n_steps == 0) return NAVSIM_OK;
     RolloutArgs R;
-    R.params = actor_params_dev; R.obs_buf = obs_buf_dev; R.act_buf = act_buf_dev; R.logp_buf = logp_buf_dev;
-    R.reward = reward_dev; R.done = done_dev; R.arrive = arrive_dev; R.ended = ended_dev; R.ep_return = ep_return_dev;
-    R.ep_length = ep_length_dev; R.ep_path = ep_path_dev; R.var_ptr = var_dev; R.step_base = step_base_dev;
-    R.seed = act_seed; R.T = n_steps;
-    const bool sens = h->P.sigma > 0.f || h->P.below_min_mode != 0;
+    const int rc = rollout_args(h, "navsim_rollout_resmlp512", [](int b) { return b == 10; },
+                                "the reference's nets read 16-wide observations (10 beams)", R, actor_params_dev, obs_buf_dev,
+                                act_buf_dev, logp_buf_dev, reward_dev, done_dev, arrive_dev, ended_dev, ep_return_dev, ep_length_dev,
+                                ep_path_dev, var_dev, act_seed, step_base_dev, n_steps);
+    if (rc != NAVSIM_OK || n_steps == 0) return rc;
     const dim3 grid((h->P.N + 15) / 16), block(64 * 8);
-    if (sens) hipLaunchKernelGGL(rollout_resmlp_kernel<true>, grid, block, 0, (hipStream_t)stream, h->P, R);
-    else hipLaunchKernelGGL(rollout_resmlp_kernel<false>, grid, block, 0, (hipStream_t)stream, h->P, R);
+    with_flag(sens_on(h), [&](auto S) {
+        hipLaunchKernelGGL(rollout_resmlp_kernel<S>, grid, block, 0, (hipStream_t)stream, h->P, R);
+    });
     HIP_TRY(hipGetLastError());
     return NAVSIM_OK;
 }
@@ -3017,23 +2999,14 @@ int navsim_evaluate_mlp64(navsim_t* h, const float* actor_params_dev, const void
     if (rc != NAVSIM_OK) return rc;
     const EvalArgs R = {actor_params_dev, obs0_dev, ep_flags_dev, ep_length_dev, ep_return_dev, ep_path_dev, count_dev, steps_dev,
                         quota, n_steps};
-    const bool sens = h->P.sigma > 0.f || h->P.below_min_mode != 0;
-    const bool boxes = h->P.tile_box != nullptr;
-    hipStream_t st = (hipStream_t)stream;
     const dim3 grid((h->P.N + 15) / 16), block(64 * 8);
-#define NAVSIM_EVAL(NB_)                                                                                                \
-    do {                                                                                                                \
-        if (boxes) {                                                                                                    \
-            if (sens) hipLaunchKernelGGL((evaluate_kernel<NB_, true, true>), grid, block, 0, st, h->P, R);              \
-            else hipLaunchKernelGGL((evaluate_kernel<NB_, false, true>), grid, block, 0, st, h->P, R);                  \
-        } else {                                                                                                        \
-            if (sens) hipLaunchKernelGGL((evaluate_kernel<NB_, true, false>), grid, block, 0, st, h->P, R);             \
-            else hipLaunchKernelGGL((evaluate_kernel<NB_, false, false>), grid, block, 0, st, h->P, R);                 \
-        }                                                                                                               \
-    } while (0)
-    if (h->P.B == 36) NAVSIM_EVAL(36);
-    else NAVSIM_EVAL(10);
-#undef NAVSIM_EVAL
+    auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)stream, h->P, R); };
+    with_flag(sens_on(h), [&](auto S) {
+        with_flag(h->P.tile_box != nullptr, [&](auto BOXES) {
+            if (h->P.B == 36) go(evaluate_kernel<36, S, BOXES>);
+            else go(evaluate_kernel<10, S, BOXES>);
+        });
+    });
     HIP_TRY(hipGetLastError());
     return NAVSIM_OK;
 }
@@ -3047,10 +3020,10 @@ int navsim_evaluate_resmlp512(navsim_t* h, const float* actor_params_dev, const 
     if (rc != NAVSIM_OK) return rc;
     const EvalArgs R = {actor_params_dev, obs0_dev, ep_flags_dev, ep_length_dev, ep_return_dev, ep_path_dev, count_dev, steps_dev,
                         quota, n_steps};
-    const bool sens = h->P.sigma > 0.f || h->P.below_min_mode != 0;
     const dim3 grid((h->P.N + 15) / 16), block(64 * 8);
-    if (sens) hipLaunchKernelGGL(evaluate_resmlp_kernel<true>, grid, block, 0, (hipStream_t)stream, h->P, R);
-    else hipLaunchKernelGGL(evaluate_resmlp_kernel<false>, grid, block, 0, (hipStream_t)stream, h->P, R);
+    with_flag(sens_on(h), [&](auto S) {
+        hipLaunchKernelGGL(evaluate_resmlp_kernel<S>, grid, block, 0, (hipStream_t)stream, h->P, R);
+    });
     HIP_TRY(hipGetLastError());
     return NAVSIM_OK;
 }

@@ -32,7 +32,7 @@ def build():
             "#define RESMLP_MARK(i) do { if (blockIdx.x == 7 && threadIdx.x == 0) { const unsigned long long now_ = wall_clock64(); "
             "g_dbg[i] += now_ - g_dbg[15]; g_dbg[15] = now_; } } while (0)\n"
             '#include "/tmp/resmlp_phases/resmlp_policy.h"')
-    t = rep(t, "        resmlp::load_weights_b(R.params, lane, wave, W);", "        RESMLP_MARK(0);\n        resmlp::load_weights_b(R.params, lane, wave, W);")
+    t = rep(t, "    resmlp::load_weights_b(params, lane, wave, W);", "    RESMLP_MARK(0);\n    resmlp::load_weights_b(params, lane, wave, W);")
     t = rep(t, "            R.logp_buf[tn + base + l15] = o.logp;\n        }\n        __syncthreads();\n",
             "            R.logp_buf[tn + base + l15] = o.logp;\n        }\n        __syncthreads();\n        RESMLP_MARK(5);\n")
     t = rep(t, "        __syncthreads();   // the observation tile of step t + 1 is complete in sm.obs", "        RESMLP_MARK(6);\n        __syncthreads();   //")
