@@ -15,8 +15,13 @@
 //     no second split, no wave_lds_fence round trips.
 //   * the sample sums db2, dW3, dW4 are per-lane partial sums over the wave's tiles (a lane owns the same sample slot in every
 //     tile), reduced across lanes once per launch; db1 rides on G1's operand (one MFMA with a ones operand per piece).
-// MFMA -> vector hazards: the compiler does not see inside the asm statements, so every chain whose accumulators the vector unit
-// reads next ends in `settle` (12 wait states; gfx950 needs 11 after an 8-pass XDL op).
+//   * layer 1 runs a tile ahead: F1 of the next tile sits inside G2, and the vector work that used to wait in front of F1, F2 and G2
+//     (bias starts, relu1, the split of H1's first k-step, the relu mask of layer 1) is spread over the 60 MFMA slots of G2 + F1, a
+//     third of which were empty.  The loop starts at F2's first MFMA; tools/verify/mfma_slot_report.py counts what sits in front of
+//     every MFMA, tests/test_isa_schedule_cpu.py holds the counts.
+// MFMA -> vector hazards: the compiler does not see inside the asm statements, so a chain whose accumulators the vector unit reads
+// right behind it ends in `settle` (12 wait states; gfx950 needs 11 after an 8-pass XDL op); where a chain's reader sits two or more
+// MFMA slots further on, the slots' own instructions are the wait states, and the lint of the listing (below) counts them.
 //
 // LDS image of a 32-sample x 64-unit matrix of pieces: row m = 128 bytes, 8-byte slots ("quads": 4 units) XOR-swizzled by
 //   f(m) = (m & 3) | ((m >> 2 ^ m >> 3) & 1) << 2 | ((m >> 1 ^ m >> 3) & 1) << 3
@@ -69,8 +74,16 @@ static_assert(sizeof(SmemS::img) / SW >= 96 * 64 * sizeof(float), "lane partials
 #define X3S_MFMA32_AZ_AV(acc, A, B) asm volatile(X3S_G "v_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=&a"(acc) : "a"(A), "v"(B))
 #define X3S_MFMA32_A_AA(acc, A, B) asm volatile(X3S_GUARD "v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(acc) : "a"(A), "a"(B))
 #define X3S_MFMA16_A_AA(acc, A, B) asm volatile(X3S_GUARD "v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc) : "a"(A), "a"(B))
+#define X3S_MFMA16_V_AA(acc, A, B) asm volatile(X3S_GUARD "v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc) : "a"(A), "a"(B))
+#define X3S_MFMA16G_V_AA(acc, A, B) asm volatile(X3S_G "v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc) : "a"(A), "a"(B))
+#define X3S_MFMA16_A_VA(acc, A, B) asm volatile(X3S_GUARD "v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc) : "v"(A), "a"(B))
+#define X3S_MFMA16_V_VA(acc, A, B) asm volatile(X3S_GUARD "v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(A), "a"(B))
 #define X3S_MFMA16G_A_AA(acc, A, B) asm volatile(X3S_G "v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc) : "a"(A), "a"(B))
 #define X3S_MFMA16_A_AV(acc, A, B) asm volatile(X3S_GUARD "v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc) : "a"(A), "v"(B))
+
+// sixty slots written out with constant slot numbers (a loop of this size is past the full-unroll limit, and a slot number that is not a
+// constant turns the register arrays into scratch memory)
+#define X3S_REP10(F, b) F(b + 0); F(b + 1); F(b + 2); F(b + 3); F(b + 4); F(b + 5); F(b + 6); F(b + 7); F(b + 8); F(b + 9);
 
 // the vector unit may read / overwrite these accumulators from here on (8-pass XDL write -> VALU: 11 wait states)
 __device__ __forceinline__ void settle(f32x16& a, f32x16& b) { asm volatile("s_nop 7\n\ts_nop 3" : "+v"(a), "+v"(b)); }
@@ -244,6 +257,9 @@ __device__ __forceinline__ void pass_body(SmemS& sm, const float* __restrict__ p
 #pragma unroll
         for (int r = 0; r < 16; ++r) pb2[t][r] = pw3[t][r] = pw4[t][r] = 0.f;
     float adb3 = 0.f, adb4 = 0.f, st0 = 0.f, st1 = 0.f, st2 = 0.f, st3 = 0.f;
+    // (no instruction: a use of dW2's accumulators in the middle of the phases that do not touch them, so that the register allocator
+    // does not park them elsewhere for those phases and fetch them back for G2 -- 96 copies per tile)
+    auto keep_w2 = [&]() { asm volatile("" : "+a"(aW2[0][0]), "+a"(aW2[0][1]), "+a"(aW2[1][0]), "+a"(aW2[1][1])); };
     u32x4 ones = {0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u};   // bf16 1.0 in every k-slot
     asm volatile("" : "+a"(ones));   // lives in AGPRs for the whole launch
 
@@ -254,16 +270,23 @@ __device__ __forceinline__ void pass_body(SmemS& sm, const float* __restrict__ p
     // and is copied over right in front of the MFMA: the hazard above) long before their use; `landed` is their s_waitcnt, placed a
     // few thousand cycles later and tied to the registers so that nothing reads or copies them before.  (Hidden loads are safe for the
     // compiler's own vmcnt bookkeeping: loads return in order, extra outstanding ones only make its waits longer.)
-    u32x4 xp[3], xbn[3];   // rows of the NEXT tile ; columns of THIS tile (G1 runs one tile late)
+    u32x4 xp[3], xbn[3];   // rows of the tile whose F1 runs next ; columns of the tile whose G1 runs next (G1 runs one tile late)
     float pre_a0 = 0.f, pre_a1 = 0.f, pre_lp = 0.f, pre_t = 0.f;
-    auto request_tile = [&](const long long next, const long long cur) {   // both clamped by the caller: always valid tiles
-        const unsigned char* r = prep + (size_t)next * kTileBytes + ((l31 * 3) * 16 + 8 * lhi) * 2;   // rows past the batch are zero in `prep`
-        const unsigned char* c = prep + (size_t)cur * kTileBytes + kRowsBytes + (l15 * 32 + 8 * kk) * 2;   // lane (f = l15, kk): samples 8 kk .. + 7
+    // Each request is placed behind the last reader of the registers it lands in (F1 for the rows, G1 for the columns, the heads for the
+    // sample's scalars: all three ride on B2's slots), so no copy of them is kept; `landed` sits in front of F1, some 85 MFMA slots
+    // later.  All tiles are clamped by the caller: always valid.
+    auto request_rows = [&](const long long t) {
+        const unsigned char* r = prep + (size_t)t * kTileBytes + ((l31 * 3) * 16 + 8 * lhi) * 2;   // rows past the batch are zero in `prep`
         asm volatile("global_load_dwordx4 %0, %3, off\n\tglobal_load_dwordx4 %1, %3, off offset:32\n\tglobal_load_dwordx4 %2, %3, off offset:64"
                      : "=a"(xp[0]), "=a"(xp[1]), "=a"(xp[2]) : "v"(r));
+    };
+    auto request_cols = [&](const long long t) {
+        const unsigned char* c = prep + (size_t)t * kTileBytes + kRowsBytes + (l15 * 32 + 8 * kk) * 2;   // lane (f = l15, kk): samples 8 kk .. + 7
         asm volatile("global_load_dwordx4 %0, %3, off\n\tglobal_load_dwordx4 %1, %3, off offset:1024\n\tglobal_load_dwordx4 %2, %3, off offset:2048"
                      : "=a"(xbn[0]), "=a"(xbn[1]), "=a"(xbn[2]) : "v"(c));
-        const long long m = next * 32 + l31;
+    };
+    auto request_scalars = [&](const long long t) {
+        const long long m = t * 32 + l31;
         if (m < M) {
             if (ACTOR) {
                 const float2 a = reinterpret_cast<const float2*>(act)[m];
@@ -298,11 +321,19 @@ __device__ __forceinline__ void pass_body(SmemS& sm, const float* __restrict__ p
         constexpr int ai[9] = {2, 2, 1, 0, 1, 1, 0, 0, 0};      // piece of dH1
         constexpr int bi[9] = {0, 0, 1, 2, 0, 0, 1, 0, 0};      // piece of X (kind 0)
         if (guard) {   // (the tail after the tile loop: the compiler moves the accumulators around there -- every MFMA waits one state)
-            if (kind[e]) { X3S_MFMA16G_A_AA(aB1[u], o.da[u].p[ai[e]], ones); }
+            if (kind[e]) { X3S_MFMA16G_V_AA(aB1[u], o.da[u].p[ai[e]], ones); }
             else { X3S_MFMA16G_A_AA(aW1[u], o.da[u].p[ai[e]], xb[bi[e]]); }
         } else {
-            if (kind[e]) { X3S_MFMA16_A_AA(aB1[u], o.da[u].p[ai[e]], ones); }
-            else { X3S_MFMA16_A_AA(aW1[u], o.da[u].p[ai[e]], xb[bi[e]]); }
+            // dH1's pieces: accumulator registers in the actor's stream; the critic's has the vector registers of the actor's second head
+            // free and keeps them there (in accumulator registers the allocator parks some of them in vector registers anyway and
+            // copies them back right in front of their MFMA: the hazard of the lint)
+            if (ACTOR) {
+                if (kind[e]) { X3S_MFMA16_V_AA(aB1[u], o.da[u].p[ai[e]], ones); }
+                else { X3S_MFMA16_A_AA(aW1[u], o.da[u].p[ai[e]], xb[bi[e]]); }
+            } else {
+                if (kind[e]) { X3S_MFMA16_V_VA(aB1[u], o.da[u].p[ai[e]], ones); }
+                else { X3S_MFMA16_A_VA(aW1[u], o.da[u].p[ai[e]], xb[bi[e]]); }
+            }
         }
     };
     // one k-step's pieces into both 8-byte slots of its two quads (6 stores)
@@ -331,72 +362,86 @@ __device__ __forceinline__ void pass_body(SmemS& sm, const float* __restrict__ p
         }
     };
 
+    // ---- layer 1 runs one tile AHEAD of the rest of the stream: F1 of the next tile sits between G2's 36th and 37th MFMA, and the vector
+    // work around it -- the b1 start of its accumulators and the W1 pieces in front, relu1, the b2 start of F2's accumulators, the split
+    // of H1's k-step 0 and F2's first weight rows behind -- shares the 60 slots of G2 + F1 with the mask, split and stores of dH1 (the
+    // table at G2).  So c2, h1, hb[0] and wn live across the back-edge and the loop starts at F2's first MFMA.  The prologue runs the
+    // same slots without G2 for the wave's first tile; the last iteration runs them on a clamped (valid) tile and drops the result.
+    // F1 runs c1[0]'s six products, then c1[1]'s (each accumulator sees its products in the order it always did): relu1 of c1[0] and the
+    // split, which reads c1[0] only, start behind c1[1]'s MFMAs.
+    f32x16 c1[2], c2[2];
+    float h1[2][16];   // H1 = relu(b1 + ..): the values the split reads
+    P3 hb[4];          // H1's pieces per k-step; [0] is made ahead
+    u32x4 wn[2][3], wa[2][3];
+    SplitState ss1;
+    auto g2_step = [&](const int k, const P3 (&dA)[2][2], const P3 (&hB)[2][2], f32x16 (&aW2)[2][2]) {
+        const int t2 = k / 24, sk = (k / 12) & 1, e = (k % 12) >> 1, t1 = k & 1;
+        constexpr int ai[6] = {2, 1, 0, 1, 0, 0}, bi[6] = {0, 1, 2, 0, 1, 0};   // small terms first
+        X3S_MFMA32_A_AA(aW2[t2][t1], dA[t2][sk].p[ai[e]], hB[t1][sk].p[bi[e]]);
+    };
+    auto b1_to_c1 = [&](const int q) {
+        const v4f b = ldv(sm.b1, q >> 2, q & 3);
+        c1[q >> 2][4 * (q & 3)] = b.x; c1[q >> 2][4 * (q & 3) + 1] = b.y; c1[q >> 2][4 * (q & 3) + 2] = b.z; c1[q >> 2][4 * (q & 3) + 3] = b.w;
+    };
+    auto b2_to_c2 = [&](const int q) {
+        const v4f b = ldv(sm.b2, q >> 2, q & 3);
+        c2[q >> 2][4 * (q & 3)] = b.x; c2[q >> 2][4 * (q & 3) + 1] = b.y; c2[q >> 2][4 * (q & 3) + 2] = b.z; c2[q >> 2][4 * (q & 3) + 3] = b.w;
+    };
+    auto ld_wa = [&](const int t, const int i) { wa[t][i] = *reinterpret_cast<const u32x4*>(&sm.W1p[i][32 * t + l31][8 * lhi]); };
+    auto ld_wn = [&](const int t, const int i) { wn[t][i] = ldw(&sm.W2p[0][0][0], t, 0, i); };
+    auto f1_mfma = [&](const int j) {   // j of 0..11: accumulator j / 6, its e-th product
+        const int t = j / 6, e = j % 6;
+        constexpr int wi[6] = {2, 1, 0, 1, 0, 0}, xi[6] = {0, 1, 2, 0, 1, 0};
+        if (e == 0) { X3S_MFMA32G_V_AA(c1[t], wa[t][wi[e]], xp[xi[e]]); } else { X3S_MFMA32_V_AA(c1[t], wa[t][wi[e]], xp[xi[e]]); }
+    };
+    auto ahead_work = [&](const int n, const bool alone) {
+        if (n == 11 || n == 13) ld_wa(0, (n - 11) / 2);
+        if (n == 15 || n == 17) ld_wa(1, (n - 15) / 2);
+        if (n == 19) { ld_wa(0, 2); ld_wa(1, 2); }
+        if (n >= 22 && n <= 29) b1_to_c1(n - 22);
+        if (n == 42) { ld_wn(0, 0); ld_wn(1, 0); ld_wn(0, 1); ld_wn(1, 1); }
+        if (n == 43) {
+            ld_wn(0, 2); ld_wn(1, 2);
+            if (alone) asm volatile("s_nop 7" : "+v"(c1[0]));   // (the prologue has no dH1 work in these slots to make up the wait states)
+            relu4(h1[0], c1[0], 0);
+        }
+        if (n == 44) relu4(h1[0], c1[0], 1);
+        if (n >= 45 && n <= 52) { split_block(h1[0], 0, n - 45, hb[0], ss1); b2_to_c2(n - 45); }
+        if (n == 53) relu4(h1[0], c1[0], 2);
+        if (n == 54) relu4(h1[0], c1[0], 3);
+        if (n >= 55 && n <= 58) relu4(h1[1], c1[1], n - 55);
+    };
+
     // imgD starts as zeros: the first tile's "previous G1" then adds nothing (the stream below has no special first iteration)
     for (int k = lane; k < kImgB / 16; k += 64) reinterpret_cast<u32x4*>(smb + img0 + IMG_D)[k] = u32x4{0u, 0u, 0u, 0u};
     bool have_prev = false;
     if (gw < n_tiles) {
-        request_tile(gw, gw);   // (the first tile's "previous" columns: any finite values -- they meet zero pieces)
-        landed();
+        request_rows(gw);
+        request_cols(gw);   // (the first tile's "previous" columns: any finite values -- they meet zero pieces)
+        request_scalars(gw);
+        auto slot = [&](const int n) {
+            if (n == 36) landed();
+            if (n >= 36 && n < 48) f1_mfma(n - 36);
+            ahead_work(n, true);
+        };
+        X3S_REP10(slot, 10) X3S_REP10(slot, 20) X3S_REP10(slot, 30) X3S_REP10(slot, 40) X3S_REP10(slot, 50)
     }
     for (long long tile = gw; tile < n_tiles; tile += stride) {
         const bool valid = tile * 32 + l31 < M;
-        const u32x4 xr[3] = {xp[0], xp[1], xp[2]}, xb[3] = {xbn[0], xbn[1], xbn[2]};
         const float cur_a0 = pre_a0, cur_a1 = pre_a1, cur_lp = pre_lp, cur_t = pre_t;
-
-        // ================================================================ F1: H1^T = relu(b1 + W1 X^T), one k-step
-        f32x16 c1[2];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {   // the accumulators start as the bias (one rounding of sum + bias)
-            const v4f b = ldv(sm.b1, q >> 2, q & 3);
-            c1[q >> 2][4 * (q & 3)] = b.x; c1[q >> 2][4 * (q & 3) + 1] = b.y; c1[q >> 2][4 * (q & 3) + 2] = b.z; c1[q >> 2][4 * (q & 3) + 3] = b.w;
-        }
-        {
-            u32x4 wa[2][3];
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int i = 0; i < 3; ++i) wa[t][i] = *reinterpret_cast<const u32x4*>(&sm.W1p[i][32 * t + l31][8 * lhi]);
-            X3S_MFMA32G_V_AA(c1[0], wa[0][2], xr[0]); X3S_MFMA32G_V_AA(c1[1], wa[1][2], xr[0]);
-            X3S_MFMA32_V_AA(c1[0], wa[0][1], xr[1]);  X3S_MFMA32_V_AA(c1[1], wa[1][1], xr[1]);
-            X3S_MFMA32_V_AA(c1[0], wa[0][0], xr[2]);  X3S_MFMA32_V_AA(c1[1], wa[1][0], xr[2]);
-            X3S_MFMA32_V_AA(c1[0], wa[0][1], xr[0]);  X3S_MFMA32_V_AA(c1[1], wa[1][1], xr[0]);
-            X3S_MFMA32_V_AA(c1[0], wa[0][0], xr[1]);  X3S_MFMA32_V_AA(c1[1], wa[1][0], xr[1]);
-            X3S_MFMA32_V_AA(c1[0], wa[0][0], xr[0]);  X3S_MFMA32_V_AA(c1[1], wa[1][0], xr[0]);
-        }
-        // the next tile's rows and this tile's columns: requested here (F1 has read the registers they land in), waited for at the end
-        // of the tile
-        request_tile(tile + stride < n_tiles ? tile + stride : tile, tile);
-        // first F2 operands while F1 drains
-        u32x4 wn[2][3];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            wn[0][i] = ldw(&sm.W2p[0][0][0], 0, 0, i);
-            wn[1][i] = ldw(&sm.W2p[0][0][0], 1, 0, i);
-        }
-        settle(c1[0], c1[1]);
-        float h1[2][16];   // H1 = relu(b1 + ..): the values the split reads
-#pragma unroll
-        for (int q = 0; q < 8; ++q) relu4(h1[q >> 2], c1[q >> 2], q & 3);
-        f32x16 c2[2];      // F2's accumulators start as b2: requested here, landed long before the first MFMA
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const v4f b = ldv(sm.b2, q >> 2, q & 3);
-            c2[q >> 2][4 * (q & 3)] = b.x; c2[q >> 2][4 * (q & 3) + 1] = b.y; c2[q >> 2][4 * (q & 3) + 2] = b.z; c2[q >> 2][4 * (q & 3) + 3] = b.w;
-        }
+        const long long tile1 = tile + stride < n_tiles ? tile + stride : tile;       // the tile whose F1 runs behind this one's G2
 
         // ================================================================ F2: H2^T = relu(b2 + W2 H1^T); H1 split once, k-step s = (t1, j)
         G1Ops g1o;
         {
-            P3 hb[4];
             u32x4 wk[4][2];   // the leading weight pieces again, for the big terms: requested behind k-step 3 (its slots carry no split)
-            SplitState ss;
-#pragma unroll
-            for (int b = 0; b < 8; ++b) split_block(h1[0], 0, b, hb[0], ss);   // k-step 0: nothing to hide it behind
+            SplitState ss;    // (k-step 0 was split a tile ahead: ahead_work)
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
                 u32x4 w[2][3];
 #pragma unroll
                 for (int i = 0; i < 3; ++i) { w[0][i] = wn[0][i]; w[1][i] = wn[1][i]; }
+                keep_w2();
                 // the stream of k-step s: 10 MFMAs; behind them the split of k-step s + 1 (8 blocks), this step's piece stores and the
                 // next step's weight rows
                 auto filler = [&](const int slot) {
@@ -439,12 +484,12 @@ __device__ __forceinline__ void pass_body(SmemS& sm, const float* __restrict__ p
         // ================================================================ heads, loss, dH2 (in place), the lane's share of db2 / dW3 / dW4;
         // behind the vector work: G1 of the PREVIOUS tile, 36 MFMAs placed one by one
         int g1k = 0;
+        keep_w2();
         float h2[2][16];   // H2, then dH2 in place
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
+            g1_step(g1k++, g1o, xbn);
             relu4(h2[q >> 2], c2[q >> 2], q & 3);
-            g1_step(g1k++, g1o, xb);
-            g1_step(g1k++, g1o, xb);
         }
         float g3 = 0.f, g4 = 0.f;
         {
@@ -526,34 +571,50 @@ __device__ __forceinline__ void pass_body(SmemS& sm, const float* __restrict__ p
                 for (int j = 0; j < 4; ++j) {
                     const int r = 4 * g + j;
                     dh2_value<ACTOR>(h2[t][r], pw3[t][r], pw4[t][r], pb2[t][r], g3, g4, wv3[j], wv4[j]);
-                    if (g1k < 36 && (j & 1)) g1_step(g1k++, g1o, xb);
+                    if (g1k < 36 && (j & 1)) g1_step(g1k++, g1o, xbn);
                 }
-                if (g1k < 36 && (g & 1)) g1_step(g1k++, g1o, xb);
+                if (g1k < 36 && (g & 1)) g1_step(g1k++, g1o, xbn);
             }
         }
-        while (g1k < 36) g1_step(g1k++, g1o, xb);   // (none left: 16 + 16 + 4)
+        // (8 + 16 + 4 so far; the last eight carry the split of dH2's k-step 0 in front of B2)
 
         // ================================================================ B2: dH1^T = (W2^T dH2^T) . [H1 > 0]; dH2 split once, k-step s = (t2, j)
         f32x16 c3[2];
         P3 hB[2][2], dA[2][2];   // G2's operands, [unit tile][sample k-step]: gathered behind B2's stream
         u32x2 mw[8];           // the leading piece of H1 at the lane's own slots: the relu mask of layer 1
+        // [H1 > 0] from the leading piece of H1, read back from the lane's own slots of the image (keeping H1 itself would hold 32
+        // vector registers through F2 / B2, where the file is full): bf16(H1) != 0.  Differs from H1 > 0 only for
+        // 0 < H1 < 2^-126 (the bf16 conversion flushes / rounds such values to zero) -- not a value a sum of O(1) terms takes.
+        float d1[2][16];   // dH1 = (W2^T dH2^T) . [H1 > 0]
+        auto d_mask = [&](const int k) {   // k = (t, j, b): registers 8 j + 4 b .. + 3 of c3[t]
+            const int t = k >> 2, r0 = 8 * ((k >> 1) & 1) + 4 * (k & 1);
+            mask4(d1[t][r0], d1[t][r0 + 1], d1[t][r0 + 2], d1[t][r0 + 3], c3[t][r0], c3[t][r0 + 1], c3[t][r0 + 2], c3[t][r0 + 3], mw[k].x, mw[k].y);
+        };
         {
             P3 db[4];
-            u32x4 wk[4][2];
+            u32x4 wk[4][2], wt[2][3];
             SplitState ss;
 #pragma unroll
             for (int i = 0; i < 3; ++i) {
-                wn[0][i] = ldw(&sm.W2Tp[0][0][0], 0, 0, i);
-                wn[1][i] = ldw(&sm.W2Tp[0][0][0], 1, 0, i);
+                wt[0][i] = ldw(&sm.W2Tp[0][0][0], 0, 0, i);
+                wt[1][i] = ldw(&sm.W2Tp[0][0][0], 1, 0, i);
             }
 #pragma unroll
-            for (int b = 0; b < 8; ++b) split_block(h2[0], 0, b, db[0], ss);
+            for (int b = 0; b < 8; ++b) {
+                g1_step(g1k++, g1o, xbn);
+                split_block(h2[0], 0, b, db[0], ss);
+            }
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
                 u32x4 w[2][3];
 #pragma unroll
-                for (int i = 0; i < 3; ++i) { w[0][i] = wn[0][i]; w[1][i] = wn[1][i]; }
+                for (int i = 0; i < 3; ++i) { w[0][i] = wt[0][i]; w[1][i] = wt[1][i]; }
+                keep_w2();
                 auto filler = [&](const int slot) {
+                    // G1 has read the columns, the heads the sample's scalars: the next ones are requested here
+                    if (s == 0 && slot == 0) request_cols(tile);
+                    if (s == 0 && slot == 1) request_rows(tile1);
+                    if (s == 3 && slot == 0) request_scalars(tile1);
                     if (s < 3 && slot >= 1 && slot <= 8) split_block(h2[(s + 1) >> 1], (s + 1) & 1, slot - 1, db[s + 1], ss);
                     if (s == 3 && slot < 8) wk[slot >> 1][slot & 1] = ldw(&sm.W2Tp[0][0][0], slot & 1, slot >> 1, 0);
                     // H1's side of G2 (imgH is complete since F2): pair q = (t, sk, i) of 0..11, three per k-step
@@ -569,8 +630,8 @@ __device__ __forceinline__ void pass_body(SmemS& sm, const float* __restrict__ p
                     }
                     if (s < 3 && (slot == 0 || slot == 4 || slot == 9)) {
                         const int i = slot == 0 ? 0 : slot == 4 ? 1 : 2;
-                        wn[0][i] = ldw(&sm.W2Tp[0][0][0], 0, s + 1, i);
-                        wn[1][i] = ldw(&sm.W2Tp[0][0][0], 1, s + 1, i);
+                        wt[0][i] = ldw(&sm.W2Tp[0][0][0], 0, s + 1, i);
+                        wt[1][i] = ldw(&sm.W2Tp[0][0][0], 1, s + 1, i);
                     }
                     if (slot == 9) store_pieces(IMG_D, s >> 1, s & 1, db[s]);
                 };
@@ -587,7 +648,10 @@ __device__ __forceinline__ void pass_body(SmemS& sm, const float* __restrict__ p
                 X3S_MFMA32_V_AV(c3[0], w[0][0], db[s].p[1]); filler(8);
                 X3S_MFMA32_V_AV(c3[1], w[1][0], db[s].p[1]); filler(9);
             }
-            int dq = 0;   // dH2's side of G2 behind the big terms (every piece store of imgD is issued): pair q = (t, sk, i)
+            // the big terms, c3[0]'s four and then c3[1]'s (each accumulator sees its products in the order it always did), so that the relu
+            // mask of c3[0] can start behind c3[1]'s last two.  Behind the first six: dH2's side of G2 (every piece store of imgD is
+            // issued), pair q = (t, sk, i)
+            int dq = 0;
             auto gather_d = [&]() {
                 const int t = dq / 6, sk = (dq / 3) & 1, i = dq % 3;
                 dA[t][sk].p[i] = cat(tr_read(smb + g_off(t, sk, 0) + IMG_D + i * kPieceB), tr_read(smb + g_off(t, sk, 1) + IMG_D + i * kPieceB));
@@ -597,61 +661,51 @@ __device__ __forceinline__ void pass_body(SmemS& sm, const float* __restrict__ p
             for (int s = 0; s < 4; ++s) {
                 X3S_MFMA32_V_AV(c3[0], wk[s][0], db[s].p[0]);
                 gather_d(); gather_d();
+            }
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
                 X3S_MFMA32_V_AV(c3[1], wk[s][1], db[s].p[0]);
-                gather_d();
+                if (s < 2) { gather_d(); gather_d(); }
+                else d_mask(s - 2);   // 15 wait states behind c3[0]'s last MFMA: eight reads and three MFMAs (the listing is linted)
             }
         }
 
         // ================================================================ G2: dW2 += dH2^T H1 over the tile's samples, both operands gathered
-        // transposed from the piece images; behind it: the relu mask of layer 1 on dH1, its split, its piece stores (into imgD: every
-        // gather of dH2 is issued before the first of them)
+        // transposed from the piece images, with F1 of the next tile between its 36th and 37th MFMA.  Behind the 60 slots: the rest of
+        // the relu mask of layer 1 on dH1 (c3[0]'s half first: the split starts with it), the split, the piece stores (into imgD: every
+        // gather of dH2 is issued before the first of them), and layer 1's vector work of the next tile (ahead_work).
+        //   slot   0 1   2..9    10     11..18  19     20 21   22..29  30     31 32   33..40  41     42..59
+        //   dH1    mask  split 0 store  split 1 store  mask    split 2 store  mask    split 3 store
+        //   ahead                       W1 pieces (6)          b1 (8)                                W2 rows, relu1, split, b2
         {
-            settle(c3[0], c3[1]);
-            // [H1 > 0] from the leading piece of H1, read back from the lane's own slots of the image (keeping H1 itself would hold 32
-            // vector registers through F2 / B2, where the file is full): bf16(H1) != 0.  Differs from H1 > 0 only for
-            // 0 < H1 < 2^-126 (the bf16 conversion flushes / rounds such values to zero) -- not a value a sum of O(1) terms takes.
-            float d1[2][16];   // dH1 = (W2^T dH2^T) . [H1 > 0]
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {   // k = (t, j, b): registers 8 j + 4 b .. + 3 of c3[t]
-                const int t = k >> 2, r0 = 8 * ((k >> 1) & 1) + 4 * (k & 1);
-                mask4(d1[t][r0], d1[t][r0 + 1], d1[t][r0 + 2], d1[t][r0 + 3], c3[t][r0], c3[t][r0 + 1], c3[t][r0 + 2], c3[t][r0 + 3], mw[k].x, mw[k].y);
-            }
             P3 eb[4];
             SplitState ss;
-            int blk = 0;   // 32 split blocks + 4 x 6 stores behind 48 MFMAs
-            auto filler = [&]() {
-                if (blk < 32) {
-                    const int s = blk >> 3;
-                    split_block(d1[s >> 1], s & 1, blk & 7, eb[s], ss);
-                    if ((blk & 7) == 7) store_pieces(IMG_D, s >> 1, s & 1, eb[s]);
-                }
-                ++blk;
+            auto d_work = [&](const int n) {
+                if (n == 0 || n == 1) d_mask(2 + n);
+                if (n == 20 || n == 21) d_mask(4 + n - 20);
+                if (n == 31 || n == 32) d_mask(6 + n - 31);
+                const int s = n < 11 ? 0 : n < 20 ? 1 : n < 31 ? 2 : 3, n0 = s == 0 ? 2 : s == 1 ? 11 : s == 2 ? 22 : 33;
+                if (n >= n0 && n < n0 + 8) split_block(d1[s >> 1], s & 1, n - n0, eb[s], ss);
+                if (n == n0 + 8) store_pieces(IMG_D, s >> 1, s & 1, eb[s]);
             };
-#pragma unroll
-            for (int t2 = 0; t2 < 2; ++t2)
-#pragma unroll
-                for (int s = 0; s < 2; ++s) {
-                    const P3& A = dA[t2][s];
-                    const P3 &B0 = hB[0][s], &B1 = hB[1][s];
-                    f32x16 &a0 = aW2[t2][0], &a1 = aW2[t2][1];
-                    X3S_MFMA32_A_AA(a0, A.p[2], B0.p[0]); filler(); X3S_MFMA32_A_AA(a1, A.p[2], B1.p[0]); filler();
-                    X3S_MFMA32_A_AA(a0, A.p[1], B0.p[1]); filler(); X3S_MFMA32_A_AA(a1, A.p[1], B1.p[1]); filler();
-                    X3S_MFMA32_A_AA(a0, A.p[0], B0.p[2]); filler(); X3S_MFMA32_A_AA(a1, A.p[0], B1.p[2]); filler();
-                    X3S_MFMA32_A_AA(a0, A.p[1], B0.p[0]); filler(); X3S_MFMA32_A_AA(a1, A.p[1], B1.p[0]); filler();
-                    X3S_MFMA32_A_AA(a0, A.p[0], B0.p[1]); filler(); X3S_MFMA32_A_AA(a1, A.p[0], B1.p[1]); filler();
-                    X3S_MFMA32_A_AA(a0, A.p[0], B0.p[0]); filler(); X3S_MFMA32_A_AA(a1, A.p[0], B1.p[0]); filler();
-                }
+            auto slot = [&](const int n) {
+                if (n == 36) landed();
+                if (n < 36) g2_step(n, dA, hB, aW2);
+                else if (n < 48) f1_mfma(n - 36);
+                else g2_step(n - 12, dA, hB, aW2);
+                d_work(n);
+                ahead_work(n, false);
+            };
+            X3S_REP10(slot, 0) X3S_REP10(slot, 10) X3S_REP10(slot, 20) X3S_REP10(slot, 30) X3S_REP10(slot, 40) X3S_REP10(slot, 50)
         }
-        landed();
         have_prev = true;
     }
     if (have_prev) {   // G1 of the last tile
-        const u32x4 xb[3] = {xbn[0], xbn[1], xbn[2]};
         G1Ops g1o;
 #pragma unroll
         for (int q = 0; q < 12; ++q) g1_gather_pair(g1o, q, h_base0, h_base1);
 #pragma unroll
-        for (int k = 0; k < 36; ++k) g1_step(k, g1o, xb, true);
+        for (int k = 0; k < 36; ++k) g1_step(k, g1o, xbn, true);
     }
 
     // ---- the lane partials -> sums over the 32 sample lanes of each half, through the wave's (now free) images
