@@ -104,6 +104,42 @@ int navppo_mlp64_update_epoch(float* params_dev, const void* obs_dev, int32_t ob
                               float* adam_v_dev, float* grad_dev, float* stats_dev, void* workspace_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------------
+ * Update epochs with gradient-norm clipping and a non-finite guard ON THE DEVICE (the epochs of an update are queued without a host
+ * round trip, so the host cannot guard them): navppo_mlp64_update_epoch_clipped, navppo_mlp64_bf16x3_update_epoch_clipped and
+ * navppo_resmlp512_update_epoch_clipped take their unclipped twins' arguments plus `max_norm` and `clip_stats_dev` in front of
+ * `stream`; navppo_adam_step_clipped is the multi-GPU form.  The same pass kernels produce the partial rows; the reduction then only
+ * sums them and a second small launch clips and steps.  Per NET (the reference clips and steps the two nets separately,
+ * ppo.py:352,381 / :389,392):
+ *   1. s = the float32 sum of squares of the net's summed (and scaled) gradient, added in one fixed order.
+ *   2. s not finite (NaN, or overflow to inf): the net's parameters and both its moments are NOT WRITTEN, its coefficient is reported
+ *      as 0 and its slice of grad_dev keeps the unclipped sum.  The caller's `step` advances all the same: the host learns of a skipped
+ *      step only from clip_stats_dev, i.e. after a synchronisation of its own -- a net that skipped k steps has taken k fewer Adam
+ *      steps than `step` says (its bias corrections are those of `step`).
+ *   3. else coef = min(1, max_norm / (sqrt(s) + 1e-6)) -- torch.nn.utils.clip_grad_norm_ -- and Adam runs on g * coef, with the very
+ *      expression of the unclipped epochs: max_norm = +inf gives their bits.
+ *   grad_dev        out: the CLIPPED gradient (what .grad holds after torch's call)
+ *   clip_stats_dev  [4] f32 out: s_actor, s_critic, coef_actor, coef_critic of THIS call (no lag, no dependence on call parity)
+ *   stats_dev       [0..2] and [4] as navppo_mlp64_loss_grad; [3] and [7] are unspecified
+ *   max_norm        > 0, +inf allowed; 0, negative or NaN: -1.  clip_stats_dev NULL: -1.
+ * Workspaces are those of the unclipped entry points (the squared-norm slots are shared): do not interleave clipped and unclipped
+ * epochs on one workspace if stats_dev[3] / [7] of the unclipped ones are read.
+ */
+int navppo_mlp64_update_epoch_clipped(float* params_dev, const void* obs_dev, int32_t obs_dim, int32_t obs_f16, const float* act_dev,
+                                      const float* logp_old_dev, const float* rtg_dev, const float* adv_dev, int64_t n_samples, float var,
+                                      float clip, float lr, float beta1, float beta2, float eps, int32_t step, float* adam_m_dev,
+                                      float* adam_v_dev, float* grad_dev, float* stats_dev, void* workspace_dev, float max_norm,
+                                      float* clip_stats_dev, void* stream);
+
+/*
+ * navppo_adam_step with the contract above: grad_dev [n] holds the all-reduced SUM; the norms are those of grad_dev x grad_scale, taken
+ * separately over [0, n_first) (the actor) and [n_first, n) (the critic); 0 <= n_first <= n (an empty segment has s = 0, coefficient 1).
+ * grad_dev receives grad x grad_scale x coef.
+ */
+int navppo_adam_step_clipped(float* params_dev, float* grad_dev, float* adam_m_dev, float* adam_v_dev, int64_t n, int64_t n_first,
+                             float grad_scale, float max_norm, float lr, float beta1, float beta2, float eps, int32_t step,
+                             float* clip_stats_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------------
  * The same update (ppo.py:305-397; 16- or 42-column rows, float32 or float16) with every matrix product evaluated on the bf16 MFMA from operands split into
  * three bf16 pieces -- "bf16x3": a = a0 + a1 + a2 exactly (8 + 8 + 8 significand bits), a b ~ the six leading piece products,
  * each exact in float32, float32 accumulation, small terms first.  float32-equivalent by measurement (against float64 the
@@ -130,6 +166,13 @@ int navppo_mlp64_bf16x3_update_epoch(float* params_dev, const void* prep_dev, in
                                      const float* rtg_dev, const float* adv_dev, int64_t n_samples, float var, float clip, float lr,
                                      float beta1, float beta2, float eps, int32_t step, float* adam_m_dev, float* adam_v_dev,
                                      float* grad_dev, float* stats_dev, void* workspace_dev, void* stream);
+
+/* navppo_mlp64_bf16x3_update_epoch with clipping and the non-finite guard: see navppo_mlp64_update_epoch_clipped */
+int navppo_mlp64_bf16x3_update_epoch_clipped(float* params_dev, const void* prep_dev, int32_t obs_dim, const float* act_dev,
+                                             const float* logp_old_dev, const float* rtg_dev, const float* adv_dev, int64_t n_samples, float var,
+                                             float clip, float lr, float beta1, float beta2, float eps, int32_t step, float* adam_m_dev,
+                                             float* adam_v_dev, float* grad_dev, float* stats_dev, void* workspace_dev, float max_norm,
+                                             float* clip_stats_dev, void* stream);
 
 /*
  * PPO.get_action() (ppo.py:673-706) for all envs of a shard in one launch: mean = actor(obs) (net_actor forward),
@@ -180,6 +223,13 @@ int navppo_resmlp512_update_epoch(float* params_dev, const void* obs_dev, int32_
                                   const float* rtg_dev, const float* adv_dev, int64_t n_samples, float var, float clip, float lr,
                                   float beta1, float beta2, float eps, int32_t step, float* adam_m_dev, float* adam_v_dev,
                                   float* grad_dev, float* stats_dev, void* workspace_dev, void* stream);
+
+/* navppo_resmlp512_update_epoch with clipping and the non-finite guard: see navppo_mlp64_update_epoch_clipped */
+int navppo_resmlp512_update_epoch_clipped(float* params_dev, const void* obs_dev, int32_t obs_f16, const float* act_dev, const float* logp_old_dev,
+                                          const float* rtg_dev, const float* adv_dev, int64_t n_samples, float var, float clip, float lr,
+                                          float beta1, float beta2, float eps, int32_t step, float* adam_m_dev, float* adam_v_dev,
+                                          float* grad_dev, float* stats_dev, void* workspace_dev, float max_norm, float* clip_stats_dev,
+                                          void* stream);
 
 /* V = critic(obs).squeeze() (ppo.py:275, :724); critic_params_dev [50257] (8-byte aligned suffices), value_dev [n] */
 int navppo_resmlp512_value(const float* critic_params_dev, const void* obs_dev, int32_t obs_f16, int64_t n_samples, float* value_dev,

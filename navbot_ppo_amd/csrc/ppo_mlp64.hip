@@ -1324,12 +1324,7 @@ __global__ __launch_bounds__(64 * kRedGroups) void reduce_adam(const float* __re
         for (int k = 0; k < kRedGroups; ++k) gr += part[k][lane];
         grad[q] = gr;
         if (ADAM) {
-            const float mm = m[q] + (gr - m[q]) * (1.0f - beta1);          // exp_avg.lerp_(grad, 1 - beta1)
-            const float vv = beta2 * v[q] + (1.0f - beta2) * (gr * gr);    // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
-            m[q] = mm;
-            v[q] = vv;
-            const float denom = sqrtf(vv) / bc2_sqrt + eps;
-            params[q] -= (lr / bc1) * (mm / denom);
+            navppo_adam_apply(params, m, v, q, gr, lr, beta1, beta2, eps, bc1, bc2_sqrt);
         }
     }
     if (parity >= 0 && g == 0) {
@@ -1370,12 +1365,90 @@ __global__ void adam_step_kernel(float* __restrict__ params, const float* __rest
                                  float bc1, float bc2_sqrt) {
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= n) return;
-    const float gr = grad[q] * grad_scale;
-    const float mm = m[q] + (gr - m[q]) * (1.0f - beta1);
-    const float vv = beta2 * v[q] + (1.0f - beta2) * (gr * gr);
-    m[q] = mm;
-    v[q] = vv;
-    params[q] -= (lr / bc1) * (mm / (sqrtf(vv) / bc2_sqrt + eps));
+    navppo_adam_apply(params, m, v, q, grad[q] * grad_scale, lr, beta1, beta2, eps, bc1, bc2_sqrt);
+}
+
+// ---------------------------------------------------------------- clipped steps (navppo_*_clipped)
+// A clipped step needs the whole net's norm before the first parameter moves, so it is a launch of its own behind the reduction: every
+// block adds up the squared-norm slots the reduction's blocks left (reduce_adam<false> / resmlp_reduce<false> with parity 0) -- all of
+// them, in the same order, hence the same bits in every block; no block waits for another -- and then clips and steps its parameters.
+constexpr int kClipThreads = 256;
+__device__ __forceinline__ float clip_block_sum(float s, float (&red)[kClipThreads / 64]) {   // fixed order: lanes, then waves
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
+    __syncthreads();   // (red is reused)
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    float t = red[0];
+#pragma unroll
+    for (int k = 1; k < kClipThreads / 64; ++k) t += red[k];
+    return t;
+}
+// torch.nn.utils.clip_grad_norm_'s coefficient; 0 = the squared norm is not finite, the net must not be stepped
+__device__ __forceinline__ float clip_coef(float s, float max_norm) {
+    return isfinite(s) ? fminf(1.0f, max_norm / (sqrtf(s) + 1e-6f)) : 0.f;
+}
+__global__ __launch_bounds__(kClipThreads) void clip_adam_kernel(float* __restrict__ params, float* __restrict__ grad, float* __restrict__ m,
+                                                                 float* __restrict__ v, int n, int n_first, float grad_scale, float max_norm,
+                                                                 float lr, float beta1, float beta2, float eps, float bc1, float bc2_sqrt,
+                                                                 const float* slots, int n_slots, int slot_stride, int slot_pitch,
+                                                                 float* clip_stats) {
+    __shared__ float red[kClipThreads / 64];
+    float sa = 0.f, sc = 0.f;
+    for (int b = threadIdx.x; b < n_slots; b += kClipThreads) {
+        const int ja = b, jc = slot_stride + b;
+        sa += slots[(size_t)(ja >> 3) * slot_pitch + (ja & 7)];
+        sc += slots[(size_t)(jc >> 3) * slot_pitch + (jc & 7)];
+    }
+    sa = clip_block_sum(sa, red);
+    sc = clip_block_sum(sc, red);
+    const float ca = clip_coef(sa, max_norm), cc = clip_coef(sc, max_norm);
+    const int q = blockIdx.x * kClipThreads + threadIdx.x;
+    if (q < n) {
+        const bool actor = q < n_first;
+        if (isfinite(actor ? sa : sc)) {   // else: parameters and moments of this net are not written at all
+            const float gr = (grad[q] * grad_scale) * (actor ? ca : cc);
+            grad[q] = gr;
+            navppo_adam_apply(params, m, v, q, gr, lr, beta1, beta2, eps, bc1, bc2_sqrt);
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        if (slots != clip_stats) {   // (navppo_adam_step_clipped hands the squared norms over in clip_stats itself)
+            clip_stats[0] = sa;
+            clip_stats[1] = sc;
+        }
+        clip_stats[2] = ca;
+        clip_stats[3] = cc;
+    }
+}
+
+// navppo_adam_step_clipped: the squared norms of grad x grad_scale over [0, n_first) and [n_first, n) into out[0], out[1]; ONE block
+// (the buffer is 43 KB or 400 KB and an all-reduce ran just before), fixed order
+constexpr int kNormThreads = 1024;
+__global__ __launch_bounds__(kNormThreads) void sqnorm2_kernel(const float* __restrict__ grad, int n, int n_first, float grad_scale,
+                                                               float* __restrict__ out) {
+    __shared__ float red[2][kNormThreads / 64];
+    float sa = 0.f, sc = 0.f;
+    for (int q = threadIdx.x; q < n; q += kNormThreads) {
+        const float g = grad[q] * grad_scale;
+        if (q < n_first) sa += g * g;
+        else sc += g * g;
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        sa += __shfl_xor(sa, o, 64);
+        sc += __shfl_xor(sc, o, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        red[0][threadIdx.x >> 6] = sa;
+        red[1][threadIdx.x >> 6] = sc;
+    }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        float t = 0.f;
+        for (int k = 0; k < kNormThreads / 64; ++k) t += red[threadIdx.x][k];
+        out[threadIdx.x] = t;
+    }
 }
 
 // ---------------------------------------------------------------- rollout-time policy step (PPO.get_action, ppo.py:673-706)
@@ -1496,6 +1569,16 @@ thread_local std::string g_err;
 }  // namespace
 
 void navppo_set_error(const char* msg) { g_err = msg ? msg : ""; }
+
+void navppo_launch_clip_adam(float* params, float* grad, float* m, float* v, int n, int n_first, float grad_scale, float max_norm, float lr,
+                             float beta1, float beta2, float eps, int step, const float* slots, int n_slots, int slot_stride, int slot_pitch,
+                             float* clip_stats, void* stream) {
+    const float bc1 = (float)(1.0 - std::pow((double)beta1, (double)step));
+    const float bc2_sqrt = (float)std::sqrt(1.0 - std::pow((double)beta2, (double)step));
+    hipLaunchKernelGGL(clip_adam_kernel, dim3((unsigned)((n + kClipThreads - 1) / kClipThreads)), dim3(kClipThreads), 0, (hipStream_t)stream, params,
+                       grad, m, v, n, n_first, grad_scale, max_norm, lr, beta1, beta2, eps, bc1, bc2_sqrt, slots, n_slots, slot_stride, slot_pitch,
+                       clip_stats);
+}
 
 #pragma GCC visibility push(default)
 extern "C" {
@@ -1650,6 +1733,29 @@ int navppo_adam_step(float* params_dev, const float* grad_dev, float* adam_m_dev
     return 0;
 }
 
+int navppo_adam_step_clipped(float* params_dev, float* grad_dev, float* adam_m_dev, float* adam_v_dev, int64_t n, int64_t n_first,
+                             float grad_scale, float max_norm, float lr, float beta1, float beta2, float eps, int32_t step,
+                             float* clip_stats_dev, void* stream) {
+    if (!params_dev || !grad_dev || !adam_m_dev || !adam_v_dev || n < 1 || n > INT32_MAX || n_first < 0 || n_first > n || step < 1 || !clip_stats_dev) {
+        g_err = "navppo_adam_step_clipped: bad argument (0 <= n_first <= n, clip_stats_dev [4])";
+        return -1;
+    }
+    if (!navppo_max_norm_ok(max_norm)) {
+        g_err = "navppo_adam_step_clipped: max_norm must be > 0 (+inf allowed)";
+        return -1;
+    }
+    hipLaunchKernelGGL(sqnorm2_kernel, dim3(1), dim3(kNormThreads), 0, (hipStream_t)stream, (const float*)grad_dev, (int)n, (int)n_first, grad_scale,
+                       clip_stats_dev);
+    navppo_launch_clip_adam(params_dev, grad_dev, adam_m_dev, adam_v_dev, (int)n, (int)n_first, grad_scale, max_norm, lr, beta1, beta2, eps, step,
+                            clip_stats_dev, 1, 1, 8, clip_stats_dev, stream);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        g_err = std::string("navppo_adam_step_clipped: ") + hipGetErrorString(e);
+        return -2;
+    }
+    return 0;
+}
+
 int navppo_mlp64_value(const float* critic_params_dev, const void* obs_dev, int32_t obs_dim, int32_t obs_f16, int64_t n_samples,
                        float* value_dev, void* stream) {
     if (!critic_params_dev || !obs_dev || !value_dev || n_samples < 1 || (obs_dim != 16 && obs_dim != 42) ||
@@ -1706,6 +1812,46 @@ int navppo_mlp64_update_epoch(float* params_dev, const void* obs_dev, int32_t ob
     return 0;
 }
 
+int navppo_mlp64_update_epoch_clipped(float* params_dev, const void* obs_dev, int32_t obs_dim, int32_t obs_f16, const float* act_dev,
+                                      const float* logp_old_dev, const float* rtg_dev, const float* adv_dev, int64_t n_samples, float var,
+                                      float clip, float lr, float beta1, float beta2, float eps, int32_t step, float* adam_m_dev,
+                                      float* adam_v_dev, float* grad_dev, float* stats_dev, void* workspace_dev, float max_norm,
+                                      float* clip_stats_dev, void* stream) {
+    if (!navppo_max_norm_ok(max_norm) || !clip_stats_dev) {
+        g_err = "navppo_mlp64_update_epoch_clipped: max_norm must be > 0 (+inf allowed) and clip_stats_dev [4] not null";
+        return -1;
+    }
+    if (!params_dev || !obs_dev || !act_dev || !logp_old_dev || !rtg_dev || !adv_dev || !grad_dev || !stats_dev ||
+        !workspace_dev || !adam_m_dev || !adam_v_dev || n_samples < 1 || !(var > 0.f) || step < 1 || (obs_dim != 16 && obs_dim != 42)) {
+        g_err = "navppo_mlp64_update_epoch_clipped: bad argument (obs_dim is 16 or 42)";
+        return -1;
+    }
+    if (!obs_aligned(obs_dev, obs_dim, obs_f16) || ((uintptr_t)act_dev & 7)) {
+        g_err = "navppo_mlp64_update_epoch_clipped: obs must be 16-byte (42 columns: 8-byte, float16: 4-byte) and act 8-byte aligned";
+        return -1;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const PassPlan pl = plan_pass(workspace_dev, n_samples, obs_dim);
+    for_obs(obs_dim, obs_f16, [&](auto in, auto f16) {
+        hipLaunchKernelGGL((mlp64_pass_both<decltype(in)::value, decltype(f16)::value>), dim3(pl.blocks), dim3(64 * Pad<decltype(in)::value>::NW), 0, st, params_dev,
+                           obs_dev, act_dev, logp_old_dev, rtg_dev, adv_dev, (long long)n_samples, var, clip, pl.inv_n, pl.partial,
+                           pl.stats_partial, pl.partial_c, pl.stats_partial_c, grad_dev, stats_dev);
+    });
+    // the reduction alone, its blocks' squared-norm slots in parity 0 (stats[3] / [7]: unspecified); then the norms, the clip and Adam
+    const int rblocks = (pl.pa + pl.pc + 63) / 64;
+    hipLaunchKernelGGL(reduce_adam<false>, dim3(rblocks), dim3(64 * kRedGroups), 0, st, pl.partial, pl.stats_partial, pl.partial_c,
+                       pl.stats_partial_c, pl.blocks, pl.inv_n, grad_dev, stats_dev, nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, 0.f, 1.f, 1.f,
+                       pl.pa, pl.pc, 0, pl.pa + pl.pc, pl.gn, 0);
+    navppo_launch_clip_adam(params_dev, grad_dev, adam_m_dev, adam_v_dev, pl.pa + pl.pc, pl.pa, 1.0f, max_norm, lr, beta1, beta2, eps, step, pl.gn,
+                            rblocks, kGnSlots, 8, clip_stats_dev, stream);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        g_err = std::string("navppo_mlp64_update_epoch_clipped: ") + hipGetErrorString(e);
+        return -2;
+    }
+    return 0;
+}
+
 size_t navppo_mlp64_bf16x3_prep_bytes(int64_t n_samples, int32_t obs_dim) {
     if (n_samples < 1 || (obs_dim != 16 && obs_dim != 42)) return 0;
     return (size_t)((n_samples + 31) / 32) * (obs_dim == 16 ? XPad<16>::kTileBytes : XPad<42>::kTileBytes);
@@ -1734,7 +1880,7 @@ int navppo_mlp64_bf16x3_prepare(const void* obs_dev, int32_t obs_dim, int32_t ob
 static int x3_epoch(const char* who, float* params_dev, const void* prep_dev, int32_t obs_dim, const float* act_dev, const float* logp_old_dev,
                     const float* rtg_dev, const float* adv_dev, int64_t n_samples, float var, float clip, int net_mask, int32_t step,
                     float lr, float beta1, float beta2, float eps, float* adam_m_dev, float* adam_v_dev, float* grad_dev,
-                    float* stats_dev, void* workspace_dev, void* stream) {
+                    float* stats_dev, void* workspace_dev, void* stream, float max_norm = 0.f, float* clip_stats_dev = nullptr) {
     if (!params_dev || !prep_dev || !act_dev || !logp_old_dev || !rtg_dev || !adv_dev || !grad_dev || !stats_dev || !workspace_dev ||
         n_samples < 1 || !(var > 0.f) || (obs_dim != 16 && obs_dim != 42) || ((uintptr_t)prep_dev & 15) || ((uintptr_t)act_dev & 7)) {
         g_err = std::string(who) + ": bad argument (obs_dim is 16 or 42; prep 16-byte, act 8-byte aligned)";
@@ -1755,7 +1901,13 @@ static int x3_epoch(const char* who, float* params_dev, const void* prep_dev, in
                            reinterpret_cast<const unsigned char*>(prep_dev), act_dev, logp_old_dev, rtg_dev, adv_dev, (long long)n_samples, var, clip,
                            pl.inv_n, net_mask, pl.partial, pl.stats_partial, pl.partial_c, pl.stats_partial_c);
     const int q0 = (net_mask & 1) ? 0 : pl.pa, q1 = (net_mask & 2) ? pl.pa + pl.pc : pl.pa;
-    if (step >= 1) {
+    if (clip_stats_dev) {   // (both nets, step >= 1) the reduction alone with this epoch's squared-norm slots, then the norms, the clip and Adam
+        hipLaunchKernelGGL(reduce_adam<false>, dim3((q1 - q0 + 63) / 64), dim3(64 * kRedGroups), 0, st, pl.partial, pl.stats_partial, pl.partial_c,
+                           pl.stats_partial_c, pl.blocks, pl.inv_n, grad_dev, stats_dev, nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, 0.f, 1.f,
+                           1.f, pl.pa, pl.pc, q0, q1, pl.gn, 0);
+        navppo_launch_clip_adam(params_dev, grad_dev, adam_m_dev, adam_v_dev, pl.pa + pl.pc, pl.pa, 1.0f, max_norm, lr, beta1, beta2, eps, step, pl.gn,
+                                (q1 - q0 + 63) / 64, kGnSlots, 8, clip_stats_dev, stream);
+    } else if (step >= 1) {
         const float bc1 = (float)(1.0 - std::pow((double)beta1, (double)step));
         const float bc2_sqrt = (float)std::sqrt(1.0 - std::pow((double)beta2, (double)step));
         hipLaunchKernelGGL(reduce_adam<true>, dim3((q1 - q0 + 63) / 64), dim3(64 * kRedGroups), 0, st, pl.partial, pl.stats_partial, pl.partial_c,
@@ -1802,6 +1954,20 @@ int navppo_mlp64_bf16x3_update_epoch(float* params_dev, const void* prep_dev, in
     }
     return x3_epoch("navppo_mlp64_bf16x3_update_epoch", params_dev, prep_dev, obs_dim, act_dev, logp_old_dev, rtg_dev, adv_dev, n_samples, var, clip,
                     3, step, lr, beta1, beta2, eps, adam_m_dev, adam_v_dev, grad_dev, stats_dev, workspace_dev, stream);
+}
+
+int navppo_mlp64_bf16x3_update_epoch_clipped(float* params_dev, const void* prep_dev, int32_t obs_dim, const float* act_dev,
+                                             const float* logp_old_dev, const float* rtg_dev, const float* adv_dev, int64_t n_samples, float var,
+                                             float clip, float lr, float beta1, float beta2, float eps, int32_t step, float* adam_m_dev,
+                                             float* adam_v_dev, float* grad_dev, float* stats_dev, void* workspace_dev, float max_norm,
+                                             float* clip_stats_dev, void* stream) {
+    if (step < 1 || !adam_m_dev || !adam_v_dev || !navppo_max_norm_ok(max_norm) || !clip_stats_dev) {
+        g_err = "navppo_mlp64_bf16x3_update_epoch_clipped: bad argument (max_norm must be > 0, +inf allowed; clip_stats_dev [4] not null)";
+        return -1;
+    }
+    return x3_epoch("navppo_mlp64_bf16x3_update_epoch_clipped", params_dev, prep_dev, obs_dim, act_dev, logp_old_dev, rtg_dev, adv_dev, n_samples, var,
+                    clip, 3, step, lr, beta1, beta2, eps, adam_m_dev, adam_v_dev, grad_dev, stats_dev, workspace_dev, stream, max_norm,
+                    clip_stats_dev);
 }
 
 int navppo_episode_sums(const uint8_t* ended_dev, const uint8_t* arrive_dev, const uint8_t* done_dev, const int32_t* ep_length_dev,

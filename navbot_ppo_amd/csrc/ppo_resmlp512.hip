@@ -1060,11 +1060,7 @@ __global__ __launch_bounds__(64 * kRedGroups) void resmlp_reduce(const float* __
         for (int k = 0; k < kRedGroups; ++k) gr += part[k][lane];
         grad[qi] = gr;
         if (ADAM) {
-            const float mm = m[qi] + (gr - m[qi]) * (1.0f - beta1);          // exp_avg.lerp_(grad, 1 - beta1)
-            const float vv = beta2 * v[qi] + (1.0f - beta2) * (gr * gr);     // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
-            m[qi] = mm;
-            v[qi] = vv;
-            params[qi] -= (lr / bc1) * (mm / (sqrtf(vv) / bc2_sqrt + eps));
+            navppo_adam_apply(params, m, v, qi, gr, lr, beta1, beta2, eps, bc1, bc2_sqrt);
         }
     }
     if (parity >= 0 && g == 0) {
@@ -1189,7 +1185,8 @@ void launch_forward(const Plan& p, const float* params, int net_base, int n_nets
 
 int loss_grad_impl(const char* name, bool adam, float* params, const void* obs, int32_t obs_f16, const float* act, const float* logp_old,
                    const float* rtg, const float* adv, int64_t n, float var, float clip, float lr, float beta1, float beta2,
-                   float eps, int32_t step, float* adam_m, float* adam_v, float* grad, float* stats, void* ws, void* stream) {
+                   float eps, int32_t step, float* adam_m, float* adam_v, float* grad, float* stats, void* ws, void* stream,
+                   float max_norm = 0.f, float* clip_stats = nullptr) {
     if (!params || !obs || !act || !logp_old || !rtg || !adv || !grad || !stats || !ws || n < 1 || !(var > 0.f) ||
         (adam && (!adam_m || !adam_v || step < 1))) {
         g_err = std::string(name) + ": bad argument";
@@ -1219,7 +1216,13 @@ int loss_grad_impl(const char* name, bool adam, float* params, const void* obs, 
     hipLaunchKernelGGL((resmlp_bwd<16, 2, kBwd1Waves>), dim3(p.wgs), dim3(64 * kBwd1Waves), 0, st, (const float*)params, 2, obs, (const float*)p.h1,
                        (const float*)p.dy2, (long long)n, p.groups, p.wpart, (float*)nullptr, (const float*)p.qb, f16);
     const int rblocks = (rp::P_ACTOR + rp::P_CRITIC + 63) / 64;
-    if (adam) {
+    if (clip_stats) {   // the reduction alone, its blocks' squared-norm slots in parity 0; then the norms, the clip and Adam (clip_adam_kernel)
+        hipLaunchKernelGGL(resmlp_reduce<false>, dim3(rblocks), dim3(64 * kRedGroups), 0, st, (const float*)p.wpart, p.groups * kBwd1Waves,
+                           p.groups * kBwd2Waves, (const float*)p.epart, p.e_blocks, inv_n, grad, stats, (float*)nullptr, (float*)nullptr, (float*)nullptr, 0.f,
+                           0.f, 0.f, 0.f, 1.f, 1.f, p.epart, 0);
+        navppo_launch_clip_adam(params, grad, adam_m, adam_v, rp::P_ACTOR + rp::P_CRITIC, rp::P_ACTOR, 1.0f, max_norm, lr, beta1, beta2, eps, step,
+                                p.epart, rblocks, kGnSlotsR, EP, clip_stats, stream);
+    } else if (adam) {
         const float bc1 = (float)(1.0 - std::pow((double)beta1, (double)step));
         const float bc2_sqrt = (float)std::sqrt(1.0 - std::pow((double)beta2, (double)step));
         hipLaunchKernelGGL(resmlp_reduce<true>, dim3(rblocks), dim3(64 * kRedGroups), 0, st, (const float*)p.wpart, p.groups * kBwd1Waves,
@@ -1257,6 +1260,22 @@ int navppo_resmlp512_update_epoch(float* params_dev, const void* obs_dev, int32_
     const int rc = loss_grad_impl("navppo_resmlp512_update_epoch", true, params_dev, obs_dev, obs_f16, act_dev, logp_old_dev, rtg_dev, adv_dev,
                                   n_samples, var, clip, lr, beta1, beta2, eps, step, adam_m_dev, adam_v_dev, grad_dev, stats_dev,
                                   workspace_dev, stream);
+    if (rc != 0) navppo_set_error(g_err.c_str());
+    return rc;
+}
+
+int navppo_resmlp512_update_epoch_clipped(float* params_dev, const void* obs_dev, int32_t obs_f16, const float* act_dev, const float* logp_old_dev,
+                                          const float* rtg_dev, const float* adv_dev, int64_t n_samples, float var, float clip, float lr,
+                                          float beta1, float beta2, float eps, int32_t step, float* adam_m_dev, float* adam_v_dev,
+                                          float* grad_dev, float* stats_dev, void* workspace_dev, float max_norm, float* clip_stats_dev,
+                                          void* stream) {
+    if (!navppo_max_norm_ok(max_norm) || !clip_stats_dev) {
+        navppo_set_error("navppo_resmlp512_update_epoch_clipped: max_norm must be > 0 (+inf allowed) and clip_stats_dev [4] not null");
+        return -1;
+    }
+    const int rc = loss_grad_impl("navppo_resmlp512_update_epoch_clipped", true, params_dev, obs_dev, obs_f16, act_dev, logp_old_dev, rtg_dev,
+                                  adv_dev, n_samples, var, clip, lr, beta1, beta2, eps, step, adam_m_dev, adam_v_dev, grad_dev, stats_dev,
+                                  workspace_dev, stream, max_norm, clip_stats_dev);
     if (rc != 0) navppo_set_error(g_err.c_str());
     return rc;
 }

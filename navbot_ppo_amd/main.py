@@ -11,7 +11,8 @@ Same flag names and defaults; what they mean on the batched simulator:
   --tiny_debug_run        20-step episodes / 40-step batches / 400 total steps (arguments.py:58-65)
   --use_external_sampler  start/goal from the curated GoalSpawnSampler tables (parsed but never wired in the reference)
 Additions (not in the reference): --n_envs, --policy, --map, --seed, --eval_persistent (with --eval: one launch instead of the
-stepping loop), --eval_every K (training: a persistent evaluation of --eval_episodes episodes every K iterations).  Vision flags are accepted and refused (the camera
+stepping loop), --eval_every K (training: a persistent evaluation of --eval_episodes episodes every K iterations), --max_grad_norm
+(per-net gradient clipping + non-finite guard inside the update).  Vision flags are accepted and refused (the camera
 modality is outside the LiDAR hot path); --mode test maps to --eval (the reference's test path is broken).
 """
 import argparse
@@ -48,6 +49,9 @@ def get_args(argv=None):
     p.add_argument("--eval_every", type=int, default=0,
                    help="training: every this many iterations, a persistent deterministic evaluation of --eval_episodes episodes "
                         "(arrival threshold 0.4) on a second set of envs; 0 = off")
+    p.add_argument("--max_grad_norm", type=float, default=None,
+                   help="clip each net's gradient to this L2 norm in every epoch and skip a net's step when its gradient is not finite "
+                        "(on the device, inside the fused update); default: off, as in the reference")
     args = p.parse_args(argv)
     if args.output_dir is None:
         args.output_dir = os.path.join(os.getcwd(), "runs")
@@ -106,7 +110,7 @@ def main(argv=None):
                  seed=args.seed, env_id_base=lo, device=ctx.device, sampler=sampler)
     cfg = ppo.PPOConfig(rollout_len=rollout, max_episode_steps=args.timesteps_per_episode, policy=args.policy, seed=args.seed,
                         save_freq=args.save_every_iterations, output_dir=args.output_dir, method_name=args.method_name,
-                        eval_every=args.eval_every, eval_episodes=args.eval_episodes)
+                        eval_every=args.eval_every, eval_episodes=args.eval_episodes, max_grad_norm=args.max_grad_norm)
     trainer = ppo.PPOTrainer(env, cfg, ctx)
     if args.resume or args.actor_model:  # main.py:52-89
         pa = args.actor_model or ev.find_latest_checkpoint(args.output_dir, args.method_name, "actor")

@@ -9,7 +9,9 @@ Follows ``project_ppo/src/ppo.py`` of the reference function by function, vector
   evaluate         ppo.py:708-737
   update           ppo.py:275-397   A = rtg - V, normalised with the unbiased std (+1e-10); 50 full-batch
                                     epochs of clipped surrogate + MSE critic, Adam(lr 3e-4), no entropy
-                                    term, no value clip, no gradient clipping
+                                    term, no value clip, no gradient clipping (PPOConfig.max_grad_norm
+                                    turns on per-net clipping + a non-finite guard; the gradient-norm
+                                    check of ppo.py:356-379,414-416 is PPOTrainer._grad_guard)
   learn            ppo.py:218-461   iteration loop, timing, checkpoints (actor_iter%04d_step%08d.pth)
 
 Multi-GPU (absent in the reference): one process per GPU, each owns a contiguous shard
@@ -61,6 +63,10 @@ class PPOConfig:
     # pass launches pay the ramp / staging / reduction of the fused one twice -- more than a 43 KB all-reduce costs on the wire);
     # True = two-stage pipeline, each net's all-reduce under the other net's pass (_pipelined_epochs): hides the wire entirely
     overlap_allreduce: bool = False
+    # None = the reference (its clip_grad_norm_(inf) calls only measure, ppo.py:352,389).  A number: in every epoch each net's
+    # gradient is clipped to this L2 norm (torch's clip_grad_norm_) before its Adam step, and a net whose gradient is not finite
+    # is not stepped at all (parameters and Adam moments untouched) -- on the device, inside the fused update (navppo_*_clipped)
+    max_grad_norm: float = None
     output_dir: str = ""                   # "" = no checkpoints / logs
     episode_csv_rows: int = 2000           # per-iteration cap on rows appended to <method>_train_episodes.csv (0 = off)
     tb_episode_rows: int = 256             # per-iteration cap on Episode_Rewards/train points in the TensorBoard file (0 = off)
@@ -231,6 +237,10 @@ class PPOUpdater:
         self.obs_dim = actor.layer1.in_features if isinstance(actor, nets.MLP64Actor) else actor.rb1.f_in
         if cfg.update_arith not in ("f32", "bf16x3"):
             raise ValueError(f"update_arith {cfg.update_arith!r}: 'f32' or 'bf16x3'")
+        if cfg.max_grad_norm is not None and not float(cfg.max_grad_norm) > 0.0:   # (NaN fails the comparison too)
+            raise ValueError(f"max_grad_norm {cfg.max_grad_norm!r}: None (off) or a number > 0")
+        self.max_norm = None if cfg.max_grad_norm is None else float(cfg.max_grad_norm)
+        self.clip_stats = None   # clipping on: [n_ep, 4] (s_actor, s_critic, coef_actor, coef_critic) of the last update(), on the device
         self.fused_resmlp512 = (on_gpu and cfg.policy == "resmlp512" and isinstance(actor, nets.ResMLPActor)
                                 and actor.rb1.f_in == 16 and actor.rb1.fc1.out_features == 512)
         if self.fused_resmlp512 and cfg.update_arith == "f32":
@@ -343,8 +353,9 @@ class PPOUpdater:
         if rc != 0:
             raise RuntimeError(f"navppo_mlp64_loss_grad_net failed: {L.navppo_last_error().decode()}")
 
-    def _fused_adam(self, grad_scale, lo=0, n=None, step=None):
-        """Scale + Adam on the flat buffer, or on the slice [lo, lo + n) at optimiser step `step` (one net of the pipelined epoch)."""
+    def _fused_adam(self, grad_scale, lo=0, n=None, step=None, cstats=None):
+        """Scale + Adam on the flat buffer, or on the slice [lo, lo + n) at optimiser step `step` (one net of the pipelined epoch).
+        cstats ([4], clipping on): navppo_adam_step_clipped -- per-net norm, guard and clip of the scaled gradient first."""
         import ctypes as C
         from ._native import lib
         L = lib()
@@ -352,6 +363,15 @@ class PPOUpdater:
         if step is None:
             self._adam_t += 1
             step = self._adam_t
+        if cstats is not None:
+            n_ = int(self.fp.numel - lo if n is None else n)
+            rc = L.navppo_adam_step_clipped(ptr(self.fp.flat), ptr(self.fp.grad), ptr(self._adam_m), ptr(self._adam_v), n_,
+                                            max(0, min(n_, self._n_actor - lo)), float(grad_scale), self.max_norm, float(self.cfg.lr),
+                                            0.9, 0.999, 1e-8, int(step), C.c_void_p(cstats.data_ptr()),
+                                            C.c_void_p(torch.cuda.current_stream().cuda_stream))
+            if rc != 0:
+                raise RuntimeError(f"navppo_adam_step_clipped failed: {L.navppo_last_error().decode()}")
+            return
         rc = L.navppo_adam_step(ptr(self.fp.flat), ptr(self.fp.grad), ptr(self._adam_m), ptr(self._adam_v),
                                 int(self.fp.numel - lo if n is None else n), float(grad_scale), float(self.cfg.lr), 0.9, 0.999, 1e-8,
                                 int(step), C.c_void_p(torch.cuda.current_stream().cuda_stream))
@@ -370,6 +390,8 @@ class PPOUpdater:
         wa = wc = None
         gn_sq = torch.zeros((max(n_ep, 1), 2), device=obs.device)   # every epoch's squared norms of the summed (actor, critic) gradient
         ga, gc = self.fp.grad[:n_a], self.fp.grad[n_a:]
+        if self.max_norm is not None:   # each net's clipped step reports into its own row; its net's columns are gathered at the end
+            return self._pipelined_epochs_clipped(n_ep, world, obs, acts, logp_old, rtg, adv, var_f)
         for ep in range(n_ep):
             if wa is not None:   # epoch ep - 1's actor gradient has arrived (long ago: it had the critic's pass to do so)
                 wa.wait()
@@ -393,6 +415,33 @@ class PPOUpdater:
         self._adam_t = t0 + n_ep
         return gn_sq / float(world) ** 2
 
+    def _pipelined_epochs_clipped(self, n_ep, world, obs, acts, logp_old, rtg, adv, var_f):
+        """_pipelined_epochs with navppo_adam_step_clipped per net: same order of launches and all-reduces; fills self.clip_stats."""
+        n_a = self._n_actor
+        n_c = self.fp.numel - n_a
+        t0 = self._adam_t
+        wa = wc = None
+        cs2 = torch.zeros((max(n_ep, 1), 2, 4), dtype=torch.float32, device=obs.device)
+        for ep in range(n_ep):
+            if wa is not None:
+                wa.wait()
+                self._fused_adam(1.0 / world, 0, n_a, t0 + ep, cstats=cs2[ep - 1, 0])
+            self._fused_loss_grad_net(0, obs, acts, logp_old, rtg, adv, var_f, self._fhist[ep])
+            wa = dist.all_reduce(self.fp.grad[:n_a], op=dist.ReduceOp.SUM, async_op=True)
+            if wc is not None:
+                wc.wait()
+                self._fused_adam(1.0 / world, n_a, n_c, t0 + ep, cstats=cs2[ep - 1, 1])
+            self._fused_loss_grad_net(1, obs, acts, logp_old, rtg, adv, var_f, self._fhist[ep])
+            wc = dist.all_reduce(self.fp.grad[n_a:], op=dist.ReduceOp.SUM, async_op=True)
+        if wa is not None:
+            wa.wait()
+            self._fused_adam(1.0 / world, 0, n_a, t0 + n_ep, cstats=cs2[n_ep - 1, 0])
+            wc.wait()
+            self._fused_adam(1.0 / world, n_a, n_c, t0 + n_ep, cstats=cs2[n_ep - 1, 1])
+        self._adam_t = t0 + n_ep
+        self.clip_stats = torch.stack([cs2[:n_ep, 0, 0], cs2[:n_ep, 1, 1], cs2[:n_ep, 0, 2], cs2[:n_ep, 1, 3]], 1)
+        return self.clip_stats[:, :2]   # squared norms of the MEAN gradient, per epoch and net
+
     def _fused_value(self, obs):
         """V = critic(obs).squeeze() (ppo.py:275) by the forward half of the critic's fused pass."""
         import ctypes as C
@@ -410,21 +459,50 @@ class PPOUpdater:
             raise RuntimeError(f"{self.fused}_value failed: {L.navppo_last_error().decode()}")
         return out
 
-    def _fused_epoch(self, obs, acts, logp_old, rtg, adv, var, stats):
-        """One epoch of ppo.py:305-392 on one GPU: losses, gradients and both Adam steps in four launches."""
+    def _fused_epoch(self, obs, acts, logp_old, rtg, adv, var, stats, cstats=None):
+        """One epoch of ppo.py:305-392 on one GPU: losses, gradients and both Adam steps in four launches.  cstats ([4], clipping on):
+        the *_update_epoch_clipped entry point -- one more small launch that clips and steps behind the reduction."""
         import ctypes as C
         from ._native import lib
         L = lib()
         ptr = lambda t: C.c_void_p(t.data_ptr())
         self._adam_t += 1
         name, oargs = (("navppo_mlp64_bf16x3", (self._prepared(obs), self.obs_dim)) if self.bf16x3 else (self.fused, self._obs_args(obs)))
-        rc = getattr(L, name + "_update_epoch")(ptr(self.fp.flat), *oargs, ptr(acts), ptr(logp_old), ptr(rtg), ptr(adv),
-                                                      int(obs.shape[0]), float(var), float(self.cfg.clip), float(self.cfg.lr), 0.9,
-                                                      0.999, 1e-8, int(self._adam_t), ptr(self._adam_m), ptr(self._adam_v),
-                                                      ptr(self.fp.grad), ptr(stats), ptr(self._workspace(obs.shape[0])),
-                                                      C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        clipped = () if cstats is None else (self.max_norm, ptr(cstats))
+        entry = name + ("_update_epoch" if cstats is None else "_update_epoch_clipped")
+        rc = getattr(L, entry)(ptr(self.fp.flat), *oargs, ptr(acts), ptr(logp_old), ptr(rtg), ptr(adv),
+                               int(obs.shape[0]), float(var), float(self.cfg.clip), float(self.cfg.lr), 0.9,
+                               0.999, 1e-8, int(self._adam_t), ptr(self._adam_m), ptr(self._adam_v),
+                               ptr(self.fp.grad), ptr(stats), ptr(self._workspace(obs.shape[0])), *clipped,
+                               C.c_void_p(torch.cuda.current_stream().cuda_stream))
         if rc != 0:
-            raise RuntimeError(f"{self.fused}_update_epoch failed: {L.navppo_last_error().decode()}")
+            raise RuntimeError(f"{entry} failed: {L.navppo_last_error().decode()}")
+
+    def _clip_and_step(self, ep):
+        """The PyTorch formulation of a clipped epoch's optimiser step (the CPU / gloo path and the tests' float32 reference), the
+        contract of the navppo_*_clipped entry points per net: s = sum of squares of the net's gradient; s not finite: that net's
+        slice of the parameters and of Adam's exp_avg / exp_avg_sq is restored after the step (the step counter advances), its
+        coefficient is 0 and its gradient stays unclipped; else the gradient is scaled by min(1, max_norm / (sqrt(s) + 1e-6))."""
+        n_a, cs = self.fp.module_numel[0], self.clip_stats
+        oks = []
+        with torch.no_grad():
+            for k, (lo, hi) in enumerate(((0, n_a), (n_a, self.fp.numel))):
+                g = self.fp.grad[lo:hi]
+                sq = (g * g).sum()
+                ok = torch.isfinite(sq)
+                coef = torch.where(ok, torch.clamp(self.max_norm / (sq.sqrt() + 1e-6), max=1.0), torch.zeros_like(sq))
+                g.mul_(torch.where(ok, coef, torch.ones_like(coef)))
+                cs[ep, k], cs[ep, 2 + k] = sq, coef
+                oks.append(ok)
+            st = self.opt.state.get(self.fp.proxy, {})
+            keys = ("exp_avg", "exp_avg_sq")
+            old = [self.fp.flat.clone()] + [st[key].clone() if key in st else torch.zeros_like(self.fp.flat) for key in keys]
+        self.opt.step()
+        with torch.no_grad():
+            st = self.opt.state[self.fp.proxy]
+            for k, (lo, hi) in enumerate(((0, n_a), (n_a, self.fp.numel))):
+                for cur, was in zip([self.fp.flat] + [st[key] for key in keys], old):
+                    cur[lo:hi].copy_(torch.where(oks[k], cur[lo:hi], was[lo:hi]))
 
     def value(self, obs):
         """V = critic(obs).squeeze() (ppo.py:275) for [n, D] rows."""
@@ -460,6 +538,10 @@ class PPOUpdater:
                 self.prepare(obs)   # ALWAYS here: the rollout kernels fill the buffer behind torch's back (no version bump)
             if self._fhist.shape[0] < n_ep:
                 self._fhist = torch.zeros((n_ep, 8), dtype=torch.float32, device=self.device)
+        clipping = self.max_norm is not None
+        if clipping:   # every epoch's (s_actor, s_critic, coef_actor, coef_critic): filled on the device, read once after the loop
+            self.clip_stats = torch.zeros((max(n_ep, 1), 4), dtype=torch.float32, device=obs.device)
+        self._last_adv = adv   # (PPOTrainer._grad_guard's diagnostics)
         pipelined = self.fused and multi and self.fused_mlp64 and cfg.overlap_allreduce
         if pipelined:
             pg = self._pipelined_epochs(n_ep, world, obs, acts, logp_old, rtg, adv, var_f)   # squared norms of the MEAN gradient, per epoch and net
@@ -473,20 +555,25 @@ class PPOUpdater:
                 elif multi:   # fused passes -> ONE all-reduce of the flat gradient (RCCL) -> scale + Adam in one launch
                     self._fused_loss_grad(obs, acts, logp_old, rtg, adv, var_f, stats=self._fhist[ep])
                     ctx.all_reduce_sum(self.fp.grad)
-                    with torch.no_grad():   # every epoch's norms of the MEAN gradient (two small launches beside an all-reduce)
-                        n_a_ = self.fp.module_numel[0]
-                        g3 = torch.stack(torch._foreach_norm([self.fp.grad[:n_a_], self.fp.grad[n_a_:], self.fp.grad])) / world
-                        multi_gn = g3 if multi_gn is None else multi_gn + g3
-                    self._fused_adam(1.0 / world)
+                    if clipping:   # (the norms of the mean gradient are in the clip statistics)
+                        self._fused_adam(1.0 / world, cstats=self.clip_stats[ep])
+                    else:
+                        with torch.no_grad():   # every epoch's norms of the MEAN gradient (two small launches beside an all-reduce)
+                            n_a_ = self.fp.module_numel[0]
+                            g3 = torch.stack(torch._foreach_norm([self.fp.grad[:n_a_], self.fp.grad[n_a_:], self.fp.grad])) / world
+                            multi_gn = g3 if multi_gn is None else multi_gn + g3
+                        self._fused_adam(1.0 / world)
                 else:
-                    self._fused_epoch(obs, acts, logp_old, rtg, adv, var_f, self._fhist[ep])
+                    self._fused_epoch(obs, acts, logp_old, rtg, adv, var_f, self._fhist[ep], self.clip_stats[ep] if clipping else None)
                 if ep == n_ep - 1:
                     h = self._fhist[:n_ep]
                     self.loss_history = h[:, 0:5:4].clone()   # columns 0 (actor loss) and 4 (critic loss)
                     hs = h.sum(0)
                     # multi-GPU: fp.grad holds the all-reduced SUM (the 1 / world scale is inside navppo_adam_step)
                     gn_last = self.fp.grad.norm() / world
-                    if not multi and n_ep > 1:
+                    if clipping:   # the pre-clip norms of every epoch, from the clip statistics (no previous-epoch slots involved)
+                        gn_sum = self.clip_stats[:n_ep, :2].sum(1).sqrt().sum()
+                    elif not multi and n_ep > 1:
                         # grad norms as the reference logs them -- every epoch's, averaged (ppo.py:351-352, 389-390) -- without a norm
                         # launch per epoch: the fused epoch leaves the squared per-net norms of the epoch BEFORE in columns 3 / 7 of
                         # its statistics row (reduce_adam / resmlp_reduce), the last epoch's come from the gradient buffer
@@ -505,7 +592,10 @@ class PPOUpdater:
             if multi:
                 ctx.all_reduce_sum(self.fp.grad)
                 self.fp.grad.div_(world)
-            self.opt.step()                                    # ppo.py:381,392
+            if clipping:
+                self._clip_and_step(ep)
+            else:
+                self.opt.step()                                # ppo.py:381,392
             with torch.no_grad():                              # ppo.py:323-336
                 lr_ = logp.detach() - logp_old
                 self.loss_history[ep] = torch.stack([a_loss.detach(), c_loss.detach()])
@@ -524,15 +614,32 @@ class PPOUpdater:
         extra = torch.stack(torch._foreach_norm([self.fp.grad[:n_a], self.fp.grad[n_a:], d[:n_a], d[n_a:]]))
         if self.fused and multi:
             extra = extra * extra.new_tensor([1.0 / world, 1.0 / world, 1.0, 1.0])   # norms of the MEAN gradient, as on one GPU
-        if fused_gn_sq is not None:   # per-net norms: the mean over the epochs, like grad_norm (the reference's actor_grad_norm / critic_grad_norm)
+        clip_cols = []
+        if clipping:   # pre-clip norms of every epoch (their mean), share of clipped epochs, skipped steps; identical on every rank
+            cs = self.clip_stats[:n_ep]
+            gn = cs[:, :2].sqrt()
+            if n_ep > 0:
+                extra = torch.cat([gn.mean(0), extra[2:]])
+                if not self.fused:
+                    acc = torch.cat([acc[:4], cs[:, :2].sum(1).sqrt().mean().reshape(1), acc[5:]])
+            clip_cols = [(cs[:, 2:] < 1.0).float().sum(0) / max(n_ep, 1), (~torch.isfinite(cs[:, :2])).float().sum(0)]
+            if n_ep == 0:
+                clip_cols = [torch.zeros(2, device=obs.device)] * 2
+        elif fused_gn_sq is not None:   # per-net norms: the mean over the epochs, like grad_norm (the reference's actor_grad_norm / critic_grad_norm)
             extra = torch.cat([(fused_gn_sq.sqrt().sum(0) + extra[:2]) / n_ep, extra[2:]])
         elif multi_gn is not None:
             extra = torch.cat([multi_gn[:2] / n_ep, extra[2:]])
         elif net_gn is not None:
             extra = torch.cat([net_gn / max(n_ep, 1), extra[2:]])
         self.stats = dict(zip(["actor_loss", "critic_loss", "approx_kl", "clip_frac", "grad_norm", "value_mean",
-                               "actor_grad_norm", "critic_grad_norm", "actor_param_delta", "critic_param_delta"],
-                              [float(v) for v in torch.cat([acc, extra]).tolist()]))   # grad norms: means over the epochs (multi-GPU fused path: the last epoch's)
+                               "actor_grad_norm", "critic_grad_norm", "actor_param_delta", "critic_param_delta",
+                               "grad_clip_frac_actor", "grad_clip_frac_critic", "skipped_steps_actor", "skipped_steps_critic"],
+                              [float(v) for v in torch.cat([acc, extra] + clip_cols).tolist()]))   # grad norms: means over the epochs (multi-GPU fused path: the last epoch's)
+        # (the last four keys exist with clipping on only: without max_grad_norm the statistics -- and with them the trainer's log
+        # dictionary and everything that enumerates it -- are exactly what they were; nothing is ever clipped or skipped there)
+        for k in ("skipped_steps_actor", "skipped_steps_critic"):
+            if k in self.stats:
+                self.stats[k] = int(self.stats[k])
         self.last_losses = (a_loss.detach(), c_loss.detach())
         return self.stats
 
@@ -764,6 +871,7 @@ class PPOTrainer:
         metrics = self._rollout_metrics(m)
         self.t_so_far += metrics["completed_steps"]
         self.i_so_far += 1
+        self._grad_guard(stats)
         world = self.ctx.world if self.ctx is not None else 1
         self.logger = dict(metrics, **stats, iteration=self.i_so_far, t_so_far=self.t_so_far,
                            rollout_time=t1 - t0, update_time=t2 - t1, iter_time=t2 - t0,
@@ -782,6 +890,47 @@ class PPOTrainer:
                 self.write_episode_csv(cfg.episode_csv_rows)
             self.write_tensorboard()
         return self.logger
+
+    # ---- the gradient check of the reference (ppo.py:356-379, 414-416), once per iteration on figures that are already on the host
+    def _grad_guard(self, stats, log=print):
+        """A per-net mean gradient norm that is <= 0 or not finite, a loss that is not finite, or a skipped step (max_grad_norm):
+        the reference's warning line, and a block in <output_dir>/grad_diagnostics.txt.  No launch and no sync unless it triggers
+        (then a few reductions over the advantages for the file); it reports only -- what happens to the weights is decided by
+        PPOConfig.max_grad_norm inside the update -- and never raises.  Returns the nets that triggered."""
+        cfg = self.cfg
+        if cfg.n_updates_per_iteration < 1:
+            return []
+        hit = []
+        for net in ("actor", "critic"):
+            gn, loss, sk = stats.get(net + "_grad_norm", 0.0), stats.get(net + "_loss", 0.0), stats.get("skipped_steps_" + net, 0)
+            if gn <= 0 or not math.isfinite(gn) or not math.isfinite(loss) or sk > 0:
+                hit.append((net, gn, loss, sk))
+        if not hit or not (self.ctx is None or self.ctx.rank == 0):
+            return [h[0] for h in hit]
+        try:
+            for net, gn, loss, sk in hit:
+                if log:
+                    log(f"[WARNING] {net.capitalize()} grad norm invalid: {gn:.6f} at iteration {self.i_so_far}. Check grad_diagnostics.txt"
+                        + (f" ({sk} of {cfg.n_updates_per_iteration} steps skipped)" if sk else ""), flush=True)
+            if cfg.output_dir:
+                adv = getattr(self.updater, "_last_adv", None)
+                a = [float("nan")] * 4 if adv is None else [float(x) for x in (adv.mean(), adv.std(), adv.min(), adv.max())]
+                os.makedirs(cfg.output_dir, exist_ok=True)
+                with open(os.path.join(cfg.output_dir, "grad_diagnostics.txt"), "a") as f:
+                    for net, gn, loss, sk in hit:
+                        f.write(f"\n[{net.upper()} GRAD ISSUE] Iteration {self.i_so_far}\n")
+                        f.write(f"  Net: {net}\n")
+                        f.write(f"  {net.capitalize()} grad norm: {gn}\n")
+                        f.write(f"  {net.capitalize()} loss: {loss}\n")
+                        f.write(f"  Skipped steps: {sk} of {cfg.n_updates_per_iteration}\n")
+                        f.write(f"  Advantage stats: mean={a[0]:.4f}, std={a[1]:.4f}, min={a[2]:.4f}, max={a[3]:.4f}\n")
+                        f.write(f"  Clip fraction: {stats.get('clip_frac', 0.0):.4f}\n")
+        except Exception as e:   # a diagnostics file must never end a run
+            try:
+                print(f"[WARNING] grad diagnostics not written: {e}", flush=True)
+            except Exception:
+                pass
+        return [h[0] for h in hit]
 
     # ---- periodic evaluation (PPOConfig.eval_every)
     EVAL_HISTORY_HEADER = ["iteration", "timesteps", "episodes", "success_rate", "collision_rate", "timeout_rate", "mean_length",
@@ -906,6 +1055,8 @@ class PPOTrainer:
                 "ppo/clip_frac": lg.get("clip_frac"), "ppo/actor_grad_norm": lg.get("actor_grad_norm"),
                 "ppo/critic_grad_norm": lg.get("critic_grad_norm"), "ppo/actor_param_delta": lg.get("actor_param_delta"),
                 "ppo/critic_param_delta": lg.get("critic_param_delta"),
+                "ppo/grad_clip_frac_actor": lg.get("grad_clip_frac_actor"), "ppo/grad_clip_frac_critic": lg.get("grad_clip_frac_critic"),
+                "ppo/skipped_steps_actor": lg.get("skipped_steps_actor"), "ppo/skipped_steps_critic": lg.get("skipped_steps_critic"),
                 **({"eval/success_rate": lg["eval_success"], "eval/collision_rate": lg["eval_collision"],
                     "eval/timeout_rate": lg["eval_timeout"], "eval/mean_return": lg["eval_return"],
                     "eval/mean_ep_length": lg["eval_length"], "time/eval": lg["eval_time"]} if "eval_success" in lg else {})}
