@@ -19,9 +19,11 @@
 //     (bias starts, relu1, the split of H1's first k-step, the relu mask of layer 1) is spread over the 60 MFMA slots of G2 + F1, a
 //     third of which were empty.  The loop starts at F2's first MFMA; tools/verify/mfma_slot_report.py counts what sits in front of
 //     every MFMA, tests/test_isa_schedule_cpu.py holds the counts.
-// MFMA -> vector hazards: the compiler does not see inside the asm statements, so a chain whose accumulators the vector unit reads
-// right behind it ends in `settle` (12 wait states; gfx950 needs 11 after an 8-pass XDL op); where a chain's reader sits two or more
-// MFMA slots further on, the slots' own instructions are the wait states, and the lint of the listing (below) counts them.
+//   * the heads ride on their neighbours: F2 ends with c2[0]'s nine products and then c2[1]'s, relu2 of c2[0] and its half of the two dot
+//     products sit behind c2[1]'s MFMAs, c2[1]'s half behind G1's first eight; what stays bare is the loss arithmetic between the halves.
+// MFMA -> vector hazards: the compiler does not see inside the asm statements, and gfx950 needs 11 wait states between an 8-pass XDL op and
+// a vector instruction that reads its accumulators.  Every chain's reader sits two or more MFMA slots behind it: the slots' own
+// instructions are the wait states, and the lint of the listing (below) counts them.
 //
 // LDS image of a 32-sample x 64-unit matrix of pieces: row m = 128 bytes, 8-byte slots ("quads": 4 units) XOR-swizzled by
 //   f(m) = (m & 3) | ((m >> 2 ^ m >> 3) & 1) << 2 | ((m >> 1 ^ m >> 3) & 1) << 3
@@ -85,8 +87,6 @@ static_assert(sizeof(SmemS::img) / SW >= 96 * 64 * sizeof(float), "lane partials
 // constant turns the register arrays into scratch memory)
 #define X3S_REP10(F, b) F(b + 0); F(b + 1); F(b + 2); F(b + 3); F(b + 4); F(b + 5); F(b + 6); F(b + 7); F(b + 8); F(b + 9);
 
-// the vector unit may read / overwrite these accumulators from here on (8-pass XDL write -> VALU: 11 wait states)
-__device__ __forceinline__ void settle(f32x16& a, f32x16& b) { asm volatile("s_nop 7\n\ts_nop 3" : "+v"(a), "+v"(b)); }
 
 // (a, b) -> p0 and the residuals: 5 instructions
 __device__ __forceinline__ void split_a(unsigned& p0, float& ra, float& rb, const float a, const float b) {
@@ -120,6 +120,23 @@ __device__ __forceinline__ void relu4(float (&h)[16], const f32x16& c, const int
     asm volatile("v_max_i32 %0, %4, 0\n\tv_max_i32 %1, %5, 0\n\tv_max_i32 %2, %6, 0\n\tv_max_i32 %3, %7, 0"
                  : "=&v"(y0), "=&v"(y1), "=&v"(y2), "=&v"(y3) : "v"(c[4 * g]), "v"(c[4 * g + 1]), "v"(c[4 * g + 2]), "v"(c[4 * g + 3]));
     h[4 * g] = y0; h[4 * g + 1] = y1; h[4 * g + 2] = y2; h[4 * g + 3] = y3;
+}
+// four steps of the heads' dot products: z3 = fmaf(h[4 g + k], w3[k], z3), k = 0..3, and z4 alike (actor) -- the fmaf chain of the
+// heads, one step after the other, as a block the caller places behind an MFMA  (8 / 4 instructions)
+template <bool ACTOR>
+__device__ __forceinline__ void dot4(float& z3, float& z4, const float (&h)[16], const int g, const v4f w3, const v4f w4) {
+    if constexpr (ACTOR)
+        asm volatile("v_fmac_f32 %0, %2, %6\n\tv_fmac_f32 %1, %2, %10\n\t"
+                     "v_fmac_f32 %0, %3, %7\n\tv_fmac_f32 %1, %3, %11\n\t"
+                     "v_fmac_f32 %0, %4, %8\n\tv_fmac_f32 %1, %4, %12\n\t"
+                     "v_fmac_f32 %0, %5, %9\n\tv_fmac_f32 %1, %5, %13"
+                     : "+v"(z3), "+v"(z4)
+                     : "v"(h[4 * g]), "v"(h[4 * g + 1]), "v"(h[4 * g + 2]), "v"(h[4 * g + 3]), "v"(w3.x), "v"(w3.y), "v"(w3.z), "v"(w3.w),
+                       "v"(w4.x), "v"(w4.y), "v"(w4.z), "v"(w4.w));
+    else
+        asm volatile("v_fmac_f32 %0, %1, %5\n\tv_fmac_f32 %0, %2, %6\n\tv_fmac_f32 %0, %3, %7\n\tv_fmac_f32 %0, %4, %8"
+                     : "+v"(z3)
+                     : "v"(h[4 * g]), "v"(h[4 * g + 1]), "v"(h[4 * g + 2]), "v"(h[4 * g + 3]), "v"(w3.x), "v"(w3.y), "v"(w3.z), "v"(w3.w));
 }
 // one value of the head's backward: h = H2 (>= 0) -> dH2 in place; the lane's partial sums  (7 / 5 instructions)
 //   pw3 += h g3 ; pw4 += h g4 ; d = g3 w3 + g4 w4 (fma(g3, w3, g4 w4)) ; h = h > 0 ? d : 0 ; pb2 += h
@@ -188,6 +205,12 @@ __device__ __forceinline__ void pass_body(SmemS& sm, const float* __restrict__ p
     const int l31 = lane & 31, lhi = lane >> 5, l15 = lane & 15, kk = lane >> 4;
 
     // ---- weights -> bf16 pieces in LDS (once per launch), as pass_body_x3
+#ifdef X3S_EXPERIMENT_COPY_PROLOGUE
+    // (timing experiment, profiles/x3s_fixed_cost.txt: what a launch would cost if the 55 KB of pieces arrived as a ready image -- a straight
+    // 16-byte copy, global memory to LDS, here of as many bytes of `prep` -- instead of being split by every workgroup; results are wrong)
+    for (int k = tid; k < (int)offsetof(SmemS, img) / 16; k += NT)
+        reinterpret_cast<u32x4*>(&sm)[k] = reinterpret_cast<const u32x4*>(prep)[k + (ACTOR ? 0 : (int)offsetof(SmemS, img) / 16)];
+#else
     for (int k = tid; k < H * H / 2; k += NT) {
         const int r = (2 * k) / H, c = (2 * k) % H;
         uint32_t p0, p1, p2;
@@ -214,6 +237,7 @@ __device__ __forceinline__ void pass_body(SmemS& sm, const float* __restrict__ p
         sm.w3[tid] = params[OFF_W3 + tid];
         sm.w4[tid] = ACTOR ? params[OFF_W4 + tid] : 0.f;
     }
+#endif
     const float b3 = params[OFF_B3];
     const float b4 = ACTOR ? params[OFF_B4] : 0.f;
     __syncthreads();
@@ -258,8 +282,11 @@ __device__ __forceinline__ void pass_body(SmemS& sm, const float* __restrict__ p
         for (int r = 0; r < 16; ++r) pb2[t][r] = pw3[t][r] = pw4[t][r] = 0.f;
     float adb3 = 0.f, adb4 = 0.f, st0 = 0.f, st1 = 0.f, st2 = 0.f, st3 = 0.f;
     // (no instruction: a use of dW2's accumulators in the middle of the phases that do not touch them, so that the register allocator
-    // does not park them elsewhere for those phases and fetch them back for G2 -- 96 copies per tile)
-    auto keep_w2 = [&]() { asm volatile("" : "+a"(aW2[0][0]), "+a"(aW2[0][1]), "+a"(aW2[1][0]), "+a"(aW2[1][1])); };
+    // does not park them elsewhere for those phases and fetch them back for G2 -- 96 copies per tile; dW1's likewise: moved aside over
+    // F2 and back in front of G1, one copy right in front of its MFMA)
+    auto keep_w2 = [&]() {
+        asm volatile("" : "+a"(aW2[0][0]), "+a"(aW2[0][1]), "+a"(aW2[1][0]), "+a"(aW2[1][1]), "+a"(aW1[0]), "+a"(aW1[1]), "+a"(aW1[2]), "+a"(aW1[3]));
+    };
     u32x4 ones = {0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u};   // bf16 1.0 in every k-slot
     asm volatile("" : "+a"(ones));   // lives in AGPRs for the whole launch
 
@@ -271,11 +298,13 @@ __device__ __forceinline__ void pass_body(SmemS& sm, const float* __restrict__ p
     // few thousand cycles later and tied to the registers so that nothing reads or copies them before.  (Hidden loads are safe for the
     // compiler's own vmcnt bookkeeping: loads return in order, extra outstanding ones only make its waits longer.)
     u32x4 xp[3], xbn[3];   // rows of the tile whose F1 runs next ; columns of the tile whose G1 runs next (G1 runs one tile late)
+    auto keep_cols = [&]() { asm volatile("" : "+a"(xbn[0]), "+a"(xbn[1]), "+a"(xbn[2])); };   // (as keep_w2, between F2 and G1: landed, not yet re-requested)
     float pre_a0 = 0.f, pre_a1 = 0.f, pre_lp = 0.f, pre_t = 0.f;
     // Each request is placed behind the last reader of the registers it lands in (F1 for the rows, G1 for the columns, the heads for the
     // sample's scalars: all three ride on B2's slots), so no copy of them is kept; `landed` sits in front of F1, some 85 MFMA slots
     // later.  All tiles are clamped by the caller: always valid.
-    auto request_rows = [&](const long long t) {
+    auto request_rows = [&](long long t) {
+        asm volatile("" : "+s"(t));   // (the address arithmetic stays in this slot: hoisted, it stands in front of B2's first MFMA)
         const unsigned char* r = prep + (size_t)t * kTileBytes + ((l31 * 3) * 16 + 8 * lhi) * 2;   // rows past the batch are zero in `prep`
         asm volatile("global_load_dwordx4 %0, %3, off\n\tglobal_load_dwordx4 %1, %3, off offset:32\n\tglobal_load_dwordx4 %2, %3, off offset:64"
                      : "=a"(xp[0]), "=a"(xp[1]), "=a"(xp[2]) : "v"(r));
@@ -286,17 +315,24 @@ __device__ __forceinline__ void pass_body(SmemS& sm, const float* __restrict__ p
                      : "=a"(xbn[0]), "=a"(xbn[1]), "=a"(xbn[2]) : "v"(c));
     };
     auto request_scalars = [&](const long long t) {
-        const long long m = t * 32 + l31;
-        if (m < M) {
-            if (ACTOR) {
+        if constexpr (ACTOR) {
+            const long long m = t * 32 + l31;
+            if (m < M) {
                 const float2 a = reinterpret_cast<const float2*>(act)[m];
                 pre_a0 = a.x;
                 pre_a1 = a.y;
                 pre_lp = logp_old[m];
                 pre_t = adv[m];
-            } else {
-                pre_t = rtg[m];
             }
+        } else {
+            // No branch in the critic's stream: with one here and its short loss block if-converted, the compiler lays the loop out
+            // rotated (it then starts in the middle of B2).  A lane past the batch reads the last sample's return instead, which is used
+            // under `valid` only.  The empty statement pins the address arithmetic to this slot (it would be hoisted to the front of B2).
+            int l = l31;
+            long long ts = t;
+            asm volatile("" : "+v"(l), "+s"(ts));
+            const long long m = ts * 32 + l;
+            pre_t = rtg[m < M ? m : M - 1];
         }
     };
     auto landed = [&]() {
@@ -433,21 +469,23 @@ __device__ __forceinline__ void pass_body(SmemS& sm, const float* __restrict__ p
 
         // ================================================================ F2: H2^T = relu(b2 + W2 H1^T); H1 split once, k-step s = (t1, j)
         G1Ops g1o;
+        float h2[2][16];   // H2, then dH2 in place
+        float z3 = 0.f, z4 = 0.f;   // the heads' pre-activations: sums over the lane's 32 units, c2[0]'s half first
         {
-            u32x4 wk[4][2];   // the leading weight pieces again, for the big terms: requested behind k-step 3 (its slots carry no split)
+            u32x4 wk[4][2];   // the leading weight pieces again, for the big terms
             SplitState ss;    // (k-step 0 was split a tile ahead: ahead_work)
 #pragma unroll
-            for (int s = 0; s < 4; ++s) {
+            for (int s = 0; s < 3; ++s) {
                 u32x4 w[2][3];
 #pragma unroll
                 for (int i = 0; i < 3; ++i) { w[0][i] = wn[0][i]; w[1][i] = wn[1][i]; }
                 keep_w2();
+                keep_cols();
                 // the stream of k-step s: 10 MFMAs; behind them the split of k-step s + 1 (8 blocks), this step's piece stores and the
                 // next step's weight rows
                 auto filler = [&](const int slot) {
-                    if (s < 3 && slot >= 1 && slot <= 8) split_block(h1[(s + 1) >> 1], (s + 1) & 1, slot - 1, hb[s + 1], ss);
-                    if (s == 3 && slot < 8) wk[slot >> 1][slot & 1] = ldw(&sm.W2p[0][0][0], slot & 1, slot >> 1, 0);
-                    if (s < 3 && (slot == 0 || slot == 4 || slot == 9)) {
+                    if (slot >= 1 && slot <= 8) split_block(h1[(s + 1) >> 1], (s + 1) & 1, slot - 1, hb[s + 1], ss);
+                    if (slot == 0 || slot == 4 || slot == 9) {
                         const int i = slot == 0 ? 0 : slot == 4 ? 1 : 2;
                         wn[0][i] = ldw(&sm.W2p[0][0][0], 0, s + 1, i);
                         wn[1][i] = ldw(&sm.W2p[0][0][0], 1, s + 1, i);
@@ -467,46 +505,71 @@ __device__ __forceinline__ void pass_body(SmemS& sm, const float* __restrict__ p
                 X3S_MFMA32_V_AV(c2[0], w[0][0], hb[s].p[1]); filler(8);
                 X3S_MFMA32_V_AV(c2[1], w[1][0], hb[s].p[1]); filler(9);
             }
-            // the big terms; behind them the operand gathers of the PREVIOUS tile's G1 (its dH1 pieces are still in imgD)
+            // k-step 3 and the big terms, c2[0]'s nine and then c2[1]'s (each accumulator sees its products in the order it always did):
+            // relu2 of c2[0] and its half of the heads' dot products start behind c2[1]'s MFMAs instead of waiting behind the chain.
+            //   MFMA    0 1       2..8          |  9 10      11           12 13                      14..17
+            //   c2[0]:  wk[.][0]  G1's gathers  |  c2[1]: wk[.][1]  store hb[3]  relu2 of c2[0], w3 / w4  z3 / z4 of c2[0]'s units
+            // (G1's operands are those of the PREVIOUS tile: its dH1 pieces are still in imgD.  relu2 sits 4 MFMAs and 12 loads / stores
+            // behind c2[0]'s last product: the listing is linted.)
             int hb0 = h_base0, hb1 = h_base1;
             asm volatile("" : "+v"(hb0), "+v"(hb1));   // the eight gather addresses are formed here, per tile: not hoisted into eight registers
             int gq = 0;
+            auto gather = [&]() { g1_gather_pair(g1o, gq, hb0, hb1); ++gq; };
+            auto ld_wk = [&](const int s, const int t) { wk[s][t] = ldw(&sm.W2p[0][0][0], t, s, 0); };
+            keep_w2();
+            keep_cols();
+            X3S_MFMA32_V_AV(c2[0], wn[0][2], hb[3].p[0]); ld_wk(0, 0); ld_wk(1, 0);
+            X3S_MFMA32_V_AV(c2[0], wn[0][1], hb[3].p[1]); ld_wk(2, 0); ld_wk(3, 0);
+            X3S_MFMA32_V_AV(c2[0], wn[0][0], hb[3].p[2]); gather(); gather();
+            X3S_MFMA32_V_AV(c2[0], wn[0][1], hb[3].p[0]); gather(); gather();
+            X3S_MFMA32_V_AV(c2[0], wn[0][0], hb[3].p[1]); gather(); gather();
+            X3S_MFMA32_V_AV(c2[0], wk[0][0], hb[0].p[0]); gather(); gather();
+            X3S_MFMA32_V_AV(c2[0], wk[1][0], hb[1].p[0]); gather(); gather();
+            X3S_MFMA32_V_AV(c2[0], wk[2][0], hb[2].p[0]); gather();
+            X3S_MFMA32_V_AV(c2[0], wk[3][0], hb[3].p[0]); gather();
+            v4f hw3[4], hw4[4] = {};   // w3 / w4 at the lane's units of c2[0]
+            auto ld_hw = [&](const int g) {   // (each two slots ahead of its use: the vector registers are full here)
+                hw3[g] = ldv(sm.w3, 0, g);
+                if (ACTOR) hw4[g] = ldv(sm.w4, 0, g);
+            };
+            X3S_MFMA32_V_AV(c2[1], wn[1][2], hb[3].p[0]); ld_wk(0, 1); ld_wk(1, 1); ld_hw(0);
+            X3S_MFMA32_V_AV(c2[1], wn[1][1], hb[3].p[1]); ld_wk(2, 1); ld_wk(3, 1); ld_hw(1);
+            X3S_MFMA32_V_AV(c2[1], wn[1][0], hb[3].p[2]); store_pieces(IMG_H, 1, 1, hb[3]);
+            X3S_MFMA32_V_AV(c2[1], wn[1][1], hb[3].p[0]); relu4(h2[0], c2[0], 0); relu4(h2[0], c2[0], 1);
+            X3S_MFMA32_V_AV(c2[1], wn[1][0], hb[3].p[1]); relu4(h2[0], c2[0], 2); relu4(h2[0], c2[0], 3);
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
-                X3S_MFMA32_V_AV(c2[0], wk[s][0], hb[s].p[0]);
-                g1_gather_pair(g1o, gq++, hb0, hb1); g1_gather_pair(g1o, gq++, hb0, hb1);
                 X3S_MFMA32_V_AV(c2[1], wk[s][1], hb[s].p[0]);
-                g1_gather_pair(g1o, gq++, hb0, hb1);
+                dot4<ACTOR>(z3, z4, h2[0], s, hw3[s], hw4[s]);
+                if (s < 2) ld_hw(s + 2);
             }
         }
-        settle(c2[0], c2[1]);
 
         // ================================================================ heads, loss, dH2 (in place), the lane's share of db2 / dW3 / dW4;
-        // behind the vector work: G1 of the PREVIOUS tile, 36 MFMAs placed one by one
+        // behind the vector work: G1 of the PREVIOUS tile, 36 MFMAs placed one by one.  c2[1]'s half of relu2 and of the dot products
+        // rides on the first eight; its relu sits three of them (and the loads between) behind c2[1]'s last product: no s_nop.
         int g1k = 0;
         keep_w2();
-        float h2[2][16];   // H2, then dH2 in place
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
+        {
+            v4f hw3[4], hw4[4] = {};
             g1_step(g1k++, g1o, xbn);
-            relu4(h2[q >> 2], c2[q >> 2], q & 3);
+            hw3[0] = ldv(sm.w3, 1, 0); hw3[1] = ldv(sm.w3, 1, 1);
+            if (ACTOR) { hw4[0] = ldv(sm.w4, 1, 0); hw4[1] = ldv(sm.w4, 1, 1); }
+            g1_step(g1k++, g1o, xbn);
+            hw3[2] = ldv(sm.w3, 1, 2); hw3[3] = ldv(sm.w3, 1, 3);
+            if (ACTOR) { hw4[2] = ldv(sm.w4, 1, 2); hw4[3] = ldv(sm.w4, 1, 3); }
+            g1_step(g1k++, g1o, xbn);
+            relu4(h2[1], c2[1], 0); relu4(h2[1], c2[1], 1);
+            g1_step(g1k++, g1o, xbn);
+            relu4(h2[1], c2[1], 2); relu4(h2[1], c2[1], 3);
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                g1_step(g1k++, g1o, xbn);
+                dot4<ACTOR>(z3, z4, h2[1], g, hw3[g], hw4[g]);
+            }
         }
         float g3 = 0.f, g4 = 0.f;
         {
-            float z3 = 0.f, z4 = 0.f;
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const v4f w = ldv(sm.w3, t, g);
-                    z3 = fmaf(h2[t][4 * g], w.x, z3); z3 = fmaf(h2[t][4 * g + 1], w.y, z3);
-                    z3 = fmaf(h2[t][4 * g + 2], w.z, z3); z3 = fmaf(h2[t][4 * g + 3], w.w, z3);
-                    if (ACTOR) {
-                        const v4f v = ldv(sm.w4, t, g);
-                        z4 = fmaf(h2[t][4 * g], v.x, z4); z4 = fmaf(h2[t][4 * g + 1], v.y, z4);
-                        z4 = fmaf(h2[t][4 * g + 2], v.z, z4); z4 = fmaf(h2[t][4 * g + 3], v.w, z4);
-                    }
-                }
             z3 += __shfl_xor(z3, 32, 64);
             if (ACTOR) z4 += __shfl_xor(z4, 32, 64);
             const float own = (lhi == 0) ? 1.f : 0.f;   // statistics are counted once per sample
