@@ -140,6 +140,46 @@ int navppo_adam_step_clipped(float* params_dev, float* grad_dev, float* adam_m_d
                              float* clip_stats_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------------
+ * Early stop at a KL limit ON THE DEVICE (`target_kl` of Stable-Baselines3 / Spinning Up: stop the update's remaining epochs once the
+ * policy has moved too far from the one that collected the batch).  navppo_mlp64_update_epoch_kl, navppo_mlp64_bf16x3_update_epoch_kl
+ * and navppo_resmlp512_update_epoch_kl take exactly the arguments of their *_clipped twins plus `kl_limit` and `kl_state_dev` in front
+ * of `stream`; navppo_adam_step_kl is the multi-GPU form.  max_norm = +inf means "no clipping", as above.
+ *   kl_state_dev  [4] f32.  The caller ZEROES it before the first epoch of an update; afterwards only the library writes it:
+ *                 [0] stopped (0 or 1)   [1] number of calls since zeroing that went on to the optimiser step
+ *                 [2] the approx_kl that tripped the stop (unchanged if nothing tripped)   [3] the `step` argument of the tripping call
+ *   kl_limit      > 0, +inf allowed; 0, negative or NaN: -1.  kl_state_dev NULL: -1.  The *_clipped checks are unchanged.
+ * Per call:
+ *   1. stopped (kl_state[0] != 0 at entry): EVERY kernel of the epoch -- the pass launches (for the 512-wide nets also the streaming
+ *      kernel), the reduction and the step launch -- returns at its entry.  Parameters, both moments, grad_dev, stats_dev,
+ *      clip_stats_dev and kl_state_dev keep their contents; the workspace stays scratch.
+ *   2. else the passes and the reduction run exactly as in the *_clipped entry point, and the step launch reads kl = stats_dev[1]
+ *      (the mean of (ratio - 1) - log ratio, ppo.py:326), which the launch before it wrote: every workgroup derives the same decision
+ *      from the same bits and none waits for another.
+ *   3. trip, !(kl <= kl_limit) -- a NaN kl trips: NEITHER net is stepped (parameters and moments are not written), grad_dev keeps the
+ *      unclipped sum, clip_stats_dev = (s_actor, s_critic, 0, 0), kl_state = (1, unchanged, kl, step).
+ *   4. no trip: the clipped epoch's step with the very same expression, and kl_state[1] += 1.  kl_limit = +inf on a zeroed state gives
+ *      the bits of *_update_epoch_clipped; with max_norm = +inf as well, those of *_update_epoch.
+ * The check comes before the step and the stop covers BOTH nets (Stable-Baselines3's convention).  Keeping the critic training after
+ * the actor stops (Spinning Up) would need a per-net Adam step count across this ABI and is not offered.  A caller whose Adam step
+ * count must be the number of steps TAKEN reads kl_state[1] after its own synchronisation.  Every family's passes are gated (the
+ * hand-placed streams included), so a stopped epoch costs its launches only.
+ */
+int navppo_mlp64_update_epoch_kl(float* params_dev, const void* obs_dev, int32_t obs_dim, int32_t obs_f16, const float* act_dev,
+                                 const float* logp_old_dev, const float* rtg_dev, const float* adv_dev, int64_t n_samples, float var,
+                                 float clip, float lr, float beta1, float beta2, float eps, int32_t step, float* adam_m_dev,
+                                 float* adam_v_dev, float* grad_dev, float* stats_dev, void* workspace_dev, float max_norm,
+                                 float* clip_stats_dev, float kl_limit, float* kl_state_dev, void* stream);
+
+/*
+ * navppo_adam_step_clipped with the contract above.  kl_dev: a device scalar holding the GLOBAL approx_kl of this epoch (multi-GPU:
+ * all-reduce [kl x n, n] and divide); the passes in front of it (navppo_*_loss_grad) are not gated, so no time is saved on this path.
+ * On a trip grad_dev keeps the all-reduced sum and clip_stats_dev = (s_actor, s_critic, 0, 0).
+ */
+int navppo_adam_step_kl(float* params_dev, float* grad_dev, float* adam_m_dev, float* adam_v_dev, int64_t n, int64_t n_first,
+                        float grad_scale, float max_norm, float lr, float beta1, float beta2, float eps, int32_t step,
+                        float* clip_stats_dev, float kl_limit, float* kl_state_dev, const float* kl_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------------
  * The same update (ppo.py:305-397; 16- or 42-column rows, float32 or float16) with every matrix product evaluated on the bf16 MFMA from operands split into
  * three bf16 pieces -- "bf16x3": a = a0 + a1 + a2 exactly (8 + 8 + 8 significand bits), a b ~ the six leading piece products,
  * each exact in float32, float32 accumulation, small terms first.  float32-equivalent by measurement (against float64 the
@@ -173,6 +213,13 @@ int navppo_mlp64_bf16x3_update_epoch_clipped(float* params_dev, const void* prep
                                              float clip, float lr, float beta1, float beta2, float eps, int32_t step, float* adam_m_dev,
                                              float* adam_v_dev, float* grad_dev, float* stats_dev, void* workspace_dev, float max_norm,
                                              float* clip_stats_dev, void* stream);
+
+/* navppo_mlp64_bf16x3_update_epoch_clipped with the early stop at a KL limit: see navppo_mlp64_update_epoch_kl */
+int navppo_mlp64_bf16x3_update_epoch_kl(float* params_dev, const void* prep_dev, int32_t obs_dim, const float* act_dev,
+                                        const float* logp_old_dev, const float* rtg_dev, const float* adv_dev, int64_t n_samples, float var,
+                                        float clip, float lr, float beta1, float beta2, float eps, int32_t step, float* adam_m_dev,
+                                        float* adam_v_dev, float* grad_dev, float* stats_dev, void* workspace_dev, float max_norm,
+                                        float* clip_stats_dev, float kl_limit, float* kl_state_dev, void* stream);
 
 /*
  * PPO.get_action() (ppo.py:673-706) for all envs of a shard in one launch: mean = actor(obs) (net_actor forward),
@@ -230,6 +277,13 @@ int navppo_resmlp512_update_epoch_clipped(float* params_dev, const void* obs_dev
                                           float beta1, float beta2, float eps, int32_t step, float* adam_m_dev, float* adam_v_dev,
                                           float* grad_dev, float* stats_dev, void* workspace_dev, float max_norm, float* clip_stats_dev,
                                           void* stream);
+
+/* navppo_resmlp512_update_epoch_clipped with the early stop at a KL limit: see navppo_mlp64_update_epoch_kl */
+int navppo_resmlp512_update_epoch_kl(float* params_dev, const void* obs_dev, int32_t obs_f16, const float* act_dev, const float* logp_old_dev,
+                                     const float* rtg_dev, const float* adv_dev, int64_t n_samples, float var, float clip, float lr,
+                                     float beta1, float beta2, float eps, int32_t step, float* adam_m_dev, float* adam_v_dev,
+                                     float* grad_dev, float* stats_dev, void* workspace_dev, float max_norm, float* clip_stats_dev,
+                                     float kl_limit, float* kl_state_dev, void* stream);
 
 /* V = critic(obs).squeeze() (ppo.py:275, :724); critic_params_dev [50257] (8-byte aligned suffices), value_dev [n] */
 int navppo_resmlp512_value(const float* critic_params_dev, const void* obs_dev, int32_t obs_f16, int64_t n_samples, float* value_dev,

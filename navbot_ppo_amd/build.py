@@ -5,7 +5,9 @@ import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
-SRCS = [os.path.join(HERE, "csrc", f) for f in ("navsim.hip", "ppo_mlp64.hip", "ppo_resmlp512.hip")]
+# ppo_*_kl.hip: the gated twins of the update's kernels (target_kl) -- each INCLUDES its partner source and compiles it a second time
+# (csrc/navppo_internal.h, NAVPPO_KL_TU), in a translation unit of its own so that the ungated kernels' listings stay what they were
+SRCS = [os.path.join(HERE, "csrc", f) for f in ("navsim.hip", "ppo_mlp64.hip", "ppo_resmlp512.hip", "ppo_mlp64_kl.hip", "ppo_resmlp512_kl.hip")]
 HDRS = ["navsim.h", "navppo.h"]
 INC = os.path.join(REPO, "include")
 LIB = os.path.join(HERE, "libnavsim.so")
@@ -28,7 +30,7 @@ def needs_build():
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = SRCS + [os.path.join(INC, h) for h in HDRS] + [os.path.join(HERE, "csrc", h) for h in ("mlp64_policy.h", "navppo_internal.h", "resmlp_policy.h", "bf16x3.h", "ppo_mlp64_x3s.h", "ppo_resmlp512_bwd2s.h")]
+    deps = SRCS + [os.path.join(INC, h) for h in HDRS] + [os.path.join(HERE, "csrc", h) for h in ("mlp64_policy.h", "navppo_internal.h", "resmlp_policy.h", "bf16x3.h", "ppo_mlp64_x3s.h", "ppo_resmlp512_bwd2s.h", "ppo_mlp64.hip", "ppo_resmlp512.hip")]
     return any(os.path.getmtime(p) > t for p in deps)
 
 
@@ -41,11 +43,12 @@ def needs_build():
 # asm: tools/verify/mfma_hazard_lint.py, tests/test_isa_lint_cpu.py) and copies 8 more registers per tile; with register-class priority
 # first it does neither.  (The other kernels of the file: same registers, no spills either way.)
 EXTRA_FLAGS = {"navsim.hip": ["-mllvm", "-disable-machine-licm"],
-               "ppo_resmlp512.hip": ["-mllvm", "-greedy-regclass-priority-trumps-globalness=1"]}
+               "ppo_resmlp512.hip": ["-mllvm", "-greedy-regclass-priority-trumps-globalness=1"],
+               "ppo_resmlp512_kl.hip": ["-mllvm", "-greedy-regclass-priority-trumps-globalness=1"]}   # (resmlp_bwd2s_kl: the same stream)
 # what a source is built with INSTEAD when hipcc rejects (or NAVSIM_NO_EXTRA_FLAGS=1 drops) its EXTRA_FLAGS: a flag that only buys speed
 # has no entry; resmlp_bwd2s without its allocation flag carries a hazard the compiler cannot see, so the file then launches the
 # compiler-scheduled resmlp_bwd<32, 2, 4> (same arithmetic, 4.3 instead of 3.2 ms per epoch)
-FALLBACK_FLAGS = {"ppo_resmlp512.hip": ["-DRESMLP_BWD2S=0"]}
+FALLBACK_FLAGS = {"ppo_resmlp512.hip": ["-DRESMLP_BWD2S=0"], "ppo_resmlp512_kl.hip": ["-DRESMLP_BWD2S=0"]}
 
 _flag_ok = {}
 
@@ -91,7 +94,7 @@ def build_native(force=False, verbose=False, navsim_src=None, out=None, extra=()
     procs, objs = [], []
     srcs = SRCS if navsim_src is None else [navsim_src] + SRCS[1:]
     lib_out = LIB if out is None else out
-    hdrs = [os.path.join(INC, h) for h in HDRS] + [os.path.join(HERE, "csrc", h) for h in ("mlp64_policy.h", "navppo_internal.h", "resmlp_policy.h", "bf16x3.h", "ppo_mlp64_x3s.h", "ppo_resmlp512_bwd2s.h")]
+    hdrs = [os.path.join(INC, h) for h in HDRS] + [os.path.join(HERE, "csrc", h) for h in ("mlp64_policy.h", "navppo_internal.h", "resmlp_policy.h", "bf16x3.h", "ppo_mlp64_x3s.h", "ppo_resmlp512_bwd2s.h", "ppo_mlp64.hip", "ppo_resmlp512.hip")]
     for k, src in enumerate(srcs):   # the sources compile side by side
         obj = os.path.join(objdir, os.path.basename(SRCS[k]) + ".o")
         per_src = per_source_flags(os.path.basename(SRCS[k]))

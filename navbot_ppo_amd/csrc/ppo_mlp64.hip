@@ -669,14 +669,15 @@ __global__ __launch_bounds__(64 * Pad<IN>::NW) void mlp64_pass_w(const float* __
 
 // both nets of one epoch in one launch (single-GPU path): the actor's tiles, then the critic's, by the same workgroups
 template <int IN, bool F16>
-__global__ __launch_bounds__(64 * Pad<IN>::NW) void mlp64_pass_both(const float* __restrict__ params, const void* __restrict__ obs,
+__global__ __launch_bounds__(64 * Pad<IN>::NW) void NAVPPO_KL_KERNEL(mlp64_pass_both)(const float* __restrict__ params, const void* __restrict__ obs,
                                                              const float* __restrict__ act, const float* __restrict__ logp_old,
                                                              const float* __restrict__ rtg, const float* __restrict__ adv,
                                                              long long M, float var, float clip, float inv_n,
                                                              float* __restrict__ partial_a, float* __restrict__ stats_partial_a,
                                                              float* __restrict__ partial_c, float* __restrict__ stats_partial_c,
-                                                             float* __restrict__ grad, float* __restrict__ stats) {
+                                                             float* __restrict__ grad, float* __restrict__ stats NAVPPO_KL_PARAM) {
     __shared__ __attribute__((aligned(16))) SmemW<IN> sm;
+    NAVPPO_KL_GATE();
     pass_body<true, false, IN, F16>(sm, params, obs, act, logp_old, rtg, adv, M, var, clip, inv_n, partial_a, stats_partial_a, grad,
                                     stats);
     __syncthreads();
@@ -1263,13 +1264,14 @@ __device__ __forceinline__ void pass_body_x3(SmemX<IN>& sm, const float* __restr
 
 // both nets of one epoch in one launch; net_mask: bit 0 = actor, bit 1 = critic (the one-net launches of the multi-GPU pipeline)
 template <int IN>
-__global__ __launch_bounds__(64 * XPad<IN>::NW) void mlp64_pass_both_x3(const float* __restrict__ params, const unsigned char* __restrict__ prep,
+__global__ __launch_bounds__(64 * XPad<IN>::NW) void NAVPPO_KL_KERNEL(mlp64_pass_both_x3)(const float* __restrict__ params, const unsigned char* __restrict__ prep,
                                                                 const float* __restrict__ act, const float* __restrict__ logp_old,
                                                                 const float* __restrict__ rtg, const float* __restrict__ adv,
                                                                 long long M, float var, float clip, float inv_n, int net_mask,
                                                                 float* __restrict__ partial_a, float* __restrict__ stats_partial_a,
-                                                                float* __restrict__ partial_c, float* __restrict__ stats_partial_c) {
+                                                                float* __restrict__ partial_c, float* __restrict__ stats_partial_c NAVPPO_KL_PARAM) {
     __shared__ __attribute__((aligned(16))) SmemX<IN> sm;
+    NAVPPO_KL_GATE();
     if (net_mask & 1) pass_body_x3<true, IN>(sm, params, prep, act, logp_old, rtg, adv, M, var, clip, inv_n, partial_a, stats_partial_a);
     if (net_mask == 3) __syncthreads();
     if (net_mask & 2) pass_body_x3<false, IN>(sm, params + Layout<IN>::P_ACTOR, prep, act, logp_old, rtg, adv, M, var, clip, inv_n, partial_c, stats_partial_c);
@@ -1289,12 +1291,13 @@ __global__ __launch_bounds__(64 * XPad<IN>::NW) void mlp64_pass_both_x3(const fl
 constexpr int kRedGroups = 16;   // row groups per block: 1024 threads, every thread sums n_blocks / 16 rows, 4 loads in flight
 constexpr int kGnSlots = 256;    // per (parity, net): one slot per block of reduce_adam (<= 235 blocks at 42 columns)
 template <bool ADAM>
-__global__ __launch_bounds__(64 * kRedGroups) void reduce_adam(const float* __restrict__ partial_a, const float* __restrict__ stats_partial_a,
+__global__ __launch_bounds__(64 * kRedGroups) void NAVPPO_KL_KERNEL(reduce_adam)(const float* __restrict__ partial_a, const float* __restrict__ stats_partial_a,
                                                    const float* __restrict__ partial_c, const float* __restrict__ stats_partial_c,
                                                    int n_blocks, float inv_n, float* __restrict__ grad, float* __restrict__ stats,
                                                    float* __restrict__ params, float* __restrict__ m, float* __restrict__ v,
                                                    float lr, float beta1, float beta2, float eps, float bc1, float bc2_sqrt,
-                                                   int pa, int pc, int q_begin, int q_end, float* __restrict__ gn, int parity) {
+                                                   int pa, int pc, int q_begin, int q_end, float* __restrict__ gn, int parity NAVPPO_KL_PARAM) {
+    NAVPPO_KL_GATE();
     // gn / parity (whole-update epochs only; parity < 0: off): the squared gradient norms per net, for the per-epoch MEANS the reference
     // logs (ppo.py:351-352, 389-390: clip_grad_norm_(inf) of each net in every epoch, averaged) without a norm launch per epoch and
     // without atomics: every block leaves the sums of its 64 squared gradients (actor part, critic part) in slot `parity`, and block 0
@@ -1359,6 +1362,7 @@ __global__ __launch_bounds__(64 * kRedGroups) void reduce_adam(const float* __re
     }
 }
 
+#ifndef NAVPPO_KL_TU   // (to the end of the file but for the launch plan: not part of the gated twins' translation unit, navppo_internal.h)
 // torch.optim.Adam's update on a flat buffer, gradient pre-scaled (multi-GPU: grad = all-reduced sum x 1 / world)
 __global__ void adam_step_kernel(float* __restrict__ params, const float* __restrict__ grad, float* __restrict__ m,
                                  float* __restrict__ v, int n, float grad_scale, float lr, float beta1, float beta2, float eps,
@@ -1388,12 +1392,20 @@ __device__ __forceinline__ float clip_block_sum(float s, float (&red)[kClipThrea
 __device__ __forceinline__ float clip_coef(float s, float max_norm) {
     return isfinite(s) ? fminf(1.0f, max_norm / (sqrtf(s) + 1e-6f)) : 0.f;
 }
-__global__ __launch_bounds__(kClipThreads) void clip_adam_kernel(float* __restrict__ params, float* __restrict__ grad, float* __restrict__ m,
-                                                                 float* __restrict__ v, int n, int n_first, float grad_scale, float max_norm,
-                                                                 float lr, float beta1, float beta2, float eps, float bc1, float bc2_sqrt,
-                                                                 const float* slots, int n_slots, int slot_stride, int slot_pitch,
-                                                                 float* clip_stats) {
+// KL (clip_adam_kl_kernel): the decision of navppo_internal.h in front of the step -- trip: no net is stepped, both coefficients are 0
+template <bool KL>
+__device__ __forceinline__ void clip_adam_body(float* __restrict__ params, float* __restrict__ grad, float* __restrict__ m,
+                                               float* __restrict__ v, int n, int n_first, float grad_scale, float max_norm,
+                                               float lr, float beta1, float beta2, float eps, float bc1, float bc2_sqrt,
+                                               const float* slots, int n_slots, int slot_stride, int slot_pitch,
+                                               float* clip_stats, const float* kl_ptr, float kl_limit, float* kl_state, int step) {
     __shared__ float red[kClipThreads / 64];
+    float kl = 0.f;
+    bool trip = false;
+    if constexpr (KL) {
+        kl = *kl_ptr;
+        trip = !(kl <= kl_limit);   // a NaN trips
+    }
     float sa = 0.f, sc = 0.f;
     for (int b = threadIdx.x; b < n_slots; b += kClipThreads) {
         const int ja = b, jc = slot_stride + b;
@@ -1402,9 +1414,9 @@ __global__ __launch_bounds__(kClipThreads) void clip_adam_kernel(float* __restri
     }
     sa = clip_block_sum(sa, red);
     sc = clip_block_sum(sc, red);
-    const float ca = clip_coef(sa, max_norm), cc = clip_coef(sc, max_norm);
+    const float ca = trip ? 0.f : clip_coef(sa, max_norm), cc = trip ? 0.f : clip_coef(sc, max_norm);
     const int q = blockIdx.x * kClipThreads + threadIdx.x;
-    if (q < n) {
+    if (q < n && !trip) {
         const bool actor = q < n_first;
         if (isfinite(actor ? sa : sc)) {   // else: parameters and moments of this net are not written at all
             const float gr = (grad[q] * grad_scale) * (actor ? ca : cc);
@@ -1419,14 +1431,41 @@ __global__ __launch_bounds__(kClipThreads) void clip_adam_kernel(float* __restri
         }
         clip_stats[2] = ca;
         clip_stats[3] = cc;
+        if constexpr (KL) {
+            if (trip) {
+                kl_state[0] = 1.f;
+                kl_state[2] = kl;
+                kl_state[3] = (float)step;
+            } else {
+                kl_state[1] += 1.f;
+            }
+        }
     }
+}
+__global__ __launch_bounds__(kClipThreads) void clip_adam_kernel(float* __restrict__ params, float* __restrict__ grad, float* __restrict__ m,
+                                                                 float* __restrict__ v, int n, int n_first, float grad_scale, float max_norm,
+                                                                 float lr, float beta1, float beta2, float eps, float bc1, float bc2_sqrt,
+                                                                 const float* slots, int n_slots, int slot_stride, int slot_pitch,
+                                                                 float* clip_stats) {
+    clip_adam_body<false>(params, grad, m, v, n, n_first, grad_scale, max_norm, lr, beta1, beta2, eps, bc1, bc2_sqrt, slots, n_slots, slot_stride,
+                          slot_pitch, clip_stats, nullptr, 0.f, nullptr, 0);
+}
+// (the flag block 0 sets on a trip may already be visible to a block of the SAME launch that starts later: that block returns at the
+// gate instead of deriving the trip itself -- either way it writes nothing)
+__global__ __launch_bounds__(kClipThreads) void clip_adam_kl_kernel(float* __restrict__ params, float* __restrict__ grad, float* __restrict__ m,
+                                                                    float* __restrict__ v, int n, int n_first, float grad_scale, float max_norm,
+                                                                    float lr, float beta1, float beta2, float eps, float bc1, float bc2_sqrt,
+                                                                    const float* slots, int n_slots, int slot_stride, int slot_pitch,
+                                                                    float* clip_stats, const float* kl_ptr, float kl_limit, float* kl_state, int step) {
+    if (navppo_kl_stopped(kl_state)) return;
+    clip_adam_body<true>(params, grad, m, v, n, n_first, grad_scale, max_norm, lr, beta1, beta2, eps, bc1, bc2_sqrt, slots, n_slots, slot_stride,
+                         slot_pitch, clip_stats, kl_ptr, kl_limit, kl_state, step);
 }
 
 // navppo_adam_step_clipped: the squared norms of grad x grad_scale over [0, n_first) and [n_first, n) into out[0], out[1]; ONE block
 // (the buffer is 43 KB or 400 KB and an all-reduce ran just before), fixed order
 constexpr int kNormThreads = 1024;
-__global__ __launch_bounds__(kNormThreads) void sqnorm2_kernel(const float* __restrict__ grad, int n, int n_first, float grad_scale,
-                                                               float* __restrict__ out) {
+__device__ __forceinline__ void sqnorm2_body(const float* __restrict__ grad, int n, int n_first, float grad_scale, float* __restrict__ out) {
     __shared__ float red[2][kNormThreads / 64];
     float sa = 0.f, sc = 0.f;
     for (int q = threadIdx.x; q < n; q += kNormThreads) {
@@ -1449,6 +1488,15 @@ __global__ __launch_bounds__(kNormThreads) void sqnorm2_kernel(const float* __re
         for (int k = 0; k < kNormThreads / 64; ++k) t += red[threadIdx.x][k];
         out[threadIdx.x] = t;
     }
+}
+__global__ __launch_bounds__(kNormThreads) void sqnorm2_kernel(const float* __restrict__ grad, int n, int n_first, float grad_scale,
+                                                               float* __restrict__ out) {
+    sqnorm2_body(grad, n, n_first, grad_scale, out);
+}
+__global__ __launch_bounds__(kNormThreads) void sqnorm2_kl_kernel(const float* __restrict__ grad, int n, int n_first, float grad_scale,
+                                                                  float* __restrict__ out, const float* __restrict__ kl_state) {
+    if (navppo_kl_stopped(kl_state)) return;
+    sqnorm2_body(grad, n, n_first, grad_scale, out);
 }
 
 // ---------------------------------------------------------------- rollout-time policy step (PPO.get_action, ppo.py:673-706)
@@ -1565,16 +1613,24 @@ __global__ __launch_bounds__(kSumBlocks) void episode_sums_final(const double* _
 }
 
 thread_local std::string g_err;
+#endif   // NAVPPO_KL_TU
 
 }  // namespace
 
+#ifndef NAVPPO_KL_TU
 void navppo_set_error(const char* msg) { g_err = msg ? msg : ""; }
 
 void navppo_launch_clip_adam(float* params, float* grad, float* m, float* v, int n, int n_first, float grad_scale, float max_norm, float lr,
                              float beta1, float beta2, float eps, int step, const float* slots, int n_slots, int slot_stride, int slot_pitch,
-                             float* clip_stats, void* stream) {
+                             float* clip_stats, void* stream, const float* kl, float kl_limit, float* kl_state) {
     const float bc1 = (float)(1.0 - std::pow((double)beta1, (double)step));
     const float bc2_sqrt = (float)std::sqrt(1.0 - std::pow((double)beta2, (double)step));
+    if (kl_state) {
+        hipLaunchKernelGGL(clip_adam_kl_kernel, dim3((unsigned)((n + kClipThreads - 1) / kClipThreads)), dim3(kClipThreads), 0, (hipStream_t)stream,
+                           params, grad, m, v, n, n_first, grad_scale, max_norm, lr, beta1, beta2, eps, bc1, bc2_sqrt, slots, n_slots, slot_stride,
+                           slot_pitch, clip_stats, kl, kl_limit, kl_state, step);
+        return;
+    }
     hipLaunchKernelGGL(clip_adam_kernel, dim3((unsigned)((n + kClipThreads - 1) / kClipThreads)), dim3(kClipThreads), 0, (hipStream_t)stream, params,
                        grad, m, v, n, n_first, grad_scale, max_norm, lr, beta1, beta2, eps, bc1, bc2_sqrt, slots, n_slots, slot_stride, slot_pitch,
                        clip_stats);
@@ -1592,6 +1648,7 @@ size_t navppo_mlp64_workspace_bytes(int32_t obs_dim) {
 
 }  // extern "C"
 #pragma GCC visibility pop
+#endif   // NAVPPO_KL_TU
 
 namespace {
 
@@ -1643,6 +1700,7 @@ PassPlan plan_pass(void* workspace_dev, int64_t n_samples, int32_t obs_dim) {
 
 }  // namespace
 
+#ifndef NAVPPO_KL_TU
 #pragma GCC visibility push(default)
 extern "C" {
 
@@ -1751,6 +1809,34 @@ int navppo_adam_step_clipped(float* params_dev, float* grad_dev, float* adam_m_d
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         g_err = std::string("navppo_adam_step_clipped: ") + hipGetErrorString(e);
+        return -2;
+    }
+    return 0;
+}
+
+int navppo_adam_step_kl(float* params_dev, float* grad_dev, float* adam_m_dev, float* adam_v_dev, int64_t n, int64_t n_first,
+                        float grad_scale, float max_norm, float lr, float beta1, float beta2, float eps, int32_t step,
+                        float* clip_stats_dev, float kl_limit, float* kl_state_dev, const float* kl_dev, void* stream) {
+    if (!params_dev || !grad_dev || !adam_m_dev || !adam_v_dev || n < 1 || n > INT32_MAX || n_first < 0 || n_first > n || step < 1 || !clip_stats_dev ||
+        !kl_dev) {
+        g_err = "navppo_adam_step_kl: bad argument (0 <= n_first <= n, clip_stats_dev [4], kl_dev [1])";
+        return -1;
+    }
+    if (!navppo_max_norm_ok(max_norm)) {
+        g_err = "navppo_adam_step_kl: max_norm must be > 0 (+inf allowed)";
+        return -1;
+    }
+    if (!navppo_kl_limit_ok(kl_limit) || !kl_state_dev) {
+        g_err = "navppo_adam_step_kl: kl_limit must be > 0 (+inf allowed) and kl_state_dev [4] not null";
+        return -1;
+    }
+    hipLaunchKernelGGL(sqnorm2_kl_kernel, dim3(1), dim3(kNormThreads), 0, (hipStream_t)stream, (const float*)grad_dev, (int)n, (int)n_first, grad_scale,
+                       clip_stats_dev, (const float*)kl_state_dev);
+    navppo_launch_clip_adam(params_dev, grad_dev, adam_m_dev, adam_v_dev, (int)n, (int)n_first, grad_scale, max_norm, lr, beta1, beta2, eps, step,
+                            clip_stats_dev, 1, 1, 8, clip_stats_dev, stream, kl_dev, kl_limit, kl_state_dev);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        g_err = std::string("navppo_adam_step_kl: ") + hipGetErrorString(e);
         return -2;
     }
     return 0;
@@ -2023,3 +2109,4 @@ int navppo_mlp64_act(const float* actor_params_dev, const void* obs_dev, int32_t
 
 }  // extern "C"
 #pragma GCC visibility pop
+#endif   // NAVPPO_KL_TU

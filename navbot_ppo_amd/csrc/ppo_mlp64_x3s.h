@@ -853,13 +853,14 @@ __device__ __forceinline__ void pass_body(SmemS& sm, const float* __restrict__ p
 }  // namespace x3s
 
 // both nets of one epoch in one launch (net_mask as mlp64_pass_both_x3), 16-column rows
-__global__ __launch_bounds__(64 * x3s::SW) void mlp64_pass_both_x3s(const float* __restrict__ params, const unsigned char* __restrict__ prep,
+__global__ __launch_bounds__(64 * x3s::SW) void NAVPPO_KL_KERNEL(mlp64_pass_both_x3s)(const float* __restrict__ params, const unsigned char* __restrict__ prep,
                                                                     const float* __restrict__ act, const float* __restrict__ logp_old,
                                                                     const float* __restrict__ rtg, const float* __restrict__ adv,
                                                                     long long M, float var, float clip, float inv_n, int net_mask,
                                                                     float* __restrict__ partial_a, float* __restrict__ stats_partial_a,
-                                                                    float* __restrict__ partial_c, float* __restrict__ stats_partial_c) {
+                                                                    float* __restrict__ partial_c, float* __restrict__ stats_partial_c NAVPPO_KL_PARAM) {
     __shared__ __attribute__((aligned(128))) x3s::SmemS sm;
+    NAVPPO_KL_GATE();
     if (net_mask & 1) x3s::pass_body<true>(sm, params, prep, act, logp_old, rtg, adv, M, var, clip, inv_n, partial_a, stats_partial_a);
     if (net_mask == 3) __syncthreads();
     if (net_mask & 2) x3s::pass_body<false>(sm, params + Layout<16>::P_ACTOR, prep, act, logp_old, rtg, adv, M, var, clip, inv_n, partial_c, stats_partial_c);

@@ -238,11 +238,12 @@ struct FwdSmem {
 // partials of resmlp_fwd<16> (p1) instead of by a streaming kernel of its own (0.25 ms per epoch); the slice-0 workgroups
 // store it to h1buf for the kernels behind.
 template <int IN>
-__global__ __launch_bounds__(kThreads) void resmlp_fwd(const float* __restrict__ params, int net_base, int n_nets,
+__global__ __launch_bounds__(kThreads) void NAVPPO_KL_KERNEL(resmlp_fwd)(const float* __restrict__ params, int net_base, int n_nets,
                                                        const void* __restrict__ obs, const float* __restrict__ p1,
                                                        float* __restrict__ h1buf, long long n, int groups,
-                                                       float* __restrict__ pout, int obs_f16) {
+                                                       float* __restrict__ pout, int obs_f16 NAVPPO_KL_PARAM) {
     __shared__ __attribute__((aligned(16))) FwdSmem<IN> sm;
+    NAVPPO_KL_GATE();
     constexpr int S2 = HS + 4, NB = IN / 16;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), l15 = lane & 15, q = lane >> 4;
     const WG wg = decode_block(blockIdx.x, n_nets, groups, NSLF);   // wg.sl: the PAIR of slices FSP wg.sl, FSP wg.sl + 1
@@ -447,11 +448,12 @@ static_assert(sizeof(BwdSmem<32, 8>) <= 160 * 1024 && sizeof(BwdSmem<32, 4>) <= 
 // swapped: A = the lane's own eight X / dY registers split once per tile, B = the weight pieces), which the 8-wave build has no
 // registers for (66 -> 125 spilled).
 template <int IN, int NST, int NWV>
-__global__ __launch_bounds__(64 * NWV) void resmlp_bwd(const float* __restrict__ params, int n_nets, const void* __restrict__ obs,
+__global__ __launch_bounds__(64 * NWV) void NAVPPO_KL_KERNEL(resmlp_bwd)(const float* __restrict__ params, int n_nets, const void* __restrict__ obs,
                                                        const float* __restrict__ h1buf, const float* __restrict__ dypre,
                                                        long long n, int groups, float* __restrict__ wpart,
-                                                       float* __restrict__ qout, const float* __restrict__ qin, int obs_f16) {
+                                                       float* __restrict__ qout, const float* __restrict__ qin, int obs_f16 NAVPPO_KL_PARAM) {
     __shared__ __attribute__((aligned(16))) BwdSmem<IN, NWV> sm;
+    NAVPPO_KL_GATE();
     constexpr int S1 = IN + 4, NB = IN / 16;
     constexpr int kWaves = NWV, kThreads = 64 * NWV;   // (shadow the 8-wave constants of the file)
     constexpr bool X3 = BwdSmem<IN, NWV>::X3, KS = BwdSmem<IN, NWV>::KS;
@@ -906,13 +908,14 @@ __device__ __forceinline__ void block_sum_to_row(float (&acc)[NV], float* red /*
 // E2: h2, heads, PPO loss / MSE, dpre2, and the sample sums d(heads), db2b, statistics.  thread = (sample, 4 of the 32 units)
 // HEAD_ONLY: V = critic(obs).squeeze() only (ppo.py:275, :724).
 template <bool HEAD_ONLY>
-__global__ __launch_bounds__(kEThreads) void resmlp_e2(const float* __restrict__ params, int net_base, const void* __restrict__ obs,
+__global__ __launch_bounds__(kEThreads) void NAVPPO_KL_KERNEL(resmlp_e2)(const float* __restrict__ params, int net_base, const void* __restrict__ obs,
                                                        const float* __restrict__ h1buf, const float* __restrict__ p2,
                                                        const float* __restrict__ act, const float* __restrict__ logp_old,
                                                        const float* __restrict__ rtg, const float* __restrict__ adv, long long n,
                                                        float var, float clip, float inv_n, float* __restrict__ dy2,
-                                                       float* __restrict__ epart, float* __restrict__ v_out, int obs_f16) {
+                                                       float* __restrict__ epart, float* __restrict__ v_out, int obs_f16 NAVPPO_KL_PARAM) {
     __shared__ float red[(kEThreads / 64) * 8 * 17];
+    NAVPPO_KL_GATE();
     const int net_i = blockIdx.y, net = net_base + net_i;
     const bool actor = net == 0;
     const float* __restrict__ pn = params + (net ? rp::P_ACTOR : 0);
@@ -1019,11 +1022,12 @@ __global__ __launch_bounds__(kEThreads) void resmlp_e2(const float* __restrict__
 // step in place (ppo.py:116-117,381,392: betas (0.9, 0.999), eps 1e-8, no weight decay).
 constexpr int kRedGroups = 16;
 template <bool ADAM>
-__global__ __launch_bounds__(64 * kRedGroups) void resmlp_reduce(const float* __restrict__ wpart, int w_rows1, int w_rows2, const float* __restrict__ epart,
+__global__ __launch_bounds__(64 * kRedGroups) void NAVPPO_KL_KERNEL(resmlp_reduce)(const float* __restrict__ wpart, int w_rows1, int w_rows2, const float* __restrict__ epart,
                                                                   int e_rows, float inv_n, float* __restrict__ grad, float* __restrict__ stats,
                                                                   float* __restrict__ params, float* __restrict__ m, float* __restrict__ v,
                                                                   float lr, float beta1, float beta2, float eps, float bc1, float bc2_sqrt,
-                                                                  float* __restrict__ gnbase, int parity) {
+                                                                  float* __restrict__ gnbase, int parity NAVPPO_KL_PARAM) {
+    NAVPPO_KL_GATE();
     // gnbase / parity: the per-net squared gradient norms of the epoch BEFORE into stats[3] / stats[7] (reduce_adam of ppo_mlp64.hip has
     // the scheme); the slots are columns 0 .. 7 of the streaming kernels' partial rows (those kernels write columns >= EC_B2B)
     auto gn_slot = [&](const int par, const int net, const int b) -> float* {
@@ -1093,6 +1097,7 @@ __global__ __launch_bounds__(64 * kRedGroups) void resmlp_reduce(const float* __
     }
 }
 
+#ifndef NAVPPO_KL_TU   // (down to the host side: not part of the gated twins' translation unit, navppo_internal.h)
 // ---------------------------------------------------------------- rollout-time policy step (PPO.get_action, ppo.py:673-706)
 // One workgroup = 16 envs on 8 waves: csrc/resmlp_policy.h (shared with the persistent rollout kernel of navsim.hip: same bits).
 constexpr int kActEnvs = resmlp::kPolEnvs;
@@ -1129,6 +1134,7 @@ __global__ __launch_bounds__(kThreads) void resmlp_act(const float* __restrict__
     }
 }
 
+#endif   // NAVPPO_KL_TU
 // ---------------------------------------------------------------- host side
 thread_local std::string g_err;
 
@@ -1174,6 +1180,7 @@ bool launch_ok(const char* what) {
     return true;
 }
 
+#ifndef NAVPPO_KL_TU   // (to the end of the file: ppo_resmlp512_kl.hip has the gated epoch's launches and entry point)
 // forward of `n_nets` nets starting at net_base (0 = actor, 1 = critic) up to the partial sums of rb2
 void launch_forward(const Plan& p, const float* params, int net_base, int n_nets, const void* obs, int obs_f16, int64_t n, hipStream_t st) {
     // (a forward workgroup = a PAIR of slices: FSP times the groups on the same number of workgroups)
@@ -1235,9 +1242,11 @@ int loss_grad_impl(const char* name, bool adam, float* params, const void* obs, 
     }
     return launch_ok(name) ? 0 : -2;
 }
+#endif   // NAVPPO_KL_TU
 
 }  // namespace
 
+#ifndef NAVPPO_KL_TU
 #pragma GCC visibility push(default)
 extern "C" {
 
@@ -1324,3 +1333,4 @@ int navppo_resmlp512_act(const float* actor_params_dev, const void* obs_dev, int
 
 }  // extern "C"
 #pragma GCC visibility pop
+#endif   // NAVPPO_KL_TU

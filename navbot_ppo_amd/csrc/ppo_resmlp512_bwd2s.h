@@ -144,12 +144,13 @@ __device__ __forceinline__ u32x4 cat(const u32x2 lo, const u32x2 hi) { return u3
 
 // OBS_F16: the observation rows are float16 (navsim_cfg.obs_f16) -- a template parameter, not an argument: the stream has no room for branches
 template <bool OBS_F16>
-__global__ __launch_bounds__(64 * b2s::SW) void resmlp_bwd2s(const float* __restrict__ params, int n_nets, const void* __restrict__ obs,
+__global__ __launch_bounds__(64 * b2s::SW) void NAVPPO_KL_KERNEL(resmlp_bwd2s)(const float* __restrict__ params, int n_nets, const void* __restrict__ obs,
                                                              const float* __restrict__ h1buf, const float* __restrict__ dypre,
                                                              long long n, int groups, float* __restrict__ wpart,
-                                                             float* __restrict__ qout) {
+                                                             float* __restrict__ qout NAVPPO_KL_PARAM) {
     using namespace b2s;
     __shared__ __attribute__((aligned(128))) Smem sm;
+    NAVPPO_KL_GATE();
     constexpr int IN = 32;
     constexpr int kWv = SW, kThr = 64 * SW;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), l15 = lane & 15, q = lane >> 4;

@@ -12,7 +12,8 @@ Same flag names and defaults; what they mean on the batched simulator:
   --use_external_sampler  start/goal from the curated GoalSpawnSampler tables (parsed but never wired in the reference)
 Additions (not in the reference): --n_envs, --policy, --map, --seed, --eval_persistent (with --eval: one launch instead of the
 stepping loop), --eval_every K (training: a persistent evaluation of --eval_episodes episodes every K iterations), --max_grad_norm
-(per-net gradient clipping + non-finite guard inside the update).  Vision flags are accepted and refused (the camera
+(per-net gradient clipping + non-finite guard inside the update), --target_kl (stop an update's remaining epochs once approx_kl
+exceeds 1.5 x the target).  Vision flags are accepted and refused (the camera
 modality is outside the LiDAR hot path); --mode test maps to --eval (the reference's test path is broken).
 """
 import argparse
@@ -52,6 +53,9 @@ def get_args(argv=None):
     p.add_argument("--max_grad_norm", type=float, default=None,
                    help="clip each net's gradient to this L2 norm in every epoch and skip a net's step when its gradient is not finite "
                         "(on the device, inside the fused update); default: off, as in the reference")
+    p.add_argument("--target_kl", type=float, default=None,
+                   help="stop an update -- both nets -- before the optimiser step of the first epoch whose approx_kl exceeds 1.5 x this "
+                        "(decided on the device inside the fused update; the remaining epochs cost their launches only); default: off")
     args = p.parse_args(argv)
     if args.output_dir is None:
         args.output_dir = os.path.join(os.getcwd(), "runs")
@@ -110,7 +114,8 @@ def main(argv=None):
                  seed=args.seed, env_id_base=lo, device=ctx.device, sampler=sampler)
     cfg = ppo.PPOConfig(rollout_len=rollout, max_episode_steps=args.timesteps_per_episode, policy=args.policy, seed=args.seed,
                         save_freq=args.save_every_iterations, output_dir=args.output_dir, method_name=args.method_name,
-                        eval_every=args.eval_every, eval_episodes=args.eval_episodes, max_grad_norm=args.max_grad_norm)
+                        eval_every=args.eval_every, eval_episodes=args.eval_episodes, max_grad_norm=args.max_grad_norm,
+                        target_kl=args.target_kl)
     trainer = ppo.PPOTrainer(env, cfg, ctx)
     if args.resume or args.actor_model:  # main.py:52-89
         pa = args.actor_model or ev.find_latest_checkpoint(args.output_dir, args.method_name, "actor")

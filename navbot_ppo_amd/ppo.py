@@ -67,6 +67,11 @@ class PPOConfig:
     # gradient is clipped to this L2 norm (torch's clip_grad_norm_) before its Adam step, and a net whose gradient is not finite
     # is not stepped at all (parameters and Adam moments untouched) -- on the device, inside the fused update (navppo_*_clipped)
     max_grad_norm: float = None
+    # None = the reference: every update runs all its epochs.  A number > 0: an update stops -- both nets, Stable-Baselines3's
+    # convention -- before the optimiser step of the first epoch whose approx_kl (the mean of (ratio - 1) - log ratio, ppo.py:326)
+    # exceeds 1.5 x target_kl; on one GPU the decision is taken on the device and the remaining queued epochs return at the entry of
+    # every kernel (navppo_*_update_epoch_kl).  Not with overlap_allreduce (the per-net pipeline has no place for the decision).
+    target_kl: float = None
     output_dir: str = ""                   # "" = no checkpoints / logs
     episode_csv_rows: int = 2000           # per-iteration cap on rows appended to <method>_train_episodes.csv (0 = off)
     tb_episode_rows: int = 256             # per-iteration cap on Episode_Rewards/train points in the TensorBoard file (0 = off)
@@ -240,6 +245,12 @@ class PPOUpdater:
         if cfg.max_grad_norm is not None and not float(cfg.max_grad_norm) > 0.0:   # (NaN fails the comparison too)
             raise ValueError(f"max_grad_norm {cfg.max_grad_norm!r}: None (off) or a number > 0")
         self.max_norm = None if cfg.max_grad_norm is None else float(cfg.max_grad_norm)
+        if cfg.target_kl is not None and not float(cfg.target_kl) > 0.0:   # (NaN fails the comparison too)
+            raise ValueError(f"target_kl {cfg.target_kl!r}: None (off) or a number > 0")
+        if cfg.target_kl is not None and cfg.overlap_allreduce:
+            raise ValueError("target_kl with overlap_allreduce=True: the per-net pipeline has no place for the stop decision")
+        self.kl_limit = None if cfg.target_kl is None else 1.5 * float(cfg.target_kl)   # Stable-Baselines3's factor
+        self.kl_state = None     # target_kl on, fused: [4] (stopped, steps taken, tripping approx_kl, its step) of the last update(), on the device
         self.clip_stats = None   # clipping on: [n_ep, 4] (s_actor, s_critic, coef_actor, coef_critic) of the last update(), on the device
         self.fused_resmlp512 = (on_gpu and cfg.policy == "resmlp512" and isinstance(actor, nets.ResMLPActor)
                                 and actor.rb1.f_in == 16 and actor.rb1.fc1.out_features == 512)
@@ -353,9 +364,10 @@ class PPOUpdater:
         if rc != 0:
             raise RuntimeError(f"navppo_mlp64_loss_grad_net failed: {L.navppo_last_error().decode()}")
 
-    def _fused_adam(self, grad_scale, lo=0, n=None, step=None, cstats=None):
+    def _fused_adam(self, grad_scale, lo=0, n=None, step=None, cstats=None, kl_dev=None):
         """Scale + Adam on the flat buffer, or on the slice [lo, lo + n) at optimiser step `step` (one net of the pipelined epoch).
-        cstats ([4], clipping on): navppo_adam_step_clipped -- per-net norm, guard and clip of the scaled gradient first."""
+        cstats ([4], clipping on): navppo_adam_step_clipped -- per-net norm, guard and clip of the scaled gradient first.
+        kl_dev ([1], target_kl on; with cstats): navppo_adam_step_kl -- the stop decision on the global approx_kl in front of that."""
         import ctypes as C
         from ._native import lib
         L = lib()
@@ -363,6 +375,16 @@ class PPOUpdater:
         if step is None:
             self._adam_t += 1
             step = self._adam_t
+        if kl_dev is not None:
+            n_ = int(self.fp.numel - lo if n is None else n)
+            rc = L.navppo_adam_step_kl(ptr(self.fp.flat), ptr(self.fp.grad), ptr(self._adam_m), ptr(self._adam_v), n_,
+                                       max(0, min(n_, self._n_actor - lo)), float(grad_scale), self._max_norm_arg(), float(self.cfg.lr),
+                                       0.9, 0.999, 1e-8, int(step), C.c_void_p(cstats.data_ptr()), self.kl_limit,
+                                       C.c_void_p(self.kl_state.data_ptr()), C.c_void_p(kl_dev.data_ptr()),
+                                       C.c_void_p(torch.cuda.current_stream().cuda_stream))
+            if rc != 0:
+                raise RuntimeError(f"navppo_adam_step_kl failed: {L.navppo_last_error().decode()}")
+            return
         if cstats is not None:
             n_ = int(self.fp.numel - lo if n is None else n)
             rc = L.navppo_adam_step_clipped(ptr(self.fp.flat), ptr(self.fp.grad), ptr(self._adam_m), ptr(self._adam_v), n_,
@@ -459,17 +481,25 @@ class PPOUpdater:
             raise RuntimeError(f"{self.fused}_value failed: {L.navppo_last_error().decode()}")
         return out
 
+    def _max_norm_arg(self):
+        """max_norm of the *_clipped / *_kl entry points: +inf = no clipping (target_kl without max_grad_norm)"""
+        return math.inf if self.max_norm is None else self.max_norm
+
     def _fused_epoch(self, obs, acts, logp_old, rtg, adv, var, stats, cstats=None):
         """One epoch of ppo.py:305-392 on one GPU: losses, gradients and both Adam steps in four launches.  cstats ([4], clipping on):
-        the *_update_epoch_clipped entry point -- one more small launch that clips and steps behind the reduction."""
+        the *_update_epoch_clipped entry point -- one more small launch that clips and steps behind the reduction.  target_kl on (with
+        cstats): the *_update_epoch_kl entry point -- gated twins of the same launches, the stop decision in the step launch."""
         import ctypes as C
         from ._native import lib
         L = lib()
         ptr = lambda t: C.c_void_p(t.data_ptr())
         self._adam_t += 1
         name, oargs = (("navppo_mlp64_bf16x3", (self._prepared(obs), self.obs_dim)) if self.bf16x3 else (self.fused, self._obs_args(obs)))
-        clipped = () if cstats is None else (self.max_norm, ptr(cstats))
+        clipped = () if cstats is None else (self._max_norm_arg(), ptr(cstats))
         entry = name + ("_update_epoch" if cstats is None else "_update_epoch_clipped")
+        if self.kl_limit is not None:
+            clipped += (self.kl_limit, ptr(self.kl_state))
+            entry = name + "_update_epoch_kl"
         rc = getattr(L, entry)(ptr(self.fp.flat), *oargs, ptr(acts), ptr(logp_old), ptr(rtg), ptr(adv),
                                int(obs.shape[0]), float(var), float(self.cfg.clip), float(self.cfg.lr), 0.9,
                                0.999, 1e-8, int(self._adam_t), ptr(self._adam_m), ptr(self._adam_v),
@@ -525,6 +555,7 @@ class PPOUpdater:
         flat_before = self.fp.flat.clone()                     # for the parameter-delta diagnostics of ppo.py:402-403
         a_loss = c_loss = torch.zeros((), device=obs.device)   # n_updates_per_iteration == 0: nothing to report
         acc = torch.zeros(6, device=obs.device)                # sums over epochs of diagnostics
+        n_stat = n_ep                                          # rows the per-epoch means are taken over (target_kl: fewer after a stop)
         fused_gn_sq = None                                     # fused single-GPU path: [n_ep - 1, 2] squared per-net gradient norms
         net_gn = None                                          # PyTorch path: sums over epochs of the per-net gradient norms
         multi_gn = None                                        # fused multi-GPU path: sums over epochs of (actor, critic, total) norms of the mean gradient
@@ -538,7 +569,16 @@ class PPOUpdater:
                 self.prepare(obs)   # ALWAYS here: the rollout kernels fill the buffer behind torch's back (no version bump)
             if self._fhist.shape[0] < n_ep:
                 self._fhist = torch.zeros((n_ep, 8), dtype=torch.float32, device=self.device)
-        clipping = self.max_norm is not None
+        kl_on = self.kl_limit is not None
+        kl_steps, kl_stopped = n_ep, 0   # target_kl on: optimiser steps taken, and whether the update stopped early
+        # target_kl without max_grad_norm runs the clipped machinery at max_norm = +inf (the bits of the unclipped epochs) and reports
+        # the unclipped statistics' keys
+        clipping = self.max_norm is not None or kl_on
+        if kl_on and self.fused:   # zeroed once per update; afterwards only the library writes it
+            self.kl_state = torch.zeros(4, dtype=torch.float32, device=obs.device)
+            kl_t0 = self._adam_t
+            if multi:
+                kl_glob = torch.zeros((max(n_ep, 1), 2), dtype=torch.float32, device=obs.device)
         if clipping:   # every epoch's (s_actor, s_critic, coef_actor, coef_critic): filled on the device, read once after the loop
             self.clip_stats = torch.zeros((max(n_ep, 1), 4), dtype=torch.float32, device=obs.device)
         self._last_adv = adv   # (PPOTrainer._grad_guard's diagnostics)
@@ -555,7 +595,14 @@ class PPOUpdater:
                 elif multi:   # fused passes -> ONE all-reduce of the flat gradient (RCCL) -> scale + Adam in one launch
                     self._fused_loss_grad(obs, acts, logp_old, rtg, adv, var_f, stats=self._fhist[ep])
                     ctx.all_reduce_sum(self.fp.grad)
-                    if clipping:   # (the norms of the mean gradient are in the clip statistics)
+                    if kl_on:   # the global approx_kl = sum(kl_r n_r) / sum(n_r) in a 2-float collective of its own; the ungated passes
+                        # above run in every epoch, so a stop saves no time on this path -- it only keeps the weights where they were
+                        kg = kl_glob[ep]
+                        kg[0], kg[1] = self._fhist[ep, 1] * float(obs.shape[0]), float(obs.shape[0])
+                        ctx.all_reduce_sum(kg)
+                        kg[0] /= kg[1]
+                        self._fused_adam(1.0 / world, cstats=self.clip_stats[ep], kl_dev=kg)
+                    elif clipping:   # (the norms of the mean gradient are in the clip statistics)
                         self._fused_adam(1.0 / world, cstats=self.clip_stats[ep])
                     else:
                         with torch.no_grad():   # every epoch's norms of the MEAN gradient (two small launches beside an all-reduce)
@@ -566,13 +613,21 @@ class PPOUpdater:
                 else:
                     self._fused_epoch(obs, acts, logp_old, rtg, adv, var_f, self._fhist[ep], self.clip_stats[ep] if clipping else None)
                 if ep == n_ep - 1:
-                    h = self._fhist[:n_ep]
+                    k = n_ep   # epochs whose passes ran = steps taken + (1 if stopped): the rows the statistics are taken over
+                    if kl_on:   # (the update synchronises for its statistics below anyway)
+                        st = self.kl_state.tolist()
+                        kl_stopped, kl_steps = int(st[0] != 0.0), int(st[1])
+                        k = kl_steps + kl_stopped
+                        self._adam_t = kl_t0 + kl_steps   # Adam's bias correction counts steps TAKEN
+                    h = self._fhist[:k]
                     self.loss_history = h[:, 0:5:4].clone()   # columns 0 (actor loss) and 4 (critic loss)
+                    if k < n_ep:
+                        self.loss_history = torch.cat([self.loss_history, torch.full((n_ep - k, 2), math.nan, device=obs.device)])
                     hs = h.sum(0)
                     # multi-GPU: fp.grad holds the all-reduced SUM (the 1 / world scale is inside navppo_adam_step)
                     gn_last = self.fp.grad.norm() / world
                     if clipping:   # the pre-clip norms of every epoch, from the clip statistics (no previous-epoch slots involved)
-                        gn_sum = self.clip_stats[:n_ep, :2].sum(1).sqrt().sum()
+                        gn_sum = self.clip_stats[:k, :2].sum(1).sqrt().sum()
                     elif not multi and n_ep > 1:
                         # grad norms as the reference logs them -- every epoch's, averaged (ppo.py:351-352, 389-390) -- without a norm
                         # launch per epoch: the fused epoch leaves the squared per-net norms of the epoch BEFORE in columns 3 / 7 of
@@ -583,8 +638,9 @@ class PPOUpdater:
                         gn_sum = multi_gn[2]
                     else:   # (the pipelined multi-GPU epochs, one epoch: the last epoch's norm stands in)
                         gn_sum = gn_last * n_ep
-                    acc = torch.cat([hs[[0, 4, 1, 2]], torch.stack([gn_sum, V0.mean() * n_ep])])
-                    a_loss, c_loss = self.loss_history[-1, 0], self.loss_history[-1, 1]
+                    acc = torch.cat([hs[[0, 4, 1, 2]], torch.stack([gn_sum, V0.mean() * k])])
+                    a_loss, c_loss = self.loss_history[k - 1, 0], self.loss_history[k - 1, 1]
+                    n_stat = k
                 continue
             a_loss, c_loss, ratios, logp, _ = ppo_losses(self.actor, self.critic, obs, acts, logp_old, rtg, adv, var, cfg.clip)
             self.fp.grad.zero_()
@@ -592,10 +648,29 @@ class PPOUpdater:
             if multi:
                 ctx.all_reduce_sum(self.fp.grad)
                 self.fp.grad.div_(world)
-            if clipping:
+            trip = False
+            if kl_on:   # the check before the step, on the global approx_kl (weighted by the ranks' batch sizes); a NaN trips
+                with torch.no_grad():
+                    lr_ = logp.detach() - logp_old
+                    kg = torch.stack([((ratios.detach() - 1) - lr_).sum(), lr_.new_tensor(float(lr_.numel()))])
+                    if multi:
+                        ctx.all_reduce_sum(kg)
+                    trip = not (float(kg[0] / kg[1]) <= self.kl_limit)
+            if trip:   # neither net is stepped; the gradient stays unclipped, the coefficients are reported as 0
+                kl_steps, kl_stopped = ep, 1
+                with torch.no_grad():
+                    n_a_ = self.fp.module_numel[0]
+                    g_a, g_c = self.fp.grad[:n_a_], self.fp.grad[n_a_:]
+                    self.clip_stats[ep] = torch.stack([(g_a * g_a).sum(), (g_c * g_c).sum(), g_a.new_zeros(()), g_a.new_zeros(())])
+            elif self.max_norm is not None:
                 self._clip_and_step(ep)
             else:
                 self.opt.step()                                # ppo.py:381,392
+                if clipping:   # (target_kl without max_grad_norm: the norms of every epoch, coefficient 1)
+                    with torch.no_grad():
+                        n_a_ = self.fp.module_numel[0]
+                        g_a, g_c = self.fp.grad[:n_a_], self.fp.grad[n_a_:]
+                        self.clip_stats[ep] = torch.stack([(g_a * g_a).sum(), (g_c * g_c).sum(), g_a.new_ones(()), g_a.new_ones(())])
             with torch.no_grad():                              # ppo.py:323-336
                 lr_ = logp.detach() - logp_old
                 self.loss_history[ep] = torch.stack([a_loss.detach(), c_loss.detach()])
@@ -605,7 +680,11 @@ class PPOUpdater:
                 n_a_ = self.fp.module_numel[0]
                 g2 = torch.stack(torch._foreach_norm([self.fp.grad[:n_a_], self.fp.grad[n_a_:]]))
                 net_gn = g2 if net_gn is None else net_gn + g2
-        acc = acc / max(n_ep, 1)
+            if trip:   # the remaining epochs do not run: their loss_history rows are NaN
+                self.loss_history[ep + 1:] = math.nan
+                n_stat = ep + 1
+                break
+        acc = acc / max(n_stat, 1)
         if multi:
             ctx.all_reduce_sum(acc)
             acc = acc / world
@@ -616,21 +695,26 @@ class PPOUpdater:
             extra = extra * extra.new_tensor([1.0 / world, 1.0 / world, 1.0, 1.0])   # norms of the MEAN gradient, as on one GPU
         clip_cols = []
         if clipping:   # pre-clip norms of every epoch (their mean), share of clipped epochs, skipped steps; identical on every rank
-            cs = self.clip_stats[:n_ep]
+            cs = self.clip_stats[:n_stat]
             gn = cs[:, :2].sqrt()
-            if n_ep > 0:
+            if n_stat > 0:
                 extra = torch.cat([gn.mean(0), extra[2:]])
                 if not self.fused:
                     acc = torch.cat([acc[:4], cs[:, :2].sum(1).sqrt().mean().reshape(1), acc[5:]])
-            clip_cols = [(cs[:, 2:] < 1.0).float().sum(0) / max(n_ep, 1), (~torch.isfinite(cs[:, :2])).float().sum(0)]
-            if n_ep == 0:
+            clipped_ep = cs[:, 2:] < 1.0
+            if kl_stopped:   # the tripping epoch: coefficient 0 because the update stopped, not because anything was clipped or skipped
+                clipped_ep = clipped_ep[:-1]
+            clip_cols = [clipped_ep.float().sum(0) / max(n_stat, 1), (~torch.isfinite(cs[:, :2])).float().sum(0)]
+            if n_stat == 0:
                 clip_cols = [torch.zeros(2, device=obs.device)] * 2
+            if self.max_norm is None:   # target_kl alone: the keys of the unclipped statistics
+                clip_cols = []
         elif fused_gn_sq is not None:   # per-net norms: the mean over the epochs, like grad_norm (the reference's actor_grad_norm / critic_grad_norm)
             extra = torch.cat([(fused_gn_sq.sqrt().sum(0) + extra[:2]) / n_ep, extra[2:]])
         elif multi_gn is not None:
             extra = torch.cat([multi_gn[:2] / n_ep, extra[2:]])
         elif net_gn is not None:
-            extra = torch.cat([net_gn / max(n_ep, 1), extra[2:]])
+            extra = torch.cat([net_gn / max(n_stat, 1), extra[2:]])
         self.stats = dict(zip(["actor_loss", "critic_loss", "approx_kl", "clip_frac", "grad_norm", "value_mean",
                                "actor_grad_norm", "critic_grad_norm", "actor_param_delta", "critic_param_delta",
                                "grad_clip_frac_actor", "grad_clip_frac_critic", "skipped_steps_actor", "skipped_steps_critic"],
@@ -640,6 +724,8 @@ class PPOUpdater:
         for k in ("skipped_steps_actor", "skipped_steps_critic"):
             if k in self.stats:
                 self.stats[k] = int(self.stats[k])
+        if kl_on:   # steps taken (n_ep if the update never stopped) and whether it stopped; identical on every rank
+            self.stats["kl_stop_epoch"], self.stats["kl_stopped"] = int(kl_steps), int(kl_stopped)
         self.last_losses = (a_loss.detach(), c_loss.detach())
         return self.stats
 
@@ -1057,6 +1143,7 @@ class PPOTrainer:
                 "ppo/critic_param_delta": lg.get("critic_param_delta"),
                 "ppo/grad_clip_frac_actor": lg.get("grad_clip_frac_actor"), "ppo/grad_clip_frac_critic": lg.get("grad_clip_frac_critic"),
                 "ppo/skipped_steps_actor": lg.get("skipped_steps_actor"), "ppo/skipped_steps_critic": lg.get("skipped_steps_critic"),
+                "ppo/kl_stop_epoch": lg.get("kl_stop_epoch"), "ppo/kl_stopped": lg.get("kl_stopped"),   # (target_kl set)
                 **({"eval/success_rate": lg["eval_success"], "eval/collision_rate": lg["eval_collision"],
                     "eval/timeout_rate": lg["eval_timeout"], "eval/mean_return": lg["eval_return"],
                     "eval/mean_ep_length": lg["eval_length"], "time/eval": lg["eval_time"]} if "eval_success" in lg else {})}
@@ -1076,6 +1163,7 @@ class PPOTrainer:
         t0 = time.time()
         recs = [(k, float(v), it) for k, v in self.tb_scalars().items() if v is not None]
         hist = self.updater.loss_history.detach().cpu().numpy()
+        hist = hist[:int(self.updater.stats.get("kl_stop_epoch", hist.shape[0])) + int(self.updater.stats.get("kl_stopped", 0))]   # (rows of epochs that ran)
         for k in range(hist.shape[0]):
             recs.append(("Actor_loss/train", float(hist[k, 0]), self._tb_loss_steps + k))
             recs.append(("Critic_loss/train", float(hist[k, 1]), self._tb_loss_steps + k))
@@ -1108,6 +1196,7 @@ class PPOTrainer:
                     f"succ={lg['success_rate']:.3f} ep_len={lg['avg_ep_lens']:6.1f} a_loss={lg['actor_loss']:.4f} "
                     f"c_loss={lg['critic_loss']:.2f} kl={lg['approx_kl']:.4f} steps/s={lg['steps_per_sec']:.0f} "
                     f"(rollout {lg['rollout_time']:.3f}s update {lg['update_time']:.3f}s)"
+                    + (f" kl_stop_epoch={lg['kl_stop_epoch']} kl_stopped={lg['kl_stopped']}" if "kl_stop_epoch" in lg else "")
                     + (f" eval: succ={lg['eval_success']:.3f} coll={lg['eval_collision']:.3f} tmo={lg['eval_timeout']:.3f} "
                        f"ret={lg['eval_return']:.2f} len={lg['eval_length']:.1f} ({lg['eval_time']:.3f}s)"
                        if "eval_success" in lg else ""))

@@ -19,7 +19,7 @@ if per_src and build.flags_accepted(per_src):
     cflags += list(per_src)
 subprocess.check_call([build.hipcc()] + cflags + flags + ["-I", build.INC, "-I", os.path.join(build.HERE, "csrc"), "-c",
                                                          os.path.join(build.HERE, "csrc", SRC), "-o", obj])
-objs = [os.path.join(R, "build", "obj", f) for f in ("navsim.hip.o", "ppo_mlp64.hip.o", "ppo_resmlp512.hip.o") if f != SRC + ".o"] + [obj]
+objs = [os.path.join(R, "build", "obj", f) for f in [os.path.basename(x) + ".o" for x in build.SRCS] if f != SRC + ".o"] + [obj]
 out = os.path.join(R, "build", f"libnavsim_{name}.so")
 subprocess.check_call([build.hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-fvisibility=hidden"] + objs + ["-o", out])
 print(out)
