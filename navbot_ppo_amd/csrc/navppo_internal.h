@@ -1,8 +1,78 @@
 // navppo_internal.h -- shared by the translation units of libnavsim.so that implement include/navppo.h (not installed)
 #pragma once
 
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <string>
+
 // stores the message navppo_last_error() returns (thread-local, defined in ppo_mlp64.hip)
 void navppo_set_error(const char* msg);
+
+// ---------------------------------------------------------------- what the entry points' host code shares
+// an argument check failed (before any launch): "<entry point>: <what>" for navppo_last_error(), the return code -1
+inline int navppo_bad_args(const char* who, const char* what) {
+    navppo_set_error((std::string(who) + ": " + what).c_str());
+    return -1;
+}
+
+// behind the last launch of an entry point: 0, or "<entry point>: <HIP's message>" and -2
+inline int navppo_launched(const char* who) {
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) return 0;
+    navppo_set_error((std::string(who) + ": " + hipGetErrorString(e)).c_str());
+    return -2;
+}
+
+// How an epoch (or navppo_adam_step*) ends -- the four step modes of include/navppo.h:
+enum class NavppoMode {
+    kGrad,     // *_loss_grad[_net]: the reduction alone, nothing is stepped
+    kAdam,     // *_update_epoch, navppo_adam_step: Adam inside the reduction (or alone)
+    kClip,     // *_clipped: the reduction with its squared-norm slots, then one launch that clips and steps (navppo_launch_clip_adam)
+    kClipKl,   // *_kl: the gated twins of those launches, the KL decision in front of the clip (below)
+};
+
+// the batch of an epoch: actions, old log-probabilities, rewards-to-go and advantages of n samples; the policy's variance, PPO's clip
+struct NavppoBatch {
+    const float *act, *logp_old, *rtg, *adv;
+    int64_t n;
+    float var, clip;
+    bool ok() const { return act && logp_old && rtg && adv && n >= 1 && var > 0.f; }   // (a NaN variance fails)
+};
+
+// the optimiser's half of an entry point's arguments; a mode reads the members it needs (kGrad: none)
+struct NavppoStep {
+    float lr, beta1, beta2, eps;
+    int32_t step;                        // Adam's step count, >= 1
+    float *m, *v;                        // exp_avg, exp_avg_sq
+    float max_norm; float* clip_stats;   // kClip, kClipKl
+    float kl_limit; float* kl_state;     // kClipKl
+};
+
+// max_norm of the *_clipped entry points, kl_limit of the *_kl entry points: a positive number, +inf included (NaN fails)
+inline bool navppo_max_norm_ok(float max_norm) { return max_norm > 0.f; }
+inline bool navppo_kl_limit_ok(float kl_limit) { return kl_limit > 0.f; }
+
+// the step arguments of `mode`; 0, or the message and -1
+inline int navppo_check_step(const char* who, NavppoMode mode, const NavppoStep& s) {
+    if (mode == NavppoMode::kGrad) return 0;
+    if (!s.m || !s.v || s.step < 1) return navppo_bad_args(who, "bad argument (adam_m_dev, adam_v_dev not null, step >= 1)");
+    if (mode == NavppoMode::kAdam) return 0;
+    if (!navppo_max_norm_ok(s.max_norm) || !s.clip_stats)
+        return navppo_bad_args(who, "max_norm must be > 0 (+inf allowed) and clip_stats_dev [4] not null");
+    if (mode == NavppoMode::kClipKl && (!navppo_kl_limit_ok(s.kl_limit) || !s.kl_state))
+        return navppo_bad_args(who, "kl_limit must be > 0 (+inf allowed) and kl_state_dev [4] not null");
+    return 0;
+}
+
+// Adam's bias corrections at step count `step`: 1 - beta1^step and sqrt(1 - beta2^step), in double, rounded once
+struct NavppoBias {
+    float bc1, bc2_sqrt;
+};
+inline NavppoBias navppo_bias(float beta1, float beta2, int step) {
+    return {(float)(1.0 - std::pow((double)beta1, (double)step)), (float)std::sqrt(1.0 - std::pow((double)beta2, (double)step))};
+}
 
 // torch.optim.Adam's step (ppo.py:116-117,381,392: no weight decay, no amsgrad) on parameter q with gradient gr: exp_avg.lerp_(grad,
 // 1 - beta1), exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2), then the bias-corrected update.  ONE expression for every kernel
@@ -17,24 +87,18 @@ __device__ __forceinline__ void navppo_adam_apply(float* __restrict__ params, fl
     params[q] -= (lr / bc1) * (mm / denom);
 }
 
-// max_norm of the *_clipped entry points: a positive number, +inf included
-inline bool navppo_max_norm_ok(float max_norm) { return max_norm > 0.f; }
-
 // The second launch of a clipped epoch (clip_adam_kernel, ppo_mlp64.hip): per net (actor = [0, n_first), critic = [n_first, n)) the
 // squared norm s = sum of the net's `n_slots` squared-norm slots -- slot i of net k at slots[(j >> 3) * slot_pitch + (j & 7)],
 // j = k * slot_stride + i (slot_pitch 8: contiguous) -- added in ONE fixed order by every block; s not finite: the net is left alone,
 // coefficient 0; else coef = min(1, max_norm / (sqrt(s) + 1e-6)), grad = grad * grad_scale * coef, Adam on that.
 // clip_stats[0..3] = s_actor, s_critic, coef_actor, coef_critic.  `stream` is a hipStream_t.
-// kl_state != nullptr (the *_kl entry points, include/navppo.h "Early stop at a KL limit"): clip_adam_kl_kernel instead -- returns at
+// kl != nullptr (the *_kl entry points, include/navppo.h "Early stop at a KL limit"): clip_adam_kl_kernel instead -- returns at
 // its entry when kl_state[0] != 0; trips when !(*kl <= kl_limit): no net is stepped, clip_stats = (s_actor, s_critic, 0, 0), block 0
 // sets kl_state = (1, unchanged, *kl, step); else the step above, the same expression, and kl_state[1] += 1.  `kl` is a device scalar
 // an EARLIER launch wrote (stats_dev[1]): every block derives the same decision from the same bits, no block waits for another.
-void navppo_launch_clip_adam(float* params, float* grad, float* m, float* v, int n, int n_first, float grad_scale, float max_norm, float lr,
-                             float beta1, float beta2, float eps, int step, const float* slots, int n_slots, int slot_stride, int slot_pitch,
-                             float* clip_stats, void* stream, const float* kl = nullptr, float kl_limit = 0.f, float* kl_state = nullptr);
-
-// kl_limit of the *_kl entry points: a positive number, +inf included (NaN fails)
-inline bool navppo_kl_limit_ok(float kl_limit) { return kl_limit > 0.f; }
+// `s`: max_norm, Adam's arguments, clip_stats; kl != nullptr: s.kl_limit and s.kl_state as well.
+void navppo_launch_clip_adam(float* params, float* grad, int n, int n_first, float grad_scale, const NavppoStep& s, const float* slots,
+                             int n_slots, int slot_stride, int slot_pitch, void* stream, const float* kl = nullptr);
 
 // The gate of the *_kl kernels: one uniform read of kl_state[0] at kernel entry.  The flag is only ever written by the LAST launch of an
 // earlier epoch (clip_adam_kl_kernel), so every workgroup of a launch reads the same value; none of the gated kernels synchronises
@@ -42,22 +106,31 @@ inline bool navppo_kl_limit_ok(float kl_limit) { return kl_limit > 0.f; }
 __device__ __forceinline__ bool navppo_kl_stopped(const float* __restrict__ kl_state) { return kl_state[0] != 0.f; }
 
 // The gated twins of the update's kernels are the SAME text compiled a second time: ppo_mlp64_kl.hip / ppo_resmlp512_kl.hip include
-// ppo_mlp64.hip / ppo_resmlp512.hip with NAVPPO_KL_TU defined, and every kernel written with the three macros below is then
-// `name_kl`, takes kl_state as one more (last) argument and starts with the gate; the host code of the included file is compiled out.
+// ppo_mlp64.hip / ppo_resmlp512.hip with NAVPPO_KL_TU defined, and every kernel written with the first three macros below is then
+// `name_kl`, takes kl_state as one more (last) argument and starts with the gate.  The host code that launches them is compiled a
+// second time as well: the epoch function of each family (mlp64_epoch, loss_grad_impl) is ONE launch sequence, a template over
+// NavppoMode that launches NAVPPO_KL_KERNEL(name) with NAVPPO_KL_ARG(kl_state) behind the last argument -- so a grid or an argument
+// cannot change for the clipped epoch and not for the gated one.  A translation unit instantiates the modes it exports
+// (kNavppoKlTu: kClipKl there, the other three here), hence only their kernels; the rest of the included file's host code --
+// the entry points, the kernels that have no twin -- is compiled out of the twins' unit.
 // Without NAVPPO_KL_TU the macros vanish: the ungated kernels are textually what they were, in a translation unit of their own.
 // (Twins in the SAME translation unit changed the ungated kernels' listings: a helper that is not force-inlined then has two callers
 // and the inliner decides differently -- mlp64_pass_both_x3s went from 491 to 486 registers, mlp64_pass_both_x3<16> from 268 to 192
 // bytes of scratch -- and a hand-placed stream's listing is exactly what tests/test_isa_*.py pin: profiles/kl_gate_resources.txt.)
 #ifdef NAVPPO_KL_TU
+constexpr bool kNavppoKlTu = true;
 #define NAVPPO_KL_KERNEL(name) name##_kl
 #define NAVPPO_KL_PARAM , const float* __restrict__ kl_state
+#define NAVPPO_KL_ARG(kl_state) , (const float*)(kl_state)
 #define NAVPPO_KL_GATE() \
     do {                 \
         if (navppo_kl_stopped(kl_state)) return; \
     } while (0)
 #else
+constexpr bool kNavppoKlTu = false;
 #define NAVPPO_KL_KERNEL(name) name
 #define NAVPPO_KL_PARAM
+#define NAVPPO_KL_ARG(kl_state)
 #define NAVPPO_KL_GATE() \
     do {                 \
     } while (0)

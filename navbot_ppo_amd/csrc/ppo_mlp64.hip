@@ -1362,7 +1362,7 @@ __global__ __launch_bounds__(64 * kRedGroups) void NAVPPO_KL_KERNEL(reduce_adam)
     }
 }
 
-#ifndef NAVPPO_KL_TU   // (to the end of the file but for the launch plan: not part of the gated twins' translation unit, navppo_internal.h)
+#ifndef NAVPPO_KL_TU   // (to the end of the file but for the launch plan and mlp64_epoch: not part of the gated twins' translation unit, navppo_internal.h)
 // torch.optim.Adam's update on a flat buffer, gradient pre-scaled (multi-GPU: grad = all-reduced sum x 1 / world)
 __global__ void adam_step_kernel(float* __restrict__ params, const float* __restrict__ grad, float* __restrict__ m,
                                  float* __restrict__ v, int n, float grad_scale, float lr, float beta1, float beta2, float eps,
@@ -1620,20 +1620,17 @@ thread_local std::string g_err;
 #ifndef NAVPPO_KL_TU
 void navppo_set_error(const char* msg) { g_err = msg ? msg : ""; }
 
-void navppo_launch_clip_adam(float* params, float* grad, float* m, float* v, int n, int n_first, float grad_scale, float max_norm, float lr,
-                             float beta1, float beta2, float eps, int step, const float* slots, int n_slots, int slot_stride, int slot_pitch,
-                             float* clip_stats, void* stream, const float* kl, float kl_limit, float* kl_state) {
-    const float bc1 = (float)(1.0 - std::pow((double)beta1, (double)step));
-    const float bc2_sqrt = (float)std::sqrt(1.0 - std::pow((double)beta2, (double)step));
-    if (kl_state) {
-        hipLaunchKernelGGL(clip_adam_kl_kernel, dim3((unsigned)((n + kClipThreads - 1) / kClipThreads)), dim3(kClipThreads), 0, (hipStream_t)stream,
-                           params, grad, m, v, n, n_first, grad_scale, max_norm, lr, beta1, beta2, eps, bc1, bc2_sqrt, slots, n_slots, slot_stride,
-                           slot_pitch, clip_stats, kl, kl_limit, kl_state, step);
-        return;
-    }
-    hipLaunchKernelGGL(clip_adam_kernel, dim3((unsigned)((n + kClipThreads - 1) / kClipThreads)), dim3(kClipThreads), 0, (hipStream_t)stream, params,
-                       grad, m, v, n, n_first, grad_scale, max_norm, lr, beta1, beta2, eps, bc1, bc2_sqrt, slots, n_slots, slot_stride, slot_pitch,
-                       clip_stats);
+void navppo_launch_clip_adam(float* params, float* grad, int n, int n_first, float grad_scale, const NavppoStep& s, const float* slots,
+                             int n_slots, int slot_stride, int slot_pitch, void* stream, const float* kl) {
+    const NavppoBias bc = navppo_bias(s.beta1, s.beta2, s.step);
+    const dim3 grid((unsigned)((n + kClipThreads - 1) / kClipThreads));
+    if (kl)
+        hipLaunchKernelGGL(clip_adam_kl_kernel, grid, dim3(kClipThreads), 0, (hipStream_t)stream, params, grad, s.m, s.v, n, n_first, grad_scale,
+                           s.max_norm, s.lr, s.beta1, s.beta2, s.eps, bc.bc1, bc.bc2_sqrt, slots, n_slots, slot_stride, slot_pitch, s.clip_stats, kl,
+                           s.kl_limit, s.kl_state, s.step);
+    else
+        hipLaunchKernelGGL(clip_adam_kernel, grid, dim3(kClipThreads), 0, (hipStream_t)stream, params, grad, s.m, s.v, n, n_first, grad_scale,
+                           s.max_norm, s.lr, s.beta1, s.beta2, s.eps, bc.bc1, bc.bc2_sqrt, slots, n_slots, slot_stride, slot_pitch, s.clip_stats);
 }
 
 #pragma GCC visibility push(default)
@@ -1698,157 +1695,157 @@ PassPlan plan_pass(void* workspace_dev, int64_t n_samples, int32_t obs_dim) {
     return pl;
 }
 
+// the rows of an epoch: float32 / float16 observations (the f32-MFMA pass), or the bf16 pieces navppo_mlp64_bf16x3_prepare made of them
+struct Mlp64Rows {
+    const void* data;
+    int32_t dim, f16;
+    bool x3;
+};
+
+// THE launch sequence of the family: every *_loss_grad[_net] / *_update_epoch[_clipped | _kl] entry point, f32 and bf16x3, is this
+// function -- the checks, the plan, the pass (the one part the two arithmetics do not share) and one reduce / step tail.
+// net_mask 3: both nets; 1 / 2 (kGrad only): the actor's / the critic's pass and its slice of the reduction.
+template <NavppoMode MODE>
+int mlp64_epoch(const char* who, float* params, const Mlp64Rows& x, const NavppoBatch& b, int net_mask, const NavppoStep& s, float* grad,
+                float* stats, void* workspace, void* stream) {
+    static_assert((MODE == NavppoMode::kClipKl) == kNavppoKlTu, "the gated mode is the twins' translation unit's, the others are not");
+    if (net_mask < 1 || net_mask > 3 || (MODE != NavppoMode::kGrad && net_mask != 3)) return navppo_bad_args(who, "net is 0 (actor) or 1 (critic)");
+    if (!params || !x.data || !b.ok() || !grad || !stats || !workspace || (x.dim != 16 && x.dim != 42))
+        return navppo_bad_args(who, "bad argument (obs_dim is 16 or 42)");
+    if (!(x.x3 ? ((uintptr_t)x.data & 15) == 0 : obs_aligned(x.data, x.dim, x.f16)) || ((uintptr_t)b.act & 7))
+        return navppo_bad_args(who, "obs must be 16-byte (42 columns: 8-byte, float16: 4-byte), prep 16-byte and act 8-byte aligned");
+    if (const int rc = navppo_check_step(who, MODE, s)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const PassPlan pl = plan_pass(workspace, b.n, x.dim);
+    const float* const w = params;
+    const long long n = b.n;
+    if (x.x3) {
+        const unsigned char* const prep = reinterpret_cast<const unsigned char*>(x.data);
+        auto pass = [&](auto kernel, int waves) {
+            hipLaunchKernelGGL(kernel, dim3(pl.blocks), dim3(64 * waves), 0, st, w, prep, b.act, b.logp_old, b.rtg, b.adv, n, b.var, b.clip, pl.inv_n,
+                               net_mask, pl.partial, pl.stats_partial, pl.partial_c, pl.stats_partial_c NAVPPO_KL_ARG(s.kl_state));
+        };
+        if (x.dim == 16 && X3_SCHED) pass(NAVPPO_KL_KERNEL(mlp64_pass_both_x3s), x3s::SW);
+        else if (x.dim == 16) pass(NAVPPO_KL_KERNEL(mlp64_pass_both_x3)<16>, XPad<16>::NW);
+        else pass(NAVPPO_KL_KERNEL(mlp64_pass_both_x3)<42>, XPad<42>::NW);
+    } else {
+        for_obs(x.dim, x.f16, [&](auto in, auto f16) {
+            constexpr int IN = decltype(in)::value;
+            constexpr bool F16 = decltype(f16)::value;
+            const dim3 grid(pl.blocks), block(64 * Pad<IN>::NW);
+            if (net_mask == 3)
+                hipLaunchKernelGGL((NAVPPO_KL_KERNEL(mlp64_pass_both)<IN, F16>), grid, block, 0, st, w, x.data, b.act, b.logp_old, b.rtg, b.adv, n, b.var,
+                                   b.clip, pl.inv_n, pl.partial, pl.stats_partial, pl.partial_c, pl.stats_partial_c, grad, stats NAVPPO_KL_ARG(s.kl_state));
+            else if constexpr (MODE == NavppoMode::kGrad) {
+                if (net_mask == 1)
+                    hipLaunchKernelGGL((mlp64_pass_w<true, false, IN, F16>), grid, block, 0, st, w, x.data, b.act, b.logp_old, b.rtg, b.adv, n, b.var,
+                                       b.clip, pl.inv_n, pl.partial, pl.stats_partial, grad, stats, (float*)nullptr);
+                else
+                    hipLaunchKernelGGL((mlp64_pass_w<false, false, IN, F16>), grid, block, 0, st, w + pl.pa, x.data, b.act, b.logp_old, b.rtg, b.adv, n,
+                                       b.var, b.clip, pl.inv_n, pl.partial_c, pl.stats_partial_c, grad + pl.pa, stats + 4, (float*)nullptr);
+            }
+        });
+    }
+    // the reduction over [q0, q1).  kAdam: Adam in the same launch, and (both nets) its blocks' squared-norm slots in parity step & 1 for
+    // the logged means.  kClip / kClipKl: the reduction alone, the slots in parity 0 (stats[3] / [7]: unspecified); then the norms,
+    // the KL decision on stats[1], the clip and Adam
+    constexpr bool kAdam = MODE == NavppoMode::kAdam, kClip = MODE == NavppoMode::kClip || MODE == NavppoMode::kClipKl;
+    const int q0 = (net_mask & 1) ? 0 : pl.pa, q1 = (net_mask & 2) ? pl.pa + pl.pc : pl.pa, rblocks = (q1 - q0 + 63) / 64;
+    const NavppoStep r = kAdam ? s : NavppoStep{};
+    const NavppoBias bc = kAdam ? navppo_bias(s.beta1, s.beta2, s.step) : NavppoBias{1.f, 1.f};
+    const int parity = kClip ? 0 : (kAdam && net_mask == 3) ? (int)(s.step & 1) : -1;
+    hipLaunchKernelGGL((NAVPPO_KL_KERNEL(reduce_adam)<kAdam>), dim3(rblocks), dim3(64 * kRedGroups), 0, st, pl.partial, pl.stats_partial, pl.partial_c,
+                       pl.stats_partial_c, pl.blocks, pl.inv_n, grad, stats, kAdam ? params : nullptr, r.m, r.v, r.lr, r.beta1, r.beta2, r.eps, bc.bc1,
+                       bc.bc2_sqrt, pl.pa, pl.pc, q0, q1, parity >= 0 ? pl.gn : nullptr, parity NAVPPO_KL_ARG(s.kl_state));
+    if constexpr (kClip)
+        navppo_launch_clip_adam(params, grad, pl.pa + pl.pc, pl.pa, 1.0f, s, pl.gn, rblocks, kGnSlots, 8, stream,
+                                MODE == NavppoMode::kClipKl ? stats + 1 : nullptr);
+    return navppo_launched(who);
+}
+
+// the f32 and bf16x3 entry points' arguments as mlp64_epoch takes them
+inline Mlp64Rows f32_rows(const void* obs_dev, int32_t obs_dim, int32_t obs_f16) { return {obs_dev, obs_dim, obs_f16, false}; }
+inline Mlp64Rows x3_rows(const void* prep_dev, int32_t obs_dim) { return {prep_dev, obs_dim, 0, true}; }
+
 }  // namespace
 
 #ifndef NAVPPO_KL_TU
+namespace {
+
+// navppo_adam_step and its clipped / KL-gated forms: the step on a flat buffer whose gradient an all-reduce summed
+int adam_step(const char* who, NavppoMode mode, float* params, float* grad, int64_t n, int64_t n_first, float grad_scale, const NavppoStep& s,
+              const float* kl, void* stream) {
+    const bool clip = mode != NavppoMode::kAdam, kl_mode = mode == NavppoMode::kClipKl;
+    if (!params || !grad || n < 1 || (clip && (n > INT32_MAX || n_first < 0 || n_first > n)) || (kl_mode && !kl))
+        return navppo_bad_args(who, !clip     ? "bad argument"
+                                    : kl_mode ? "bad argument (0 <= n_first <= n; kl_dev [1] not null)"
+                                              : "bad argument (0 <= n_first <= n)");
+    if (const int rc = navppo_check_step(who, mode, s)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (!clip) {
+        const NavppoBias bc = navppo_bias(s.beta1, s.beta2, s.step);
+        hipLaunchKernelGGL(adam_step_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, params, (const float*)grad, s.m, s.v, (int)n,
+                           grad_scale, s.lr, s.beta1, s.beta2, s.eps, bc.bc1, bc.bc2_sqrt);
+    } else {   // the squared norms into clip_stats[0..1], which the step launch then reads as its (one) slot per net
+        if (kl)
+            hipLaunchKernelGGL(sqnorm2_kl_kernel, dim3(1), dim3(kNormThreads), 0, st, (const float*)grad, (int)n, (int)n_first, grad_scale,
+                               s.clip_stats, (const float*)s.kl_state);
+        else
+            hipLaunchKernelGGL(sqnorm2_kernel, dim3(1), dim3(kNormThreads), 0, st, (const float*)grad, (int)n, (int)n_first, grad_scale, s.clip_stats);
+        navppo_launch_clip_adam(params, grad, (int)n, (int)n_first, grad_scale, s, s.clip_stats, 1, 1, 8, stream, kl);
+    }
+    return navppo_launched(who);
+}
+
+inline int net_mask_of(int32_t net) { return net == 0 ? 1 : net == 1 ? 2 : 0; }   // (0: mlp64_epoch's "net is ..." error)
+
+}  // namespace
+
 #pragma GCC visibility push(default)
 extern "C" {
 
 int navppo_mlp64_loss_grad(const float* params_dev, const void* obs_dev, int32_t obs_dim, int32_t obs_f16, const float* act_dev,
                            const float* logp_old_dev, const float* rtg_dev, const float* adv_dev, int64_t n_samples,
                            float var, float clip, float* grad_dev, float* stats_dev, void* workspace_dev, void* stream) {
-    if (!params_dev || !obs_dev || !act_dev || !logp_old_dev || !rtg_dev || !adv_dev || !grad_dev || !stats_dev ||
-        !workspace_dev || n_samples < 1 || !(var > 0.f) || (obs_dim != 16 && obs_dim != 42)) {
-        g_err = "navppo_mlp64_loss_grad: bad argument (obs_dim is 16 or 42)";
-        return -1;
-    }
-    if (!obs_aligned(obs_dev, obs_dim, obs_f16) || ((uintptr_t)act_dev & 7)) {
-        g_err = "navppo_mlp64_loss_grad: obs must be 16-byte (42 columns: 8-byte, float16: 4-byte) and act 8-byte aligned";
-        return -1;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    const PassPlan pl = plan_pass(workspace_dev, n_samples, obs_dim);
-    for_obs(obs_dim, obs_f16, [&](auto in, auto f16) {
-        hipLaunchKernelGGL((mlp64_pass_both<decltype(in)::value, decltype(f16)::value>), dim3(pl.blocks), dim3(64 * Pad<decltype(in)::value>::NW), 0, st, params_dev,
-                           obs_dev, act_dev, logp_old_dev, rtg_dev, adv_dev, (long long)n_samples, var, clip, pl.inv_n, pl.partial,
-                           pl.stats_partial, pl.partial_c, pl.stats_partial_c, grad_dev, stats_dev);
-    });
-    hipLaunchKernelGGL(reduce_adam<false>, dim3((pl.pa + pl.pc + 63) / 64), dim3(64 * kRedGroups), 0, st, pl.partial, pl.stats_partial,
-                       pl.partial_c, pl.stats_partial_c, pl.blocks, pl.inv_n, grad_dev, stats_dev, nullptr, nullptr, nullptr, 0.f, 0.f, 0.f,
-                       0.f, 1.f, 1.f, pl.pa, pl.pc, 0, pl.pa + pl.pc, (float*)nullptr, -1);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        g_err = std::string("navppo_mlp64_loss_grad: ") + hipGetErrorString(e);
-        return -2;
-    }
-    return 0;
+    return mlp64_epoch<NavppoMode::kGrad>("navppo_mlp64_loss_grad", const_cast<float*>(params_dev), f32_rows(obs_dev, obs_dim, obs_f16),
+                                          {act_dev, logp_old_dev, rtg_dev, adv_dev, n_samples, var, clip}, 3, {}, grad_dev, stats_dev, workspace_dev,
+                                          stream);
 }
 
 int navppo_mlp64_loss_grad_net(int32_t net, const float* params_dev, const void* obs_dev, int32_t obs_dim, int32_t obs_f16,
                                const float* act_dev, const float* logp_old_dev, const float* rtg_dev, const float* adv_dev,
                                int64_t n_samples, float var, float clip, float* grad_dev, float* stats_dev, void* workspace_dev,
                                void* stream) {
-    if ((net != 0 && net != 1) || !params_dev || !obs_dev || !act_dev || !logp_old_dev || !rtg_dev || !adv_dev || !grad_dev ||
-        !stats_dev || !workspace_dev || n_samples < 1 || !(var > 0.f) || (obs_dim != 16 && obs_dim != 42)) {
-        g_err = "navppo_mlp64_loss_grad_net: bad argument (obs_dim is 16 or 42)";
-        return -1;
-    }
-    if (!obs_aligned(obs_dev, obs_dim, obs_f16) || ((uintptr_t)act_dev & 7)) {
-        g_err = "navppo_mlp64_loss_grad_net: obs must be 16-byte (42 columns: 8-byte, float16: 4-byte) and act 8-byte aligned";
-        return -1;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    const PassPlan pl = plan_pass(workspace_dev, n_samples, obs_dim);
-    for_obs(obs_dim, obs_f16, [&](auto in, auto f16) {
-        constexpr int IN = decltype(in)::value;
-        constexpr bool F16 = decltype(f16)::value;
-        if (net == 0)
-            hipLaunchKernelGGL((mlp64_pass_w<true, false, IN, F16>), dim3(pl.blocks), dim3(64 * Pad<IN>::NW), 0, st, params_dev, obs_dev, act_dev,
-                               logp_old_dev, rtg_dev, adv_dev, (long long)n_samples, var, clip, pl.inv_n, pl.partial, pl.stats_partial,
-                               grad_dev, stats_dev, (float*)nullptr);
-        else
-            hipLaunchKernelGGL((mlp64_pass_w<false, false, IN, F16>), dim3(pl.blocks), dim3(64 * Pad<IN>::NW), 0, st, params_dev + pl.pa, obs_dev,
-                               act_dev, logp_old_dev, rtg_dev, adv_dev, (long long)n_samples, var, clip, pl.inv_n, pl.partial_c,
-                               pl.stats_partial_c, grad_dev + pl.pa, stats_dev + 4, (float*)nullptr);
-    });
-    const int q0 = net == 0 ? 0 : pl.pa, q1 = net == 0 ? pl.pa : pl.pa + pl.pc;
-    hipLaunchKernelGGL(reduce_adam<false>, dim3((q1 - q0 + 63) / 64), dim3(64 * kRedGroups), 0, st, pl.partial, pl.stats_partial, pl.partial_c,
-                       pl.stats_partial_c, pl.blocks, pl.inv_n, grad_dev, stats_dev, nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, 0.f, 1.f, 1.f,
-                       pl.pa, pl.pc, q0, q1, (float*)nullptr, -1);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        g_err = std::string("navppo_mlp64_loss_grad_net: ") + hipGetErrorString(e);
-        return -2;
-    }
-    return 0;
+    return mlp64_epoch<NavppoMode::kGrad>("navppo_mlp64_loss_grad_net", const_cast<float*>(params_dev), f32_rows(obs_dev, obs_dim, obs_f16),
+                                          {act_dev, logp_old_dev, rtg_dev, adv_dev, n_samples, var, clip}, net_mask_of(net), {}, grad_dev, stats_dev,
+                                          workspace_dev, stream);
 }
 
 int navppo_adam_step(float* params_dev, const float* grad_dev, float* adam_m_dev, float* adam_v_dev, int64_t n, float grad_scale,
                      float lr, float beta1, float beta2, float eps, int32_t step, void* stream) {
-    if (!params_dev || !grad_dev || !adam_m_dev || !adam_v_dev || n < 1 || step < 1) {
-        g_err = "navppo_adam_step: bad argument";
-        return -1;
-    }
-    const float bc1 = (float)(1.0 - std::pow((double)beta1, (double)step));
-    const float bc2_sqrt = (float)std::sqrt(1.0 - std::pow((double)beta2, (double)step));
-    hipLaunchKernelGGL(adam_step_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, params_dev, grad_dev,
-                       adam_m_dev, adam_v_dev, (int)n, grad_scale, lr, beta1, beta2, eps, bc1, bc2_sqrt);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        g_err = std::string("navppo_adam_step: ") + hipGetErrorString(e);
-        return -2;
-    }
-    return 0;
+    return adam_step("navppo_adam_step", NavppoMode::kAdam, params_dev, const_cast<float*>(grad_dev), n, 0, grad_scale,
+                     {lr, beta1, beta2, eps, step, adam_m_dev, adam_v_dev}, nullptr, stream);
 }
 
 int navppo_adam_step_clipped(float* params_dev, float* grad_dev, float* adam_m_dev, float* adam_v_dev, int64_t n, int64_t n_first,
                              float grad_scale, float max_norm, float lr, float beta1, float beta2, float eps, int32_t step,
                              float* clip_stats_dev, void* stream) {
-    if (!params_dev || !grad_dev || !adam_m_dev || !adam_v_dev || n < 1 || n > INT32_MAX || n_first < 0 || n_first > n || step < 1 || !clip_stats_dev) {
-        g_err = "navppo_adam_step_clipped: bad argument (0 <= n_first <= n, clip_stats_dev [4])";
-        return -1;
-    }
-    if (!navppo_max_norm_ok(max_norm)) {
-        g_err = "navppo_adam_step_clipped: max_norm must be > 0 (+inf allowed)";
-        return -1;
-    }
-    hipLaunchKernelGGL(sqnorm2_kernel, dim3(1), dim3(kNormThreads), 0, (hipStream_t)stream, (const float*)grad_dev, (int)n, (int)n_first, grad_scale,
-                       clip_stats_dev);
-    navppo_launch_clip_adam(params_dev, grad_dev, adam_m_dev, adam_v_dev, (int)n, (int)n_first, grad_scale, max_norm, lr, beta1, beta2, eps, step,
-                            clip_stats_dev, 1, 1, 8, clip_stats_dev, stream);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        g_err = std::string("navppo_adam_step_clipped: ") + hipGetErrorString(e);
-        return -2;
-    }
-    return 0;
+    return adam_step("navppo_adam_step_clipped", NavppoMode::kClip, params_dev, grad_dev, n, n_first, grad_scale,
+                     {lr, beta1, beta2, eps, step, adam_m_dev, adam_v_dev, max_norm, clip_stats_dev}, nullptr, stream);
 }
 
 int navppo_adam_step_kl(float* params_dev, float* grad_dev, float* adam_m_dev, float* adam_v_dev, int64_t n, int64_t n_first,
                         float grad_scale, float max_norm, float lr, float beta1, float beta2, float eps, int32_t step,
                         float* clip_stats_dev, float kl_limit, float* kl_state_dev, const float* kl_dev, void* stream) {
-    if (!params_dev || !grad_dev || !adam_m_dev || !adam_v_dev || n < 1 || n > INT32_MAX || n_first < 0 || n_first > n || step < 1 || !clip_stats_dev ||
-        !kl_dev) {
-        g_err = "navppo_adam_step_kl: bad argument (0 <= n_first <= n, clip_stats_dev [4], kl_dev [1])";
-        return -1;
-    }
-    if (!navppo_max_norm_ok(max_norm)) {
-        g_err = "navppo_adam_step_kl: max_norm must be > 0 (+inf allowed)";
-        return -1;
-    }
-    if (!navppo_kl_limit_ok(kl_limit) || !kl_state_dev) {
-        g_err = "navppo_adam_step_kl: kl_limit must be > 0 (+inf allowed) and kl_state_dev [4] not null";
-        return -1;
-    }
-    hipLaunchKernelGGL(sqnorm2_kl_kernel, dim3(1), dim3(kNormThreads), 0, (hipStream_t)stream, (const float*)grad_dev, (int)n, (int)n_first, grad_scale,
-                       clip_stats_dev, (const float*)kl_state_dev);
-    navppo_launch_clip_adam(params_dev, grad_dev, adam_m_dev, adam_v_dev, (int)n, (int)n_first, grad_scale, max_norm, lr, beta1, beta2, eps, step,
-                            clip_stats_dev, 1, 1, 8, clip_stats_dev, stream, kl_dev, kl_limit, kl_state_dev);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        g_err = std::string("navppo_adam_step_kl: ") + hipGetErrorString(e);
-        return -2;
-    }
-    return 0;
+    return adam_step("navppo_adam_step_kl", NavppoMode::kClipKl, params_dev, grad_dev, n, n_first, grad_scale,
+                     {lr, beta1, beta2, eps, step, adam_m_dev, adam_v_dev, max_norm, clip_stats_dev, kl_limit, kl_state_dev}, kl_dev, stream);
 }
 
 int navppo_mlp64_value(const float* critic_params_dev, const void* obs_dev, int32_t obs_dim, int32_t obs_f16, int64_t n_samples,
                        float* value_dev, void* stream) {
     if (!critic_params_dev || !obs_dev || !value_dev || n_samples < 1 || (obs_dim != 16 && obs_dim != 42) ||
-        !obs_aligned(obs_dev, obs_dim, obs_f16)) {
-        g_err = "navppo_mlp64_value: bad argument (obs_dim is 16 or 42; obs 16-byte aligned, 42 columns: 8-byte, float16: 4-byte)";
-        return -1;
-    }
+        !obs_aligned(obs_dev, obs_dim, obs_f16))
+        return navppo_bad_args("navppo_mlp64_value", "bad argument (obs_dim is 16 or 42; obs 16-byte aligned, 42 columns: 8-byte, float16: 4-byte)");
     const long long wtiles = (n_samples + 31) / 32;
     const long long want = (wtiles + kWWaves - 1) / kWWaves;
     const int blocks = (int)(want < kWMaxBlocks ? want : kWMaxBlocks);
@@ -1857,45 +1854,16 @@ int navppo_mlp64_value(const float* critic_params_dev, const void* obs_dev, int3
                            (hipStream_t)stream, critic_params_dev, obs_dev, nullptr, nullptr, nullptr, nullptr, (long long)n_samples, 1.f,
                            0.f, 0.f, nullptr, nullptr, nullptr, nullptr, value_dev);
     });
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        g_err = std::string("navppo_mlp64_value: ") + hipGetErrorString(e);
-        return -2;
-    }
-    return 0;
+    return navppo_launched("navppo_mlp64_value");
 }
 
 int navppo_mlp64_update_epoch(float* params_dev, const void* obs_dev, int32_t obs_dim, int32_t obs_f16, const float* act_dev,
                               const float* logp_old_dev, const float* rtg_dev, const float* adv_dev, int64_t n_samples, float var,
                               float clip, float lr, float beta1, float beta2, float eps, int32_t step, float* adam_m_dev,
                               float* adam_v_dev, float* grad_dev, float* stats_dev, void* workspace_dev, void* stream) {
-    if (!params_dev || !obs_dev || !act_dev || !logp_old_dev || !rtg_dev || !adv_dev || !grad_dev || !stats_dev ||
-        !workspace_dev || !adam_m_dev || !adam_v_dev || n_samples < 1 || !(var > 0.f) || step < 1 || (obs_dim != 16 && obs_dim != 42)) {
-        g_err = "navppo_mlp64_update_epoch: bad argument (obs_dim is 16 or 42)";
-        return -1;
-    }
-    if (!obs_aligned(obs_dev, obs_dim, obs_f16) || ((uintptr_t)act_dev & 7)) {
-        g_err = "navppo_mlp64_update_epoch: obs must be 16-byte (42 columns: 8-byte, float16: 4-byte) and act 8-byte aligned";
-        return -1;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    const PassPlan pl = plan_pass(workspace_dev, n_samples, obs_dim);
-    const float bc1 = (float)(1.0 - std::pow((double)beta1, (double)step));
-    const float bc2_sqrt = (float)std::sqrt(1.0 - std::pow((double)beta2, (double)step));
-    for_obs(obs_dim, obs_f16, [&](auto in, auto f16) {
-        hipLaunchKernelGGL((mlp64_pass_both<decltype(in)::value, decltype(f16)::value>), dim3(pl.blocks), dim3(64 * Pad<decltype(in)::value>::NW), 0, st, params_dev,
-                           obs_dev, act_dev, logp_old_dev, rtg_dev, adv_dev, (long long)n_samples, var, clip, pl.inv_n, pl.partial,
-                           pl.stats_partial, pl.partial_c, pl.stats_partial_c, grad_dev, stats_dev);
-    });
-    hipLaunchKernelGGL(reduce_adam<true>, dim3((pl.pa + pl.pc + 63) / 64), dim3(64 * kRedGroups), 0, st, pl.partial, pl.stats_partial,
-                       pl.partial_c, pl.stats_partial_c, pl.blocks, pl.inv_n, grad_dev, stats_dev, params_dev, adam_m_dev, adam_v_dev, lr,
-                       beta1, beta2, eps, bc1, bc2_sqrt, pl.pa, pl.pc, 0, pl.pa + pl.pc, pl.gn, (int)(step & 1));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        g_err = std::string("navppo_mlp64_update_epoch: ") + hipGetErrorString(e);
-        return -2;
-    }
-    return 0;
+    return mlp64_epoch<NavppoMode::kAdam>("navppo_mlp64_update_epoch", params_dev, f32_rows(obs_dev, obs_dim, obs_f16),
+                                          {act_dev, logp_old_dev, rtg_dev, adv_dev, n_samples, var, clip}, 3,
+                                          {lr, beta1, beta2, eps, step, adam_m_dev, adam_v_dev}, grad_dev, stats_dev, workspace_dev, stream);
 }
 
 int navppo_mlp64_update_epoch_clipped(float* params_dev, const void* obs_dev, int32_t obs_dim, int32_t obs_f16, const float* act_dev,
@@ -1903,39 +1871,10 @@ int navppo_mlp64_update_epoch_clipped(float* params_dev, const void* obs_dev, in
                                       float clip, float lr, float beta1, float beta2, float eps, int32_t step, float* adam_m_dev,
                                       float* adam_v_dev, float* grad_dev, float* stats_dev, void* workspace_dev, float max_norm,
                                       float* clip_stats_dev, void* stream) {
-    if (!navppo_max_norm_ok(max_norm) || !clip_stats_dev) {
-        g_err = "navppo_mlp64_update_epoch_clipped: max_norm must be > 0 (+inf allowed) and clip_stats_dev [4] not null";
-        return -1;
-    }
-    if (!params_dev || !obs_dev || !act_dev || !logp_old_dev || !rtg_dev || !adv_dev || !grad_dev || !stats_dev ||
-        !workspace_dev || !adam_m_dev || !adam_v_dev || n_samples < 1 || !(var > 0.f) || step < 1 || (obs_dim != 16 && obs_dim != 42)) {
-        g_err = "navppo_mlp64_update_epoch_clipped: bad argument (obs_dim is 16 or 42)";
-        return -1;
-    }
-    if (!obs_aligned(obs_dev, obs_dim, obs_f16) || ((uintptr_t)act_dev & 7)) {
-        g_err = "navppo_mlp64_update_epoch_clipped: obs must be 16-byte (42 columns: 8-byte, float16: 4-byte) and act 8-byte aligned";
-        return -1;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    const PassPlan pl = plan_pass(workspace_dev, n_samples, obs_dim);
-    for_obs(obs_dim, obs_f16, [&](auto in, auto f16) {
-        hipLaunchKernelGGL((mlp64_pass_both<decltype(in)::value, decltype(f16)::value>), dim3(pl.blocks), dim3(64 * Pad<decltype(in)::value>::NW), 0, st, params_dev,
-                           obs_dev, act_dev, logp_old_dev, rtg_dev, adv_dev, (long long)n_samples, var, clip, pl.inv_n, pl.partial,
-                           pl.stats_partial, pl.partial_c, pl.stats_partial_c, grad_dev, stats_dev);
-    });
-    // the reduction alone, its blocks' squared-norm slots in parity 0 (stats[3] / [7]: unspecified); then the norms, the clip and Adam
-    const int rblocks = (pl.pa + pl.pc + 63) / 64;
-    hipLaunchKernelGGL(reduce_adam<false>, dim3(rblocks), dim3(64 * kRedGroups), 0, st, pl.partial, pl.stats_partial, pl.partial_c,
-                       pl.stats_partial_c, pl.blocks, pl.inv_n, grad_dev, stats_dev, nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, 0.f, 1.f, 1.f,
-                       pl.pa, pl.pc, 0, pl.pa + pl.pc, pl.gn, 0);
-    navppo_launch_clip_adam(params_dev, grad_dev, adam_m_dev, adam_v_dev, pl.pa + pl.pc, pl.pa, 1.0f, max_norm, lr, beta1, beta2, eps, step, pl.gn,
-                            rblocks, kGnSlots, 8, clip_stats_dev, stream);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        g_err = std::string("navppo_mlp64_update_epoch_clipped: ") + hipGetErrorString(e);
-        return -2;
-    }
-    return 0;
+    return mlp64_epoch<NavppoMode::kClip>("navppo_mlp64_update_epoch_clipped", params_dev, f32_rows(obs_dev, obs_dim, obs_f16),
+                                          {act_dev, logp_old_dev, rtg_dev, adv_dev, n_samples, var, clip}, 3,
+                                          {lr, beta1, beta2, eps, step, adam_m_dev, adam_v_dev, max_norm, clip_stats_dev}, grad_dev, stats_dev,
+                                          workspace_dev, stream);
 }
 
 size_t navppo_mlp64_bf16x3_prep_bytes(int64_t n_samples, int32_t obs_dim) {
@@ -1945,101 +1884,40 @@ size_t navppo_mlp64_bf16x3_prep_bytes(int64_t n_samples, int32_t obs_dim) {
 
 int navppo_mlp64_bf16x3_prepare(const void* obs_dev, int32_t obs_dim, int32_t obs_f16, int64_t n_samples, void* prep_dev, void* stream) {
     if (!obs_dev || !prep_dev || n_samples < 1 || (obs_dim != 16 && obs_dim != 42) || !obs_aligned(obs_dev, obs_dim, obs_f16) ||
-        ((uintptr_t)prep_dev & 15)) {
-        g_err = "navppo_mlp64_bf16x3_prepare: bad argument (obs_dim is 16 or 42; obs aligned as for navppo_mlp64_loss_grad, prep 16-byte aligned)";
-        return -1;
-    }
+        ((uintptr_t)prep_dev & 15))
+        return navppo_bad_args("navppo_mlp64_bf16x3_prepare",
+                               "bad argument (obs_dim is 16 or 42; obs aligned as for navppo_mlp64_loss_grad, prep 16-byte aligned)");
     const unsigned tiles = (unsigned)((n_samples + 31) / 32);
     for_obs(obs_dim, obs_f16, [&](auto in, auto f16) {
         hipLaunchKernelGGL((mlp64_split_obs<decltype(f16)::value, decltype(in)::value>), dim3(tiles), dim3(64), 0, (hipStream_t)stream, obs_dev,
                            (long long)n_samples, reinterpret_cast<unsigned char*>(prep_dev));
     });
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        g_err = std::string("navppo_mlp64_bf16x3_prepare: ") + hipGetErrorString(e);
-        return -2;
-    }
-    return 0;
-}
-
-// net_mask 3: both nets; 1 / 2: the actor's / the critic's pass and its slice of the reduction; step >= 1: Adam in the reduction
-static int x3_epoch(const char* who, float* params_dev, const void* prep_dev, int32_t obs_dim, const float* act_dev, const float* logp_old_dev,
-                    const float* rtg_dev, const float* adv_dev, int64_t n_samples, float var, float clip, int net_mask, int32_t step,
-                    float lr, float beta1, float beta2, float eps, float* adam_m_dev, float* adam_v_dev, float* grad_dev,
-                    float* stats_dev, void* workspace_dev, void* stream, float max_norm = 0.f, float* clip_stats_dev = nullptr) {
-    if (!params_dev || !prep_dev || !act_dev || !logp_old_dev || !rtg_dev || !adv_dev || !grad_dev || !stats_dev || !workspace_dev ||
-        n_samples < 1 || !(var > 0.f) || (obs_dim != 16 && obs_dim != 42) || ((uintptr_t)prep_dev & 15) || ((uintptr_t)act_dev & 7)) {
-        g_err = std::string(who) + ": bad argument (obs_dim is 16 or 42; prep 16-byte, act 8-byte aligned)";
-        return -1;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    const PassPlan pl = plan_pass(workspace_dev, n_samples, obs_dim);
-    if (obs_dim == 16 && X3_SCHED)
-        hipLaunchKernelGGL(mlp64_pass_both_x3s, dim3(pl.blocks), dim3(64 * x3s::SW), 0, st, params_dev,
-                           reinterpret_cast<const unsigned char*>(prep_dev), act_dev, logp_old_dev, rtg_dev, adv_dev, (long long)n_samples, var, clip,
-                           pl.inv_n, net_mask, pl.partial, pl.stats_partial, pl.partial_c, pl.stats_partial_c);
-    else if (obs_dim == 16)
-        hipLaunchKernelGGL(mlp64_pass_both_x3<16>, dim3(pl.blocks), dim3(64 * XPad<16>::NW), 0, st, params_dev,
-                           reinterpret_cast<const unsigned char*>(prep_dev), act_dev, logp_old_dev, rtg_dev, adv_dev, (long long)n_samples, var, clip,
-                           pl.inv_n, net_mask, pl.partial, pl.stats_partial, pl.partial_c, pl.stats_partial_c);
-    else
-        hipLaunchKernelGGL(mlp64_pass_both_x3<42>, dim3(pl.blocks), dim3(64 * XPad<42>::NW), 0, st, params_dev,
-                           reinterpret_cast<const unsigned char*>(prep_dev), act_dev, logp_old_dev, rtg_dev, adv_dev, (long long)n_samples, var, clip,
-                           pl.inv_n, net_mask, pl.partial, pl.stats_partial, pl.partial_c, pl.stats_partial_c);
-    const int q0 = (net_mask & 1) ? 0 : pl.pa, q1 = (net_mask & 2) ? pl.pa + pl.pc : pl.pa;
-    if (clip_stats_dev) {   // (both nets, step >= 1) the reduction alone with this epoch's squared-norm slots, then the norms, the clip and Adam
-        hipLaunchKernelGGL(reduce_adam<false>, dim3((q1 - q0 + 63) / 64), dim3(64 * kRedGroups), 0, st, pl.partial, pl.stats_partial, pl.partial_c,
-                           pl.stats_partial_c, pl.blocks, pl.inv_n, grad_dev, stats_dev, nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, 0.f, 1.f,
-                           1.f, pl.pa, pl.pc, q0, q1, pl.gn, 0);
-        navppo_launch_clip_adam(params_dev, grad_dev, adam_m_dev, adam_v_dev, pl.pa + pl.pc, pl.pa, 1.0f, max_norm, lr, beta1, beta2, eps, step, pl.gn,
-                                (q1 - q0 + 63) / 64, kGnSlots, 8, clip_stats_dev, stream);
-    } else if (step >= 1) {
-        const float bc1 = (float)(1.0 - std::pow((double)beta1, (double)step));
-        const float bc2_sqrt = (float)std::sqrt(1.0 - std::pow((double)beta2, (double)step));
-        hipLaunchKernelGGL(reduce_adam<true>, dim3((q1 - q0 + 63) / 64), dim3(64 * kRedGroups), 0, st, pl.partial, pl.stats_partial, pl.partial_c,
-                           pl.stats_partial_c, pl.blocks, pl.inv_n, grad_dev, stats_dev, params_dev, adam_m_dev, adam_v_dev, lr, beta1, beta2,
-                           eps, bc1, bc2_sqrt, pl.pa, pl.pc, q0, q1, pl.gn, net_mask == 3 ? (int)(step & 1) : -1);
-    } else {
-        hipLaunchKernelGGL(reduce_adam<false>, dim3((q1 - q0 + 63) / 64), dim3(64 * kRedGroups), 0, st, pl.partial, pl.stats_partial, pl.partial_c,
-                           pl.stats_partial_c, pl.blocks, pl.inv_n, grad_dev, stats_dev, nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, 0.f, 1.f,
-                           1.f, pl.pa, pl.pc, q0, q1, (float*)nullptr, -1);
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        g_err = std::string(who) + ": " + hipGetErrorString(e);
-        return -2;
-    }
-    return 0;
+    return navppo_launched("navppo_mlp64_bf16x3_prepare");
 }
 
 int navppo_mlp64_bf16x3_loss_grad(const float* params_dev, const void* prep_dev, int32_t obs_dim, const float* act_dev,
                                   const float* logp_old_dev, const float* rtg_dev, const float* adv_dev, int64_t n_samples, float var, float clip,
                                   float* grad_dev, float* stats_dev, void* workspace_dev, void* stream) {
-    return x3_epoch("navppo_mlp64_bf16x3_loss_grad", const_cast<float*>(params_dev), prep_dev, obs_dim, act_dev, logp_old_dev, rtg_dev, adv_dev,
-                    n_samples, var, clip, 3, 0, 0.f, 0.f, 0.f, 0.f, nullptr, nullptr, grad_dev, stats_dev, workspace_dev, stream);
+    return mlp64_epoch<NavppoMode::kGrad>("navppo_mlp64_bf16x3_loss_grad", const_cast<float*>(params_dev), x3_rows(prep_dev, obs_dim),
+                                          {act_dev, logp_old_dev, rtg_dev, adv_dev, n_samples, var, clip}, 3, {}, grad_dev, stats_dev, workspace_dev,
+                                          stream);
 }
 
 int navppo_mlp64_bf16x3_loss_grad_net(int32_t net, const float* params_dev, const void* prep_dev, int32_t obs_dim, const float* act_dev,
                                       const float* logp_old_dev, const float* rtg_dev, const float* adv_dev, int64_t n_samples, float var,
                                       float clip, float* grad_dev, float* stats_dev, void* workspace_dev, void* stream) {
-    if (net != 0 && net != 1) {
-        g_err = "navppo_mlp64_bf16x3_loss_grad_net: net is 0 (actor) or 1 (critic)";
-        return -1;
-    }
-    return x3_epoch("navppo_mlp64_bf16x3_loss_grad_net", const_cast<float*>(params_dev), prep_dev, obs_dim, act_dev, logp_old_dev, rtg_dev, adv_dev,
-                    n_samples, var, clip, net == 0 ? 1 : 2, 0, 0.f, 0.f, 0.f, 0.f, nullptr, nullptr, grad_dev, stats_dev, workspace_dev, stream);
+    return mlp64_epoch<NavppoMode::kGrad>("navppo_mlp64_bf16x3_loss_grad_net", const_cast<float*>(params_dev), x3_rows(prep_dev, obs_dim),
+                                          {act_dev, logp_old_dev, rtg_dev, adv_dev, n_samples, var, clip}, net_mask_of(net), {}, grad_dev, stats_dev,
+                                          workspace_dev, stream);
 }
 
 int navppo_mlp64_bf16x3_update_epoch(float* params_dev, const void* prep_dev, int32_t obs_dim, const float* act_dev, const float* logp_old_dev,
                                      const float* rtg_dev, const float* adv_dev, int64_t n_samples, float var, float clip, float lr,
                                      float beta1, float beta2, float eps, int32_t step, float* adam_m_dev, float* adam_v_dev,
                                      float* grad_dev, float* stats_dev, void* workspace_dev, void* stream) {
-    if (step < 1 || !adam_m_dev || !adam_v_dev) {
-        g_err = "navppo_mlp64_bf16x3_update_epoch: bad argument";
-        return -1;
-    }
-    return x3_epoch("navppo_mlp64_bf16x3_update_epoch", params_dev, prep_dev, obs_dim, act_dev, logp_old_dev, rtg_dev, adv_dev, n_samples, var, clip,
-                    3, step, lr, beta1, beta2, eps, adam_m_dev, adam_v_dev, grad_dev, stats_dev, workspace_dev, stream);
+    return mlp64_epoch<NavppoMode::kAdam>("navppo_mlp64_bf16x3_update_epoch", params_dev, x3_rows(prep_dev, obs_dim),
+                                          {act_dev, logp_old_dev, rtg_dev, adv_dev, n_samples, var, clip}, 3,
+                                          {lr, beta1, beta2, eps, step, adam_m_dev, adam_v_dev}, grad_dev, stats_dev, workspace_dev, stream);
 }
 
 int navppo_mlp64_bf16x3_update_epoch_clipped(float* params_dev, const void* prep_dev, int32_t obs_dim, const float* act_dev,
@@ -2047,21 +1925,16 @@ int navppo_mlp64_bf16x3_update_epoch_clipped(float* params_dev, const void* prep
                                              float clip, float lr, float beta1, float beta2, float eps, int32_t step, float* adam_m_dev,
                                              float* adam_v_dev, float* grad_dev, float* stats_dev, void* workspace_dev, float max_norm,
                                              float* clip_stats_dev, void* stream) {
-    if (step < 1 || !adam_m_dev || !adam_v_dev || !navppo_max_norm_ok(max_norm) || !clip_stats_dev) {
-        g_err = "navppo_mlp64_bf16x3_update_epoch_clipped: bad argument (max_norm must be > 0, +inf allowed; clip_stats_dev [4] not null)";
-        return -1;
-    }
-    return x3_epoch("navppo_mlp64_bf16x3_update_epoch_clipped", params_dev, prep_dev, obs_dim, act_dev, logp_old_dev, rtg_dev, adv_dev, n_samples, var,
-                    clip, 3, step, lr, beta1, beta2, eps, adam_m_dev, adam_v_dev, grad_dev, stats_dev, workspace_dev, stream, max_norm,
-                    clip_stats_dev);
+    return mlp64_epoch<NavppoMode::kClip>("navppo_mlp64_bf16x3_update_epoch_clipped", params_dev, x3_rows(prep_dev, obs_dim),
+                                          {act_dev, logp_old_dev, rtg_dev, adv_dev, n_samples, var, clip}, 3,
+                                          {lr, beta1, beta2, eps, step, adam_m_dev, adam_v_dev, max_norm, clip_stats_dev}, grad_dev, stats_dev,
+                                          workspace_dev, stream);
 }
 
 int navppo_episode_sums(const uint8_t* ended_dev, const uint8_t* arrive_dev, const uint8_t* done_dev, const int32_t* ep_length_dev,
                         const float* ep_return_dev, int64_t n, double* sums_dev, void* workspace_dev, void* stream) {
-    if (!ended_dev || !arrive_dev || !done_dev || !ep_length_dev || !ep_return_dev || !sums_dev || !workspace_dev || n < 0) {
-        g_err = "navppo_episode_sums: bad argument";
-        return -1;
-    }
+    if (!ended_dev || !arrive_dev || !done_dev || !ep_length_dev || !ep_return_dev || !sums_dev || !workspace_dev || n < 0)
+        return navppo_bad_args("navppo_episode_sums", "bad argument");
     double* partial = reinterpret_cast<double*>(workspace_dev);
     const long long want = (n + kSumThreads - 1) / kSumThreads;
     const int blocks = (int)(want < 1 ? 1 : (want < kSumBlocks ? want : kSumBlocks));
@@ -2074,37 +1947,23 @@ int navppo_episode_sums(const uint8_t* ended_dev, const uint8_t* arrive_dev, con
         hipLaunchKernelGGL(episode_sums_partial<false>, dim3(blocks), dim3(kSumThreads), 0, (hipStream_t)stream, ended_dev, arrive_dev,
                            done_dev, ep_length_dev, ep_return_dev, (long long)n, partial);
     hipLaunchKernelGGL(episode_sums_final, dim3(1), dim3(kSumBlocks), 0, (hipStream_t)stream, partial, blocks, sums_dev);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        g_err = std::string("navppo_episode_sums: ") + hipGetErrorString(e);
-        return -2;
-    }
-    return 0;
+    return navppo_launched("navppo_episode_sums");
 }
 
 int navppo_mlp64_act(const float* actor_params_dev, const void* obs_dev, int32_t obs_dim, int32_t obs_f16, const float* noise_dev,
                      int64_t n_envs, const float* var_dev, uint64_t seed, uint64_t env_id_base, const uint32_t* step_base_dev,
                      uint32_t step_offset, float* act_dev, float* logp_dev, float* mean_dev, void* stream) {
-    if (!actor_params_dev || !obs_dev || !act_dev || !logp_dev || n_envs < 1 || !var_dev || (obs_dim != 16 && obs_dim != 42)) {
-        g_err = "navppo_mlp64_act: bad argument (obs_dim is 16 or 42)";
-        return -1;
-    }
-    if (((uintptr_t)actor_params_dev & 15) || !obs_aligned(obs_dev, obs_dim, obs_f16)) {
-        g_err = "navppo_mlp64_act: params must be 16-byte aligned, obs 16-byte (42 columns: 8-byte, float16: 4-byte)";
-        return -1;
-    }
+    if (!actor_params_dev || !obs_dev || !act_dev || !logp_dev || n_envs < 1 || !var_dev || (obs_dim != 16 && obs_dim != 42))
+        return navppo_bad_args("navppo_mlp64_act", "bad argument (obs_dim is 16 or 42)");
+    if (((uintptr_t)actor_params_dev & 15) || !obs_aligned(obs_dev, obs_dim, obs_f16))
+        return navppo_bad_args("navppo_mlp64_act", "params must be 16-byte aligned, obs 16-byte (42 columns: 8-byte, float16: 4-byte)");
     const int blocks = (int)((n_envs + kActEnvs - 1) / kActEnvs);
     for_obs(obs_dim, obs_f16, [&](auto in, auto f16) {
         hipLaunchKernelGGL((mlp64_act<decltype(in)::value, decltype(f16)::value>), dim3(blocks), dim3(64), 0, (hipStream_t)stream,
                            actor_params_dev, obs_dev, noise_dev, (long long)n_envs, var_dev, seed, env_id_base, step_base_dev, step_offset,
                            act_dev, logp_dev, mean_dev);
     });
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        g_err = std::string("navppo_mlp64_act: ") + hipGetErrorString(e);
-        return -2;
-    }
-    return 0;
+    return navppo_launched("navppo_mlp64_act");
 }
 
 }  // extern "C"

@@ -1136,8 +1136,6 @@ __global__ __launch_bounds__(kThreads) void resmlp_act(const float* __restrict__
 
 #endif   // NAVPPO_KL_TU
 // ---------------------------------------------------------------- host side
-thread_local std::string g_err;
-
 struct Plan {
     int groups, wgs, e_blocks;
     float *p1, *h1, *p2, *dy2, *qb, *wpart, *epart;
@@ -1171,78 +1169,61 @@ Plan make_plan(void* ws, int64_t n, int n_nets) {
     return p;
 }
 
-bool launch_ok(const char* what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        g_err = std::string(what) + ": " + hipGetErrorString(e);
-        return false;
-    }
-    return true;
-}
-
-#ifndef NAVPPO_KL_TU   // (to the end of the file: ppo_resmlp512_kl.hip has the gated epoch's launches and entry point)
 // forward of `n_nets` nets starting at net_base (0 = actor, 1 = critic) up to the partial sums of rb2
-void launch_forward(const Plan& p, const float* params, int net_base, int n_nets, const void* obs, int obs_f16, int64_t n, hipStream_t st) {
+void launch_forward(const Plan& p, const float* params, int net_base, int n_nets, const void* obs, int obs_f16, long long n, hipStream_t st,
+                    const float* kl_state = nullptr) {
     // (a forward workgroup = a PAIR of slices: FSP times the groups on the same number of workgroups)
-    hipLaunchKernelGGL(resmlp_fwd<16>, dim3(p.wgs), dim3(kThreads), 0, st, params, net_base, n_nets, obs, (const float*)nullptr,
-                       (float*)nullptr, (long long)n, p.groups * FSP, p.p1, obs_f16);
-    hipLaunchKernelGGL(resmlp_fwd<32>, dim3(p.wgs), dim3(kThreads), 0, st, params, net_base, n_nets, obs, (const float*)p.p1, p.h1,
-                       (long long)n, p.groups * FSP, p.p2, obs_f16);
+    hipLaunchKernelGGL(NAVPPO_KL_KERNEL(resmlp_fwd)<16>, dim3(p.wgs), dim3(kThreads), 0, st, params, net_base, n_nets, obs, (const float*)nullptr,
+                       (float*)nullptr, n, p.groups * FSP, p.p1, obs_f16 NAVPPO_KL_ARG(kl_state));
+    hipLaunchKernelGGL(NAVPPO_KL_KERNEL(resmlp_fwd)<32>, dim3(p.wgs), dim3(kThreads), 0, st, params, net_base, n_nets, obs, (const float*)p.p1, p.h1,
+                       n, p.groups * FSP, p.p2, obs_f16 NAVPPO_KL_ARG(kl_state));
 }
 
-int loss_grad_impl(const char* name, bool adam, float* params, const void* obs, int32_t obs_f16, const float* act, const float* logp_old,
-                   const float* rtg, const float* adv, int64_t n, float var, float clip, float lr, float beta1, float beta2,
-                   float eps, int32_t step, float* adam_m, float* adam_v, float* grad, float* stats, void* ws, void* stream,
-                   float max_norm = 0.f, float* clip_stats = nullptr) {
-    if (!params || !obs || !act || !logp_old || !rtg || !adv || !grad || !stats || !ws || n < 1 || !(var > 0.f) ||
-        (adam && (!adam_m || !adam_v || step < 1))) {
-        g_err = std::string(name) + ": bad argument";
-        return -1;
-    }
-    if (((uintptr_t)obs & 15) || ((uintptr_t)act & 7)) {
-        g_err = std::string(name) + ": obs must be 16-byte and act 8-byte aligned";
-        return -1;
-    }
+// THE launch sequence of the family: navppo_resmlp512_loss_grad and _update_epoch[_clipped | _kl] are this function (the gated epoch:
+// compiled in ppo_resmlp512_kl.hip, every kernel its twin -- navppo_internal.h)
+template <NavppoMode MODE>
+int loss_grad_impl(const char* name, float* params, const void* obs, int32_t obs_f16, const NavppoBatch& b, const NavppoStep& s, float* grad,
+                   float* stats, void* ws, void* stream) {
+    static_assert((MODE == NavppoMode::kClipKl) == kNavppoKlTu, "the gated mode is the twins' translation unit's, the others are not");
+    if (!params || !obs || !b.ok() || !grad || !stats || !ws) return navppo_bad_args(name, "bad argument");
+    if (((uintptr_t)obs & 15) || ((uintptr_t)b.act & 7)) return navppo_bad_args(name, "obs must be 16-byte and act 8-byte aligned");
+    if (const int rc = navppo_check_step(name, MODE, s)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const Plan p = make_plan(ws, n, 2);
-    const float inv_n = 1.0f / (float)n;
+    const Plan p = make_plan(ws, b.n, 2);
+    const float inv_n = 1.0f / (float)b.n;
     const int f16 = obs_f16 != 0;
-    launch_forward(p, params, 0, 2, obs, f16, n, st);
-    hipLaunchKernelGGL(resmlp_e2<false>, dim3(p.e_blocks, 2), dim3(kEThreads), 0, st, (const float*)params, 0, obs, (const float*)p.h1,
-                       (const float*)p.p2, act, logp_old, rtg, adv, (long long)n, var, clip, inv_n, p.dy2, p.epart, (float*)nullptr, f16);
+    const long long n = b.n;
+    const float *const w = params, *const h1 = p.h1, *const dy2 = p.dy2;
+    launch_forward(p, w, 0, 2, obs, f16, n, st, s.kl_state);
+    hipLaunchKernelGGL(NAVPPO_KL_KERNEL(resmlp_e2)<false>, dim3(p.e_blocks, 2), dim3(kEThreads), 0, st, w, 0, obs, h1, (const float*)p.p2, b.act,
+                       b.logp_old, b.rtg, b.adv, n, b.var, b.clip, inv_n, p.dy2, p.epart, (float*)nullptr, f16 NAVPPO_KL_ARG(s.kl_state));
     if constexpr (RESMLP_BWD2S && kBwd2Waves == b2s::SW) {
         if (f16)
-            hipLaunchKernelGGL(resmlp_bwd2s<true>, dim3(p.wgs), dim3(64 * b2s::SW), 0, st, (const float*)params, 2, obs, (const float*)p.h1,
-                               (const float*)p.dy2, (long long)n, p.groups, p.wpart, p.qb);
+            hipLaunchKernelGGL(NAVPPO_KL_KERNEL(resmlp_bwd2s)<true>, dim3(p.wgs), dim3(64 * b2s::SW), 0, st, w, 2, obs, h1, dy2, n, p.groups, p.wpart,
+                               p.qb NAVPPO_KL_ARG(s.kl_state));
         else
-            hipLaunchKernelGGL(resmlp_bwd2s<false>, dim3(p.wgs), dim3(64 * b2s::SW), 0, st, (const float*)params, 2, obs, (const float*)p.h1,
-                               (const float*)p.dy2, (long long)n, p.groups, p.wpart, p.qb);
+            hipLaunchKernelGGL(NAVPPO_KL_KERNEL(resmlp_bwd2s)<false>, dim3(p.wgs), dim3(64 * b2s::SW), 0, st, w, 2, obs, h1, dy2, n, p.groups, p.wpart,
+                               p.qb NAVPPO_KL_ARG(s.kl_state));
     } else
-        hipLaunchKernelGGL((resmlp_bwd<32, 2, kBwd2Waves>), dim3(p.wgs), dim3(64 * kBwd2Waves), 0, st, (const float*)params, 2, obs, (const float*)p.h1,
-                           (const float*)p.dy2, (long long)n, p.groups, p.wpart, p.qb, (const float*)nullptr, f16);
-    hipLaunchKernelGGL((resmlp_bwd<16, 2, kBwd1Waves>), dim3(p.wgs), dim3(64 * kBwd1Waves), 0, st, (const float*)params, 2, obs, (const float*)p.h1,
-                       (const float*)p.dy2, (long long)n, p.groups, p.wpart, (float*)nullptr, (const float*)p.qb, f16);
+        hipLaunchKernelGGL((NAVPPO_KL_KERNEL(resmlp_bwd)<32, 2, kBwd2Waves>), dim3(p.wgs), dim3(64 * kBwd2Waves), 0, st, w, 2, obs, h1, dy2, n, p.groups,
+                           p.wpart, p.qb, (const float*)nullptr, f16 NAVPPO_KL_ARG(s.kl_state));
+    hipLaunchKernelGGL((NAVPPO_KL_KERNEL(resmlp_bwd)<16, 2, kBwd1Waves>), dim3(p.wgs), dim3(64 * kBwd1Waves), 0, st, w, 2, obs, h1, dy2, n, p.groups,
+                       p.wpart, (float*)nullptr, (const float*)p.qb, f16 NAVPPO_KL_ARG(s.kl_state));
+    // the reduction.  kAdam: Adam in the same launch, its blocks' squared-norm slots in parity step & 1 for the logged means.
+    // kClip / kClipKl: the reduction alone, the slots in parity 0; then the norms, the KL decision on stats[1], the clip and Adam
+    constexpr bool kAdam = MODE == NavppoMode::kAdam, kClip = MODE == NavppoMode::kClip || MODE == NavppoMode::kClipKl;
     const int rblocks = (rp::P_ACTOR + rp::P_CRITIC + 63) / 64;
-    if (clip_stats) {   // the reduction alone, its blocks' squared-norm slots in parity 0; then the norms, the clip and Adam (clip_adam_kernel)
-        hipLaunchKernelGGL(resmlp_reduce<false>, dim3(rblocks), dim3(64 * kRedGroups), 0, st, (const float*)p.wpart, p.groups * kBwd1Waves,
-                           p.groups * kBwd2Waves, (const float*)p.epart, p.e_blocks, inv_n, grad, stats, (float*)nullptr, (float*)nullptr, (float*)nullptr, 0.f,
-                           0.f, 0.f, 0.f, 1.f, 1.f, p.epart, 0);
-        navppo_launch_clip_adam(params, grad, adam_m, adam_v, rp::P_ACTOR + rp::P_CRITIC, rp::P_ACTOR, 1.0f, max_norm, lr, beta1, beta2, eps, step,
-                                p.epart, rblocks, kGnSlotsR, EP, clip_stats, stream);
-    } else if (adam) {
-        const float bc1 = (float)(1.0 - std::pow((double)beta1, (double)step));
-        const float bc2_sqrt = (float)std::sqrt(1.0 - std::pow((double)beta2, (double)step));
-        hipLaunchKernelGGL(resmlp_reduce<true>, dim3(rblocks), dim3(64 * kRedGroups), 0, st, (const float*)p.wpart, p.groups * kBwd1Waves,
-                           p.groups * kBwd2Waves, (const float*)p.epart, p.e_blocks, inv_n, grad, stats, params, adam_m, adam_v, lr, beta1, beta2, eps, bc1, bc2_sqrt,
-                           p.epart, (int)(step & 1));
-    } else {
-        hipLaunchKernelGGL(resmlp_reduce<false>, dim3(rblocks), dim3(64 * kRedGroups), 0, st, (const float*)p.wpart, p.groups * kBwd1Waves,
-                           p.groups * kBwd2Waves, (const float*)p.epart, p.e_blocks, inv_n, grad, stats, (float*)nullptr, (float*)nullptr, (float*)nullptr, 0.f,
-                           0.f, 0.f, 0.f, 1.f, 1.f, (float*)nullptr, -1);
-    }
-    return launch_ok(name) ? 0 : -2;
+    const NavppoStep r = kAdam ? s : NavppoStep{};
+    const NavppoBias bc = kAdam ? navppo_bias(s.beta1, s.beta2, s.step) : NavppoBias{1.f, 1.f};
+    const int parity = kClip ? 0 : kAdam ? (int)(s.step & 1) : -1;
+    hipLaunchKernelGGL(NAVPPO_KL_KERNEL(resmlp_reduce)<kAdam>, dim3(rblocks), dim3(64 * kRedGroups), 0, st, (const float*)p.wpart, p.groups * kBwd1Waves,
+                       p.groups * kBwd2Waves, (const float*)p.epart, p.e_blocks, inv_n, grad, stats, kAdam ? params : nullptr, r.m, r.v, r.lr, r.beta1,
+                       r.beta2, r.eps, bc.bc1, bc.bc2_sqrt, parity >= 0 ? p.epart : nullptr, parity NAVPPO_KL_ARG(s.kl_state));
+    if constexpr (kClip)
+        navppo_launch_clip_adam(params, grad, rp::P_ACTOR + rp::P_CRITIC, rp::P_ACTOR, 1.0f, s, p.epart, rblocks, kGnSlotsR, EP, stream,
+                                MODE == NavppoMode::kClipKl ? stats + 1 : nullptr);
+    return navppo_launched(name);
 }
-#endif   // NAVPPO_KL_TU
 
 }  // namespace
 
@@ -1255,22 +1236,18 @@ size_t navppo_resmlp512_workspace_bytes(int64_t n_samples) { return n_samples < 
 int navppo_resmlp512_loss_grad(const float* params_dev, const void* obs_dev, int32_t obs_f16, const float* act_dev, const float* logp_old_dev,
                                const float* rtg_dev, const float* adv_dev, int64_t n_samples, float var, float clip,
                                float* grad_dev, float* stats_dev, void* workspace_dev, void* stream) {
-    const int rc = loss_grad_impl("navppo_resmlp512_loss_grad", false, const_cast<float*>(params_dev), obs_dev, obs_f16, act_dev, logp_old_dev,
-                                  rtg_dev, adv_dev, n_samples, var, clip, 0.f, 0.f, 0.f, 0.f, 1, nullptr, nullptr, grad_dev, stats_dev,
-                                  workspace_dev, stream);
-    if (rc != 0) navppo_set_error(g_err.c_str());
-    return rc;
+    return loss_grad_impl<NavppoMode::kGrad>("navppo_resmlp512_loss_grad", const_cast<float*>(params_dev), obs_dev, obs_f16,
+                                             {act_dev, logp_old_dev, rtg_dev, adv_dev, n_samples, var, clip}, {}, grad_dev, stats_dev, workspace_dev,
+                                             stream);
 }
 
 int navppo_resmlp512_update_epoch(float* params_dev, const void* obs_dev, int32_t obs_f16, const float* act_dev, const float* logp_old_dev,
                                   const float* rtg_dev, const float* adv_dev, int64_t n_samples, float var, float clip, float lr,
                                   float beta1, float beta2, float eps, int32_t step, float* adam_m_dev, float* adam_v_dev,
                                   float* grad_dev, float* stats_dev, void* workspace_dev, void* stream) {
-    const int rc = loss_grad_impl("navppo_resmlp512_update_epoch", true, params_dev, obs_dev, obs_f16, act_dev, logp_old_dev, rtg_dev, adv_dev,
-                                  n_samples, var, clip, lr, beta1, beta2, eps, step, adam_m_dev, adam_v_dev, grad_dev, stats_dev,
-                                  workspace_dev, stream);
-    if (rc != 0) navppo_set_error(g_err.c_str());
-    return rc;
+    return loss_grad_impl<NavppoMode::kAdam>("navppo_resmlp512_update_epoch", params_dev, obs_dev, obs_f16,
+                                             {act_dev, logp_old_dev, rtg_dev, adv_dev, n_samples, var, clip},
+                                             {lr, beta1, beta2, eps, step, adam_m_dev, adam_v_dev}, grad_dev, stats_dev, workspace_dev, stream);
 }
 
 int navppo_resmlp512_update_epoch_clipped(float* params_dev, const void* obs_dev, int32_t obs_f16, const float* act_dev, const float* logp_old_dev,
@@ -1278,23 +1255,16 @@ int navppo_resmlp512_update_epoch_clipped(float* params_dev, const void* obs_dev
                                           float beta1, float beta2, float eps, int32_t step, float* adam_m_dev, float* adam_v_dev,
                                           float* grad_dev, float* stats_dev, void* workspace_dev, float max_norm, float* clip_stats_dev,
                                           void* stream) {
-    if (!navppo_max_norm_ok(max_norm) || !clip_stats_dev) {
-        navppo_set_error("navppo_resmlp512_update_epoch_clipped: max_norm must be > 0 (+inf allowed) and clip_stats_dev [4] not null");
-        return -1;
-    }
-    const int rc = loss_grad_impl("navppo_resmlp512_update_epoch_clipped", true, params_dev, obs_dev, obs_f16, act_dev, logp_old_dev, rtg_dev,
-                                  adv_dev, n_samples, var, clip, lr, beta1, beta2, eps, step, adam_m_dev, adam_v_dev, grad_dev, stats_dev,
-                                  workspace_dev, stream, max_norm, clip_stats_dev);
-    if (rc != 0) navppo_set_error(g_err.c_str());
-    return rc;
+    return loss_grad_impl<NavppoMode::kClip>("navppo_resmlp512_update_epoch_clipped", params_dev, obs_dev, obs_f16,
+                                             {act_dev, logp_old_dev, rtg_dev, adv_dev, n_samples, var, clip},
+                                             {lr, beta1, beta2, eps, step, adam_m_dev, adam_v_dev, max_norm, clip_stats_dev}, grad_dev, stats_dev,
+                                             workspace_dev, stream);
 }
 
 int navppo_resmlp512_value(const float* critic_params_dev, const void* obs_dev, int32_t obs_f16, int64_t n_samples, float* value_dev,
                            void* workspace_dev, void* stream) {
-    if (!critic_params_dev || !obs_dev || !value_dev || !workspace_dev || n_samples < 1 || ((uintptr_t)obs_dev & 15)) {
-        navppo_set_error("navppo_resmlp512_value: bad argument (obs must be 16-byte aligned)");
-        return -1;
-    }
+    if (!critic_params_dev || !obs_dev || !value_dev || !workspace_dev || n_samples < 1 || ((uintptr_t)obs_dev & 15))
+        return navppo_bad_args("navppo_resmlp512_value", "bad argument (obs must be 16-byte aligned)");
     hipStream_t st = (hipStream_t)stream;
     const Plan p = make_plan(workspace_dev, n_samples, 1);
     // the kernels index the flat [actor | critic] buffer by net: hand them the address the actor would have
@@ -1303,32 +1273,19 @@ int navppo_resmlp512_value(const float* critic_params_dev, const void* obs_dev, 
     hipLaunchKernelGGL(resmlp_e2<true>, dim3(p.e_blocks, 1), dim3(kEThreads), 0, st, base, 1, obs_dev, (const float*)p.h1,
                        (const float*)p.p2, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr,
                        (long long)n_samples, 1.f, 0.f, 0.f, (float*)nullptr, (float*)nullptr, value_dev, (int)(obs_f16 != 0));
-    if (!launch_ok("navppo_resmlp512_value")) {
-        navppo_set_error(g_err.c_str());
-        return -2;
-    }
-    return 0;
+    return navppo_launched("navppo_resmlp512_value");
 }
 
 int navppo_resmlp512_act(const float* actor_params_dev, const void* obs_dev, int32_t obs_f16, const float* noise_dev, int64_t n_envs,
                          const float* var_dev, uint64_t seed, uint64_t env_id_base, const uint32_t* step_base_dev,
                          uint32_t step_offset, float* act_dev, float* logp_dev, float* mean_dev, void* stream) {
-    if (!actor_params_dev || !obs_dev || !act_dev || !logp_dev || n_envs < 1 || !var_dev) {
-        navppo_set_error("navppo_resmlp512_act: bad argument");
-        return -1;
-    }
-    if (((uintptr_t)actor_params_dev & 15) || ((uintptr_t)obs_dev & 15)) {
-        navppo_set_error("navppo_resmlp512_act: params and obs must be 16-byte aligned");
-        return -1;
-    }
+    if (!actor_params_dev || !obs_dev || !act_dev || !logp_dev || n_envs < 1 || !var_dev) return navppo_bad_args("navppo_resmlp512_act", "bad argument");
+    if (((uintptr_t)actor_params_dev & 15) || ((uintptr_t)obs_dev & 15))
+        return navppo_bad_args("navppo_resmlp512_act", "params and obs must be 16-byte aligned");
     const int blocks = (int)((n_envs + kActEnvs - 1) / kActEnvs);
     hipLaunchKernelGGL(resmlp_act, dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, actor_params_dev, obs_dev, noise_dev,
                        (long long)n_envs, var_dev, seed, env_id_base, step_base_dev, step_offset, act_dev, logp_dev, mean_dev, (int)(obs_f16 != 0));
-    if (!launch_ok("navppo_resmlp512_act")) {
-        navppo_set_error(g_err.c_str());
-        return -2;
-    }
-    return 0;
+    return navppo_launched("navppo_resmlp512_act");
 }
 
 }  // extern "C"

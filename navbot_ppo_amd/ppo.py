@@ -19,6 +19,7 @@ of env ids; after each backward ONE all-reduce (RCCL over xGMI; gloo on CPU for 
 flat gradient buffer holding actor+critic; the advantage mean/std come from all-reduced
 (sum, sum of squares, count) so they equal the single-process values of ppo.py:284.
 """
+import ctypes as C
 import dataclasses
 import math
 import os
@@ -28,8 +29,21 @@ import torch
 import torch.distributed as dist
 
 from . import nets
+from ._native import check, lib
 
 LOG_2PI = math.log(2.0 * math.pi)
+
+
+def _ptr(t, offset=0):
+    return C.c_void_p(t.data_ptr() + offset) if offset else C.c_void_p(t.data_ptr())
+
+
+def _navppo(entry, *args):
+    """Calls the navppo_* entry point `entry` (include/navppo.h) with `args` and the current stream; a failure raises under the name
+    of the entry point that was called, with its message."""
+    L = lib()
+    if getattr(L, entry)(*args, C.c_void_p(torch.cuda.current_stream().cuda_stream)) != 0:
+        raise RuntimeError(f"{entry} failed: {L.navppo_last_error().decode()}")
 
 
 @dataclasses.dataclass
@@ -266,7 +280,6 @@ class PPOUpdater:
         self.bf16x3 = self.fused_mlp64 and cfg.update_arith == "bf16x3"   # (16- and 42-column rows, float32 or float16)
         self._prep = self._prep_key = None
         if self.fused:
-            from ._native import lib
             self._n_actor = self.fp.module_numel[0]
             d = self.obs_dim
             assert tuple(self.fp.module_numel) == ((64 * d + 4354, 64 * d + 4289) if self.fused_mlp64 else (50290, 50257))
@@ -283,7 +296,6 @@ class PPOUpdater:
     def _workspace(self, n):
         """Scratch of the fused kernels: fixed for the 2x64 heads, per-sample partial block outputs for the 512-wide nets."""
         if self.fused_resmlp512:
-            from ._native import lib
             need = lib().navppo_resmlp512_workspace_bytes(int(n)) // 4 + 4
             if self._ws is None or self._ws.numel() < need:
                 self._ws = None
@@ -294,30 +306,23 @@ class PPOUpdater:
         """The observation arguments of the fused entry points -- (pointer, obs_dim, obs_f16) for the D-64-64 heads, (pointer, obs_f16)
         for the 512-wide nets -- after checking what is behind the pointer: rows of self.obs_dim columns, float32 or float16 (the
         kernels widen half rows as they load)."""
-        import ctypes as C
         ok = (torch.float32, torch.float16)
         if obs.dim() != 2 or obs.shape[1] != self.obs_dim or obs.dtype not in ok or not obs.is_contiguous():
             raise ValueError(f"{self.fused}: observations must be contiguous [n, {self.obs_dim}] rows of {ok}, got "
                              f"{tuple(obs.shape)} {obs.dtype}")
-        p = C.c_void_p(obs.data_ptr())
+        p = _ptr(obs)
         f16 = int(obs.dtype == torch.float16)
         return (p, self.obs_dim, f16) if self.fused_mlp64 else (p, f16)
 
     def prepare(self, obs):
         """bf16x3: split the batch's observations into bf16 pieces (navppo_mlp64_bf16x3_prepare) -- once per update, the rows do not
         change over the epochs.  The epoch entry points use the prepared buffer while `obs` is the tensor it was made from."""
-        import ctypes as C
-        from ._native import lib
-        L = lib()
         p, d, f16 = self._obs_args(obs)
-        need = L.navppo_mlp64_bf16x3_prep_bytes(int(obs.shape[0]), self.obs_dim)
+        need = lib().navppo_mlp64_bf16x3_prep_bytes(int(obs.shape[0]), self.obs_dim)
         if self._prep is None or self._prep.numel() < need:
             self._prep = None
             self._prep = torch.empty(need, dtype=torch.uint8, device=self.device)
-        rc = L.navppo_mlp64_bf16x3_prepare(p, d, f16, int(obs.shape[0]), C.c_void_p(self._prep.data_ptr()),
-                                           C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        if rc != 0:
-            raise RuntimeError(f"navppo_mlp64_bf16x3_prepare failed: {L.navppo_last_error().decode()}")
+        _navppo("navppo_mlp64_bf16x3_prepare", p, d, f16, int(obs.shape[0]), _ptr(self._prep))
         self._prep_key = (obs.data_ptr(), tuple(obs.shape), obs.dtype, obs._version)
 
     def invalidate_prepared(self):
@@ -328,157 +333,90 @@ class PPOUpdater:
     def _prepared(self, obs):
         """The pre-split pieces of `obs`.  Reused while `obs` is the very tensor prepare() saw, unchanged as far as torch knows
         (pointer, shape, dtype, version counter) AND nobody called invalidate_prepared() since."""
-        import ctypes as C
         if self._prep_key != (obs.data_ptr(), tuple(obs.shape), obs.dtype, obs._version):
             self.prepare(obs)
-        return C.c_void_p(self._prep.data_ptr())
+        return _ptr(self._prep)
+
+    def _batch_args(self, obs, acts, logp_old, rtg, adv, var):
+        """(family, the arguments every *_loss_grad / *_update_epoch entry point of it takes between params_dev and the step's): the
+        rows -- obs, or their prepared pieces -- then acts, logp_old, rtg, adv, n, var, clip."""
+        fam, rows = (("navppo_mlp64_bf16x3", (self._prepared(obs), self.obs_dim)) if self.bf16x3 else (self.fused, self._obs_args(obs)))
+        return fam, (*rows, _ptr(acts), _ptr(logp_old), _ptr(rtg), _ptr(adv), int(obs.shape[0]), float(var), float(self.cfg.clip))
 
     def _fused_loss_grad(self, obs, acts, logp_old, rtg, adv, var, stats=None):
         """evaluate + losses + backward of ppo.py:307-386 in the HIP kernels of csrc/ppo_mlp64.hip; gradients land
         in the flat gradient buffer, (actor_loss, approx_kl, clip_frac, -, critic_loss) in self._fstats."""
-        import ctypes as C
-        from ._native import lib
-        L = lib()
-        ptr = lambda t: C.c_void_p(t.data_ptr())
         for t in (acts, logp_old, rtg, adv):
             assert t.is_contiguous() and t.dtype == torch.float32
-        name, oargs = (("navppo_mlp64_bf16x3", (self._prepared(obs), self.obs_dim)) if self.bf16x3 else (self.fused, self._obs_args(obs)))
-        rc = getattr(L, name + "_loss_grad")(ptr(self.fp.flat), *oargs, ptr(acts), ptr(logp_old), ptr(rtg), ptr(adv),
-                                                   int(obs.shape[0]), float(var), float(self.cfg.clip), ptr(self.fp.grad),
-                                                   ptr(self._fstats if stats is None else stats), ptr(self._workspace(obs.shape[0])),
-                                                   C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        if rc != 0:
-            raise RuntimeError(f"{self.fused}_loss_grad failed: {L.navppo_last_error().decode()}")
+        fam, batch = self._batch_args(obs, acts, logp_old, rtg, adv, var)
+        _navppo(fam + "_loss_grad", _ptr(self.fp.flat), *batch, _ptr(self.fp.grad), _ptr(self._fstats if stats is None else stats),
+                _ptr(self._workspace(obs.shape[0])))
 
     def _fused_loss_grad_net(self, net, obs, acts, logp_old, rtg, adv, var, stats):
-        """One net's half of _fused_loss_grad (navppo_mlp64_loss_grad_net): its slice of the flat gradient, its statistics."""
-        import ctypes as C
-        from ._native import lib
-        L = lib()
-        ptr = lambda t: C.c_void_p(t.data_ptr())
-        fn, oargs = ((L.navppo_mlp64_bf16x3_loss_grad_net, (self._prepared(obs), self.obs_dim)) if self.bf16x3
-                     else (L.navppo_mlp64_loss_grad_net, self._obs_args(obs)))
-        rc = fn(int(net), ptr(self.fp.flat), *oargs, ptr(acts), ptr(logp_old), ptr(rtg), ptr(adv),
-                                          int(obs.shape[0]), float(var), float(self.cfg.clip), ptr(self.fp.grad), ptr(stats),
-                                          ptr(self._workspace(obs.shape[0])), C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        if rc != 0:
-            raise RuntimeError(f"navppo_mlp64_loss_grad_net failed: {L.navppo_last_error().decode()}")
+        """One net's half of _fused_loss_grad (navppo_mlp64[_bf16x3]_loss_grad_net): its slice of the flat gradient, its statistics."""
+        fam, batch = self._batch_args(obs, acts, logp_old, rtg, adv, var)
+        _navppo(fam + "_loss_grad_net", int(net), _ptr(self.fp.flat), *batch, _ptr(self.fp.grad), _ptr(stats),
+                _ptr(self._workspace(obs.shape[0])))
 
     def _fused_adam(self, grad_scale, lo=0, n=None, step=None, cstats=None, kl_dev=None):
         """Scale + Adam on the flat buffer, or on the slice [lo, lo + n) at optimiser step `step` (one net of the pipelined epoch).
         cstats ([4], clipping on): navppo_adam_step_clipped -- per-net norm, guard and clip of the scaled gradient first.
         kl_dev ([1], target_kl on; with cstats): navppo_adam_step_kl -- the stop decision on the global approx_kl in front of that."""
-        import ctypes as C
-        from ._native import lib
-        L = lib()
-        ptr = lambda t: C.c_void_p(t.data_ptr() + 4 * lo)
         if step is None:
             self._adam_t += 1
             step = self._adam_t
-        if kl_dev is not None:
-            n_ = int(self.fp.numel - lo if n is None else n)
-            rc = L.navppo_adam_step_kl(ptr(self.fp.flat), ptr(self.fp.grad), ptr(self._adam_m), ptr(self._adam_v), n_,
-                                       max(0, min(n_, self._n_actor - lo)), float(grad_scale), self._max_norm_arg(), float(self.cfg.lr),
-                                       0.9, 0.999, 1e-8, int(step), C.c_void_p(cstats.data_ptr()), self.kl_limit,
-                                       C.c_void_p(self.kl_state.data_ptr()), C.c_void_p(kl_dev.data_ptr()),
-                                       C.c_void_p(torch.cuda.current_stream().cuda_stream))
-            if rc != 0:
-                raise RuntimeError(f"navppo_adam_step_kl failed: {L.navppo_last_error().decode()}")
-            return
-        if cstats is not None:
-            n_ = int(self.fp.numel - lo if n is None else n)
-            rc = L.navppo_adam_step_clipped(ptr(self.fp.flat), ptr(self.fp.grad), ptr(self._adam_m), ptr(self._adam_v), n_,
-                                            max(0, min(n_, self._n_actor - lo)), float(grad_scale), self.max_norm, float(self.cfg.lr),
-                                            0.9, 0.999, 1e-8, int(step), C.c_void_p(cstats.data_ptr()),
-                                            C.c_void_p(torch.cuda.current_stream().cuda_stream))
-            if rc != 0:
-                raise RuntimeError(f"navppo_adam_step_clipped failed: {L.navppo_last_error().decode()}")
-            return
-        rc = L.navppo_adam_step(ptr(self.fp.flat), ptr(self.fp.grad), ptr(self._adam_m), ptr(self._adam_v),
-                                int(self.fp.numel - lo if n is None else n), float(grad_scale), float(self.cfg.lr), 0.9, 0.999, 1e-8,
-                                int(step), C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        if rc != 0:
-            raise RuntimeError(f"navppo_adam_step failed: {L.navppo_last_error().decode()}")
+        n_ = int(self.fp.numel - lo if n is None else n)
+        head = tuple(_ptr(t, 4 * lo) for t in (self.fp.flat, self.fp.grad, self._adam_m, self._adam_v)) + (n_,)
+        hyper = (float(self.cfg.lr), 0.9, 0.999, 1e-8, int(step))
+        if cstats is None and kl_dev is None:
+            entry, args = "navppo_adam_step", head + (float(grad_scale),) + hyper
+        else:
+            entry = "navppo_adam_step_clipped"
+            args = head + (max(0, min(n_, self._n_actor - lo)), float(grad_scale), self._max_norm_arg()) + hyper + (_ptr(cstats),)
+            if kl_dev is not None:
+                entry, args = "navppo_adam_step_kl", args + (self.kl_limit, _ptr(self.kl_state), _ptr(kl_dev))
+        _navppo(entry, *args)
 
     def _pipelined_epochs(self, n_ep, world, obs, acts, logp_old, rtg, adv, var_f):
         """The multi-GPU epochs of the 2x64 heads as a two-stage pipeline.  Actor and critic are disjoint nets whose losses share
         nothing inside the epoch loop (the advantages are fixed before it, ppo.py:275-284), so each net's all-reduce (RCCL's own
         stream) runs under the OTHER net's pass -- the actor's under the critic's pass of the same epoch, the critic's under the
         actor's pass of the next one -- and neither the wire time nor the cross-stream hand-over is on the compute stream's
-        critical path.  Same kernels on the same data as the unpipelined order: the weights are bit-identical."""
+        critical path.  Same kernels on the same data as the unpipelined order: the weights are bit-identical.
+        Returns every epoch's squared norms of the mean (actor, critic) gradient.  Clipping on: each net's step is
+        navppo_adam_step_clipped, which reports into its own row -- its net's columns are gathered into self.clip_stats at the end."""
         n_a = self._n_actor
-        n_c = self.fp.numel - n_a
         t0 = self._adam_t
-        wa = wc = None
-        gn_sq = torch.zeros((max(n_ep, 1), 2), device=obs.device)   # every epoch's squared norms of the summed (actor, critic) gradient
-        ga, gc = self.fp.grad[:n_a], self.fp.grad[n_a:]
-        if self.max_norm is not None:   # each net's clipped step reports into its own row; its net's columns are gathered at the end
-            return self._pipelined_epochs_clipped(n_ep, world, obs, acts, logp_old, rtg, adv, var_f)
-        for ep in range(n_ep):
-            if wa is not None:   # epoch ep - 1's actor gradient has arrived (long ago: it had the critic's pass to do so)
-                wa.wait()
-                self._fused_adam(1.0 / world, 0, n_a, t0 + ep)
-                gn_sq[ep - 1, 0] = torch.dot(ga, ga)
-            self._fused_loss_grad_net(0, obs, acts, logp_old, rtg, adv, var_f, self._fhist[ep])
-            wa = dist.all_reduce(self.fp.grad[:n_a], op=dist.ReduceOp.SUM, async_op=True)
-            if wc is not None:
-                wc.wait()
-                self._fused_adam(1.0 / world, n_a, n_c, t0 + ep)
-                gn_sq[ep - 1, 1] = torch.dot(gc, gc)
-            self._fused_loss_grad_net(1, obs, acts, logp_old, rtg, adv, var_f, self._fhist[ep])
-            wc = dist.all_reduce(self.fp.grad[n_a:], op=dist.ReduceOp.SUM, async_op=True)
-        if wa is not None:
-            wa.wait()
-            self._fused_adam(1.0 / world, 0, n_a, t0 + n_ep)
-            gn_sq[n_ep - 1, 0] = torch.dot(ga, ga)
-            wc.wait()
-            self._fused_adam(1.0 / world, n_a, n_c, t0 + n_ep)
-            gn_sq[n_ep - 1, 1] = torch.dot(gc, gc)
+        clipped = self.max_norm is not None
+        nets_ = ((0, n_a, self.fp.grad[:n_a]), (n_a, self.fp.numel - n_a, self.fp.grad[n_a:]))   # (offset, parameters, gradient)
+        if clipped:
+            cs2 = torch.zeros((max(n_ep, 1), 2, 4), dtype=torch.float32, device=obs.device)
+        else:
+            gn_sq = torch.zeros((max(n_ep, 1), 2), device=obs.device)
+        waits = [None, None]
+        for ep in range(n_ep + 1):   # (the last round: only the steps of epoch n_ep - 1)
+            for k, (lo, n, g) in enumerate(nets_):
+                if waits[k] is not None:   # epoch ep - 1's gradient of net k has arrived (long ago: it had the other net's pass to do so)
+                    waits[k].wait()
+                    if clipped:
+                        self._fused_adam(1.0 / world, lo, n, t0 + ep, cstats=cs2[ep - 1, k])
+                    else:
+                        self._fused_adam(1.0 / world, lo, n, t0 + ep)
+                        gn_sq[ep - 1, k] = torch.dot(g, g)
+                if ep < n_ep:
+                    self._fused_loss_grad_net(k, obs, acts, logp_old, rtg, adv, var_f, self._fhist[ep])
+                    waits[k] = dist.all_reduce(g, op=dist.ReduceOp.SUM, async_op=True)
         self._adam_t = t0 + n_ep
+        if clipped:
+            self.clip_stats = torch.stack([cs2[:n_ep, 0, 0], cs2[:n_ep, 1, 1], cs2[:n_ep, 0, 2], cs2[:n_ep, 1, 3]], 1)
+            return self.clip_stats[:, :2]   # squared norms of the MEAN gradient, per epoch and net
         return gn_sq / float(world) ** 2
-
-    def _pipelined_epochs_clipped(self, n_ep, world, obs, acts, logp_old, rtg, adv, var_f):
-        """_pipelined_epochs with navppo_adam_step_clipped per net: same order of launches and all-reduces; fills self.clip_stats."""
-        n_a = self._n_actor
-        n_c = self.fp.numel - n_a
-        t0 = self._adam_t
-        wa = wc = None
-        cs2 = torch.zeros((max(n_ep, 1), 2, 4), dtype=torch.float32, device=obs.device)
-        for ep in range(n_ep):
-            if wa is not None:
-                wa.wait()
-                self._fused_adam(1.0 / world, 0, n_a, t0 + ep, cstats=cs2[ep - 1, 0])
-            self._fused_loss_grad_net(0, obs, acts, logp_old, rtg, adv, var_f, self._fhist[ep])
-            wa = dist.all_reduce(self.fp.grad[:n_a], op=dist.ReduceOp.SUM, async_op=True)
-            if wc is not None:
-                wc.wait()
-                self._fused_adam(1.0 / world, n_a, n_c, t0 + ep, cstats=cs2[ep - 1, 1])
-            self._fused_loss_grad_net(1, obs, acts, logp_old, rtg, adv, var_f, self._fhist[ep])
-            wc = dist.all_reduce(self.fp.grad[n_a:], op=dist.ReduceOp.SUM, async_op=True)
-        if wa is not None:
-            wa.wait()
-            self._fused_adam(1.0 / world, 0, n_a, t0 + n_ep, cstats=cs2[n_ep - 1, 0])
-            wc.wait()
-            self._fused_adam(1.0 / world, n_a, n_c, t0 + n_ep, cstats=cs2[n_ep - 1, 1])
-        self._adam_t = t0 + n_ep
-        self.clip_stats = torch.stack([cs2[:n_ep, 0, 0], cs2[:n_ep, 1, 1], cs2[:n_ep, 0, 2], cs2[:n_ep, 1, 3]], 1)
-        return self.clip_stats[:, :2]   # squared norms of the MEAN gradient, per epoch and net
 
     def _fused_value(self, obs):
         """V = critic(obs).squeeze() (ppo.py:275) by the forward half of the critic's fused pass."""
-        import ctypes as C
-        from ._native import lib
-        L = lib()
         out = torch.empty(obs.shape[0], dtype=torch.float32, device=obs.device)
-        critic = C.c_void_p(self.fp.flat.data_ptr() + 4 * self._n_actor)
-        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        if self.fused_resmlp512:
-            rc = L.navppo_resmlp512_value(critic, *self._obs_args(obs), int(obs.shape[0]), C.c_void_p(out.data_ptr()),
-                                          C.c_void_p(self._workspace(obs.shape[0]).data_ptr()), st)
-        else:
-            rc = L.navppo_mlp64_value(critic, *self._obs_args(obs), int(obs.shape[0]), C.c_void_p(out.data_ptr()), st)
-        if rc != 0:
-            raise RuntimeError(f"{self.fused}_value failed: {L.navppo_last_error().decode()}")
+        ws = (_ptr(self._workspace(obs.shape[0])),) if self.fused_resmlp512 else ()
+        _navppo(self.fused + "_value", _ptr(self.fp.flat, 4 * self._n_actor), *self._obs_args(obs), int(obs.shape[0]), _ptr(out), *ws)
         return out
 
     def _max_norm_arg(self):
@@ -489,24 +427,15 @@ class PPOUpdater:
         """One epoch of ppo.py:305-392 on one GPU: losses, gradients and both Adam steps in four launches.  cstats ([4], clipping on):
         the *_update_epoch_clipped entry point -- one more small launch that clips and steps behind the reduction.  target_kl on (with
         cstats): the *_update_epoch_kl entry point -- gated twins of the same launches, the stop decision in the step launch."""
-        import ctypes as C
-        from ._native import lib
-        L = lib()
-        ptr = lambda t: C.c_void_p(t.data_ptr())
         self._adam_t += 1
-        name, oargs = (("navppo_mlp64_bf16x3", (self._prepared(obs), self.obs_dim)) if self.bf16x3 else (self.fused, self._obs_args(obs)))
-        clipped = () if cstats is None else (self._max_norm_arg(), ptr(cstats))
-        entry = name + ("_update_epoch" if cstats is None else "_update_epoch_clipped")
+        fam, batch = self._batch_args(obs, acts, logp_old, rtg, adv, var)
+        mode, extra = "", ()
+        if cstats is not None:
+            mode, extra = "_clipped", (self._max_norm_arg(), _ptr(cstats))
         if self.kl_limit is not None:
-            clipped += (self.kl_limit, ptr(self.kl_state))
-            entry = name + "_update_epoch_kl"
-        rc = getattr(L, entry)(ptr(self.fp.flat), *oargs, ptr(acts), ptr(logp_old), ptr(rtg), ptr(adv),
-                               int(obs.shape[0]), float(var), float(self.cfg.clip), float(self.cfg.lr), 0.9,
-                               0.999, 1e-8, int(self._adam_t), ptr(self._adam_m), ptr(self._adam_v),
-                               ptr(self.fp.grad), ptr(stats), ptr(self._workspace(obs.shape[0])), *clipped,
-                               C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        if rc != 0:
-            raise RuntimeError(f"{entry} failed: {L.navppo_last_error().decode()}")
+            mode, extra = "_kl", extra + (self.kl_limit, _ptr(self.kl_state))
+        _navppo(fam + "_update_epoch" + mode, _ptr(self.fp.flat), *batch, float(self.cfg.lr), 0.9, 0.999, 1e-8, int(self._adam_t),
+                _ptr(self._adam_m), _ptr(self._adam_v), _ptr(self.fp.grad), _ptr(stats), _ptr(self._workspace(obs.shape[0])), *extra)
 
     def _clip_and_step(self, ep):
         """The PyTorch formulation of a clipped epoch's optimiser step (the CPU / gloo path and the tests' float32 reference), the
@@ -779,8 +708,6 @@ class PPOTrainer:
 
     def _fused_act(self, t, noise=None):
         """PPO.get_action for all envs in ONE launch (csrc/ppo_mlp64.hip: mlp64_act, csrc/ppo_resmlp512.hip: resmlp_act)."""
-        import ctypes as C
-        from ._native import lib
         ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())
         L = lib()
         rc = getattr(L, self.updater.fused + "_act")(ptr(self.updater.fp.flat), *self.updater._obs_args(self.obs_buf[t]), ptr(noise), self.env.N,
@@ -810,8 +737,6 @@ class PPOTrainer:
     def _persistent_rollout(self):
         """ppo.py:505-594 in ONE launch (csrc/navsim.hip: rollout_kernel): policy step and env step alternate inside the
         kernel; same device functions and Philox keys as the per-step path, so the buffers come out bit-identical."""
-        import ctypes as C
-        from ._native import check, lib
         ptr = lambda x: C.c_void_p(x.data_ptr())
         sim = self.env.sim
         entry = lib().navsim_rollout_resmlp512 if self.updater.fused_resmlp512 else lib().navsim_rollout_mlp64
@@ -905,8 +830,6 @@ class PPOTrainer:
     def _rollout_metrics_dev(self):
         """The six sums behind the iteration's episode metrics as ONE device tensor (all-reduced over the ranks); nothing
         here waits for the GPU, so the update can be queued behind it."""
-        import ctypes as C   # one pass over the five buffers (navppo_episode_sums), deterministic
-        from ._native import lib
         ptr = lambda x: C.c_void_p(x.data_ptr())
         if getattr(self, "_sums_ws", None) is None:
             self._sums_ws = torch.empty(256 * 6, dtype=torch.float64, device=self.device)

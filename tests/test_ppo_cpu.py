@@ -254,3 +254,58 @@ def test_tensorboard_event_writer_roundtrip(tmp_path):
     assert T.read_scalars(w.path) == [("train/mean_return", 3, 12.5), ("loss/actor", 300, -0.25), ("perf/steps_per_sec", 1 << 40, 3.5e7)]
     raw = open(w.path, "rb").read()
     assert b"brain.Event:2" in raw[:64]
+
+
+@pytest.mark.parametrize("max_norm", [None, 0.5])
+@pytest.mark.parametrize("n_ep", [0, 1, 3])
+def test_pipelined_epochs_order_of_passes_all_reduces_waits_and_steps(monkeypatch, n_ep, max_norm):
+    """The two-stage pipeline of PPOUpdater._pipelined_epochs without a device: the per-net passes, the asynchronous all-reduces, the
+    waits and the per-net optimiser steps, in the order the loop issues them (each net's all-reduce under the other net's pass)."""
+    torch.manual_seed(0)
+    a, c = nets.make_policy("mlp64x2")
+    up = ppo.PPOUpdater(a, c, ppo.PPOConfig(policy="mlp64x2", n_updates_per_iteration=3, max_grad_norm=max_norm), None, torch.device("cpu"))
+    n_a, n_c = 5378, 5313
+    assert tuple(up.fp.module_numel) == (n_a, n_c)
+    up._n_actor, up._adam_t, up._fhist = n_a, 10, torch.zeros((3, 8))
+    log = []
+    where = lambda t: (t.storage_offset(), t.numel())
+
+    class Handle:
+        def __init__(self, sl):
+            self.sl = sl
+
+        def wait(self):
+            log.append(("wait", self.sl, None, False))
+
+    def all_reduce(t, op=None, async_op=False):
+        assert async_op and op == ppo.dist.ReduceOp.SUM and t.untyped_storage().data_ptr() == up.fp.grad.untyped_storage().data_ptr()
+        log.append(("all_reduce", where(t), None, False))
+        return Handle(where(t))
+
+    def loss_grad_net(net, obs, acts, logp_old, rtg, adv, var, stats):
+        log.append(("pass", net, stats.storage_offset() // 8, False))   # (third entry: the row of _fhist, the epoch)
+
+    def adam(grad_scale, lo=0, n=None, step=None, cstats=None, kl_dev=None):
+        assert grad_scale == 0.5 and kl_dev is None
+        log.append(("step", (lo, n), step, cstats is not None))
+
+    monkeypatch.setattr(up, "_fused_loss_grad_net", loss_grad_net)
+    monkeypatch.setattr(up, "_fused_adam", adam)
+    monkeypatch.setattr(ppo.dist, "all_reduce", all_reduce)
+    z = torch.zeros(4)
+    out = up._pipelined_epochs(n_ep, 2, torch.zeros((4, 16)), z, z, z, z, 0.6)
+    A, B, K = (0, n_a), (n_a, n_c), max_norm is not None
+    first = [("pass", 0, 0, False), ("all_reduce", A, None, False), ("pass", 1, 0, False), ("all_reduce", B, None, False)]
+    want = {0: [],
+            1: first + [("wait", A, None, False), ("step", A, 11, K), ("wait", B, None, False), ("step", B, 11, K)],
+            3: first + [("wait", A, None, False), ("step", A, 11, K), ("pass", 0, 1, False), ("all_reduce", A, None, False),
+                        ("wait", B, None, False), ("step", B, 11, K), ("pass", 1, 1, False), ("all_reduce", B, None, False),
+                        ("wait", A, None, False), ("step", A, 12, K), ("pass", 0, 2, False), ("all_reduce", A, None, False),
+                        ("wait", B, None, False), ("step", B, 12, K), ("pass", 1, 2, False), ("all_reduce", B, None, False),
+                        ("wait", A, None, False), ("step", A, 13, K), ("wait", B, None, False), ("step", B, 13, K)]}[n_ep]
+    assert log == want
+    assert up._adam_t == 10 + n_ep
+    if K:
+        assert tuple(out.shape) == (n_ep, 2) and tuple(up.clip_stats.shape) == (n_ep, 4)
+    else:
+        assert tuple(out.shape) == (max(n_ep, 1), 2) and up.clip_stats is None
