@@ -32,6 +32,7 @@ from . import nets
 from ._native import check, lib
 
 LOG_2PI = math.log(2.0 * math.pi)
+ADAM_HYPER = (0.9, 0.999, 1e-8)   # Adam's (beta1, beta2, eps), torch's defaults (ppo.py:116-117): torch.optim.Adam and the fused steps
 
 
 def _ptr(t, offset=0):
@@ -236,8 +237,16 @@ def normalise_advantages(adv, ctx=None):
     return ((adv - mean.float()) / (std.float() + 1e-10))
 
 
+# What each of PPOUpdater's four epoch runners hands to _summarise.  k: the epochs whose passes ran = the rows the statistics are taken
+# over; steps, stopped: optimiser steps taken, whether target_kl stopped the update early (k = steps + stopped); losses: [n_ep, 2] per-epoch
+# (actor, critic) loss, NaN behind a stop; sums: [4] sums over the k epochs of (actor loss, critic loss, approx_kl, clip_frac); gn_sum, v_sum:
+# the same of the whole gradient's norm and the mean value; net_gn: [2] of the per-net norms, if the runner has them; net_gn_open: less the last's
+_Epochs = dataclasses.make_dataclass("_Epochs", ["k", "steps", "stopped", "losses", "sums", "gn_sum", "v_sum",
+                                                 ("net_gn", object, None), ("net_gn_open", bool, False)])
+
+
 class PPOUpdater:
-    """The update half of PPO.learn (ppo.py:275-397) on a fixed batch; device-agnostic PyTorch."""
+    """The update half of PPO.learn (ppo.py:275-397) on a fixed batch: the host side of the fused HIP update and its PyTorch formulation."""
 
     def __init__(self, actor, critic, cfg, ctx=None, device=None):
         self.actor, self.critic, self.cfg, self.ctx = actor, critic, cfg, ctx
@@ -246,7 +255,7 @@ class PPOUpdater:
         if ctx is not None:
             ctx.broadcast(self.fp.flat, 0)  # identical replicas; identical Adam steps keep them in sync
         fused = self.device.type == "cuda"
-        self.opt = torch.optim.Adam([self.fp.proxy], lr=cfg.lr, fused=fused)  # == the two Adam(lr) of ppo.py:116-117
+        self.opt = torch.optim.Adam([self.fp.proxy], lr=cfg.lr, betas=ADAM_HYPER[:2], eps=ADAM_HYPER[2], fused=fused)  # == ppo.py:116-117
         self.stats = {}
         # HIP paths: fused f32-MFMA kernels instead of ~40 (mlp64x2) / ~120 (resmlp512) PyTorch kernels per epoch
         on_gpu = self.device.type == "cuda" and cfg.fused_update
@@ -264,6 +273,8 @@ class PPOUpdater:
         if cfg.target_kl is not None and cfg.overlap_allreduce:
             raise ValueError("target_kl with overlap_allreduce=True: the per-net pipeline has no place for the stop decision")
         self.kl_limit = None if cfg.target_kl is None else 1.5 * float(cfg.target_kl)   # Stable-Baselines3's factor
+        # the clipped machinery runs and fills clip_stats: max_grad_norm, or target_kl alone -- at max_norm = +inf: the unclipped epochs' bits
+        self._clipping = self.max_norm is not None or self.kl_limit is not None
         self.kl_state = None     # target_kl on, fused: [4] (stopped, steps taken, tripping approx_kl, its step) of the last update(), on the device
         self.clip_stats = None   # clipping on: [n_ep, 4] (s_actor, s_critic, coef_actor, coef_critic) of the last update(), on the device
         self.fused_resmlp512 = (on_gpu and cfg.policy == "resmlp512" and isinstance(actor, nets.ResMLPActor)
@@ -279,8 +290,8 @@ class PPOUpdater:
         self.fused = "navppo_mlp64" if self.fused_mlp64 else "navppo_resmlp512" if self.fused_resmlp512 else None
         self.bf16x3 = self.fused_mlp64 and cfg.update_arith == "bf16x3"   # (16- and 42-column rows, float32 or float16)
         self._prep = self._prep_key = None
+        self._n_actor = self.fp.module_numel[0]   # the actor's slice of the flat buffers is [0, _n_actor), the critic's the rest
         if self.fused:
-            self._n_actor = self.fp.module_numel[0]
             d = self.obs_dim
             assert tuple(self.fp.module_numel) == ((64 * d + 4354, 64 * d + 4289) if self.fused_mlp64 else (50290, 50257))
             self._ws = None
@@ -367,7 +378,7 @@ class PPOUpdater:
             step = self._adam_t
         n_ = int(self.fp.numel - lo if n is None else n)
         head = tuple(_ptr(t, 4 * lo) for t in (self.fp.flat, self.fp.grad, self._adam_m, self._adam_v)) + (n_,)
-        hyper = (float(self.cfg.lr), 0.9, 0.999, 1e-8, int(step))
+        hyper = (float(self.cfg.lr), *ADAM_HYPER, int(step))
         if cstats is None and kl_dev is None:
             entry, args = "navppo_adam_step", head + (float(grad_scale),) + hyper
         else:
@@ -434,7 +445,7 @@ class PPOUpdater:
             mode, extra = "_clipped", (self._max_norm_arg(), _ptr(cstats))
         if self.kl_limit is not None:
             mode, extra = "_kl", extra + (self.kl_limit, _ptr(self.kl_state))
-        _navppo(fam + "_update_epoch" + mode, _ptr(self.fp.flat), *batch, float(self.cfg.lr), 0.9, 0.999, 1e-8, int(self._adam_t),
+        _navppo(fam + "_update_epoch" + mode, _ptr(self.fp.flat), *batch, float(self.cfg.lr), *ADAM_HYPER, int(self._adam_t),
                 _ptr(self._adam_m), _ptr(self._adam_v), _ptr(self.fp.grad), _ptr(stats), _ptr(self._workspace(obs.shape[0])), *extra)
 
     def _clip_and_step(self, ep):
@@ -442,7 +453,7 @@ class PPOUpdater:
         contract of the navppo_*_clipped entry points per net: s = sum of squares of the net's gradient; s not finite: that net's
         slice of the parameters and of Adam's exp_avg / exp_avg_sq is restored after the step (the step counter advances), its
         coefficient is 0 and its gradient stays unclipped; else the gradient is scaled by min(1, max_norm / (sqrt(s) + 1e-6))."""
-        n_a, cs = self.fp.module_numel[0], self.clip_stats
+        n_a, cs = self._n_actor, self.clip_stats
         oks = []
         with torch.no_grad():
             for k, (lo, hi) in enumerate(((0, n_a), (n_a, self.fp.numel))):
@@ -470,192 +481,181 @@ class PPOUpdater:
                 return self._fused_value(obs)
             return self.critic(obs.float()).squeeze(-1)
 
-    def update(self, obs, acts, logp_old, rtg, var, adv_raw=None, V0=None):
-        """adv_raw / V0: advantages (before normalisation) and values computed by the caller (GAE); default = the reference's
-        A = rtg - V (ppo.py:275-277)."""
-        cfg, ctx = self.cfg, self.ctx
-        world = ctx.world if ctx is not None else 1
-        multi = ctx is not None and ctx.enabled   # collectives run (world > 1, or one rank forced through the backend)
-        with torch.no_grad():
-            if V0 is None:
-                V0 = self.value(obs)
-            adv = normalise_advantages(rtg - V0 if adv_raw is None else adv_raw, ctx)          # ppo.py:275-284
-        n_ep = cfg.n_updates_per_iteration
-        flat_before = self.fp.flat.clone()                     # for the parameter-delta diagnostics of ppo.py:402-403
-        a_loss = c_loss = torch.zeros((), device=obs.device)   # n_updates_per_iteration == 0: nothing to report
-        acc = torch.zeros(6, device=obs.device)                # sums over epochs of diagnostics
-        n_stat = n_ep                                          # rows the per-epoch means are taken over (target_kl: fewer after a stop)
-        fused_gn_sq = None                                     # fused single-GPU path: [n_ep - 1, 2] squared per-net gradient norms
-        net_gn = None                                          # PyTorch path: sums over epochs of the per-net gradient norms
-        multi_gn = None                                        # fused multi-GPU path: sums over epochs of (actor, critic, total) norms of the mean gradient
-        self.loss_history = torch.zeros((n_ep, 2), device=obs.device)  # per-epoch (actor, critic) loss, ppo.py:396-397
-        var_f = float(var) if self.fused else None
-        if not (self.fused and obs.dtype == torch.float16):
-            obs = obs.float()   # half rows (obs_f16 envs) are consumed as they are by the fused kernels only
-        if self.fused:
-            obs, acts, logp_old, rtg, adv = (t.contiguous() for t in (obs, acts, logp_old, rtg, adv))
-            if self.bf16x3 and n_ep > 0:
-                self.prepare(obs)   # ALWAYS here: the rollout kernels fill the buffer behind torch's back (no version bump)
-            if self._fhist.shape[0] < n_ep:
-                self._fhist = torch.zeros((n_ep, 8), dtype=torch.float32, device=self.device)
-        kl_on = self.kl_limit is not None
-        kl_steps, kl_stopped = n_ep, 0   # target_kl on: optimiser steps taken, and whether the update stopped early
-        # target_kl without max_grad_norm runs the clipped machinery at max_norm = +inf (the bits of the unclipped epochs) and reports
-        # the unclipped statistics' keys
-        clipping = self.max_norm is not None or kl_on
-        if kl_on and self.fused:   # zeroed once per update; afterwards only the library writes it
-            self.kl_state = torch.zeros(4, dtype=torch.float32, device=obs.device)
-            kl_t0 = self._adam_t
-            if multi:
-                kl_glob = torch.zeros((max(n_ep, 1), 2), dtype=torch.float32, device=obs.device)
-        if clipping:   # every epoch's (s_actor, s_critic, coef_actor, coef_critic): filled on the device, read once after the loop
-            self.clip_stats = torch.zeros((max(n_ep, 1), 4), dtype=torch.float32, device=obs.device)
-        self._last_adv = adv   # (PPOTrainer._grad_guard's diagnostics)
-        pipelined = self.fused and multi and self.fused_mlp64 and cfg.overlap_allreduce
-        if pipelined:
-            pg = self._pipelined_epochs(n_ep, world, obs, acts, logp_old, rtg, adv, var_f)   # squared norms of the MEAN gradient, per epoch and net
-            if n_ep > 0:
-                multi_gn = torch.cat([pg.sqrt().sum(0), pg.sum(1).sqrt().sum().reshape(1)])
+    def _clip_row(self, ep, c):
+        """This epoch's clip-statistics row from the gradient as it stands, coefficient c: 0 = the update stopped before this step, 1 = unclipped."""
+        g_a, g_c = self.fp.grad[:self._n_actor], self.fp.grad[self._n_actor:]
+        self.clip_stats[ep] = torch.stack([(g_a * g_a).sum(), (g_c * g_c).sum(), g_a.new_full((), c), g_a.new_full((), c)])
+
+    def _fused_record(self, n_ep, V0, world, r0, gn_sum=None, net_gn=None):
+        """What every fused runner ends with: ONE synchronisation (kl_state) after the last epoch, then the record from the first k rows
+        of _fhist.  gn_sum / net_gn: the runner's own sums of norms; the single-GPU epochs have none and take them from the rows."""
+        if n_ep == 0:
+            return r0
+        steps, stopped = n_ep, 0
+        if self.kl_limit is not None:   # (the update synchronises for its statistics anyway)
+            st = self.kl_state.tolist()
+            steps, stopped = int(st[1]), int(st[0] != 0.0)
+            self._adam_t -= n_ep - steps   # Adam's bias correction counts steps TAKEN: every epoch's launch counted one
+        k = steps + stopped
+        h = self._fhist[:k]
+        losses = h[:, 0:5:4].clone()   # columns 0 (actor loss) and 4 (critic loss)
+        if k < n_ep:
+            losses = torch.cat([losses, torch.full((n_ep - k, 2), math.nan, device=h.device)])
+        gn_last = self.fp.grad.norm() / world   # multi-GPU: fp.grad holds the all-reduced SUM (the 1 / world scale is inside navppo_adam_step)
+        own = gn_sum is not None
+        if not own and not self._clipping:
+            # every epoch's norms as the reference logs them (ppo.py:351-352, 389-390) without a norm launch per epoch: the fused epoch leaves
+            # the squared per-net norms of the epoch BEFORE in columns 3 / 7 of its row (reduce_adam / resmlp_reduce), the last epoch's stand
+            if n_ep > 1:
+                prev = h[1:, 3:8:4].clone()   # [n_ep - 1, (actor, critic)]
+                gn_sum, net_gn = prev.sum(1).sqrt().sum() + gn_last, prev.sqrt().sum(0)
+            else:
+                gn_sum = gn_last * n_ep
+        return _Epochs(k=k, steps=steps, stopped=stopped, losses=losses, sums=h.sum(0)[[0, 4, 1, 2]], gn_sum=gn_sum, v_sum=V0.mean() * k,
+                       net_gn=net_gn, net_gn_open=not own)
+
+    def _run_fused_single(self, n_ep, batch, var_f, V0, multi, world, r0):
+        """One GPU: _fused_epoch.  Per-epoch diagnostics land in row ep of a device buffer: no extra launches inside the epoch loop."""
+        for ep in range(n_ep):
+            self._fused_epoch(*batch, var_f, self._fhist[ep], self.clip_stats[ep] if self._clipping else None)
+        return self._fused_record(n_ep, V0, world, r0)
+
+    def _run_fused_multi(self, n_ep, batch, var_f, V0, multi, world, r0):
+        """Several GPUs: fused passes -> ONE all-reduce of the flat gradient (RCCL) -> scale + Adam in one launch."""
+        ctx, n_a, n, gn = self.ctx, self._n_actor, float(batch[0].shape[0]), None   # gn: epoch sums of the MEAN gradient's (actor, critic, whole) norm
+        kl_glob = torch.zeros((max(n_ep, 1), 2), dtype=torch.float32, device=self.device) if self.kl_limit is not None else None
+        for ep in range(n_ep):
+            self._fused_loss_grad(*batch, var_f, stats=self._fhist[ep])
+            ctx.all_reduce_sum(self.fp.grad)
+            if self.kl_limit is not None:
+                # the global approx_kl = sum(kl_r n_r) / sum(n_r), a 2-float collective; the passes are ungated: a stop only keeps the weights
+                kg = kl_glob[ep]
+                kg[0], kg[1] = self._fhist[ep, 1] * n, n
+                ctx.all_reduce_sum(kg)
+                kg[0] /= kg[1]
+                self._fused_adam(1.0 / world, cstats=self.clip_stats[ep], kl_dev=kg)
+            elif self._clipping:   # (the norms of the mean gradient are in the clip statistics)
+                self._fused_adam(1.0 / world, cstats=self.clip_stats[ep])
+            else:   # every epoch's norms of the MEAN gradient (two small launches beside an all-reduce)
+                g3 = torch.stack(torch._foreach_norm([self.fp.grad[:n_a], self.fp.grad[n_a:], self.fp.grad])) / world
+                gn = g3 if gn is None else gn + g3
+                self._fused_adam(1.0 / world)
+        return self._fused_record(n_ep, V0, world, r0, *((gn[2], gn[:2]) if gn is not None else ()))
+
+    def _run_fused_pipelined(self, n_ep, batch, var_f, V0, multi, world, r0):
+        """Several GPUs, overlap_allreduce: every epoch runs in _pipelined_epochs; pg: its squared norms of the MEAN gradient."""
+        pg = self._pipelined_epochs(n_ep, world, *batch, var_f)
+        gn = torch.cat([pg.sqrt().sum(0), pg.sum(1).sqrt().sum().reshape(1)]) if n_ep > 0 else None
+        return self._fused_record(n_ep, V0, world, r0, *((gn[2], gn[:2]) if gn is not None else ()))
+
+    def _run_pytorch(self, n_ep, batch, var, V0, multi, world, r0):
+        """CPU, gloo, and resmlp512 with update_arith="f32": ppo.py:305-392 in PyTorch."""
+        obs, acts, logp_old, rtg, adv = batch
+        steps, stopped, losses = n_ep, 0, r0.losses
+        acc, net_gn = torch.zeros(6, device=obs.device), None  # sums over epochs of the diagnostics and of the per-net gradient norms
         for ep in range(n_ep):                                 # ppo.py:305
-            if self.fused:
-                # per-epoch diagnostics land in row ep of a device buffer: no extra launches inside the epoch loop
-                if pipelined:
-                    pass   # all epochs ran above; only the diagnostics of the last one are gathered below
-                elif multi:   # fused passes -> ONE all-reduce of the flat gradient (RCCL) -> scale + Adam in one launch
-                    self._fused_loss_grad(obs, acts, logp_old, rtg, adv, var_f, stats=self._fhist[ep])
-                    ctx.all_reduce_sum(self.fp.grad)
-                    if kl_on:   # the global approx_kl = sum(kl_r n_r) / sum(n_r) in a 2-float collective of its own; the ungated passes
-                        # above run in every epoch, so a stop saves no time on this path -- it only keeps the weights where they were
-                        kg = kl_glob[ep]
-                        kg[0], kg[1] = self._fhist[ep, 1] * float(obs.shape[0]), float(obs.shape[0])
-                        ctx.all_reduce_sum(kg)
-                        kg[0] /= kg[1]
-                        self._fused_adam(1.0 / world, cstats=self.clip_stats[ep], kl_dev=kg)
-                    elif clipping:   # (the norms of the mean gradient are in the clip statistics)
-                        self._fused_adam(1.0 / world, cstats=self.clip_stats[ep])
-                    else:
-                        with torch.no_grad():   # every epoch's norms of the MEAN gradient (two small launches beside an all-reduce)
-                            n_a_ = self.fp.module_numel[0]
-                            g3 = torch.stack(torch._foreach_norm([self.fp.grad[:n_a_], self.fp.grad[n_a_:], self.fp.grad])) / world
-                            multi_gn = g3 if multi_gn is None else multi_gn + g3
-                        self._fused_adam(1.0 / world)
-                else:
-                    self._fused_epoch(obs, acts, logp_old, rtg, adv, var_f, self._fhist[ep], self.clip_stats[ep] if clipping else None)
-                if ep == n_ep - 1:
-                    k = n_ep   # epochs whose passes ran = steps taken + (1 if stopped): the rows the statistics are taken over
-                    if kl_on:   # (the update synchronises for its statistics below anyway)
-                        st = self.kl_state.tolist()
-                        kl_stopped, kl_steps = int(st[0] != 0.0), int(st[1])
-                        k = kl_steps + kl_stopped
-                        self._adam_t = kl_t0 + kl_steps   # Adam's bias correction counts steps TAKEN
-                    h = self._fhist[:k]
-                    self.loss_history = h[:, 0:5:4].clone()   # columns 0 (actor loss) and 4 (critic loss)
-                    if k < n_ep:
-                        self.loss_history = torch.cat([self.loss_history, torch.full((n_ep - k, 2), math.nan, device=obs.device)])
-                    hs = h.sum(0)
-                    # multi-GPU: fp.grad holds the all-reduced SUM (the 1 / world scale is inside navppo_adam_step)
-                    gn_last = self.fp.grad.norm() / world
-                    if clipping:   # the pre-clip norms of every epoch, from the clip statistics (no previous-epoch slots involved)
-                        gn_sum = self.clip_stats[:k, :2].sum(1).sqrt().sum()
-                    elif not multi and n_ep > 1:
-                        # grad norms as the reference logs them -- every epoch's, averaged (ppo.py:351-352, 389-390) -- without a norm
-                        # launch per epoch: the fused epoch leaves the squared per-net norms of the epoch BEFORE in columns 3 / 7 of
-                        # its statistics row (reduce_adam / resmlp_reduce), the last epoch's come from the gradient buffer
-                        fused_gn_sq = h[1:, 3:8:4].clone()                         # [n_ep - 1, (actor, critic)]
-                        gn_sum = fused_gn_sq.sum(1).sqrt().sum() + gn_last
-                    elif multi_gn is not None:
-                        gn_sum = multi_gn[2]
-                    else:   # (the pipelined multi-GPU epochs, one epoch: the last epoch's norm stands in)
-                        gn_sum = gn_last * n_ep
-                    acc = torch.cat([hs[[0, 4, 1, 2]], torch.stack([gn_sum, V0.mean() * k])])
-                    a_loss, c_loss = self.loss_history[k - 1, 0], self.loss_history[k - 1, 1]
-                    n_stat = k
-                continue
-            a_loss, c_loss, ratios, logp, _ = ppo_losses(self.actor, self.critic, obs, acts, logp_old, rtg, adv, var, cfg.clip)
+            a_loss, c_loss, ratios, logp, _ = ppo_losses(self.actor, self.critic, obs, acts, logp_old, rtg, adv, var, self.cfg.clip)
             self.fp.grad.zero_()
             (a_loss + c_loss).backward()                       # disjoint nets: same grads as the two backward()s of :349,:386
             if multi:
-                ctx.all_reduce_sum(self.fp.grad)
+                self.ctx.all_reduce_sum(self.fp.grad)
                 self.fp.grad.div_(world)
-            trip = False
-            if kl_on:   # the check before the step, on the global approx_kl (weighted by the ranks' batch sizes); a NaN trips
-                with torch.no_grad():
-                    lr_ = logp.detach() - logp_old
-                    kg = torch.stack([((ratios.detach() - 1) - lr_).sum(), lr_.new_tensor(float(lr_.numel()))])
-                    if multi:
-                        ctx.all_reduce_sum(kg)
-                    trip = not (float(kg[0] / kg[1]) <= self.kl_limit)
-            if trip:   # neither net is stepped; the gradient stays unclipped, the coefficients are reported as 0
-                kl_steps, kl_stopped = ep, 1
-                with torch.no_grad():
-                    n_a_ = self.fp.module_numel[0]
-                    g_a, g_c = self.fp.grad[:n_a_], self.fp.grad[n_a_:]
-                    self.clip_stats[ep] = torch.stack([(g_a * g_a).sum(), (g_c * g_c).sum(), g_a.new_zeros(()), g_a.new_zeros(())])
+            ratios, lr_, trip = ratios.detach(), logp.detach() - logp_old, False
+            if self.kl_limit is not None:   # the check before the step, on the global approx_kl (weighted by the ranks' batch sizes); a NaN trips
+                kg = torch.stack([((ratios - 1) - lr_).sum(), lr_.new_tensor(float(lr_.numel()))])
+                if multi:
+                    self.ctx.all_reduce_sum(kg)
+                trip = not (float(kg[0] / kg[1]) <= self.kl_limit)
+            if trip:   # neither net is stepped; the gradient stays unclipped, the coefficients are reported as 0, the remaining epochs do not run
+                steps, stopped = ep, 1
+                self._clip_row(ep, 0.0)
+                losses[ep + 1:] = math.nan
             elif self.max_norm is not None:
                 self._clip_and_step(ep)
             else:
                 self.opt.step()                                # ppo.py:381,392
-                if clipping:   # (target_kl without max_grad_norm: the norms of every epoch, coefficient 1)
-                    with torch.no_grad():
-                        n_a_ = self.fp.module_numel[0]
-                        g_a, g_c = self.fp.grad[:n_a_], self.fp.grad[n_a_:]
-                        self.clip_stats[ep] = torch.stack([(g_a * g_a).sum(), (g_c * g_c).sum(), g_a.new_ones(()), g_a.new_ones(())])
+                if self._clipping:   # (target_kl without max_grad_norm: the norms of every epoch, coefficient 1)
+                    self._clip_row(ep, 1.0)
             with torch.no_grad():                              # ppo.py:323-336
-                lr_ = logp.detach() - logp_old
-                self.loss_history[ep] = torch.stack([a_loss.detach(), c_loss.detach()])
-                acc += torch.stack([a_loss.detach(), c_loss.detach(), ((ratios.detach() - 1) - lr_).mean(),
-                                    ((ratios.detach() - 1).abs() > cfg.clip).float().mean(),
-                                    self.fp.grad.norm(), V0.mean()])
-                n_a_ = self.fp.module_numel[0]
-                g2 = torch.stack(torch._foreach_norm([self.fp.grad[:n_a_], self.fp.grad[n_a_:]]))
+                losses[ep] = torch.stack([a_loss.detach(), c_loss.detach()])
+                acc += torch.stack([a_loss.detach(), c_loss.detach(), ((ratios - 1) - lr_).mean(),
+                                    ((ratios - 1).abs() > self.cfg.clip).float().mean(), self.fp.grad.norm(), V0.mean()])
+                g2 = torch.stack(torch._foreach_norm([self.fp.grad[:self._n_actor], self.fp.grad[self._n_actor:]]))
                 net_gn = g2 if net_gn is None else net_gn + g2
-            if trip:   # the remaining epochs do not run: their loss_history rows are NaN
-                self.loss_history[ep + 1:] = math.nan
-                n_stat = ep + 1
+            if trip:
                 break
-        acc = acc / max(n_stat, 1)
+        return _Epochs(k=steps + stopped, steps=steps, stopped=stopped, losses=losses, sums=acc[:4], gn_sum=acc[4], v_sum=acc[5], net_gn=net_gn)
+
+    def _summarise(self, r, flat_before, multi, world):
+        """The record of the epochs that ran -> the stats dict.  Gradient norms are means over the r.k epochs, from the first source
+        that has them: the clip statistics (every epoch's pre-clip norms), the runner's own sums, the gradient as it stands."""
+        k, n_a, clipping = r.k, self._n_actor, self._clipping
+        cs = self.clip_stats[:k] if clipping else None
+        # every epoch's pre-clip norm of the whole gradient: folded in before the ranks' mean when fused, after it in PyTorch (not the same last bit)
+        total = cs[:, :2].sum(1).sqrt() if clipping and k > 0 else None
+        acc = torch.cat([r.sums, torch.stack([total.sum() if total is not None and self.fused else r.gn_sum, r.v_sum])]) / max(k, 1)
         if multi:
-            ctx.all_reduce_sum(acc)
+            self.ctx.all_reduce_sum(acc)
             acc = acc / world
-        n_a = self.fp.module_numel[0]
-        d = self.fp.flat - flat_before
+        if total is not None and not self.fused:
+            acc = torch.cat([acc[:4], total.mean().reshape(1), acc[5:]])
+        d = self.fp.flat - flat_before                         # the parameter-delta diagnostics of ppo.py:402-403
         extra = torch.stack(torch._foreach_norm([self.fp.grad[:n_a], self.fp.grad[n_a:], d[:n_a], d[n_a:]]))
         if self.fused and multi:
             extra = extra * extra.new_tensor([1.0 / world, 1.0 / world, 1.0, 1.0])   # norms of the MEAN gradient, as on one GPU
+        if total is not None:
+            extra = torch.cat([cs[:, :2].sqrt().mean(0), extra[2:]])
+        elif r.net_gn is not None:   # (open: the runner's sums lack the last epoch, whose gradient still stands)
+            extra = torch.cat([(r.net_gn + extra[:2] if r.net_gn_open else r.net_gn) / k, extra[2:]])
         clip_cols = []
-        if clipping:   # pre-clip norms of every epoch (their mean), share of clipped epochs, skipped steps; identical on every rank
-            cs = self.clip_stats[:n_stat]
-            gn = cs[:, :2].sqrt()
-            if n_stat > 0:
-                extra = torch.cat([gn.mean(0), extra[2:]])
-                if not self.fused:
-                    acc = torch.cat([acc[:4], cs[:, :2].sum(1).sqrt().mean().reshape(1), acc[5:]])
-            clipped_ep = cs[:, 2:] < 1.0
-            if kl_stopped:   # the tripping epoch: coefficient 0 because the update stopped, not because anything was clipped or skipped
-                clipped_ep = clipped_ep[:-1]
-            clip_cols = [clipped_ep.float().sum(0) / max(n_stat, 1), (~torch.isfinite(cs[:, :2])).float().sum(0)]
-            if n_stat == 0:
-                clip_cols = [torch.zeros(2, device=obs.device)] * 2
-            if self.max_norm is None:   # target_kl alone: the keys of the unclipped statistics
-                clip_cols = []
-        elif fused_gn_sq is not None:   # per-net norms: the mean over the epochs, like grad_norm (the reference's actor_grad_norm / critic_grad_norm)
-            extra = torch.cat([(fused_gn_sq.sqrt().sum(0) + extra[:2]) / n_ep, extra[2:]])
-        elif multi_gn is not None:
-            extra = torch.cat([multi_gn[:2] / n_ep, extra[2:]])
-        elif net_gn is not None:
-            extra = torch.cat([net_gn / max(n_stat, 1), extra[2:]])
-        self.stats = dict(zip(["actor_loss", "critic_loss", "approx_kl", "clip_frac", "grad_norm", "value_mean",
-                               "actor_grad_norm", "critic_grad_norm", "actor_param_delta", "critic_param_delta",
-                               "grad_clip_frac_actor", "grad_clip_frac_critic", "skipped_steps_actor", "skipped_steps_critic"],
-                              [float(v) for v in torch.cat([acc, extra] + clip_cols).tolist()]))   # grad norms: means over the epochs (multi-GPU fused path: the last epoch's)
-        # (the last four keys exist with clipping on only: without max_grad_norm the statistics -- and with them the trainer's log
-        # dictionary and everything that enumerates it -- are exactly what they were; nothing is ever clipped or skipped there)
-        for k in ("skipped_steps_actor", "skipped_steps_critic"):
-            if k in self.stats:
-                self.stats[k] = int(self.stats[k])
-        if kl_on:   # steps taken (n_ep if the update never stopped) and whether it stopped; identical on every rank
-            self.stats["kl_stop_epoch"], self.stats["kl_stopped"] = int(kl_steps), int(kl_stopped)
-        self.last_losses = (a_loss.detach(), c_loss.detach())
+        if clipping:   # share of clipped epochs, skipped steps; identical on every rank
+            # (not the tripping epoch: its coefficient is 0 because the update stopped, not because anything was clipped or skipped)
+            clipped_ep = (cs[:, 2:] < 1.0)[:k - r.stopped]
+            clip_cols = [clipped_ep.float().sum(0) / max(k, 1), (~torch.isfinite(cs[:, :2])).float().sum(0)]
+            if k == 0:
+                clip_cols = [torch.zeros(2, device=self.device)] * 2
+        # (the last four keys exist with max_grad_norm only -- not with target_kl alone: without it the trainer's log dictionary is what it was)
+        keys = ["actor_loss", "critic_loss", "approx_kl", "clip_frac", "grad_norm", "value_mean", "actor_grad_norm", "critic_grad_norm",
+                "actor_param_delta", "critic_param_delta",
+                "grad_clip_frac_actor", "grad_clip_frac_critic", "skipped_steps_actor", "skipped_steps_critic"]
+        vals = [float(v) for v in torch.cat([acc, extra] + (clip_cols if self.max_norm is not None else [])).tolist()]
+        stats = dict(zip(keys, vals[:12] + [int(v) for v in vals[12:]]))
+        if self.kl_limit is not None:   # steps taken (n_ep if the update never stopped) and whether it stopped; identical on every rank
+            stats["kl_stop_epoch"], stats["kl_stopped"] = r.steps, r.stopped
+        return stats
+
+    def update(self, obs, acts, logp_old, rtg, var, adv_raw=None, V0=None):
+        """adv_raw / V0: advantages (before normalisation) and values computed by the caller (GAE); default = the reference's
+        A = rtg - V (ppo.py:275-277).  Prologue, the epochs on the one path that applies, the summary, the published results."""
+        cfg, ctx, n_ep = self.cfg, self.ctx, self.cfg.n_updates_per_iteration
+        world, multi = (ctx.world, ctx.enabled) if ctx is not None else (1, False)   # multi: collectives run (also one forced rank)
+        with torch.no_grad():
+            V0 = self.value(obs) if V0 is None else V0
+            adv = normalise_advantages(rtg - V0 if adv_raw is None else adv_raw, ctx)          # ppo.py:275-284
+        flat_before = self.fp.flat.clone()
+        zero = torch.zeros((), device=obs.device)   # n_updates_per_iteration == 0: nothing to report
+        r0 = _Epochs(k=0, steps=0, stopped=0, losses=torch.zeros((n_ep, 2), device=obs.device), sums=torch.zeros(4, device=obs.device),
+                     gn_sum=zero, v_sum=zero)
+        if not (self.fused and obs.dtype == torch.float16):
+            obs = obs.float()   # half rows (obs_f16 envs) are consumed as they are by the fused kernels only
+        batch = (obs, acts, logp_old, rtg, adv)
+        if self.fused:
+            batch = tuple(t.contiguous() for t in batch)
+            if self.bf16x3 and n_ep > 0:
+                self.prepare(batch[0])   # ALWAYS here: the rollout kernels fill the buffer behind torch's back (no version bump)
+            if self._fhist.shape[0] < n_ep:
+                self._fhist = torch.zeros((n_ep, 8), dtype=torch.float32, device=self.device)
+            if self.kl_limit is not None:   # zeroed once per update; afterwards only the library writes it
+                self.kl_state = torch.zeros(4, dtype=torch.float32, device=obs.device)
+        if self._clipping:   # every epoch's (s_actor, s_critic, coef_actor, coef_critic): filled on the device, read once after the epochs
+            self.clip_stats = torch.zeros((max(n_ep, 1), 4), dtype=torch.float32, device=obs.device)
+        self._last_adv = batch[4]   # (PPOTrainer._grad_guard's diagnostics)
+        runner = (self._run_pytorch if not self.fused else self._run_fused_single if not multi else
+                  self._run_fused_pipelined if self.fused_mlp64 and cfg.overlap_allreduce else self._run_fused_multi)
+        run = runner(n_ep, batch, float(var) if self.fused else var, V0, multi, world, r0)
+        self.stats = self._summarise(run, flat_before, multi, world)
+        self.loss_history = run.losses   # per-epoch (actor, critic) loss, ppo.py:396-397; NaN rows behind an early stop
+        self.last_losses = (run.losses[run.k - 1, 0].detach(), run.losses[run.k - 1, 1].detach()) if run.k else (zero, zero)
         return self.stats
 
 
