@@ -123,6 +123,32 @@ int navsim_get_info(navsim_t* h, navsim_info* out);
 int navsim_set_map(navsim_t* h, const float* seg_dev, int32_t n_segments, int32_t per_env, void* stream);
 
 /*
+ * Moving obstacles -- an EXTENSION (the reference's worlds are static; its stated subject, mapless navigation in dynamic
+ * environments, is not): a periodic TAPE of segments cast beside the static map by every step kernel.
+ *   tape_dev   [period][n_segments][4] f32 (ax,ay,bx,by) as in navsim_set_map, 16-byte aligned, BORROWED like a per-env map (it must
+ *              stay alive and unchanged while the handle uses it); 1 <= n_segments <= 64, 1 <= period <= 65536.  The kernels do no
+ *              trajectory arithmetic: the host writes whatever motion it likes into the tape.  A segment with a NaN coordinate is
+ *              never hit: the way to pad a phase that has fewer live segments.  NULL turns movers off: the handle then launches
+ *              exactly what it launched before the first call.
+ *   phase0_dev [N] i32, nullable (= all zero): per-env phase offset in [0, period).  Copied; validated on the host at this call.
+ * Phase rule, k = env i's episode step counter before the step:
+ *   a step's scan sees tape[(k + 1 + phase0[i]) mod period]; every reset observation (navsim_reset, the in-step auto-reset, the
+ *   resets inside the persistent kernels) sees tape[phase0[i]] -- the batched form of Gazebo's reset_simulation, which puts every
+ *   model back at its start.  navsim_raycast sees tape[(k + phase0[i]) mod period], the phase the env last observed.
+ * Everything behind the scan -- collision rule, observation row, reward, episode logic -- is unchanged: a mover that reaches the robot
+ * ends the episode as a wall does.  The scan equals, bit for bit, that of a static map holding the static segments and the phase's.
+ * With a tape every stepping entry point (navsim_step, navsim_step_seq, both rollouts, both evaluations) runs 16 envs on 8 waves per
+ * workgroup at every shard size (navsim_set_shape has no effect; navsim_get_info reports it).
+ * Like the map, the tape is part of the kernel arguments: set it BEFORE a step is captured into a graph.
+ * Re-casts the spawn scans on `stream` (with phase0 they become per-env); a later navsim_set_map keeps the tape and does the same.
+ * Synchronises `stream`.
+ * NAVSIM_E_STATE before navsim_set_map.  NAVSIM_E_ARG: sizes or a phase0 value out of range, a misaligned tape, and: movers need 10
+ * beams and a shared static map: movers with 36 beams or with a per-env static map are not built.
+ */
+int navsim_set_movers(navsim_t* h, const float* tape_dev, int32_t period, int32_t n_segments, const int32_t* phase0_dev,
+                      void* stream);
+
+/*
  * Goal-rejection rectangles (xmin,xmax,ymin,ymax; inclusive), host pointer, copied.
  * which=0: used by reset (environment_new.py:340-343); which=1: used by the arrival
  * re-spawn (environment_new.py:248-251).  Defaults are the reference's stage_1 values.

@@ -109,8 +109,22 @@ struct Params {
     int K, G;
     double min_dist, max_dist;
     const Rects* rects;
+    // ---- moving obstacles (navsim_set_movers), appended: nothing above moves.  Read by the MOV instantiations, the reset /
+    // ray-cast kernels and (spawn_per_env) the MOV spec lanes only.
+    const float4* mov_tape;      // [mov_P][mov_M] segments, borrowed; null = no movers
+    const int32_t* mov_phase0;   // [N] per-env phase offset in [0, mov_P), the handle's copy; null = all zero
+    int mov_P, mov_M;
+    int mov_pack_log2;           // mover pass: log2(lanes per env) = log2(pow2ceil(mov_M)), as seg_pack_log2 for the static map
+    int spawn_per_env;           // spawn_scan / spawn_obs are [N][K][B]: per_env != 0, or movers with a per-env phase offset
 };
 static_assert(offsetof(Params, max_ep_steps) == 128, "the hot head of Params");
+
+// The tape phase env i casts: `k` = steps taken in the episode (a step's scan: k = the counter before the step, + 1; a reset
+// observation and navsim_raycast before the first step: k = 0).  k < 2^30 + 1, phase0 < P <= 65536: no overflow.
+template <class PRef>
+__device__ __forceinline__ uint32_t mover_phase(PRef P, const uint32_t k, const uint32_t phase0) {
+    return (k + phase0) % (uint32_t)P.mov_P;
+}
 
 // ---------------------------------------------------------------- device helpers
 
@@ -350,6 +364,13 @@ struct StepSmem {
     float2 st_pact[EPB];
     uint32_t st_step[EPB], st_ctr[EPB];
 };
+// What the MOV instantiations (moving obstacles, Params::mov_tape) keep in LDS on top of it: a kernel with movers declares this
+// one, step_body takes the base and reaches the rest through a cast that only its MOV branches contain.
+template <int NB, int EPB, int NW = 4>
+struct StepSmemMov : StepSmem<NB, EPB, NW> {
+    uint32_t mv_phase[EPB];      // the tape phase each env's scan sees this step, published by the pose lanes before barrier A
+    uint32_t mv_phase0[EPB];     // persistent kernels: Params::mov_phase0 of the workgroup's envs, staged once per launch
+};
 
 // Correctly rounded K / Dn for positive, normal-range operands (Dn in [2^-60, 2^20], K in {0} U [2^-60, 2^20]):
 // the reciprocal-refinement sequence the compiler emits for an IEEE float32 divide (v_rcp, 2 fma to refine,
@@ -449,6 +470,9 @@ __device__ __forceinline__ float write_lidar(float* row, const float* best, int 
 // NW: waves per workgroup (4; the persistent rollout kernel, one workgroup per CU, runs 8 for a shorter cast).
 // BOXES: shared map with tile bounding boxes (Params::tile_box): whole 64-segment tiles that lie behind the beam fan or out of
 // range are skipped without being loaded (the house map: 32 tiles, ~5 of them near any one pose).
+// MOV: moving obstacles (Params::mov_tape, navsim_set_movers): the pose lanes publish each env's tape phase before barrier A and
+// the ray waves cast that phase's segments (lane = segment) through the same stage-A queue, behind their static tiles.  `sm` is then
+// the base of a StepSmemMov.  Off, nothing of it is compiled: every instantiation without it is what it was.
 // row0: element offset of this step's row in the [T, N] output buffers `io` points at (navsim_step_seq: t N; the pointers are
 // then read from the kernarg segment at their use instead of living in SGPRs through the body; 0 elsewhere).
 // PRef / IORef: how the parameter block and the I/O pointers are reached.  The persistent rollout passes plain references to its
@@ -483,11 +507,12 @@ struct NoHook {
     __device__ __forceinline__ void operator()(int, int) const {}
 };
 template <int NB, int EPB, bool SENS, bool PERSIST, int NW = 4, bool BOXES = false, int PAIR = 0, class PRef = const Params&,
-          class IORef = const StepIO&, class Hook = NoHook>
+          class IORef = const StepIO&, class Hook = NoHook, bool MOV = false>
 __device__ __forceinline__ void step_body(PRef P, StepSmem<NB, EPB, NW>& sm, int& next_env, IORef io, const bool last_step = true,
                                           const size_t row0 = 0, Hook hook = Hook()) {
     static_assert(EPB <= 64 && EPB >= 4 && NB % 2 == 0, "EPB / NB");
     static_assert(!(PAIR && BOXES), "tile boxes describe 64-segment tiles");
+    static_assert(!MOV || (NB == 10 && EPB == 16 && NW == 8 && PAIR == 0), "movers: the 16-env, 8-wave shape with 10 beams");
     constexpr int kThreads = 64 * NW;
     constexpr bool kEval = std::is_same<typename std::remove_cv<typename std::remove_reference<IORef>::type>::type, EvalIO>::value;
     static_assert(!kEval || PERSIST, "the episode table is the persistent evaluation kernels' output");
@@ -517,6 +542,7 @@ __device__ __forceinline__ void step_body(PRef P, StepSmem<NB, EPB, NW>& sm, int
     double x = 0, y = 0, th = 0, gx = 0, gy = 0, pdist = 0, dist = 0, yaw = 0, rel_theta = 0, diff = 0, ret0 = 0, path0 = 0;
     float2 act = make_float2(0.f, 0.f), pact = make_float2(0.f, 0.f);
     uint32_t ctr = 0, stepw = 0;
+    [[maybe_unused]] uint32_t mv_ph0 = 0;   // MOV: the env's phase offset (Params::mov_phase0)
     const int el_pose = (64 / LPE) * wave + (lane / LPE);  // env (local) this pose lane works for
     const int rr = lane % LPE;
     const bool pose_lane = (wave < PWP) && (el_pose < EPB);
@@ -617,6 +643,9 @@ __device__ __forceinline__ void step_body(PRef P, StepSmem<NB, EPB, NW>& sm, int
             act = io.action[i];
             ctr = P.rng_ctr[i];
             stepw = (uint32_t)P.ep_step[i];
+            if constexpr (MOV) {
+                if (rr == 0 && P.mov_phase0) mv_ph0 = (uint32_t)P.mov_phase0[i];
+            }
             if (rr == 0) {
                 x = P.x[i]; y = P.y[i];
                 gx = P.gx[i]; gy = P.gy[i]; pdist = P.past_dist[i];
@@ -687,6 +716,7 @@ __device__ __forceinline__ void step_body(PRef P, StepSmem<NB, EPB, NW>& sm, int
                 act = sm.act_l[e];
                 ctr = sm.st_ctr[e];
                 stepw = sm.st_step[e];
+                if constexpr (MOV) mv_ph0 = static_cast<StepSmemMov<NB, EPB, NW>&>(sm).mv_phase0[e];
                 if (rr == 0) {
                     x = sm.st_d[0][e]; y = sm.st_d[1][e];
                     gx = sm.st_d[3][e]; gy = sm.st_d[4][e]; pdist = sm.st_d[5][e];
@@ -709,6 +739,12 @@ __device__ __forceinline__ void step_body(PRef P, StepSmem<NB, EPB, NW>& sm, int
             // the heading after the step is th0 + kSubsteps additions of delta_theta (same roundings as the serial loop, :160)
             for (int k = 0; k < kSubsteps; ++k) th += delta_theta;
             arg = (rr == 0) ? th : (delta_theta / 2.0);
+            // MOV: the phase this step's scan sees, tape[(k + 1 + phase0) mod P] with k the step counter before the step -- integer
+            // work that issues under the latency of the float64 chain above
+            if constexpr (MOV) {
+                if (rr == 0)
+                    static_cast<StepSmemMov<NB, EPB, NW>&>(sm).mv_phase[el_pose] = mover_phase<PRef>(P, (stepw & kStepMask) + 1u, mv_ph0);
+            }
         }
         // spec lanes that share wave 0 with the pose lanes (small shapes): behind the wheel arithmetic -- the wait for the state
         // loads is over, the sincos covers this round trip
@@ -868,7 +904,7 @@ __device__ __forceinline__ void step_body(PRef P, StepSmem<NB, EPB, NW>& sm, int
             float2 row[NB / 2];
             auto request_row = [&](const int k) __attribute__((always_inline)) {
                 const float2* sp = reinterpret_cast<const float2*>((SENS ? P.spawn_scan : P.spawn_obs) +
-                                                                   ((P.per_env ? (size_t)ie * P.K : 0) + k) * B);
+                                                                   (((MOV ? P.spawn_per_env : P.per_env) ? (size_t)ie * P.K : 0) + k) * B);
 #pragma unroll
                 for (int b = 0; b < NB / 2; ++b) row[b] = sp[b];
             };
@@ -1180,6 +1216,29 @@ __device__ __forceinline__ void step_body(PRef P, StepSmem<NB, EPB, NW>& sm, int
         } else if (BOXES) {   // ray waves: the live tiles of the item their last pre-assigned tile belongs to
             cur_live = (p2.it < n_items) ? item_live(p2.it) : 0ull;
         }
+        // MOV: the tape segments of this step, lane = segment (several envs per pass when the tape has <= 32 segments per phase, as
+        // for a small static map).  Pass m covers envs m mepp .. m mepp + mepp - 1 and belongs to ray wave m % RW: static, so that
+        // every request leaves here -- right behind barrier A, where the phases became visible -- and lands under the static
+        // tiles.  The requests are unconditional and EVERY wave issues them (a front wave's, and a pass past the last env, re-read a
+        // clamped valid address and are never consumed): the count of requests behind the three static slots is then the same on
+        // every path into the loop below, which is what lets its waits name the oldest slot only.
+        constexpr int kMovRW = NW - PW, kMovPasses = MOV ? (EPB + kMovRW - 1) / kMovRW : 1;
+        [[maybe_unused]] float4 mg[kMovPasses];
+        [[maybe_unused]] int m_el[kMovPasses];
+        [[maybe_unused]] bool m_v[kMovPasses];
+        if constexpr (MOV) {
+            const StepSmemMov<NB, EPB, NW>& ms = static_cast<const StepSmemMov<NB, EPB, NW>&>(sm);
+            const int mspl = P.mov_pack_log2, M = P.mov_M;
+            const int mepp = 64 >> mspl, msub = lane >> mspl, mj = lane & ((1 << mspl) - 1);
+            const float4* const tape = P.mov_tape;
+#pragma unroll
+            for (int q = 0; q < kMovPasses; ++q) {
+                const int el = ((wave - PW) + kMovRW * q) * mepp + msub;
+                m_v[q] = (wave >= PW) && (el < nloc) && (mj < M);
+                m_el[q] = min(max(el, 0), nloc - 1);
+                mg[q] = tape[(size_t)ms.mv_phase[m_el[q]] * (size_t)M + (size_t)min(mj, M - 1)];
+            }
+        }
         // three tiles in flight; the slots take turns (a register rotation would have to wait for the load it moves)
         for (;;) {   // wave-uniform
             if (p0.it >= n_items) break;
@@ -1194,6 +1253,19 @@ __device__ __forceinline__ void step_body(PRef P, StepSmem<NB, EPB, NW>& sm, int
             consume(p2, g2, v2, g2b, v2b);
             p2 = advance(p1);
             request(p2, g2, v2, g2b, v2b);
+        }
+        // MOV: the mover passes join the stage-A queue like any tile: the same cull (plus: a segment with a NaN coordinate -- the
+        // documented padding of a phase -- is dropped here instead of failing every exact test), the same queues, the same exact
+        // tests and atomic-min -- so the scan is that of a static map holding the static segments and this phase's tape segments
+        if constexpr (MOV) {
+#pragma unroll
+            for (int q = 0; q < kMovPasses; ++q) {
+                if (!__any(m_v[q])) continue;   // wave-uniform: a front wave, a pass past the last env
+                const float4 g = mg[q];
+                const float2 o = sm.org[m_el[q]], h = sm.hd[m_el[q]];
+                const float sum = (g.x + g.y) + (g.z + g.w);
+                push(g, (unsigned)m_el[q], keep_of(g, o, h) & m_v[q] & (sum == sum));
+            }
         }
         // The tail.  10 beams: stage A2 only filters, so when everything that is left fits one stage-B pass it is skipped: the
         // stage-A survivors join the stage-B queue directly (one pass of 206 VALU instead of 75 + 206; a small map never needs A2).
@@ -1426,6 +1498,34 @@ __global__ __launch_bounds__(64 * NW, min_waves_per_simd(NB, EPB, NW, PAIR, fals
               const StepIO __attribute__((address_space(4)))&>(A->P, sm, next_env, A->io);
 }
 
+// The shared-memory block of a kernel: with movers the extended one (StepSmemMov)
+template <int NB, int EPB, int NW, bool MOV>
+using StepSmemFor = typename std::conditional<MOV, StepSmemMov<NB, EPB, NW>, StepSmem<NB, EPB, NW>>::type;
+
+// Movers (navsim_set_movers): every entry point takes the 16-env, 8-wave shape with 10 beams.  The MOV kernels are twins of their
+// own name (`*_mov_kernel`), so that the kernels a handle without a tape launches keep their symbols and their code.
+// No second launch bound (min_waves_per_simd): the mover passes hold three more tiles in registers.
+// They are the SENS instantiations for every handle -- with the range noise off and below_min at its default those compute the
+// same bits (sensor_value with sigma = 0, mode 0) -- which halves what movers add to the build time of this file.
+constexpr bool kMovSens = true;
+template <bool BOXES>
+__global__ __launch_bounds__(64 * 8) void step_mov_kernel(StepKArgs) {
+    constexpr bool SENS = kMovSens;
+    __shared__ StepSmemMov<10, 16, 8> sm;
+    __shared__ int next_env;
+    StepKArgsPtr A = (StepKArgsPtr)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(A));
+    step_body<10, 16, SENS, false, 8, BOXES, 0, const Params __attribute__((address_space(4)))&,
+              const StepIO __attribute__((address_space(4)))&, NoHook, true>(A->P, sm, next_env, A->io);
+}
+
+// persistent kernels with movers: the phase offsets of the workgroup's envs -> LDS, once per launch
+template <int NB, int EPB, int NW, class PRef>
+__device__ __forceinline__ void load_mover_phase0(PRef P, StepSmemMov<NB, EPB, NW>& sm, const int base, const int nloc) {
+    const int32_t* const ph0 = P.mov_phase0;
+    if ((int)threadIdx.x < nloc) sm.mv_phase0[threadIdx.x] = ph0 ? (uint32_t)ph0[base + threadIdx.x] : 0u;
+}
+
 // ---------------------------------------------------------------- the persistent rollout kernel (PPO.rollout, ppo.py:463-641)
 // All T steps of the rollout in ONE launch for the 16-64-64 policy: a workgroup owns its EPB envs for the whole rollout and
 // alternates   policy phase (wave 0: PPO.get_action of mlp64_policy.h on the observation tile in LDS -> action, log-prob)
@@ -1570,17 +1670,15 @@ __host__ __device__ __forceinline__ StepIO rollout_io(const RolloutArgs& R, cons
                   R.ep_path ? R.ep_path + tn : nullptr};
 }
 
-template <int NB, int EPB, bool SENS, int NW, bool BOXES = false>
-__global__ __launch_bounds__(64 * NW) void rollout_kernel(Params P, RolloutArgs R) {
+// (A persistent kernel and its *_mov_kernel twin share one body function; each declares its own LDS variables, under the names
+// they had, and hands them to the body.  What the move into a body function did to the kernels without movers -- one or two VGPRs in
+// twelve instantiations, nothing else -- is listed in profiles/movers_kernel_resources.txt.)
+template <int NB, int EPB, bool SENS, int NW, bool BOXES, bool MOV>
+__device__ __forceinline__ void rollout_body(const Params& P, const RolloutArgs& R, StepSmemFor<NB, EPB, NW, MOV>& sm, int& next_env,
+                                             float* const wts, float2 (&pol_z)[4][16], float2 (&pol_eps)[16], unsigned& pol_cnt) {
     constexpr int D = NB + 6, kThreads = 64 * NW;
     using PL = mlp64::Layout<D>;   // the (B + 6)-64-64 policy: 16-wide rows with 10 beams, 42-wide with 36
     constexpr int KS = PL::KS;
-    __shared__ StepSmem<NB, EPB, NW> sm;
-    __shared__ int next_env;
-    __shared__ __attribute__((aligned(16))) float wts[PL::P_ACTOR + 2];   // the actor, staged once for all T steps
-    __shared__ float2 pol_z[4][16];   // policy phase: per-tile partial sums of the two output units
-    __shared__ float2 pol_eps[16];    // ... and the step's action noise
-    __shared__ unsigned pol_cnt;      // arrivals of the in-step policy's five waves (the last one finishes)
     static_assert(NW >= 6 && EPB <= 16, "policy phase: four tile waves + the noise wave beside wave 0's rules; one 16-env policy tile per workgroup");
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int base = blockIdx.x * EPB;
@@ -1591,6 +1689,7 @@ __global__ __launch_bounds__(64 * NW) void rollout_kernel(Params P, RolloutArgs 
     const bool half_rows = P.obs_f16 != 0;   // float16 observation buffers: the policy reads what a reader of the buffers would
     load_obs_tile<NB, EPB, NW>(sm, R.obs_buf, base, nloc, half_rows);
     load_tables<NB, EPB, NW, const Params&>(P, sm);
+    if constexpr (MOV) load_mover_phase0<NB, EPB, NW, const Params&>(P, sm, base, nloc);
     const uint32_t step0 = R.step_base ? *R.step_base : 0u;
     const float var = *R.var_ptr;
     if (tid == 0) pol_cnt = 0u;
@@ -1657,10 +1756,32 @@ __global__ __launch_bounds__(64 * NW) void rollout_kernel(Params P, RolloutArgs 
                 });
             }
         };
-        step_body<NB, EPB, SENS, true, NW, BOXES, 0, const Params&, const StepIO&, decltype(hook)>(P, sm, next_env, io,
-                                                                                                 t == R.T - 1, 0, hook);
+        step_body<NB, EPB, SENS, true, NW, BOXES, 0, const Params&, const StepIO&, decltype(hook), MOV>(P, sm, next_env, io,
+                                                                                                      t == R.T - 1, 0, hook);
         // the observation tile of step t + 1 is in sm.obs (its store only reads it), its action in sm.act_l
     }
+}
+template <int NB, int EPB, bool SENS, int NW, bool BOXES = false>
+__global__ __launch_bounds__(64 * NW) void rollout_kernel(Params P, RolloutArgs R) {
+    using PL = mlp64::Layout<NB + 6>;
+    __shared__ StepSmem<NB, EPB, NW> sm;
+    __shared__ int next_env;
+    __shared__ __attribute__((aligned(16))) float wts[PL::P_ACTOR + 2];   // the actor, staged once for all T steps
+    __shared__ float2 pol_z[4][16];   // policy phase: per-tile partial sums of the two output units
+    __shared__ float2 pol_eps[16];    // ... and the step's action noise
+    __shared__ unsigned pol_cnt;      // arrivals of the in-step policy's five waves (the last one finishes)
+    rollout_body<NB, EPB, SENS, NW, BOXES, false>(P, R, sm, next_env, wts, pol_z, pol_eps, pol_cnt);
+}
+template <bool BOXES>
+__global__ __launch_bounds__(64 * 8) void rollout_mov_kernel(Params P, RolloutArgs R) {
+    using PL = mlp64::Layout<16>;
+    __shared__ StepSmemMov<10, 16, 8> sm;
+    __shared__ int next_env;
+    __shared__ __attribute__((aligned(16))) float wts[PL::P_ACTOR + 2];
+    __shared__ float2 pol_z[4][16];
+    __shared__ float2 pol_eps[16];
+    __shared__ unsigned pol_cnt;
+    rollout_body<10, 16, kMovSens, 8, BOXES, true>(P, R, sm, next_env, wts, pol_z, pol_eps, pol_cnt);
 }
 
 // ---------------------------------------------------------------- the persistent rollout for the reference's ACTIVE actor
@@ -1681,15 +1802,11 @@ __global__ __launch_bounds__(64 * NW) void rollout_kernel(Params P, RolloutArgs 
 // step body (24-58 spilled VGPRs, 6.9-7.4 ms).  The phases of one step (tools/resmlp_rollout_phases.py; profiles/
 // r05_rollout_resmlp_phases.txt): block 1 2.1 us, sum 1.9 (it waits for block 2's weights), block 2 2.3 (the f32 MFMA floor of
 // both blocks on one CU is 2.6), sum + finish 1.3, env step 4.0.
-template <bool SENS>
-__global__ __launch_bounds__(64 * 8) void rollout_resmlp_kernel(Params P, RolloutArgs R) {
+template <bool SENS, bool MOV>
+__device__ __forceinline__ void rollout_resmlp_body(const Params& P, const RolloutArgs& R, StepSmemFor<10, 16, 8, MOV>& sm, int& next_env,
+                                                    resmlp::PolicySmem& ps, resmlp::Block1Smem& bs, float2 (&pol_eps)[16]) {
     constexpr int NB = 10, EPB = 16, NW = 8, D = NB + 6;
     static_assert(D == resmlp::rp::D && EPB == resmlp::kPolEnvs && NW == resmlp::kPolWaves, "the policy step's workgroup");
-    __shared__ StepSmem<NB, EPB, NW> sm;
-    __shared__ int next_env;
-    __shared__ __attribute__((aligned(16))) resmlp::PolicySmem ps;
-    __shared__ __attribute__((aligned(16))) resmlp::Block1Smem bs;   // block 1's weights + the small tail of the parameters
-    __shared__ float2 pol_eps[EPB];   // the action noise of the next policy step (drawn inside the env step in front of it)
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int base = blockIdx.x * EPB;
     const int nloc = min(EPB, P.N - base);
@@ -1698,6 +1815,7 @@ __global__ __launch_bounds__(64 * 8) void rollout_resmlp_kernel(Params P, Rollou
     const bool half_rows = P.obs_f16 != 0;   // float16 observation buffers (BASELINE configs[4]): the policy reads what a reader of the buffers would
     load_obs_tile<NB, EPB, NW>(sm, R.obs_buf, base, nloc, half_rows);
     load_tables<NB, EPB, NW, const Params&>(P, sm);
+    if constexpr (MOV) load_mover_phase0<NB, EPB, NW, const Params&>(P, sm, base, nloc);
     const uint32_t step0 = R.step_base ? *R.step_base : 0u;
     const float var = *R.var_ptr;
     const int l15 = lane & 15, q = lane >> 4;
@@ -1735,9 +1853,27 @@ __global__ __launch_bounds__(64 * 8) void rollout_resmlp_kernel(Params P, Rollou
                 if (wv == 5 && ln < nloc) draw_noise(step0 + (uint32_t)(t + 1));
             }
         };
-        step_body<NB, EPB, SENS, true, NW, false, 0, const Params&, const StepIO&, decltype(hook)>(P, sm, next_env, io, t == R.T - 1, 0, hook);
+        step_body<NB, EPB, SENS, true, NW, false, 0, const Params&, const StepIO&, decltype(hook), MOV>(P, sm, next_env, io, t == R.T - 1, 0, hook);
         __syncthreads();   // the observation tile of step t + 1 is complete in sm.obs (the tile store only reads it)
     }
+}
+template <bool SENS>
+__global__ __launch_bounds__(64 * 8) void rollout_resmlp_kernel(Params P, RolloutArgs R) {
+    constexpr int NB = 10, EPB = 16, NW = 8;
+    __shared__ StepSmem<NB, EPB, NW> sm;
+    __shared__ int next_env;
+    __shared__ __attribute__((aligned(16))) resmlp::PolicySmem ps;
+    __shared__ __attribute__((aligned(16))) resmlp::Block1Smem bs;   // block 1's weights + the small tail of the parameters
+    __shared__ float2 pol_eps[EPB];   // the action noise of the next policy step (drawn inside the env step in front of it)
+    rollout_resmlp_body<SENS, false>(P, R, sm, next_env, ps, bs, pol_eps);
+}
+__global__ __launch_bounds__(64 * 8) void rollout_resmlp_mov_kernel(Params P, RolloutArgs R) {
+    __shared__ StepSmemMov<10, 16, 8> sm;
+    __shared__ int next_env;
+    __shared__ __attribute__((aligned(16))) resmlp::PolicySmem ps;
+    __shared__ __attribute__((aligned(16))) resmlp::Block1Smem bs;
+    __shared__ float2 pol_eps[16];
+    rollout_resmlp_body<kMovSens, true>(P, R, sm, next_env, ps, bs, pol_eps);
 }
 
 // ---------------------------------------------------------------- the evaluation form of the two persistent rollouts
@@ -1776,17 +1912,12 @@ __device__ __forceinline__ bool eval_quota_met(const int* ep_cnt, const int lane
     return __builtin_amdgcn_ballot_w64(ep_cnt[lane & (EPB - 1)] < quota) == 0ull;
 }
 
-template <int NB, bool SENS, bool BOXES>
-__global__ __launch_bounds__(64 * 8) void evaluate_kernel(Params P, EvalArgs R) {
+template <int NB, bool SENS, bool BOXES, bool MOV>
+__device__ __forceinline__ void evaluate_body(const Params& P, const EvalArgs& R, StepSmemFor<NB, 16, 8, MOV>& sm, int& next_env,
+                                              float* const wts, float2 (&pol_z)[4][16], unsigned& pol_cnt, int (&ep_cnt)[16]) {
     constexpr int EPB = 16, NW = 8, D = NB + 6, kThreads = 64 * NW;
     using PL = mlp64::Layout<D>;
     constexpr int KS = PL::KS;
-    __shared__ StepSmem<NB, EPB, NW> sm;
-    __shared__ int next_env;
-    __shared__ __attribute__((aligned(16))) float wts[PL::P_ACTOR + 2];   // the actor, staged once for the whole launch
-    __shared__ float2 pol_z[4][16];   // policy phase: per-tile partial sums of the two output units
-    __shared__ unsigned pol_cnt;      // arrivals of the in-step policy's four tile waves (the last one finishes)
-    __shared__ int ep_cnt[EPB];       // episodes recorded per env
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int base = blockIdx.x * EPB;
     const int nloc = min(EPB, P.N - base);
@@ -1796,6 +1927,7 @@ __global__ __launch_bounds__(64 * 8) void evaluate_kernel(Params P, EvalArgs R) 
     const bool half_rows = P.obs_f16 != 0;
     load_obs_tile<NB, EPB, NW>(sm, R.obs0, base, nloc, half_rows);
     load_tables<NB, EPB, NW, const Params&>(P, sm);
+    if constexpr (MOV) load_mover_phase0<NB, EPB, NW, const Params&>(P, sm, base, nloc);
     if (tid == 0) pol_cnt = 0u;
     __syncthreads();
     const float sigma = SENS ? P.sigma : 0.f;
@@ -1837,7 +1969,7 @@ __global__ __launch_bounds__(64 * 8) void evaluate_kernel(Params P, EvalArgs R) 
                 });
             }
         };
-        step_body<NB, EPB, SENS, true, NW, BOXES, 0, const Params&, const EvalIO&, decltype(hook)>(P, sm, next_env, io, false, 0, hook);
+        step_body<NB, EPB, SENS, true, NW, BOXES, 0, const Params&, const EvalIO&, decltype(hook), MOV>(P, sm, next_env, io, false, 0, hook);
         n_done = t + 1;
         if (eval_quota_met<EPB>(ep_cnt, lane, R.quota)) break;   // behind barrier C: workgroup-uniform (see above)
     }
@@ -1847,19 +1979,38 @@ __global__ __launch_bounds__(64 * 8) void evaluate_kernel(Params P, EvalArgs R) 
     }
     if (tid == 0) R.steps[blockIdx.x] = n_done;
 }
+template <int NB, bool SENS, bool BOXES>
+__global__ __launch_bounds__(64 * 8) void evaluate_kernel(Params P, EvalArgs R) {
+    constexpr int EPB = 16, NW = 8;
+    using PL = mlp64::Layout<NB + 6>;
+    __shared__ StepSmem<NB, EPB, NW> sm;
+    __shared__ int next_env;
+    __shared__ __attribute__((aligned(16))) float wts[PL::P_ACTOR + 2];   // the actor, staged once for the whole launch
+    __shared__ float2 pol_z[4][16];   // policy phase: per-tile partial sums of the two output units
+    __shared__ unsigned pol_cnt;      // arrivals of the in-step policy's four tile waves (the last one finishes)
+    __shared__ int ep_cnt[EPB];       // episodes recorded per env
+    evaluate_body<NB, SENS, BOXES, false>(P, R, sm, next_env, wts, pol_z, pol_cnt, ep_cnt);
+}
+template <bool BOXES>
+__global__ __launch_bounds__(64 * 8) void evaluate_mov_kernel(Params P, EvalArgs R) {
+    using PL = mlp64::Layout<16>;
+    __shared__ StepSmemMov<10, 16, 8> sm;
+    __shared__ int next_env;
+    __shared__ __attribute__((aligned(16))) float wts[PL::P_ACTOR + 2];
+    __shared__ float2 pol_z[4][16];
+    __shared__ unsigned pol_cnt;
+    __shared__ int ep_cnt[16];
+    evaluate_body<10, kMovSens, BOXES, true>(P, R, sm, next_env, wts, pol_z, pol_cnt, ep_cnt);
+}
 
 // (evaluate_resmlp_kernel keeps the parent commit's form of the staging, the policy phase and the EvalIO set-up: through
 // load_obs_tile / load_tables / resmlp_preact / eval_io it took 5.503 instead of 5.482-5.498 ms per launch, profiles/
 // persistent_refactor_ab.txt)
-template <bool SENS>
-__global__ __launch_bounds__(64 * 8) void evaluate_resmlp_kernel(Params P, EvalArgs R) {
+template <bool SENS, bool MOV>
+__device__ __forceinline__ void evaluate_resmlp_body(const Params& P, const EvalArgs& R, StepSmemFor<10, 16, 8, MOV>& sm, int& next_env,
+                                                     resmlp::PolicySmem& ps, resmlp::Block1Smem& bs, int (&ep_cnt)[16]) {
     constexpr int NB = 10, EPB = 16, NW = 8, D = NB + 6, DP = D + 1, kThreads = 64 * NW;
     static_assert(D == resmlp::rp::D && EPB == resmlp::kPolEnvs && NW == resmlp::kPolWaves, "the policy step's workgroup");
-    __shared__ StepSmem<NB, EPB, NW> sm;
-    __shared__ int next_env;
-    __shared__ __attribute__((aligned(16))) resmlp::PolicySmem ps;
-    __shared__ __attribute__((aligned(16))) resmlp::Block1Smem bs;   // block 1's weights + the small tail of the parameters
-    __shared__ int ep_cnt[EPB];       // episodes recorded per env
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int base = blockIdx.x * EPB;
     const int nloc = min(EPB, P.N - base);
@@ -1872,6 +2023,7 @@ __global__ __launch_bounds__(64 * 8) void evaluate_resmlp_kernel(Params P, EvalA
     for (int k = tid; k < 2 * NB; k += kThreads) sm.beam[k] = P.beam_cs[k];
     for (int k = tid; k < (int)(sizeof(Rects) / 8); k += kThreads)
         reinterpret_cast<uint64_t*>(&sm.rects)[k] = reinterpret_cast<const uint64_t*>(P.rects)[k];
+    if constexpr (MOV) load_mover_phase0<NB, EPB, NW, const Params&>(P, sm, base, nloc);
     const int l15 = lane & 15, q = lane >> 4;
     const bool valid = l15 < nloc;
     resmlp::Weights W;
@@ -1901,7 +2053,7 @@ __global__ __launch_bounds__(64 * 8) void evaluate_resmlp_kernel(Params P, EvalA
         if (wave == 0 && q == 0 && valid) sm.act_l[l15] = resmlp::policy_finish_mean(bs.tail, z3, z4);
         __syncthreads();
         // ---- the env step
-        step_body<NB, EPB, SENS, true, NW, false, 0, const Params&, const EvalIO&>(P, sm, next_env, io, false, 0);
+        step_body<NB, EPB, SENS, true, NW, false, 0, const Params&, const EvalIO&, NoHook, MOV>(P, sm, next_env, io, false, 0);
         n_done = t + 1;    // (behind barrier C: the observation tile of step t + 1 is complete in sm.obs)
         if (eval_quota_met<EPB>(ep_cnt, lane, R.quota)) break;   // workgroup-uniform (see above)
     }
@@ -1910,6 +2062,24 @@ __global__ __launch_bounds__(64 * 8) void evaluate_resmlp_kernel(Params P, EvalA
         R.count[base + tid] = ep_cnt[tid];
     }
     if (tid == 0) R.steps[blockIdx.x] = n_done;
+}
+template <bool SENS>
+__global__ __launch_bounds__(64 * 8) void evaluate_resmlp_kernel(Params P, EvalArgs R) {
+    constexpr int NB = 10, EPB = 16, NW = 8;
+    __shared__ StepSmem<NB, EPB, NW> sm;
+    __shared__ int next_env;
+    __shared__ __attribute__((aligned(16))) resmlp::PolicySmem ps;
+    __shared__ __attribute__((aligned(16))) resmlp::Block1Smem bs;   // block 1's weights + the small tail of the parameters
+    __shared__ int ep_cnt[EPB];       // episodes recorded per env
+    evaluate_resmlp_body<SENS, false>(P, R, sm, next_env, ps, bs, ep_cnt);
+}
+__global__ __launch_bounds__(64 * 8) void evaluate_resmlp_mov_kernel(Params P, EvalArgs R) {
+    __shared__ StepSmemMov<10, 16, 8> sm;
+    __shared__ int next_env;
+    __shared__ __attribute__((aligned(16))) resmlp::PolicySmem ps;
+    __shared__ __attribute__((aligned(16))) resmlp::Block1Smem bs;
+    __shared__ int ep_cnt[16];
+    evaluate_resmlp_body<kMovSens, true>(P, R, sm, next_env, ps, bs, ep_cnt);
 }
 
 // ---------------------------------------------------------------- n steps of an action tape in ONE launch (navsim_step_seq)
@@ -1935,10 +2105,8 @@ typedef const SeqKArgs __attribute__((address_space(4))) * SeqKArgsPtr;
 
 static_assert(std::is_trivially_copyable<SeqKArgs>::value && offsetof(SeqKArgs, P) == 0, "kernarg mirror of steps_kernel");
 
-template <int NB, int EPB, bool SENS, int NW = 4, bool BOXES = false, int PAIR = 0>
-__global__ __launch_bounds__(64 * NW, min_waves_per_simd(NB, EPB, NW, PAIR, true)) void steps_kernel(SeqKArgs) {   // the segment IS the struct (see step_kernel)
-    __shared__ StepSmem<NB, EPB, NW> sm;
-    __shared__ int next_env;
+template <int NB, int EPB, bool SENS, int NW, bool BOXES, int PAIR, bool MOV>
+__device__ __forceinline__ void steps_body(StepSmemFor<NB, EPB, NW, MOV>& sm, int& next_env) {
     // parameters through the kernarg segment pointer, as in step_kernel (scalar loads at each use, no spilled SGPRs)
     SeqKArgsPtr A = (SeqKArgsPtr)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(A));
@@ -1956,6 +2124,7 @@ __global__ __launch_bounds__(64 * NW, min_waves_per_simd(NB, EPB, NW, PAIR, true
         load_state<NB, EPB, NW, PRef>(P, sm, e, i);
     }
     load_tables<NB, EPB, NW, PRef>(P, sm);
+    if constexpr (MOV) load_mover_phase0<NB, EPB, NW, PRef>(P, sm, base, nloc);
     for (int t = 0; t < T; ++t) {
         const size_t N = (size_t)P.N;
         const size_t tn = (size_t)t * N;
@@ -1964,9 +2133,21 @@ __global__ __launch_bounds__(64 * NW, min_waves_per_simd(NB, EPB, NW, PAIR, true
             if (t + 1 < T) a_next = R.io.action[tn + N + base + tid];   // lands under this step
         }
         __syncthreads();
-        step_body<NB, EPB, SENS, true, NW, BOXES, PAIR, PRef, const StepIO __attribute__((address_space(4)))&>(P, sm, next_env, R.io,
-                                                                                                           t == T - 1, tn);
+        step_body<NB, EPB, SENS, true, NW, BOXES, PAIR, PRef, const StepIO __attribute__((address_space(4)))&, NoHook, MOV>(
+            P, sm, next_env, R.io, t == T - 1, tn);
     }
+}
+template <int NB, int EPB, bool SENS, int NW = 4, bool BOXES = false, int PAIR = 0>
+__global__ __launch_bounds__(64 * NW, min_waves_per_simd(NB, EPB, NW, PAIR, true)) void steps_kernel(SeqKArgs) {   // the segment IS the struct (see step_kernel)
+    __shared__ StepSmem<NB, EPB, NW> sm;
+    __shared__ int next_env;
+    steps_body<NB, EPB, SENS, NW, BOXES, PAIR, false>(sm, next_env);
+}
+template <bool BOXES>
+__global__ __launch_bounds__(64 * 8) void steps_mov_kernel(SeqKArgs) {
+    __shared__ StepSmemMov<10, 16, 8> sm;
+    __shared__ int next_env;
+    steps_body<10, 16, kMovSens, 8, BOXES, 0, true>(sm, next_env);
 }
 
 // ---------------------------------------------------------------- the persistent rollout at the big shard shapes
@@ -2137,7 +2318,7 @@ __global__ void reset_kernel(Params P, const uint8_t* __restrict__ mask, void* _
     const double x = P.starts[3 * k0], y = P.starts[3 * k0 + 1], th = P.starts[3 * k0 + 2];
     goal_angles(x, y, th, gx, gy, yaw, rel_theta, diff);
     const double dist = hypot(gx - x, gy - y);
-    const float* sp = P.spawn_scan + ((P.per_env ? (size_t)i * P.K : 0) + k0) * B;  // nearest hits at the start pose
+    const float* sp = P.spawn_scan + ((P.spawn_per_env ? (size_t)i * P.K : 0) + k0) * B;  // nearest hits at the start pose
     const uint64_t gid = P.env_id_base + (uint64_t)i;
     auto lidar = [&](int b) {
         const float n = (P.sigma > 0.f) ? lidar_noise(P.key0, P.key1, gid, ctr, 0xFFFFu, b) : 0.f;
@@ -2168,6 +2349,8 @@ __global__ void reset_kernel(Params P, const uint8_t* __restrict__ mask, void* _
 // thread = (env, pose): thread t casts pose[(t % n_poses_per_env) or t] against env (t / n_poses_per_env)'s map.
 //   spawn scans:  n_poses_per_env = K, shared_poses = 1 : pose table [K][3] reused by every env
 //   navsim_raycast: n_poses_per_env = 1, shared_poses = 0 : pose[t]
+// Movers (Params::mov_tape): the env's tape phase joins its static map -- the reset phase phase0[env] for the spawn scans
+// (shared_poses = 1), the phase the env last observed, (ep_step + phase0) mod P, for navsim_raycast (shared_poses = 0).
 __global__ void raycast_kernel(Params P, const double* __restrict__ pose, int n_poses_per_env, int shared_poses, int n,
                                int raw, float* __restrict__ ranges) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -2178,13 +2361,19 @@ __global__ void raycast_kernel(Params P, const double* __restrict__ pose, int n_
     const double cth = cos(th), sth = sin(th);
     const float ox = (float)(x + kLidarX * cth), oy = (float)(y + kLidarX * sth);
     const float4* __restrict__ sp = P.seg + (P.per_env ? (size_t)env * P.S : 0);
+    const float4* __restrict__ mv = nullptr;
+    if (P.mov_tape) {
+        const uint32_t k = shared_poses ? 0u : ((uint32_t)P.ep_step[env] & kStepMask);
+        mv = P.mov_tape + (size_t)mover_phase<const Params&>(P, k, P.mov_phase0 ? (uint32_t)P.mov_phase0[env] : 0u) * (size_t)P.mov_M;
+    }
+    const int n_mov = mv ? P.mov_M : 0;
     for (int b = 0; b < P.B; ++b) {
         const double bc = P.beam_cs[b], bs = P.beam_cs[P.B + b];
         const float c = (float)(cth * bc - sth * bs);
         const float s = (float)(sth * bc + cth * bs);
         float best = INFINITY;
-        for (int j = 0; j < P.S; ++j) {
-            const float4 g = sp[j];
+        for (int j = 0; j < P.S + n_mov; ++j) {
+            const float4 g = (j < P.S) ? sp[j] : mv[j - P.S];
             const float rx = g.x - ox, ry = g.y - oy;
             const float ex = g.z - g.x, ey = g.w - g.y;
             const float k = fmaf(rx, ey, -(ry * ex));
@@ -2366,6 +2555,7 @@ struct navsim {
     double* starts_sc_dev = nullptr;  // [K]
     double* goals_dev = nullptr;    // [G][2]
     const float* seg_dev = nullptr;
+    int32_t* mov_phase0_dev = nullptr;   // navsim_set_movers: the handle's copy of the per-env phase offsets
     bool has_map = false;
     // kernel-shape overrides of THIS handle (navsim_set_shape; tests and A/B timing): envs per workgroup, 0 = the rule of pick_epb
     // below; pair_cast false = 64-segment passes for every map
@@ -2426,6 +2616,7 @@ struct ShapePick {
 static ShapePick pick_shape(const navsim* h, bool tape) {
     const int NB = h->P.B;
     const bool boxes = h->P.tile_box != nullptr;
+    if (h->P.mov_tape) return ShapePick{16, 8, boxes ? 3 : 0};   // movers: the one shape that has the MOV form (navsim_set_movers)
     const int want = pick_epb(h, h->P.N, NB, tape, boxes, h->P.per_env != 0);
     ShapePick sp;
     if (want == 8) sp.epb = 8, sp.waves = 8;                                    // eight waves: one env per wave
@@ -2480,6 +2671,12 @@ static void launch_step(const navsim* h, const float* action, const float* past,
         else hipLaunchKernelGGL(kernel, dim3((h->P.N + epb - 1) / epb), dim3(64 * nw), 0, st, ka);
     };
     const ShapePick sp = pick_shape(h, false);
+    if constexpr (NB == 10) {
+        if (h->P.mov_tape) {
+            with_flag(sp.cast == 3, [&](auto BX) { go(step_mov_kernel<BX>, 16, 8); });
+            return;
+        }
+    }
     NAVSIM_DISPATCH_SHAPE(step_kernel);
 }
 
@@ -2492,6 +2689,12 @@ static void launch_steps(const navsim* h, const SeqArgs& R, hipStream_t st, hipF
         else hipLaunchKernelGGL(kernel, dim3((h->P.N + epb - 1) / epb), dim3(64 * nw), 0, st, ka);
     };
     const ShapePick sp = pick_shape(h, true);
+    if constexpr (NB == 10) {
+        if (h->P.mov_tape) {
+            with_flag(sp.cast == 3, [&](auto BX) { go(steps_mov_kernel<BX>, 16, 8); });
+            return;
+        }
+    }
     NAVSIM_DISPATCH_SHAPE(steps_kernel);
 }
 #undef NAVSIM_DISPATCH_SHAPE
@@ -2514,6 +2717,7 @@ static RolloutPick pick_rollout(const navsim* h) {
     if (h->P.B != 10 && h->P.B != 36) return rp;
     const bool boxes = h->P.tile_box != nullptr;
     const bool pair = h->pair_cast && !boxes && h->P.S > 64 && h->P.seg_pack_log2 == 6;
+    if (h->P.mov_tape) return RolloutPick{1, 16, 8, boxes ? 3 : 0};   // movers: rollout_mov_kernel at every shard size (in rounds beyond 4096 envs)
     if (h->P.B == 10 && (h->force_epb == 64 || h->force_epb == 32 || (h->force_epb == 0 && h->P.N > 16 * 256))) {
         rp.kind = 2; rp.epb = 64; rp.waves = 16;
         // tile-box maps (the 2048-segment house map: a vector-issue-bound cast) on 4097..8192 envs: 64-env workgroups would leave half
@@ -2625,6 +2829,10 @@ static int init_handle(navsim* h, const navsim_cfg* cfg) {
     return NAVSIM_OK;
 }
 
+// what navsim_set_movers (and a navsim_set_map behind it) refuses; the same sentence stands in include/navsim.h
+static const char* const kMoversNotBuilt =
+    "movers need 10 beams and a shared static map: movers with 36 beams or with a per-env static map are not built";
+
 #pragma GCC visibility push(default)
 extern "C" {
 
@@ -2676,6 +2884,7 @@ void navsim_destroy(navsim_t* h) {
     (void)hipFree(h->starts_dev);
     (void)hipFree(h->starts_sc_dev);
     (void)hipFree(h->goals_dev);
+    (void)hipFree(h->mov_phase0_dev);
     delete h;
 }
 
@@ -2734,7 +2943,8 @@ int navsim_set_goal_rects(navsim_t* h, int32_t which, const double* rects_host, 
 
 static int rebuild_spawn_scans(navsim* h, hipStream_t st) {
     Params& P = h->P;
-    const size_t n_poses = (size_t)(P.per_env ? P.N : 1) * P.K;
+    P.spawn_per_env = (P.per_env || (P.mov_tape && P.mov_phase0)) ? 1 : 0;   // movers with phase offsets: every env resets into its own phase
+    const size_t n_poses = (size_t)(P.spawn_per_env ? P.N : 1) * P.K;
     if (h->spawn_scan_dev) {
         HIP_TRY(hipStreamSynchronize(st));
         HIP_TRY(hipFree(h->spawn_scan_dev));
@@ -2755,6 +2965,8 @@ static int rebuild_spawn_scans(navsim* h, hipStream_t st) {
 
 int navsim_set_map(navsim_t* h, const float* seg_dev, int32_t n_segments, int32_t per_env, void* stream) {
     if (!h || !seg_dev || n_segments < 1) return fail(NAVSIM_E_ARG, "navsim_set_map: bad argument");
+    if (h->P.mov_tape && per_env)
+        return fail(NAVSIM_E_ARG, "navsim_set_map: movers are set and " + std::string(kMoversNotBuilt));
     Params& P = h->P;
     P.seg = reinterpret_cast<const float4*>(seg_dev);
     P.S = n_segments;
@@ -2834,6 +3046,49 @@ int navsim_set_map(navsim_t* h, const float* seg_dev, int32_t n_segments, int32_
     if (rc != NAVSIM_OK) return rc;
     h->has_map = true;
     return NAVSIM_OK;
+}
+
+int navsim_set_movers(navsim_t* h, const float* tape_dev, int32_t period, int32_t n_segments, const int32_t* phase0_dev,
+                      void* stream) {
+    if (!h) return fail(NAVSIM_E_ARG, "navsim_set_movers: null handle");
+    if (!h->has_map) return fail(NAVSIM_E_STATE, "navsim_set_movers: call navsim_set_map first");
+    hipStream_t st = (hipStream_t)stream;
+    Params& P = h->P;
+    if (tape_dev) {
+        if (period < 1 || period > 65536 || n_segments < 1 || n_segments > 64)
+            return fail(NAVSIM_E_ARG, "navsim_set_movers: 1 <= period <= 65536 and 1 <= n_segments <= 64");
+        if ((uintptr_t)tape_dev & 15) return fail(NAVSIM_E_ARG, "navsim_set_movers: the tape must be 16-byte aligned");
+        if (P.B != 10 || (P.per_env & 1)) return fail(NAVSIM_E_ARG, std::string("navsim_set_movers: ") + kMoversNotBuilt);
+    }
+    HIP_TRY(hipStreamSynchronize(st));   // launches in flight read the old tape / phase offsets
+    std::vector<int32_t> ph0;
+    if (tape_dev && phase0_dev) {
+        ph0.resize((size_t)P.N);
+        HIP_TRY(hipMemcpy(ph0.data(), phase0_dev, sizeof(int32_t) * P.N, hipMemcpyDeviceToHost));
+        for (const int32_t v : ph0)
+            if (v < 0 || v >= period) return fail(NAVSIM_E_ARG, "navsim_set_movers: a phase0 value lies outside [0, period)");
+    }
+    (void)hipFree(h->mov_phase0_dev);
+    h->mov_phase0_dev = nullptr;
+    P.mov_tape = nullptr;
+    P.mov_phase0 = nullptr;
+    P.mov_P = P.mov_M = P.mov_pack_log2 = 0;
+    if (tape_dev) {
+        if (!ph0.empty()) {
+            HIP_TRY(hipMalloc(&h->mov_phase0_dev, sizeof(int32_t) * P.N));
+            HIP_TRY(hipMemcpy(h->mov_phase0_dev, ph0.data(), sizeof(int32_t) * P.N, hipMemcpyHostToDevice));
+        }
+        P.mov_tape = reinterpret_cast<const float4*>(tape_dev);
+        P.mov_phase0 = h->mov_phase0_dev;
+        P.mov_P = period;
+        P.mov_M = n_segments;
+        int lg = 0;
+        while ((1 << lg) < n_segments) ++lg;
+        P.mov_pack_log2 = lg;
+    }
+    // the reset observation sees tape[phase0[i]]: the spawn tables (and with them the cached next-episode records' scan rows, which
+    // are read through the tables at every step) are rebuilt for the new world
+    return rebuild_spawn_scans(h, st);
 }
 
 int navsim_set_spawn_sampler(navsim_t* h, const double* starts_host, int32_t n_starts, const double* goals_host,
@@ -2938,7 +3193,9 @@ int navsim_rollout_mlp64(navsim_t* h, const float* actor_params_dev, void* obs_b
         constexpr int kRollWaves = 8;
         auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, st, h->P, R); };
         with_flag(sens_on(h), [&](auto S) {
-            if (h->P.B == 36) {
+            if (h->P.mov_tape) {   // (10 beams: navsim_set_movers)
+                with_flag(rp.cast == 3, [&](auto BX) { go(rollout_mov_kernel<BX>); });
+            } else if (h->P.B == 36) {
                 if (rp.cast == 3) go(rollout_kernel<36, 16, S, kRollWaves, true>);
                 else go(rollout_kernel<36, 16, S, kRollWaves>);
             } else if (rp.cast == 3) go(rollout_kernel<10, 16, S, kRollWaves, true>);
@@ -2963,7 +3220,8 @@ int navsim_rollout_resmlp512(navsim_t* h, const float* actor_params_dev, void* o
     if (rc != NAVSIM_OK || n_steps == 0) return rc;
     const dim3 grid((h->P.N + 15) / 16), block(64 * 8);
     with_flag(sens_on(h), [&](auto S) {
-        hipLaunchKernelGGL(rollout_resmlp_kernel<S>, grid, block, 0, (hipStream_t)stream, h->P, R);
+        if (h->P.mov_tape) hipLaunchKernelGGL(rollout_resmlp_mov_kernel, grid, block, 0, (hipStream_t)stream, h->P, R);
+        else hipLaunchKernelGGL(rollout_resmlp_kernel<S>, grid, block, 0, (hipStream_t)stream, h->P, R);
     });
     HIP_TRY(hipGetLastError());
     return NAVSIM_OK;
@@ -3003,7 +3261,8 @@ int navsim_evaluate_mlp64(navsim_t* h, const float* actor_params_dev, const void
     auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)stream, h->P, R); };
     with_flag(sens_on(h), [&](auto S) {
         with_flag(h->P.tile_box != nullptr, [&](auto BOXES) {
-            if (h->P.B == 36) go(evaluate_kernel<36, S, BOXES>);
+            if (h->P.mov_tape) go(evaluate_mov_kernel<BOXES>);   // (10 beams: navsim_set_movers)
+            else if (h->P.B == 36) go(evaluate_kernel<36, S, BOXES>);
             else go(evaluate_kernel<10, S, BOXES>);
         });
     });
@@ -3022,7 +3281,8 @@ int navsim_evaluate_resmlp512(navsim_t* h, const float* actor_params_dev, const 
                         quota, n_steps};
     const dim3 grid((h->P.N + 15) / 16), block(64 * 8);
     with_flag(sens_on(h), [&](auto S) {
-        hipLaunchKernelGGL(evaluate_resmlp_kernel<S>, grid, block, 0, (hipStream_t)stream, h->P, R);
+        if (h->P.mov_tape) hipLaunchKernelGGL(evaluate_resmlp_mov_kernel, grid, block, 0, (hipStream_t)stream, h->P, R);
+        else hipLaunchKernelGGL(evaluate_resmlp_kernel<S>, grid, block, 0, (hipStream_t)stream, h->P, R);
     });
     HIP_TRY(hipGetLastError());
     return NAVSIM_OK;

@@ -62,6 +62,8 @@ class NavSim:
         with torch.cuda.device(self.device):
             check(lib().navsim_create(C.byref(self.cfg), C.byref(self._h)), "navsim_create")
         self._seg = None  # keeps the map tensor alive: the handle only borrows the pointer
+        self._mov_tape = self._mov_phase0 = None   # the same for the mover tape (set_movers)
+        self.movers_period = self.movers_segments = 0
         self.generation = 0  # bumped whenever device pointers / scalars a captured hipGraph would have frozen change
         def knob(name):   # a dev tool's environment variable; anything that is not an integer is ignored, as the library used to
             try:
@@ -115,6 +117,40 @@ class NavSim:
             check(lib().navsim_set_map(self._h, _ptr(seg), int(seg.shape[-2]), int(bool(per_env)), _stream()), "navsim_set_map")
         self._seg = seg
         self.S, self.per_env = int(seg.shape[-2]), bool(per_env)
+        self.generation += 1
+
+    def set_movers(self, tape, phase0=None):
+        """Moving obstacles (navsim_set_movers): tape [P, M, 4] float32 segments (ax, ay, bx, by), P phases of M segments (M <= 64,
+        P <= 65536; pad a phase with NaN segments), cast beside the static map: a step's scan of env i sees
+        tape[(k + 1 + phase0[i]) % P] with k its episode step counter before the step, every reset observation tape[phase0[i]].
+        phase0: [N] integers in [0, P) or None (all zero).  tape=None turns movers off.  Call after set_map (10 beams, a shared static
+        map).  The handle BORROWS the tape tensor (kept alive here; after editing it in place nothing needs to be called unless phase
+        tape[phase0[i]] changed, which the spawn scans have cached: then call set_movers again) and copies phase0."""
+        if tape is None:
+            with torch.cuda.device(self.device):
+                check(lib().navsim_set_movers(self._h, None, 0, 0, None, _stream()), "navsim_set_movers")
+            self._mov_tape = self._mov_phase0 = None
+            self.movers_period = self.movers_segments = 0
+            self.generation += 1
+            return
+        tape = torch.as_tensor(np.asarray(tape, dtype=np.float32) if not torch.is_tensor(tape) else tape)
+        tape = tape.to(device=self.device, dtype=torch.float32).contiguous()
+        if tape.dim() != 3 or tape.shape[-1] != 4 or tape.shape[0] < 1 or tape.shape[1] < 1:
+            raise NavsimError(f"set_movers: tape must be [P, M, 4], got {tuple(tape.shape)}")
+        if tape.data_ptr() % 16:
+            raise NavsimError("set_movers: the tape must be 16-byte aligned")
+        if phase0 is not None:
+            ph = torch.as_tensor(np.asarray(phase0) if not torch.is_tensor(phase0) else phase0)
+            if ph.is_floating_point() or ph.numel() != self.N:
+                raise NavsimError(f"set_movers: phase0 must be {self.N} integers, got {ph.dtype} {tuple(ph.shape)}")
+            phase0 = ph.reshape(self.N).to(device=self.device, dtype=torch.int32).contiguous()
+            self._chk("set_movers: phase0", phase0, torch.int32, self.N)
+        self._chk("set_movers: tape", tape, torch.float32, tape.numel())
+        with torch.cuda.device(self.device):
+            check(lib().navsim_set_movers(self._h, _ptr(tape), int(tape.shape[0]), int(tape.shape[1]), _ptr(phase0), _stream()),
+                  "navsim_set_movers")
+        self._mov_tape, self._mov_phase0 = tape, phase0
+        self.movers_period, self.movers_segments = int(tape.shape[0]), int(tape.shape[1])
         self.generation += 1
 
     def set_goal_rects(self, which, rects):
@@ -297,12 +333,16 @@ class VecEnv:
 
     def __init__(self, n_envs, map="stage_1", n_beams=10, max_episode_steps=500, auto_reset=True, is_training=True,
                  seed=0, env_id_base=0, per_env_map=False, map_seed=0, obs_f16=False, device=None, sampler=None,
-                 lidar_below_min="clamp", lidar_noise_sigma=0.0, respawn_on_arrive=False, envs_per_workgroup=None, pair_cast=None):
+                 lidar_below_min="clamp", lidar_noise_sigma=0.0, respawn_on_arrive=False, envs_per_workgroup=None, pair_cast=None,
+                 movers=None):
+        """movers: moving obstacles (NavSim.set_movers) -- a name of maps.movers_by_name ("orbit4"), a tape [P, M, 4], or a dict:
+        tape=... or name=... (+ period=...), phase="random" (default: phase0[i] drawn from (map_seed, env_id_base + i) only, so
+        the shards of a multi-GPU run and the single-GPU run give every global env the same phase) | "zero"."""
         thr = 0.2 if is_training else 0.4  # environment_new.py:44-47
         # what a sibling env on the same world is built from (PPOTrainer's evaluation env: same map / beams / row type / sensor)
         self.world_args = dict(map=map, n_beams=n_beams, per_env_map=per_env_map, map_seed=map_seed, obs_f16=obs_f16,
                                sampler=sampler, lidar_below_min=lidar_below_min, lidar_noise_sigma=lidar_noise_sigma,
-                               respawn_on_arrive=respawn_on_arrive)
+                               respawn_on_arrive=respawn_on_arrive, movers=movers)
         self.sim = NavSim(n_envs, n_beams=n_beams, max_episode_steps=max_episode_steps, auto_reset=auto_reset,
                           respawn_on_arrive=respawn_on_arrive, seed=seed, env_id_base=env_id_base, threshold_arrive=thr,
                           obs_f16=obs_f16, device=device, lidar_below_min=lidar_below_min,
@@ -324,6 +364,10 @@ class VecEnv:
             if isinstance(sampler, str):
                 sampler = _maps.spawn_tables(sampler)
             self.sim.set_spawn_sampler(*sampler)
+        if movers is not None:
+            tape, phase = _maps.resolve_movers(movers)
+            phase0 = None if phase == "zero" else _maps.mover_phases(tape.shape[0], self.N, map_seed=map_seed, env_id_base=env_id_base)
+            self.sim.set_movers(tape, phase0)
         self.io = self.sim.alloc_io()
 
     def close(self):

@@ -57,7 +57,7 @@ def persistent_policy(actor, n_beams=10):
 
 @torch.no_grad()
 def evaluate(actor, num_episodes=100, max_timesteps_per_episode=500, map="stage_1", n_parallel=None, seed=0, device=None,
-             output_dir="", method_name="baseline", log=print, persistent=False, timing=None):
+             output_dir="", method_name="baseline", log=print, persistent=False, timing=None, movers=None):
     """Every env plays a FIXED quota of q = ceil(num_episodes / n_parallel) whole episodes (its first q; later ones are
     ignored) and stepping continues until every env has met it, so which episodes are reported does not depend on how
     long they last -- taking "the first num_episodes to finish" would over-sample short episodes (early collisions) and
@@ -67,14 +67,14 @@ def evaluate(actor, num_episodes=100, max_timesteps_per_episode=500, map="stage_
     persistent=True replaces the stepping loop by ONE launch (VecEnv.evaluate_policy: the HIP actor and the env step alternate
     inside the kernel, the quota is kept on chip, a workgroup stops when its envs are done); rows, order, CSV, summary and log
     line come from the same code.  The ``time`` column is then length x (wall clock / the most steps any workgroup ran).  An
-    actor or beam count without an evaluation kernel raises ValueError.  timing: a dict that receives ``seconds`` (wall clock
+    actor or beam count without an evaluation kernel raises ValueError.  movers: moving obstacles as for VecEnv.  timing: a dict that receives ``seconds`` (wall clock
     of the stepping alone) and ``steps`` (env steps behind it)."""
     n_par = int(n_parallel or min(num_episodes, 1024))
     quota = -(-int(num_episodes) // n_par)
     if persistent:
         policy, flat_actor = persistent_policy(actor)
     env = VecEnv(n_par, map=map, max_episode_steps=max_timesteps_per_episode, auto_reset=True, is_training=False, seed=seed,
-                 device=device)
+                 device=device, movers=movers)
     dev = env.device
     if persistent:
         flat_actor = flat_actor.to(dev)

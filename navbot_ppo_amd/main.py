@@ -13,7 +13,7 @@ Same flag names and defaults; what they mean on the batched simulator:
 Additions (not in the reference): --n_envs, --policy, --map, --seed, --eval_persistent (with --eval: one launch instead of the
 stepping loop), --eval_every K (training: a persistent evaluation of --eval_episodes episodes every K iterations), --max_grad_norm
 (per-net gradient clipping + non-finite guard inside the update), --target_kl (stop an update's remaining epochs once approx_kl
-exceeds 1.5 x the target).  Vision flags are accepted and refused (the camera
+exceeds 1.5 x the target), --movers NAME / --movers_period P (moving obstacles beside the static map, training and evaluation).  Vision flags are accepted and refused (the camera
 modality is outside the LiDAR hot path); --mode test maps to --eval (the reference's test path is broken).
 """
 import argparse
@@ -56,6 +56,10 @@ def get_args(argv=None):
     p.add_argument("--target_kl", type=float, default=None,
                    help="stop an update -- both nets -- before the optimiser step of the first epoch whose approx_kl exceeds 1.5 x this "
                         "(decided on the device inside the fused update; the remaining epochs cost their launches only); default: off")
+    p.add_argument("--movers", type=str, default=None,
+                   help="moving obstacles cast beside the static map (maps.movers_by_name: orbit4 = four pillars orbiting the spawn "
+                        "pose); authored geometry: parity unpinned (no reference geometry); default: none")
+    p.add_argument("--movers_period", type=int, default=None, help="env steps per cycle of --movers (default 64)")
     args = p.parse_args(argv)
     if args.output_dir is None:
         args.output_dir = os.path.join(os.getcwd(), "runs")
@@ -81,6 +85,7 @@ def schedule(args, world=1):
 
 def main(argv=None):
     args = get_args(argv)
+    movers = dict(name=args.movers, period=args.movers_period) if args.movers else None
     import torch
     from . import evaluate as ev
     from . import maps, ppo
@@ -94,7 +99,8 @@ def main(argv=None):
         print(f"Loading actor: {path}", flush=True)
         actor, _ = ev.load_actor(path, "cuda")
         s = ev.evaluate(actor, num_episodes=args.eval_episodes, max_timesteps_per_episode=args.timesteps_per_episode, map=args.map,
-                        seed=args.seed, output_dir=args.output_dir, method_name=args.method_name, persistent=args.eval_persistent)
+                        seed=args.seed, output_dir=args.output_dir, method_name=args.method_name, persistent=args.eval_persistent,
+                        movers=movers)
         return 0 if s["episodes"] == args.eval_episodes else 1
 
     ctx = ppo.DistCtx()
@@ -111,7 +117,7 @@ def main(argv=None):
                   flush=True)
         sampler = (st, g, dmin, dmax)
     env = VecEnv(hi - lo, map=args.map, max_episode_steps=args.timesteps_per_episode, auto_reset=True, is_training=True,
-                 seed=args.seed, env_id_base=lo, device=ctx.device, sampler=sampler)
+                 seed=args.seed, env_id_base=lo, device=ctx.device, sampler=sampler, movers=movers)
     cfg = ppo.PPOConfig(rollout_len=rollout, max_episode_steps=args.timesteps_per_episode, policy=args.policy, seed=args.seed,
                         save_freq=args.save_every_iterations, output_dir=args.output_dir, method_name=args.method_name,
                         eval_every=args.eval_every, eval_episodes=args.eval_episodes, max_grad_norm=args.max_grad_norm,

@@ -161,6 +161,74 @@ def open_tables(seg, starts, goals, n_beams=10, open_thresh=0.4):
     return np.asarray(starts)[ks], np.asarray(goals)[kg]
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# Moving obstacles (NavSim.set_movers): a tape [P, M, 4] of P phases with M segments each.  Everything here is AUTHORED:
+# results on it are "parity unpinned (no reference geometry)".
+def mover_tape(frames):
+    """frames: P phases, each M segments (ax, ay, bx, by) -> float32 [P, M, 4]; computed in float64 and rounded once, like a
+    map.  Pad a phase that has fewer segments with NaN rows (a segment with a NaN coordinate is never hit)."""
+    t = np.asarray(frames, dtype=np.float64)
+    if t.ndim != 3 or t.shape[-1] != 4:
+        raise ValueError(f"mover_tape: frames must be [P, M, 4], got {t.shape}")
+    return t.astype(np.float32)
+
+
+def orbit_frame(p, period, n=4, orbit_radius=1.0, radius=0.15, sides=8, centre=(0.0, 0.0)):
+    """Phase p of orbit_movers: pillar k is a regular ``sides``-gon of circumradius ``radius`` (not turning about its own axis)
+    centred at centre + orbit_radius (cos a, sin a), a = 2 pi ((p mod period) / period + k / n).  float64 [n * sides, 4]."""
+    segs = []
+    for k in range(n):
+        a = 2.0 * math.pi * ((p % period) / period + k / n)
+        segs += cylinder_to_segments(radius, centre[0] + orbit_radius * math.cos(a), centre[1] + orbit_radius * math.sin(a),
+                                     sides=sides)
+    return np.asarray(segs, dtype=np.float64)
+
+
+def orbit_movers(period, n=4, orbit_radius=1.0, radius=0.15, sides=8, centre=(0.0, 0.0)):
+    """AUTHORED: ``n`` regular-polygon pillars on a circle about ``centre``, one revolution per ``period`` steps.  Tape
+    [period, n * sides, 4] float32.  With the defaults the pillars pass 0.85 m from the stage spawn pose (0, 0): the reset scans
+    stay clear of them, a robot that drives outwards has to cross their orbit."""
+    return mover_tape([orbit_frame(p, period, n, orbit_radius, radius, sides, centre) for p in range(period)])
+
+
+MOVERS_DEFAULT_PERIOD = 64
+
+
+def movers_by_name(name, period=None):
+    table = {"orbit4": lambda P: orbit_movers(P, n=4)}
+    if name not in table:
+        raise KeyError(f"unknown movers {name!r}; have {sorted(table)}")
+    return table[name](int(period or MOVERS_DEFAULT_PERIOD))
+
+
+def resolve_movers(movers):
+    """VecEnv's ``movers`` argument -> (tape [P, M, 4], phase rule "random" | "zero")."""
+    spec = dict(movers) if isinstance(movers, dict) else ({"name": movers} if isinstance(movers, str) else {"tape": movers})
+    phase = spec.pop("phase", "random")
+    if phase not in ("random", "zero"):
+        raise ValueError(f"movers: phase must be 'random' or 'zero', got {phase!r}")
+    if ("tape" in spec) == ("name" in spec):
+        raise ValueError("movers: give a tape or a name")
+    if "tape" in spec:
+        tape = spec.pop("tape")
+    else:
+        tape = movers_by_name(spec.pop("name"), spec.pop("period", None))
+    if spec:
+        raise ValueError(f"movers: unknown entries {sorted(spec)}")
+    return tape, phase
+
+
+def mover_phases(period, n_envs, map_seed=0, env_id_base=0):
+    """phase0[i] in [0, period) for envs env_id_base .. env_id_base + n_envs - 1: a hash (the splitmix64 finaliser) of
+    (map_seed, global env id) and of nothing else, so every shard of a run draws the phases the single-GPU run draws."""
+    g = np.arange(int(env_id_base), int(env_id_base) + int(n_envs), dtype=np.uint64)
+    z = g * np.uint64(0x9E3779B97F4A7C15) + np.uint64((int(map_seed) * 0xD1B54A32D192ED03 + 0x2545F4914F6CDD1D) & 0xFFFFFFFFFFFFFFFF)
+    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    z = z ^ (z >> np.uint64(31))
+    return (z % np.uint64(int(period))).astype(np.int32)
+
+
 def by_name(name):
     table = {"stage_1": stage_1, "stage_2": stage_2, "stage_4": stage_4, "house": house, "house_base": house_base}
     if name not in table:
