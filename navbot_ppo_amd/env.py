@@ -121,10 +121,12 @@ class NavSim:
 
     def set_movers(self, tape, phase0=None):
         """Moving obstacles (navsim_set_movers): tape [P, M, 4] float32 segments (ax, ay, bx, by), P phases of M segments (M <= 64,
-        P <= 65536; pad a phase with NaN segments), cast beside the static map: a step's scan of env i sees
+        P <= 65536; pad a phase with NaN segments: ONE NaN coordinate suffices to make a segment absent, everywhere -- infinite coordinates
+        are undefined), cast beside the static map: a step's scan of env i sees
         tape[(k + 1 + phase0[i]) % P] with k its episode step counter before the step, every reset observation tape[phase0[i]].
         phase0: [N] integers in [0, P) or None (all zero).  tape=None turns movers off.  Call after set_map (10 beams, a shared static
-        map).  The handle BORROWS the tape tensor (kept alive here; after editing it in place nothing needs to be called unless phase
+        map).  The handle BORROWS the tape tensor -- a float32, contiguous, 16-byte aligned tensor on the handle's device is used where it lies, a
+        view into a larger allocation included (kept alive here; after editing it in place nothing needs to be called unless phase
         tape[phase0[i]] changed, which the spawn scans have cached: then call set_movers again) and copies phase0."""
         if tape is None:
             with torch.cuda.device(self.device):

@@ -575,6 +575,17 @@ ORC_API void orc_sim_reset(orc_sim* s, const uint8_t* mask, float* obs) {
         if (!mask || mask[i]) reset_env(s, i, obs + (size_t)i * D, 0, 0, 0);
 }
 
+/* The reset an in-step auto-reset performs, as a call of its own: as orc_sim_reset, but env i's sensor noise is keyed by
+ * (noise_ctr[i], noise_step[i]) -- the draws of the step that ended its episode (rng_ctr and ep_step BEFORE that step) -- instead
+ * of the explicit reset's (goal draws after sampling, 0xFFFF).  For callers that run the steps without auto_reset because the
+ * world changes between a step and the reset behind it (tests/_movers.py composes a per-env map per call). */
+ORC_API void orc_sim_reset_keyed(orc_sim* s, const uint8_t* mask, float* obs, const uint32_t* noise_ctr,
+                                 const uint32_t* noise_step) {
+    int N = s->cfg.n_envs, D = s->cfg.n_beams + 6;
+    for (int i = 0; i < N; ++i)
+        if (!mask || mask[i]) reset_env(s, i, obs + (size_t)i * D, 1, noise_ctr[i], noise_step[i]);
+}
+
 /* one env step for all envs.  past_action_override: nullable [N][2] (Env.step(action, past_action)).
  * ended / ep_return / ep_length nullable. */
 ORC_API void orc_sim_step(orc_sim* s, const float* action, const float* past_action_override,

@@ -86,6 +86,8 @@ def lib():
         L.orc_sim_set_state.argtypes = [vp] * 7
         L.orc_sim_reset.restype = None
         L.orc_sim_reset.argtypes = [vp, vp, vp]
+        L.orc_sim_reset_keyed.restype = None
+        L.orc_sim_reset_keyed.argtypes = [vp, vp, vp, vp, vp]
         L.orc_sim_step.restype = None
         L.orc_sim_step.argtypes = [vp] * 11
         _lib = L
@@ -220,11 +222,18 @@ class OracleSim:
              cv(ep_step, np.int32), cv(rng_ctr, np.uint32)]
         lib().orc_sim_set_state(self._h, *[_p(x) for x in a])
 
-    def reset(self, mask=None, obs=None):
+    def reset(self, mask=None, obs=None, noise_key=None):
+        """noise_key: (rng_ctr [N], ep_step [N]) as they were BEFORE the step that ended the masked envs' episodes -- the reset is
+        then the one that step's auto-reset performs (orc_sim_reset_keyed: it re-uses the step's sensor-noise draws)."""
         if obs is None:
             obs = np.zeros((self.N, self.D), dtype=np.float32)
         m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
-        lib().orc_sim_reset(self._h, _p(m), _p(obs))
+        if noise_key is None:
+            lib().orc_sim_reset(self._h, _p(m), _p(obs))
+        else:
+            ctr, step = (np.ascontiguousarray(a, dtype=np.uint32) for a in noise_key)
+            assert ctr.shape == step.shape == (self.N,)
+            lib().orc_sim_reset_keyed(self._h, _p(m), _p(obs), _p(ctr), _p(step))
         return obs
 
     def step(self, action, past_action=None):

@@ -47,16 +47,17 @@ def _actor(policy, D, seed=5):
     return a, nets.flat_actor_params(a).to(DEV)
 
 
-def _sim(N, B, f16, map_name, seed, cap=CAP, auto_reset=True):
+def _sim(N, B, f16, map_name, seed, cap=CAP, auto_reset=True, **kw):
     """An evaluation handle (arrival threshold 0.4).  stage_1: the robot starts 0.7 m in front of the inner wall and the goals
     fall in a 1 m box around it, so that arrivals, collisions and time-outs all happen within 40-step episodes; house_base (256
-    segments: the tile-box cast): the curated start / goal tables of the house."""
+    segments: the tile-box cast): the curated start / goal tables of the house.  kw: further handle options (the sensor's)."""
     if map_name == "stage_1":
         s = NavSim(N, n_beams=B, max_episode_steps=cap, auto_reset=auto_reset, seed=seed, threshold_arrive=0.4, obs_f16=f16,
-                   spawn=(1.2, 0.8, 0.0), goal_box=(0.6, 1.6), device=DEV)
+                   spawn=(1.2, 0.8, 0.0), goal_box=(0.6, 1.6), device=DEV, **kw)
         s.set_map(maps.by_name(map_name))
     else:
-        s = NavSim(N, n_beams=B, max_episode_steps=cap, auto_reset=auto_reset, seed=seed, threshold_arrive=0.4, obs_f16=f16, device=DEV)
+        s = NavSim(N, n_beams=B, max_episode_steps=cap, auto_reset=auto_reset, seed=seed, threshold_arrive=0.4, obs_f16=f16, device=DEV,
+                   **kw)
         s.set_map(maps.by_name(map_name))
         s.set_spawn_sampler(*maps.spawn_tables("small_house", min_dist=0.3, max_dist=6.0))
     return s
@@ -188,6 +189,39 @@ def test_cases_exercise_every_outcome_and_the_early_exit():
     assert ragged and len(exits) > 1
 
 
+SENS = dict(lidar_noise_sigma=0.01, lidar_below_min="gazebo")
+
+
+@pytest.mark.parametrize("pol", ["mlp64x2", "resmlp512"])
+@pytest.mark.parametrize("world", ["stage_1", "house_base", "stage_1-movers", "stage_2-movers"])
+def test_table_equals_per_step_entry_points_with_sensor_options(pol, world):
+    """1b. The same comparison with LiDAR noise and Gazebo's below-range rule on: the SENS instantiations of evaluate_kernel /
+    evaluate_resmlp_kernel (no tape; house_base: the tile-box cast) and the *_mov_kernel twins, which are always SENS (a tape of
+    the mover tests, 50 envs: three full workgroups and one of 2)."""
+    N, quota = 50, 2
+    flat = _actor(pol, 16)[1]
+    tabs = []
+    for fn in (reference_table, kernel_table):
+        if world.endswith("-movers"):
+            from test_gpu_movers import _gpu, _phase0, _tape
+            cap = 20
+            s = _gpu(N, world.split("-")[0], _tape(7, 37), _phase0(7, 37, N), max_episode_steps=cap, auto_reset=True, seed=13,
+                     threshold_arrive=0.4, **SENS)
+            assert s.info()["step_waves"] == 8
+        else:
+            cap = CAP
+            s = _sim(N, 10, False, world, 13, **SENS)
+        try:
+            r = fn(s, pol, flat, quota, quota * cap)
+        finally:
+            s.close()
+        tabs.append(r[0] if isinstance(r, tuple) else r)
+    want, got = tabs
+    print(f"{pol} {world}: outcomes {np.bincount(want['flags'].reshape(-1), minlength=5)[[1, 2, 4]]} steps {want['steps']}")
+    assert (want["count"] == quota).all()
+    assert_tables_equal(got, want, f"{pol} {world}")
+
+
 def test_n_steps_runs_out():
     """2. n_steps below one episode cap: envs still running have count < quota, unreached slots keep the caller's fill value, every
     workgroup reports n_steps -- through VecEnv.evaluate_policy on the standard evaluation env."""
@@ -210,16 +244,26 @@ def test_n_steps_runs_out():
                 assert got["flags"][q, i] == FILL and got["length"][q, i] == FILL and got["ret"][q, i] == FILL and got["path"][q, i] == FILL
 
 
-@pytest.mark.parametrize("pol,B,f16", [("mlp64x2", 10, False), ("mlp64x2", 36, True), ("resmlp512", 10, False)])
-def test_outputs_guarded(pol, B, f16):
+@pytest.mark.parametrize("pol,B,f16,mov", [pytest.param("mlp64x2", 10, False, None, id="mlp64x2-10-False"),
+                                           pytest.param("mlp64x2", 36, True, None, id="mlp64x2-36-True"),
+                                           pytest.param("resmlp512", 10, False, None, id="resmlp512-10-False"),
+                                           pytest.param("mlp64x2", 10, False, 37, id="mlp64x2-10-False-movers37"),
+                                           pytest.param("resmlp512", 10, False, 5, id="resmlp512-10-False-movers5"),
+                                           pytest.param("mlp64x2", 10, True, 5, id="mlp64x2-10-True-movers5"),
+                                           pytest.param("resmlp512", 10, False, 37, id="resmlp512-10-False-movers37")])
+def test_outputs_guarded(pol, B, f16, mov):
     """3. Every argument inside a guarded allocation (tests/_guards.py), N = 50 (a ragged tail workgroup), at a 256-byte boundary
-    and at the minimum alignment: guards intact, every slot written (quota * cap steps), outputs identical between placements."""
+    and at the minimum alignment: guards intact, every slot written (quota * cap steps), outputs identical between placements.
+    mov: with a guarded mover tape of that many segments per phase (test_gpu_tails._movers): the evaluate_*_mov_kernel twins."""
     N, quota = 50, 2
     flat = _actor(pol, B + 6)[1]
 
     def call(g):
         s = _sim(N, B, f16, "stage_1", 21)
         try:
+            if mov:
+                from test_gpu_tails import _movers
+                _movers(s, g, mov)
             obs0 = g.out((N, B + 6), s.obs_dtype, 16)
             s.reset(obs0)
             pr = g.inp(flat, 16)
@@ -234,7 +278,7 @@ def test_outputs_guarded(pol, B, f16):
         finally:
             s.close()
 
-    run_both(DEV, call, f"{ENTRY[pol]} B={B} f16={f16}")
+    run_both(DEV, call, f"{ENTRY[pol]} B={B} f16={f16} movers={mov}")
 
 
 def _save_actor(policy, tmp_path):

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 import torch
 
-from _movers import MoverOracle, blade_tape, compose
+from _movers import MoverOracle, blade_tape, blade_tape_m1, compose
 from navbot_ppo_amd import maps, ppo
 from navbot_ppo_amd._native import lib
 from navbot_ppo_amd.env import NavSim, NavsimError, VecEnv
@@ -91,14 +91,19 @@ def test_lockstep_against_the_composed_oracle(map_name, P, M):
 
 
 # ---------------------------------------------------------------- 2. bit identity against the static kernels
-@pytest.mark.parametrize("map_name,P,M", [("stage_1", 7, 32), ("stage_1", 40, 37), ("stage_4", 7, 64), ("stage_2", 40, 32), ("stage_2", 1, 1)])
-def test_bit_identical_to_the_static_kernels_on_the_composed_map(map_name, P, M):
-    """MOV path against a second handle whose per-env map is rewritten from the host before every step"""
+def bits(x):
+    """float tensors as bit patterns (the NaN log-prob of a -inf reading compares equal to itself)"""
+    return x.view({4: torch.int32, 2: torch.int16}[x.element_size()]) if x.is_floating_point() else x
+
+
+def _vs_static_kernels(map_name, P, M, **kw):
+    """MOV path against a second handle (same options kw: the static per-env kernel) whose per-env map is rewritten from the host
+    before every step"""
     N, T = 40, 30
     tape, ph0 = _tape(P, M), _phase0(P, M, N)
     static = maps.by_name(map_name)
-    a = _gpu(N, map_name, tape, ph0, seed=9)
-    b = NavSim(N, device=DEV, seed=9)
+    a = _gpu(N, map_name, tape, ph0, seed=9, **kw)
+    b = NavSim(N, device=DEV, seed=9, **kw)
     rr, rs = maps.goal_rects(map_name)
     b.set_goal_rects(0, rr)
     b.set_goal_rects(1, rs)
@@ -115,19 +120,30 @@ def test_bit_identical_to_the_static_kernels_on_the_composed_map(map_name, P, M)
         a.step(act, ia.obs, ia.reward, ia.done, ia.arrive, ia.ended)
         b.step(act, ib.obs, ib.reward, ib.done, ib.arrive, ib.ended)
         for k in ("obs", "reward", "done", "arrive", "ended"):
-            assert torch.equal(getattr(ia, k), getattr(ib, k)), (k, t)
+            assert torch.equal(bits(getattr(ia, k)), bits(getattr(ib, k))), (k, t)
         hits += int(ia.done.sum())
     assert hits > 0
     a.close()
     b.close()
 
 
+@pytest.mark.parametrize("map_name,P,M", [("stage_1", 7, 32), ("stage_1", 40, 37), ("stage_4", 7, 64), ("stage_2", 40, 32), ("stage_2", 1, 1)])
+def test_bit_identical_to_the_static_kernels_on_the_composed_map(map_name, P, M):
+    _vs_static_kernels(map_name, P, M)
+
+
 # ---------------------------------------------------------------- 3. phase arithmetic
-@pytest.mark.parametrize("k0", ["P-1", "P", "2**20+3"])
-def test_phase_follows_the_episode_step_counter(k0):
-    N, P, M = 24, 7, 32
-    k = {"P-1": P - 1, "P": P, "2**20+3": 2 ** 20 + 3}[k0]
-    tape, ph0 = _tape(P, M), _phase0(P, M, N)
+@pytest.mark.parametrize("P,M,k0", [pytest.param(7, 32, "P-1", id="P-1"), pytest.param(7, 32, "P", id="P"),
+                                    pytest.param(7, 32, "2**20+3", id="2**20+3"), pytest.param(7, 32, "2**30-2", id="2**30-2"),
+                                    pytest.param(65536, 1, "P-1", id="P65536-P-1"), pytest.param(65536, 1, "2**30-2", id="P65536-2**30-2")])
+def test_phase_follows_the_episode_step_counter(P, M, k0):
+    """2**30-2: the step counter one short of the 30-bit mask of the ep_step word.  P = 65536: the host's upper bound on the period
+    (a 1 MB tape of one blade, built without a loop), with phase0 values at both ends of the range."""
+    N = 24
+    k = {"P-1": P - 1, "P": P, "2**20+3": 2 ** 20 + 3, "2**30-2": 2 ** 30 - 2}[k0]
+    tape, ph0 = (blade_tape_m1(P), _phase0(P, M, N)) if P == 65536 else (_tape(P, M), _phase0(P, M, N))
+    if P == 65536:
+        ph0[:4] = [65535, 0, 65535, 1]
     gpu = _gpu(N, "stage_1", tape, ph0, seed=3)
     cpu = MoverOracle(N, maps.stage_1(), tape, ph0, seed=3)
     io = gpu.alloc_io()
@@ -194,29 +210,29 @@ def test_raycast_sees_the_phase_the_env_last_observed():
 
 
 # ---------------------------------------------------------------- 4. persistent forms
-@pytest.mark.parametrize("map_name,P,M", [("stage_1", 7, 32), ("stage_2", 40, 64)])
-def test_step_seq_equals_step_launches(map_name, P, M):
-    N, T, cap = 40, 24, 9   # auto-resets and the wrap of the phase both happen inside the launch
-    tape, ph0 = _tape(P, M, R_NEAR), _phase0(P, M, N)
-    acts = torch.from_numpy(_actions(np.random.default_rng(45), T, N)).to(DEV)
-    a = _gpu(N, map_name, tape, ph0, max_episode_steps=cap, auto_reset=True, seed=8)
-    b = _gpu(N, map_name, tape, ph0, max_episode_steps=cap, auto_reset=True, seed=8)
+def _seq_equals_steps(map_name, P, M, N=40, T=24, cap=9, radius=R_NEAR, acts=None, seed=8, **kw):
+    """navsim_step_seq against T navsim_step launches, any handle options kw.  Defaults: auto-resets and the wrap of the phase both
+    happen inside the launch."""
+    tape, ph0 = _tape(P, M, radius), _phase0(P, M, N)
+    acts = torch.from_numpy(_actions(np.random.default_rng(45), T, N) if acts is None else acts).to(DEV)
+    a = _gpu(N, map_name, tape, ph0, max_episode_steps=cap, auto_reset=True, seed=seed, **kw)
+    b = _gpu(N, map_name, tape, ph0, max_episode_steps=cap, auto_reset=True, seed=seed, **kw)
     inf = a.info()
     assert (inf["seq_epb"], inf["seq_waves"]) == (16, 8), inf
     ia, ib = a.alloc_io(), b.alloc_io()
     assert torch.equal(a.reset(ia.obs), b.reset(ib.obs))
     z = lambda dt=torch.float32, *s: torch.zeros((T, N) + s, dtype=dt, device=DEV)
-    seq = dict(obs=z(torch.float32, 16), reward=z(), done=z(torch.uint8), arrive=z(torch.uint8), ended=z(torch.uint8), ep_return=z(),
+    seq = dict(obs=z(a.obs_dtype, 16), reward=z(), done=z(torch.uint8), arrive=z(torch.uint8), ended=z(torch.uint8), ep_return=z(),
                ep_length=z(torch.int32), ep_path=z())
     a.step_seq(acts, seq["obs"], seq["reward"], seq["done"], seq["arrive"], seq["ended"], seq["ep_return"], seq["ep_length"], seq["ep_path"])
     for t in range(T):
         b.step(acts[t], ib.obs, ib.reward, ib.done, ib.arrive, ib.ended, ib.ep_return, ib.ep_length, ep_path=ib.ep_path)
         for k in ("obs", "reward", "done", "arrive", "ended"):
-            assert torch.equal(seq[k][t], getattr(ib, k)), (k, t)
+            assert torch.equal(bits(seq[k][t]), bits(getattr(ib, k))), (k, t)
         e = ib.ended.bool()
         for k in ("ep_return", "ep_length", "ep_path"):
-            assert torch.equal(seq[k][t][e], getattr(ib, k)[e]), (k, t)
-    # every env times out twice in 24 steps at the latest; the movers end episodes earlier
+            assert torch.equal(bits(seq[k][t][e]), bits(getattr(ib, k)[e])), (k, t)
+    # (defaults: every env times out twice in 24 steps at the latest;) the movers end episodes earlier
     assert int(seq["ended"].sum()) > 2 * N and int(seq["done"].sum()) > 0
     sa, sb = a.get_state(), b.get_state()
     for k in sa:
@@ -225,16 +241,20 @@ def test_step_seq_equals_step_launches(map_name, P, M):
     b.close()
 
 
-@pytest.mark.parametrize("policy", ["mlp64x2", "resmlp512"])
-@pytest.mark.parametrize("map_name", ["stage_1", "stage_2"])
-def test_persistent_rollout_equals_per_step_rollout(policy, map_name):
+@pytest.mark.parametrize("map_name,P,M", [("stage_1", 7, 32), ("stage_2", 40, 64)])
+def test_step_seq_equals_step_launches(map_name, P, M):
+    _seq_equals_steps(map_name, P, M)
+
+
+def _rollouts_equal(policy, map_name, **kw):
     """navsim_rollout_mlp64 / navsim_rollout_resmlp512 with a tape against T pairs of navppo_*_act / navsim_step (the pattern of
-    test_gpu_ppo.test_persistent_rollout_equals_per_step_rollout): every buffer and the state bit-identical, two rollouts."""
+    test_gpu_ppo.test_persistent_rollout_equals_per_step_rollout): every buffer and the state bit-identical, two rollouts.  kw: env
+    options (sensor, float16 rows)."""
     N, T, cap = 40, 24, 9
     movers = dict(tape=_tape(7, 32, R_NEAR), phase="random")
     outs = []
     for persistent in (True, False):
-        env = VecEnv(N, map=map_name, max_episode_steps=cap, seed=3, map_seed=5, movers=movers)
+        env = VecEnv(N, map=map_name, max_episode_steps=cap, seed=3, map_seed=5, movers=movers, **kw)
         cfg = ppo.PPOConfig(rollout_len=T, max_episode_steps=cap, n_updates_per_iteration=1, policy=policy, seed=5,
                             persistent_rollout=persistent, use_graph=False)
         tr = ppo.PPOTrainer(env, cfg)
@@ -250,13 +270,19 @@ def test_persistent_rollout_equals_per_step_rollout(policy, map_name):
         outs.append((bufs, env.sim.get_state()))
         env.close()
     (a, sa), (b, sb) = outs
+    assert a[0][0].dtype == (torch.float16 if kw.get("obs_f16") else torch.float32)
     assert int(a[0][6].sum()) >= 2 * N   # cap 9, 24 steps: every env ends twice at least -- resets and phase wraps inside the launch
-    bits = lambda x: x.view(torch.int32) if x.dtype == torch.float32 else x
     for ra, rb in zip(a, b):
         for x, y in zip(ra, rb):
             assert torch.equal(bits(x), bits(y))
     for k in sa:
         np.testing.assert_array_equal(sa[k], sb[k])
+
+
+@pytest.mark.parametrize("policy", ["mlp64x2", "resmlp512"])
+@pytest.mark.parametrize("map_name", ["stage_1", "stage_2"])
+def test_persistent_rollout_equals_per_step_rollout(policy, map_name):
+    _rollouts_equal(policy, map_name)
 
 
 @pytest.mark.parametrize("policy", ["mlp64x2", "resmlp512"])

@@ -353,13 +353,31 @@ def _map(N, per_env, g):
     return g.inp(seg.to(DEV), 16)   # NaN segments (poison) after N * S * 4 floats
 
 
-@pytest.mark.parametrize("B,f16,per_env,epb", [(10, 0, False, 0), (10, 1, True, 0), (36, 0, False, 0), (36, 1, True, 0),
-                                               (10, 0, False, 8), (10, 0, True, 64), (36, 0, False, 16)])
-def test_navsim_step_entry_points_guarded(B, f16, per_env, epb):
+def _movers(s, g, M):
+    """a tape of M segments per phase (M = 37: padded to 40 rows with NaN segments), P = 7, and per-env phase offsets, both placed by
+    the Guards: the tape at 16 bytes (the ABI's minimum), BORROWED where it lies; phase0 at 4 bytes (the library copies it)"""
+    from _movers import blade_tape
+    P = 7
+    tape = g.inp(torch.from_numpy(blade_tape(P, M, pad_to=40 if M == 37 else None, radius=0.45)).to(DEV), 16)
+    ph0 = g.inp((torch.arange(s.N, dtype=torch.int32) * 5 % P).to(DEV), 4)
+    s.set_movers(tape, ph0)
+    assert s._mov_tape.data_ptr() == tape.data_ptr() and s._mov_phase0.data_ptr() == ph0.data_ptr()
+    assert (s.movers_period, s.movers_segments) == (P, tape.shape[1])
+    inf = s.info()
+    assert (inf["step_epb"], inf["step_waves"], inf["seq_epb"], inf["rollout_kind"], inf["rollout_epb"]) == (16, 8, 16, 1, 16), inf
+
+
+_OLD = [(10, 0, False, 0), (10, 1, True, 0), (36, 0, False, 0), (36, 1, True, 0), (10, 0, False, 8), (10, 0, True, 64), (36, 0, False, 16)]
+
+
+@pytest.mark.parametrize("B,f16,per_env,epb,mov", [pytest.param(*c, None, id="-".join(str(x) for x in c)) for c in _OLD] +
+                         [pytest.param(10, 0, False, 0, 37, id="10-0-False-0-movers37"), pytest.param(10, 1, False, 0, 5, id="10-1-False-0-movers5")])
+def test_navsim_step_entry_points_guarded(B, f16, per_env, epb, mov):
     """navsim_reset (masked: unmasked rows keep the canary), navsim_step, navsim_step_seq ([T, N, .] rows, guard after the last row),
     navsim_raycast and navsim_rollout_mlp64 on N that is not a multiple of the picked envs_per_workgroup (read from navsim_get_info,
     other shapes forced with set_shape), per-env maps with NaN segments after N * S * 4.  Buffers at 256 bytes and at the smallest
-    alignment the header states (actions 8, obs of the rollout 16) or, where it states none, 16 bytes."""
+    alignment the header states (actions 8, obs of the rollout 16) or, where it states none, 16 bytes.  mov: with a mover tape
+    (_movers), so the calls launch the *_mov_kernel twins: step_mov, steps_mov, rollout_mov, and the reset / ray cast on the tape."""
     N, T = 1000 + 3, 5
     D = B + 6
     odt = torch.float16 if f16 else torch.float32
@@ -373,6 +391,8 @@ def test_navsim_step_entry_points_guarded(B, f16, per_env, epb):
         s = _sim(N, B, f16, 5, epb)
         try:
             s.set_map(_map(N, per_env, g))
+            if mov:
+                _movers(s, g, mov)
             info = s.info()
             assert info["step_epb"] > 0 and N % info["step_epb"] != 0 and N % max(info["rollout_epb"], 1) != 0
             al = 16 if g.minimal else 256
@@ -422,11 +442,21 @@ def test_navsim_step_entry_points_guarded(B, f16, per_env, epb):
         finally:
             s.close()
 
-    run_both(DEV, call, f"navsim B={B} f16={f16} per_env={per_env} epb={epb}")
+    run_both(DEV, call, f"navsim B={B} f16={f16} per_env={per_env} epb={epb} movers={mov}")
 
 
 def test_navsim_rollout_resmlp512_guarded():
     """navsim_rollout_resmlp512 with [T, N, .] rows guarded after the last row, N not a multiple of its 16 envs per workgroup."""
+    _rollout_resmlp512_guarded(None)
+
+
+@pytest.mark.parametrize("mov", [37, 5])
+def test_navsim_rollout_resmlp512_guarded_with_movers(mov):
+    """... and rollout_resmlp_mov_kernel: the same call on a handle with a guarded mover tape (_movers)"""
+    _rollout_resmlp512_guarded(mov)
+
+
+def _rollout_resmlp512_guarded(mov):
     N, T = 16 * 9 + 5, 4
     _, _, flat = _resmlp_flat(2)
 
@@ -434,6 +464,8 @@ def test_navsim_rollout_resmlp512_guarded():
         s = _sim(N, 10, 0, 3)
         try:
             s.set_map(_map(N, False, g))
+            if mov:
+                _movers(s, g, mov)
             o0 = g.out((N, 16), torch.float32, 16 if g.minimal else 256)
             s.reset(o0)
             start = torch.cat([o0[None], canary_of(torch.float32).to(DEV).expand(T, N, 16)]).contiguous()
@@ -452,7 +484,7 @@ def test_navsim_rollout_resmlp512_guarded():
         finally:
             s.close()
 
-    run_both(DEV, call, "rollout_resmlp512")
+    run_both(DEV, call, f"rollout_resmlp512 movers={mov}")
 
 
 # ================================================================================================ C: per-sample probes against float64

@@ -94,3 +94,96 @@ def test_main_has_the_movers_flags():
     assert a.movers == "orbit4" and a.movers_period == 20
     a = main.get_args([])
     assert a.movers is None and a.movers_period is None
+
+
+# ---------------------------------------------------------------- the helpers of tests/test_gpu_movers_edges.py check themselves
+def test_tripwire_rows_are_seen_by_every_beam_and_the_interior_is_the_tape():
+    from _movers import blade_tape, embed_with_tripwires, tripwire_rows
+    from oracle import navsim_oracle as O
+    for M in (4, 5, 40):
+        wire = tripwire_rows(M)
+        assert wire.shape == (M, 4) and wire.dtype == np.float32
+        scan = O.raycast(wire, 0.0, 0.0, 0.0)
+        assert scan.shape == (10,) and (scan >= 0.3).all() and (scan < 0.4).all()   # all 10 beams, nearer than any blade of the tests
+        tape = blade_tape(7, M if M != 40 else 37, pad_to=40 if M == 40 else None, radius=0.45)
+        whole = embed_with_tripwires(tape)
+        assert whole.shape == (9, M, 4) and whole.dtype == np.float32 and whole.flags["C_CONTIGUOUS"]
+        np.testing.assert_array_equal(whole[1:8], tape)                             # NaN padding included, bit for bit
+        assert whole[1:8].tobytes() == tape.tobytes()
+        np.testing.assert_array_equal(whole[0], wire)
+        np.testing.assert_array_equal(whole[8], wire)
+        # ... and the wall changes the scan the tape alone gives at the spawn pose, in every beam
+        fin = tape[0][np.isfinite(tape[0]).all(axis=1)]
+        assert (O.raycast(np.concatenate([fin, wire]), 0.0, 0.0, 0.0) != O.raycast(fin, 0.0, 0.0, 0.0)).all()
+
+
+@pytest.mark.parametrize("M", [5, 37, 64])
+def test_below_min_poses_face_a_tape_segment_and_no_static_one(M):
+    from _movers import LIDAR_X, RANGE_MIN, below_min_poses, blade_tape
+    from oracle import navsim_oracle as O
+    tape = blade_tape(7, M, pad_to=40 if M == 37 else None)
+    phases = np.arange(40) % 7
+    pose = below_min_poses(tape, phases)
+    assert pose.shape == (40, 3)
+    static = maps.stage_1()
+    for p, ph in zip(pose, phases):
+        ox, oy = p[0] + LIDAR_X * math.cos(p[2]), p[1] + LIDAR_X * math.sin(p[2])
+        seg = tape[ph][np.isfinite(tape[ph]).all(axis=1)].astype(np.float64)
+        a, e = seg[:, :2], seg[:, 2:] - seg[:, :2]
+        t = np.clip(((np.array([ox, oy]) - a) * e).sum(1) / (e * e).sum(1), 0, 1)
+        d = np.hypot(*(a + t[:, None] * e - [ox, oy]).T)
+        assert d.min() < RANGE_MIN - 0.04                        # the sensor is 7 cm from a tape segment ...
+        assert (O.raycast(static, *p) > 1.0).all()               # ... over a metre from every static one in sight,
+        assert O.raycast(seg, *p)[4:6].max() == np.float32(RANGE_MIN)   # and the beams beside straight ahead end on the tape below range_min
+        assert (O.raycast(seg, *p) >= np.float32(RANGE_MIN)).all()      # (orc_raycast clamps a nearer hit to range_min)
+
+
+def test_partial_nan_tape_has_one_nan_per_marked_segment():
+    from _movers import blade_tape, blade_tape_m1, partial_nan_tape
+    tape, whole = partial_nan_tape(7, 12)
+    assert tape.shape == whole.shape == (7, 12, 4) and np.isfinite(whole).all()
+    nan = np.isnan(tape)
+    assert (nan.sum(axis=2)[:, [0, 1, 10, 11]] == 1).all() and not nan[:, 2:10].any()
+    assert sorted(np.argwhere(nan[0])[:, 1].tolist()) == [0, 1, 2, 3]               # one in each of the four positions
+    np.testing.assert_array_equal(tape[~nan], whole[~nan])
+    np.testing.assert_array_equal(tape[:, 2:10], blade_tape(7, 8))
+    np.testing.assert_array_equal(blade_tape_m1(64), blade_tape(64, 1))
+    big = blade_tape_m1(65536)
+    assert big.shape == (65536, 1, 4) and big.nbytes == 1 << 20 and np.isfinite(big).all()
+
+
+def test_watching_oracle_tells_a_tape_in_sight_from_one_out_of_sight():
+    from _movers import MoverOracle, blade_tape
+    near = MoverOracle(3, maps.stage_1(), blade_tape(7, 5), watch=True, seed=1)
+    far = MoverOracle(3, maps.stage_1(), blade_tape(7, 5) + np.float32(100.0), watch=True, seed=1)
+    for s in (near, far):
+        s.reset()
+        s.step(np.zeros((3, 2), np.float32))
+    assert near.seen == [True] and far.seen == [False]
+    assert near.tape_in_scan().all() and not far.tape_in_scan().any()
+
+
+@pytest.mark.parametrize("opts", [dict(), dict(lidar_noise_sigma=0.02), dict(lidar_noise_sigma=0.02, lidar_below_min="gazebo")], ids=str)
+def test_mover_oracle_on_a_tape_out_of_sight_is_the_auto_resetting_oracle(opts):
+    """MoverOracle steps without auto_reset and resets by a call of its own; with the tape far away that must be, bit for bit, the
+    OracleSim with auto_reset on the static map -- the sensor noise of the reset rows included (the in-step auto-reset re-uses the
+    step's noise draws: OracleSim.reset(noise_key=...))."""
+    from _movers import MoverOracle, blade_tape
+    from oracle import navsim_oracle as O
+    N, T = 12, 40
+    rng = np.random.default_rng(5)
+    acts = np.stack([rng.uniform(0.5, 1, (T, N)), rng.uniform(-1, 1, (T, N))], 2).astype(np.float32)
+    a = MoverOracle(N, maps.stage_1(), blade_tape(7, 5) + np.float32(100.0), np.arange(N) % 7, max_episode_steps=6, seed=2, **opts)
+    b = O.OracleSim(N, max_episode_steps=6, auto_reset=True, seed=2, **opts)
+    b.set_map(np.concatenate([maps.stage_1(), blade_tape(7, 5)[0] + np.float32(100.0)]))
+    np.testing.assert_array_equal(a.reset(), b.reset())
+    ends = 0
+    for t in range(T):
+        oa, ob = a.step(acts[t]), b.step(acts[t])
+        for k in ("obs", "reward", "done", "arrive", "ended"):
+            np.testing.assert_array_equal(oa[k], ob[k], err_msg=f"{k}, step {t}")
+        ends += int(ob["ended"].sum())
+    assert ends >= 6 * N
+    sa, sb = a.get_state(), b.get_state()
+    for k in sa:
+        np.testing.assert_array_equal(sa[k], sb[k])
