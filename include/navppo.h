@@ -221,6 +221,35 @@ int navppo_mlp64_bf16x3_update_epoch_kl(float* params_dev, const void* prep_dev,
                                         float* adam_v_dev, float* grad_dev, float* stats_dev, void* workspace_dev, float max_norm,
                                         float* clip_stats_dev, float kl_limit, float* kl_state_dev, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------------
+ * Minibatch updates.  Every *_loss_grad / *_update_epoch[_clipped | _kl] entry point takes pointers and n_samples, so one optimiser
+ * step on a CONTIGUOUS slice [start, start + m) of a batch is the same call with every pointer advanced by `start` samples and
+ * n_samples = m; for the bf16x3 entry points prep_dev advances by navppo_mlp64_bf16x3_prep_bytes(start, obs_dim), which needs
+ * start % 32 == 0 (prep_dev is an array of per-32-sample tile blocks; the slice's own end may lie anywhere).  Calls on slices of one
+ * update use consecutive `step` numbers; stats_dev[3] / [7] of the 512-wide nets' *_update_epoch then hold the call before only while
+ * n_samples does not change between the two calls (their squared-norm slots lie behind the per-sample part of the workspace).
+ *
+ * navppo_shuffle_batch makes the slices random subsets: out[i] = in[pi(i)], 0 <= i < n, for the five per-sample arrays of a batch
+ * (rows as navppo_mlp64_loss_grad takes them), in one launch, pi computed per index on the device -- no table, no host round trip.
+ * pi is a pure function of (n, key, counter); uint32_t arithmetic wraps, `hi(p)` / `lo(p)` are the words of a 64-bit product:
+ *   b = the smallest integer with 2^b >= n;  a = b / 2 (rounded down);  c = b - a
+ *   (o0, o1, .., ..) = Philox4x32-10(counter = (lo(counter), hi(counter), (uint32_t)n, 0x73687566), key = (lo(key), hi(key)))
+ *   F(r, k0, k1):  p = (uint64_t)0xD2511F53 * (uint32_t)(r + k0);  t = hi(p) ^ lo(p) ^ k1;  q = (uint64_t)0xCD9E8D57 * t;  hi(q) ^ lo(q)
+ *   E(x), a bijection of [0, 2^b): (wl, wr) = (a, c); for j = 0 .. 5: L = x >> wr, R = x & (2^wr - 1),
+ *         x = (R << wl) | (L ^ (F(R, o0 + j * 0x9E3779B9, o1 + j * 0xBB67AE85) & (2^wl - 1))), then swap wl and wr
+ *         (a 6-round Feistel network whose halves trade places and widths every round: unbalanced when b is odd)
+ *   pi(i) = the first of E(i), E(E(i)), ... that is < n                                    (cycle walking; n = 1: pi(0) = 0)
+ *   obs_dev / obs_out     [n, obs_dim] rows, float32 or float16 (obs_f16), aligned as for navppo_mlp64_loss_grad
+ *   act_dev / act_out     [n, 2] f32, 8-byte aligned      logp_old_dev, rtg_dev, adv_dev and their outputs [n] f32
+ *   gate_dev              nullable: the kl_state_dev [4] of the *_kl entry points -- gate_dev[0] != 0 (the update stopped): the kernel
+ *                         returns at its entry and the outputs keep their contents
+ * -1 and nothing launched: a null pointer (gate_dev aside), n_samples < 1 or >= 2^31, obs_dim not 16 or 42, a misaligned buffer, an
+ * output that overlaps an input or another output.
+ */
+int navppo_shuffle_batch(const void* obs_dev, int32_t obs_dim /* 16 | 42 */, int32_t obs_f16, const float* act_dev, const float* logp_old_dev,
+                         const float* rtg_dev, const float* adv_dev, int64_t n_samples, uint64_t key, uint64_t counter, void* obs_out,
+                         float* act_out, float* logp_out, float* rtg_out, float* adv_out, const float* gate_dev, void* stream);
+
 /*
  * PPO.get_action() (ppo.py:673-706) for all envs of a shard in one launch: mean = actor(obs) (net_actor forward),
  * sample MVN(mean, var*I), clamp a0 to [0,1] and a1 to [-1,1] (ppo.py:700-703), log-prob of the CLAMPED action (:704).

@@ -13,7 +13,8 @@ Same flag names and defaults; what they mean on the batched simulator:
 Additions (not in the reference): --n_envs, --policy, --map, --seed, --eval_persistent (with --eval: one launch instead of the
 stepping loop), --eval_every K (training: a persistent evaluation of --eval_episodes episodes every K iterations), --max_grad_norm
 (per-net gradient clipping + non-finite guard inside the update), --target_kl (stop an update's remaining epochs once approx_kl
-exceeds 1.5 x the target), --movers NAME / --movers_period P (moving obstacles beside the static map, training and evaluation).  Vision flags are accepted and refused (the camera
+exceeds 1.5 x the target), --minibatch_size M / --minibatch_shuffle MODE (K = ceil(batch / M) optimiser steps per epoch on slices of the
+batch, shuffled on the device), --movers NAME / --movers_period P (moving obstacles beside the static map, training and evaluation).  Vision flags are accepted and refused (the camera
 modality is outside the LiDAR hot path); --mode test maps to --eval (the reference's test path is broken).
 """
 import argparse
@@ -56,6 +57,12 @@ def get_args(argv=None):
     p.add_argument("--target_kl", type=float, default=None,
                    help="stop an update -- both nets -- before the optimiser step of the first epoch whose approx_kl exceeds 1.5 x this "
                         "(decided on the device inside the fused update; the remaining epochs cost their launches only); default: off")
+    p.add_argument("--minibatch_size", type=int, default=None,
+                   help="samples per optimiser step and rank, a multiple of 32: every epoch takes ceil(batch / this) steps on slices of the "
+                        "batch instead of one on all of it; default (or >= the batch): full-batch epochs, as in the reference")
+    p.add_argument("--minibatch_shuffle", type=str, default="epoch", choices=["epoch", "update", "none"],
+                   help="with --minibatch_size: a fresh device-side permutation of the batch before every epoch (epoch), one per update "
+                        "(update), or contiguous slices of the batch as it lies (none)")
     p.add_argument("--movers", type=str, default=None,
                    help="moving obstacles cast beside the static map (maps.movers_by_name: orbit4 = four pillars orbiting the spawn "
                         "pose); authored geometry: parity unpinned (no reference geometry); default: none")
@@ -81,6 +88,15 @@ def schedule(args, world=1):
         n_envs = max(world, n_envs // world * world)
     rollout = max(1, -(-args.steps_per_iteration // n_envs))
     return n_envs, rollout
+
+
+def config_of(args, rollout):
+    """The PPOConfig of a training run: every flag that has a field."""
+    from . import ppo
+    return ppo.PPOConfig(rollout_len=rollout, max_episode_steps=args.timesteps_per_episode, policy=args.policy, seed=args.seed,
+                         save_freq=args.save_every_iterations, output_dir=args.output_dir, method_name=args.method_name,
+                         eval_every=args.eval_every, eval_episodes=args.eval_episodes, max_grad_norm=args.max_grad_norm,
+                         target_kl=args.target_kl, minibatch_size=args.minibatch_size, minibatch_shuffle=args.minibatch_shuffle)
 
 
 def main(argv=None):
@@ -118,10 +134,7 @@ def main(argv=None):
         sampler = (st, g, dmin, dmax)
     env = VecEnv(hi - lo, map=args.map, max_episode_steps=args.timesteps_per_episode, auto_reset=True, is_training=True,
                  seed=args.seed, env_id_base=lo, device=ctx.device, sampler=sampler, movers=movers)
-    cfg = ppo.PPOConfig(rollout_len=rollout, max_episode_steps=args.timesteps_per_episode, policy=args.policy, seed=args.seed,
-                        save_freq=args.save_every_iterations, output_dir=args.output_dir, method_name=args.method_name,
-                        eval_every=args.eval_every, eval_episodes=args.eval_episodes, max_grad_norm=args.max_grad_norm,
-                        target_kl=args.target_kl)
+    cfg = config_of(args, rollout)
     trainer = ppo.PPOTrainer(env, cfg, ctx)
     if args.resume or args.actor_model:  # main.py:52-89
         pa = args.actor_model or ev.find_latest_checkpoint(args.output_dir, args.method_name, "actor")

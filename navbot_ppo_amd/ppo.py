@@ -12,6 +12,8 @@ Follows ``project_ppo/src/ppo.py`` of the reference function by function, vector
                                     term, no value clip, no gradient clipping (PPOConfig.max_grad_norm
                                     turns on per-net clipping + a non-finite guard; the gradient-norm
                                     check of ppo.py:356-379,414-416 is PPOTrainer._grad_guard)
+                                    PPOConfig.minibatch_size: K optimiser steps per epoch on slices of the batch, shuffled
+                                    on the device (navppo_shuffle_batch; host mirror: batch_permutation)
   learn            ppo.py:218-461   iteration loop, timing, checkpoints (actor_iter%04d_step%08d.pth)
 
 Multi-GPU (absent in the reference): one process per GPU, each owns a contiguous shard
@@ -87,6 +89,14 @@ class PPOConfig:
     # exceeds 1.5 x target_kl; on one GPU the decision is taken on the device and the remaining queued epochs return at the entry of
     # every kernel (navppo_*_update_epoch_kl).  Not with overlap_allreduce (the per-net pipeline has no place for the decision).
     target_kl: float = None
+    # None, or a value >= the batch = the reference: every epoch is ONE optimiser step on the whole batch (ppo.py:237-240).  A positive
+    # multiple of 32 (per rank): an epoch is K = ceil(n / minibatch_size) steps on slices of the batch, the last one shorter if n is no
+    # multiple -- kept, not dropped; Adam's step counter, max_grad_norm and target_kl act per step.  Not with overlap_allreduce.
+    minibatch_size: int = None
+    # which samples a slice holds: "epoch" = a fresh permutation of the batch before every epoch (Stable-Baselines3, CleanRL), "update" =
+    # one permutation per update, reused by its epochs, "none" = contiguous slices of the batch as it lies ([T, N]: time slices), no copy.
+    # The permutations are batch_permutation(n, key(seed, rank), (update index, epoch index)): navppo_shuffle_batch on the device
+    minibatch_shuffle: str = "epoch"
     output_dir: str = ""                   # "" = no checkpoints / logs
     episode_csv_rows: int = 2000           # per-iteration cap on rows appended to <method>_train_episodes.csv (0 = off)
     tb_episode_rows: int = 256             # per-iteration cap on Episode_Rewards/train points in the TensorBoard file (0 = off)
@@ -96,6 +106,88 @@ class PPOConfig:
     # the reference's users quote (main.py:135-252), not that of the noisy training rollouts -- on a second set of envs
     eval_every: int = 0
     eval_episodes: int = 100
+
+    def __post_init__(self):
+        check_minibatch_config(self)
+
+
+# --------------------------------------------------------------------------- minibatch updates
+MINIBATCH_SHUFFLES = ("epoch", "update", "none")
+
+
+def check_minibatch_config(cfg):
+    """PPOConfig.minibatch_size / minibatch_shuffle, at the construction of the config and again of the updater (a config is mutable)."""
+    mb = cfg.minibatch_size
+    if mb is not None:
+        if isinstance(mb, bool) or not isinstance(mb, int) or mb < 32 or mb % 32:
+            raise ValueError(f"minibatch_size {mb!r}: None (full-batch epochs) or a positive multiple of 32")
+        if cfg.overlap_allreduce:
+            raise ValueError("minibatch_size with overlap_allreduce=True: the per-net pipeline runs whole-batch epochs only")
+    if cfg.minibatch_shuffle not in MINIBATCH_SHUFFLES:
+        raise ValueError(f"minibatch_shuffle {cfg.minibatch_shuffle!r}: one of {MINIBATCH_SHUFFLES}")
+
+
+_PHILOX_M0, _PHILOX_M1, _PHILOX_W0, _PHILOX_W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
+_M32, _M64 = 0xFFFFFFFF, 0xFFFFFFFFFFFFFFFF
+
+
+def _philox4x32_10(ctr, key):
+    """Philox4x32-10 of the kernels (csrc/mlp64_policy.h: philox10) on Python integers."""
+    c0, c1, c2, c3 = ctr
+    k0, k1 = key
+    for _ in range(10):
+        p0, p1 = _PHILOX_M0 * c0, _PHILOX_M1 * c2
+        c0, c1, c2, c3 = (p1 >> 32) ^ c1 ^ k0, p1 & _M32, (p0 >> 32) ^ c3 ^ k1, p0 & _M32
+        k0, k1 = (k0 + _PHILOX_W0) & _M32, (k1 + _PHILOX_W1) & _M32
+    return c0, c1, c2, c3
+
+
+def batch_permutation(n, key, counter):
+    """The permutation pi of navppo_shuffle_batch (include/navppo.h states it) as an int64 tensor on the CPU: out[i] = in[pi[i]].
+    A pure function of (n, key, counter): a 6-round Feistel network on ceil(log2 n) bits whose halves trade places and widths every
+    round, cycle-walked into [0, n); the round function is two of Philox's multiply-mix rounds, the round keys a Weyl sequence from
+    Philox4x32-10 over (counter, n) keyed by `key`.  The kernel matches it exactly (tests/test_gpu_minibatch.py)."""
+    import numpy as np
+    n, key, counter = int(n), int(key) & _M64, int(counter) & _M64
+    if not 1 <= n < 1 << 31:
+        raise ValueError(f"batch_permutation: n = {n} outside [1, 2^31)")
+    b = (n - 1).bit_length()
+    a = b // 2
+    c = b - a
+    o = _philox4x32_10((counter & _M32, counter >> 32, n, 0x73687566), (key & _M32, key >> 32))
+    u64 = np.uint64
+    m32, s32 = u64(_M32), u64(32)
+
+    def network(x):
+        wl, wr, k0, k1 = a, c, o[0], o[1]
+        for _ in range(6):
+            left, r = x >> u64(wr), x & u64((1 << wr) - 1)
+            p = u64(_PHILOX_M0) * ((r + u64(k0)) & m32)
+            t = (p >> s32) ^ (p & m32) ^ u64(k1)
+            q = u64(_PHILOX_M1) * t
+            f = (q >> s32) ^ (q & m32)
+            x = (r << u64(wl)) | (left ^ (f & u64((1 << wl) - 1)))
+            wl, wr = wr, wl
+            k0, k1 = (k0 + _PHILOX_W0) & _M32, (k1 + _PHILOX_W1) & _M32
+        return x
+
+    x = network(np.arange(n, dtype=u64))
+    while True:   # cycle walking: the network is a bijection of [0, 2^b), so every walk from an index < n comes back below n
+        walk = np.nonzero(x >= u64(n))[0]
+        if walk.size == 0:
+            break
+        x[walk] = network(x[walk])
+    return torch.from_numpy(x.astype(np.int64))
+
+
+def minibatch_key(seed, rank=0):
+    """`key` of an updater's permutations: PPOConfig.seed mixed with the global rank (every rank shuffles its own shard its own way)."""
+    return (int(seed) * 0x9E3779B97F4A7C15 + 0x6D6273 + int(rank) * 0xD1B54A32D192ED03) & _M64
+
+
+def minibatch_counter(update_index, epoch_index):
+    """`counter` of a permutation: (update index, epoch index) -- no two epochs of a run share one."""
+    return ((int(update_index) & _M32) << 32) | (int(epoch_index) & _M32)
 
 
 # --------------------------------------------------------------------------- distributed context
@@ -240,9 +332,11 @@ def normalise_advantages(adv, ctx=None):
 # What each of PPOUpdater's four epoch runners hands to _summarise.  k: the epochs whose passes ran = the rows the statistics are taken
 # over; steps, stopped: optimiser steps taken, whether target_kl stopped the update early (k = steps + stopped); losses: [n_ep, 2] per-epoch
 # (actor, critic) loss, NaN behind a stop; sums: [4] sums over the k epochs of (actor loss, critic loss, approx_kl, clip_frac); gn_sum, v_sum:
-# the same of the whole gradient's norm and the mean value; net_gn: [2] of the per-net norms, if the runner has them; net_gn_open: less the last's
+# the same of the whole gradient's norm and the mean value; net_gn: [2] of the per-net norms, if the runner has them; net_gn_open: less the last's.
+# Minibatches (K = slices per epoch > 1): k, steps and the sums count optimiser STEPS (K to an epoch); losses stays per epoch -- a row is
+# the mean over the steps of its epoch that ran, NaN where none did
 _Epochs = dataclasses.make_dataclass("_Epochs", ["k", "steps", "stopped", "losses", "sums", "gn_sum", "v_sum",
-                                                 ("net_gn", object, None), ("net_gn_open", bool, False)])
+                                                 ("net_gn", object, None), ("net_gn_open", bool, False), ("K", int, 1)])
 
 
 class PPOUpdater:
@@ -273,6 +367,11 @@ class PPOUpdater:
         if cfg.target_kl is not None and cfg.overlap_allreduce:
             raise ValueError("target_kl with overlap_allreduce=True: the per-net pipeline has no place for the stop decision")
         self.kl_limit = None if cfg.target_kl is None else 1.5 * float(cfg.target_kl)   # Stable-Baselines3's factor
+        check_minibatch_config(cfg)
+        self.update_index = 0    # updates run so far: the high word of the shuffle's counter
+        self._mb_key = minibatch_key(cfg.seed, ctx.rank if ctx is not None else 0)
+        self._mb = None          # the minibatch plan of the update in flight (_plan_minibatches); None = whole-batch epochs
+        self._shuf = self._shuf_key = None   # the ONE permuted copy of the batch (navppo_shuffle_batch's outputs), regrown like _prep
         # the clipped machinery runs and fills clip_stats: max_grad_norm, or target_kl alone -- at max_norm = +inf: the unclipped epochs' bits
         self._clipping = self.max_norm is not None or self.kl_limit is not None
         self.kl_state = None     # target_kl on, fused: [4] (stopped, steps taken, tripping approx_kl, its step) of the last update(), on the device
@@ -351,7 +450,11 @@ class PPOUpdater:
     def _batch_args(self, obs, acts, logp_old, rtg, adv, var):
         """(family, the arguments every *_loss_grad / *_update_epoch entry point of it takes between params_dev and the step's): the
         rows -- obs, or their prepared pieces -- then acts, logp_old, rtg, adv, n, var, clip."""
-        fam, rows = (("navppo_mlp64_bf16x3", (self._prepared(obs), self.obs_dim)) if self.bf16x3 else (self.fused, self._obs_args(obs)))
+        if self.bf16x3 and self._mb is not None:   # a slice of the prepared batch: whole tile blocks in front of it (start % 32 == 0)
+            rows = (_ptr(self._prep, self._mb["prep_off"]), self.obs_dim)
+        else:
+            rows = (self._prepared(obs), self.obs_dim) if self.bf16x3 else self._obs_args(obs)
+        fam = "navppo_mlp64_bf16x3" if self.bf16x3 else self.fused
         return fam, (*rows, _ptr(acts), _ptr(logp_old), _ptr(rtg), _ptr(adv), int(obs.shape[0]), float(var), float(self.cfg.clip))
 
     def _fused_loss_grad(self, obs, acts, logp_old, rtg, adv, var, stats=None):
@@ -481,6 +584,77 @@ class PPOUpdater:
                 return self._fused_value(obs)
             return self.critic(obs.float()).squeeze(-1)
 
+    # ---- minibatches (PPOConfig.minibatch_size): the plan of an update, the one permuted copy, the steps in order
+    def _plan_minibatches(self, n, multi):
+        """None = whole-batch epochs (minibatch_size None or >= n: today's launches, nothing else runs), else the plan of this update:
+        K slices of `size` samples per epoch (the last one shorter if n is no multiple), the shuffle mode, and -- bf16x3 -- the byte offset
+        of the current slice in the prepared buffer.  Several ranks: all must hold the same n (one collective), else every rank raises."""
+        cfg = self.cfg
+        check_minibatch_config(cfg)
+        if cfg.minibatch_size is None:
+            return None
+        if multi:
+            nn = torch.tensor([n, -n], dtype=torch.int64, device=self.device)
+            self.ctx.all_reduce_max(nn)
+            hi, lo = int(nn[0]), -int(nn[1])
+            if hi != lo:
+                raise ValueError(f"minibatch_size: every rank must hold the same number of samples, got between {lo} and {hi} (this rank: {n})")
+        if cfg.minibatch_size >= n:
+            return None
+        return dict(K=-(-n // cfg.minibatch_size), size=cfg.minibatch_size, n=n, mode=cfg.minibatch_shuffle, prep_off=0)
+
+    def _shuffled(self, batch, counter):
+        """`batch` gathered by batch_permutation(n, key, counter): always from the ORIGINAL batch into the one permuted copy.  Fused: one
+        navppo_shuffle_batch launch (gated by kl_state: behind an early stop it returns at its entry), then -- bf16x3 -- the split of the
+        permuted rows into the prepared buffer.  PyTorch: index_select by the host mirror."""
+        obs = batch[0]
+        n = int(obs.shape[0])
+        if not self.fused:
+            perm = batch_permutation(n, self._mb_key, counter).to(obs.device)
+            return tuple(t.index_select(0, perm) for t in batch)
+        key = (obs.dtype, obs.shape[1])
+        if self._shuf is None or self._shuf_key != key or self._shuf[1].shape[0] < n:
+            self._shuf = None
+            f32 = dict(dtype=torch.float32, device=self.device)
+            self._shuf = (torch.empty((n, obs.shape[1]), dtype=obs.dtype, device=self.device), torch.empty((n, 2), **f32),
+                          torch.empty(n, **f32), torch.empty(n, **f32), torch.empty(n, **f32))
+            self._shuf_key = key
+        out = tuple(t[:n] for t in self._shuf)
+        p, d, f16 = self._obs_args(obs)[:1] + (self.obs_dim, int(obs.dtype == torch.float16))
+        _navppo("navppo_shuffle_batch", p, d, f16, *(_ptr(t) for t in batch[1:]), n, self._mb_key, int(counter), *(_ptr(t) for t in out),
+                None if self.kl_state is None else _ptr(self.kl_state))
+        if self.bf16x3:
+            self.prepare(out[0])
+        return out
+
+    def _steps(self, n_ep, batch):
+        """Every optimiser step's batch of an update, in order: n_ep times the whole batch, or -- minibatches -- per epoch its K slices,
+        of the batch as it lies ("none") or of its permuted copy, drawn before every epoch ("epoch") or once ("update")."""
+        mb = self._mb
+        if mb is None:
+            for _ in range(n_ep):
+                yield batch
+            return
+        src = batch
+        for ep in range(n_ep):
+            if mb["mode"] == "epoch" or (mb["mode"] == "update" and ep == 0):
+                src = self._shuffled(batch, minibatch_counter(self.update_index, ep if mb["mode"] == "epoch" else 0))
+            for lo in range(0, mb["n"], mb["size"]):
+                if self.bf16x3:
+                    mb["prep_off"] = int(lib().navppo_mlp64_bf16x3_prep_bytes(lo, self.obs_dim))   # (0 samples: 0 bytes)
+                yield tuple(t[lo:lo + mb["size"]] for t in src)
+
+    def _epoch_losses(self, rows, k, n_ep):
+        """[n_ep, 2] per-epoch (actor, critic) losses from the first k rows of `rows`, one per step that ran: K = 1 the rows themselves;
+        else row e is the mean over the steps of epoch e that ran; NaN where none ran."""
+        K = self._mb["K"] if self._mb is not None else 1
+        if K == 1:
+            losses = rows[:k].clone()
+            return losses if k >= n_ep else torch.cat([losses, torch.full((n_ep - k, 2), math.nan, device=rows.device)])
+        ran = (torch.arange(n_ep * K, device=rows.device) < k).reshape(n_ep, K, 1)
+        r = torch.where(ran, rows[:n_ep * K].reshape(n_ep, K, 2), torch.zeros((), device=rows.device))
+        return r.sum(1) / ran.sum(1)   # (0 / 0: NaN)
+
     def _clip_row(self, ep, c):
         """This epoch's clip-statistics row from the gradient as it stands, coefficient c: 0 = the update stopped before this step, 1 = unclipped."""
         g_a, g_c = self.fp.grad[:self._n_actor], self.fp.grad[self._n_actor:]
@@ -491,41 +665,53 @@ class PPOUpdater:
         of _fhist.  gn_sum / net_gn: the runner's own sums of norms; the single-GPU epochs have none and take them from the rows."""
         if n_ep == 0:
             return r0
-        steps, stopped = n_ep, 0
+        K = self._mb["K"] if self._mb is not None else 1
+        n_st = n_ep * K   # optimiser steps queued: with minibatches every row below is a STEP's
+        steps, stopped = n_st, 0
         if self.kl_limit is not None:   # (the update synchronises for its statistics anyway)
             st = self.kl_state.tolist()
             steps, stopped = int(st[1]), int(st[0] != 0.0)
-            self._adam_t -= n_ep - steps   # Adam's bias correction counts steps TAKEN: every epoch's launch counted one
+            self._adam_t -= n_st - steps   # Adam's bias correction counts steps TAKEN: every step's launch counted one
         k = steps + stopped
         h = self._fhist[:k]
-        losses = h[:, 0:5:4].clone()   # columns 0 (actor loss) and 4 (critic loss)
-        if k < n_ep:
-            losses = torch.cat([losses, torch.full((n_ep - k, 2), math.nan, device=h.device)])
+        losses = self._epoch_losses(self._fhist[:, 0:5:4], k, n_ep)   # columns 0 (actor loss) and 4 (critic loss)
         gn_last = self.fp.grad.norm() / world   # multi-GPU: fp.grad holds the all-reduced SUM (the 1 / world scale is inside navppo_adam_step)
         own = gn_sum is not None
         if not own and not self._clipping:
             # every epoch's norms as the reference logs them (ppo.py:351-352, 389-390) without a norm launch per epoch: the fused epoch leaves
             # the squared per-net norms of the epoch BEFORE in columns 3 / 7 of its row (reduce_adam / resmlp_reduce), the last epoch's stand
-            if n_ep > 1:
-                prev = h[1:, 3:8:4].clone()   # [n_ep - 1, (actor, critic)]
+            # (minibatches: a row per step, the slots of the step before -- reduce_adam's lie at a fixed place of the workspace and its grid
+            # does not depend on n, so a shorter last slice and an epoch boundary change nothing; resmlp_reduce's lie BEHIND the per-sample
+            # part of the workspace and move with n: _run_fused_single takes that family's norms itself when the slices are not all equal)
+            if n_st > 1:
+                prev = h[1:, 3:8:4].clone()   # [n_st - 1, (actor, critic)]
                 gn_sum, net_gn = prev.sum(1).sqrt().sum() + gn_last, prev.sqrt().sum(0)
             else:
-                gn_sum = gn_last * n_ep
+                gn_sum = gn_last * n_st
         return _Epochs(k=k, steps=steps, stopped=stopped, losses=losses, sums=h.sum(0)[[0, 4, 1, 2]], gn_sum=gn_sum, v_sum=V0.mean() * k,
-                       net_gn=net_gn, net_gn_open=not own)
+                       net_gn=net_gn, net_gn_open=not own, K=K)
 
     def _run_fused_single(self, n_ep, batch, var_f, V0, multi, world, r0):
         """One GPU: _fused_epoch.  Per-epoch diagnostics land in row ep of a device buffer: no extra launches inside the epoch loop."""
-        for ep in range(n_ep):
-            self._fused_epoch(*batch, var_f, self._fhist[ep], self.clip_stats[ep] if self._clipping else None)
-        return self._fused_record(n_ep, V0, world, r0)
+        # gn (resmlp512 on slices of two lengths, no clip statistics): every step's per-net norms by two small launches -- the slot of
+        # the step before is read at the wrong place when n changes between two calls (the shorter last slice, the epoch boundary)
+        mb, n_a = self._mb, self._n_actor
+        gn = (torch.zeros((n_ep * mb["K"], 2), device=self.device)
+              if mb is not None and self.fused_resmlp512 and not self._clipping and mb["n"] % mb["size"] else None)
+        for st, sl in enumerate(self._steps(n_ep, batch)):
+            self._fused_epoch(*sl, var_f, self._fhist[st], self.clip_stats[st] if self._clipping else None)
+            if gn is not None:
+                gn[st] = torch.stack(torch._foreach_norm([self.fp.grad[:n_a], self.fp.grad[n_a:]]))
+        return self._fused_record(n_ep, V0, world, r0, *((gn.pow(2).sum(1).sqrt().sum(), gn.sum(0)) if gn is not None and n_ep > 0 else ()))
 
     def _run_fused_multi(self, n_ep, batch, var_f, V0, multi, world, r0):
         """Several GPUs: fused passes -> ONE all-reduce of the flat gradient (RCCL) -> scale + Adam in one launch."""
-        ctx, n_a, n, gn = self.ctx, self._n_actor, float(batch[0].shape[0]), None   # gn: epoch sums of the MEAN gradient's (actor, critic, whole) norm
-        kl_glob = torch.zeros((max(n_ep, 1), 2), dtype=torch.float32, device=self.device) if self.kl_limit is not None else None
-        for ep in range(n_ep):
-            self._fused_loss_grad(*batch, var_f, stats=self._fhist[ep])
+        ctx, n_a, gn = self.ctx, self._n_actor, None   # gn: step sums of the MEAN gradient's (actor, critic, whole) norm
+        n_st = n_ep * (self._mb["K"] if self._mb is not None else 1)
+        kl_glob = torch.zeros((max(n_st, 1), 2), dtype=torch.float32, device=self.device) if self.kl_limit is not None else None
+        for ep, sl in enumerate(self._steps(n_ep, batch)):   # (ep: the step -- an epoch, or a slice of one)
+            n = float(sl[0].shape[0])
+            self._fused_loss_grad(*sl, var_f, stats=self._fhist[ep])
             ctx.all_reduce_sum(self.fp.grad)
             if self.kl_limit is not None:
                 # the global approx_kl = sum(kl_r n_r) / sum(n_r), a 2-float collective; the passes are ungated: a stop only keeps the weights
@@ -550,10 +736,10 @@ class PPOUpdater:
 
     def _run_pytorch(self, n_ep, batch, var, V0, multi, world, r0):
         """CPU, gloo, and resmlp512 with update_arith="f32": ppo.py:305-392 in PyTorch."""
-        obs, acts, logp_old, rtg, adv = batch
-        steps, stopped, losses = n_ep, 0, r0.losses
-        acc, net_gn = torch.zeros(6, device=obs.device), None  # sums over epochs of the diagnostics and of the per-net gradient norms
-        for ep in range(n_ep):                                 # ppo.py:305
+        K = self._mb["K"] if self._mb is not None else 1
+        steps, stopped, losses = n_ep * K, 0, torch.zeros((n_ep * K, 2), device=batch[0].device)   # (a row per step)
+        acc, net_gn = torch.zeros(6, device=batch[0].device), None  # sums over steps of the diagnostics and of the per-net gradient norms
+        for ep, (obs, acts, logp_old, rtg, adv) in enumerate(self._steps(n_ep, batch)):   # ppo.py:305 (ep: the step -- an epoch, or a slice of one)
             a_loss, c_loss, ratios, logp, _ = ppo_losses(self.actor, self.critic, obs, acts, logp_old, rtg, adv, var, self.cfg.clip)
             self.fp.grad.zero_()
             (a_loss + c_loss).backward()                       # disjoint nets: same grads as the two backward()s of :349,:386
@@ -569,7 +755,6 @@ class PPOUpdater:
             if trip:   # neither net is stepped; the gradient stays unclipped, the coefficients are reported as 0, the remaining epochs do not run
                 steps, stopped = ep, 1
                 self._clip_row(ep, 0.0)
-                losses[ep + 1:] = math.nan
             elif self.max_norm is not None:
                 self._clip_and_step(ep)
             else:
@@ -584,7 +769,8 @@ class PPOUpdater:
                 net_gn = g2 if net_gn is None else net_gn + g2
             if trip:
                 break
-        return _Epochs(k=steps + stopped, steps=steps, stopped=stopped, losses=losses, sums=acc[:4], gn_sum=acc[4], v_sum=acc[5], net_gn=net_gn)
+        return _Epochs(k=steps + stopped, steps=steps, stopped=stopped, losses=self._epoch_losses(losses, steps + stopped, n_ep), sums=acc[:4],
+                       gn_sum=acc[4], v_sum=acc[5], net_gn=net_gn, K=K)
 
     def _summarise(self, r, flat_before, multi, world):
         """The record of the epochs that ran -> the stats dict.  Gradient norms are means over the r.k epochs, from the first source
@@ -621,7 +807,10 @@ class PPOUpdater:
         vals = [float(v) for v in torch.cat([acc, extra] + (clip_cols if self.max_norm is not None else [])).tolist()]
         stats = dict(zip(keys, vals[:12] + [int(v) for v in vals[12:]]))
         if self.kl_limit is not None:   # steps taken (n_ep if the update never stopped) and whether it stopped; identical on every rank
-            stats["kl_stop_epoch"], stats["kl_stopped"] = r.steps, r.stopped
+            # (minibatches: kl_stop_step counts the steps, kl_stop_epoch the whole epochs completed)
+            stats["kl_stop_epoch"], stats["kl_stopped"] = r.steps // r.K, r.stopped
+            if r.K > 1:
+                stats["kl_stop_step"] = r.steps
         return stats
 
     def update(self, obs, acts, logp_old, rtg, var, adv_raw=None, V0=None):
@@ -639,23 +828,31 @@ class PPOUpdater:
         if not (self.fused and obs.dtype == torch.float16):
             obs = obs.float()   # half rows (obs_f16 envs) are consumed as they are by the fused kernels only
         batch = (obs, acts, logp_old, rtg, adv)
+        self._mb = self._plan_minibatches(int(obs.shape[0]), multi)
+        n_st = n_ep * (self._mb["K"] if self._mb is not None else 1)   # optimiser steps: a row of every per-step buffer each
+        shuffling = self._mb is not None and self._mb["mode"] != "none"
         if self.fused:
             batch = tuple(t.contiguous() for t in batch)
-            if self.bf16x3 and n_ep > 0:
+            if self.bf16x3 and n_ep > 0 and not shuffling:   # (shuffling: the permuted copy is prepared behind every shuffle instead)
                 self.prepare(batch[0])   # ALWAYS here: the rollout kernels fill the buffer behind torch's back (no version bump)
-            if self._fhist.shape[0] < n_ep:
-                self._fhist = torch.zeros((n_ep, 8), dtype=torch.float32, device=self.device)
+            if self._fhist.shape[0] < n_st:
+                self._fhist = torch.zeros((n_st, 8), dtype=torch.float32, device=self.device)
             if self.kl_limit is not None:   # zeroed once per update; afterwards only the library writes it
                 self.kl_state = torch.zeros(4, dtype=torch.float32, device=obs.device)
-        if self._clipping:   # every epoch's (s_actor, s_critic, coef_actor, coef_critic): filled on the device, read once after the epochs
-            self.clip_stats = torch.zeros((max(n_ep, 1), 4), dtype=torch.float32, device=obs.device)
+        if self._clipping:   # every step's (s_actor, s_critic, coef_actor, coef_critic): filled on the device, read once after the epochs
+            self.clip_stats = torch.zeros((max(n_st, 1), 4), dtype=torch.float32, device=obs.device)
         self._last_adv = batch[4]   # (PPOTrainer._grad_guard's diagnostics)
         runner = (self._run_pytorch if not self.fused else self._run_fused_single if not multi else
                   self._run_fused_pipelined if self.fused_mlp64 and cfg.overlap_allreduce else self._run_fused_multi)
-        run = runner(n_ep, batch, float(var) if self.fused else var, V0, multi, world, r0)
-        self.stats = self._summarise(run, flat_before, multi, world)
+        try:
+            run = runner(n_ep, batch, float(var) if self.fused else var, V0, multi, world, r0)
+            self.stats = self._summarise(run, flat_before, multi, world)
+        finally:   # (the plan belongs to this update: _batch_args of a later call on a whole batch must not see it)
+            self._mb = None
+            self.update_index += 1
         self.loss_history = run.losses   # per-epoch (actor, critic) loss, ppo.py:396-397; NaN rows behind an early stop
-        self.last_losses = (run.losses[run.k - 1, 0].detach(), run.losses[run.k - 1, 1].detach()) if run.k else (zero, zero)
+        last = (run.k - 1) // run.K      # the last epoch a step of which ran
+        self.last_losses = (run.losses[last, 0].detach(), run.losses[last, 1].detach()) if run.k else (zero, zero)
         return self.stats
 
 
@@ -1067,6 +1264,7 @@ class PPOTrainer:
                 "ppo/grad_clip_frac_actor": lg.get("grad_clip_frac_actor"), "ppo/grad_clip_frac_critic": lg.get("grad_clip_frac_critic"),
                 "ppo/skipped_steps_actor": lg.get("skipped_steps_actor"), "ppo/skipped_steps_critic": lg.get("skipped_steps_critic"),
                 "ppo/kl_stop_epoch": lg.get("kl_stop_epoch"), "ppo/kl_stopped": lg.get("kl_stopped"),   # (target_kl set)
+                **({"ppo/kl_stop_step": lg["kl_stop_step"]} if "kl_stop_step" in lg else {}),           # (target_kl and minibatches)
                 **({"eval/success_rate": lg["eval_success"], "eval/collision_rate": lg["eval_collision"],
                     "eval/timeout_rate": lg["eval_timeout"], "eval/mean_return": lg["eval_return"],
                     "eval/mean_ep_length": lg["eval_length"], "time/eval": lg["eval_time"]} if "eval_success" in lg else {})}
@@ -1120,6 +1318,7 @@ class PPOTrainer:
                     f"c_loss={lg['critic_loss']:.2f} kl={lg['approx_kl']:.4f} steps/s={lg['steps_per_sec']:.0f} "
                     f"(rollout {lg['rollout_time']:.3f}s update {lg['update_time']:.3f}s)"
                     + (f" kl_stop_epoch={lg['kl_stop_epoch']} kl_stopped={lg['kl_stopped']}" if "kl_stop_epoch" in lg else "")
+                    + (f" kl_stop_step={lg['kl_stop_step']}" if "kl_stop_step" in lg else "")
                     + (f" eval: succ={lg['eval_success']:.3f} coll={lg['eval_collision']:.3f} tmo={lg['eval_timeout']:.3f} "
                        f"ret={lg['eval_return']:.2f} len={lg['eval_length']:.1f} ({lg['eval_time']:.3f}s)"
                        if "eval_success" in lg else ""))
