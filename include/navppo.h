@@ -250,6 +250,43 @@ int navppo_shuffle_batch(const void* obs_dev, int32_t obs_dim /* 16 | 42 */, int
                          const float* rtg_dev, const float* adv_dev, int64_t n_samples, uint64_t key, uint64_t counter, void* obs_out,
                          float* act_out, float* logp_out, float* rtg_out, float* adv_out, const float* gate_dev, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------------
+ * Reward normalisation by a running variance of the discounted return (Stable-Baselines3's VecNormalize(norm_reward=True)): two entry
+ * points that run IN FRONT of the return scan on the [T, N] buffers a rollout fills.  Both are asynchronous on `stream`, make no host
+ * round trip and no device synchronisation, read nothing from the process environment and check their arguments before any HIP call
+ * (-1 and nothing launched; message in navppo_last_error()).  float64 statistics throughout; navbot_ppo_amd.ppo.reward_norm_reference
+ * is the host mirror of both.
+ *
+ * navppo_return_moments: per env column i the forward discounted return, in float64 --
+ *     R = carry[i] (0 when carry_dev is NULL);  for t = 0 .. T - 1:  R = gamma R + rew[t, i];  R joins the batch;  R = 0 where ended[t, i]
+ * -- afterwards carry[i] = R (if given: a rollout that continues passes the same buffer to its next call) and
+ *     moments_dev [3] f64 = (n, mean, M2) of the T N values of R:  n = T N,  M2 = sum of (R - mean)^2
+ * The column is split over T (chunks of 32 rows composed through float64 carries, as navsim_rtg_scan), so a value may differ from the
+ * serial recurrence in its last float64 bits; the moments are combined with Chan's pairwise formula along one fixed tree (threads,
+ * then workgroups, in index order; no floating-point atomics): the same input gives the same bits.
+ *   rew_dev [T, N] f32   ended_dev [T, N] u8 (the layout navsim_rtg_scan takes)   carry_dev [N] f64, nullable, in / out
+ * Refused: a null pointer (carry_dev aside), T < 1, N < 1, gamma outside [0, 1] (NaN included), rew_dev not 4-byte or
+ * moments_dev / carry_dev not 8-byte aligned.  The workgroups' partial results pass through storage the library owns, one copy per
+ * device: calls on ONE device must be ordered with each other (one stream, or streams that wait for each other).
+ *
+ * navppo_reward_scale: first merges rows k = 0 .. K - 1 of moments_dev [K, 3] f64 (each as navppo_return_moments writes it; K = 1 on
+ * one GPU, one row per rank in rank order on several -- every rank then holds the same bits), in order, into the running statistics
+ *   rms_dev [4] f64 = (mean, var, count, scale), in / out       (a fresh run: 0, 1, 1e-4, anything -- RunningMeanStd's start)
+ *     d = bm - mean;  tot = count + bn;  mean += d bn / tot;  var = (var count + bM2 + d^2 count bn / tot) / tot;  count = tot
+ * (a row with bn <= 0 or a non-finite bn, bm or bM2 is skipped and leaves the statistics as they are: one bad batch must not poison
+ * them for good), then stores scale = 1 / sqrt(var + eps) to rms_dev[3] and writes
+ *     rew_out[i] = clamp(float32(double(rew_in[i]) * scale), -clip, clip),  0 <= i < n          (a NaN reward stays NaN)
+ * K = 0 scales with the statistics as they stand; n = 0 only merges; rew_out_dev may be rew_in_dev.  The bound is float32(clip).
+ * Refused: rms_dev null, moments_dev null with K > 0, a reward pointer null with n > 0, K < 0, n < 0, eps negative or not finite,
+ * clip not positive (+inf allowed), rms_dev / moments_dev not 8-byte or a reward pointer not 4-byte aligned.
+ * Deviation from VecNormalize: it normalises step t with the statistics after step t; here the statistics take all T N returns of a
+ * rollout at once and then scale the whole rollout.  The statistics after the rollout are the same (tests/test_reward_norm_cpu.py).
+ */
+int navppo_return_moments(const float* rew_dev, const uint8_t* ended_dev, int32_t T, int32_t N, double gamma, double* carry_dev,
+                          double* moments_dev, void* stream);
+int navppo_reward_scale(double* rms_dev, const double* moments_dev, int32_t K, const float* rew_in_dev, float* rew_out_dev, int64_t n,
+                        double eps, double clip, void* stream);
+
 /*
  * PPO.get_action() (ppo.py:673-706) for all envs of a shard in one launch: mean = actor(obs) (net_actor forward),
  * sample MVN(mean, var*I), clamp a0 to [0,1] and a1 to [-1,1] (ppo.py:700-703), log-prob of the CLAMPED action (:704).

@@ -105,6 +105,8 @@ SYMBOLS = [
      [_vp, _vp, _i32] + [_vp] * 4 + [C.c_int64] + [C.c_float] * 6 + [_i32] + [_vp] * 5 + [C.c_float, _vp, C.c_float, _vp, _vp]),
     ("navppo_adam_step_kl", C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_int64] + [C.c_float] * 6 + [_i32, _vp, C.c_float, _vp, _vp, _vp]),
     ("navppo_shuffle_batch", C.c_int, [_vp, _i32, _i32] + [_vp] * 4 + [C.c_int64, C.c_uint64, C.c_uint64] + [_vp] * 7),
+    ("navppo_return_moments", C.c_int, [_vp, _vp, _i32, _i32, _d, _vp, _vp, _vp]),
+    ("navppo_reward_scale", C.c_int, [_vp, _vp, _i32, _vp, _vp, C.c_int64, _d, _d, _vp]),
     ("navppo_resmlp512_value", C.c_int, [_vp, _vp, _i32, C.c_int64, _vp, _vp, _vp]),
     ("navppo_resmlp512_act", C.c_int, [_vp, _vp, _i32, _vp, C.c_int64, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint32, _vp, _vp, _vp, _vp]),
 ]

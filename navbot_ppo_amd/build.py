@@ -8,7 +8,8 @@ REPO = os.path.dirname(HERE)
 # ppo_*_kl.hip: the gated twins of the update's kernels (target_kl) -- each INCLUDES its partner source and compiles it a second time
 # (csrc/navppo_internal.h, NAVPPO_KL_TU), in a translation unit of its own so that the ungated kernels' listings stay what they were
 SRCS = [os.path.join(HERE, "csrc", f) for f in ("navsim.hip", "ppo_mlp64.hip", "ppo_resmlp512.hip", "ppo_mlp64_kl.hip", "ppo_resmlp512_kl.hip",
-                                                   "ppo_shuffle.hip")]   # ppo_shuffle.hip: navppo_shuffle_batch (minibatch updates)
+                                                   "ppo_shuffle.hip",    # ppo_shuffle.hip: navppo_shuffle_batch (minibatch updates)
+                                                   "ppo_reward_norm.hip")]   # navppo_return_moments, navppo_reward_scale (norm_reward)
 HDRS = ["navsim.h", "navppo.h"]
 INC = os.path.join(REPO, "include")
 LIB = os.path.join(HERE, "libnavsim.so")

@@ -14,7 +14,8 @@ Additions (not in the reference): --n_envs, --policy, --map, --seed, --eval_pers
 stepping loop), --eval_every K (training: a persistent evaluation of --eval_episodes episodes every K iterations), --max_grad_norm
 (per-net gradient clipping + non-finite guard inside the update), --target_kl (stop an update's remaining epochs once approx_kl
 exceeds 1.5 x the target), --minibatch_size M / --minibatch_shuffle MODE (K = ceil(batch / M) optimiser steps per epoch on slices of the
-batch, shuffled on the device), --movers NAME / --movers_period P (moving obstacles beside the static map, training and evaluation).  Vision flags are accepted and refused (the camera
+batch, shuffled on the device), --norm_reward / --clip_reward C (rewards scaled by the running standard deviation of the discounted
+return and clipped to +-C before the return scan), --movers NAME / --movers_period P (moving obstacles beside the static map, training and evaluation).  Vision flags are accepted and refused (the camera
 modality is outside the LiDAR hot path); --mode test maps to --eval (the reference's test path is broken).
 """
 import argparse
@@ -63,6 +64,10 @@ def get_args(argv=None):
     p.add_argument("--minibatch_shuffle", type=str, default="epoch", choices=["epoch", "update", "none"],
                    help="with --minibatch_size: a fresh device-side permutation of the batch before every epoch (epoch), one per update "
                         "(update), or contiguous slices of the batch as it lies (none)")
+    p.add_argument("--norm_reward", action="store_true", default=False,
+                   help="divide every rollout's rewards by the running standard deviation of the discounted return before the return "
+                        "scan (VecNormalize's norm_reward, on the device); metrics and CSVs stay raw; default: off, as in the reference")
+    p.add_argument("--clip_reward", type=float, default=10.0, help="with --norm_reward: the scaled rewards are clipped to +- this")
     p.add_argument("--movers", type=str, default=None,
                    help="moving obstacles cast beside the static map (maps.movers_by_name: orbit4 = four pillars orbiting the spawn "
                         "pose); authored geometry: parity unpinned (no reference geometry); default: none")
@@ -96,7 +101,8 @@ def config_of(args, rollout):
     return ppo.PPOConfig(rollout_len=rollout, max_episode_steps=args.timesteps_per_episode, policy=args.policy, seed=args.seed,
                          save_freq=args.save_every_iterations, output_dir=args.output_dir, method_name=args.method_name,
                          eval_every=args.eval_every, eval_episodes=args.eval_episodes, max_grad_norm=args.max_grad_norm,
-                         target_kl=args.target_kl, minibatch_size=args.minibatch_size, minibatch_shuffle=args.minibatch_shuffle)
+                         target_kl=args.target_kl, minibatch_size=args.minibatch_size, minibatch_shuffle=args.minibatch_shuffle,
+                         norm_reward=args.norm_reward, clip_reward=args.clip_reward)
 
 
 def main(argv=None):

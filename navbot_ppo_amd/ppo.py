@@ -97,6 +97,13 @@ class PPOConfig:
     # one permutation per update, reused by its epochs, "none" = contiguous slices of the batch as it lies ([T, N]: time slices), no copy.
     # The permutations are batch_permutation(n, key(seed, rank), (update index, epoch index)): navppo_shuffle_batch on the device
     minibatch_shuffle: str = "epoch"
+    # False = the reference: the critic regresses on raw returns (hundreds, at this simulator's rewards).  True: every rollout's rewards
+    # are divided by the running standard deviation of the discounted return and clipped to +-clip_reward before the return scan
+    # (Stable-Baselines3's VecNormalize(norm_reward=True); navppo_return_moments + navppo_reward_scale on the device, host mirror:
+    # reward_norm_reference).  The critic then learns in scaled units; episode returns, metrics and CSVs stay raw.
+    norm_reward: bool = False
+    clip_reward: float = 10.0              # VecNormalize's clip_reward
+    norm_reward_eps: float = 1e-8          # VecNormalize's epsilon: scale = 1 / sqrt(var + eps)
     output_dir: str = ""                   # "" = no checkpoints / logs
     episode_csv_rows: int = 2000           # per-iteration cap on rows appended to <method>_train_episodes.csv (0 = off)
     tb_episode_rows: int = 256             # per-iteration cap on Episode_Rewards/train points in the TensorBoard file (0 = off)
@@ -109,6 +116,7 @@ class PPOConfig:
 
     def __post_init__(self):
         check_minibatch_config(self)
+        check_reward_norm_config(self)
 
 
 # --------------------------------------------------------------------------- minibatch updates
@@ -188,6 +196,109 @@ def minibatch_key(seed, rank=0):
 def minibatch_counter(update_index, epoch_index):
     """`counter` of a permutation: (update index, epoch index) -- no two epochs of a run share one."""
     return ((int(update_index) & _M32) << 32) | (int(epoch_index) & _M32)
+
+
+# --------------------------------------------------------------------------- reward normalisation
+RET_RMS_INIT = (0.0, 1.0, 1e-4)   # (mean, var, count) of a fresh run: Stable-Baselines3's RunningMeanStd(epsilon=1e-4)
+
+
+def check_reward_norm_config(cfg):
+    """PPOConfig.norm_reward / clip_reward / norm_reward_eps, at the construction of the config and again of the trainer."""
+    c, e = cfg.clip_reward, cfg.norm_reward_eps
+    if isinstance(c, bool) or not isinstance(c, (int, float)) or not c > 0:
+        raise ValueError(f"clip_reward {c!r}: a number > 0")
+    if isinstance(e, bool) or not isinstance(e, (int, float)) or not (0 <= e < math.inf):
+        raise ValueError(f"norm_reward_eps {e!r}: a finite number >= 0")
+
+
+def _chk_rewards(what, rew, ended=None):
+    from ._native import NavsimError
+    if not rew.is_cuda:
+        raise NavsimError(f"{what} needs device tensors; there is no CPU path")
+    assert rew.dtype == torch.float32 and rew.is_contiguous(), f"{what}: rewards are contiguous float32"
+    if ended is not None:
+        assert rew.dim() == 2 and ended.dtype == torch.uint8 and ended.shape == rew.shape and ended.is_contiguous() and ended.device == rew.device
+
+
+def _chk_f64(what, t, shape, device):
+    assert t.dtype == torch.float64 and tuple(t.shape) == tuple(shape) and t.is_contiguous() and t.device == device, \
+        f"{what}: a contiguous float64 tensor of shape {tuple(shape)} on {device}"
+
+
+def return_moments(rew, ended, gamma, carry=None, out=None):
+    """(n, mean, M2) of the T N forward discounted returns of a [T, N] rollout, as a float64 [3] device tensor (navppo_return_moments;
+    `out`: where to write it).  carry: float64 [N], the running return in front of row 0 on entry and behind row T - 1 on return
+    (None: every column starts at 0).  Asynchronous on the current stream; calls on one device must not overlap in time."""
+    _chk_rewards("return_moments", rew, ended)
+    T, N = rew.shape
+    if out is None:
+        out = torch.empty(3, dtype=torch.float64, device=rew.device)
+    _chk_f64("return_moments: out", out, (3,), rew.device)
+    if carry is not None:
+        _chk_f64("return_moments: carry", carry, (N,), rew.device)
+    with torch.cuda.device(rew.device):
+        _navppo("navppo_return_moments", _ptr(rew), _ptr(ended), T, N, float(gamma), None if carry is None else _ptr(carry), _ptr(out))
+    return out
+
+
+def reward_scale(rms, moments, rew, clip=10.0, eps=1e-8, out=None):
+    """Merges the rows of `moments` ([K, 3] or [3] float64, None = no row: frozen statistics) into rms = (mean, var, count, scale)
+    (float64 [4], updated in place) and returns clamp(float32(rew * scale), -clip, clip) with scale = 1 / sqrt(var + eps)
+    (navppo_reward_scale).  out: where to write the scaled rewards (may be `rew`).  Asynchronous on the current stream."""
+    _chk_rewards("reward_scale", rew)
+    _chk_f64("reward_scale: rms", rms, (4,), rew.device)
+    K = 0
+    if moments is not None:
+        K = 1 if moments.dim() == 1 else int(moments.shape[0])
+        _chk_f64("reward_scale: moments", moments, (3,) if moments.dim() == 1 else (K, 3), rew.device)
+    if out is None:
+        out = torch.empty_like(rew)
+    assert out.dtype == torch.float32 and out.shape == rew.shape and out.is_contiguous() and out.device == rew.device
+    with torch.cuda.device(rew.device):
+        _navppo("navppo_reward_scale", _ptr(rms), None if K == 0 else _ptr(moments), K, _ptr(rew), _ptr(out), rew.numel(), float(eps),
+                float(clip))
+    return out
+
+
+def merge_return_moments(rms, rows):
+    """The merge rule of navppo_reward_scale on the host, float64: rms = (mean, var, count[, ...]), rows [K, 3] = (n, mean, M2) per
+    batch, merged in order with the formula of RunningMeanStd.update_from_moments; a row with n <= 0 or a non-finite entry is skipped.
+    Returns (mean, var, count) as a numpy array."""
+    import numpy as np
+    mean, var, count = (np.float64(v) for v in list(rms)[:3])
+    for bn, bm, bm2 in np.asarray(rows, dtype=np.float64).reshape(-1, 3):
+        if not (bn > 0 and np.isfinite(bn) and np.isfinite(bm) and np.isfinite(bm2)):
+            continue
+        d, tot = bm - mean, count + bn
+        mean = mean + d * bn / tot
+        var = (var * count + bm2 + d * d * count * bn / tot) / tot
+        count = tot
+    return np.array([mean, var, count], dtype=np.float64)
+
+
+def reward_norm_reference(rew, ended, gamma, rms=RET_RMS_INIT, carry=None, clip=10.0, eps=1e-8):
+    """Host mirror of navppo_return_moments followed by navppo_reward_scale(K = 1), numpy float64 -- the statement of the rule.
+    rew [T, N] float32, ended [T, N] (non-zero = an episode ended on that row), rms = (mean, var, count) before the rollout,
+    carry [N] float64 or None.  Returns a namespace: moments (n, mean, M2) of the T N running returns, carry [N] behind the last row,
+    rms (mean, var, count, scale) after the merge, out [T, N] float32 = clip(float32(rew * scale), -clip, clip)."""
+    import types
+    import numpy as np
+    rew = np.ascontiguousarray(np.asarray(rew, dtype=np.float32))
+    done = np.asarray(ended) != 0
+    T, N = rew.shape
+    R = np.zeros(N, dtype=np.float64) if carry is None else np.array(carry, dtype=np.float64)
+    g = np.float64(gamma)
+    rets = np.empty((T, N), dtype=np.float64)
+    for t in range(T):
+        R = g * R + rew[t].astype(np.float64)
+        rets[t] = R
+        R = np.where(done[t], 0.0, R)
+    mean = rets.mean()
+    moments = np.array([float(T * N), mean, ((rets - mean) ** 2).sum()], dtype=np.float64)
+    m = merge_return_moments(rms, moments)
+    scale = np.float64(1.0) / np.sqrt(m[1] + np.float64(eps))
+    out = np.clip((rew.astype(np.float64) * scale).astype(np.float32), np.float32(-clip), np.float32(clip))
+    return types.SimpleNamespace(moments=moments, carry=R, rms=np.append(m, scale), out=out)
 
 
 # --------------------------------------------------------------------------- distributed context
@@ -842,6 +953,8 @@ class PPOUpdater:
         if self._clipping:   # every step's (s_actor, s_critic, coef_actor, coef_critic): filled on the device, read once after the epochs
             self.clip_stats = torch.zeros((max(n_st, 1), 4), dtype=torch.float32, device=obs.device)
         self._last_adv = batch[4]   # (PPOTrainer._grad_guard's diagnostics)
+        if cfg.norm_reward:
+            self._last_V0 = V0      # (the trainer's explained_variance: the critic before this update)
         runner = (self._run_pytorch if not self.fused else self._run_fused_single if not multi else
                   self._run_fused_pipelined if self.fused_mlp64 and cfg.overlap_allreduce else self._run_fused_multi)
         try:
@@ -889,6 +1002,11 @@ class PPOTrainer:
         self.eplen_buf = torch.zeros((T, N), dtype=torch.int32, device=dev)
         self.eppath_buf = torch.zeros((T, N), dtype=f32, device=dev)
         self.rtg_buf = torch.zeros((T, N), dtype=f32, device=dev)
+        check_reward_norm_config(cfg)
+        if cfg.norm_reward:   # (off: not one tensor, launch or read-back more than before)
+            self._init_ret_rms(dev)
+            self.rew_scaled_buf = torch.zeros((T, N), dtype=f32, device=dev)   # what the scans read; rew_buf keeps the raw rewards
+            self._ret_rows = torch.zeros((ctx.world if ctx is not None else 1, 3), dtype=torch.float64, device=dev)   # one row per rank
         self.var = torch.full((), cfg.init_var, dtype=f32, device=dev)  # ppo.py:123-124 (0.8 * I)
         self.var_host = float(cfg.init_var)   # host mirror, refreshed at every rollout start
         self._lo = torch.tensor([0.0, -1.0], device=dev)
@@ -902,6 +1020,35 @@ class PPOTrainer:
         self.i_so_far = 0
         self.episode_starts = 0
         self.logger = {}
+
+    # ---- PPOConfig.norm_reward: the running statistics of the discounted return and the scaled copy of a rollout's rewards
+    def _init_ret_rms(self, device, mean=RET_RMS_INIT[0], var=RET_RMS_INIT[1], count=RET_RMS_INIT[2]):
+        """ret_rms = (mean, var, count, scale), float64 on the device; a fresh run starts like RunningMeanStd (0, 1, 1e-4)."""
+        mean, var, count = float(mean), float(var), float(count)
+        self.ret_rms = torch.tensor([mean, var, count, 1.0 / math.sqrt(var + self.cfg.norm_reward_eps)], dtype=torch.float64, device=device)
+
+    def _normalise_rewards(self):
+        """Behind the rollout, in front of the return scan: this rank's (n, mean, M2) of the rollout's running returns (carry-in 0:
+        every rollout starts from a reset), every rank's row gathered by ONE all-reduce of a zero-filled [world, 3] tensor (adding
+        zeros is exact), all rows merged in rank order on every rank -- bit-identical statistics -- and the rollout scaled by them.
+        Two entry points, no host round trip."""
+        cfg, ctx = self.cfg, self.ctx
+        rows = self._ret_rows
+        multi = ctx is not None and ctx.enabled
+        if multi and rows.shape[0] > 1:
+            rows.zero_()
+        return_moments(self.rew_buf, self.ended_buf, cfg.gamma, out=rows[ctx.rank if ctx is not None else 0])
+        if multi:
+            ctx.all_reduce_sum(rows)
+        return reward_scale(self.ret_rms, rows, self.rew_buf, clip=cfg.clip_reward, eps=cfg.norm_reward_eps, out=self.rew_scaled_buf)
+
+    def _reward_norm_figures_dev(self):
+        """(mean, var, count, scale, explained variance) as one float64 device tensor, queued behind the update and read with the
+        iteration's one read-back.  explained_variance = 1 - Var(target - V0) / Var(target) over this rank's samples, V0 the critic
+        before the update: scale-free, unlike critic_loss, whose units change with the option."""
+        tgt, v0 = self.rtg_buf.reshape(-1).double(), self.updater._last_V0.reshape(-1).double()
+        ev = 1.0 - (tgt - v0).var(unbiased=False) / tgt.var(unbiased=False)
+        return torch.cat([self.ret_rms, ev.reshape(1)])
 
     def _fused_act(self, t, noise=None):
         """PPO.get_action for all envs in ONE launch (csrc/ppo_mlp64.hip: mlp64_act, csrc/ppo_resmlp512.hip: resmlp_act)."""
@@ -993,8 +1140,9 @@ class PPOTrainer:
             self._rollout_body()
         from .env import gae_scan, rtg_scan
         self._gae = None
+        rew = self._normalise_rewards() if cfg.norm_reward else self.rew_buf   # (the scans below are the same either way)
         if cfg.gae_lambda is None:
-            rtg_scan(self.rew_buf, self.ended_buf, cfg.gamma, out=self.rtg_buf)  # ppo.py:619 -> 643-671
+            rtg_scan(rew, self.ended_buf, cfg.gamma, out=self.rtg_buf)  # ppo.py:619 -> 643-671
         else:   # extension: the critic's values of the stored observations -> lambda-returns (critic targets) and advantages
             # lambda < 1: the envs still running at the batch end are bootstrapped with V(obs_buf[T]), the observation behind the last
             # row (an env that ended on the last row has ended[T-1] set, which cuts the bootstrap).  lambda = 1 keeps the reference's
@@ -1003,7 +1151,7 @@ class PPOTrainer:
             boot = cfg.gae_lambda < 1.0
             Vall = self.updater.value(self.obs_buf[:T + 1 if boot else T].reshape(-1, D)).reshape(-1, N)
             V = Vall[:T].contiguous()
-            adv, ret = gae_scan(self.rew_buf, self.ended_buf, V, cfg.gamma, cfg.gae_lambda, last_value=Vall[T] if boot else None)
+            adv, ret = gae_scan(rew, self.ended_buf, V, cfg.gamma, cfg.gae_lambda, last_value=Vall[T] if boot else None)
             self.rtg_buf.copy_(ret)
             self._gae = (adv.reshape(T * N), V.reshape(T * N))
         self.env_steps += cfg.rollout_len * self.env.N
@@ -1042,7 +1190,8 @@ class PPOTrainer:
         return m
 
     def _rollout_metrics(self, m=None):
-        ep, succ, coll, tmo, steps, ret = [float(x) for x in (self._rollout_metrics_dev() if m is None else m).tolist()]
+        m = self._rollout_metrics_dev() if m is None else m   # (a tensor, or the six figures already on the host)
+        ep, succ, coll, tmo, steps, ret = [float(x) for x in (m.tolist() if torch.is_tensor(m) else m)]
         self.episode_starts = ep / (self.ctx.world if self.ctx is not None else 1) + self.env.N
         return dict(episodes=int(ep), successes=int(succ), collisions=int(coll), timeouts=int(tmo),
                     completed_steps=int(steps), avg_ep_rews=(ret / ep if ep else 0.0),       # ppo.py:833
@@ -1069,11 +1218,18 @@ class PPOTrainer:
                                     **({} if self._gae is None else dict(adv_raw=self._gae[0], V0=self._gae[1])))
         if cuda:
             ev[2].record()
+        if cfg.norm_reward:   # the option's figures ride on the episode sums' read-back below: one tensor, one copy
+            m = torch.cat([m, self._reward_norm_figures_dev()])
+        if cuda:
             torch.cuda.synchronize(self.device)
         t2 = time.time()
         if cuda:   # the host ran ahead of the stream: split the wall clock of the iteration by the stream's own stamps
             r_ms, u_ms = ev[0].elapsed_time(ev[1]), ev[1].elapsed_time(ev[2])
             t1 = t0 + (t2 - t0) * r_ms / max(r_ms + u_ms, 1e-9)
+        if cfg.norm_reward:
+            m = m.tolist()
+            rn, m = m[6:], m[:6]
+            stats = dict(stats, reward_scale=rn[3], ret_rms_mean=rn[0], ret_rms_std=math.sqrt(max(rn[1], 0.0)), explained_variance=rn[4])
         metrics = self._rollout_metrics(m)
         self.t_so_far += metrics["completed_steps"]
         self.i_so_far += 1
@@ -1265,6 +1421,8 @@ class PPOTrainer:
                 "ppo/skipped_steps_actor": lg.get("skipped_steps_actor"), "ppo/skipped_steps_critic": lg.get("skipped_steps_critic"),
                 "ppo/kl_stop_epoch": lg.get("kl_stop_epoch"), "ppo/kl_stopped": lg.get("kl_stopped"),   # (target_kl set)
                 **({"ppo/kl_stop_step": lg["kl_stop_step"]} if "kl_stop_step" in lg else {}),           # (target_kl and minibatches)
+                **({"ppo/" + k: lg[k] for k in ("reward_scale", "ret_rms_mean", "ret_rms_std", "explained_variance")}
+                   if "reward_scale" in lg else {}),                                                    # (norm_reward)
                 **({"eval/success_rate": lg["eval_success"], "eval/collision_rate": lg["eval_collision"],
                     "eval/timeout_rate": lg["eval_timeout"], "eval/mean_return": lg["eval_return"],
                     "eval/mean_ep_length": lg["eval_length"], "time/eval": lg["eval_time"]} if "eval_success" in lg else {})}
@@ -1335,10 +1493,29 @@ class PPOTrainer:
         pa, pc = os.path.join(d, "actor_" + tag), os.path.join(d, "critic_" + tag)
         torch.save({k: v.detach().cpu().clone() for k, v in self.actor.state_dict().items()}, pa)
         torch.save({k: v.detach().cpu().clone() for k, v in self.critic.state_dict().items()}, pc)
+        if self.cfg.norm_reward:   # a third file beside the two reference-named ones: the critic's units
+            mean, var, count = self.ret_rms[:3].tolist()
+            torch.save({"mean": mean, "var": var, "count": count}, os.path.join(d, "retnorm_" + tag))
         return pa, pc
 
+    @staticmethod
+    def retnorm_path(actor_path):
+        """retnorm_<tag>.pth beside actor_<tag>.pth"""
+        d, base = os.path.split(actor_path)
+        return os.path.join(d, "retnorm_" + (base[len("actor_"):] if base.startswith("actor_") else base))
+
     def load_checkpoint(self, actor_path, critic_path):
-        """main.py:52-89: state_dicts only (optimiser state and covariance are not part of a checkpoint)."""
+        """main.py:52-89: state_dicts only (optimiser state and covariance are not part of a checkpoint).  With norm_reward the return
+        statistics come from retnorm_<tag>.pth beside the actor's file; without that file: one warning line and fresh statistics."""
+        if self.cfg.norm_reward:
+            pr = self.retnorm_path(actor_path)
+            if os.path.exists(pr):
+                s = torch.load(pr, map_location="cpu")
+                self._init_ret_rms(self.ret_rms.device, s["mean"], s["var"], s["count"])
+            else:
+                import warnings
+                warnings.warn(f"norm_reward: {pr} not found -- the return statistics start fresh; the critic's units are off until they settle")
+                self._init_ret_rms(self.ret_rms.device)
         sa = torch.load(actor_path, map_location="cpu")
         sc = torch.load(critic_path, map_location="cpu")
         with torch.no_grad():
