@@ -195,13 +195,18 @@ template <bool ACTOR>
 __device__ __forceinline__ void pass_body(SmemS& sm, const float* __restrict__ params, const unsigned char* __restrict__ prep,
                                           const float* __restrict__ act, const float* __restrict__ logp_old,
                                           const float* __restrict__ rtg, const float* __restrict__ adv, long long M, float var,
-                                          float clip, float inv_n, float* __restrict__ partial, float* __restrict__ stats_partial) {
+                                          float clip, float inv_n, float* __restrict__ partial, float* __restrict__ stats_partial,
+                                          const int block) {   // block: whose tiles this pass walks and whose row it writes (the wrapper pairs workgroups)
     using L = Layout<16>;
     constexpr int OFF_W1 = L::OFF_W1, OFF_B1 = L::OFF_B1, OFF_W2 = L::OFF_W2, OFF_B2 = L::OFF_B2, OFF_W3 = L::OFF_W3, OFF_B3 = L::OFF_B3,
                   OFF_W4 = L::OFF_W4, OFF_B4 = L::OFF_B4;
     constexpr int P = ACTOR ? L::P_ACTOR : L::P_CRITIC;
     constexpr int NT = 64 * SW, kTileBytes = XPad<16>::kTileBytes, kRowsBytes = XPad<16>::kRowsBytes;
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    int tid = threadIdx.x;
+    // (no instruction: the wrapper calls this body from a loop over its two phases, and everything below that depends on the thread
+    // index alone would be computed once in front of that loop, for both nets, and held in registers -- or in scratch -- across it)
+    asm volatile("" : "+v"(tid));
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, lhi = lane >> 5, l15 = lane & 15, kk = lane >> 4;
 
     // ---- weights -> bf16 pieces in LDS (once per launch), as pass_body_x3
@@ -266,21 +271,26 @@ __device__ __forceinline__ void pass_body(SmemS& sm, const float* __restrict__ p
     const int vec_off = 4 * lhi;
     auto ldv = [&](const float* v, const int t, const int g) { return *reinterpret_cast<const v4f*>(v + 32 * t + 8 * g + vec_off); };
 
-    // ---- accumulators that persist over this wave's tiles
+    // ---- accumulators that persist over this wave's tiles (zf: a zero the compiler cannot see through -- as `tid` above, registers of
+    // zeros for both nets' accumulators would be set up in front of the wrapper's loop and held across it)
+    float zf = 0.f;
+    asm volatile("" : "+v"(zf));
     f32x16 aW2[2][2];
     v4f aW1[4], aB1[4];
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
-        for (int b = 0; b < 2; ++b) aW2[a][b] = zero16();
+        for (int b = 0; b < 2; ++b)
 #pragma unroll
-    for (int u = 0; u < 4; ++u) aW1[u] = aB1[u] = v4f{0.f, 0.f, 0.f, 0.f};
+            for (int r = 0; r < 16; ++r) aW2[a][b][r] = zf;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) aW1[u] = aB1[u] = v4f{zf, zf, zf, zf};
     float pb2[2][16], pw3[2][16], pw4[2][16];   // per-lane partial sums over the tiles: db2, dW3, dW4 of the lane's 32 units
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) pb2[t][r] = pw3[t][r] = pw4[t][r] = 0.f;
-    float adb3 = 0.f, adb4 = 0.f, st0 = 0.f, st1 = 0.f, st2 = 0.f, st3 = 0.f;
+        for (int r = 0; r < 16; ++r) pb2[t][r] = pw3[t][r] = pw4[t][r] = zf;
+    float adb3 = zf, adb4 = zf, st0 = zf, st1 = zf, st2 = zf, st3 = zf;
     // (no instruction: a use of dW2's accumulators in the middle of the phases that do not touch them, so that the register allocator
     // does not park them elsewhere for those phases and fetch them back for G2 -- 96 copies per tile; dW1's likewise: moved aside over
     // F2 and back in front of G1, one copy right in front of its MFMA)
@@ -291,7 +301,7 @@ __device__ __forceinline__ void pass_body(SmemS& sm, const float* __restrict__ p
     asm volatile("" : "+a"(ones));   // lives in AGPRs for the whole launch
 
     const long long n_tiles = (M + 31) / 32;
-    const long long gw = (long long)blockIdx.x * SW + wave, stride = (long long)gridDim.x * SW;
+    const long long gw = (long long)block * SW + wave, stride = (long long)gridDim.x * SW;
     // Operands that come from global memory -- the tile's observation rows (F1's B operand) and columns (G1's B operand), pre-split by
     // mlp64_split_obs -- are requested by asm loads straight into AGPRs (a compiler-issued load lands in vector registers, which are full,
     // and is copied over right in front of the MFMA: the hazard above) long before their use; `landed` is their s_waitcnt, placed a
@@ -451,6 +461,9 @@ __device__ __forceinline__ void pass_body(SmemS& sm, const float* __restrict__ p
     // imgD starts as zeros: the first tile's "previous G1" then adds nothing (the stream below has no special first iteration)
     for (int k = lane; k < kImgB / 16; k += 64) reinterpret_cast<u32x4*>(smb + img0 + IMG_D)[k] = u32x4{0u, 0u, 0u, 0u};
     bool have_prev = false;
+    // A wave with tiles: the look-ahead, the tile loop and the last tile's G1 in ONE block (closed behind that G1; the loop keeps its
+    // indentation).  Closed in front of the loop, the operands requested here met "not requested" where the paths join, and the
+    // compiler carried such registers from one phase of the wrapper's loop into the next, through both tile loops.
     if (gw < n_tiles) {
         request_rows(gw);
         request_cols(gw);   // (the first tile's "previous" columns: any finite values -- they meet zero pieces)
@@ -461,7 +474,6 @@ __device__ __forceinline__ void pass_body(SmemS& sm, const float* __restrict__ p
             ahead_work(n, true);
         };
         X3S_REP10(slot, 10) X3S_REP10(slot, 20) X3S_REP10(slot, 30) X3S_REP10(slot, 40) X3S_REP10(slot, 50)
-    }
     for (long long tile = gw; tile < n_tiles; tile += stride) {
         const bool valid = tile * 32 + l31 < M;
         const float cur_a0 = pre_a0, cur_a1 = pre_a1, cur_lp = pre_lp, cur_t = pre_t;
@@ -769,7 +781,10 @@ __device__ __forceinline__ void pass_body(SmemS& sm, const float* __restrict__ p
         for (int q = 0; q < 12; ++q) g1_gather_pair(g1o, q, h_base0, h_base1);
 #pragma unroll
         for (int k = 0; k < 36; ++k) g1_step(k, g1o, xbn, true);
+        // (dW1 / db1 may be copied right behind this block, where the two paths around it meet: the last MFMAs' wait states)
+        asm volatile("s_nop 7" : "+a"(aW1[0]), "+a"(aW1[1]), "+a"(aW1[2]), "+a"(aW1[3]), "+v"(aB1[0]), "+v"(aB1[1]), "+v"(aB1[2]), "+v"(aB1[3]));
     }
+    }   // (gw < n_tiles)
 
     // ---- the lane partials -> sums over the 32 sample lanes of each half, through the wave's (now free) images
     __syncthreads();
@@ -844,13 +859,25 @@ __device__ __forceinline__ void pass_body(SmemS& sm, const float* __restrict__ p
         }
     }
     __syncthreads();
-    float* out = partial + (size_t)blockIdx.x * P;
+    float* out = partial + (size_t)block * P;
     const float* red = red0;
     for (int k = tid; k < P; k += NT) out[k] = (red[k] + red[RP + k]) + (red[2 * RP + k] + red[3 * RP + k]);
-    if (tid < 3) stats_partial[blockIdx.x * 4 + tid] = (red[P + tid] + red[RP + P + tid]) + (red[2 * RP + P + tid] + red[3 * RP + P + tid]);
+    if (tid < 3) stats_partial[block * 4 + tid] = (red[P + tid] + red[RP + P + tid]) + (red[2 * RP + P + tid] + red[3 * RP + P + tid]);
 }
 
 }  // namespace x3s
+
+// X3S_PAIR: the block-index bit that joins two workgroups into a pair (0: no pairing, every workgroup walks its own tiles for both
+// nets, actor then critic -- the A/B partner, tools/build_mlp64_variant.py).  Both nets read the same pre-split tiles; unpaired, a
+// workgroup comes back to a tile a whole pass later, when the caches have long dropped it.  Paired, workgroup b runs the actor over
+// the tiles of block b while b ^ X3S_PAIR runs the critic over the same tiles, then the two swap: the second reader of a tile follows
+// the first by microseconds.  Workgroups are dealt round-robin over the 8 XCDs, so b and b ^ 8 share an L2 (a speed matter only: nothing
+// is handed from one workgroup to the other).  WHICH workgroup computes a partial row does not change it -- every (wave, net) sums the
+// same tiles in the same order into the same row -- so the results are bit for bit those of the unpaired launch.
+#ifndef X3S_PAIR
+#define X3S_PAIR 8
+#endif
+static_assert(X3S_PAIR >= 0 && (X3S_PAIR & (X3S_PAIR - 1)) == 0, "X3S_PAIR is 0 or one bit of the block index");
 
 // both nets of one epoch in one launch (net_mask as mlp64_pass_both_x3), 16-column rows
 __global__ __launch_bounds__(64 * x3s::SW) void NAVPPO_KL_KERNEL(mlp64_pass_both_x3s)(const float* __restrict__ params, const unsigned char* __restrict__ prep,
@@ -861,7 +888,31 @@ __global__ __launch_bounds__(64 * x3s::SW) void NAVPPO_KL_KERNEL(mlp64_pass_both
                                                                     float* __restrict__ partial_c, float* __restrict__ stats_partial_c NAVPPO_KL_PARAM) {
     __shared__ __attribute__((aligned(128))) x3s::SmemS sm;
     NAVPPO_KL_GATE();
-    if (net_mask & 1) x3s::pass_body<true>(sm, params, prep, act, logp_old, rtg, adv, M, var, clip, inv_n, partial_a, stats_partial_a);
+#if X3S_PAIR
+    // paired: both nets and whole pair groups only (single-net launches, small and odd grids keep the order below on their own block).
+    // The critic's pass is always the partner's block: a workgroup with the pair bit clear runs actor(b), critic(b ^ X3S_PAIR), one with
+    // it set runs critic(b ^ X3S_PAIR), actor(b) -- every row of either net is written once, by one workgroup.  One loop of two phases,
+    // not unrolled: each body has ONE call site, so the listing holds each tile loop once (tests/test_isa_schedule_cpu.py).
+    const int b = blockIdx.x;
+    const bool paired = net_mask == 3 && gridDim.x % (2 * X3S_PAIR) == 0;
+    const bool critic_first = paired && (b & X3S_PAIR);
+#pragma nounroll
+    for (int phase = 0; phase < 2; ++phase) {
+        int blk = b;
+        asm volatile("" : "+s"(blk));
+        if (__builtin_expect((phase == 0) != critic_first, 1)) {
+            if (net_mask & 1) x3s::pass_body<true>(sm, params, prep, act, logp_old, rtg, adv, M, var, clip, inv_n, partial_a, stats_partial_a, blk);
+        } else {
+            if (net_mask & 2)
+                x3s::pass_body<false>(sm, params + Layout<16>::P_ACTOR, prep, act, logp_old, rtg, adv, M, var, clip, inv_n, partial_c, stats_partial_c,
+                                      paired ? blk ^ X3S_PAIR : blk);
+        }
+        if (phase == 0 && net_mask == 3) __syncthreads();   // the first body's last LDS reads, the second's weight pieces
+    }
+#else
+    if (net_mask & 1) x3s::pass_body<true>(sm, params, prep, act, logp_old, rtg, adv, M, var, clip, inv_n, partial_a, stats_partial_a, blockIdx.x);
     if (net_mask == 3) __syncthreads();
-    if (net_mask & 2) x3s::pass_body<false>(sm, params + Layout<16>::P_ACTOR, prep, act, logp_old, rtg, adv, M, var, clip, inv_n, partial_c, stats_partial_c);
+    if (net_mask & 2)
+        x3s::pass_body<false>(sm, params + Layout<16>::P_ACTOR, prep, act, logp_old, rtg, adv, M, var, clip, inv_n, partial_c, stats_partial_c, blockIdx.x);
+#endif
 }

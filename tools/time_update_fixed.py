@@ -5,7 +5,9 @@ weights into bf16 pieces (once per workgroup and net), the epilogues, the reduct
 on synthetic rows with HIP events at n = 32 * 1024 * k samples, k = 1, 2, 4 .. 64 (the pass runs 256 workgroups of 4 waves: k tiles per
 wave and net), takes the median of 5 and fits  t(k) = intercept + slope * k  by least squares.  The intercept bounds what any change
 to the per-launch work can win; the slope is the cost of a tile pair per wave.
-usage: python tools/time_update_fixed.py [--label NAME] [--epochs E] [--reps R] [--out profiles/x3s_fixed_cost.txt] [--append]"""
+--k 24,32,40,...: these tile counts instead (profiles/pass_pairing.txt: the marginal cost of a tile pair on either side of the batch size
+that still fits the Infinity Cache), each row with its step from the row before.
+usage: python tools/time_update_fixed.py [--label NAME] [--epochs E] [--reps R] [--k K1,K2,...] [--out profiles/x3s_fixed_cost.txt] [--append]"""
 import argparse
 import os
 import statistics
@@ -19,6 +21,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--label", default="tree")
 ap.add_argument("--epochs", type=int, default=20)
 ap.add_argument("--reps", type=int, default=5)
+ap.add_argument("--k", default="1,2,4,8,16,32,64", help="tiles per wave and net, ascending")
 ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "x3s_fixed_cost.txt"))
 ap.add_argument("--append", action="store_true", help="add this tree's block to --out instead of replacing the file")
 args = ap.parse_args()
@@ -26,7 +29,8 @@ if not torch.cuda.is_available():
     sys.exit("time_update_fixed: needs the GPU (there is no CPU timing of a HIP kernel)")
 
 dev = torch.device("cuda")
-KS = (1, 2, 4, 8, 16, 32, 64)
+KS = tuple(int(k) for k in args.k.split(","))
+assert len(KS) >= 2 and all(a < b for a, b in zip(KS, KS[1:])) and KS[0] >= 1, "--k: two or more ascending tile counts"
 n_max = 32 * 1024 * KS[-1]
 g = torch.Generator().manual_seed(1)
 obs = torch.rand((n_max, 16), generator=g).to(dev)
@@ -66,8 +70,9 @@ med = []
 for k in KS:
     ts = epochs_us(32 * 1024 * k)
     med.append(statistics.median(ts))
-    lines.append(f"  k = {k:2d}  n = {32 * 1024 * k:8d}  median {med[-1]:8.2f}  min {min(ts):8.2f}  max {max(ts):8.2f}")
-# least squares of t = a + b k over the seven points
+    step = f"  {(med[-1] - med[-2]) / (k - KS[len(med) - 2]):6.2f} us per tile pair from the row above" if len(med) > 1 else ""
+    lines.append(f"  k = {k:2d}  n = {32 * 1024 * k:8d}  median {med[-1]:8.2f}  min {min(ts):8.2f}  max {max(ts):8.2f}{step}")
+# least squares of t = a + b k over the points
 mk, mt = sum(KS) / len(KS), sum(med) / len(med)
 slope = sum((k - mk) * (t - mt) for k, t in zip(KS, med)) / sum((k - mk) ** 2 for k in KS)
 icpt = mt - slope * mk
