@@ -180,6 +180,55 @@ int navppo_adam_step_kl(float* params_dev, float* grad_dev, float* adam_m_dev, f
                         float* clip_stats_dev, float kl_limit, float* kl_state_dev, const float* kl_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------------
+ * Adaptive learning rate ON THE DEVICE (the KL-adaptive step size of rsl_rl / rl_games: after every optimiser step the rate is divided
+ * by 1.5 when the policy moved more than twice the desired KL and multiplied by 1.5 when it moved less than half of it).  The epochs of
+ * an update are queued without a host round trip, so the rate cannot be a by-value argument: it lives in lr_state_dev.
+ * navppo_mlp64_update_epoch_lr, navppo_mlp64_bf16x3_update_epoch_lr and navppo_resmlp512_update_epoch_lr take exactly the arguments of
+ * their *_clipped twins plus `kl_target, lr_min, lr_max, adapt, lr_state_dev` in front of `stream`; navppo_adam_step_lr is the multi-GPU
+ * form.  The passes, the reduction and their launches are those of *_clipped (nothing is gated); only the step launch differs
+ * (clip_adam_lr_kernel).  max_norm = +inf means "no clipping", as above.
+ *   lr_state_dev  [4] f32.  [0], [1]: two learning-rate slots   [2] raises, [3] lowerings since the caller zeroed the state.
+ *                 The caller zeroes it (a fresh run) or writes a saved rate into BOTH slots (a resumed run); afterwards only the
+ *                 library writes it.
+ *   kl_target     > 0;  lr_min > 0;  lr_max >= lr_min;  adapt 0 or 1;  lr_state_dev not NULL -- else -1 and nothing is launched (a NaN
+ *                 fails each comparison).  The *_clipped checks are unchanged.
+ * Per call, with Adam step count `step` (calls on one state use consecutive `step`, as for stats_dev[3] / [7]):
+ *   1. lr_in = lr_state[step & 1]; a slot holding exactly 0.0f means "not started": lr_in = the `lr` argument.
+ *   2. kl = stats_dev[1] of this call (the mean of (ratio - 1) - log ratio, ppo.py:326; navppo_adam_step_lr: *kl_dev), which an
+ *      EARLIER launch wrote.  In float32, the expressions as written (the library is compiled with -ffp-contract=off):
+ *        adapt == 0:                                   lr = lr_in
+ *        else !(kl <= 2.0f * kl_target):               lr = fmaxf(lr_min, lr_in / 1.5f)      -- a NaN kl lowers
+ *        else kl < 0.5f * kl_target && kl > 0.0f:      lr = fminf(lr_max, lr_in * 1.5f)
+ *        else:                                         lr = lr_in
+ *      Every workgroup of the step launch derives lr itself from the same bits; none waits for another.
+ *   3. the clipped epoch's step with that lr, the very expression of *_clipped: the non-finite guard, max_norm, grad_dev and
+ *      clip_stats_dev behave and are filled as there.
+ *   4. workgroup 0 writes lr to lr_state[(step + 1) & 1] and adds 1 to [2] (the raising branch was taken) or [3] (the lowering branch
+ *      was taken) -- also where a clamp held the rate, and whether or not a net was skipped.
+ * Two slots because the step launch has many workgroups (42 to about 400) that must all step with ONE rate: a single slot rewritten
+ * by workgroup 0 would be read by workgroups of the same launch that start later.  The slot a launch writes is read by the NEXT call only.
+ * adapt = 0 on a zeroed state gives the bits of *_update_epoch_clipped with the same lr; with max_norm = +inf as well, those of
+ * *_update_epoch.  A caller passes adapt = 0 for the first step of an update: the weights are then those that collected the batch and
+ * kl is the rounding noise of two log-probability computations.  navbot_ppo_amd.ppo.adaptive_lr_reference is the host mirror of step 2.
+ * Not combined with the *_kl entry points (two answers to the same signal).
+ */
+int navppo_mlp64_update_epoch_lr(float* params_dev, const void* obs_dev, int32_t obs_dim, int32_t obs_f16, const float* act_dev,
+                                 const float* logp_old_dev, const float* rtg_dev, const float* adv_dev, int64_t n_samples, float var,
+                                 float clip, float lr, float beta1, float beta2, float eps, int32_t step, float* adam_m_dev,
+                                 float* adam_v_dev, float* grad_dev, float* stats_dev, void* workspace_dev, float max_norm,
+                                 float* clip_stats_dev, float kl_target, float lr_min, float lr_max, int32_t adapt, float* lr_state_dev,
+                                 void* stream);
+
+/*
+ * navppo_adam_step_clipped with the contract above.  kl_dev: a device scalar holding the GLOBAL approx_kl of this step (multi-GPU:
+ * all-reduce [kl x n, n] and divide), so that every rank derives the same rate; NULL: -1.
+ */
+int navppo_adam_step_lr(float* params_dev, float* grad_dev, float* adam_m_dev, float* adam_v_dev, int64_t n, int64_t n_first,
+                        float grad_scale, float max_norm, float lr, float beta1, float beta2, float eps, int32_t step,
+                        float* clip_stats_dev, float kl_target, float lr_min, float lr_max, int32_t adapt, float* lr_state_dev,
+                        const float* kl_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------------
  * The same update (ppo.py:305-397; 16- or 42-column rows, float32 or float16) with every matrix product evaluated on the bf16 MFMA from operands split into
  * three bf16 pieces -- "bf16x3": a = a0 + a1 + a2 exactly (8 + 8 + 8 significand bits), a b ~ the six leading piece products,
  * each exact in float32, float32 accumulation, small terms first.  float32-equivalent by measurement (against float64 the
@@ -220,6 +269,14 @@ int navppo_mlp64_bf16x3_update_epoch_kl(float* params_dev, const void* prep_dev,
                                         float clip, float lr, float beta1, float beta2, float eps, int32_t step, float* adam_m_dev,
                                         float* adam_v_dev, float* grad_dev, float* stats_dev, void* workspace_dev, float max_norm,
                                         float* clip_stats_dev, float kl_limit, float* kl_state_dev, void* stream);
+
+/* navppo_mlp64_bf16x3_update_epoch_clipped with the adaptive learning rate: see navppo_mlp64_update_epoch_lr */
+int navppo_mlp64_bf16x3_update_epoch_lr(float* params_dev, const void* prep_dev, int32_t obs_dim, const float* act_dev,
+                                        const float* logp_old_dev, const float* rtg_dev, const float* adv_dev, int64_t n_samples, float var,
+                                        float clip, float lr, float beta1, float beta2, float eps, int32_t step, float* adam_m_dev,
+                                        float* adam_v_dev, float* grad_dev, float* stats_dev, void* workspace_dev, float max_norm,
+                                        float* clip_stats_dev, float kl_target, float lr_min, float lr_max, int32_t adapt,
+                                        float* lr_state_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------------
  * Minibatch updates.  Every *_loss_grad / *_update_epoch[_clipped | _kl] entry point takes pointers and n_samples, so one optimiser
@@ -350,6 +407,13 @@ int navppo_resmlp512_update_epoch_kl(float* params_dev, const void* obs_dev, int
                                      float beta1, float beta2, float eps, int32_t step, float* adam_m_dev, float* adam_v_dev,
                                      float* grad_dev, float* stats_dev, void* workspace_dev, float max_norm, float* clip_stats_dev,
                                      float kl_limit, float* kl_state_dev, void* stream);
+
+/* navppo_resmlp512_update_epoch_clipped with the adaptive learning rate: see navppo_mlp64_update_epoch_lr */
+int navppo_resmlp512_update_epoch_lr(float* params_dev, const void* obs_dev, int32_t obs_f16, const float* act_dev, const float* logp_old_dev,
+                                     const float* rtg_dev, const float* adv_dev, int64_t n_samples, float var, float clip, float lr,
+                                     float beta1, float beta2, float eps, int32_t step, float* adam_m_dev, float* adam_v_dev,
+                                     float* grad_dev, float* stats_dev, void* workspace_dev, float max_norm, float* clip_stats_dev,
+                                     float kl_target, float lr_min, float lr_max, int32_t adapt, float* lr_state_dev, void* stream);
 
 /* V = critic(obs).squeeze() (ppo.py:275, :724); critic_params_dev [50257] (8-byte aligned suffices), value_dev [n] */
 int navppo_resmlp512_value(const float* critic_params_dev, const void* obs_dev, int32_t obs_f16, int64_t n_samples, float* value_dev,

@@ -25,12 +25,13 @@ inline int navppo_launched(const char* who) {
     return -2;
 }
 
-// How an epoch (or navppo_adam_step*) ends -- the four step modes of include/navppo.h:
+// How an epoch (or navppo_adam_step*) ends -- the five step modes of include/navppo.h:
 enum class NavppoMode {
     kGrad,     // *_loss_grad[_net]: the reduction alone, nothing is stepped
     kAdam,     // *_update_epoch, navppo_adam_step: Adam inside the reduction (or alone)
     kClip,     // *_clipped: the reduction with its squared-norm slots, then one launch that clips and steps (navppo_launch_clip_adam)
     kClipKl,   // *_kl: the gated twins of those launches, the KL decision in front of the clip (below)
+    kClipLr,   // *_lr: kClip's (ungated) launches, the step launch derives its learning rate from the KL and lr_state (clip_adam_lr_kernel)
 };
 
 // the batch of an epoch: actions, old log-probabilities, rewards-to-go and advantages of n samples; the policy's variance, PPO's clip
@@ -48,11 +49,17 @@ struct NavppoStep {
     float *m, *v;                        // exp_avg, exp_avg_sq
     float max_norm; float* clip_stats;   // kClip, kClipKl
     float kl_limit; float* kl_state;     // kClipKl
+    float kl_target, lr_min, lr_max;     // kClipLr: the desired KL and the clamps of the learning rate
+    int32_t adapt; float* lr_state;      // kClipLr: 0 = keep the rate, 1 = apply the rule; [4] (two rate slots, raises, lowerings)
 };
 
 // max_norm of the *_clipped entry points, kl_limit of the *_kl entry points: a positive number, +inf included (NaN fails)
 inline bool navppo_max_norm_ok(float max_norm) { return max_norm > 0.f; }
 inline bool navppo_kl_limit_ok(float kl_limit) { return kl_limit > 0.f; }
+// the *_lr entry points' own arguments: kl_target > 0, 0 < lr_min <= lr_max (a NaN fails each), adapt 0 or 1, the state
+inline bool navppo_lr_args_ok(const NavppoStep& s) {
+    return s.kl_target > 0.f && s.lr_min > 0.f && s.lr_max >= s.lr_min && (s.adapt == 0 || s.adapt == 1) && s.lr_state;
+}
 
 // the step arguments of `mode`; 0, or the message and -1
 inline int navppo_check_step(const char* who, NavppoMode mode, const NavppoStep& s) {
@@ -63,6 +70,8 @@ inline int navppo_check_step(const char* who, NavppoMode mode, const NavppoStep&
         return navppo_bad_args(who, "max_norm must be > 0 (+inf allowed) and clip_stats_dev [4] not null");
     if (mode == NavppoMode::kClipKl && (!navppo_kl_limit_ok(s.kl_limit) || !s.kl_state))
         return navppo_bad_args(who, "kl_limit must be > 0 (+inf allowed) and kl_state_dev [4] not null");
+    if (mode == NavppoMode::kClipLr && !navppo_lr_args_ok(s))
+        return navppo_bad_args(who, "kl_target > 0, 0 < lr_min <= lr_max, adapt 0 or 1 and lr_state_dev [4] not null");
     return 0;
 }
 
@@ -96,9 +105,13 @@ __device__ __forceinline__ void navppo_adam_apply(float* __restrict__ params, fl
 // its entry when kl_state[0] != 0; trips when !(*kl <= kl_limit): no net is stepped, clip_stats = (s_actor, s_critic, 0, 0), block 0
 // sets kl_state = (1, unchanged, *kl, step); else the step above, the same expression, and kl_state[1] += 1.  `kl` is a device scalar
 // an EARLIER launch wrote (stats_dev[1]): every block derives the same decision from the same bits, no block waits for another.
-// `s`: max_norm, Adam's arguments, clip_stats; kl != nullptr: s.kl_limit and s.kl_state as well.
+// adaptive_lr (the *_lr entry points, include/navppo.h "Adaptive learning rate"; kl as above, never null): clip_adam_lr_kernel instead
+// -- no gate, no trip: every block reads the rate slot lr_state[step & 1] (0 = not started: s.lr) and *kl, derives the step's rate by
+// the rule, and steps as above with it; block 0 writes the rate to slot (step + 1) & 1 -- which no block of THIS launch reads -- and
+// counts the raise or the lowering.
+// `s`: max_norm, Adam's arguments, clip_stats; kl != nullptr: s.kl_limit and s.kl_state, or (adaptive_lr) s.kl_target .. s.lr_state.
 void navppo_launch_clip_adam(float* params, float* grad, int n, int n_first, float grad_scale, const NavppoStep& s, const float* slots,
-                             int n_slots, int slot_stride, int slot_pitch, void* stream, const float* kl = nullptr);
+                             int n_slots, int slot_stride, int slot_pitch, void* stream, const float* kl = nullptr, bool adaptive_lr = false);
 
 // The gate of the *_kl kernels: one uniform read of kl_state[0] at kernel entry.  The flag is only ever written by the LAST launch of an
 // earlier epoch (clip_adam_kl_kernel), so every workgroup of a launch reads the same value; none of the gated kernels synchronises
@@ -111,7 +124,7 @@ __device__ __forceinline__ bool navppo_kl_stopped(const float* __restrict__ kl_s
 // second time as well: the epoch function of each family (mlp64_epoch, loss_grad_impl) is ONE launch sequence, a template over
 // NavppoMode that launches NAVPPO_KL_KERNEL(name) with NAVPPO_KL_ARG(kl_state) behind the last argument -- so a grid or an argument
 // cannot change for the clipped epoch and not for the gated one.  A translation unit instantiates the modes it exports
-// (kNavppoKlTu: kClipKl there, the other three here), hence only their kernels; the rest of the included file's host code --
+// (kNavppoKlTu: kClipKl there, the other four here), hence only their kernels; the rest of the included file's host code --
 // the entry points, the kernels that have no twin -- is compiled out of the twins' unit.
 // Without NAVPPO_KL_TU the macros vanish: the ungated kernels are textually what they were, in a translation unit of their own.
 // (Twins in the SAME translation unit changed the ungated kernels' listings: a helper that is not force-inlined then has two callers

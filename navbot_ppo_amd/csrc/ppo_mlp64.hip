@@ -1461,6 +1461,36 @@ __global__ __launch_bounds__(kClipThreads) void clip_adam_kl_kernel(float* __res
     clip_adam_body<true>(params, grad, m, v, n, n_first, grad_scale, max_norm, lr, beta1, beta2, eps, bc1, bc2_sqrt, slots, n_slots, slot_stride,
                          slot_pitch, clip_stats, kl_ptr, kl_limit, kl_state, step);
 }
+// The *_lr entry points' step launch (include/navppo.h, "Adaptive learning rate ON THE DEVICE"): the clipped step with a learning rate
+// every block derives from the same bits -- the rate slot the launch BEFORE wrote (step & 1; 0 = not started: `lr`) and *kl_ptr, which
+// an earlier launch of this call wrote.  Block 0 writes the OTHER slot, which no block of this launch reads: no block waits for another.
+// float32, the expressions as the header states them (navbot_ppo_amd.ppo.adaptive_lr_reference is their host mirror).
+__global__ __launch_bounds__(kClipThreads) void clip_adam_lr_kernel(float* __restrict__ params, float* __restrict__ grad, float* __restrict__ m,
+                                                                    float* __restrict__ v, int n, int n_first, float grad_scale, float max_norm,
+                                                                    float lr, float beta1, float beta2, float eps, float bc1, float bc2_sqrt,
+                                                                    const float* slots, int n_slots, int slot_stride, int slot_pitch,
+                                                                    float* clip_stats, const float* kl_ptr, float kl_target, float lr_min,
+                                                                    float lr_max, int adapt, float* lr_state, int step) {
+    const float slot = lr_state[step & 1], lr_in = slot == 0.0f ? lr : slot, kl = *kl_ptr;
+    float lr_step = lr_in;
+    int moved = 0;   // +1: raised, -1: lowered (the rule's branch, also where a clamp holds the rate)
+    if (adapt) {
+        if (!(kl <= 2.0f * kl_target)) {   // a NaN lowers
+            lr_step = fmaxf(lr_min, lr_in / 1.5f);
+            moved = -1;
+        } else if (kl < 0.5f * kl_target && kl > 0.0f) {
+            lr_step = fminf(lr_max, lr_in * 1.5f);
+            moved = 1;
+        }
+    }
+    clip_adam_body<false>(params, grad, m, v, n, n_first, grad_scale, max_norm, lr_step, beta1, beta2, eps, bc1, bc2_sqrt, slots, n_slots,
+                          slot_stride, slot_pitch, clip_stats, nullptr, 0.f, nullptr, 0);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {   // (whether or not a net was skipped)
+        lr_state[(step + 1) & 1] = lr_step;
+        if (moved > 0) lr_state[2] += 1.f;
+        else if (moved < 0) lr_state[3] += 1.f;
+    }
+}
 
 // navppo_adam_step_clipped: the squared norms of grad x grad_scale over [0, n_first) and [n_first, n) into out[0], out[1]; ONE block
 // (the buffer is 43 KB or 400 KB and an all-reduce ran just before), fixed order
@@ -1621,10 +1651,14 @@ thread_local std::string g_err;
 void navppo_set_error(const char* msg) { g_err = msg ? msg : ""; }
 
 void navppo_launch_clip_adam(float* params, float* grad, int n, int n_first, float grad_scale, const NavppoStep& s, const float* slots,
-                             int n_slots, int slot_stride, int slot_pitch, void* stream, const float* kl) {
+                             int n_slots, int slot_stride, int slot_pitch, void* stream, const float* kl, bool adaptive_lr) {
     const NavppoBias bc = navppo_bias(s.beta1, s.beta2, s.step);
     const dim3 grid((unsigned)((n + kClipThreads - 1) / kClipThreads));
-    if (kl)
+    if (adaptive_lr)
+        hipLaunchKernelGGL(clip_adam_lr_kernel, grid, dim3(kClipThreads), 0, (hipStream_t)stream, params, grad, s.m, s.v, n, n_first, grad_scale,
+                           s.max_norm, s.lr, s.beta1, s.beta2, s.eps, bc.bc1, bc.bc2_sqrt, slots, n_slots, slot_stride, slot_pitch, s.clip_stats, kl,
+                           s.kl_target, s.lr_min, s.lr_max, (int)s.adapt, s.lr_state, s.step);
+    else if (kl)
         hipLaunchKernelGGL(clip_adam_kl_kernel, grid, dim3(kClipThreads), 0, (hipStream_t)stream, params, grad, s.m, s.v, n, n_first, grad_scale,
                            s.max_norm, s.lr, s.beta1, s.beta2, s.eps, bc.bc1, bc.bc2_sqrt, slots, n_slots, slot_stride, slot_pitch, s.clip_stats, kl,
                            s.kl_limit, s.kl_state, s.step);
@@ -1747,9 +1781,10 @@ int mlp64_epoch(const char* who, float* params, const Mlp64Rows& x, const Navppo
         });
     }
     // the reduction over [q0, q1).  kAdam: Adam in the same launch, and (both nets) its blocks' squared-norm slots in parity step & 1 for
-    // the logged means.  kClip / kClipKl: the reduction alone, the slots in parity 0 (stats[3] / [7]: unspecified); then the norms,
-    // the KL decision on stats[1], the clip and Adam
-    constexpr bool kAdam = MODE == NavppoMode::kAdam, kClip = MODE == NavppoMode::kClip || MODE == NavppoMode::kClipKl;
+    // the logged means.  kClip / kClipKl / kClipLr: the reduction alone, the slots in parity 0 (stats[3] / [7]: unspecified); then the
+    // norms, the KL decision (kClipKl) or the learning rate (kClipLr) from stats[1], the clip and Adam
+    constexpr bool kAdam = MODE == NavppoMode::kAdam, kLr = MODE == NavppoMode::kClipLr;
+    constexpr bool kClip = MODE == NavppoMode::kClip || MODE == NavppoMode::kClipKl || kLr;
     const int q0 = (net_mask & 1) ? 0 : pl.pa, q1 = (net_mask & 2) ? pl.pa + pl.pc : pl.pa, rblocks = (q1 - q0 + 63) / 64;
     const NavppoStep r = kAdam ? s : NavppoStep{};
     const NavppoBias bc = kAdam ? navppo_bias(s.beta1, s.beta2, s.step) : NavppoBias{1.f, 1.f};
@@ -1759,7 +1794,7 @@ int mlp64_epoch(const char* who, float* params, const Mlp64Rows& x, const Navppo
                        bc.bc2_sqrt, pl.pa, pl.pc, q0, q1, parity >= 0 ? pl.gn : nullptr, parity NAVPPO_KL_ARG(s.kl_state));
     if constexpr (kClip)
         navppo_launch_clip_adam(params, grad, pl.pa + pl.pc, pl.pa, 1.0f, s, pl.gn, rblocks, kGnSlots, 8, stream,
-                                MODE == NavppoMode::kClipKl ? stats + 1 : nullptr);
+                                MODE == NavppoMode::kClipKl || kLr ? stats + 1 : nullptr, kLr);
     return navppo_launched(who);
 }
 
@@ -1772,14 +1807,14 @@ inline Mlp64Rows x3_rows(const void* prep_dev, int32_t obs_dim) { return {prep_d
 #ifndef NAVPPO_KL_TU
 namespace {
 
-// navppo_adam_step and its clipped / KL-gated forms: the step on a flat buffer whose gradient an all-reduce summed
+// navppo_adam_step and its clipped / KL-gated / adaptive-rate forms: the step on a flat buffer whose gradient an all-reduce summed
 int adam_step(const char* who, NavppoMode mode, float* params, float* grad, int64_t n, int64_t n_first, float grad_scale, const NavppoStep& s,
               const float* kl, void* stream) {
-    const bool clip = mode != NavppoMode::kAdam, kl_mode = mode == NavppoMode::kClipKl;
-    if (!params || !grad || n < 1 || (clip && (n > INT32_MAX || n_first < 0 || n_first > n)) || (kl_mode && !kl))
-        return navppo_bad_args(who, !clip     ? "bad argument"
-                                    : kl_mode ? "bad argument (0 <= n_first <= n; kl_dev [1] not null)"
-                                              : "bad argument (0 <= n_first <= n)");
+    const bool clip = mode != NavppoMode::kAdam, kl_mode = mode == NavppoMode::kClipKl, lr_mode = mode == NavppoMode::kClipLr;
+    if (!params || !grad || n < 1 || (clip && (n > INT32_MAX || n_first < 0 || n_first > n)) || ((kl_mode || lr_mode) && !kl))
+        return navppo_bad_args(who, !clip                ? "bad argument"
+                                    : kl_mode || lr_mode ? "bad argument (0 <= n_first <= n; kl_dev [1] not null)"
+                                                         : "bad argument (0 <= n_first <= n)");
     if (const int rc = navppo_check_step(who, mode, s)) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (!clip) {
@@ -1787,12 +1822,12 @@ int adam_step(const char* who, NavppoMode mode, float* params, float* grad, int6
         hipLaunchKernelGGL(adam_step_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, params, (const float*)grad, s.m, s.v, (int)n,
                            grad_scale, s.lr, s.beta1, s.beta2, s.eps, bc.bc1, bc.bc2_sqrt);
     } else {   // the squared norms into clip_stats[0..1], which the step launch then reads as its (one) slot per net
-        if (kl)
+        if (kl_mode)
             hipLaunchKernelGGL(sqnorm2_kl_kernel, dim3(1), dim3(kNormThreads), 0, st, (const float*)grad, (int)n, (int)n_first, grad_scale,
                                s.clip_stats, (const float*)s.kl_state);
         else
             hipLaunchKernelGGL(sqnorm2_kernel, dim3(1), dim3(kNormThreads), 0, st, (const float*)grad, (int)n, (int)n_first, grad_scale, s.clip_stats);
-        navppo_launch_clip_adam(params, grad, (int)n, (int)n_first, grad_scale, s, s.clip_stats, 1, 1, 8, stream, kl);
+        navppo_launch_clip_adam(params, grad, (int)n, (int)n_first, grad_scale, s, s.clip_stats, 1, 1, 8, stream, kl, lr_mode);
     }
     return navppo_launched(who);
 }
@@ -1841,6 +1876,16 @@ int navppo_adam_step_kl(float* params_dev, float* grad_dev, float* adam_m_dev, f
                      {lr, beta1, beta2, eps, step, adam_m_dev, adam_v_dev, max_norm, clip_stats_dev, kl_limit, kl_state_dev}, kl_dev, stream);
 }
 
+int navppo_adam_step_lr(float* params_dev, float* grad_dev, float* adam_m_dev, float* adam_v_dev, int64_t n, int64_t n_first,
+                        float grad_scale, float max_norm, float lr, float beta1, float beta2, float eps, int32_t step,
+                        float* clip_stats_dev, float kl_target, float lr_min, float lr_max, int32_t adapt, float* lr_state_dev,
+                        const float* kl_dev, void* stream) {
+    return adam_step("navppo_adam_step_lr", NavppoMode::kClipLr, params_dev, grad_dev, n, n_first, grad_scale,
+                     {lr, beta1, beta2, eps, step, adam_m_dev, adam_v_dev, max_norm, clip_stats_dev, 0.f, nullptr, kl_target, lr_min, lr_max, adapt,
+                      lr_state_dev},
+                     kl_dev, stream);
+}
+
 int navppo_mlp64_value(const float* critic_params_dev, const void* obs_dev, int32_t obs_dim, int32_t obs_f16, int64_t n_samples,
                        float* value_dev, void* stream) {
     if (!critic_params_dev || !obs_dev || !value_dev || n_samples < 1 || (obs_dim != 16 && obs_dim != 42) ||
@@ -1875,6 +1920,19 @@ int navppo_mlp64_update_epoch_clipped(float* params_dev, const void* obs_dev, in
                                           {act_dev, logp_old_dev, rtg_dev, adv_dev, n_samples, var, clip}, 3,
                                           {lr, beta1, beta2, eps, step, adam_m_dev, adam_v_dev, max_norm, clip_stats_dev}, grad_dev, stats_dev,
                                           workspace_dev, stream);
+}
+
+int navppo_mlp64_update_epoch_lr(float* params_dev, const void* obs_dev, int32_t obs_dim, int32_t obs_f16, const float* act_dev,
+                                 const float* logp_old_dev, const float* rtg_dev, const float* adv_dev, int64_t n_samples, float var,
+                                 float clip, float lr, float beta1, float beta2, float eps, int32_t step, float* adam_m_dev,
+                                 float* adam_v_dev, float* grad_dev, float* stats_dev, void* workspace_dev, float max_norm,
+                                 float* clip_stats_dev, float kl_target, float lr_min, float lr_max, int32_t adapt, float* lr_state_dev,
+                                 void* stream) {
+    return mlp64_epoch<NavppoMode::kClipLr>("navppo_mlp64_update_epoch_lr", params_dev, f32_rows(obs_dev, obs_dim, obs_f16),
+                                            {act_dev, logp_old_dev, rtg_dev, adv_dev, n_samples, var, clip}, 3,
+                                            {lr, beta1, beta2, eps, step, adam_m_dev, adam_v_dev, max_norm, clip_stats_dev, 0.f, nullptr, kl_target,
+                                             lr_min, lr_max, adapt, lr_state_dev},
+                                            grad_dev, stats_dev, workspace_dev, stream);
 }
 
 size_t navppo_mlp64_bf16x3_prep_bytes(int64_t n_samples, int32_t obs_dim) {
@@ -1929,6 +1987,19 @@ int navppo_mlp64_bf16x3_update_epoch_clipped(float* params_dev, const void* prep
                                           {act_dev, logp_old_dev, rtg_dev, adv_dev, n_samples, var, clip}, 3,
                                           {lr, beta1, beta2, eps, step, adam_m_dev, adam_v_dev, max_norm, clip_stats_dev}, grad_dev, stats_dev,
                                           workspace_dev, stream);
+}
+
+int navppo_mlp64_bf16x3_update_epoch_lr(float* params_dev, const void* prep_dev, int32_t obs_dim, const float* act_dev,
+                                        const float* logp_old_dev, const float* rtg_dev, const float* adv_dev, int64_t n_samples, float var,
+                                        float clip, float lr, float beta1, float beta2, float eps, int32_t step, float* adam_m_dev,
+                                        float* adam_v_dev, float* grad_dev, float* stats_dev, void* workspace_dev, float max_norm,
+                                        float* clip_stats_dev, float kl_target, float lr_min, float lr_max, int32_t adapt,
+                                        float* lr_state_dev, void* stream) {
+    return mlp64_epoch<NavppoMode::kClipLr>("navppo_mlp64_bf16x3_update_epoch_lr", params_dev, x3_rows(prep_dev, obs_dim),
+                                            {act_dev, logp_old_dev, rtg_dev, adv_dev, n_samples, var, clip}, 3,
+                                            {lr, beta1, beta2, eps, step, adam_m_dev, adam_v_dev, max_norm, clip_stats_dev, 0.f, nullptr, kl_target,
+                                             lr_min, lr_max, adapt, lr_state_dev},
+                                            grad_dev, stats_dev, workspace_dev, stream);
 }
 
 int navppo_episode_sums(const uint8_t* ended_dev, const uint8_t* arrive_dev, const uint8_t* done_dev, const int32_t* ep_length_dev,

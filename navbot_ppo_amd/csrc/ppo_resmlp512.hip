@@ -1210,8 +1210,10 @@ int loss_grad_impl(const char* name, float* params, const void* obs, int32_t obs
     hipLaunchKernelGGL((NAVPPO_KL_KERNEL(resmlp_bwd)<16, 2, kBwd1Waves>), dim3(p.wgs), dim3(64 * kBwd1Waves), 0, st, w, 2, obs, h1, dy2, n, p.groups,
                        p.wpart, (float*)nullptr, (const float*)p.qb, f16 NAVPPO_KL_ARG(s.kl_state));
     // the reduction.  kAdam: Adam in the same launch, its blocks' squared-norm slots in parity step & 1 for the logged means.
-    // kClip / kClipKl: the reduction alone, the slots in parity 0; then the norms, the KL decision on stats[1], the clip and Adam
-    constexpr bool kAdam = MODE == NavppoMode::kAdam, kClip = MODE == NavppoMode::kClip || MODE == NavppoMode::kClipKl;
+    // kClip / kClipKl / kClipLr: the reduction alone, the slots in parity 0; then the norms, the KL decision (kClipKl) or the learning
+    // rate (kClipLr) from stats[1], the clip and Adam
+    constexpr bool kAdam = MODE == NavppoMode::kAdam, kLr = MODE == NavppoMode::kClipLr;
+    constexpr bool kClip = MODE == NavppoMode::kClip || MODE == NavppoMode::kClipKl || kLr;
     const int rblocks = (rp::P_ACTOR + rp::P_CRITIC + 63) / 64;
     const NavppoStep r = kAdam ? s : NavppoStep{};
     const NavppoBias bc = kAdam ? navppo_bias(s.beta1, s.beta2, s.step) : NavppoBias{1.f, 1.f};
@@ -1221,7 +1223,7 @@ int loss_grad_impl(const char* name, float* params, const void* obs, int32_t obs
                        r.beta2, r.eps, bc.bc1, bc.bc2_sqrt, parity >= 0 ? p.epart : nullptr, parity NAVPPO_KL_ARG(s.kl_state));
     if constexpr (kClip)
         navppo_launch_clip_adam(params, grad, rp::P_ACTOR + rp::P_CRITIC, rp::P_ACTOR, 1.0f, s, p.epart, rblocks, kGnSlotsR, EP, stream,
-                                MODE == NavppoMode::kClipKl ? stats + 1 : nullptr);
+                                MODE == NavppoMode::kClipKl || kLr ? stats + 1 : nullptr, kLr);
     return navppo_launched(name);
 }
 
@@ -1259,6 +1261,18 @@ int navppo_resmlp512_update_epoch_clipped(float* params_dev, const void* obs_dev
                                              {act_dev, logp_old_dev, rtg_dev, adv_dev, n_samples, var, clip},
                                              {lr, beta1, beta2, eps, step, adam_m_dev, adam_v_dev, max_norm, clip_stats_dev}, grad_dev, stats_dev,
                                              workspace_dev, stream);
+}
+
+int navppo_resmlp512_update_epoch_lr(float* params_dev, const void* obs_dev, int32_t obs_f16, const float* act_dev, const float* logp_old_dev,
+                                     const float* rtg_dev, const float* adv_dev, int64_t n_samples, float var, float clip, float lr,
+                                     float beta1, float beta2, float eps, int32_t step, float* adam_m_dev, float* adam_v_dev,
+                                     float* grad_dev, float* stats_dev, void* workspace_dev, float max_norm, float* clip_stats_dev,
+                                     float kl_target, float lr_min, float lr_max, int32_t adapt, float* lr_state_dev, void* stream) {
+    return loss_grad_impl<NavppoMode::kClipLr>("navppo_resmlp512_update_epoch_lr", params_dev, obs_dev, obs_f16,
+                                               {act_dev, logp_old_dev, rtg_dev, adv_dev, n_samples, var, clip},
+                                               {lr, beta1, beta2, eps, step, adam_m_dev, adam_v_dev, max_norm, clip_stats_dev, 0.f, nullptr,
+                                                kl_target, lr_min, lr_max, adapt, lr_state_dev},
+                                               grad_dev, stats_dev, workspace_dev, stream);
 }
 
 int navppo_resmlp512_value(const float* critic_params_dev, const void* obs_dev, int32_t obs_f16, int64_t n_samples, float* value_dev,

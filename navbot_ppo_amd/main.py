@@ -15,7 +15,8 @@ stepping loop), --eval_every K (training: a persistent evaluation of --eval_epis
 (per-net gradient clipping + non-finite guard inside the update), --target_kl (stop an update's remaining epochs once approx_kl
 exceeds 1.5 x the target), --minibatch_size M / --minibatch_shuffle MODE (K = ceil(batch / M) optimiser steps per epoch on slices of the
 batch, shuffled on the device), --norm_reward / --clip_reward C (rewards scaled by the running standard deviation of the discounted
-return and clipped to +-C before the return scan), --movers NAME / --movers_period P (moving obstacles beside the static map, training and evaluation).  Vision flags are accepted and refused (the camera
+return and clipped to +-C before the return scan), --lr_schedule adaptive|linear with --desired_kl / --lr_min / --lr_max (the KL-adaptive
+step size decided on the device after every optimiser step, or a linear decay over --max_timesteps), --movers NAME / --movers_period P (moving obstacles beside the static map, training and evaluation).  Vision flags are accepted and refused (the camera
 modality is outside the LiDAR hot path); --mode test maps to --eval (the reference's test path is broken).
 """
 import argparse
@@ -68,6 +69,13 @@ def get_args(argv=None):
                    help="divide every rollout's rewards by the running standard deviation of the discounted return before the return "
                         "scan (VecNormalize's norm_reward, on the device); metrics and CSVs stay raw; default: off, as in the reference")
     p.add_argument("--clip_reward", type=float, default=10.0, help="with --norm_reward: the scaled rewards are clipped to +- this")
+    p.add_argument("--lr_schedule", type=str, default=None, choices=["adaptive", "linear"],
+                   help="adaptive: after every optimiser step lr /= 1.5 if its approx_kl > 2 x --desired_kl, lr *= 1.5 if below half of it "
+                        "(decided on the device inside the fused update; not with --target_kl); linear: lr x (1 - t / max_timesteps) per "
+                        "iteration; default: the constant lr of the reference")
+    p.add_argument("--desired_kl", type=float, default=0.01, help="with --lr_schedule adaptive: the KL per optimiser step the rule steers towards")
+    p.add_argument("--lr_min", type=float, default=1e-5, help="with --lr_schedule adaptive: the lower clamp of the learning rate")
+    p.add_argument("--lr_max", type=float, default=1e-2, help="with --lr_schedule adaptive: the upper clamp of the learning rate")
     p.add_argument("--movers", type=str, default=None,
                    help="moving obstacles cast beside the static map (maps.movers_by_name: orbit4 = four pillars orbiting the spawn "
                         "pose); authored geometry: parity unpinned (no reference geometry); default: none")
@@ -102,7 +110,8 @@ def config_of(args, rollout):
                          save_freq=args.save_every_iterations, output_dir=args.output_dir, method_name=args.method_name,
                          eval_every=args.eval_every, eval_episodes=args.eval_episodes, max_grad_norm=args.max_grad_norm,
                          target_kl=args.target_kl, minibatch_size=args.minibatch_size, minibatch_shuffle=args.minibatch_shuffle,
-                         norm_reward=args.norm_reward, clip_reward=args.clip_reward)
+                         norm_reward=args.norm_reward, clip_reward=args.clip_reward, lr_schedule=args.lr_schedule,
+                         desired_kl=args.desired_kl, lr_min=args.lr_min, lr_max=args.lr_max)
 
 
 def main(argv=None):

@@ -14,6 +14,9 @@ Follows ``project_ppo/src/ppo.py`` of the reference function by function, vector
                                     check of ppo.py:356-379,414-416 is PPOTrainer._grad_guard)
                                     PPOConfig.minibatch_size: K optimiser steps per epoch on slices of the batch, shuffled
                                     on the device (navppo_shuffle_batch; host mirror: batch_permutation)
+                                    PPOConfig.lr_schedule: "adaptive" = the learning rate follows every step's approx_kl, decided
+                                    on the device (navppo_*_update_epoch_lr; host mirror: adaptive_lr_reference); "linear" = decay
+                                    over learn()'s budget, set per iteration
   learn            ppo.py:218-461   iteration loop, timing, checkpoints (actor_iter%04d_step%08d.pth)
 
 Multi-GPU (absent in the reference): one process per GPU, each owns a contiguous shard
@@ -55,7 +58,7 @@ class PPOConfig:
     max_episode_steps: int = 500           # main.py / arguments.py:30 (timesteps_per_episode)
     gamma: float = 0.99                    # main.py:470
     n_updates_per_iteration: int = 50      # main.py:471
-    lr: float = 3e-4                       # main.py:472
+    lr: float = 3e-4                       # main.py:472 (lr_schedule: where the rate starts)
     clip: float = 0.2                      # main.py:473
     policy: str = "resmlp512"              # reference nets; "mlp64x2" = BASELINE config 2
     gae_lambda: float = None               # None = the reference's estimator A = rtgs - V (ppo.py:277); a number in [0, 1] turns
@@ -104,6 +107,16 @@ class PPOConfig:
     norm_reward: bool = False
     clip_reward: float = 10.0              # VecNormalize's clip_reward
     norm_reward_eps: float = 1e-8          # VecNormalize's epsilon: scale = 1 / sqrt(var + eps)
+    # None = the reference: `lr` is one constant.  "adaptive" = the KL-adaptive step size of rsl_rl / rl_games: after every optimiser step
+    # but the first of an update, lr /= 1.5 if that step's approx_kl > 2 desired_kl, lr *= 1.5 if 0 < approx_kl < desired_kl / 2, clamped
+    # to [lr_min, lr_max]; it starts at `lr` and carries over from update to update.  On one GPU the decision is taken on the device, in
+    # the step launch of navppo_*_update_epoch_lr (host mirror: adaptive_lr_reference).  Not with target_kl, not with overlap_allreduce.
+    # "linear" = lr x max(0, 1 - t_so_far / total_timesteps), set at the start of every iteration of learn() (Stable-Baselines3's linear
+    # schedule, CleanRL's anneal_lr): host only, the existing entry points take it as their lr argument.
+    lr_schedule: str = None
+    desired_kl: float = 0.01               # "adaptive": the KL the rule steers the per-step approx_kl towards
+    lr_min: float = 1e-5                   # "adaptive": the clamps of the learning rate
+    lr_max: float = 1e-2
     output_dir: str = ""                   # "" = no checkpoints / logs
     episode_csv_rows: int = 2000           # per-iteration cap on rows appended to <method>_train_episodes.csv (0 = off)
     tb_episode_rows: int = 256             # per-iteration cap on Episode_Rewards/train points in the TensorBoard file (0 = off)
@@ -117,6 +130,7 @@ class PPOConfig:
     def __post_init__(self):
         check_minibatch_config(self)
         check_reward_norm_config(self)
+        check_lr_schedule_config(self)
 
 
 # --------------------------------------------------------------------------- minibatch updates
@@ -301,6 +315,66 @@ def reward_norm_reference(rew, ended, gamma, rms=RET_RMS_INIT, carry=None, clip=
     return types.SimpleNamespace(moments=moments, carry=R, rms=np.append(m, scale), out=out)
 
 
+# --------------------------------------------------------------------------- learning-rate schedules
+LR_SCHEDULES = (None, "adaptive", "linear")
+LR_FACTOR = 1.5   # the rule's step (rsl_rl, rl_games); not configurable
+
+
+def check_lr_schedule_config(cfg):
+    """PPOConfig.lr_schedule and its parameters, at the construction of the config and again of the updater (a config is mutable)."""
+    if cfg.lr_schedule not in LR_SCHEDULES:
+        raise ValueError(f"lr_schedule {cfg.lr_schedule!r}: one of {LR_SCHEDULES}")
+    if cfg.lr_schedule != "adaptive":
+        return
+    if cfg.target_kl is not None:
+        raise ValueError("lr_schedule='adaptive' with target_kl: two answers to the same signal; choose one")
+    if cfg.overlap_allreduce:
+        raise ValueError("lr_schedule='adaptive' with overlap_allreduce=True: the per-net pipeline has no place for the decision")
+    for name in ("desired_kl", "lr_min", "lr_max"):
+        if not float(getattr(cfg, name)) > 0.0:   # (NaN fails the comparison too)
+            raise ValueError(f"{name} {getattr(cfg, name)!r}: a number > 0")
+    if not float(cfg.lr_max) >= float(cfg.lr_min):
+        raise ValueError(f"lr_max {cfg.lr_max!r} < lr_min {cfg.lr_min!r}")
+    if not float(cfg.lr_min) <= float(cfg.lr) <= float(cfg.lr_max):
+        raise ValueError(f"lr {cfg.lr!r} outside [lr_min, lr_max] = [{cfg.lr_min!r}, {cfg.lr_max!r}]")
+
+
+def adaptive_lr_direction(kl, desired_kl, adapt=True):
+    """The branch of the rule an optimiser step with approx_kl `kl` takes: -1 = lower, +1 = raise, 0 = keep.  float32 comparisons, the
+    expressions of clip_adam_lr_kernel (include/navppo.h, "Adaptive learning rate"): a NaN or +inf kl lowers; kl <= 0 keeps."""
+    import numpy as np
+    f = np.float32
+    if not adapt:
+        return 0
+    with np.errstate(all="ignore"):
+        kl, tgt = f(kl), f(desired_kl)
+        if not (kl <= f(2.0) * tgt):
+            return -1
+        if kl < f(0.5) * tgt and kl > f(0.0):
+            return 1
+    return 0
+
+
+def adaptive_lr_reference(lr, kl, desired_kl, lr_min, lr_max, adapt=True):
+    """Host mirror of the learning rate clip_adam_lr_kernel steps with: float32 arithmetic, bit for bit.  lr: the rate before the step;
+    returns the rate of this step (a Python float holding the float32 value)."""
+    import numpy as np
+    f = np.float32
+    lr = f(lr)
+    d = adaptive_lr_direction(kl, desired_kl, adapt)
+    with np.errstate(all="ignore"):
+        if d < 0:
+            lr = max(f(lr_min), lr / f(LR_FACTOR))
+        elif d > 0:
+            lr = min(f(lr_max), lr * f(LR_FACTOR))
+    return float(lr)
+
+
+def linear_lr(lr, t_so_far, total_timesteps):
+    """lr_schedule="linear": the rate of an iteration that starts after t_so_far of total_timesteps"""
+    return float(lr) * max(0.0, 1.0 - float(t_so_far) / float(total_timesteps))
+
+
 # --------------------------------------------------------------------------- distributed context
 class DistCtx:
     """torch.distributed wrapper that degrades to a no-op for a single process."""
@@ -479,12 +553,22 @@ class PPOUpdater:
             raise ValueError("target_kl with overlap_allreduce=True: the per-net pipeline has no place for the stop decision")
         self.kl_limit = None if cfg.target_kl is None else 1.5 * float(cfg.target_kl)   # Stable-Baselines3's factor
         check_minibatch_config(cfg)
+        check_lr_schedule_config(cfg)
+        # lr_schedule: lr_adaptive = the rule runs after every optimiser step; lr_value = the rate the next step starts from (adaptive),
+        # or the rate set_lr() put in force ("linear": the trainer, per iteration); None = cfg.lr as it stands at every call
+        self.lr_adaptive = cfg.lr_schedule == "adaptive"
+        self.lr_value = float(cfg.lr) if self.lr_adaptive else None
+        self.lr_state = None     # adaptive, fused: [4] (two rate slots, raises, lowerings) on the device, zeroed here: the first step starts at cfg.lr
+        self.lr_counts = (0, 0)  # adaptive: raises and lowerings since construction
+        self.kl_steps = None     # adaptive: [steps] the approx_kl (global, on several ranks) of every optimiser step of the last update()
+        self._lr_step = 0        # adaptive: optimiser steps queued in the update in flight (the first one does not adapt)
         self.update_index = 0    # updates run so far: the high word of the shuffle's counter
         self._mb_key = minibatch_key(cfg.seed, ctx.rank if ctx is not None else 0)
         self._mb = None          # the minibatch plan of the update in flight (_plan_minibatches); None = whole-batch epochs
         self._shuf = self._shuf_key = None   # the ONE permuted copy of the batch (navppo_shuffle_batch's outputs), regrown like _prep
         # the clipped machinery runs and fills clip_stats: max_grad_norm, or target_kl alone -- at max_norm = +inf: the unclipped epochs' bits
-        self._clipping = self.max_norm is not None or self.kl_limit is not None
+        # (adaptive lr: the step launch is the clipped one's)
+        self._clipping = self.max_norm is not None or self.kl_limit is not None or self.lr_adaptive
         self.kl_state = None     # target_kl on, fused: [4] (stopped, steps taken, tripping approx_kl, its step) of the last update(), on the device
         self.clip_stats = None   # clipping on: [n_ep, 4] (s_actor, s_critic, coef_actor, coef_critic) of the last update(), on the device
         self.fused_resmlp512 = (on_gpu and cfg.policy == "resmlp512" and isinstance(actor, nets.ResMLPActor)
@@ -513,6 +597,26 @@ class PPOUpdater:
             self._adam_m = torch.zeros_like(self.fp.flat)
             self._adam_v = torch.zeros_like(self.fp.flat)
             self._adam_t = 0
+            if self.lr_adaptive:
+                self.lr_state = torch.zeros(4, dtype=torch.float32, device=self.device)
+
+    def _lr(self):
+        """the `lr` argument of the fused entry points (adaptive: where a zeroed state starts)"""
+        return float(self.cfg.lr if self.lr_value is None or self.lr_adaptive else self.lr_value)
+
+    def set_lr(self, lr):
+        """Puts a learning rate in force: lr_schedule="linear" (the trainer, per iteration), and the resumed rate of "adaptive" -- into
+        BOTH slots of the device state, whichever the next step reads."""
+        self.lr_value = float(lr)
+        self.opt.param_groups[0]["lr"] = self.lr_value
+        if self.lr_state is not None:
+            self.lr_state[:2] = self.lr_value
+
+    def _lr_args(self):
+        """kl_target, lr_min, lr_max, adapt, lr_state_dev of the *_lr entry points; counts the step: the first of an update does not adapt"""
+        cfg, adapt = self.cfg, int(self._lr_step > 0)
+        self._lr_step += 1
+        return (float(cfg.desired_kl), float(cfg.lr_min), float(cfg.lr_max), adapt, _ptr(self.lr_state))
 
     def _workspace(self, n):
         """Scratch of the fused kernels: fixed for the 2x64 heads, per-sample partial block outputs for the 512-wide nets."""
@@ -586,19 +690,22 @@ class PPOUpdater:
     def _fused_adam(self, grad_scale, lo=0, n=None, step=None, cstats=None, kl_dev=None):
         """Scale + Adam on the flat buffer, or on the slice [lo, lo + n) at optimiser step `step` (one net of the pipelined epoch).
         cstats ([4], clipping on): navppo_adam_step_clipped -- per-net norm, guard and clip of the scaled gradient first.
-        kl_dev ([1], target_kl on; with cstats): navppo_adam_step_kl -- the stop decision on the global approx_kl in front of that."""
+        kl_dev ([1], target_kl on; with cstats): navppo_adam_step_kl -- the stop decision on the global approx_kl in front of that;
+        adaptive lr: navppo_adam_step_lr -- the step's rate from the global approx_kl and the device state."""
         if step is None:
             self._adam_t += 1
             step = self._adam_t
         n_ = int(self.fp.numel - lo if n is None else n)
         head = tuple(_ptr(t, 4 * lo) for t in (self.fp.flat, self.fp.grad, self._adam_m, self._adam_v)) + (n_,)
-        hyper = (float(self.cfg.lr), *ADAM_HYPER, int(step))
+        hyper = (self._lr(), *ADAM_HYPER, int(step))
         if cstats is None and kl_dev is None:
             entry, args = "navppo_adam_step", head + (float(grad_scale),) + hyper
         else:
             entry = "navppo_adam_step_clipped"
             args = head + (max(0, min(n_, self._n_actor - lo)), float(grad_scale), self._max_norm_arg()) + hyper + (_ptr(cstats),)
-            if kl_dev is not None:
+            if kl_dev is not None and self.lr_adaptive:
+                entry, args = "navppo_adam_step_lr", args + self._lr_args() + (_ptr(kl_dev),)
+            elif kl_dev is not None:
                 entry, args = "navppo_adam_step_kl", args + (self.kl_limit, _ptr(self.kl_state), _ptr(kl_dev))
         _navppo(entry, *args)
 
@@ -659,7 +766,9 @@ class PPOUpdater:
             mode, extra = "_clipped", (self._max_norm_arg(), _ptr(cstats))
         if self.kl_limit is not None:
             mode, extra = "_kl", extra + (self.kl_limit, _ptr(self.kl_state))
-        _navppo(fam + "_update_epoch" + mode, _ptr(self.fp.flat), *batch, float(self.cfg.lr), *ADAM_HYPER, int(self._adam_t),
+        elif self.lr_adaptive:   # the clipped epoch's launches, the step launch derives its rate on the device
+            mode, extra = "_lr", extra + self._lr_args()
+        _navppo(fam + "_update_epoch" + mode, _ptr(self.fp.flat), *batch, self._lr(), *ADAM_HYPER, int(self._adam_t),
                 _ptr(self._adam_m), _ptr(self._adam_v), _ptr(self.fp.grad), _ptr(stats), _ptr(self._workspace(obs.shape[0])), *extra)
 
     def _clip_and_step(self, ep):
@@ -813,18 +922,21 @@ class PPOUpdater:
             self._fused_epoch(*sl, var_f, self._fhist[st], self.clip_stats[st] if self._clipping else None)
             if gn is not None:
                 gn[st] = torch.stack(torch._foreach_norm([self.fp.grad[:n_a], self.fp.grad[n_a:]]))
+        if self.lr_adaptive:
+            self.kl_steps = self._fhist[:self._lr_step, 1].clone()
         return self._fused_record(n_ep, V0, world, r0, *((gn.pow(2).sum(1).sqrt().sum(), gn.sum(0)) if gn is not None and n_ep > 0 else ()))
 
     def _run_fused_multi(self, n_ep, batch, var_f, V0, multi, world, r0):
         """Several GPUs: fused passes -> ONE all-reduce of the flat gradient (RCCL) -> scale + Adam in one launch."""
         ctx, n_a, gn = self.ctx, self._n_actor, None   # gn: step sums of the MEAN gradient's (actor, critic, whole) norm
         n_st = n_ep * (self._mb["K"] if self._mb is not None else 1)
-        kl_glob = torch.zeros((max(n_st, 1), 2), dtype=torch.float32, device=self.device) if self.kl_limit is not None else None
+        need_kl = self.kl_limit is not None or self.lr_adaptive   # (adaptive lr: every rank must derive the same rate)
+        kl_glob = torch.zeros((max(n_st, 1), 2), dtype=torch.float32, device=self.device) if need_kl else None
         for ep, sl in enumerate(self._steps(n_ep, batch)):   # (ep: the step -- an epoch, or a slice of one)
             n = float(sl[0].shape[0])
             self._fused_loss_grad(*sl, var_f, stats=self._fhist[ep])
             ctx.all_reduce_sum(self.fp.grad)
-            if self.kl_limit is not None:
+            if need_kl:
                 # the global approx_kl = sum(kl_r n_r) / sum(n_r), a 2-float collective; the passes are ungated: a stop only keeps the weights
                 kg = kl_glob[ep]
                 kg[0], kg[1] = self._fhist[ep, 1] * n, n
@@ -837,6 +949,8 @@ class PPOUpdater:
                 g3 = torch.stack(torch._foreach_norm([self.fp.grad[:n_a], self.fp.grad[n_a:], self.fp.grad])) / world
                 gn = g3 if gn is None else gn + g3
                 self._fused_adam(1.0 / world)
+        if self.lr_adaptive:
+            self.kl_steps = kl_glob[:n_st, 0]
         return self._fused_record(n_ep, V0, world, r0, *((gn[2], gn[:2]) if gn is not None else ()))
 
     def _run_fused_pipelined(self, n_ep, batch, var_f, V0, multi, world, r0):
@@ -850,6 +964,7 @@ class PPOUpdater:
         K = self._mb["K"] if self._mb is not None else 1
         steps, stopped, losses = n_ep * K, 0, torch.zeros((n_ep * K, 2), device=batch[0].device)   # (a row per step)
         acc, net_gn = torch.zeros(6, device=batch[0].device), None  # sums over steps of the diagnostics and of the per-net gradient norms
+        kls = []   # adaptive lr: every step's (global) approx_kl, float32
         for ep, (obs, acts, logp_old, rtg, adv) in enumerate(self._steps(n_ep, batch)):   # ppo.py:305 (ep: the step -- an epoch, or a slice of one)
             a_loss, c_loss, ratios, logp, _ = ppo_losses(self.actor, self.critic, obs, acts, logp_old, rtg, adv, var, self.cfg.clip)
             self.fp.grad.zero_()
@@ -863,6 +978,18 @@ class PPOUpdater:
                 if multi:
                     self.ctx.all_reduce_sum(kg)
                 trip = not (float(kg[0] / kg[1]) <= self.kl_limit)
+            if self.lr_adaptive:   # the rule before the step, on the global approx_kl, through the kernel's host mirror; not on an update's first step
+                kl = float(((ratios - 1) - lr_).mean())
+                if multi:   # (weighted by the ranks' batch sizes, as target_kl's)
+                    kg = torch.stack([((ratios - 1) - lr_).sum(), lr_.new_tensor(float(lr_.numel()))])
+                    self.ctx.all_reduce_sum(kg)
+                    kl = float(kg[0] / kg[1])
+                d = adaptive_lr_direction(kl, self.cfg.desired_kl, adapt=ep > 0)
+                self.lr_value = adaptive_lr_reference(self.lr_value, kl, self.cfg.desired_kl, self.cfg.lr_min, self.cfg.lr_max, adapt=ep > 0)
+                self.lr_counts = (self.lr_counts[0] + (d > 0), self.lr_counts[1] + (d < 0))
+                self.opt.param_groups[0]["lr"] = self.lr_value
+                kls.append(kl)
+                self._lr_step += 1
             if trip:   # neither net is stepped; the gradient stays unclipped, the coefficients are reported as 0, the remaining epochs do not run
                 steps, stopped = ep, 1
                 self._clip_row(ep, 0.0)
@@ -880,6 +1007,8 @@ class PPOUpdater:
                 net_gn = g2 if net_gn is None else net_gn + g2
             if trip:
                 break
+        if self.lr_adaptive:
+            self.kl_steps = torch.tensor(kls, dtype=torch.float32)
         return _Epochs(k=steps + stopped, steps=steps, stopped=stopped, losses=self._epoch_losses(losses, steps + stopped, n_ep), sums=acc[:4],
                        gn_sum=acc[4], v_sum=acc[5], net_gn=net_gn, K=K)
 
@@ -915,8 +1044,21 @@ class PPOUpdater:
         keys = ["actor_loss", "critic_loss", "approx_kl", "clip_frac", "grad_norm", "value_mean", "actor_grad_norm", "critic_grad_norm",
                 "actor_param_delta", "critic_param_delta",
                 "grad_clip_frac_actor", "grad_clip_frac_critic", "skipped_steps_actor", "skipped_steps_critic"]
-        vals = [float(v) for v in torch.cat([acc, extra] + (clip_cols if self.max_norm is not None else [])).tolist()]
+        lr_cols = [self.lr_state] if self.lr_state is not None else []   # (adaptive lr, fused: the state rides on this read-back)
+        vals = [float(v) for v in torch.cat([acc, extra] + (clip_cols if self.max_norm is not None else []) + lr_cols).tolist()]
+        if lr_cols:   # the slot the last step wrote; the counts are cumulative
+            vals, st = vals[:-4], vals[-4:]
+            if self._lr_step > 0:
+                self.lr_value = st[(self._adam_t + 1) & 1]
+            ups, downs = int(st[2]), int(st[3])
+        elif self.lr_adaptive:
+            ups, downs = self.lr_counts
         stats = dict(zip(keys, vals[:12] + [int(v) for v in vals[12:]]))
+        if self.lr_adaptive:   # the rate after the update's last step, the raises and lowerings of this update; identical on every rank
+            stats["lr"], stats["lr_ups"], stats["lr_downs"] = self.lr_value, ups - self._lr_counts0[0], downs - self._lr_counts0[1]
+            self.lr_counts = (ups, downs)
+        elif self.lr_value is not None:   # ("linear": the rate this update ran with)
+            stats["lr"] = self.lr_value
         if self.kl_limit is not None:   # steps taken (n_ep if the update never stopped) and whether it stopped; identical on every rank
             # (minibatches: kl_stop_step counts the steps, kl_stop_epoch the whole epochs completed)
             stats["kl_stop_epoch"], stats["kl_stopped"] = r.steps // r.K, r.stopped
@@ -940,6 +1082,7 @@ class PPOUpdater:
             obs = obs.float()   # half rows (obs_f16 envs) are consumed as they are by the fused kernels only
         batch = (obs, acts, logp_old, rtg, adv)
         self._mb = self._plan_minibatches(int(obs.shape[0]), multi)
+        self._lr_step, self._lr_counts0 = 0, self.lr_counts
         n_st = n_ep * (self._mb["K"] if self._mb is not None else 1)   # optimiser steps: a row of every per-step buffer each
         shuffling = self._mb is not None and self._mb["mode"] != "none"
         if self.fused:
@@ -1421,6 +1564,7 @@ class PPOTrainer:
                 "ppo/skipped_steps_actor": lg.get("skipped_steps_actor"), "ppo/skipped_steps_critic": lg.get("skipped_steps_critic"),
                 "ppo/kl_stop_epoch": lg.get("kl_stop_epoch"), "ppo/kl_stopped": lg.get("kl_stopped"),   # (target_kl set)
                 **({"ppo/kl_stop_step": lg["kl_stop_step"]} if "kl_stop_step" in lg else {}),           # (target_kl and minibatches)
+                **({"ppo/" + k: lg[k] for k in ("lr", "lr_ups", "lr_downs") if k in lg}),               # (lr_schedule set)
                 **({"ppo/" + k: lg[k] for k in ("reward_scale", "ret_rms_mean", "ret_rms_std", "explained_variance")}
                    if "reward_scale" in lg else {}),                                                    # (norm_reward)
                 **({"eval/success_rate": lg["eval_success"], "eval/collision_rate": lg["eval_collision"],
@@ -1469,6 +1613,8 @@ class PPOTrainer:
         per_iter = self.cfg.rollout_len * self.env.N * world
         max_iters = 4 * (-(-int(total_timesteps) // per_iter)) + 4
         while self.t_so_far < total_timesteps and self.i_so_far < max_iters:  # ppo.py:245
+            if self.cfg.lr_schedule == "linear":
+                self.updater.set_lr(linear_lr(self.cfg.lr, self.t_so_far, total_timesteps))
             lg = self.iteration()
             if log and (self.ctx is None or self.ctx.rank == 0):
                 log(f"[iter {lg['iteration']:4d}] t={lg['t_so_far']:>10d} mean_ep_rew={lg['avg_ep_rews']:8.2f} "
@@ -1477,6 +1623,8 @@ class PPOTrainer:
                     f"(rollout {lg['rollout_time']:.3f}s update {lg['update_time']:.3f}s)"
                     + (f" kl_stop_epoch={lg['kl_stop_epoch']} kl_stopped={lg['kl_stopped']}" if "kl_stop_epoch" in lg else "")
                     + (f" kl_stop_step={lg['kl_stop_step']}" if "kl_stop_step" in lg else "")
+                    + (f" lr={lg['lr']:.3e}" if "lr" in lg else "")
+                    + (f" lr_ups={lg['lr_ups']} lr_downs={lg['lr_downs']}" if "lr_ups" in lg else "")
                     + (f" eval: succ={lg['eval_success']:.3f} coll={lg['eval_collision']:.3f} tmo={lg['eval_timeout']:.3f} "
                        f"ret={lg['eval_return']:.2f} len={lg['eval_length']:.1f} ({lg['eval_time']:.3f}s)"
                        if "eval_success" in lg else ""))
@@ -1496,6 +1644,8 @@ class PPOTrainer:
         if self.cfg.norm_reward:   # a third file beside the two reference-named ones: the critic's units
             mean, var, count = self.ret_rms[:3].tolist()
             torch.save({"mean": mean, "var": var, "count": count}, os.path.join(d, "retnorm_" + tag))
+        if self.cfg.lr_schedule == "adaptive":   # the rate the next step starts from (on the host since the last update's read-back)
+            torch.save({"lr": float(self.updater.lr_value)}, os.path.join(d, "lrsched_" + tag))
         return pa, pc
 
     @staticmethod
@@ -1504,9 +1654,24 @@ class PPOTrainer:
         d, base = os.path.split(actor_path)
         return os.path.join(d, "retnorm_" + (base[len("actor_"):] if base.startswith("actor_") else base))
 
+    @staticmethod
+    def lrsched_path(actor_path):
+        """lrsched_<tag>.pth beside actor_<tag>.pth"""
+        d, base = os.path.split(actor_path)
+        return os.path.join(d, "lrsched_" + (base[len("actor_"):] if base.startswith("actor_") else base))
+
     def load_checkpoint(self, actor_path, critic_path):
         """main.py:52-89: state_dicts only (optimiser state and covariance are not part of a checkpoint).  With norm_reward the return
-        statistics come from retnorm_<tag>.pth beside the actor's file; without that file: one warning line and fresh statistics."""
+        statistics come from retnorm_<tag>.pth beside the actor's file; without that file: one warning line and fresh statistics.
+        With lr_schedule="adaptive" the learning rate comes from lrsched_<tag>.pth; without that file: one warning line and cfg.lr."""
+        if self.cfg.lr_schedule == "adaptive":
+            pl = self.lrsched_path(actor_path)
+            if os.path.exists(pl):
+                self.updater.set_lr(float(torch.load(pl, map_location="cpu")["lr"]))
+            else:
+                import warnings
+                warnings.warn(f"lr_schedule='adaptive': {pl} not found -- the learning rate starts at lr = {self.cfg.lr}")
+                self.updater.set_lr(float(self.cfg.lr))
         if self.cfg.norm_reward:
             pr = self.retnorm_path(actor_path)
             if os.path.exists(pr):
