@@ -258,6 +258,31 @@ int navsim_gae_scan(const float* rew_dev, const uint8_t* ended_dev, const float*
                     int32_t N, double gamma, double lam, float* adv_dev, float* ret_dev, int32_t exact, void* stream);
 
 /*
+ * The truncation-aware form of navsim_gae_scan -- partial-episode bootstrapping (Pardo et al. 2018) by rsl_rl's rule; an EXTENSION,
+ * off by default (PPOConfig.bootstrap_truncated = False).  The two scans above treat every episode end as terminal; an episode
+ * that merely ran into max_episode_steps did not end for the robot, and regressing on "the return stops here" teaches the critic
+ * a clock the observation does not hold.  A TIME-OUT is a row with ended set and neither done nor arrive (navppo_episode_sums'
+ * definition); the value of the state behind it, which no buffer holds (the step kernels overwrite the terminal observation with
+ * the reset one), is estimated by V of the row itself -- rsl_rl: rewards += gamma * values * time_outs.
+ *   done_dev, arrive_dev [T,N] u8 as navsim_step / the rollouts write them; the other buffers as in navsim_gae_scan.
+ * Per column, from the last row backwards, float64, the expressions as written (the library is built with -ffp-contract=off):
+ *     trunc[t] = ended[t] && !done[t] && !arrive[t]
+ *     add      = (double)rew[t] + (trunc[t] ? gamma * (double)V[t] : ended[t] ? 0.0 : gamma * (1 - lam) * (double)V[t+1])
+ *     R[t]     = add + R[t+1] * (ended[t] ? 0.0 : gamma * lam)          V[T] = R[T] = last_value, or 0 when last_value_dev is NULL
+ *     ret_dev [T,N] (nullable) = float32(R[t])     adv_dev [T,N] = float32(R[t]) - V[t]
+ * Rows with done or arrive set but ended clear (respawn_on_arrive, handles without auto_reset) do not truncate.  What stays
+ * terminal: collisions and arrivals, and the batch end unless last_value_dev bootstraps it.
+ * Contract (that of the scans above): N % 16 == 0 and exact == 0 run the T-split kernel, every stored float32 within ONE ulp of the
+ * serial recurrence and bit-identical to it on every row with ended set (the factor there is 0: the carry-in does not enter);
+ * any other N, or exact != 0, runs the serial recurrence bit for bit.  With no time-out in the batch both outputs are bit-identical
+ * to navsim_gae_scan's with the same arguments.  NAVSIM_E_ARG, before any HIP call: a negative size; (T, N > 0) a null rew / ended /
+ * done / arrive / value / adv; lam outside [0, 1] (NaN included).  gamma is not checked.  T == 0 or N == 0: nothing to do, NAVSIM_OK.
+ */
+int navsim_gae_scan_trunc(const float* rew_dev, const uint8_t* ended_dev, const uint8_t* done_dev, const uint8_t* arrive_dev,
+                          const float* value_dev, const float* last_value_dev, int32_t T, int32_t N, double gamma, double lam,
+                          float* adv_dev, float* ret_dev, int32_t exact, void* stream);
+
+/*
  * The hot loop of PPO.rollout (project_ppo/src/ppo.py:505-594) for the (B + 6)-64-64 policy, all n_steps steps in ONE launch:
  * per step PPO.get_action (ppo.py:673-706; what navppo_mlp64_act computes, include/navppo.h) followed by what navsim_step
  * computes, for every env, with the rows of step t written at offset t * N of each [n_steps, N, .] buffer.  A workgroup

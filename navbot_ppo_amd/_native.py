@@ -64,6 +64,7 @@ SYMBOLS = [
     ("navsim_set_state", C.c_int, [_vp] * 8),
     ("navsim_rtg_scan", C.c_int, [_vp, _vp, _i32, _i32, _d, _vp, _i32, _vp]),
     ("navsim_gae_scan", C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _d, _d, _vp, _vp, _i32, _vp]),
+    ("navsim_gae_scan_trunc", C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _d, _d, _vp, _vp, _i32, _vp]),
     ("navsim_raycast", C.c_int, [_vp, _vp, _vp, _vp]),
     ("navsim_odometry", C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("navsim_rollout_mlp64", C.c_int, [_vp] * 13 + [C.c_uint64, _vp, _i32, _vp]),

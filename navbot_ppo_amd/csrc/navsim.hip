@@ -2418,10 +2418,19 @@ constexpr int kRtgCols = 16, kRtgChunks = 16, kRtgRows = 32, kRtgSuper = kRtgChu
 // (episode ends and the batch end are terminal as in ppo.py:552-553,658-666; last_value bootstraps the batch end only when
 // given), advantage A[t] = float32(R[t]) - V[t].  lambda = 1 without bootstrap: the additive term is r[t] + 0 and the factor
 // gamma * 1, i.e. the arithmetic of the return scan bit for bit, and A = rtg - V (ppo.py:277).
-template <bool GAE>
+//
+// TRUNC (off by default; navsim_gae_scan_trunc): a time-out -- ended without done or arrive, navppo_episode_sums' definition -- is
+// not the end of the robot: the value of the next state the batch never saw is estimated by V of the row itself (rsl_rl:
+// rewards += gamma * values * time_outs), so the additive term of such a row is r[t] + gamma V[t] while its factor stays 0 like
+// that of every episode end.  Two more byte streams (done, arrive), folded into the chunk's ended byte right at the load; rows
+// without a time-out evaluate the expressions of the GAE form, so a batch without one comes out bit-identical to it.
+template <bool GAE, bool TRUNC = false>
 __global__ __launch_bounds__(256) void rtg_kernel_split(const float* __restrict__ rew, const uint8_t* __restrict__ ended, int T, int N,
                                                         double gamma, float* __restrict__ out, const float* __restrict__ value,
-                                                        const float* __restrict__ last_value, double lam, float* __restrict__ adv) {
+                                                        const float* __restrict__ last_value, double lam, float* __restrict__ adv,
+                                                        const uint8_t* __restrict__ done = nullptr,
+                                                        const uint8_t* __restrict__ arrive = nullptr) {
+    static_assert(GAE || !TRUNC, "a time-out bootstraps with V: the truncation-aware scan is a GAE scan");
     __shared__ double s_b[kRtgChunks][kRtgCols], s_a[kRtgChunks][kRtgCols], s_sup[kRtgCols];
     const int tid = threadIdx.x, col = tid & (kRtgCols - 1), c = tid >> 4;
     // Workgroups go round-robin over the 8 XCDs (one L2 each) while a 128-byte line holds the rewards of 2 column blocks and
@@ -2455,6 +2464,10 @@ __global__ __launch_bounds__(256) void rtg_kernel_split(const float* __restrict_
             r[u] = rew[k];
             e[u] = ended[k];
             if (GAE) v[u] = value[k];
+            if constexpr (TRUNC) {   // both bytes loaded whatever `ended` holds (a load behind a select would wait for that byte first)
+                const uint8_t term = done[k] | arrive[k];
+                e[u] = e[u] ? (term ? 1 : 2) : 0;   // 2 = a time-out: ended, neither done nor arrive
+            }
         }
         // The batch end is terminal like an episode end (ppo.py:601,658) unless last_value bootstraps it: then the last row's
         // factor stays gamma lambda and R beyond it is last_value (rsup above), so R[T-1] = r + gamma (1-lambda) V_last + gamma lambda V_last
@@ -2463,7 +2476,8 @@ __global__ __launch_bounds__(256) void rtg_kernel_split(const float* __restrict_
 #pragma unroll
         for (int u = kRtgRows - 1; u >= 0; --u) {
             const double g = e[u] ? 0.0 : gl;
-            const double add = GAE ? (double)r[u] + (e[u] ? 0.0 : gv * (double)v[u + 1]) : (double)r[u];
+            double add = GAE ? (double)r[u] + (e[u] ? 0.0 : gv * (double)v[u + 1]) : (double)r[u];
+            if constexpr (TRUNC) add = (double)r[u] + (e[u] == 2 ? gamma * (double)v[u] : e[u] ? 0.0 : gv * (double)v[u + 1]);
             b = add + b * g;
             any |= e[u] != 0;
         }
@@ -2483,7 +2497,8 @@ __global__ __launch_bounds__(256) void rtg_kernel_split(const float* __restrict_
 #pragma unroll
         for (int u = kRtgRows - 1; u >= 0; --u) {
             const double g = e[u] ? 0.0 : gl;
-            const double add = GAE ? (double)r[u] + (e[u] ? 0.0 : gv * (double)v[u + 1]) : (double)r[u];
+            double add = GAE ? (double)r[u] + (e[u] ? 0.0 : gv * (double)v[u + 1]) : (double)r[u];
+            if constexpr (TRUNC) add = (double)r[u] + (e[u] == 2 ? gamma * (double)v[u] : e[u] ? 0.0 : gv * (double)v[u + 1]);
             R = add + R * g;   // ppo.py:665
             if (t0 + u >= 0) {
                 const size_t k = (size_t)(t0 + u) * N + n;
@@ -2530,6 +2545,32 @@ __global__ void gae_kernel_generic(const float* __restrict__ rew, const uint8_t*
         const float vt = value[k];
         const double g = e ? 0.0 : gl;
         const double add = (double)rew[k] + (e ? 0.0 : gv * (double)vnext);
+        R = add + R * g;
+        if (ret) ret[k] = (float)R;
+        adv[k] = (float)R - vt;
+        vnext = vt;
+    }
+}
+
+// the truncation-aware twin of gae_kernel_generic (navsim_gae_scan_trunc; the recurrence of rtg_kernel_split<true, true>, serially):
+// a time-out's additive term is r + gamma V of the row itself, everything else as above
+__global__ void gae_trunc_kernel_generic(const float* __restrict__ rew, const uint8_t* __restrict__ ended, const uint8_t* __restrict__ done,
+                                         const uint8_t* __restrict__ arrive, const float* __restrict__ value,
+                                         const float* __restrict__ last_value, int T, int N, double gamma, double lam,
+                                         float* __restrict__ adv, float* __restrict__ ret) {
+    const int n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= N) return;
+    const double gl = gamma * lam, gv = gamma * (1.0 - lam);
+    double R = last_value ? (double)last_value[n] : 0.0;
+    float vnext = last_value ? last_value[n] : 0.f;
+    for (int t = T - 1; t >= 0; --t) {
+        const size_t k = (size_t)t * N + n;
+        const bool e = ended[k] != 0;
+        const uint8_t term = done[k] | arrive[k];   // loaded whatever `ended` holds: no load waits for another
+        const bool trunc = e && !term;
+        const float vt = value[k];
+        const double g = e ? 0.0 : gl;
+        const double add = (double)rew[k] + (trunc ? gamma * (double)vt : e ? 0.0 : gv * (double)vnext);
         R = add + R * g;
         if (ret) ret[k] = (float)R;
         adv[k] = (float)R - vt;
@@ -3431,6 +3472,24 @@ int navsim_gae_scan(const float* rew_dev, const uint8_t* ended_dev, const float*
     else
         hipLaunchKernelGGL(gae_kernel_generic, dim3((N + 63) / 64), dim3(64), 0, (hipStream_t)stream, rew_dev, ended_dev, value_dev,
                            last_value_dev, T, N, gamma, lam, adv_dev, ret_dev);
+    HIP_TRY(hipGetLastError());
+    return NAVSIM_OK;
+}
+
+int navsim_gae_scan_trunc(const float* rew_dev, const uint8_t* ended_dev, const uint8_t* done_dev, const uint8_t* arrive_dev,
+                          const float* value_dev, const float* last_value_dev, int32_t T, int32_t N, double gamma, double lam,
+                          float* adv_dev, float* ret_dev, int32_t exact, void* stream) {
+    if (T < 0 || N < 0) return fail(NAVSIM_E_ARG, "navsim_gae_scan_trunc: negative size");
+    if (T == 0 || N == 0) return NAVSIM_OK;
+    if (!rew_dev || !ended_dev || !done_dev || !arrive_dev || !value_dev || !adv_dev)
+        return fail(NAVSIM_E_ARG, "navsim_gae_scan_trunc: null buffer");
+    if (!(lam >= 0.0 && lam <= 1.0)) return fail(NAVSIM_E_ARG, "navsim_gae_scan_trunc: lambda outside [0, 1]");
+    if (N % kRtgCols == 0 && !exact)
+        hipLaunchKernelGGL((rtg_kernel_split<true, true>), dim3(N / kRtgCols), dim3(256), 0, (hipStream_t)stream, rew_dev, ended_dev, T, N,
+                           gamma, ret_dev, value_dev, last_value_dev, lam, adv_dev, done_dev, arrive_dev);
+    else
+        hipLaunchKernelGGL(gae_trunc_kernel_generic, dim3((N + 63) / 64), dim3(64), 0, (hipStream_t)stream, rew_dev, ended_dev, done_dev,
+                           arrive_dev, value_dev, last_value_dev, T, N, gamma, lam, adv_dev, ret_dev);
     HIP_TRY(hipGetLastError());
     return NAVSIM_OK;
 }

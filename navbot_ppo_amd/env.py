@@ -20,7 +20,7 @@ import torch
 from . import maps as _maps
 from ._native import NavsimCfg, NavsimError, NavsimInfo, check, lib
 
-__all__ = ["NavSim", "VecEnv", "Env", "NavsimError", "rtg_scan", "gae_scan"]
+__all__ = ["NavSim", "VecEnv", "Env", "NavsimError", "rtg_scan", "gae_scan", "gae_scan_trunc", "truncated_returns_reference"]
 
 
 def _ptr(t):
@@ -322,6 +322,52 @@ def gae_scan(rew, ended, value, gamma, lam, last_value=None, want_returns=True, 
         check(lib().navsim_gae_scan(_ptr(rew), _ptr(ended), _ptr(value), _ptr(last_value), T, N, float(gamma), float(lam),
                                     _ptr(adv), _ptr(ret), int(bool(exact)), _stream()), "navsim_gae_scan")
     return adv, ret
+
+
+def gae_scan_trunc(rew, ended, done, arrive, value, gamma, lam, last_value=None, want_returns=True, exact=False):
+    """gae_scan with time-outs bootstrapped (navsim_gae_scan_trunc): on a row with `ended` set and neither `done` nor `arrive` the
+    value of the unseen next state is estimated by V of the row itself (rsl_rl's rule; truncated_returns_reference states it).
+    Returns (adv, lambda_returns); without such a row both are gae_scan's, bit for bit."""
+    if not rew.is_cuda:
+        raise NavsimError("gae_scan_trunc needs device tensors; there is no CPU path")
+    T, N = rew.shape
+    rew, ended, done, arrive, value = (t.contiguous() for t in (rew, ended, done, arrive, value))
+    assert rew.dtype == torch.float32 and value.dtype == torch.float32 and all(f.dtype == torch.uint8 for f in (ended, done, arrive))
+    assert ended.shape == done.shape == arrive.shape == rew.shape == value.shape and (last_value is None or last_value.shape == (N,))
+    if last_value is not None:
+        last_value = last_value.to(torch.float32).contiguous()
+    adv = torch.empty_like(rew)
+    ret = torch.empty_like(rew) if want_returns else None
+    with torch.cuda.device(rew.device):
+        check(lib().navsim_gae_scan_trunc(_ptr(rew), _ptr(ended), _ptr(done), _ptr(arrive), _ptr(value), _ptr(last_value), T, N,
+                                          float(gamma), float(lam), _ptr(adv), _ptr(ret), int(bool(exact)), _stream()),
+              "navsim_gae_scan_trunc")
+    return adv, ret
+
+
+def truncated_returns_reference(rew, ended, done, arrive, value, gamma, lam, last_value=None):
+    """Host mirror of navsim_gae_scan_trunc, numpy float64 -- the statement of the rule.  rew, value [T, N] float32; ended, done,
+    arrive [T, N] (non-zero = set); last_value [N] float32 or None (= zeros: the batch end is terminal).  Per column, backwards:
+        trunc[t] = ended[t] and not done[t] and not arrive[t]                    (a time-out, as navppo_episode_sums counts them)
+        add      = rew[t] + (gamma V[t] if trunc[t] else 0 if ended[t] else gamma (1 - lam) V[t+1])        V[T] = last_value
+        R[t]     = add + R[t+1] * (0 if ended[t] else gamma lam)                                           R[T] = last_value
+    Returns (adv, ret) as float32 arrays: ret = float32(R), adv = ret - V."""
+    rew = np.asarray(rew, dtype=np.float32)
+    V = np.asarray(value, dtype=np.float32)
+    T, N = rew.shape
+    end = np.asarray(ended).reshape(T, N) != 0
+    trunc = end & ~(np.asarray(done).reshape(T, N) != 0) & ~(np.asarray(arrive).reshape(T, N) != 0)
+    g, lm = np.float64(gamma), np.float64(lam)
+    gl, gv = g * lm, g * (np.float64(1.0) - lm)
+    vnext = np.zeros(N, dtype=np.float32) if last_value is None else np.asarray(last_value, dtype=np.float32).reshape(N)
+    R = vnext.astype(np.float64)
+    ret = np.empty((T, N), dtype=np.float32)
+    for t in range(T - 1, -1, -1):
+        boot = np.where(trunc[t], g * V[t].astype(np.float64), np.where(end[t], 0.0, gv * vnext.astype(np.float64)))
+        R = (rew[t].astype(np.float64) + boot) + R * np.where(end[t], 0.0, gl)
+        ret[t] = R.astype(np.float32)
+        vnext = V[t]
+    return ret - V, ret
 
 
 class VecEnv:

@@ -16,7 +16,8 @@ stepping loop), --eval_every K (training: a persistent evaluation of --eval_epis
 exceeds 1.5 x the target), --minibatch_size M / --minibatch_shuffle MODE (K = ceil(batch / M) optimiser steps per epoch on slices of the
 batch, shuffled on the device), --norm_reward / --clip_reward C (rewards scaled by the running standard deviation of the discounted
 return and clipped to +-C before the return scan), --lr_schedule adaptive|linear with --desired_kl / --lr_min / --lr_max (the KL-adaptive
-step size decided on the device after every optimiser step, or a linear decay over --max_timesteps), --movers NAME / --movers_period P (moving obstacles beside the static map, training and evaluation).  Vision flags are accepted and refused (the camera
+step size decided on the device after every optimiser step, or a linear decay over --max_timesteps), --bootstrap_truncated (time-outs
+bootstrap with gamma V of their own row and the batch end with V of the next observation instead of counting as terminal), --movers NAME / --movers_period P (moving obstacles beside the static map, training and evaluation).  Vision flags are accepted and refused (the camera
 modality is outside the LiDAR hot path); --mode test maps to --eval (the reference's test path is broken).
 """
 import argparse
@@ -76,6 +77,10 @@ def get_args(argv=None):
     p.add_argument("--desired_kl", type=float, default=0.01, help="with --lr_schedule adaptive: the KL per optimiser step the rule steers towards")
     p.add_argument("--lr_min", type=float, default=1e-5, help="with --lr_schedule adaptive: the lower clamp of the learning rate")
     p.add_argument("--lr_max", type=float, default=1e-2, help="with --lr_schedule adaptive: the upper clamp of the learning rate")
+    p.add_argument("--bootstrap_truncated", action="store_true", default=False,
+                   help="partial-episode bootstrapping: an episode cut by --timesteps_per_episode adds gamma V of its last stored "
+                        "observation (rsl_rl's rule) and the envs still running at the batch end bootstrap with V of the next one, for "
+                        "every lambda; collisions and arrivals stay terminal; default: off, as in the reference")
     p.add_argument("--movers", type=str, default=None,
                    help="moving obstacles cast beside the static map (maps.movers_by_name: orbit4 = four pillars orbiting the spawn "
                         "pose); authored geometry: parity unpinned (no reference geometry); default: none")
@@ -111,7 +116,8 @@ def config_of(args, rollout):
                          eval_every=args.eval_every, eval_episodes=args.eval_episodes, max_grad_norm=args.max_grad_norm,
                          target_kl=args.target_kl, minibatch_size=args.minibatch_size, minibatch_shuffle=args.minibatch_shuffle,
                          norm_reward=args.norm_reward, clip_reward=args.clip_reward, lr_schedule=args.lr_schedule,
-                         desired_kl=args.desired_kl, lr_min=args.lr_min, lr_max=args.lr_max)
+                         desired_kl=args.desired_kl, lr_min=args.lr_min, lr_max=args.lr_max,
+                         bootstrap_truncated=args.bootstrap_truncated)
 
 
 def main(argv=None):

@@ -6,6 +6,9 @@ Follows ``project_ppo/src/ppo.py`` of the reference function by function, vector
                                     the step kernel writes into directly (no host round trip)
   sample_action    ppo.py:673-706   MVN(mean, var*I) sample, clamp, log-prob of the CLAMPED action
   compute returns  ppo.py:643-671   navsim_rtg_scan (HIP): reward-to-go, no bootstrap
+                                    PPOConfig.bootstrap_truncated: time-outs and the batch end stop being terminal -- a time-out row
+                                    bootstraps with gamma V of its own observation (rsl_rl's rule), the batch end with V(obs_buf[T]),
+                                    for every lambda (navsim_gae_scan_trunc; host mirror: env.truncated_returns_reference)
   evaluate         ppo.py:708-737
   update           ppo.py:275-397   A = rtg - V, normalised with the unbiased std (+1e-10); 50 full-batch
                                     epochs of clipped surrogate + MSE critic, Adam(lr 3e-4), no entropy
@@ -63,6 +66,12 @@ class PPOConfig:
     policy: str = "resmlp512"              # reference nets; "mlp64x2" = BASELINE config 2
     gae_lambda: float = None               # None = the reference's estimator A = rtgs - V (ppo.py:277); a number in [0, 1] turns
                                            # on GAE(lambda) (navsim_gae_scan): advantages and critic targets from the lambda-return
+    # False = the reference: every episode end and the batch end are terminal (ppo.py:552-553,601,658-666).  True: partial-episode
+    # bootstrapping (Pardo et al. 2018) by rsl_rl's rule -- a time-out (ended, neither done nor arrive) adds gamma V(s_t) of its own
+    # row, the stand-in for the next state the in-kernel reset overwrote, and the envs still running on the last row bootstrap with
+    # V(obs_buf[T]), for every lambda (gae_lambda = None runs as lambda = 1: A = R - V on truncation-aware returns).  Collisions and
+    # arrivals stay terminal.  navsim_gae_scan_trunc on the device; per rank, no collective.
+    bootstrap_truncated: bool = False
     init_var: float = 0.8                  # ppo.py:123
     var_decay: float = 0.995               # ppo.py:695
     var_floor: float = 0.1                 # ppo.py:694
@@ -131,6 +140,13 @@ class PPOConfig:
         check_minibatch_config(self)
         check_reward_norm_config(self)
         check_lr_schedule_config(self)
+        check_bootstrap_config(self)
+
+
+def check_bootstrap_config(cfg):
+    """PPOConfig.bootstrap_truncated, at the construction of the config and again of the trainer (a config is mutable)."""
+    if not isinstance(cfg.bootstrap_truncated, bool):
+        raise ValueError(f"bootstrap_truncated {cfg.bootstrap_truncated!r}: True or False")
 
 
 # --------------------------------------------------------------------------- minibatch updates
@@ -1146,6 +1162,7 @@ class PPOTrainer:
         self.eppath_buf = torch.zeros((T, N), dtype=f32, device=dev)
         self.rtg_buf = torch.zeros((T, N), dtype=f32, device=dev)
         check_reward_norm_config(cfg)
+        check_bootstrap_config(cfg)
         if cfg.norm_reward:   # (off: not one tensor, launch or read-back more than before)
             self._init_ret_rms(dev)
             self.rew_scaled_buf = torch.zeros((T, N), dtype=f32, device=dev)   # what the scans read; rew_buf keeps the raw rewards
@@ -1281,10 +1298,22 @@ class PPOTrainer:
             self._graph.replay()
         else:
             self._rollout_body()
-        from .env import gae_scan, rtg_scan
+        from .env import gae_scan, gae_scan_trunc, rtg_scan
         self._gae = None
         rew = self._normalise_rewards() if cfg.norm_reward else self.rew_buf   # (the scans below are the same either way)
-        if cfg.gae_lambda is None:
+        if cfg.bootstrap_truncated:
+            # extension: neither a time-out nor the batch end is the end of the robot.  V of all T + 1 stored rows; a time-out row adds
+            # gamma V of its own observation (the terminal observation is gone: the step kernels store the reset one), the envs still
+            # running on the last row bootstrap with V(obs_buf[T]) (ended[T-1] cuts that for an env that ended there) -- for every
+            # lambda; None runs as 1: the reference's A = R - V on truncation-aware returns.  rew is in the critic's units either way.
+            T, N, D = cfg.rollout_len, self.env.N, self.env.D
+            Vall = self.updater.value(self.obs_buf.reshape(-1, D)).reshape(-1, N)
+            V = Vall[:T].contiguous()
+            adv, ret = gae_scan_trunc(rew, self.ended_buf, self.done_buf, self.arrive_buf, V, cfg.gamma,
+                                      1.0 if cfg.gae_lambda is None else cfg.gae_lambda, last_value=Vall[T])
+            self.rtg_buf.copy_(ret)
+            self._gae = (adv.reshape(T * N), V.reshape(T * N))
+        elif cfg.gae_lambda is None:
             rtg_scan(rew, self.ended_buf, cfg.gamma, out=self.rtg_buf)  # ppo.py:619 -> 643-671
         else:   # extension: the critic's values of the stored observations -> lambda-returns (critic targets) and advantages
             # lambda < 1: the envs still running at the batch end are bootstrapped with V(obs_buf[T]), the observation behind the last
@@ -1374,6 +1403,8 @@ class PPOTrainer:
             rn, m = m[6:], m[:6]
             stats = dict(stats, reward_scale=rn[3], ret_rms_mean=rn[0], ret_rms_std=math.sqrt(max(rn[1], 0.0)), explained_variance=rn[4])
         metrics = self._rollout_metrics(m)
+        if cfg.bootstrap_truncated:   # the share of rows the scan bootstrapped as time-outs: the episode sums' figure, nothing launched
+            stats = dict(stats, bootstrapped_frac=metrics["timeouts"] / max(T * N * (self.ctx.world if self.ctx is not None else 1), 1))
         self.t_so_far += metrics["completed_steps"]
         self.i_so_far += 1
         self._grad_guard(stats)
@@ -1567,6 +1598,7 @@ class PPOTrainer:
                 **({"ppo/" + k: lg[k] for k in ("lr", "lr_ups", "lr_downs") if k in lg}),               # (lr_schedule set)
                 **({"ppo/" + k: lg[k] for k in ("reward_scale", "ret_rms_mean", "ret_rms_std", "explained_variance")}
                    if "reward_scale" in lg else {}),                                                    # (norm_reward)
+                **({"ppo/bootstrapped_frac": lg["bootstrapped_frac"]} if "bootstrapped_frac" in lg else {}),   # (bootstrap_truncated)
                 **({"eval/success_rate": lg["eval_success"], "eval/collision_rate": lg["eval_collision"],
                     "eval/timeout_rate": lg["eval_timeout"], "eval/mean_return": lg["eval_return"],
                     "eval/mean_ep_length": lg["eval_length"], "time/eval": lg["eval_time"]} if "eval_success" in lg else {})}
@@ -1625,6 +1657,7 @@ class PPOTrainer:
                     + (f" kl_stop_step={lg['kl_stop_step']}" if "kl_stop_step" in lg else "")
                     + (f" lr={lg['lr']:.3e}" if "lr" in lg else "")
                     + (f" lr_ups={lg['lr_ups']} lr_downs={lg['lr_downs']}" if "lr_ups" in lg else "")
+                    + (f" bootstrapped_frac={lg['bootstrapped_frac']:.4f}" if "bootstrapped_frac" in lg else "")
                     + (f" eval: succ={lg['eval_success']:.3f} coll={lg['eval_collision']:.3f} tmo={lg['eval_timeout']:.3f} "
                        f"ret={lg['eval_return']:.2f} len={lg['eval_length']:.1f} ({lg['eval_time']:.3f}s)"
                        if "eval_success" in lg else ""))

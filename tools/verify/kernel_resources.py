@@ -6,7 +6,8 @@
 
 `compare` is how a change that must leave the existing kernels alone shows it without a GPU: every kernel symbol of PARENT must
 exist in THIS with the same VGPR / SGPR / scratch / LDS figures (the kernarg size is listed, and may differ when the parameter block
-grows); kernels only THIS has are listed as new.  Exit status 1 if a figure other than the kernarg size differs or a symbol is gone.
+grows); kernels only THIS has are listed as new.  A kernel template that gained trailing DEFAULTED template parameters or trailing
+arguments has new symbols for its old instantiations: those are paired (listed as EXTENDED) and compared like the rest.  Exit status 1 if a figure other than the kernarg size differs or a symbol is gone.
 No GPU needed (hipcc cross-compiles)."""
 import os
 import re
@@ -51,8 +52,45 @@ def fmt(name, r):
     return f"{name:<96} vgpr {r['vgpr']:>3} agpr {r['agpr']:>3} sgpr {r['sgpr']:>3} scratch {r['scratch']:>4} lds {r['lds']:>6} kernarg {r['kernarg']:>4}"
 
 
+def _split_name(name):
+    """'void f<a, b>(p, q)' -> ('f', ['a', 'b'], ['p', 'q']); the kernels' arguments hold no nested parentheses or angle brackets"""
+    m = re.match(r"(?:void )?([\w:]+)(?:<([^<>]*)>)?\((.*)\)$", name)
+    if not m:
+        return None
+    lst = lambda s: [x.strip() for x in s.split(",")] if s else []
+    return m.group(1), lst(m.group(2)), lst(m.group(3))
+
+
+def extended(ta, tb):
+    """{parent symbol: symbol of this build} for the parent's kernels whose symbol is gone because the kernel GAINED trailing template
+    parameters and / or trailing arguments (a defaulted `template <..., bool NEW = false>` changes the mangled name of every
+    instantiation): the one new symbol of the same function whose template arguments start with the parent's and end in `false` / 0
+    (the default) and whose argument list starts with the parent's."""
+    out = {}
+    for n in set(ta) - set(tb):
+        pa = _split_name(n)
+        if not pa:
+            continue
+        hits = []
+        for cand in set(tb) - set(ta):
+            pb = _split_name(cand)
+            if (pb and pb[0] == pa[0] and pb[1][:len(pa[1])] == pa[1] and pb[2][:len(pa[2])] == pa[2]
+                    and all(x in ("false", "0") for x in pb[1][len(pa[1]):])):
+                hits.append(cand)
+        if len(hits) == 1:
+            out[n] = hits[0]
+    return out
+
+
 def compare(a, b):
     ta, tb = table(a), table(b)
+    ext = extended(ta, tb)
+    if ext:
+        print("== kernels that gained defaulted template parameters / trailing arguments: compared under the parent's symbol")
+        for n in sorted(ext):
+            print(f"EXTENDED {n}\n      -> {ext[n]}")
+            tb[n] = tb.pop(ext[n])
+        print()
     bad = 0
     print(f"== parent: {len(ta)} kernels")
     for n in sorted(ta):
