@@ -3,6 +3,8 @@ library is missing or a call fails, this raises."""
 import ctypes as C
 import os
 
+import torch   # (before the library is loaded: lib() says why)
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # NAVSIM_LIB: another build of the same library (tools/build_variant.py A/B timing); never a different implementation
 LIB_PATH = os.environ.get("NAVSIM_LIB") or os.path.join(_HERE, "libnavsim.so")
@@ -151,3 +153,16 @@ def check(rc, what="navsim"):
     if rc != 0:
         msg = lib().navsim_last_error()
         raise NavsimError(f"{what} failed (code {rc}): {msg.decode() if msg else ''}")
+
+
+def _ptr(t, offset=0):
+    """The address of tensor `t` (+ `offset` bytes) as an entry point's void*; None (an argument left out) stays None."""
+    return None if t is None else C.c_void_p(t.data_ptr() + offset)
+
+
+def _navppo(entry, *args):
+    """Calls the navppo_* entry point `entry` (include/navppo.h) with `args` and the current stream; a failure raises under the name
+    of the entry point that was called, with its message."""
+    L = lib()
+    if getattr(L, entry)(*args, C.c_void_p(torch.cuda.current_stream().cuda_stream)) != 0:
+        raise RuntimeError(f"{entry} failed: {L.navppo_last_error().decode()}")

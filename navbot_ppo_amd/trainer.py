@@ -1,0 +1,609 @@
+"""PPO.learn for a VecEnv shard (ppo.py:218-461): rollout, return scan, update, logging and checkpoints."""
+import ctypes as C
+import math
+import os
+import time
+
+import torch
+
+from . import nets
+from ._native import _navppo, _ptr, check, lib
+from .config import PPOConfig, check_bootstrap_config, check_reward_norm_config
+from .distributed import as_ctx
+from .lr_schedule import linear_lr
+from .reward_norm import RET_RMS_INIT, return_moments, reward_scale
+from .updater import LOG_2PI, PPOUpdater, gaussian_log_prob
+
+
+class PPOTrainer:
+    """PPO.learn for a ``VecEnv`` shard.  Construct one per process (= per GPU)."""
+
+    def __init__(self, env, cfg=None, ctx=None):
+        self.env, self.cfg = env, cfg or PPOConfig()
+        self.ctx = ctx = as_ctx(ctx)
+        self.device = env.device
+        cfg = self.cfg
+        N, T, D = env.N, cfg.rollout_len, env.D
+        torch.manual_seed(cfg.seed)  # same initial weights on every rank (then broadcast anyway)
+        self.actor, self.critic = nets.make_policy(cfg.policy, D, 2)
+        self.actor.to(self.device)
+        self.critic.to(self.device)
+        self.updater = PPOUpdater(self.actor, self.critic, cfg, ctx, self.device)
+        torch.manual_seed(cfg.seed * 1000003 + 17 + ctx.rank)  # exploration noise differs per shard
+        dev = self.device
+        f32, u8 = torch.float32, torch.uint8
+        # the observation rows in the dtype the simulator writes them (float16 on an obs_f16 env: BASELINE configs[4]); half rows
+        # are read directly by the fused kernels of both policies (round 6: the 512-wide ones too), a PyTorch policy widens them
+        self.obs_buf = torch.zeros((T + 1, N, D), dtype=env.sim.obs_dtype, device=dev)
+        self._half_obs = env.sim.obs_dtype == torch.float16
+        self.act_buf = torch.zeros((T, N, 2), dtype=f32, device=dev)
+        self.logp_buf = torch.zeros((T, N), dtype=f32, device=dev)
+        self.rew_buf = torch.zeros((T, N), dtype=f32, device=dev)
+        self.done_buf = torch.zeros((T, N), dtype=u8, device=dev)
+        self.arrive_buf = torch.zeros((T, N), dtype=u8, device=dev)
+        self.ended_buf = torch.zeros((T, N), dtype=u8, device=dev)
+        self.epret_buf = torch.zeros((T, N), dtype=f32, device=dev)
+        self.eplen_buf = torch.zeros((T, N), dtype=torch.int32, device=dev)
+        self.eppath_buf = torch.zeros((T, N), dtype=f32, device=dev)
+        self.rtg_buf = torch.zeros((T, N), dtype=f32, device=dev)
+        check_reward_norm_config(cfg)
+        check_bootstrap_config(cfg)
+        if cfg.norm_reward:   # (off: not one tensor, launch or read-back more than before)
+            self._init_ret_rms(dev)
+            self.rew_scaled_buf = torch.zeros((T, N), dtype=f32, device=dev)   # what the scans read; rew_buf keeps the raw rewards
+            self._ret_rows = torch.zeros((ctx.world, 3), dtype=torch.float64, device=dev)   # one row per rank
+        self.var = torch.full((), cfg.init_var, dtype=f32, device=dev)  # ppo.py:123-124 (0.8 * I)
+        self.var_host = float(cfg.init_var)   # host mirror, refreshed at every rollout start
+        self._lo = torch.tensor([0.0, -1.0], device=dev)
+        self._hi = torch.tensor([1.0, 1.0], device=dev)
+        self._graph = None
+        self._step_base = torch.zeros((), dtype=torch.int32, device=dev)  # rollout steps taken so far (noise counter)
+        self._act_seed = (cfg.seed * 0x9E3779B97F4A7C15 + 0xAC7) & 0xFFFFFFFFFFFFFFFF
+        self._env_id_base = int(env.sim.cfg.env_id_base)
+        self.t_so_far = 0     # completed-episode steps, as the reference counts (ppo.py:258)
+        self.env_steps = 0    # all simulated steps
+        self.i_so_far = 0
+        self.episode_starts = 0
+        self.logger = {}
+
+    @property
+    def ctx(self):
+        """the ranks of the run: a DistCtx, or the single-process context (also when None was assigned)"""
+        return self._ctx
+
+    @ctx.setter
+    def ctx(self, ctx):
+        self._ctx = as_ctx(ctx)
+
+    @property
+    def writes_files(self):
+        """rank 0 alone logs, evaluates and writes checkpoints, CSVs and diagnostics"""
+        return self.ctx.rank == 0
+
+    # ---- PPOConfig.norm_reward: the running statistics of the discounted return and the scaled copy of a rollout's rewards
+    def _init_ret_rms(self, device, mean=RET_RMS_INIT[0], var=RET_RMS_INIT[1], count=RET_RMS_INIT[2]):
+        """ret_rms = (mean, var, count, scale), float64 on the device; a fresh run starts like RunningMeanStd (0, 1, 1e-4)."""
+        mean, var, count = float(mean), float(var), float(count)
+        self.ret_rms = torch.tensor([mean, var, count, 1.0 / math.sqrt(var + self.cfg.norm_reward_eps)], dtype=torch.float64, device=device)
+
+    def _normalise_rewards(self):
+        """Behind the rollout, in front of the return scan: this rank's (n, mean, M2) of the rollout's running returns (carry-in 0:
+        every rollout starts from a reset), every rank's row gathered by ONE all-reduce of a zero-filled [world, 3] tensor (adding
+        zeros is exact), all rows merged in rank order on every rank -- bit-identical statistics -- and the rollout scaled by them.
+        Two entry points, no host round trip."""
+        cfg, ctx = self.cfg, self.ctx
+        rows = self._ret_rows
+        if ctx.enabled and rows.shape[0] > 1:
+            rows.zero_()
+        return_moments(self.rew_buf, self.ended_buf, cfg.gamma, out=rows[ctx.rank])
+        ctx.all_reduce_sum(rows)
+        return reward_scale(self.ret_rms, rows, self.rew_buf, clip=cfg.clip_reward, eps=cfg.norm_reward_eps, out=self.rew_scaled_buf)
+
+    def _reward_norm_figures_dev(self):
+        """(mean, var, count, scale, explained variance) as one float64 device tensor, queued behind the update and read with the
+        iteration's one read-back.  explained_variance = 1 - Var(target - V0) / Var(target) over this rank's samples, V0 the critic
+        before the update: scale-free, unlike critic_loss, whose units change with the option."""
+        tgt, v0 = self.rtg_buf.reshape(-1).double(), self.updater._last_V0.reshape(-1).double()
+        ev = 1.0 - (tgt - v0).var(unbiased=False) / tgt.var(unbiased=False)
+        return torch.cat([self.ret_rms, ev.reshape(1)])
+
+    def _fused_act(self, t, noise=None):
+        """PPO.get_action for all envs in ONE launch (csrc/ppo_mlp64.hip: mlp64_act, csrc/ppo_resmlp512.hip: resmlp_act)."""
+        up = self.updater
+        _navppo(up.fused + "_act", _ptr(up.fp.flat), *up._obs_args(self.obs_buf[t]), _ptr(noise), self.env.N, _ptr(self.var), self._act_seed,
+                self._env_id_base, _ptr(self._step_base), t, _ptr(self.act_buf[t]), _ptr(self.logp_buf[t]), None)
+
+    # ---- ppo.py:673-706 + env.step, for rollout step t (all envs)
+    def _rollout_step(self, t):
+        if self.updater.fused:
+            self._fused_act(t)
+        else:
+            obs = self.obs_buf[t].float()
+            mean = self.actor(obs)
+            std = torch.sqrt(self.var)
+            raw = torch.addcmul(mean, torch.randn_like(mean), std)          # dist.sample(), ppo.py:698
+            act = self.act_buf[t]
+            torch.clamp(raw, self._lo, self._hi, out=act)                   # ppo.py:700-703
+            self.logp_buf[t] = gaussian_log_prob(mean, act, self.var)       # log-prob of the clamped action, :704
+        self.env.sim.step(self.act_buf[t], self.obs_buf[t + 1], self.rew_buf[t], self.done_buf[t], self.arrive_buf[t],
+                          self.ended_buf[t], self.epret_buf[t], self.eplen_buf[t], ep_path=self.eppath_buf[t])
+
+    def _persistent_rollout(self):
+        """ppo.py:505-594 in ONE launch (csrc/navsim.hip: rollout_kernel): policy step and env step alternate inside the
+        kernel; same device functions and Philox keys as the per-step path, so the buffers come out bit-identical."""
+        sim = self.env.sim
+        name = "navsim_rollout_" + ("resmlp512" if self.updater.fused_resmlp512 else "mlp64")
+        with torch.cuda.device(self.device):
+            check(getattr(lib(), name)(sim._h, _ptr(self.updater.fp.flat), _ptr(self.obs_buf), _ptr(self.act_buf), _ptr(self.logp_buf),
+                                       _ptr(self.rew_buf), _ptr(self.done_buf), _ptr(self.arrive_buf), _ptr(self.ended_buf),
+                                       _ptr(self.epret_buf), _ptr(self.eplen_buf), _ptr(self.eppath_buf), _ptr(self.var), self._act_seed,
+                                       _ptr(self._step_base), self.cfg.rollout_len,
+                                       C.c_void_p(torch.cuda.current_stream().cuda_stream)), name)
+        self._step_base += self.cfg.rollout_len
+
+    def _rollout_body(self):
+        for t in range(self.cfg.rollout_len):
+            self._rollout_step(t)
+        self._step_base += self.cfg.rollout_len  # inside the captured graph: every replay draws fresh noise
+
+    @property
+    def uses_persistent_rollout(self):
+        """All T steps of PPO.rollout in ONE launch: navsim_rollout_mlp64 (the (B + 6)-64-64 actor, 10 or 36 beams, float32 or float16
+        rows) or navsim_rollout_resmlp512 (the reference's 512-wide actor, 10 beams, float32 or float16 rows).  Anything else runs the
+        hipGraph of per-step launches."""
+        return bool(self.cfg.persistent_rollout and ((self.updater.fused_mlp64 and self.env.B in (10, 36)) or
+                                                     (self.updater.fused_resmlp512 and self.env.B == 10)))
+
+    @torch.no_grad()
+    def rollout(self):
+        cfg = self.cfg
+        self._decay_exploration()
+        self.epret_buf.zero_()
+        self.eplen_buf.zero_()
+        self.updater.invalidate_prepared()   # the kernels below rewrite obs_buf behind torch's version counter
+        self.env.sim.reset(self.obs_buf[0])  # ppo.py:486: every batch starts from a reset
+        # (round 5: both rollout kernels have the tile-box cast of shared 65..4096-segment maps; until then shards up to 4096 envs on
+        # such a map took the hipGraph of per-step launches)
+        if self.uses_persistent_rollout:
+            self._persistent_rollout()
+        elif cfg.use_graph and self.device.type == "cuda":
+            if self._graph is not None and self._graph_gen != self.env.sim.generation:
+                self._graph = None   # set_map / set_spawn_sampler / set_goal_rects re-allocated what the capture froze
+            if self._graph is None:
+                self._graph_gen = self.env.sim.generation
+                s = torch.cuda.Stream(self.device)
+                s.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(s):  # warm-up outside capture (allocator, hipBLASLt workspaces)
+                    self._rollout_step(0)
+                torch.cuda.current_stream().wait_stream(s)
+                torch.cuda.synchronize()
+                self.env.sim.reset(self.obs_buf[0])
+                self._graph = torch.cuda.CUDAGraph()
+                # thread_local: other threads (the RCCL watchdog of torch.distributed) may touch the HIP runtime while
+                # this thread captures; the default global mode would turn that into a capture error on multi-GPU runs
+                with torch.cuda.graph(self._graph, capture_error_mode="thread_local"):
+                    self._rollout_body()
+            self._graph.replay()
+        else:
+            self._rollout_body()
+        from .env import gae_scan, gae_scan_trunc, rtg_scan
+        self._gae = None
+        rew = self._normalise_rewards() if cfg.norm_reward else self.rew_buf   # (the scans below are the same either way)
+        trunc, lam = cfg.bootstrap_truncated, cfg.gae_lambda
+        if not trunc and lam is None:
+            rtg_scan(rew, self.ended_buf, cfg.gamma, out=self.rtg_buf)  # ppo.py:619 -> 643-671
+        else:   # extension: the critic's values of the stored observations -> lambda-returns (critic targets) and advantages
+            # gae_lambda alone, lambda < 1: the envs still running at the batch end are bootstrapped with V(obs_buf[T]), the observation
+            # behind the last row (an env that ended on the last row has ended[T-1] set, which cuts the bootstrap).  lambda = 1 keeps the
+            # reference's convention -- the batch end is terminal, ppo.py:601,658-666 -- and stays bit-identical to compute_rtgs.
+            # bootstrap_truncated: neither a time-out nor the batch end is the end of the robot.  V of all T + 1 stored rows; a time-out row
+            # adds gamma V of its own observation (the terminal observation is gone: the step kernels store the reset one), the envs still
+            # running on the last row bootstrap with V(obs_buf[T]) (ended[T-1] cuts that for an env that ended there) -- for every
+            # lambda; None runs as 1: the reference's A = R - V on truncation-aware returns.  rew is in the critic's units either way.
+            T, N, D = cfg.rollout_len, self.env.N, self.env.D
+            lam = 1.0 if lam is None else lam
+            boot = trunc or lam < 1.0   # V(obs_buf[T]) bootstraps the last row
+            Vall = self.updater.value(self.obs_buf[:T + 1 if boot else T].reshape(-1, D)).reshape(-1, N)
+            V = Vall[:T].contiguous()
+            last = Vall[T] if boot else None
+            if trunc:
+                adv, ret = gae_scan_trunc(rew, self.ended_buf, self.done_buf, self.arrive_buf, V, cfg.gamma, lam, last_value=last)
+            else:
+                adv, ret = gae_scan(rew, self.ended_buf, V, cfg.gamma, lam, last_value=last)
+            self.rtg_buf.copy_(ret)
+            self._gae = (adv.reshape(T * N), V.reshape(T * N))
+        self.env_steps += cfg.rollout_len * self.env.N
+
+    def _decay_exploration(self):
+        """ppo.py:694-695 multiplies the covariance by 0.995 at every episode start once t_so_far > 50000 while
+        it is >= 0.1, with t_so_far frozen during a rollout.  With N envs there are N x more episode starts per
+        iteration, so the decay is applied once per N episode starts (per mean episode) -- identical for N=1
+        up to being applied at the rollout boundary; documented deviation."""
+        cfg = self.cfg
+        v = float(self.var)   # the one read-back of the iteration, at its start (the stream is idle here)
+        if self.t_so_far > cfg.var_decay_after:
+            k = int(round(self.episode_starts / max(self.env.N, 1)))
+            for _ in range(k):
+                if v >= cfg.var_floor:
+                    v *= cfg.var_decay
+            self.var.fill_(v)
+        self.var_host = v
+        self.episode_starts = 0
+
+    def _rollout_metrics_dev(self):
+        """The six sums behind the iteration's episode metrics as ONE device tensor (all-reduced over the ranks); nothing
+        here waits for the GPU, so the update can be queued behind it."""
+        if getattr(self, "_sums_ws", None) is None:
+            self._sums_ws = torch.empty(256 * 6, dtype=torch.float64, device=self.device)
+        m = torch.empty(6, dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            _navppo("navppo_episode_sums", _ptr(self.ended_buf), _ptr(self.arrive_buf), _ptr(self.done_buf), _ptr(self.eplen_buf),
+                    _ptr(self.epret_buf), self.ended_buf.numel(), _ptr(m), _ptr(self._sums_ws))
+        self.ctx.all_reduce_sum(m)
+        return m
+
+    def _rollout_metrics(self, m=None):
+        m = self._rollout_metrics_dev() if m is None else m   # (a tensor, or the six figures already on the host)
+        ep, succ, coll, tmo, steps, ret = [float(x) for x in (m.tolist() if torch.is_tensor(m) else m)]
+        self.episode_starts = ep / self.ctx.world + self.env.N
+        return dict(episodes=int(ep), successes=int(succ), collisions=int(coll), timeouts=int(tmo),
+                    completed_steps=int(steps), avg_ep_rews=(ret / ep if ep else 0.0),       # ppo.py:833
+                    avg_ep_lens=(steps / ep if ep else 0.0), success_rate=(succ / ep if ep else 0.0))
+
+    def iteration(self):
+        """One pass of the loop of PPO.learn (ppo.py:241-459).  Rollout, metric sums and update are queued back to back and
+        the host waits once, at the end; rollout / update times come from events on the stream (wall clock on CPU)."""
+        cfg = self.cfg
+        cuda = self.device.type == "cuda"
+        T, N, D = cfg.rollout_len, self.env.N, self.env.D
+        t0 = time.time()
+        if cuda:
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+            ev[0].record()
+        self.rollout()
+        if cuda:
+            ev[1].record()
+        t1 = time.time()
+        m = self._rollout_metrics_dev()
+        stats = self.updater.update(self.obs_buf[:T].reshape(T * N, D), self.act_buf.reshape(T * N, 2),
+                                    self.logp_buf.reshape(T * N), self.rtg_buf.reshape(T * N),
+                                    self.var_host if self.updater.fused else self.var,
+                                    **({} if self._gae is None else dict(adv_raw=self._gae[0], V0=self._gae[1])))
+        if cuda:
+            ev[2].record()
+        if cfg.norm_reward:   # the option's figures ride on the episode sums' read-back below: one tensor, one copy
+            m = torch.cat([m, self._reward_norm_figures_dev()])
+        if cuda:
+            torch.cuda.synchronize(self.device)
+        t2 = time.time()
+        if cuda:   # the host ran ahead of the stream: split the wall clock of the iteration by the stream's own stamps
+            r_ms, u_ms = ev[0].elapsed_time(ev[1]), ev[1].elapsed_time(ev[2])
+            t1 = t0 + (t2 - t0) * r_ms / max(r_ms + u_ms, 1e-9)
+        if cfg.norm_reward:
+            m = m.tolist()
+            rn, m = m[6:], m[:6]
+            stats = dict(stats, reward_scale=rn[3], ret_rms_mean=rn[0], ret_rms_std=math.sqrt(max(rn[1], 0.0)), explained_variance=rn[4])
+        metrics = self._rollout_metrics(m)
+        world = self.ctx.world
+        if cfg.bootstrap_truncated:   # the share of rows the scan bootstrapped as time-outs: the episode sums' figure, nothing launched
+            stats = dict(stats, bootstrapped_frac=metrics["timeouts"] / max(T * N * world, 1))
+        self.t_so_far += metrics["completed_steps"]
+        self.i_so_far += 1
+        self._grad_guard(stats)
+        self.logger = dict(metrics, **stats, iteration=self.i_so_far, t_so_far=self.t_so_far,
+                           rollout_time=t1 - t0, update_time=t2 - t1, iter_time=t2 - t0,
+                           steps_per_sec=T * N * world / (t2 - t0),                      # ppo.py:855
+                           rollout_steps_per_sec=T * N * world / (t1 - t0), var=self.var_host)
+        if cfg.eval_every > 0 and self.i_so_far % cfg.eval_every == 0 and self.writes_files:
+            self.logger.update(self.evaluate_now())   # rank 0 alone, no collective: the other ranks go on to their next rollout
+        if cfg.output_dir and self.writes_files:
+            if self.i_so_far % cfg.save_freq == 0:
+                self.save_checkpoint()
+            import json
+            os.makedirs(self.log_dir(), exist_ok=True)
+            with open(os.path.join(self.log_dir(), "scalars.jsonl"), "a") as f:
+                f.write(json.dumps(dict(self.tb_scalars(), iteration=self.i_so_far, t_so_far=self.t_so_far)) + "\n")
+            if cfg.episode_csv_rows:
+                self.write_episode_csv(cfg.episode_csv_rows)
+            self.write_tensorboard()
+        return self.logger
+
+    # ---- the gradient check of the reference (ppo.py:356-379, 414-416), once per iteration on figures that are already on the host
+    def _grad_guard(self, stats, log=print):
+        """A per-net mean gradient norm that is <= 0 or not finite, a loss that is not finite, or a skipped step (max_grad_norm):
+        the reference's warning line, and a block in <output_dir>/grad_diagnostics.txt.  No launch and no sync unless it triggers
+        (then a few reductions over the advantages for the file); it reports only -- what happens to the weights is decided by
+        PPOConfig.max_grad_norm inside the update -- and never raises.  Returns the nets that triggered."""
+        cfg = self.cfg
+        if cfg.n_updates_per_iteration < 1:
+            return []
+        hit = []
+        for net in ("actor", "critic"):
+            gn, loss, sk = stats.get(net + "_grad_norm", 0.0), stats.get(net + "_loss", 0.0), stats.get("skipped_steps_" + net, 0)
+            if gn <= 0 or not math.isfinite(gn) or not math.isfinite(loss) or sk > 0:
+                hit.append((net, gn, loss, sk))
+        if not hit or not self.writes_files:
+            return [h[0] for h in hit]
+        try:
+            for net, gn, loss, sk in hit:
+                if log:
+                    log(f"[WARNING] {net.capitalize()} grad norm invalid: {gn:.6f} at iteration {self.i_so_far}. Check grad_diagnostics.txt"
+                        + (f" ({sk} of {cfg.n_updates_per_iteration} steps skipped)" if sk else ""), flush=True)
+            if cfg.output_dir:
+                adv = getattr(self.updater, "_last_adv", None)
+                a = [float("nan")] * 4 if adv is None else [float(x) for x in (adv.mean(), adv.std(), adv.min(), adv.max())]
+                os.makedirs(cfg.output_dir, exist_ok=True)
+                with open(os.path.join(cfg.output_dir, "grad_diagnostics.txt"), "a") as f:
+                    for net, gn, loss, sk in hit:
+                        f.write(f"\n[{net.upper()} GRAD ISSUE] Iteration {self.i_so_far}\n")
+                        f.write(f"  Net: {net}\n")
+                        f.write(f"  {net.capitalize()} grad norm: {gn}\n")
+                        f.write(f"  {net.capitalize()} loss: {loss}\n")
+                        f.write(f"  Skipped steps: {sk} of {cfg.n_updates_per_iteration}\n")
+                        f.write(f"  Advantage stats: mean={a[0]:.4f}, std={a[1]:.4f}, min={a[2]:.4f}, max={a[3]:.4f}\n")
+                        f.write(f"  Clip fraction: {stats.get('clip_frac', 0.0):.4f}\n")
+        except Exception as e:   # a diagnostics file must never end a run
+            try:
+                print(f"[WARNING] grad diagnostics not written: {e}", flush=True)
+            except Exception:
+                pass
+        return [h[0] for h in hit]
+
+    # ---- periodic evaluation (PPOConfig.eval_every)
+    EVAL_HISTORY_HEADER = ["iteration", "timesteps", "episodes", "success_rate", "collision_rate", "timeout_rate", "mean_length",
+                           "mean_return", "mean_path_length"]
+
+    @property
+    def stats(self):
+        """the last iteration's figures (what iteration() returned)"""
+        return self.logger
+
+    def _make_eval_env(self):
+        from .env import VecEnv
+        w = dict(getattr(self.env, "world_args", None) or {})
+        if not w:
+            raise ValueError("PPOConfig.eval_every: the training env does not describe its world (VecEnv.world_args)")
+        if torch.is_tensor(w["map"]) and w["map"].dim() == 3:
+            raise ValueError("PPOConfig.eval_every: a per-env segment tensor cannot be reused for the evaluation envs; pass a map "
+                             "name or a shared [S, 4] map (per_env_map=True replicates it)")
+        n_par = min(int(self.cfg.eval_episodes), 1024)
+        if n_par < 1:
+            raise ValueError("PPOConfig.eval_episodes must be at least 1")
+        seed = (int(self.cfg.seed) * 1000003 + 7919) & 0xFFFFFFFF   # its own goal / spawn stream, derived from cfg.seed
+        return VecEnv(n_par, max_episode_steps=self.cfg.max_episode_steps, auto_reset=True, is_training=False, seed=seed,
+                      device=self.device, **w)
+
+    def evaluate_now(self):
+        """eval_episodes episodes of the current actor in ONE launch on the evaluation envs (created at the first call): the
+        deterministic mean action, arrival threshold 0.4, a fixed quota of whole episodes per env, rows cut slot-major to
+        eval_episodes as evaluate() does.  Reads the flat parameter buffer the update writes and nothing of the training env
+        (its state, RNG counters, the noise counter and the captured graph are untouched).  Returns the eval_* figures and
+        appends one row to <method>_eval_history.csv."""
+        cfg = self.cfg
+        if not (self.updater.fused_mlp64 or self.updater.fused_resmlp512):
+            raise ValueError(f"PPOConfig.eval_every: no evaluation kernel for policy {cfg.policy!r} on this update path "
+                             "(it needs the fused HIP update's flat parameter layout)")
+        if getattr(self, "_eval_env", None) is None:
+            self._eval_env = self._make_eval_env()
+        env = self._eval_env
+        n_ep = int(cfg.eval_episodes)
+        quota = -(-n_ep // env.N)
+        t0 = time.time()
+        tab = env.evaluate_policy(self.updater.fp.flat, quota, policy="resmlp512" if self.updater.fused_resmlp512 else "mlp64x2")
+        cut = lambda x: x.reshape(-1)[:n_ep]
+        fl = cut(tab.flags)
+        sums = torch.stack([(fl & 1).sum().double(), ((fl >> 1) & 1).sum().double(), ((fl >> 2) & 1).sum().double(),
+                            cut(tab.length).double().sum(), cut(tab.ret).double().sum(), cut(tab.path).double().sum(),
+                            tab.count.min().double(), tab.steps.max().double()]).cpu().numpy()   # the one host sync
+        if int(sums[6]) < quota:
+            raise RuntimeError("evaluate_now: an env did not finish its quota of episodes")
+        sums = [float(v) for v in sums]
+        out = dict(eval_episodes=n_ep, eval_success=sums[0] / n_ep, eval_collision=sums[1] / n_ep, eval_timeout=sums[2] / n_ep,
+                   eval_length=sums[3] / n_ep, eval_return=sums[4] / n_ep, eval_path_length=sums[5] / n_ep,
+                   eval_steps=int(sums[7]), eval_time=time.time() - t0)
+        if cfg.output_dir:
+            import csv
+            os.makedirs(self.log_dir(), exist_ok=True)
+            path = os.path.join(self.log_dir(), f"{cfg.method_name}_eval_history.csv")
+            new = not os.path.exists(path)
+            with open(path, "a", newline="") as f:
+                w = csv.writer(f)
+                if new:
+                    w.writerow(self.EVAL_HISTORY_HEADER)
+                w.writerow([self.i_so_far, self.t_so_far, n_ep, out["eval_success"], out["eval_collision"], out["eval_timeout"],
+                            out["eval_length"], out["eval_return"], out["eval_path_length"]])
+        return out
+
+    # ---- logging surface of the reference: per-episode CSV (ppo.py:159-163,739-746) and the TensorBoard scalar names
+    #      (ppo.py:892-939) written as one JSON object per iteration (tensorboardX is not a dependency here)
+    EPISODE_CSV_HEADER = ["episode", "timestep", "success", "collision", "timeout", "length", "return", "path_length", "time"]
+
+    def log_dir(self):
+        return os.path.join(self.cfg.output_dir, self.cfg.method_name, "logs")
+
+    def write_episode_csv(self, max_rows=None):
+        """Appends the episodes finished in the last rollout, in (step, env) order (ppo.py:739-746).  path_length is the
+        simulator's per-episode accumulator (ppo.py:533-537 semantics: the final step's displacement is not part of it);
+        time is the episode's share of the rollout wall clock, length x (rollout_time / T): the envs advance in lock
+        step, so an episode of L steps occupied L / T of the rollout."""
+        import csv
+        os.makedirs(self.log_dir(), exist_ok=True)
+        path = os.path.join(self.log_dir(), f"{self.cfg.method_name}_train_episodes.csv")
+        new = not os.path.exists(path)
+        ended = self.ended_buf.bool()
+        t_idx, n_idx = torch.nonzero(ended, as_tuple=True)
+        if max_rows is not None:
+            t_idx, n_idx = t_idx[:max_rows], n_idx[:max_rows]
+        d = self.done_buf[t_idx, n_idx].cpu().numpy()
+        a = self.arrive_buf[t_idx, n_idx].cpu().numpy()
+        ln = self.eplen_buf[t_idx, n_idx].cpu().numpy()
+        rt = self.epret_buf[t_idx, n_idx].cpu().numpy()
+        pl = self.eppath_buf[t_idx, n_idx].cpu().numpy()
+        tt = t_idx.cpu().numpy()
+        sec_per_step = float(self.logger.get("rollout_time", 0.0)) / max(self.cfg.rollout_len, 1)
+        base = getattr(self, "_episode_count", 0)
+        with open(path, "a", newline="") as f:
+            w = csv.writer(f)
+            if new:
+                w.writerow(self.EPISODE_CSV_HEADER)
+            for k in range(len(tt)):
+                succ = int(a[k]); coll = int(d[k] and not a[k]); tmo = int(not d[k] and not a[k])  # ppo.py:558-560
+                w.writerow([base + k, self.env_steps - (self.cfg.rollout_len - int(tt[k]) - 1) * self.env.N, succ, coll, tmo,
+                            int(ln[k]), float(rt[k]), float(pl[k]), float(ln[k]) * sec_per_step])
+        self._episode_count = base + len(tt)
+        return path
+
+    def tb_scalars(self):
+        """The scalars the reference hands to SummaryWriter.add_scalar once per iteration, under its tag names
+        (ppo.py:892-918), for the last iteration."""
+        lg = self.logger
+        ep = max(lg.get("episodes", 0), 1)
+        n_ep = self.cfg.n_updates_per_iteration
+        var = float(lg.get("var", self.cfg.init_var))
+        sec_per_step = float(lg.get("rollout_time", 0.0)) / max(self.cfg.rollout_len, 1)
+        return {"train/success_rate": lg.get("success_rate"), "train/collision_rate": lg.get("collisions", 0) / ep,
+                "train/timeout_rate": lg.get("timeouts", 0) / ep, "train/mean_return": lg.get("avg_ep_rews"),
+                "train/mean_ep_length": lg.get("avg_ep_lens"), "train/mean_ep_time": lg.get("avg_ep_lens", 0.0) * sec_per_step,
+                "loss/actor": lg.get("actor_loss"), "loss/critic": lg.get("critic_loss"), "train/timesteps": lg.get("t_so_far"),
+                "time/rollout": lg.get("rollout_time"), "time/update": lg.get("update_time"), "time/iteration": lg.get("iter_time"),
+                "perf/steps_per_sec": lg.get("steps_per_sec"), "perf/actor_grad_steps": n_ep, "perf/critic_grad_steps": n_ep,
+                "ppo/approx_kl": lg.get("approx_kl"),
+                "ppo/entropy": 1.0 + LOG_2PI + math.log(max(var, 1e-30)),   # MultivariateNormal(mean, var I).entropy(), 2-D
+                "ppo/clip_frac": lg.get("clip_frac"), "ppo/actor_grad_norm": lg.get("actor_grad_norm"),
+                "ppo/critic_grad_norm": lg.get("critic_grad_norm"), "ppo/actor_param_delta": lg.get("actor_param_delta"),
+                "ppo/critic_param_delta": lg.get("critic_param_delta"),
+                "ppo/grad_clip_frac_actor": lg.get("grad_clip_frac_actor"), "ppo/grad_clip_frac_critic": lg.get("grad_clip_frac_critic"),
+                "ppo/skipped_steps_actor": lg.get("skipped_steps_actor"), "ppo/skipped_steps_critic": lg.get("skipped_steps_critic"),
+                "ppo/kl_stop_epoch": lg.get("kl_stop_epoch"), "ppo/kl_stopped": lg.get("kl_stopped"),   # (target_kl set)
+                **({"ppo/kl_stop_step": lg["kl_stop_step"]} if "kl_stop_step" in lg else {}),           # (target_kl and minibatches)
+                **({"ppo/" + k: lg[k] for k in ("lr", "lr_ups", "lr_downs") if k in lg}),               # (lr_schedule set)
+                **({"ppo/" + k: lg[k] for k in ("reward_scale", "ret_rms_mean", "ret_rms_std", "explained_variance")}
+                   if "reward_scale" in lg else {}),                                                    # (norm_reward)
+                **({"ppo/bootstrapped_frac": lg["bootstrapped_frac"]} if "bootstrapped_frac" in lg else {}),   # (bootstrap_truncated)
+                **({"eval/success_rate": lg["eval_success"], "eval/collision_rate": lg["eval_collision"],
+                    "eval/timeout_rate": lg["eval_timeout"], "eval/mean_return": lg["eval_return"],
+                    "eval/mean_ep_length": lg["eval_length"], "time/eval": lg["eval_time"]} if "eval_success" in lg else {})}
+
+    def tb_dir(self):
+        return os.path.join(self.cfg.output_dir, self.cfg.method_name, "tb")   # ppo.py:66
+
+    def write_tensorboard(self):
+        """The reference's TensorBoard stream (ppo.py:892-939): per-iteration scalars at step i_so_far, the per-epoch
+        Actor_loss/train and Critic_loss/train series, Episode_Rewards/train (return / length of every finished episode,
+        ppo.py:586, capped per iteration like the CSV) and avg_ep_rews/train."""
+        from .tb_writer import SummaryWriter
+        if getattr(self, "_tb", None) is None:
+            self._tb = SummaryWriter(self.tb_dir())
+            self._tb_loss_steps = self._tb_ep_steps = 0
+        w, it = self._tb, self.i_so_far
+        t0 = time.time()
+        recs = [(k, float(v), it) for k, v in self.tb_scalars().items() if v is not None]
+        hist = self.updater.loss_history.detach().cpu().numpy()
+        hist = hist[:int(self.updater.stats.get("kl_stop_epoch", hist.shape[0])) + int(self.updater.stats.get("kl_stopped", 0))]   # (rows of epochs that ran)
+        for k in range(hist.shape[0]):
+            recs.append(("Actor_loss/train", float(hist[k, 0]), self._tb_loss_steps + k))
+            recs.append(("Critic_loss/train", float(hist[k, 1]), self._tb_loss_steps + k))
+        self._tb_loss_steps += hist.shape[0]
+        cap = int(self.cfg.tb_episode_rows or 0)
+        if cap:   # own cap, independent of the CSV's: with 4096 envs an iteration finishes ~1e5 episodes
+            ended = self.ended_buf.bool()
+            t_idx, n_idx = torch.nonzero(ended, as_tuple=True)
+            t_idx, n_idx = t_idx[:cap], n_idx[:cap]
+            per_step = (self.epret_buf[t_idx, n_idx] / self.eplen_buf[t_idx, n_idx].clamp(min=1)).cpu().numpy()
+            recs.extend(("Episode_Rewards/train", float(r), self._tb_ep_steps + k) for k, r in enumerate(per_step))
+            self._tb_ep_steps += len(per_step)
+        recs.append(("avg_ep_rews/train", float(self.logger.get("avg_ep_rews", 0.0)), it))
+        recs.append(("time/log", float(getattr(self, "_last_log_time", 0.0)), it))   # the previous iteration's logging cost
+        w.add_scalars(recs)   # one TFRecord per point; CRCs vectorised over the records (tb_writer._masked_crc_many)
+        w.flush()
+        self._last_log_time = time.time() - t0
+
+    def learn(self, total_timesteps, log=print):
+        # The reference counts only COMPLETED episodes toward the budget (ppo.py:258); if a configuration never completes
+        # one (rollout shorter than the episode cap) its loop would spin forever -- bound the iterations by the budget in
+        # simulated steps instead of hanging.
+        per_iter = self.cfg.rollout_len * self.env.N * self.ctx.world
+        max_iters = 4 * (-(-int(total_timesteps) // per_iter)) + 4
+        while self.t_so_far < total_timesteps and self.i_so_far < max_iters:  # ppo.py:245
+            if self.cfg.lr_schedule == "linear":
+                self.updater.set_lr(linear_lr(self.cfg.lr, self.t_so_far, total_timesteps))
+            lg = self.iteration()
+            if log and self.writes_files:
+                log(f"[iter {lg['iteration']:4d}] t={lg['t_so_far']:>10d} mean_ep_rew={lg['avg_ep_rews']:8.2f} "
+                    f"succ={lg['success_rate']:.3f} ep_len={lg['avg_ep_lens']:6.1f} a_loss={lg['actor_loss']:.4f} "
+                    f"c_loss={lg['critic_loss']:.2f} kl={lg['approx_kl']:.4f} steps/s={lg['steps_per_sec']:.0f} "
+                    f"(rollout {lg['rollout_time']:.3f}s update {lg['update_time']:.3f}s)"
+                    + (f" kl_stop_epoch={lg['kl_stop_epoch']} kl_stopped={lg['kl_stopped']}" if "kl_stop_epoch" in lg else "")
+                    + (f" kl_stop_step={lg['kl_stop_step']}" if "kl_stop_step" in lg else "")
+                    + (f" lr={lg['lr']:.3e}" if "lr" in lg else "")
+                    + (f" lr_ups={lg['lr_ups']} lr_downs={lg['lr_downs']}" if "lr_ups" in lg else "")
+                    + (f" bootstrapped_frac={lg['bootstrapped_frac']:.4f}" if "bootstrapped_frac" in lg else "")
+                    + (f" eval: succ={lg['eval_success']:.3f} coll={lg['eval_collision']:.3f} tmo={lg['eval_timeout']:.3f} "
+                       f"ret={lg['eval_return']:.2f} len={lg['eval_length']:.1f} ({lg['eval_time']:.3f}s)"
+                       if "eval_success" in lg else ""))
+        return self.logger
+
+    # ---- ppo.py:452-457 file naming; state_dict keys match the reference's nets for policy resmlp512
+    def checkpoint_dir(self):
+        return os.path.join(self.cfg.output_dir, self.cfg.method_name, "checkpoints")
+
+    def save_checkpoint(self):
+        d = self.checkpoint_dir()
+        os.makedirs(d, exist_ok=True)
+        tag = f"iter{self.i_so_far:04d}_step{self.t_so_far:08d}.pth"
+        pa, pc = os.path.join(d, "actor_" + tag), os.path.join(d, "critic_" + tag)
+        torch.save({k: v.detach().cpu().clone() for k, v in self.actor.state_dict().items()}, pa)
+        torch.save({k: v.detach().cpu().clone() for k, v in self.critic.state_dict().items()}, pc)
+        if self.cfg.norm_reward:   # a third file beside the two reference-named ones: the critic's units
+            mean, var, count = self.ret_rms[:3].tolist()
+            torch.save({"mean": mean, "var": var, "count": count}, os.path.join(d, "retnorm_" + tag))
+        if self.cfg.lr_schedule == "adaptive":   # the rate the next step starts from (on the host since the last update's read-back)
+            torch.save({"lr": float(self.updater.lr_value)}, os.path.join(d, "lrsched_" + tag))
+        return pa, pc
+
+    @staticmethod
+    def sidecar_path(kind, actor_path):
+        """<kind>_<tag>.pth beside actor_<tag>.pth: the files save_checkpoint() writes beside the two reference-named ones"""
+        d, base = os.path.split(actor_path)
+        return os.path.join(d, kind + "_" + (base[len("actor_"):] if base.startswith("actor_") else base))
+
+    @staticmethod
+    def retnorm_path(actor_path):
+        return PPOTrainer.sidecar_path("retnorm", actor_path)
+
+    @staticmethod
+    def lrsched_path(actor_path):
+        return PPOTrainer.sidecar_path("lrsched", actor_path)
+
+    def _load_sidecar(self, kind, actor_path, missing):
+        """What save_checkpoint() stored in the `kind` file beside the actor's, or -- no such file -- None after ONE warning line:
+        `missing` with the file's path in its {}."""
+        path = self.sidecar_path(kind, actor_path)
+        if os.path.exists(path):
+            return torch.load(path, map_location="cpu")
+        import warnings
+        warnings.warn(missing.format(path))
+        return None
+
+    def load_checkpoint(self, actor_path, critic_path):
+        """main.py:52-89: state_dicts only (optimiser state and covariance are not part of a checkpoint).  With norm_reward the return
+        statistics come from retnorm_<tag>.pth beside the actor's file; without that file: one warning line and fresh statistics.
+        With lr_schedule="adaptive" the learning rate comes from lrsched_<tag>.pth; without that file: one warning line and cfg.lr."""
+        if self.cfg.lr_schedule == "adaptive":
+            s = self._load_sidecar("lrsched", actor_path,
+                                   "lr_schedule='adaptive': {} not found -- the learning rate starts at lr = " + str(self.cfg.lr))
+            self.updater.set_lr(float(s["lr"] if s else self.cfg.lr))
+        if self.cfg.norm_reward:
+            s = self._load_sidecar("retnorm", actor_path,
+                                   "norm_reward: {} not found -- the return statistics start fresh; the critic's units are off until they settle")
+            self._init_ret_rms(self.ret_rms.device, *((s["mean"], s["var"], s["count"]) if s else ()))
+        sa = torch.load(actor_path, map_location="cpu")
+        sc = torch.load(critic_path, map_location="cpu")
+        with torch.no_grad():
+            for mod, sd in ((self.actor, sa), (self.critic, sc)):
+                own = mod.state_dict()
+                missing = set(own) - set(sd)
+                if missing:
+                    raise KeyError(f"checkpoint lacks keys {sorted(missing)}")
+                for k, v in own.items():
+                    v.copy_(sd[k])  # in place: parameters stay views of the flat buffer

@@ -198,7 +198,7 @@ def test_linear_schedule_through_learn():
     a, c = _nets()
     cfg = ppo.PPOConfig(policy="mlp64x2", n_updates_per_iteration=2, lr_schedule="linear", rollout_len=8)
     t = ppo.PPOTrainer.__new__(ppo.PPOTrainer)
-    t.cfg, t.ctx, t.env = cfg, None, types.SimpleNamespace(N=8)
+    t.cfg, t.ctx, t.env = cfg, ppo.SingleProcessCtx(), types.SimpleNamespace(N=8)
     t.updater = ppo.PPOUpdater(a, c, cfg, None, CPU)
     t.t_so_far = t.i_so_far = 0
     t.logger = {}

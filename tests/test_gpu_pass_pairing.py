@@ -85,7 +85,7 @@ def test_update_epoch_equals_the_unpaired_build(unpaired_lib, monkeypatch):
     for variant in (False, True):
         with monkeypatch.context() as mp:
             if variant:
-                mp.setattr(ppo, "lib", lambda: unpaired_lib)
+                mp.setattr(_native, "lib", lambda: unpaired_lib)   # (where the entry points are called from)
             up = _updater(dev)
             up._ws.zero_()   # (stats[3] / [7] of an epoch are the squared norms the PREVIOUS step left in the workspace: none here)
             st = torch.zeros(8, device=dev)

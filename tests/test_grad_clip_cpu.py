@@ -164,7 +164,7 @@ def test_pytorch_path_skips_a_net_with_a_non_finite_gradient_and_restores_adam_s
 def _guard_trainer(tmp_path, max_grad_norm):
     t = ppo.PPOTrainer.__new__(ppo.PPOTrainer)
     t.cfg = ppo.PPOConfig(policy="mlp64x2", n_updates_per_iteration=2, max_grad_norm=max_grad_norm, output_dir=str(tmp_path) if tmp_path else "")
-    t.ctx, t.i_so_far = None, 7
+    t.ctx, t.i_so_far = ppo.SingleProcessCtx(), 7
     t.updater = _updater(max_grad_norm, n_ep=2)
     return t
 

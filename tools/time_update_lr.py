@@ -56,11 +56,10 @@ for policy, n in (("mlp64x2", 4096 * 512), ("resmlp512", 64 * 4096)):
 
     def update(leg):
         up = ups[leg]
-        up._lr_step = 0   # (an update's first step does not adapt)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         for ep in range(E):
-            up._fused_epoch(obs, acts, logp, rtg, adv, 0.8, st, cs[ep])
+            up._fused_epoch(obs, acts, logp, rtg, adv, 0.8, st, cs[ep], adapt=ep > 0)   # (an update's first step does not adapt)
         e1.record()
         torch.cuda.synchronize()
         return e0.elapsed_time(e1) * 1e3 / E
