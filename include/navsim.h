@@ -149,6 +149,33 @@ int navsim_set_movers(navsim_t* h, const float* tape_dev, int32_t period, int32_
                       void* stream);
 
 /*
+ * A BANK of tapes, one scenario per env, with per-tape goal rectangles.  navsim_set_movers IS this call with n_tapes = 1,
+ * period[0] = period, no ids and no rectangles; a call of either replaces what the other set, bank_dev = NULL turns movers off.
+ *   bank_dev        [n_tapes][max_period][n_segments][4] f32, 16-byte aligned, BORROWED like the tape.  n_segments <= 64,
+ *                   max_period <= 65536, 1 <= n_tapes, n_tapes * max_period <= 2^24.  Rows period[k] .. max_period-1 of tape k are
+ *                   never read; a tape with fewer segments is padded with NaN segments (never hit).
+ *   period_host     [n_tapes] i32 on the HOST, 1 <= period[k] <= max_period.
+ *   tape_id_dev     [N] i32, nullable (= all 0): the tape of env i, 0 <= id < n_tapes.  Copied; validated on the host at this call.
+ *   phase0_dev      [N] i32, nullable (= all 0): 0 <= phase0[i] < period[tape_id[i]].  Copied; validated likewise.
+ *   goal_rects_host [n_tapes][n_rects][4] f64 (xmin,xmax,ymin,ymax) on the HOST, nullable (= none), n_rects <= 8; a row with a NaN
+ *                   entry is absent.  A uniform-box goal draw of env i (the reset draw and the arrival re-spawn draw) is rejected
+ *                   if it lies in one of the handle's rectangles (navsim_set_goal_rects) OR in one of its tape's.  The draw stream,
+ *                   the 64-try cap and the last-draw-kept rule are unchanged; with goal tables (navsim_set_spawn_sampler with
+ *                   goals) they do not apply, as the handle's own do not.
+ * Phase rule, k = env i's episode step counter before the step, t = tape_id[i]: a step's scan sees
+ * bank[t][(k + 1 + phase0[i]) mod period[t]], a reset observation bank[t][phase0[i]], navsim_raycast
+ * bank[t][(k + phase0[i]) mod period[t]]: the rule of navsim_set_movers with the period and the base row taken per env.
+ * The tape of an env never changes between calls.  The spawn tables are per env as soon as ids or phases are given.
+ * Everything else is as navsim_set_movers says (kernel shape, graphs, a later navsim_set_map, synchronises `stream`).
+ * NAVSIM_E_STATE before navsim_set_map.  NAVSIM_E_ARG, with nothing changed on the handle: sizes out of range, a misaligned bank, an
+ * id, a period or a phase out of range, n_rects outside 0..8 or rectangles without a pointer, and: movers need 10 beams and a shared
+ * static map: movers with 36 beams or with a per-env static map are not built.
+ */
+int navsim_set_mover_bank(navsim_t* h, const float* bank_dev, int32_t n_tapes, int32_t max_period, int32_t n_segments,
+                          const int32_t* period_host, const int32_t* tape_id_dev, const int32_t* phase0_dev,
+                          const double* goal_rects_host, int32_t n_rects, void* stream);
+
+/*
  * Goal-rejection rectangles (xmin,xmax,ymin,ymax; inclusive), host pointer, copied.
  * which=0: used by reset (environment_new.py:340-343); which=1: used by the arrival
  * re-spawn (environment_new.py:248-251).  Defaults are the reference's stage_1 values.

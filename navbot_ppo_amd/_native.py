@@ -58,6 +58,7 @@ SYMBOLS = [
     ("navsim_get_info", C.c_int, [_vp, C.POINTER(NavsimInfo)]),
     ("navsim_set_map", C.c_int, [_vp, _vp, _i32, _i32, _vp]),
     ("navsim_set_movers", C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp]),
+    ("navsim_set_mover_bank", C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp]),
     ("navsim_set_goal_rects", C.c_int, [_vp, _i32, _vp, _i32]),
     ("navsim_set_spawn_sampler", C.c_int, [_vp, _vp, _i32, _vp, _i32, _d, _d, _vp]),
     ("navsim_reset", C.c_int, [_vp, _vp, _vp, _vp]),

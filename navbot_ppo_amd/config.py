@@ -87,6 +87,10 @@ class PPOConfig:
     # the reference's users quote (main.py:135-252), not that of the noisy training rollouts -- on a second set of envs
     eval_every: int = 0
     eval_episodes: int = 100
+    # None: the evaluation env is built from the training world (its movers included).  Anything else is resolved like VecEnv's
+    # ``movers`` and given to the evaluation env only -- a held-out set of scenarios; with a bank of tapes the eval_* entries gain
+    # eval_scenario_success_min / eval_scenario_success_mean
+    eval_movers: object = None
 
     def __post_init__(self):
         check_minibatch_config(self)

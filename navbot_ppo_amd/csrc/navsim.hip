@@ -115,15 +115,26 @@ struct Params {
     const int32_t* mov_phase0;   // [N] per-env phase offset in [0, mov_P), the handle's copy; null = all zero
     int mov_P, mov_M;
     int mov_pack_log2;           // mover pass: log2(lanes per env) = log2(pow2ceil(mov_M)), as seg_pack_log2 for the static map
-    int spawn_per_env;           // spawn_scan / spawn_obs are [N][K][B]: per_env != 0, or movers with a per-env phase offset
+    int spawn_per_env;           // spawn_scan / spawn_obs are [N][K][B]: per_env != 0, or movers with a per-env phase offset / tape
+    // ---- a bank of tapes (navsim_set_mover_bank), appended.  mov_tape is then [K][Pmax][mov_M] and mov_P = period[0].
+    const uint2* mov_bp;         // [N] (base row = tape_id * Pmax, period of the env's tape), the handle's; null = (0, mov_P) for all
+    const int32_t* mov_tid;      // [N] tape id per env (the goal rectangles' index), the handle's; null = all zero
+    const double* mov_rects;     // [K][mov_n_rects][4] per-tape goal rejection rectangles (a NaN row is absent), the handle's; null = none
+    int mov_n_rects;
 };
 static_assert(offsetof(Params, max_ep_steps) == 128, "the hot head of Params");
 
-// The tape phase env i casts: `k` = steps taken in the episode (a step's scan: k = the counter before the step, + 1; a reset
-// observation and navsim_raycast before the first step: k = 0).  k < 2^30 + 1, phase0 < P <= 65536: no overflow.
+// The tape row env i casts: `k` = steps taken in the episode (a step's scan: k = the counter before the step, + 1; a reset
+// observation and navsim_raycast before the first step: k = 0), `bp` = (base row, period) of the env's tape.
+// k < 2^30 + 1, phase0 < period <= 65536, base < 2^24: no overflow.
+__device__ __forceinline__ uint32_t mover_row(const uint2 bp, const uint32_t k, const uint32_t phase0) {
+    return bp.x + (k + phase0) % bp.y;
+}
+// (base row, period) of env i's tape from global memory (the single-step kernels, reset scans, navsim_raycast)
 template <class PRef>
-__device__ __forceinline__ uint32_t mover_phase(PRef P, const uint32_t k, const uint32_t phase0) {
-    return (k + phase0) % (uint32_t)P.mov_P;
+__device__ __forceinline__ uint2 mover_bp(PRef P, const int i) {
+    const uint2* const bp = P.mov_bp;
+    return bp ? bp[i] : make_uint2(0u, (uint32_t)P.mov_P);
 }
 
 // ---------------------------------------------------------------- device helpers
@@ -278,11 +289,21 @@ __device__ __forceinline__ bool goal_rejected(const Rects& R, int which, double 
 
 // goal ~ U(lo,hi)^2 with rejection (environment_new.py:337-345 reset, :245-253 respawn);
 // one Philox call per attempt, counter = (env id, draws so far).
-template <class PRef>
+// MOV (the mover kernels, the reset kernel): the rectangles of env i's tape (Params::mov_rects, navsim_set_mover_bank) reject as
+// the handle's do, for both `which`.  They are read from global memory: a goal is drawn at episode ends only.
+template <class PRef, bool MOV = false>
 __device__ __forceinline__ void sample_goal(PRef P, const Rects& R, int i, int which, uint32_t& ctr, double& gx, double& gy) {
     const uint64_t gid = P.env_id_base + (uint64_t)i;
     gx = 0;
     gy = 0;
+    [[maybe_unused]] const double* tr = nullptr;
+    [[maybe_unused]] int tn = 0;
+    if constexpr (MOV) {
+        if (P.mov_rects) {
+            tn = P.mov_n_rects;
+            tr = P.mov_rects + (size_t)(P.mov_tid ? P.mov_tid[i] : 0) * (size_t)tn * 4;
+        }
+    }
     for (int tries = 0; tries < kMaxGoalTries; ++tries) {
         uint32_t r[4];
         philox4x32_10((uint32_t)gid, (uint32_t)(gid >> 32), ctr, 0x6e617673u, P.key0, P.key1, r);
@@ -291,7 +312,14 @@ __device__ __forceinline__ void sample_goal(PRef P, const Rects& R, int i, int w
         const double uy = (double)((((uint64_t)r[2] << 32) | r[3]) >> 11) * 0x1.0p-53;
         gx = P.goal_lo + (P.goal_hi - P.goal_lo) * ux;
         gy = P.goal_lo + (P.goal_hi - P.goal_lo) * uy;
-        if (!goal_rejected(R, which, gx, gy)) break;
+        bool rej = goal_rejected(R, which, gx, gy);
+        if constexpr (MOV) {
+            for (int k = 0; k < tn; ++k) {   // (a NaN entry compares false: the row is absent)
+                const double* q = tr + 4 * k;
+                rej |= (q[0] <= gx) & (gx <= q[1]) & (q[2] <= gy) & (gy <= q[3]);
+            }
+        }
+        if (!rej) break;
     }
 }
 
@@ -300,11 +328,11 @@ __device__ __forceinline__ void sample_goal(PRef P, const Rects& R, int i, int w
 //   G  > 0  GoalSpawnSampler.sample_start_and_goal (project_ppo/src/spawn_goal_sampler.py:52-62): uniform picks from the
 //           start-pose and goal tables until min_dist <= |start - goal| <= max_dist, at most 100 attempts, then one
 //           unconditional pick.  One Philox call per attempt.
-template <class PRef>
+template <class PRef, bool MOV = false>
 __device__ __forceinline__ void sample_episode(PRef P, const Rects& R, int i, uint32_t& ctr, int& k, double& gx, double& gy) {
     if (P.G == 0) {
         k = 0;
-        sample_goal<PRef>(P, R, i, 0, ctr, gx, gy);
+        sample_goal<PRef, MOV>(P, R, i, 0, ctr, gx, gy);
         return;
     }
     const uint64_t gid = P.env_id_base + (uint64_t)i;
@@ -368,8 +396,9 @@ struct StepSmem {
 // one, step_body takes the base and reaches the rest through a cast that only its MOV branches contain.
 template <int NB, int EPB, int NW = 4>
 struct StepSmemMov : StepSmem<NB, EPB, NW> {
-    uint32_t mv_phase[EPB];      // the tape phase each env's scan sees this step, published by the pose lanes before barrier A
+    uint32_t mv_phase[EPB];      // the tape row each env's scan sees this step, published by the pose lanes before barrier A
     uint32_t mv_phase0[EPB];     // persistent kernels: Params::mov_phase0 of the workgroup's envs, staged once per launch
+    uint2 mv_bp[EPB];            // ... and their tapes' (base row, period) (Params::mov_bp)
 };
 
 // Correctly rounded K / Dn for positive, normal-range operands (Dn in [2^-60, 2^20], K in {0} U [2^-60, 2^20]):
@@ -543,6 +572,7 @@ __device__ __forceinline__ void step_body(PRef P, StepSmem<NB, EPB, NW>& sm, int
     float2 act = make_float2(0.f, 0.f), pact = make_float2(0.f, 0.f);
     uint32_t ctr = 0, stepw = 0;
     [[maybe_unused]] uint32_t mv_ph0 = 0;   // MOV: the env's phase offset (Params::mov_phase0)
+    [[maybe_unused]] uint2 mv_bp = make_uint2(0u, 1u);   // MOV: (base row, period) of the env's tape (Params::mov_bp)
     const int el_pose = (64 / LPE) * wave + (lane / LPE);  // env (local) this pose lane works for
     const int rr = lane % LPE;
     const bool pose_lane = (wave < PWP) && (el_pose < EPB);
@@ -645,6 +675,7 @@ __device__ __forceinline__ void step_body(PRef P, StepSmem<NB, EPB, NW>& sm, int
             stepw = (uint32_t)P.ep_step[i];
             if constexpr (MOV) {
                 if (rr == 0 && P.mov_phase0) mv_ph0 = (uint32_t)P.mov_phase0[i];
+                if (rr == 0) mv_bp = mover_bp<PRef>(P, i);
             }
             if (rr == 0) {
                 x = P.x[i]; y = P.y[i];
@@ -716,7 +747,10 @@ __device__ __forceinline__ void step_body(PRef P, StepSmem<NB, EPB, NW>& sm, int
                 act = sm.act_l[e];
                 ctr = sm.st_ctr[e];
                 stepw = sm.st_step[e];
-                if constexpr (MOV) mv_ph0 = static_cast<StepSmemMov<NB, EPB, NW>&>(sm).mv_phase0[e];
+                if constexpr (MOV) {
+                    mv_ph0 = static_cast<StepSmemMov<NB, EPB, NW>&>(sm).mv_phase0[e];
+                    mv_bp = static_cast<StepSmemMov<NB, EPB, NW>&>(sm).mv_bp[e];
+                }
                 if (rr == 0) {
                     x = sm.st_d[0][e]; y = sm.st_d[1][e];
                     gx = sm.st_d[3][e]; gy = sm.st_d[4][e]; pdist = sm.st_d[5][e];
@@ -739,11 +773,11 @@ __device__ __forceinline__ void step_body(PRef P, StepSmem<NB, EPB, NW>& sm, int
             // the heading after the step is th0 + kSubsteps additions of delta_theta (same roundings as the serial loop, :160)
             for (int k = 0; k < kSubsteps; ++k) th += delta_theta;
             arg = (rr == 0) ? th : (delta_theta / 2.0);
-            // MOV: the phase this step's scan sees, tape[(k + 1 + phase0) mod P] with k the step counter before the step -- integer
-            // work that issues under the latency of the float64 chain above
+            // MOV: the row this step's scan sees, base + (k + 1 + phase0) mod period of the env's tape with k the step counter before
+            // the step -- integer work that issues under the latency of the float64 chain above
             if constexpr (MOV) {
                 if (rr == 0)
-                    static_cast<StepSmemMov<NB, EPB, NW>&>(sm).mv_phase[el_pose] = mover_phase<PRef>(P, (stepw & kStepMask) + 1u, mv_ph0);
+                    static_cast<StepSmemMov<NB, EPB, NW>&>(sm).mv_phase[el_pose] = mover_row(mv_bp, (stepw & kStepMask) + 1u, mv_ph0);
             }
         }
         // spec lanes that share wave 0 with the pose lanes (small shapes): behind the wheel arithmetic -- the wait for the state
@@ -925,12 +959,12 @@ __device__ __forceinline__ void step_body(PRef P, StepSmem<NB, EPB, NW>& sm, int
             }
             if (!current) {
                 if (c == 1) {
-                    sample_goal<PRef>(P, sm.rects, ie, 1, sctr, rgx, rgy);
+                    sample_goal<PRef, MOV>(P, sm.rects, ie, 1, sctr, rgx, rgy);
                     rctr = sctr;
                     P.rsp_g[ie] = rgx; P.rsp_g[N + ie] = rgy; P.rsp_ctr[ie] = rctr;
                 }
                 if (P.auto_reset) {
-                    sample_episode<PRef>(P, sm.rects, ie, sctr, sk, tgx, tgy);
+                    sample_episode<PRef, MOV>(P, sm.rects, ie, sctr, sk, tgx, tgy);
                     request_row(sk);
                     px = P.starts[3 * sk]; py = P.starts[3 * sk + 1]; pth = P.starts[3 * sk + 2];
                     double ryaw, rrel, rdiff;
@@ -1523,7 +1557,10 @@ __global__ __launch_bounds__(64 * 8) void step_mov_kernel(StepKArgs) {
 template <int NB, int EPB, int NW, class PRef>
 __device__ __forceinline__ void load_mover_phase0(PRef P, StepSmemMov<NB, EPB, NW>& sm, const int base, const int nloc) {
     const int32_t* const ph0 = P.mov_phase0;
-    if ((int)threadIdx.x < nloc) sm.mv_phase0[threadIdx.x] = ph0 ? (uint32_t)ph0[base + threadIdx.x] : 0u;
+    if ((int)threadIdx.x < nloc) {
+        sm.mv_phase0[threadIdx.x] = ph0 ? (uint32_t)ph0[base + threadIdx.x] : 0u;
+        sm.mv_bp[threadIdx.x] = mover_bp<PRef>(P, base + (int)threadIdx.x);   // (a bank: the tape of each env)
+    }
 }
 
 // ---------------------------------------------------------------- the persistent rollout kernel (PPO.rollout, ppo.py:463-641)
@@ -2314,7 +2351,7 @@ __global__ void reset_kernel(Params P, const uint8_t* __restrict__ mask, void* _
     uint32_t ctr = P.rng_ctr[i];
     double gx, gy, yaw, rel_theta, diff;
     int k0;
-    sample_episode<const Params&>(P, *P.rects, i, ctr, k0, gx, gy);
+    sample_episode<const Params&, true>(P, *P.rects, i, ctr, k0, gx, gy);
     const double x = P.starts[3 * k0], y = P.starts[3 * k0 + 1], th = P.starts[3 * k0 + 2];
     goal_angles(x, y, th, gx, gy, yaw, rel_theta, diff);
     const double dist = hypot(gx - x, gy - y);
@@ -2350,7 +2387,8 @@ __global__ void reset_kernel(Params P, const uint8_t* __restrict__ mask, void* _
 //   spawn scans:  n_poses_per_env = K, shared_poses = 1 : pose table [K][3] reused by every env
 //   navsim_raycast: n_poses_per_env = 1, shared_poses = 0 : pose[t]
 // Movers (Params::mov_tape): the env's tape phase joins its static map -- the reset phase phase0[env] for the spawn scans
-// (shared_poses = 1), the phase the env last observed, (ep_step + phase0) mod P, for navsim_raycast (shared_poses = 0).
+// (shared_poses = 1), the phase the env last observed, (ep_step + phase0) mod P, for navsim_raycast (shared_poses = 0); with a
+// bank of tapes (navsim_set_mover_bank) P and the base row are those of the env's own tape (mover_bp).
 __global__ void raycast_kernel(Params P, const double* __restrict__ pose, int n_poses_per_env, int shared_poses, int n,
                                int raw, float* __restrict__ ranges) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -2364,7 +2402,7 @@ __global__ void raycast_kernel(Params P, const double* __restrict__ pose, int n_
     const float4* __restrict__ mv = nullptr;
     if (P.mov_tape) {
         const uint32_t k = shared_poses ? 0u : ((uint32_t)P.ep_step[env] & kStepMask);
-        mv = P.mov_tape + (size_t)mover_phase<const Params&>(P, k, P.mov_phase0 ? (uint32_t)P.mov_phase0[env] : 0u) * (size_t)P.mov_M;
+        mv = P.mov_tape + (size_t)mover_row(mover_bp<const Params&>(P, env), k, P.mov_phase0 ? (uint32_t)P.mov_phase0[env] : 0u) * (size_t)P.mov_M;
     }
     const int n_mov = mv ? P.mov_M : 0;
     for (int b = 0; b < P.B; ++b) {
@@ -2597,6 +2635,9 @@ struct navsim {
     double* goals_dev = nullptr;    // [G][2]
     const float* seg_dev = nullptr;
     int32_t* mov_phase0_dev = nullptr;   // navsim_set_movers: the handle's copy of the per-env phase offsets
+    uint2* mov_bp_dev = nullptr;         // navsim_set_mover_bank: (base row, period), the tape id and the tapes' goal rectangles
+    int32_t* mov_tid_dev = nullptr;
+    double* mov_rects_dev = nullptr;
     bool has_map = false;
     // kernel-shape overrides of THIS handle (navsim_set_shape; tests and A/B timing): envs per workgroup, 0 = the rule of pick_epb
     // below; pair_cast false = 64-segment passes for every map
@@ -2926,6 +2967,9 @@ void navsim_destroy(navsim_t* h) {
     (void)hipFree(h->starts_sc_dev);
     (void)hipFree(h->goals_dev);
     (void)hipFree(h->mov_phase0_dev);
+    (void)hipFree(h->mov_bp_dev);
+    (void)hipFree(h->mov_tid_dev);
+    (void)hipFree(h->mov_rects_dev);
     delete h;
 }
 
@@ -2984,7 +3028,7 @@ int navsim_set_goal_rects(navsim_t* h, int32_t which, const double* rects_host, 
 
 static int rebuild_spawn_scans(navsim* h, hipStream_t st) {
     Params& P = h->P;
-    P.spawn_per_env = (P.per_env || (P.mov_tape && P.mov_phase0)) ? 1 : 0;   // movers with phase offsets: every env resets into its own phase
+    P.spawn_per_env = (P.per_env || (P.mov_tape && (P.mov_phase0 || P.mov_bp))) ? 1 : 0;   // movers with phase offsets or tape ids: every env resets into its own row
     const size_t n_poses = (size_t)(P.spawn_per_env ? P.N : 1) * P.K;
     if (h->spawn_scan_dev) {
         HIP_TRY(hipStreamSynchronize(st));
@@ -3089,47 +3133,121 @@ int navsim_set_map(navsim_t* h, const float* seg_dev, int32_t n_segments, int32_
     return NAVSIM_OK;
 }
 
-int navsim_set_movers(navsim_t* h, const float* tape_dev, int32_t period, int32_t n_segments, const int32_t* phase0_dev,
-                      void* stream) {
-    if (!h) return fail(NAVSIM_E_ARG, "navsim_set_movers: null handle");
-    if (!h->has_map) return fail(NAVSIM_E_STATE, "navsim_set_movers: call navsim_set_map first");
-    hipStream_t st = (hipStream_t)stream;
+// The one implementation behind navsim_set_movers (K = 1, no ids, no rectangles) and navsim_set_mover_bank: every check comes
+// before the first change of the handle.  `fn` names the entry point in the messages.
+static int set_mover_bank_impl(navsim* h, const char* fn, const float* bank_dev, int32_t K, int32_t Pmax, int32_t M,
+                               const int32_t* period_host, const int32_t* tape_id_dev, const int32_t* phase0_dev,
+                               const double* rects_host, int32_t n_rects, hipStream_t st) {
     Params& P = h->P;
-    if (tape_dev) {
-        if (period < 1 || period > 65536 || n_segments < 1 || n_segments > 64)
-            return fail(NAVSIM_E_ARG, "navsim_set_movers: 1 <= period <= 65536 and 1 <= n_segments <= 64");
-        if ((uintptr_t)tape_dev & 15) return fail(NAVSIM_E_ARG, "navsim_set_movers: the tape must be 16-byte aligned");
-        if (P.B != 10 || (P.per_env & 1)) return fail(NAVSIM_E_ARG, std::string("navsim_set_movers: ") + kMoversNotBuilt);
-    }
+    const std::string pre = std::string(fn) + ": ";
     HIP_TRY(hipStreamSynchronize(st));   // launches in flight read the old tape / phase offsets
-    std::vector<int32_t> ph0;
-    if (tape_dev && phase0_dev) {
-        ph0.resize((size_t)P.N);
-        HIP_TRY(hipMemcpy(ph0.data(), phase0_dev, sizeof(int32_t) * P.N, hipMemcpyDeviceToHost));
-        for (const int32_t v : ph0)
-            if (v < 0 || v >= period) return fail(NAVSIM_E_ARG, "navsim_set_movers: a phase0 value lies outside [0, period)");
+    std::vector<int32_t> ph0, tid;
+    std::vector<uint2> bp;
+    if (bank_dev) {
+        for (int k = 0; k < K; ++k)
+            if (period_host[k] < 1 || period_host[k] > Pmax) return fail(NAVSIM_E_ARG, pre + "a period lies outside [1, max_period]");
+        if (tape_id_dev) {
+            tid.resize((size_t)P.N);
+            HIP_TRY(hipMemcpy(tid.data(), tape_id_dev, sizeof(int32_t) * P.N, hipMemcpyDeviceToHost));
+            for (const int32_t v : tid)
+                if (v < 0 || v >= K) return fail(NAVSIM_E_ARG, pre + "a tape id lies outside [0, n_tapes)");
+        }
+        if (phase0_dev) {
+            ph0.resize((size_t)P.N);
+            HIP_TRY(hipMemcpy(ph0.data(), phase0_dev, sizeof(int32_t) * P.N, hipMemcpyDeviceToHost));
+            for (int i = 0; i < P.N; ++i)
+                if (ph0[i] < 0 || ph0[i] >= period_host[tid.empty() ? 0 : tid[i]])
+                    return fail(NAVSIM_E_ARG, pre + "a phase0 value lies outside [0, period)");
+        }
+        if (!tid.empty()) {
+            bp.resize((size_t)P.N);
+            for (int i = 0; i < P.N; ++i) bp[i] = make_uint2((uint32_t)tid[i] * (uint32_t)Pmax, (uint32_t)period_host[tid[i]]);
+        }
     }
+    const bool had_rects = P.mov_rects != nullptr;
     (void)hipFree(h->mov_phase0_dev);
-    h->mov_phase0_dev = nullptr;
+    (void)hipFree(h->mov_bp_dev);
+    (void)hipFree(h->mov_tid_dev);
+    (void)hipFree(h->mov_rects_dev);
+    h->mov_phase0_dev = h->mov_tid_dev = nullptr;
+    h->mov_bp_dev = nullptr;
+    h->mov_rects_dev = nullptr;
     P.mov_tape = nullptr;
     P.mov_phase0 = nullptr;
-    P.mov_P = P.mov_M = P.mov_pack_log2 = 0;
-    if (tape_dev) {
+    P.mov_bp = nullptr;
+    P.mov_tid = nullptr;
+    P.mov_rects = nullptr;
+    P.mov_P = P.mov_M = P.mov_pack_log2 = P.mov_n_rects = 0;
+    if (bank_dev) {
         if (!ph0.empty()) {
             HIP_TRY(hipMalloc(&h->mov_phase0_dev, sizeof(int32_t) * P.N));
             HIP_TRY(hipMemcpy(h->mov_phase0_dev, ph0.data(), sizeof(int32_t) * P.N, hipMemcpyHostToDevice));
         }
-        P.mov_tape = reinterpret_cast<const float4*>(tape_dev);
+        if (!tid.empty()) {
+            HIP_TRY(hipMalloc(&h->mov_tid_dev, sizeof(int32_t) * P.N));
+            HIP_TRY(hipMemcpy(h->mov_tid_dev, tid.data(), sizeof(int32_t) * P.N, hipMemcpyHostToDevice));
+            HIP_TRY(hipMalloc(&h->mov_bp_dev, sizeof(uint2) * P.N));
+            HIP_TRY(hipMemcpy(h->mov_bp_dev, bp.data(), sizeof(uint2) * P.N, hipMemcpyHostToDevice));
+        }
+        if (rects_host && n_rects > 0) {
+            HIP_TRY(hipMalloc(&h->mov_rects_dev, sizeof(double) * 4 * (size_t)n_rects * (size_t)K));
+            HIP_TRY(hipMemcpy(h->mov_rects_dev, rects_host, sizeof(double) * 4 * (size_t)n_rects * (size_t)K, hipMemcpyHostToDevice));
+            P.mov_rects = h->mov_rects_dev;
+            P.mov_n_rects = n_rects;
+        }
+        P.mov_tape = reinterpret_cast<const float4*>(bank_dev);
         P.mov_phase0 = h->mov_phase0_dev;
-        P.mov_P = period;
-        P.mov_M = n_segments;
+        P.mov_bp = h->mov_bp_dev;
+        P.mov_tid = h->mov_tid_dev;
+        P.mov_P = period_host[0];
+        P.mov_M = M;
         int lg = 0;
-        while ((1 << lg) < n_segments) ++lg;
+        while ((1 << lg) < M) ++lg;
         P.mov_pack_log2 = lg;
     }
-    // the reset observation sees tape[phase0[i]]: the spawn tables (and with them the cached next-episode records' scan rows, which
-    // are read through the tables at every step) are rebuilt for the new world
+    // per-tape goal rectangles came or went: the cached next-episode records hold goals drawn under the old ones
+    if (had_rects || P.mov_rects) {
+        const int rc = invalidate_records(h, st);
+        if (rc != NAVSIM_OK) return rc;
+    }
+    // the reset observation sees bank[t][phase0[i]]: the spawn tables (and with them the cached next-episode records' scan rows,
+    // which are read through the tables at every step) are rebuilt for the new world
     return rebuild_spawn_scans(h, st);
+}
+
+int navsim_set_movers(navsim_t* h, const float* tape_dev, int32_t period, int32_t n_segments, const int32_t* phase0_dev,
+                      void* stream) {
+    if (!h) return fail(NAVSIM_E_ARG, "navsim_set_movers: null handle");
+    if (!h->has_map) return fail(NAVSIM_E_STATE, "navsim_set_movers: call navsim_set_map first");
+    if (tape_dev) {
+        if (period < 1 || period > 65536 || n_segments < 1 || n_segments > 64)
+            return fail(NAVSIM_E_ARG, "navsim_set_movers: 1 <= period <= 65536 and 1 <= n_segments <= 64");
+        if ((uintptr_t)tape_dev & 15) return fail(NAVSIM_E_ARG, "navsim_set_movers: the tape must be 16-byte aligned");
+        if (h->P.B != 10 || (h->P.per_env & 1)) return fail(NAVSIM_E_ARG, std::string("navsim_set_movers: ") + kMoversNotBuilt);
+    }
+    // the bank with one tape, ids 0 and no rectangles
+    return set_mover_bank_impl(h, "navsim_set_movers", tape_dev, 1, period, n_segments, &period, nullptr, phase0_dev, nullptr, 0,
+                               (hipStream_t)stream);
+}
+
+int navsim_set_mover_bank(navsim_t* h, const float* bank_dev, int32_t n_tapes, int32_t max_period, int32_t n_segments,
+                          const int32_t* period_host, const int32_t* tape_id_dev, const int32_t* phase0_dev,
+                          const double* goal_rects_host, int32_t n_rects, void* stream) {
+    if (!h) return fail(NAVSIM_E_ARG, "navsim_set_mover_bank: null handle");
+    if (!h->has_map) return fail(NAVSIM_E_STATE, "navsim_set_mover_bank: call navsim_set_map first");
+    if (bank_dev) {
+        if (n_tapes < 1 || max_period < 1 || max_period > 65536 || n_segments < 1 || n_segments > 64 ||
+            (int64_t)n_tapes * (int64_t)max_period > ((int64_t)1 << 24))
+            return fail(NAVSIM_E_ARG, "navsim_set_mover_bank: 1 <= n_tapes, 1 <= max_period <= 65536, n_tapes * max_period <= 2^24 "
+                                      "and 1 <= n_segments <= 64");
+        if (!period_host) return fail(NAVSIM_E_ARG, "navsim_set_mover_bank: the periods are missing");
+        if ((uintptr_t)bank_dev & 15) return fail(NAVSIM_E_ARG, "navsim_set_mover_bank: the bank must be 16-byte aligned");
+        if (n_rects < 0 || n_rects > 8) return fail(NAVSIM_E_ARG, "navsim_set_mover_bank: 0 <= n_rects <= 8");
+        if (n_rects > 0 && !goal_rects_host) return fail(NAVSIM_E_ARG, "navsim_set_mover_bank: n_rects > 0 without rectangles");
+        if (h->P.B != 10 || (h->P.per_env & 1)) return fail(NAVSIM_E_ARG, std::string("navsim_set_mover_bank: ") + kMoversNotBuilt);
+    }
+    return set_mover_bank_impl(h, "navsim_set_mover_bank", bank_dev, n_tapes, max_period, n_segments, period_host, tape_id_dev,
+                               phase0_dev, goal_rects_host, n_rects, (hipStream_t)stream);
 }
 
 int navsim_set_spawn_sampler(navsim_t* h, const double* starts_host, int32_t n_starts, const double* goals_host,

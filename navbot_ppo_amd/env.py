@@ -64,6 +64,7 @@ class NavSim:
         self._seg = None  # keeps the map tensor alive: the handle only borrows the pointer
         self._mov_tape = self._mov_phase0 = None   # the same for the mover tape (set_movers)
         self.movers_period = self.movers_segments = 0
+        self.movers_tapes, self.movers_tape_id = 0, None   # set_mover_bank: tapes in the bank, the envs' tape ids (None = all 0)
         self.generation = 0  # bumped whenever device pointers / scalars a captured hipGraph would have frozen change
         def knob(name):   # a dev tool's environment variable; anything that is not an integer is ignored, as the library used to
             try:
@@ -133,6 +134,7 @@ class NavSim:
                 check(lib().navsim_set_movers(self._h, None, 0, 0, None, _stream()), "navsim_set_movers")
             self._mov_tape = self._mov_phase0 = None
             self.movers_period = self.movers_segments = 0
+            self.movers_tapes, self.movers_tape_id = 0, None
             self.generation += 1
             return
         tape = torch.as_tensor(np.asarray(tape, dtype=np.float32) if not torch.is_tensor(tape) else tape)
@@ -153,6 +155,56 @@ class NavSim:
                   "navsim_set_movers")
         self._mov_tape, self._mov_phase0 = tape, phase0
         self.movers_period, self.movers_segments = int(tape.shape[0]), int(tape.shape[1])
+        self.movers_tapes, self.movers_tape_id = 1, None
+        self.generation += 1
+
+    def set_mover_bank(self, bank, periods=None, tape_id=None, phase0=None, goal_rects=None):
+        """A bank of tapes, one scenario per env (navsim_set_mover_bank): bank [K, Pmax, M, 4] float32 (maps.mover_bank pads it),
+        periods [K] integers in [1, Pmax] (None: all Pmax), tape_id [N] integers in [0, K) (None: all 0), phase0 [N] integers in
+        [0, periods[tape_id[i]]) (None: all 0), goal_rects [K, R, 4] float64 (xmin, xmax, ymin, ymax), R <= 8, a row with a NaN absent
+        (None: none).  Env i's scan sees bank[t][(k + 1 + phase0[i]) % periods[t]], t = tape_id[i]: set_movers' rule per env; a
+        uniform-box goal draw of env i is also rejected inside its tape's rectangles.  Rows periods[k] .. Pmax-1 of a tape are never
+        read.  The bank is BORROWED exactly as set_movers borrows its tape; ids, phases, periods and rectangles are copied.  A call
+        of either replaces what the other set; bank=None turns movers off."""
+        if bank is None:
+            return self.set_movers(None)
+        bank = torch.as_tensor(np.asarray(bank, dtype=np.float32) if not torch.is_tensor(bank) else bank)
+        bank = bank.to(device=self.device, dtype=torch.float32).contiguous()
+        if bank.dim() != 4 or bank.shape[-1] != 4 or min(bank.shape[:3]) < 1:
+            raise NavsimError(f"set_mover_bank: bank must be [K, Pmax, M, 4], got {tuple(bank.shape)}")
+        K, Pmax, M = (int(v) for v in bank.shape[:3])
+        if bank.data_ptr() % 16:
+            raise NavsimError("set_mover_bank: the bank must be 16-byte aligned")
+        per = np.full(K, Pmax, dtype=np.int32) if periods is None else np.ascontiguousarray(np.asarray(periods).reshape(-1))
+        if per.size != K or not np.issubdtype(per.dtype, np.integer):
+            raise NavsimError(f"set_mover_bank: periods must be {K} integers, got {per.dtype} {per.shape}")
+        per = np.ascontiguousarray(per, dtype=np.int32)
+
+        def per_env(name, v):
+            if v is None:
+                return None
+            t = torch.as_tensor(np.asarray(v) if not torch.is_tensor(v) else v)
+            if t.is_floating_point() or t.numel() != self.N:
+                raise NavsimError(f"set_mover_bank: {name} must be {self.N} integers, got {t.dtype} {tuple(t.shape)}")
+            t = t.reshape(self.N).to(device=self.device, dtype=torch.int32).contiguous()
+            self._chk(f"set_mover_bank: {name}", t, torch.int32, self.N)
+            return t
+        tape_id, phase0 = per_env("tape_id", tape_id), per_env("phase0", phase0)
+        rects, n_rects = None, 0
+        if goal_rects is not None:
+            rects = np.ascontiguousarray(goal_rects, dtype=np.float64)
+            if rects.ndim != 3 or rects.shape[0] != K or rects.shape[2] != 4 or rects.shape[1] > 8:
+                raise NavsimError(f"set_mover_bank: goal_rects must be [{K}, R <= 8, 4], got {rects.shape}")
+            n_rects = int(rects.shape[1])
+            if n_rects == 0:
+                rects = None
+        self._chk("set_mover_bank: bank", bank, torch.float32, bank.numel())
+        with torch.cuda.device(self.device):
+            check(lib().navsim_set_mover_bank(self._h, _ptr(bank), K, Pmax, M, _np_ptr(per), _ptr(tape_id), _ptr(phase0),
+                                              _np_ptr(rects), n_rects, _stream()), "navsim_set_mover_bank")
+        self._mov_tape, self._mov_phase0 = bank, phase0
+        self.movers_period, self.movers_segments = Pmax, M
+        self.movers_tapes, self.movers_tape_id = K, tape_id
         self.generation += 1
 
     def set_goal_rects(self, which, rects):
@@ -385,7 +437,10 @@ class VecEnv:
                  movers=None):
         """movers: moving obstacles (NavSim.set_movers) -- a name of maps.movers_by_name ("orbit4"), a tape [P, M, 4], or a dict:
         tape=... or name=... (+ period=...), phase="random" (default: phase0[i] drawn from (map_seed, env_id_base + i) only, so
-        the shards of a multi-GPU run and the single-GPU run give every global env the same phase) | "zero"."""
+        the shards of a multi-GPU run and the single-GPU run give every global env the same phase) | "zero".
+        A BANK of tapes, one scenario per env (NavSim.set_mover_bank, maps.resolve_movers): dict(bank=..., periods=..., rects=...,
+        assign="random" (default: the tape id from the same hash) | "cycle" | [N] ids), "random:K" (dict(name="random:K", seed=...))
+        or "bank:orbit4,patrol2,..."."""
         thr = 0.2 if is_training else 0.4  # environment_new.py:44-47
         # what a sibling env on the same world is built from (PPOTrainer's evaluation env: same map / beams / row type / sensor)
         self.world_args = dict(map=map, n_beams=n_beams, per_env_map=per_env_map, map_seed=map_seed, obs_f16=obs_f16,
@@ -414,8 +469,13 @@ class VecEnv:
             self.sim.set_spawn_sampler(*sampler)
         if movers is not None:
             tape, phase = _maps.resolve_movers(movers)
-            phase0 = None if phase == "zero" else _maps.mover_phases(tape.shape[0], self.N, map_seed=map_seed, env_id_base=env_id_base)
-            self.sim.set_movers(tape, phase0)
+            if isinstance(tape, _maps.MoverBank):   # one scenario per env: ids and phases from (map_seed, global env id) only
+                ids = tape.tape_ids(self.N, map_seed=map_seed, env_id_base=env_id_base)
+                phase0 = None if phase == "zero" else _maps.mover_bank_phases(tape.periods[ids], map_seed=map_seed, env_id_base=env_id_base)
+                self.sim.set_mover_bank(tape.bank, tape.periods, ids, phase0, tape.rects)
+            else:
+                phase0 = None if phase == "zero" else _maps.mover_phases(tape.shape[0], self.N, map_seed=map_seed, env_id_base=env_id_base)
+                self.sim.set_movers(tape, phase0)
         self.io = self.sim.alloc_io()
 
     def close(self):

@@ -67,7 +67,9 @@ def evaluate(actor, num_episodes=100, max_timesteps_per_episode=500, map="stage_
     persistent=True replaces the stepping loop by ONE launch (VecEnv.evaluate_policy: the HIP actor and the env step alternate
     inside the kernel, the quota is kept on chip, a workgroup stops when its envs are done); rows, order, CSV, summary and log
     line come from the same code.  The ``time`` column is then length x (wall clock / the most steps any workgroup ran).  An
-    actor or beam count without an evaluation kernel raises ValueError.  movers: moving obstacles as for VecEnv.  timing: a dict that receives ``seconds`` (wall clock
+    actor or beam count without an evaluation kernel raises ValueError.  movers: moving obstacles as for VecEnv; with a bank of
+    tapes the result also holds ``scenarios`` (scenario_report: per tape id episodes and success / collision / time-out rate),
+    ``scenario_success_min`` / ``_mean``, logged and, with an output_dir, written to ``<method>_eval_scenarios.csv``.  timing: a dict that receives ``seconds`` (wall clock
     of the stepping alone) and ``steps`` (env steps behind it)."""
     n_par = int(n_parallel or min(num_episodes, 1024))
     quota = -(-int(num_episodes) // n_par)
@@ -76,6 +78,9 @@ def evaluate(actor, num_episodes=100, max_timesteps_per_episode=500, map="stage_
     env = VecEnv(n_par, map=map, max_episode_steps=max_timesteps_per_episode, auto_reset=True, is_training=False, seed=seed,
                  device=device, movers=movers)
     dev = env.device
+    # a bank of tapes (one scenario per env): the episode table is also grouped by the env's tape id, on the host
+    tape_id = None if env.sim.movers_tape_id is None else env.sim.movers_tape_id.cpu().numpy()
+    n_tapes = env.sim.movers_tapes
     if persistent:
         flat_actor = flat_actor.to(dev)
         torch.cuda.synchronize(dev)
@@ -90,7 +95,7 @@ def evaluate(actor, num_episodes=100, max_timesteps_per_episode=500, map="stage_
         fl = tab.flags
         res = torch.stack([(fl & 1).double(), ((fl >> 1) & 1).double(), ((fl >> 2) & 1).double(), tab.length.double(),
                            tab.ret.double(), tab.path.double()], 2)
-        return _report(res, quota, n_par, num_episodes, seconds, steps, output_dir, method_name, log, timing)
+        return _report(res, quota, n_par, num_episodes, seconds, steps, output_dir, method_name, log, timing, tape_id, n_tapes)
     actor = actor.to(dev).eval()
     obs = env.reset()
     count = torch.zeros(n_par, dtype=torch.int64, device=dev)
@@ -118,10 +123,32 @@ def evaluate(actor, num_episodes=100, max_timesteps_per_episode=500, map="stage_
     torch.cuda.synchronize(dev)
     seconds = time.time() - t0
     env.close()
-    return _report(res, quota, n_par, num_episodes, seconds, steps, output_dir, method_name, log, timing)
+    return _report(res, quota, n_par, num_episodes, seconds, steps, output_dir, method_name, log, timing, tape_id, n_tapes)
 
 
-def _report(res, quota, n_par, num_episodes, seconds, steps, output_dir, method_name, log, timing):
+def scenario_report(rows, tape_id, n_tapes):
+    """The episode table grouped by scenario: rows = evaluate()'s rows in their slot-major order (row r was played by env
+    r mod len(tape_id)), tape_id [n_par] the tape of each env -> one dict per tape of the bank: scenario, episodes and the success,
+    collision and time-out rate of its episodes (NaN for a scenario no reported episode played)."""
+    tape_id = np.asarray(tape_id).reshape(-1)
+    arr = np.array([r[1:4] for r in rows], dtype=np.float64).reshape(-1, 3)
+    of_row = tape_id[np.arange(arr.shape[0]) % tape_id.size]
+    out = []
+    for k in range(int(n_tapes)):
+        sel = arr[of_row == k]
+        rate = sel.mean(axis=0) if sel.shape[0] else np.full(3, np.nan)
+        out.append(dict(scenario=k, episodes=int(sel.shape[0]), success_rate=float(rate[0]), collision_rate=float(rate[1]),
+                        timeout_rate=float(rate[2])))
+    return out
+
+
+def scenario_success(scenarios):
+    """(min, mean) of the success rate over the scenarios that played at least one episode"""
+    s = [d["success_rate"] for d in scenarios if d["episodes"] > 0]
+    return (min(s), sum(s) / len(s)) if s else (float("nan"), float("nan"))
+
+
+def _report(res, quota, n_par, num_episodes, seconds, steps, output_dir, method_name, log, timing, tape_id=None, n_tapes=0):
     """rows, CSV, summary and log line of evaluate() from the [quota, n_par, 6] episode table of either stepping path"""
     sec_per_step = seconds / max(steps, 1)
     if timing is not None:
@@ -149,4 +176,20 @@ def _report(res, quota, n_par, num_episodes, seconds, steps, output_dir, method_
             + (f" csv={csv_path}" if csv_path else ""))
     summary["csv"] = csv_path
     summary["rows"] = rows
+    if tape_id is not None:
+        sc = scenario_report(rows, tape_id, n_tapes)
+        summary["scenarios"] = sc
+        summary["scenario_success_min"], summary["scenario_success_mean"] = scenario_success(sc)
+        summary["scenarios_csv"] = None
+        if output_dir:
+            summary["scenarios_csv"] = os.path.join(log_dir, f"{method_name}_eval_scenarios.csv")
+            with open(summary["scenarios_csv"], "w", newline="") as f:
+                w = csv.writer(f)
+                w.writerow(["scenario", "episodes", "success_rate", "collision_rate", "timeout_rate"])
+                w.writerows([[d["scenario"], d["episodes"], d["success_rate"], d["collision_rate"], d["timeout_rate"]] for d in sc])
+        if log:
+            log(f"EVALUATION SCENARIOS  method={method_name} scenarios={len(sc)} success min={summary['scenario_success_min'] * 100:.2f}% "
+                f"mean={summary['scenario_success_mean'] * 100:.2f}%  "
+                + " ".join(f"[{d['scenario']}: n={d['episodes']} succ={d['success_rate'] * 100:.1f}% coll={d['collision_rate'] * 100:.1f}% "
+                           f"tmo={d['timeout_rate'] * 100:.1f}%]" for d in sc))
     return summary

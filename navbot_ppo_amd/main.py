@@ -17,7 +17,7 @@ exceeds 1.5 x the target), --minibatch_size M / --minibatch_shuffle MODE (K = ce
 batch, shuffled on the device), --norm_reward / --clip_reward C (rewards scaled by the running standard deviation of the discounted
 return and clipped to +-C before the return scan), --lr_schedule adaptive|linear with --desired_kl / --lr_min / --lr_max (the KL-adaptive
 step size decided on the device after every optimiser step, or a linear decay over --max_timesteps), --bootstrap_truncated (time-outs
-bootstrap with gamma V of their own row and the batch end with V of the next observation instead of counting as terminal), --movers NAME / --movers_period P (moving obstacles beside the static map, training and evaluation).  Vision flags are accepted and refused (the camera
+bootstrap with gamma V of their own row and the batch end with V of the next observation instead of counting as terminal), --movers NAME / --movers_period P (moving obstacles beside the static map, training and evaluation; NAME random:K with --movers_seed or bank:a,b,... is a bank of scenarios, one per env), --eval_movers NAME / --eval_movers_seed (held-out scenarios for --eval_every).  Vision flags are accepted and refused (the camera
 modality is outside the LiDAR hot path); --mode test maps to --eval (the reference's test path is broken).
 """
 import argparse
@@ -85,6 +85,11 @@ def get_args(argv=None):
                    help="moving obstacles cast beside the static map (maps.movers_by_name: orbit4 = four pillars orbiting the spawn "
                         "pose); authored geometry: parity unpinned (no reference geometry); default: none")
     p.add_argument("--movers_period", type=int, default=None, help="env steps per cycle of --movers (default 64)")
+    p.add_argument("--movers_seed", type=int, default=0, help="the seed of --movers random:K (maps.random_mover_bank)")
+    p.add_argument("--eval_movers", type=str, default=None,
+                   help="training with --eval_every: the movers of the EVALUATION envs only, e.g. random:32 with another "
+                        "--eval_movers_seed -- a held-out set of scenarios; default: the training world's")
+    p.add_argument("--eval_movers_seed", type=int, default=1, help="the seed of --eval_movers random:K")
     args = p.parse_args(argv)
     if args.output_dir is None:
         args.output_dir = os.path.join(os.getcwd(), "runs")
@@ -117,12 +122,23 @@ def config_of(args, rollout):
                          target_kl=args.target_kl, minibatch_size=args.minibatch_size, minibatch_shuffle=args.minibatch_shuffle,
                          norm_reward=args.norm_reward, clip_reward=args.clip_reward, lr_schedule=args.lr_schedule,
                          desired_kl=args.desired_kl, lr_min=args.lr_min, lr_max=args.lr_max,
-                         bootstrap_truncated=args.bootstrap_truncated)
+                         bootstrap_truncated=args.bootstrap_truncated,
+                         eval_movers=movers_of(args.eval_movers, args.movers_period, args.eval_movers_seed))
+
+
+def movers_of(name, period, seed):
+    """--movers / --eval_movers -> VecEnv's ``movers``: a scene name, "random:K" (a seeded bank of scenarios, one per env) or
+    "bank:scene,scene,..." (maps.resolve_movers)"""
+    if not name:
+        return None
+    if name.startswith("random:"):
+        return dict(name=name, seed=seed)
+    return dict(name=name, period=period)
 
 
 def main(argv=None):
     args = get_args(argv)
-    movers = dict(name=args.movers, period=args.movers_period) if args.movers else None
+    movers = movers_of(args.movers, args.movers_period, args.movers_seed)
     import torch
     from . import evaluate as ev
     from . import maps, ppo

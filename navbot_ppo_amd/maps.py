@@ -194,39 +194,240 @@ def orbit_movers(period, n=4, orbit_radius=1.0, radius=0.15, sides=8, centre=(0.
 MOVERS_DEFAULT_PERIOD = 64
 
 
+def patrol_frame(p, period, ends, radius=0.15, sides=8):
+    """Phase p of patrol_movers: pillar k stands at a + s (b - a) of ends[k] = (ax, ay, bx, by), s = 1 - |1 - 2 (p mod period) / period|
+    (a at phase 0, b at half the period, back at a after one period).  float64 [len(ends) * sides, 4]."""
+    s = 1.0 - abs(1.0 - 2.0 * (p % period) / period)
+    segs = []
+    for ax, ay, bx, by in np.asarray(ends, dtype=np.float64).reshape(-1, 4):
+        segs += cylinder_to_segments(radius, ax + s * (bx - ax), ay + s * (by - ay), sides=sides)
+    return np.asarray(segs, dtype=np.float64)
+
+
+def patrol_movers(period, ends, radius=0.15, sides=8):
+    """AUTHORED: regular-polygon pillars going back and forth along the segments ``ends`` [n, 4] (ax, ay, bx, by), one round trip per
+    ``period`` steps.  Tape [period, n * sides, 4] float32."""
+    return mover_tape([patrol_frame(p, period, ends, radius, sides) for p in range(period)])
+
+
+def clutter_tape(centres, radius=0.15, sides=8):
+    """AUTHORED: standing pillars at ``centres`` [n, 2] as a tape of period 1 -- extra STATIC obstacles that differ from env to env
+    when they come from a bank.  Tape [1, n * sides, 4] float32."""
+    segs = []
+    for cx, cy in np.asarray(centres, dtype=np.float64).reshape(-1, 2):
+        segs += cylinder_to_segments(radius, cx, cy, sides=sides)
+    return mover_tape([segs])
+
+
+def clutter_rects(centres, radius=0.15, margin=0.3):
+    """Goal-rejection rectangles [n, 4] (xmin, xmax, ymin, ymax) round the pillars of clutter_tape: the pillar's bounding square
+    grown by ``margin`` (stage_2's rectangles: radius 0.3, margin 0.3)."""
+    c = np.asarray(centres, dtype=np.float64).reshape(-1, 2)
+    h = float(radius) + float(margin)
+    return np.stack([c[:, 0] - h, c[:, 0] + h, c[:, 1] - h, c[:, 1] + h], axis=1)
+
+
+def mover_bank(tapes, rects=None):
+    """A bank of tapes for NavSim.set_mover_bank: tapes = K arrays [P_k, M_k, 4], rects = None or K lists of rectangles
+    (xmin, xmax, ymin, ymax), possibly empty -> (bank [K, Pmax, Mmax, 4] float32, periods [K] int32, rects [K, R, 4] float64).
+    What a tape or a rectangle list does not fill is NaN: a segment with a NaN coordinate is never hit, a rectangle row with one
+    is absent, and rows periods[k] .. Pmax-1 of tape k are never read."""
+    tapes = [np.asarray(t, dtype=np.float32) for t in tapes]
+    if not tapes or any(t.ndim != 3 or t.shape[-1] != 4 or t.shape[0] < 1 or t.shape[1] < 1 for t in tapes):
+        raise ValueError("mover_bank: tapes must be a non-empty list of [P, M, 4] arrays")
+    K = len(tapes)
+    bank = np.full((K, max(t.shape[0] for t in tapes), max(t.shape[1] for t in tapes), 4), np.nan, dtype=np.float32)
+    for k, t in enumerate(tapes):
+        bank[k, :t.shape[0], :t.shape[1]] = t
+    periods = np.array([t.shape[0] for t in tapes], dtype=np.int32)
+    rl = [np.zeros((0, 4))] * K if rects is None else [np.asarray(r, dtype=np.float64).reshape(-1, 4) for r in rects]
+    if len(rl) != K:
+        raise ValueError(f"mover_bank: {len(rl)} rectangle lists for {K} tapes")
+    out = np.full((K, max(r.shape[0] for r in rl), 4), np.nan, dtype=np.float64)
+    for k, r in enumerate(rl):
+        out[k, :r.shape[0]] = r
+    return bank, periods, out
+
+
+def _scene_patrol2(P):
+    return patrol_movers(P, [(1.0, -1.0, 1.0, 1.0), (-1.0, 1.0, -1.0, -1.0)])
+
+
+_CLUTTER4 = [(2.6, 2.6), (-2.6, 2.6), (-2.6, -2.6), (2.6, -2.6)]   # where stage_2 has its pillars
+
+# name -> (tape of period P, goal rectangles or None).  All AUTHORED: parity unpinned (no reference geometry).
+_SCENES = {"orbit4": (lambda P: orbit_movers(P, n=4), None),
+           "orbit2": (lambda P: orbit_movers(P, n=2, orbit_radius=1.4), None),
+           "patrol2": (_scene_patrol2, None),
+           "clutter4": (lambda P: clutter_tape(_CLUTTER4, radius=0.3), clutter_rects(_CLUTTER4, 0.3, 0.3))}
+
+
 def movers_by_name(name, period=None):
-    table = {"orbit4": lambda P: orbit_movers(P, n=4)}
-    if name not in table:
-        raise KeyError(f"unknown movers {name!r}; have {sorted(table)}")
-    return table[name](int(period or MOVERS_DEFAULT_PERIOD))
+    if name not in _SCENES:
+        raise KeyError(f"unknown movers {name!r}; have {sorted(_SCENES)}")
+    return _SCENES[name][0](int(period or MOVERS_DEFAULT_PERIOD))
+
+
+def _seg_point_dist(ax, ay, bx, by, px, py):
+    ex, ey = bx - ax, by - ay
+    t = np.clip(((px - ax) * ex + (py - ay) * ey) / np.maximum(ex * ex + ey * ey, 1e-300), 0.0, 1.0)
+    return np.hypot(ax + t * ex - px, ay + t * ey - py)
+
+
+def mover_clearance(tape, starts=((0.0, 0.0),)):
+    """The smallest distance between a segment of any phase of ``tape`` [..., 4] and a start pose (NaN segments are absent)."""
+    g = np.asarray(tape, dtype=np.float64).reshape(-1, 4)
+    g = g[~np.isnan(g).any(axis=1)]
+    return min(float(_seg_point_dist(g[:, 0], g[:, 1], g[:, 2], g[:, 3], p[0], p[1]).min()) for p in starts) if g.size else math.inf
+
+
+def random_scenario(rng, period, goal_box=3.6, start=(0.0, 0.0), clear_radius=0.6, radius=0.15, sides=8, pillars=4):
+    """One AUTHORED scenario from ``rng``: ``pillars`` pillars, each an orbiter about the start pose, a patrol between two points of
+    the goal box or a standing pillar (period 1: standing pillars only), none of which comes within ``clear_radius`` of the start
+    pose in any phase.  -> (tape [period, pillars * sides, 4], rectangles round the standing pillars [n, 4])."""
+    keep = clear_radius + radius + 0.05
+
+    def point():
+        while True:
+            q = rng.uniform(-goal_box, goal_box, 2)
+            if math.hypot(q[0] - start[0], q[1] - start[1]) >= keep:
+                return q
+    kinds = ["clutter"] * pillars if period == 1 else list(rng.choice(["orbit", "patrol", "clutter"], size=pillars))
+    orbit, patrol, clutter = [], [], []
+    for kind in kinds:
+        if kind == "orbit":
+            orbit.append((rng.uniform(keep + 0.15, 1.6), rng.uniform(0.0, 2.0 * math.pi), rng.choice([-1.0, 1.0])))
+        elif kind == "patrol":
+            while True:
+                a, b = point(), point()
+                if _seg_point_dist(a[0], a[1], b[0], b[1], start[0], start[1]) >= keep:
+                    break
+            patrol.append((a[0], a[1], b[0], b[1]))
+        else:
+            clutter.append(point())
+    frames = []
+    for p in range(period):
+        segs = []
+        for r, a0, sgn in orbit:
+            a = a0 + sgn * 2.0 * math.pi * p / period
+            segs += cylinder_to_segments(radius, start[0] + r * math.cos(a), start[1] + r * math.sin(a), sides=sides)
+        if patrol:
+            segs += patrol_frame(p, period, patrol, radius, sides).tolist()
+        for cx, cy in clutter:
+            segs += cylinder_to_segments(radius, cx, cy, sides=sides)
+        frames.append(segs)
+    return mover_tape(frames), (clutter_rects(clutter, radius, 0.3) if clutter else np.zeros((0, 4)))
+
+
+def random_mover_bank(K, seed=0, period_choices=(1, 32, 64, 128), goal_box=3.6, start=(0.0, 0.0), clear_radius=0.6, radius=0.15,
+                      sides=8, pillars=4):
+    """AUTHORED: K scenarios, scenario k a pure function of (seed, k): a period drawn from ``period_choices`` and
+    random_scenario's mix of orbiters, patrols and standing clutter inside the goal box (period 1: clutter only, i.e. extra static
+    obstacles that differ from env to env).  Standing pillars come with their goal rectangles.  -> mover_bank's triple, every
+    tape with pillars * sides segments (32: orbit4's)."""
+    tapes, rects = [], []
+    for k in range(int(K)):
+        rng = np.random.default_rng([int(seed), k])
+        period = int(rng.choice(np.asarray(period_choices)))
+        t, r = random_scenario(rng, period, goal_box, start, clear_radius, radius, sides, pillars)
+        tapes.append(t)
+        rects.append(r)
+    return mover_bank(tapes, rects)
+
+
+class MoverBank:
+    """What resolve_movers returns for a bank: the arrays of mover_bank and how the envs are given their tapes."""
+
+    def __init__(self, bank, periods, rects, assign):
+        self.bank, self.periods, self.rects, self.assign = bank, periods, rects, assign
+
+    def tape_ids(self, n_envs, map_seed=0, env_id_base=0):
+        K = len(self.periods)
+        if isinstance(self.assign, str):
+            if self.assign == "random":
+                return mover_tape_ids(K, n_envs, map_seed, env_id_base)
+            return ((int(env_id_base) + np.arange(int(n_envs))) % K).astype(np.int32)   # "cycle", by the GLOBAL env id
+        ids = np.asarray(self.assign)
+        if ids.shape != (int(n_envs),) or not np.issubdtype(ids.dtype, np.integer) or ids.min() < 0 or ids.max() >= K:
+            raise ValueError(f"movers: assign must be 'random', 'cycle' or {n_envs} tape ids in [0, {K})")
+        return ids.astype(np.int32)
 
 
 def resolve_movers(movers):
-    """VecEnv's ``movers`` argument -> (tape [P, M, 4], phase rule "random" | "zero")."""
+    """VecEnv's ``movers`` argument -> (tape [P, M, 4], phase rule "random" | "zero") for a single tape -- a tape, a scene name
+    ("orbit4"), dict(tape=... | name=..., period=...) -- or (MoverBank, phase rule) for a bank of tapes, one scenario per env:
+    dict(bank=[K, Pmax, M, 4], periods=[K], rects=[K, R, 4], assign="random" | "cycle" | [N] ids), the name "random:K"
+    (random_mover_bank(K, seed), dict(name="random:K", seed=...)) or "bank:orbit4,patrol2,..." (one tape per listed scene)."""
     spec = dict(movers) if isinstance(movers, dict) else ({"name": movers} if isinstance(movers, str) else {"tape": movers})
     phase = spec.pop("phase", "random")
     if phase not in ("random", "zero"):
         raise ValueError(f"movers: phase must be 'random' or 'zero', got {phase!r}")
-    if ("tape" in spec) == ("name" in spec):
-        raise ValueError("movers: give a tape or a name")
-    if "tape" in spec:
-        tape = spec.pop("tape")
+    if sum(k in spec for k in ("tape", "name", "bank")) != 1:
+        raise ValueError("movers: give a tape or a name" if "bank" not in spec else "movers: give a bank, a tape or a name")
+    out = None
+    name = spec.get("name")
+    if "bank" in spec:
+        bank = np.asarray(spec.pop("bank"), dtype=np.float32)
+        if bank.ndim != 4 or bank.shape[-1] != 4:
+            raise ValueError(f"movers: bank must be [K, Pmax, M, 4], got {bank.shape}")
+        periods = spec.pop("periods", None)
+        periods = np.full(bank.shape[0], bank.shape[1], dtype=np.int32) if periods is None else np.asarray(periods, dtype=np.int32)
+        if periods.shape != (bank.shape[0],) or periods.min() < 1 or periods.max() > bank.shape[1]:
+            raise ValueError(f"movers: periods must be {bank.shape[0]} integers in [1, {bank.shape[1]}]")
+        out = MoverBank(bank, periods, spec.pop("rects", None), spec.pop("assign", "random"))
+    elif isinstance(name, str) and name.startswith("random:"):
+        spec.pop("name")
+        try:
+            K = int(name[len("random:"):])
+        except ValueError:
+            K = 0
+        if K < 1:
+            raise ValueError(f"movers: {name!r} is not 'random:K' with K >= 1")
+        out = MoverBank(*random_mover_bank(K, seed=int(spec.pop("seed", 0))), spec.pop("assign", "random"))
+    elif isinstance(name, str) and name.startswith("bank:"):
+        spec.pop("name")
+        scenes = [n for n in name[len("bank:"):].split(",") if n]
+        if not scenes:
+            raise ValueError(f"movers: {name!r} lists no scene; have {sorted(_SCENES)}")
+        P = spec.pop("period", None)
+        out = MoverBank(*mover_bank([movers_by_name(n, P) for n in scenes], [_SCENES[n][1] if _SCENES[n][1] is not None else [] for n in scenes]),
+                        spec.pop("assign", "random"))
+    elif "tape" in spec:
+        out = spec.pop("tape")
     else:
-        tape = movers_by_name(spec.pop("name"), spec.pop("period", None))
+        out = movers_by_name(spec.pop("name"), spec.pop("period", None))
+    if isinstance(out, MoverBank) and isinstance(out.assign, str) and out.assign not in ("random", "cycle"):
+        raise ValueError(f"movers: assign must be 'random', 'cycle' or an array of tape ids, got {out.assign!r}")
     if spec:
         raise ValueError(f"movers: unknown entries {sorted(spec)}")
-    return tape, phase
+    return out, phase
+
+
+def _env_hash(n_envs, map_seed, env_id_base, salt):
+    """the splitmix64 finaliser of (map_seed, global env id) and of nothing else, one uint64 per env"""
+    g = np.arange(int(env_id_base), int(env_id_base) + int(n_envs), dtype=np.uint64)
+    z = g * np.uint64(0x9E3779B97F4A7C15) + np.uint64((int(map_seed) * 0xD1B54A32D192ED03 + salt) & 0xFFFFFFFFFFFFFFFF)
+    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return z ^ (z >> np.uint64(31))
 
 
 def mover_phases(period, n_envs, map_seed=0, env_id_base=0):
     """phase0[i] in [0, period) for envs env_id_base .. env_id_base + n_envs - 1: a hash (the splitmix64 finaliser) of
     (map_seed, global env id) and of nothing else, so every shard of a run draws the phases the single-GPU run draws."""
-    g = np.arange(int(env_id_base), int(env_id_base) + int(n_envs), dtype=np.uint64)
-    z = g * np.uint64(0x9E3779B97F4A7C15) + np.uint64((int(map_seed) * 0xD1B54A32D192ED03 + 0x2545F4914F6CDD1D) & 0xFFFFFFFFFFFFFFFF)
-    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-    z = z ^ (z >> np.uint64(31))
-    return (z % np.uint64(int(period))).astype(np.int32)
+    return (_env_hash(n_envs, map_seed, env_id_base, 0x2545F4914F6CDD1D) % np.uint64(int(period))).astype(np.int32)
+
+
+def mover_tape_ids(K, n_envs, map_seed=0, env_id_base=0):
+    """tape_id[i] in [0, K): mover_phases' counterpart for the tape of a bank, with a constant of its own (so that an env's tape and
+    its phase are independent).  Every shard of a run gives a global env the tape the single-GPU run gives it."""
+    return (_env_hash(n_envs, map_seed, env_id_base, 0x6A09E667F3BCC909) % np.uint64(int(K))).astype(np.int32)
+
+
+def mover_bank_phases(periods_of_env, map_seed=0, env_id_base=0):
+    """phase0[i] in [0, periods_of_env[i]): the hash of mover_phases reduced by each env's own period (K = 1: mover_phases)."""
+    per = np.asarray(periods_of_env).astype(np.uint64).reshape(-1)
+    return (_env_hash(per.size, map_seed, env_id_base, 0x2545F4914F6CDD1D) % per).astype(np.int32)
 
 
 def by_name(name):

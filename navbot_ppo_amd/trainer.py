@@ -370,6 +370,8 @@ class PPOTrainer:
         if n_par < 1:
             raise ValueError("PPOConfig.eval_episodes must be at least 1")
         seed = (int(self.cfg.seed) * 1000003 + 7919) & 0xFFFFFFFF   # its own goal / spawn stream, derived from cfg.seed
+        if self.cfg.eval_movers is not None:   # the held-out set: resolved like VecEnv's movers, given to the evaluation env only
+            w["movers"] = self.cfg.eval_movers
         return VecEnv(n_par, max_episode_steps=self.cfg.max_episode_steps, auto_reset=True, is_training=False, seed=seed,
                       device=self.device, **w)
 
@@ -394,13 +396,23 @@ class PPOTrainer:
         fl = cut(tab.flags)
         sums = torch.stack([(fl & 1).sum().double(), ((fl >> 1) & 1).sum().double(), ((fl >> 2) & 1).sum().double(),
                             cut(tab.length).double().sum(), cut(tab.ret).double().sum(), cut(tab.path).double().sum(),
-                            tab.count.min().double(), tab.steps.max().double()]).cpu().numpy()   # the one host sync
+                            tab.count.min().double(), tab.steps.max().double()])
+        n_tapes = env.sim.movers_tapes if env.sim.movers_tape_id is not None else 0
+        if n_tapes:   # a bank of tapes: episodes and successes per scenario (row r of the table was played by env r mod N)
+            ids = cut(env.sim.movers_tape_id.long().repeat(quota))
+            sums = torch.cat([sums, torch.bincount(ids, minlength=n_tapes).double(),
+                              torch.bincount(ids, weights=(fl & 1).double(), minlength=n_tapes)])
+        sums = sums.cpu().numpy()   # the one host sync
+        per_tape = sums[8:].reshape(2, -1)
         if int(sums[6]) < quota:
             raise RuntimeError("evaluate_now: an env did not finish its quota of episodes")
         sums = [float(v) for v in sums]
         out = dict(eval_episodes=n_ep, eval_success=sums[0] / n_ep, eval_collision=sums[1] / n_ep, eval_timeout=sums[2] / n_ep,
                    eval_length=sums[3] / n_ep, eval_return=sums[4] / n_ep, eval_path_length=sums[5] / n_ep,
                    eval_steps=int(sums[7]), eval_time=time.time() - t0)
+        if n_tapes:
+            rate = per_tape[1][per_tape[0] > 0] / per_tape[0][per_tape[0] > 0]   # (scenarios that played at least one episode)
+            out.update(eval_scenario_success_min=float(rate.min()), eval_scenario_success_mean=float(rate.mean()))
         if cfg.output_dir:
             import csv
             os.makedirs(self.log_dir(), exist_ok=True)
@@ -540,7 +552,9 @@ class PPOTrainer:
                     + (f" bootstrapped_frac={lg['bootstrapped_frac']:.4f}" if "bootstrapped_frac" in lg else "")
                     + (f" eval: succ={lg['eval_success']:.3f} coll={lg['eval_collision']:.3f} tmo={lg['eval_timeout']:.3f} "
                        f"ret={lg['eval_return']:.2f} len={lg['eval_length']:.1f} ({lg['eval_time']:.3f}s)"
-                       if "eval_success" in lg else ""))
+                       if "eval_success" in lg else "")
+                    + (f" scenarios: min={lg['eval_scenario_success_min']:.3f} mean={lg['eval_scenario_success_mean']:.3f}"
+                       if "eval_scenario_success_min" in lg else ""))
         return self.logger
 
     # ---- ppo.py:452-457 file naming; state_dict keys match the reference's nets for policy resmlp512
