@@ -85,6 +85,8 @@ void navsim_destroy(navsim_t* h);
  * shape writes the same rows).  envs_per_workgroup: 0 = the built-in rule (by shard size, beam count, map kind and entry
  * point), or 4 (navsim_rollout_mlp64 only) | 8 | 16 | 32 | 64.  pair_cast: -1 = the rule, 0 = 64-segment passes for every
  * map, 1 = 128-segment passes where the rule allows them.  Takes effect from the next launch.
+ * With movers (navsim_set_movers) a forced shape applies to navsim_rollout_mlp64 ONLY, and only 32 or 64 do: every other stepping
+ * entry point has the mover form in the 16-env shape alone and keeps it (step_epb / seq_epb stay 16 envs on 8 waves).
  */
 int navsim_set_shape(navsim_t* h, int32_t envs_per_workgroup, int32_t pair_cast);
 
@@ -94,7 +96,9 @@ int navsim_set_shape(navsim_t* h, int32_t envs_per_workgroup, int32_t pair_cast)
  * 1 = 128-segment passes, 2 = 128-segment passes with non-temporal loads, 3 = tile bounding boxes.
  * rollout_kind: 0 = navsim_rollout_mlp64 unavailable for this handle, 1 = rollout_kernel (rollout_epb = 4 | 8 | 16 envs on 8
  * waves), 2 = rollout_big_kernel (rollout_epb = 64 envs on 16 waves, or 32 envs on 8 waves: tile-box maps on 4097..8192 envs and
- * the forced 32-env shape).  forced_epb / forced_pair_cast: what navsim_set_shape was last given (0 / -1 = the rule).
+ * the forced 32-env shape).  With movers: 1 = rollout_mov_kernel (16 envs on 8 waves), 2 = rollout_big_mov_kernel (the same shapes
+ * under the same rule as without movers, rollout_cast 0 or 3) -- while step_* / seq_* keep reporting 16 envs on 8 waves.
+ * forced_epb / forced_pair_cast: what navsim_set_shape was last given (0 / -1 = the rule).
  */
 typedef struct navsim_info {
     int32_t abi_version, n_envs, n_beams, obs_f16;
@@ -137,8 +141,10 @@ int navsim_set_map(navsim_t* h, const float* seg_dev, int32_t n_segments, int32_
  *   model back at its start.  navsim_raycast sees tape[(k + phase0[i]) mod period], the phase the env last observed.
  * Everything behind the scan -- collision rule, observation row, reward, episode logic -- is unchanged: a mover that reaches the robot
  * ends the episode as a wall does.  The scan equals, bit for bit, that of a static map holding the static segments and the phase's.
- * With a tape every stepping entry point (navsim_step, navsim_step_seq, both rollouts, both evaluations) runs 16 envs on 8 waves per
- * workgroup at every shard size (navsim_set_shape has no effect; navsim_get_info reports it).
+ * With a tape navsim_step, navsim_step_seq, navsim_rollout_resmlp512 and both evaluations run 16 envs on 8 waves per workgroup at
+ * every shard size (navsim_set_shape has no effect on them).  navsim_rollout_mlp64 runs that shape up to 4096 envs and, as without
+ * movers, 64 envs on 16 waves beyond (32 on 8 for tile-box maps up to 8192 envs), or the 32- / 64-env shape navsim_set_shape forces;
+ * navsim_get_info reports the choice.  Every shape writes the same rows.
  * Like the map, the tape is part of the kernel arguments: set it BEFORE a step is captured into a graph.
  * Re-casts the spawn scans on `stream` (with phase0 they become per-env); a later navsim_set_map keeps the tape and does the same.
  * Synchronises `stream`.

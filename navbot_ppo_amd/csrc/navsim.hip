@@ -501,7 +501,9 @@ __device__ __forceinline__ float write_lidar(float* row, const float* best, int 
 // range are skipped without being loaded (the house map: 32 tiles, ~5 of them near any one pose).
 // MOV: moving obstacles (Params::mov_tape, navsim_set_movers): the pose lanes publish each env's tape phase before barrier A and
 // the ray waves cast that phase's segments (lane = segment) through the same stage-A queue, behind their static tiles.  `sm` is then
-// the base of a StepSmemMov.  Off, nothing of it is compiled: every instantiation without it is what it was.
+// the base of a StepSmemMov.  Off, nothing of it is compiled: every instantiation without it is what it was.  The 16-env shape holds
+// its three mover passes in registers of their own from barrier A on; the 32- / 64-env shapes (six passes, a kernel at its
+// 128 registers) feed them through the three request slots of the static tiles instead (kMovRot, in the cast).
 // row0: element offset of this step's row in the [T, N] output buffers `io` points at (navsim_step_seq: t N; the pointers are
 // then read from the kernarg segment at their use instead of living in SGPRs through the body; 0 elsewhere).
 // PRef / IORef: how the parameter block and the I/O pointers are reached.  The persistent rollout passes plain references to its
@@ -541,7 +543,10 @@ __device__ __forceinline__ void step_body(PRef P, StepSmem<NB, EPB, NW>& sm, int
                                           const size_t row0 = 0, Hook hook = Hook()) {
     static_assert(EPB <= 64 && EPB >= 4 && NB % 2 == 0, "EPB / NB");
     static_assert(!(PAIR && BOXES), "tile boxes describe 64-segment tiles");
-    static_assert(!MOV || (NB == 10 && EPB == 16 && NW == 8 && PAIR == 0), "movers: the 16-env, 8-wave shape with 10 beams");
+    static_assert(!MOV || (NB == 10 && PAIR == 0 && ((EPB == 16 && NW == 8) || (EPB == 32 && NW == 8) || (EPB == 64 && NW == 16))),
+                  "movers: 10 beams without the 128-segment passes, on 16 or 32 envs and 8 waves or on 64 envs and 16 waves");
+    // movers in the big shapes (32 / 64 envs): the mover passes go through the three request slots of the static tiles (see the cast)
+    constexpr bool kMovRot = MOV && EPB > 16;
     constexpr int kThreads = 64 * NW;
     constexpr bool kEval = std::is_same<typename std::remove_cv<typename std::remove_reference<IORef>::type>::type, EvalIO>::value;
     static_assert(!kEval || PERSIST, "the episode table is the persistent evaluation kernels' output");
@@ -1256,11 +1261,13 @@ __device__ __forceinline__ void step_body(PRef P, StepSmem<NB, EPB, NW>& sm, int
         // tiles.  The requests are unconditional and EVERY wave issues them (a front wave's, and a pass past the last env, re-read a
         // clamped valid address and are never consumed): the count of requests behind the three static slots is then the same on
         // every path into the loop below, which is what lets its waits name the oldest slot only.
-        constexpr int kMovRW = NW - PW, kMovPasses = MOV ? (EPB + kMovRW - 1) / kMovRW : 1;
+        // (The 16-env shape: three passes.  The big shapes would hold six tiles here, beside the three static slots, in a kernel
+        // that sits at its 128 registers: they take the rotation below instead.)
+        constexpr int kMovRW = NW - PW, kMovPasses = (MOV && !kMovRot) ? (EPB + kMovRW - 1) / kMovRW : 1;
         [[maybe_unused]] float4 mg[kMovPasses];
         [[maybe_unused]] int m_el[kMovPasses];
         [[maybe_unused]] bool m_v[kMovPasses];
-        if constexpr (MOV) {
+        if constexpr (MOV && !kMovRot) {
             const StepSmemMov<NB, EPB, NW>& ms = static_cast<const StepSmemMov<NB, EPB, NW>&>(sm);
             const int mspl = P.mov_pack_log2, M = P.mov_M;
             const int mepp = 64 >> mspl, msub = lane >> mspl, mj = lane & ((1 << mspl) - 1);
@@ -1273,25 +1280,105 @@ __device__ __forceinline__ void step_body(PRef P, StepSmem<NB, EPB, NW>& sm, int
                 mg[q] = tape[(size_t)ms.mv_phase[m_el[q]] * (size_t)M + (size_t)min(mj, M - 1)];
             }
         }
+        // MOV in the big shapes (kMovRot): the mover passes are further positions of the SAME three-slot rotation.  Position
+        // n_items + q of ray wave r is its q-th mover pass (envs (r + RW q) mepp ..: the static assignment of the 16-env shape), and
+        // the wave's stream runs on behind its last static tile up to n_end = n_items + its number of passes that hold an env.  A slot
+        // whose static stream has ended requests a mover pass where it used to re-read a clamped address, so the tape segments are in
+        // flight under the last static tiles, no register holds a tile beside the three slots, and every turn of a slot still issues
+        // exactly ONE request on every path (ld or ld_mov, by a wave-uniform test): the count of requests behind any given one stays
+        // the same on every path, i.e. the waits of the loop still name the oldest slot only.  The phases are published at barrier A:
+        // a position the ray waves pre-assigned past the last item before it (never requested as a mover pass there) is re-requested
+        // here, in slot order, so the three slots are again requested oldest first on every path into the loop.
+        [[maybe_unused]] int n_end_m = n_items, mv_spl = 6, mv_M = 1;
+        [[maybe_unused]] const float4* mv_tape = nullptr;
+        if constexpr (kMovRot) {
+            mv_spl = P.mov_pack_log2;
+            mv_M = P.mov_M;
+            mv_tape = P.mov_tape;
+            const int n_mit = (nloc + (64 >> mv_spl) - 1) >> (6 - mv_spl);   // mover passes of the workgroup
+            if (wave >= PW && n_mit > wave - PW) n_end_m = n_items + (n_mit - (wave - PW) + kMovRW - 1) / kMovRW;
+        }
+        const int n_end = kMovRot ? n_end_m : n_items;
+        // lane -> (env, segment) of mover pass q = p.it - n_items of this wave; the env clamped to a present one
+        auto mov_el = [&](const Pos p, bool& present) __attribute__((always_inline)) -> int {
+            const int el = ((wave - PW) + kMovRW * (p.it - n_items)) * (64 >> mv_spl) + (lane >> mv_spl);
+            present = (p.it < n_end) && (el < nloc);
+            return min(max(el, 0), nloc - 1);
+        };
+        auto ld_mov = [&](const Pos p, float4& g, bool& v) __attribute__((always_inline)) {
+            const int mj = lane & ((1 << mv_spl) - 1);
+            bool present;
+            const int el = mov_el(p, present);
+            v = present && (mj < mv_M);
+            g = mv_tape[(size_t)static_cast<const StepSmemMov<NB, EPB, NW>&>(sm).mv_phase[el] * (size_t)mv_M + (size_t)min(mj, mv_M - 1)];
+        };
+        auto request_m = [&](const Pos p, float4& ga, bool& va, float4& gb, bool& vb) __attribute__((always_inline)) {
+            if constexpr (kMovRot) {
+                if (p.it >= n_items) ld_mov(p, ga, va);
+                else request(p, ga, va, gb, vb);
+            } else {
+                request(p, ga, va, gb, vb);
+            }
+        };
+        // the cull of a mover pass: that of a static tile, plus: a segment with a NaN coordinate (the documented padding of a phase)
+        // is dropped here instead of failing every exact test
+        auto consume_m = [&](const Pos p, const float4 ga, const bool va, const float4 gb, const bool vb) __attribute__((always_inline)) {
+            if constexpr (kMovRot) {
+                if (p.it >= n_items) {
+                    bool present;
+                    const int el = mov_el(p, present);
+                    const float2 o = sm.org[el], h = sm.hd[el];
+                    const float sum = (ga.x + ga.y) + (ga.z + ga.w);
+                    push(ga, (unsigned)el, keep_of(ga, o, h) & va & (sum == sum));
+                    return;
+                }
+            }
+            consume(p, ga, va, gb, vb);
+        };
+        auto advance_m = [&](const Pos p) __attribute__((always_inline)) -> Pos {
+            if constexpr (kMovRot) {
+                if (p.it >= n_items) return Pos{p.it + 1, 0};   // the wave's next mover pass (from n_end on: the end)
+                const Pos r = advance(p);
+                return (r.it >= n_items) ? Pos{n_items, 0} : r;   // behind the last static tile: mover pass 0
+            } else {
+                return advance(p);
+            }
+        };
+        if constexpr (kMovRot) {
+            if (wave >= PW) {
+                if (p0.it >= n_items) {
+                    p0 = Pos{n_items, 0};
+                    ld_mov(p0, g0, v0);
+                }
+                if (p1.it >= n_items) {
+                    p1 = Pos{max(p0.it, n_items - 1) + 1, 0};
+                    ld_mov(p1, g1, v1);
+                }
+                if (p2.it >= n_items) {
+                    p2 = Pos{max(p1.it, n_items - 1) + 1, 0};
+                    ld_mov(p2, g2, v2);
+                }
+            }
+        }
         // three tiles in flight; the slots take turns (a register rotation would have to wait for the load it moves)
         for (;;) {   // wave-uniform
-            if (p0.it >= n_items) break;
-            consume(p0, g0, v0, g0b, v0b);
-            p0 = advance(p2);
-            request(p0, g0, v0, g0b, v0b);
-            if (p1.it >= n_items) break;
-            consume(p1, g1, v1, g1b, v1b);
-            p1 = advance(p0);
-            request(p1, g1, v1, g1b, v1b);
-            if (p2.it >= n_items) break;
-            consume(p2, g2, v2, g2b, v2b);
-            p2 = advance(p1);
-            request(p2, g2, v2, g2b, v2b);
+            if (p0.it >= n_end) break;
+            consume_m(p0, g0, v0, g0b, v0b);
+            p0 = advance_m(p2);
+            request_m(p0, g0, v0, g0b, v0b);
+            if (p1.it >= n_end) break;
+            consume_m(p1, g1, v1, g1b, v1b);
+            p1 = advance_m(p0);
+            request_m(p1, g1, v1, g1b, v1b);
+            if (p2.it >= n_end) break;
+            consume_m(p2, g2, v2, g2b, v2b);
+            p2 = advance_m(p1);
+            request_m(p2, g2, v2, g2b, v2b);
         }
         // MOV: the mover passes join the stage-A queue like any tile: the same cull (plus: a segment with a NaN coordinate -- the
         // documented padding of a phase -- is dropped here instead of failing every exact test), the same queues, the same exact
         // tests and atomic-min -- so the scan is that of a static map holding the static segments and this phase's tape segments
-        if constexpr (MOV) {
+        if constexpr (MOV && !kMovRot) {
 #pragma unroll
             for (int q = 0; q < kMovPasses; ++q) {
                 if (!__any(m_v[q])) continue;   // wave-uniform: a front wave, a pass past the last env
@@ -1536,7 +1623,8 @@ __global__ __launch_bounds__(64 * NW, min_waves_per_simd(NB, EPB, NW, PAIR, fals
 template <int NB, int EPB, int NW, bool MOV>
 using StepSmemFor = typename std::conditional<MOV, StepSmemMov<NB, EPB, NW>, StepSmem<NB, EPB, NW>>::type;
 
-// Movers (navsim_set_movers): every entry point takes the 16-env, 8-wave shape with 10 beams.  The MOV kernels are twins of their
+// Movers (navsim_set_movers): every entry point takes the 16-env, 8-wave shape with 10 beams; navsim_rollout_mlp64 alone also has
+// the big shapes (rollout_big_mov_kernel below).  The MOV kernels are twins of their
 // own name (`*_mov_kernel`), so that the kernels a handle without a tape launches keep their symbols and their code.
 // No second launch bound (min_waves_per_simd): the mover passes hold three more tiles in registers.
 // They are the SENS instantiations for every handle -- with the range noise off and below_min at its default those compute the
@@ -2207,15 +2295,19 @@ typedef const BigKArgs __attribute__((address_space(4))) * BigKArgsPtr;
 
 static_assert(std::is_trivially_copyable<BigKArgs>::value && offsetof(BigKArgs, P) == 0, "kernarg mirror of rollout_big_kernel");
 
-template <int EPB, bool SENS, int NW, bool BOXES = false, int PAIR = 0>
-__global__ __launch_bounds__(64 * NW) void rollout_big_kernel(BigKArgs) {   // the segment IS the struct (see step_kernel)
+// (rollout_big_kernel and its twin with movers, rollout_big_mov_kernel, share this body.  Unlike the other twins' bodies it declares
+// the LDS variables itself -- one set per instantiation, i.e. per kernel, as each is inlined into exactly one: these kernels sit
+// at their 128 registers, and with the variables handed in as references three SENS instantiations WITHOUT movers changed their
+// scratch; see profiles/movers_big_kernel_resources.txt.)
+template <int EPB, bool SENS, int NW, bool BOXES, int PAIR, bool MOV>
+__device__ __forceinline__ void rollout_big_body() {
     constexpr int NB = 10, D = NB + 6, DP = D + 1, kThreads = 64 * NW;
     constexpr int TW = EPB / 16;   // policy tiles = MFMA waves of the policy phase
     using PL = mlp64::Layout<D>;
     constexpr int KS = PL::KS;
     static_assert(D == mlp64::IN, "64-env workgroups: the 10-beam tile (36 beams do not fit the LDS)");
     static_assert(EPB % 16 == 0 && EPB <= 64 && TW < NW, "policy phase: EPB / 16 tile waves + the noise wave");
-    __shared__ StepSmem<NB, EPB, NW> sm;
+    __shared__ StepSmemFor<NB, EPB, NW, MOV> sm;   // (movers: 16 bytes per env more, 153,352 bytes at 64 envs)
     __shared__ int next_env;
     __shared__ __attribute__((aligned(16))) float wts[mlp64::P_ACTOR + 2];   // the actor, staged once for all T steps
     __shared__ float2 pol_eps[2][EPB];   // action noise of this step and of the next one
@@ -2236,6 +2328,7 @@ __global__ __launch_bounds__(64 * NW) void rollout_big_kernel(BigKArgs) {   // t
     const bool half_rows = P.obs_f16 != 0;   // float16 observation buffers: the policy reads what a reader of the buffers would
     load_obs_tile<NB, EPB, NW>(sm, R.obs_buf, base, nloc, half_rows);
     load_tables<NB, EPB, NW, PRef>(P, sm);
+    if constexpr (MOV) load_mover_phase0<NB, EPB, NW, PRef>(P, sm, base, nloc);
     const uint32_t step0 = R.step_base ? *R.step_base : 0u;
     const float var = *R.var_ptr;
     const uint64_t seed = R.seed, gid = P.env_id_base + (uint64_t)(base + lane);
@@ -2281,7 +2374,15 @@ __global__ __launch_bounds__(64 * NW) void rollout_big_kernel(BigKArgs) {   // t
     };
     auto draw_noise = [&](const int t) __attribute__((always_inline)) {   // the noise of rollout row t: rows take turns in two LDS rows
         float e0, e1;
-        mlp64::policy_noise(step0 + (uint32_t)t, seed, gid, e0, e1);
+        if constexpr (MOV) {
+            // the global env id is worked out HERE, from a lane index the compiler cannot follow out of the step loop: held in a
+            // register pair across the steps it was the one value the 64-env twin with tile boxes spilled (12 bytes of scratch)
+            int ln = lane;
+            asm volatile("" : "+v"(ln));
+            mlp64::policy_noise(step0 + (uint32_t)t, seed, P.env_id_base + (uint64_t)(base + ln), e0, e1);
+        } else {
+            mlp64::policy_noise(step0 + (uint32_t)t, seed, gid, e0, e1);
+        }
         pol_eps[t & 1][lane] = make_float2(e0, e1);
     };
     if (wave == kNoiseWave && lane < nloc) {
@@ -2309,10 +2410,22 @@ __global__ __launch_bounds__(64 * NW) void rollout_big_kernel(BigKArgs) {   // t
                 else if (wv == kNoiseWave && ln < nloc && t + 2 < T) draw_noise(t + 2);   // row (t + 2) & 1: not the one being read
             }
         };
-        step_body<NB, EPB, SENS, true, NW, BOXES, PAIR, PRef, const StepIO __attribute__((address_space(4)))&, decltype(hook)>(
+        step_body<NB, EPB, SENS, true, NW, BOXES, PAIR, PRef, const StepIO __attribute__((address_space(4)))&, decltype(hook), MOV>(
             P, sm, next_env, A->io, t == T - 1, tn, hook);
         // the observation tile of step t + 1 is in sm.obs (its store only reads it) and its action in sm.act_l
     }
+}
+template <int EPB, bool SENS, int NW, bool BOXES = false, int PAIR = 0>
+__global__ __launch_bounds__(64 * NW) void rollout_big_kernel(BigKArgs) {   // the segment IS the struct (see step_kernel)
+    rollout_big_body<EPB, SENS, NW, BOXES, PAIR, false>();
+}
+// Movers in the big shapes (navsim_rollout_mlp64 only: pick_rollout): 64 envs on 16 waves or 32 on 8, with the 64-segment passes or
+// the tile boxes (movers need a shared static map, so the 128-segment passes never meet a tape).  SENS is a parameter here, unlike
+// in the 16-env twins: the 64-env workgroup sits at its 128 registers, and a handle without the sensor options should not carry
+// them there (registers, scratch and LDS of the eight twins beside their siblings: profiles/movers_big_kernel_resources.txt).
+template <int EPB, bool SENS, int NW, bool BOXES>
+__global__ __launch_bounds__(64 * NW) void rollout_big_mov_kernel(BigKArgs) {
+    rollout_big_body<EPB, SENS, NW, BOXES, 0, true>();
 }
 
 // Env.getOdometry (environment_new.py:138-181) for n independent (position, orientation quaternion, goal) triples
@@ -2799,17 +2912,21 @@ static RolloutPick pick_rollout(const navsim* h) {
     if (h->P.B != 10 && h->P.B != 36) return rp;
     const bool boxes = h->P.tile_box != nullptr;
     const bool pair = h->pair_cast && !boxes && h->P.S > 64 && h->P.seg_pack_log2 == 6;
-    if (h->P.mov_tape) return RolloutPick{1, 16, 8, boxes ? 3 : 0};   // movers: rollout_mov_kernel at every shard size (in rounds beyond 4096 envs)
+    // movers: rollout_big_mov_kernel under the same rule (the tape needs a shared map: cast 0 or 3), else rollout_mov_kernel.
+    // Measured (profiles/movers_big_rollout.txt; orbit_movers M = 32, 512 steps, ms per rollout, the 16-env twin / the big twin):
+    // stage_1 8192 envs 6.66 / 5.25, 16384 envs 13.29 / 5.30; the 2048-segment house map (tile boxes, 32 envs on 8 waves) 8192 envs
+    // 17.36 / 14.95 -- each far outside the spread of the blocks (0.01-0.06 ms), so the rule is the one without movers.
     if (h->P.B == 10 && (h->force_epb == 64 || h->force_epb == 32 || (h->force_epb == 0 && h->P.N > 16 * 256))) {
         rp.kind = 2; rp.epb = 64; rp.waves = 16;
         // tile-box maps (the 2048-segment house map: a vector-issue-bound cast) on 4097..8192 envs: 64-env workgroups would leave half
         // the CUs empty (8192 envs: 35.4 us per step) -- 32 envs on 8 waves, one workgroup on every CU
         if (h->force_epb == 32 || (h->force_epb == 0 && boxes && h->P.N <= 32 * 256)) rp.epb = 32, rp.waves = 8;
         rp.cast = boxes ? 3 : (pair ? ((h->P.per_env & 2) ? 2 : 1) : 0);   // 2: one step's per-env stream exceeds 1.25 x the Infinity Cache
-        if (rp.epb == 32 && rp.cast != 3) rp.cast = 0;   // (the forced 32-env shape exists with 64-segment passes and with tile boxes)
+        if ((rp.epb == 32 || h->P.mov_tape) && rp.cast != 3) rp.cast = 0;   // (the forced 32-env shape, and every shape with movers, exists with 64-segment passes and with tile boxes)
         return rp;
     }
     rp.kind = 1; rp.waves = 8;
+    if (h->P.mov_tape) return RolloutPick{1, 16, 8, boxes ? 3 : 0};   // (movers: the 16-env shape is the only small one with the MOV form)
     rp.epb = (h->P.B == 10 && !boxes && (h->force_epb == 4 || h->force_epb == 8)) ? h->force_epb : 16;
     rp.cast = boxes ? 3 : 0;   // (round 5: the 16-env shape has the tile-box cast too -- the house map on shards up to 4096 envs)
     return rp;
@@ -2911,7 +3028,9 @@ static int init_handle(navsim* h, const navsim_cfg* cfg) {
     return NAVSIM_OK;
 }
 
-// what navsim_set_movers (and a navsim_set_map behind it) refuses; the same sentence stands in include/navsim.h
+// what navsim_set_movers (and a navsim_set_map behind it) refuses; the same sentence stands in include/navsim.h.  (What IS built
+// beside the 16-env twins: the big shapes of navsim_rollout_mlp64, rollout_big_mov_kernel; every other stepping entry point keeps 16
+// envs on 8 waves whatever navsim_set_shape says.)
 static const char* const kMoversNotBuilt =
     "movers need 10 beams and a shared static map: movers with 36 beams or with a per-env static map are not built";
 
@@ -3340,7 +3459,12 @@ int navsim_rollout_mlp64(navsim_t* h, const float* actor_params_dev, void* obs_b
         const BigKArgs ka = {h->P, R, rollout_io(R, (size_t)h->P.N, (size_t)h->P.B + 6, 0, h->P.obs_f16 != 0)};
         auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, st, ka); };
         with_flag(sens_on(h), [&](auto S) {
-            if (rp.epb == 32) {   // (tile boxes; forced: any map without the 128-segment passes)
+            if (h->P.mov_tape) {   // (a shared map: cast 0 or 3)
+                with_flag(rp.cast == 3, [&](auto BX) {
+                    if (rp.epb == 32) go(rollout_big_mov_kernel<32, S, 8, BX>);
+                    else go(rollout_big_mov_kernel<64, S, 16, BX>);
+                });
+            } else if (rp.epb == 32) {   // (tile boxes; forced: any map without the 128-segment passes)
                 if (rp.cast == 3) go(rollout_big_kernel<32, S, 8, true, 0>);
                 else go(rollout_big_kernel<32, S, 8, false, 0>);
             } else if (rp.cast == 3) go(rollout_big_kernel<64, S, 16, true, 0>);

@@ -615,6 +615,30 @@ class _Pose:
         self.position = _XY()
 
 
+def resolve_env_movers(movers):
+    """Env's ``movers`` argument -> (tape [P, M, 4] float32, phase offset in [0, P)): a name of maps.movers_by_name ("orbit4"), a tape
+    [P, M, 4], or a dict tape=... | name=... (+ period=...) with phase=int (default 0: the one env's scans start at the tape's row 0
+    after every reset, unlike VecEnv's hashed per-env offsets)."""
+    spec = dict(movers) if isinstance(movers, dict) else ({"name": movers} if isinstance(movers, str) else {"tape": movers})
+    phase = spec.pop("phase", 0)
+    period = spec.pop("period", None)
+    if sum(k in spec for k in ("tape", "name")) != 1 or len(spec) != 1:
+        raise ValueError("movers: give a tape or a name (and, in a dict, period=... with a name, phase=int)")
+    if "name" in spec:
+        tape = _maps.movers_by_name(spec["name"], period)
+    elif period is not None:
+        raise ValueError("movers: period goes with a name (a tape has its own)")
+    else:
+        tape = spec["tape"]
+    tape = tape.detach().cpu().numpy() if torch.is_tensor(tape) else np.asarray(tape)
+    tape = np.ascontiguousarray(tape, dtype=np.float32)
+    if tape.ndim != 3 or tape.shape[2] != 4 or tape.shape[0] < 1:
+        raise ValueError(f"movers: a tape is [P, M, 4], got {tape.shape}")
+    if isinstance(phase, (bool, str)) or not isinstance(phase, (int, np.integer)) or not 0 <= int(phase) < tape.shape[0]:
+        raise ValueError(f"movers: phase must be an integer in [0, {tape.shape[0]}), got {phase!r}")
+    return tape, int(phase)
+
+
 class Env:
     """Single-env drop-in for the reference ``Env`` (environment_new.py:26-382).
 
@@ -629,7 +653,10 @@ class Env:
     resets, and on arrival it re-spawns the goal like ``setReward`` does (environment_new.py:245-267).
     """
 
-    def __init__(self, is_training, use_vision=False, vision_dim=64, map="stage_1", seed=0, device=None):
+    def __init__(self, is_training, use_vision=False, vision_dim=64, map="stage_1", seed=0, device=None, movers=None):
+        """movers: moving obstacles (an extension, NavSim.set_movers; resolve_env_movers: a scene name, a tape [P, M, 4] or
+        dict(tape=... | name=..., phase=int)).  The scan of a step sees tape[(k + 1 + phase) mod P], k = the steps taken since the last
+        reset(); the reset observation sees tape[phase].  None: the static world, exactly as without the keyword."""
         if use_vision:
             raise NotImplementedError("camera modality is outside the LiDAR hot path (SURVEY.md 2a)")
         self.use_vision = False
@@ -645,6 +672,10 @@ class Env:
         else:
             seg = map
         self._sim.set_map(seg)
+        self.movers_phase0 = 0
+        if movers is not None:
+            tape, self.movers_phase0 = resolve_env_movers(movers)
+            self._sim.set_movers(tape, np.full(1, self.movers_phase0, np.int32) if self.movers_phase0 else None)
         # One pinned (host-mapped, device-visible) block carries a step's inputs and outputs: the kernel reads the action pair
         # from it and stores observation, reward and flags into it, so a step is one launch + a poll of the block (_wait_results), no copies.
         self._pin = torch.zeros(48, dtype=torch.float32).pin_memory()
@@ -696,6 +727,12 @@ class Env:
     @property
     def past_distance(self):
         return float(self._st()["past_dist"][0])
+
+    @property
+    def mover_phase(self):
+        """the tape row the NEXT step's scan sees, (k + 1 + phase) mod P with k the steps since the last reset (None without movers)"""
+        P = self._sim.movers_period
+        return (int(self._st()["ep_step"][0]) + 1 + self.movers_phase0) % P if P else None
 
     def _wait(self):
         self._stream_obj.synchronize()
