@@ -99,6 +99,8 @@ int navsim_set_shape(navsim_t* h, int32_t envs_per_workgroup, int32_t pair_cast)
  * the forced 32-env shape).  With movers: 1 = rollout_mov_kernel (16 envs on 8 waves), 2 = rollout_big_mov_kernel (the same shapes
  * under the same rule as without movers, rollout_cast 0 or 3) -- while step_* / seq_* keep reporting 16 envs on 8 waves.
  * forced_epb / forced_pair_cast: what navsim_set_shape was last given (0 / -1 = the rule).
+ * The scan-history entry points (navsim_rollout_mlp64_hist, navsim_evaluate_mlp64_hist) always take 16 envs on 8 waves, in rounds of
+ * workgroups beyond 4096 envs: a forced 32 / 64 shape does not apply to them and rollout_* does not describe them.
  */
 typedef struct navsim_info {
     int32_t abi_version, n_envs, n_beams, obs_f16;
@@ -393,6 +395,56 @@ int navsim_evaluate_mlp64(navsim_t* h, const float* actor_params_dev, const void
 int navsim_evaluate_resmlp512(navsim_t* h, const float* actor_params_dev, const void* obs0_dev, int32_t quota, int32_t n_steps,
                               uint8_t* ep_flags_dev, int32_t* ep_length_dev, float* ep_return_dev, float* ep_path_dev,
                               int32_t* count_dev, int32_t* steps_dev, void* stream);
+
+/*
+ * SCAN HISTORY -- an EXTENSION: the policy sees the last three 10-beam scans instead of one.  A HISTORY ROW has 42 columns, every
+ * one a copy of a value of the last three ordinary 16-column rows (row_t = what navsim_step / navsim_reset write: 10 beams / 3.5,
+ * past_action (2), 4 goal columns):
+ *     0..15   row_t[0:16]       the ordinary row, unchanged
+ *     16..25  row_{t-1}[0:10]   the previous scan
+ *     26..35  row_{t-2}[0:10]
+ *     36..37  row_{t-1}[10:12]  the action between the two older scans (ego motion against obstacle motion)
+ *     38..41  0
+ * The episode cut: with r(t) the latest row index s <= t such that s == 0 or ended[s-1] != 0, row_{t-j} means
+ * row_{max(t-j, r(t))}.  On an episode's first row all three frames are that row's scan and columns 36..37 its past_action (zeros
+ * after a reset); a zero-filled frame would read as "obstacle at distance 0" in this normalisation.  Row 0 of a buffer always counts
+ * as an episode start: a caller that continues episodes across launches loses two frames at the seam.  With float16 rows every
+ * copy is a copy of the half value.  Nothing is recomputed, so everything below is exact.
+ *
+ * navsim_stack_rows builds the history rows of a whole buffer; it takes no handle.
+ *   obs_dev   [R, N, 16] f32 (f16 if obs_f16 != 0)   rows as navsim_rollout_mlp64's obs_buf_dev holds them
+ *   ended_dev [R - 1, N] u8   ended_dev[t] is the flag of the step between rows t and t + 1; NULL allowed when R == 1
+ *   out_dev   [R, N, 42]      the type of obs_dev
+ * Called on the three-row window t-2..t of a stepping loop (R = 3; shorter at the start) its LAST output row is the history row of
+ * row t, whatever lies in front of the window: the rule never looks further back than two rows.
+ * NAVSIM_E_ARG: R < 1, N < 1, a null obs_dev / out_dev, a null ended_dev with R > 1, obs_dev or out_dev not 16-byte aligned.
+ */
+int navsim_stack_rows(const void* obs_dev, int32_t obs_f16, const uint8_t* ended_dev, int32_t R, int32_t N, void* out_dev,
+                      void* stream);
+
+/*
+ * navsim_rollout_mlp64 with the 42-64-64 actor (NAVPPO_MLP64_ACTOR_PARAMS_D(42) = 7042 parameters) reading the history row of
+ * every step, assembled on chip: the two older scans and the older action pair of a workgroup's envs stay in LDS.  The argument
+ * list and every buffer are navsim_rollout_mlp64's: obs_buf_dev stays [n_steps + 1, N, 16] -- the env side is bit-identical to the
+ * 16-column rollout's for the same actions, navsim_step_seq replays it -- and row 0 counts as an episode start.  The results are
+ * bit-identical to n_steps rounds of navsim_stack_rows (on the last three rows) / navppo_mlp64_act (obs_dim = 42) / navsim_step.
+ * Needs n_beams == 10 (NAVSIM_E_ARG otherwise).  Always 16 envs on 8 waves per workgroup, in rounds of workgroups beyond 4096 envs:
+ * navsim_set_shape has no effect, and the rollout_* fields of navsim_get_info describe navsim_rollout_mlp64, not this entry point.
+ * Both cast variants of that shape, the sensor-fidelity options, float16 rows, a tape or a bank of tapes are covered.
+ */
+int navsim_rollout_mlp64_hist(navsim_t* h, const float* actor_params_dev, void* obs_buf_dev, float* act_buf_dev,
+                              float* logp_buf_dev, float* reward_dev, uint8_t* done_dev, uint8_t* arrive_dev, uint8_t* ended_dev,
+                              float* ep_return_dev, int32_t* ep_length_dev, float* ep_path_dev, const float* var_dev,
+                              uint64_t act_seed, const uint32_t* step_base_dev, int32_t n_steps, void* stream);
+
+/*
+ * navsim_evaluate_mlp64 with the 42-64-64 actor on history rows, as navsim_rollout_mlp64_hist: obs0_dev stays [N, 16] and counts as
+ * every env's episode start.  Arguments, outputs and errors as for navsim_evaluate_mlp64, except that n_beams must be 10; every
+ * record is bit-identical to a loop of navsim_stack_rows / navppo_mlp64_act (obs_dim = 42, noise_dev = zeros) / navsim_step calls.
+ */
+int navsim_evaluate_mlp64_hist(navsim_t* h, const float* actor_params_dev, const void* obs0_dev, int32_t quota, int32_t n_steps,
+                               uint8_t* ep_flags_dev, int32_t* ep_length_dev, float* ep_return_dev, float* ep_path_dev,
+                               int32_t* count_dev, int32_t* steps_dev, void* stream);
 
 /*
  * n_steps calls of navsim_step with the actions of a tape, in ONE launch: the step loop of PPO.rollout (ppo.py:505-594) or of the

@@ -75,6 +75,10 @@ SYMBOLS = [
     ("navsim_step_seq", C.c_int, [_vp, _vp, _i32] + [_vp] * 9),
     ("navsim_evaluate_mlp64", C.c_int, [_vp, _vp, _vp, _i32, _i32] + [_vp] * 7),
     ("navsim_evaluate_resmlp512", C.c_int, [_vp, _vp, _vp, _i32, _i32] + [_vp] * 7),
+    # scan history: the 42-column rows of the last three 10-beam scans
+    ("navsim_stack_rows", C.c_int, [_vp, _i32, _vp, _i32, _i32, _vp, _vp]),
+    ("navsim_rollout_mlp64_hist", C.c_int, [_vp] * 13 + [C.c_uint64, _vp, _i32, _vp]),
+    ("navsim_evaluate_mlp64_hist", C.c_int, [_vp, _vp, _vp, _i32, _i32] + [_vp] * 7),
     # include/navppo.h
     ("navppo_last_error", C.c_char_p, []),
     ("navppo_mlp64_workspace_bytes", C.c_size_t, [_i32]),

@@ -91,12 +91,29 @@ class PPOConfig:
     # ``movers`` and given to the evaluation env only -- a held-out set of scenarios; with a bank of tapes the eval_* entries gain
     # eval_scenario_success_min / eval_scenario_success_mean
     eval_movers: object = None
+    # False: the policy reads one 16-column row per step.  True (policy "mlp64x2", 10 beams, the persistent rollout and the fused
+    # update, on the GPU): actor and critic are the 42-64-64 nets on SCAN-HISTORY rows -- the row, the scans of the two rows before
+    # it and the action between them, never reaching across an episode's first row (env.stack_rows_reference).  The rollout assembles
+    # the rows on chip (navsim_rollout_mlp64_hist); the update's batch comes from navsim_stack_rows, once per iteration.
+    scan_history: bool = False
 
     def __post_init__(self):
         check_minibatch_config(self)
         check_reward_norm_config(self)
         check_lr_schedule_config(self)
         check_bootstrap_config(self)
+        check_scan_history_config(self)
+
+
+def check_scan_history_config(cfg):
+    """PPOConfig.scan_history, at the construction of the config and again of the trainer (a config is mutable)."""
+    if not isinstance(cfg.scan_history, bool):
+        raise ValueError(f"scan_history {cfg.scan_history!r}: True or False")
+    if cfg.scan_history and cfg.policy == "resmlp512":
+        raise ValueError("scan_history with policy='resmlp512': its kernels read 16-column rows only; use policy='mlp64x2'")
+    if cfg.scan_history and not (cfg.persistent_rollout and cfg.fused_update):
+        raise ValueError("scan_history needs persistent_rollout=True and fused_update=True: only the persistent rollout kernel "
+                         "keeps the scan history on chip, and only the fused update has the 42-column entry points")
 
 
 def check_bootstrap_config(cfg):

@@ -1746,6 +1746,120 @@ __device__ __forceinline__ ObsRow<mlp64::Layout<NB + 6>::KS> mlp64_obs_row(PRef 
     return r;
 }
 
+// ---- scan history (navsim_rollout_mlp64_hist / navsim_evaluate_mlp64_hist): the 42-column row of navsim_stack_rows, assembled on
+// chip.  Per env the workgroup keeps kHistLen = 22 floats in LDS: the scan of the previous row [0..9], the scan of the row before it
+// [10..19] and the previous row's past_action [20..21] -- in that order they ARE columns 16..37 of a row that does not start an episode
+// -- each clamped to the episode's first row (the cut) and, with float16 rows, rounded as the buffer holds it.  Row stride 23: odd.
+constexpr int kHistLen = 22, kHistStride = 23, kHistD = 42;
+// the column of the CURRENT 16-column row that column f (16..37) of the stacked row copies when the row starts an episode
+__device__ __forceinline__ int hist_src_col(const int f) { return f < 26 ? f - 16 : f - 26; }
+
+// Whether step t ends env e's episode, from the three values that are final at barrier B2: the predicate under which part 3 of
+// step_body writes `ended` (d || a || timeout there; next_obs_n evaluates the same three).
+template <int NB, int EPB, int NW, bool SENS, class PRef>
+__device__ __forceinline__ bool hist_step_ends(PRef P, const StepSmem<NB, EPB, NW>& sm, const int e) {
+    const float mn = (SENS && sm.neg[e]) ? -INFINITY : __uint_as_float(sm.mn_bits[e]);
+    const bool d = (0.2 > (double)mn) && ((double)mn > 0);                                        // environment_new.py:200
+    const bool a = sm.sv_d[6][e] <= P.thr;                                                       // :204
+    const uint32_t step = (sm.sv_step[e] & kStepMask) + 1;
+    const bool timeout = (P.max_ep_steps > 0) && ((int)step >= P.max_ep_steps);                  // ppo.py:552
+    return d || a || timeout;
+}
+// Entry idx (0..11: the scan and past_action) of the row the step will leave for env e, behind barrier B2: next_obs_n's value for
+// one run-time column (`ends`: hist_step_ends).  With auto_reset the reset observation's entry -- its scan through THIS step's range
+// noise under SENS, past_action 0 -- else the row in sm.obs (which part 3 then leaves alone).
+template <int NB, int EPB, int NW, bool SENS, class PRef>
+__device__ __forceinline__ float hist_next_entry(PRef P, const StepSmem<NB, EPB, NW>& sm, const int e, const int idx, const bool ends,
+                                                 const float sigma, const int below_min) {
+    constexpr int DP = NB + 7;
+    if (!(ends && P.auto_reset)) return sm.obs[e * DP + idx];
+    if (idx >= NB) return 0.f;                                                                   // environment_new.py:372-373
+    const int c = ((sm.sv_d[6][e] <= P.thr) && P.respawn) ? 1 : 0;
+    float val = sm.sp_scan[c][e][idx];
+    if (SENS) {
+        float r = sensor_value(val, sigma, (sigma > 0.f) ? sm.noise[idx * EPB + e] : 0.f, below_min);
+        if (r == INFINITY) r = 3.5f;
+        val = r / 3.5f;
+    }
+    return val;
+}
+// The input of lane (env e, kk) of the 42-column policy tile: columns 11 kk .. 11 kk + 10 of the stacked row (44 padded features).
+// Columns 0..15 are mlp64_obs_row's of the 16-column policy (next_obs_n / sm.obs); columns 16..37 come from `hist`, or -- on a row
+// that starts an episode (row 0 of the launch: !IN_STEP; a row behind an ended step) -- are copies of the row's own scan and
+// past_action; 38..43 are 0.  Every value rounded to half when the buffers are (idempotent on what hist already holds).
+template <int NB, int EPB, int NW, bool SENS, bool IN_STEP, class PRef>
+__device__ __forceinline__ ObsRow<11> hist_obs_row(PRef P, const StepSmem<NB, EPB, NW>& sm, const float* hist, const int e, const int kk,
+                                                   const int nloc, const bool half_rows, const float sigma, const int below_min) {
+    static_assert(NB == 10, "the history row stacks 10-beam scans");
+    constexpr int KS = 11, D = NB + 6, DP = NB + 7;
+    const bool valid = e < nloc;
+    const int el = min(e, nloc - 1);
+    ObsRow<KS> r;
+    float (&xs)[KS] = r.x;
+    bool ends = true;
+    if constexpr (IN_STEP) {
+        next_obs_n<NB, EPB, NW, SENS, KS, PRef>(P, sm, el, KS * kk, sigma, below_min, xs);   // (columns past 15: 0)
+        ends = hist_step_ends<NB, EPB, NW, SENS, PRef>(P, sm, el);
+    } else {
+#pragma unroll
+        for (int j = 0; j < KS; ++j) xs[j] = (KS * kk + j < D) ? sm.obs[el * DP + min(KS * kk + j, D - 1)] : 0.f;
+    }
+#pragma unroll
+    for (int j = 0; j < KS; ++j) {
+        const int f = KS * kk + j;
+        if (f >= D && f < D + kHistLen) {
+            float v;
+            if (ends) {
+                if constexpr (IN_STEP) v = hist_next_entry<NB, EPB, NW, SENS, PRef>(P, sm, el, hist_src_col(f), true, sigma, below_min);
+                else v = sm.obs[el * DP + hist_src_col(f)];
+            } else {
+                v = hist[el * kHistStride + (f - D)];
+            }
+            xs[j] = v;
+        }
+    }
+    if (half_rows) {
+#pragma unroll
+        for (int j = 0; j < KS; ++j) xs[j] = __half2float(__float2half_rn(xs[j]));
+    }
+    if (!valid) {
+#pragma unroll
+        for (int j = 0; j < KS; ++j) xs[j] = 0.f;
+    }
+    return r;
+}
+// The history of the launch's row 0, straight from the observation buffer (before the first step overwrites the tile): both older
+// frames are row 0's scan, the older action its past_action.
+template <int NB, int NW>
+__device__ __forceinline__ void hist_init(float* hist, const void* obs, const int base, const int nloc, const bool half_rows) {
+    constexpr int D = NB + 6;
+    for (int k = threadIdx.x; k < nloc * kHistLen; k += 64 * NW) {
+        const int e = k / kHistLen, c = k % kHistLen;
+        const size_t src = (size_t)(base + e) * D + (size_t)hist_src_col(D + c);
+        hist[e * kHistStride + c] = half_rows ? __half2float(reinterpret_cast<const __half*>(obs)[src])
+                                              : reinterpret_cast<const float*>(obs)[src];
+    }
+}
+// The shift, lane = env, by the wave that arrives last at the in-step policy (last_arrival: the four tile waves have read `hist`,
+// and the next read is behind barrier B2 of the next step, which no wave reaches before this wave has passed barrier C):
+// the row the step leaves becomes the previous row.  On a row that starts an episode both frames become its scan.
+template <int NB, int EPB, int NW, bool SENS, class PRef>
+__device__ __forceinline__ void hist_shift(PRef P, const StepSmem<NB, EPB, NW>& sm, float* hist, const int e, const bool half_rows,
+                                           const float sigma, const int below_min) {
+    const bool ends = hist_step_ends<NB, EPB, NW, SENS, PRef>(P, sm, e);
+    float* h = hist + e * kHistStride;
+    for (int c = 0; c < NB + 2; ++c) {
+        float v = hist_next_entry<NB, EPB, NW, SENS, PRef>(P, sm, e, c, ends, sigma, below_min);
+        if (half_rows) v = __half2float(__float2half_rn(v));
+        if (c < NB) {
+            h[NB + c] = ends ? v : h[c];
+            h[c] = v;
+        } else {
+            h[NB + c] = v;   // [20..21]
+        }
+    }
+}
+
 // Each of K waves calls this once its part of a phase is in LDS; the wave that arrives last resets the counter for the next phase
 // and runs finish(): an LDS counter -- a wave's LDS operations are performed in order, so the one that reads K - 1 sees what the
 // other waves wrote.
@@ -1798,11 +1912,16 @@ __host__ __device__ __forceinline__ StepIO rollout_io(const RolloutArgs& R, cons
 // (A persistent kernel and its *_mov_kernel twin share one body function; each declares its own LDS variables, under the names
 // they had, and hands them to the body.  What the move into a body function did to the kernels without movers -- one or two VGPRs in
 // twelve instantiations, nothing else -- is listed in profiles/movers_kernel_resources.txt.)
-template <int NB, int EPB, bool SENS, int NW, bool BOXES, bool MOV>
+// HIST (navsim_rollout_mlp64_hist): the policy is the 42-64-64 one on the stacked row of the last three 10-beam scans (hist_obs_row;
+// `hist`: the workgroup's [16][kHistStride] LDS block); the env side and every buffer are those of the 16-column form.  Off, nothing
+// of it is compiled.
+template <int NB, int EPB, bool SENS, int NW, bool BOXES, bool MOV, bool HIST = false>
 __device__ __forceinline__ void rollout_body(const Params& P, const RolloutArgs& R, StepSmemFor<NB, EPB, NW, MOV>& sm, int& next_env,
-                                             float* const wts, float2 (&pol_z)[4][16], float2 (&pol_eps)[16], unsigned& pol_cnt) {
+                                             float* const wts, float2 (&pol_z)[4][16], float2 (&pol_eps)[16], unsigned& pol_cnt,
+                                             [[maybe_unused]] float* const hist = nullptr) {
     constexpr int D = NB + 6, kThreads = 64 * NW;
-    using PL = mlp64::Layout<D>;   // the (B + 6)-64-64 policy: 16-wide rows with 10 beams, 42-wide with 36
+    static_assert(!HIST || (NB == 10 && EPB == 16), "scan history: 16 envs, 10 beams");
+    using PL = mlp64::Layout<HIST ? kHistD : D>;   // the (B + 6)-64-64 policy: 16-wide rows with 10 beams, 42-wide with 36 (HIST: 42-wide on 10)
     constexpr int KS = PL::KS;
     static_assert(NW >= 6 && EPB <= 16, "policy phase: four tile waves + the noise wave beside wave 0's rules; one 16-env policy tile per workgroup");
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1815,6 +1934,7 @@ __device__ __forceinline__ void rollout_body(const Params& P, const RolloutArgs&
     load_obs_tile<NB, EPB, NW>(sm, R.obs_buf, base, nloc, half_rows);
     load_tables<NB, EPB, NW, const Params&>(P, sm);
     if constexpr (MOV) load_mover_phase0<NB, EPB, NW, const Params&>(P, sm, base, nloc);
+    if constexpr (HIST) hist_init<NB, NW>(hist, R.obs_buf, base, nloc, half_rows);
     const uint32_t step0 = R.step_base ? *R.step_base : 0u;
     const float var = *R.var_ptr;
     if (tid == 0) pol_cnt = 0u;
@@ -1826,6 +1946,16 @@ __device__ __forceinline__ void rollout_body(const Params& P, const RolloutArgs&
     const int below_min = SENS ? P.below_min_mode : 0;
     auto tile_part = [&](const int t2, auto in_step) __attribute__((always_inline)) {
         const int e = lane & 15, kk = lane >> 4;
+        if constexpr (HIST) {
+            const auto row = hist_obs_row<NB, EPB, NW, SENS, decltype(in_step)::value, const Params&>(P, sm, hist, e, kk, nloc,
+                                                                                                    half_rows, sigma, below_min);
+            const float (&xs)[KS] = row.x;
+            mlp64::f32x4 c1[4];
+            mlp64::policy_hidden1<PL>(wts, xs, lane, c1);
+            float pz3, pz4;
+            mlp64::policy_tile2<PL>(wts, c1, lane, t2, pz3, pz4);
+            if (kk == 0) pol_z[t2][e] = make_float2(pz3, pz4);
+        } else {
         const auto row = mlp64_obs_row<NB, EPB, NW, SENS, decltype(in_step)::value, const Params&>(P, sm, e, kk, nloc, half_rows,
                                                                                                  sigma, below_min);
         const float (&xs)[KS] = row.x;
@@ -1834,6 +1964,7 @@ __device__ __forceinline__ void rollout_body(const Params& P, const RolloutArgs&
         float pz3, pz4;
         mlp64::policy_tile2<PL>(wts, c1, lane, t2, pz3, pz4);
         if (kk == 0) pol_z[t2][e] = make_float2(pz3, pz4);
+        }
     };
     auto draw_noise = [&](const uint32_t step) __attribute__((always_inline)) {
         float e0, e1;
@@ -1878,6 +2009,9 @@ __device__ __forceinline__ void rollout_body(const Params& P, const RolloutArgs&
                 else if (ln < nloc) draw_noise(step0 + (uint32_t)(t + 1));
                 last_arrival<5>(pol_cnt, ln, [&]() __attribute__((always_inline)) {
                     if (ln < nloc) finish(tn + N);
+                    if constexpr (HIST) {
+                        if (ln < nloc) hist_shift<NB, EPB, NW, SENS, const Params&>(P, sm, hist, ln, half_rows, sigma, below_min);
+                    }
                 });
             }
         };
@@ -1907,6 +2041,33 @@ __global__ __launch_bounds__(64 * 8) void rollout_mov_kernel(Params P, RolloutAr
     __shared__ float2 pol_eps[16];
     __shared__ unsigned pol_cnt;
     rollout_body<10, 16, kMovSens, 8, BOXES, true>(P, R, sm, next_env, wts, pol_z, pol_eps, pol_cnt);
+}
+
+// The scan-history twins (navsim_rollout_mlp64_hist): 16 envs on 8 waves, 10 beams, the 42-64-64 actor staged in LDS.  Kernels of
+// their own names, so that what a rollout without history launches keeps its symbols and its code.
+template <bool SENS, bool BOXES>
+__global__ __launch_bounds__(64 * 8) void rollout_hist_kernel(Params P, RolloutArgs R) {
+    using PL = mlp64::Layout<kHistD>;
+    __shared__ StepSmem<10, 16, 8> sm;
+    __shared__ int next_env;
+    __shared__ __attribute__((aligned(16))) float wts[PL::P_ACTOR + 2];
+    __shared__ float2 pol_z[4][16];
+    __shared__ float2 pol_eps[16];
+    __shared__ unsigned pol_cnt;
+    __shared__ float hist[16 * kHistStride];   // the two older scans and the older action pair of the workgroup's envs
+    rollout_body<10, 16, SENS, 8, BOXES, false, true>(P, R, sm, next_env, wts, pol_z, pol_eps, pol_cnt, hist);
+}
+template <bool BOXES>
+__global__ __launch_bounds__(64 * 8) void rollout_hist_mov_kernel(Params P, RolloutArgs R) {
+    using PL = mlp64::Layout<kHistD>;
+    __shared__ StepSmemMov<10, 16, 8> sm;
+    __shared__ int next_env;
+    __shared__ __attribute__((aligned(16))) float wts[PL::P_ACTOR + 2];
+    __shared__ float2 pol_z[4][16];
+    __shared__ float2 pol_eps[16];
+    __shared__ unsigned pol_cnt;
+    __shared__ float hist[16 * kHistStride];
+    rollout_body<10, 16, kMovSens, 8, BOXES, true, true>(P, R, sm, next_env, wts, pol_z, pol_eps, pol_cnt, hist);
 }
 
 // ---------------------------------------------------------------- the persistent rollout for the reference's ACTIVE actor
@@ -2037,11 +2198,13 @@ __device__ __forceinline__ bool eval_quota_met(const int* ep_cnt, const int lane
     return __builtin_amdgcn_ballot_w64(ep_cnt[lane & (EPB - 1)] < quota) == 0ull;
 }
 
-template <int NB, bool SENS, bool BOXES, bool MOV>
+template <int NB, bool SENS, bool BOXES, bool MOV, bool HIST = false>   // HIST: as in rollout_body (navsim_evaluate_mlp64_hist)
 __device__ __forceinline__ void evaluate_body(const Params& P, const EvalArgs& R, StepSmemFor<NB, 16, 8, MOV>& sm, int& next_env,
-                                              float* const wts, float2 (&pol_z)[4][16], unsigned& pol_cnt, int (&ep_cnt)[16]) {
+                                              float* const wts, float2 (&pol_z)[4][16], unsigned& pol_cnt, int (&ep_cnt)[16],
+                                              [[maybe_unused]] float* const hist = nullptr) {
     constexpr int EPB = 16, NW = 8, D = NB + 6, kThreads = 64 * NW;
-    using PL = mlp64::Layout<D>;
+    static_assert(!HIST || NB == 10, "scan history: 10 beams");
+    using PL = mlp64::Layout<HIST ? kHistD : D>;
     constexpr int KS = PL::KS;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int base = blockIdx.x * EPB;
@@ -2053,12 +2216,23 @@ __device__ __forceinline__ void evaluate_body(const Params& P, const EvalArgs& R
     load_obs_tile<NB, EPB, NW>(sm, R.obs0, base, nloc, half_rows);
     load_tables<NB, EPB, NW, const Params&>(P, sm);
     if constexpr (MOV) load_mover_phase0<NB, EPB, NW, const Params&>(P, sm, base, nloc);
+    if constexpr (HIST) hist_init<NB, NW>(hist, R.obs0, base, nloc, half_rows);
     if (tid == 0) pol_cnt = 0u;
     __syncthreads();
     const float sigma = SENS ? P.sigma : 0.f;
     const int below_min = SENS ? P.below_min_mode : 0;
     auto tile_part = [&](const int t2, auto in_step) __attribute__((always_inline)) {   // as in rollout_kernel
         const int e = lane & 15, kk = lane >> 4;
+        if constexpr (HIST) {
+            const auto row = hist_obs_row<NB, EPB, NW, SENS, decltype(in_step)::value, const Params&>(P, sm, hist, e, kk, nloc,
+                                                                                                    half_rows, sigma, below_min);
+            const float (&xs)[KS] = row.x;
+            mlp64::f32x4 c1[4];
+            mlp64::policy_hidden1<PL>(wts, xs, lane, c1);
+            float pz3, pz4;
+            mlp64::policy_tile2<PL>(wts, c1, lane, t2, pz3, pz4);
+            if (kk == 0) pol_z[t2][e] = make_float2(pz3, pz4);
+        } else {
         const auto row = mlp64_obs_row<NB, EPB, NW, SENS, decltype(in_step)::value, const Params&>(P, sm, e, kk, nloc, half_rows,
                                                                                                  sigma, below_min);
         const float (&xs)[KS] = row.x;
@@ -2067,6 +2241,7 @@ __device__ __forceinline__ void evaluate_body(const Params& P, const EvalArgs& R
         float pz3, pz4;
         mlp64::policy_tile2<PL>(wts, c1, lane, t2, pz3, pz4);
         if (kk == 0) pol_z[t2][e] = make_float2(pz3, pz4);
+        }
     };
     auto finish = [&]() __attribute__((always_inline)) {   // any wave, lane = env
         const int e = lane;
@@ -2091,6 +2266,9 @@ __device__ __forceinline__ void evaluate_body(const Params& P, const EvalArgs& R
                 tile_part(wv - 1, std::true_type{});
                 last_arrival<4>(pol_cnt, ln, [&]() __attribute__((always_inline)) {
                     if (ln < nloc) finish();
+                    if constexpr (HIST) {
+                        if (ln < nloc) hist_shift<NB, EPB, NW, SENS, const Params&>(P, sm, hist, ln, half_rows, sigma, below_min);
+                    }
                 });
             }
         };
@@ -2126,6 +2304,32 @@ __global__ __launch_bounds__(64 * 8) void evaluate_mov_kernel(Params P, EvalArgs
     __shared__ unsigned pol_cnt;
     __shared__ int ep_cnt[16];
     evaluate_body<10, kMovSens, BOXES, true>(P, R, sm, next_env, wts, pol_z, pol_cnt, ep_cnt);
+}
+
+// the scan-history twins (navsim_evaluate_mlp64_hist), as rollout_hist_kernel / rollout_hist_mov_kernel
+template <bool SENS, bool BOXES>
+__global__ __launch_bounds__(64 * 8) void evaluate_hist_kernel(Params P, EvalArgs R) {
+    using PL = mlp64::Layout<kHistD>;
+    __shared__ StepSmem<10, 16, 8> sm;
+    __shared__ int next_env;
+    __shared__ __attribute__((aligned(16))) float wts[PL::P_ACTOR + 2];
+    __shared__ float2 pol_z[4][16];
+    __shared__ unsigned pol_cnt;
+    __shared__ int ep_cnt[16];
+    __shared__ float hist[16 * kHistStride];
+    evaluate_body<10, SENS, BOXES, false, true>(P, R, sm, next_env, wts, pol_z, pol_cnt, ep_cnt, hist);
+}
+template <bool BOXES>
+__global__ __launch_bounds__(64 * 8) void evaluate_hist_mov_kernel(Params P, EvalArgs R) {
+    using PL = mlp64::Layout<kHistD>;
+    __shared__ StepSmemMov<10, 16, 8> sm;
+    __shared__ int next_env;
+    __shared__ __attribute__((aligned(16))) float wts[PL::P_ACTOR + 2];
+    __shared__ float2 pol_z[4][16];
+    __shared__ unsigned pol_cnt;
+    __shared__ int ep_cnt[16];
+    __shared__ float hist[16 * kHistStride];
+    evaluate_body<10, kMovSens, BOXES, true, true>(P, R, sm, next_env, wts, pol_z, pol_cnt, ep_cnt, hist);
 }
 
 // (evaluate_resmlp_kernel keeps the parent commit's form of the staging, the policy phase and the EvalIO set-up: through
@@ -2543,6 +2747,57 @@ __global__ void spawn_obs_kernel(const float* __restrict__ best, int n, int belo
     float r = sensor_value(best[k], 0.f, 0.f, below_min_mode);
     if (r == INFINITY) r = 3.5f;
     out[k] = r / 3.5f;
+}
+
+// ---------------------------------------------------------------- navsim_stack_rows: [R, N, 16] rows -> [R, N, 42] history rows
+// Column c of out[r][n] is a copy of one entry of obs[r'][n], r' in {r, r - 1, r - 2} clamped to the episode's first row (the rule
+// is written out in include/navsim.h; env.stack_rows_reference is its host mirror).  A bandwidth kernel: the output is one flat
+// array, a thread owns 16 bytes of it (4 floats / 8 halves, crossing a row boundary where they do) and stores them at once;
+// neighbouring threads read neighbouring entries of the same three source rows, which the caches serve (each input row is read
+// three times, the output written once: 3.6 x the input's bytes in all).
+template <class T>
+__global__ __launch_bounds__(256) void stack_rows_kernel(const T* __restrict__ obs, const uint8_t* __restrict__ ended, const int R,
+                                                         const int N, T* __restrict__ out) {
+    constexpr int V = 16 / (int)sizeof(T), DI = 16, DO = kHistD;
+    const size_t total = (size_t)R * (size_t)N * DO;
+    const size_t k0 = ((size_t)blockIdx.x * 256 + threadIdx.x) * V;
+    if (k0 >= total) return;
+    size_t q = k0 / DO;             // flat row index r N + n
+    int c = (int)(k0 - q * DO);
+    const size_t n_rows = (size_t)R * (size_t)N;
+    size_t s0 = 0, s1 = 0, s2 = 0;   // element offsets of the rows frames 0, 1, 2 are copied from
+    auto locate = [&](const size_t row) {
+        const size_t r = row / (size_t)N;
+        const bool cut0 = (r == 0) || (ended[row - (size_t)N] != 0);                  // row r starts an episode
+        const bool cut1 = cut0 || (r == 1) || (ended[row - 2 * (size_t)N] != 0);      // ... or row r - 1 does
+        s0 = row * DI;
+        s1 = cut0 ? s0 : s0 - (size_t)N * DI;
+        s2 = cut0 ? s0 : (cut1 ? s1 : s1 - (size_t)N * DI);
+    };
+    locate(q);
+    alignas(16) T v[V];
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+        T x = T(0.f);
+        if (q < n_rows) {
+            if (c < DI) x = obs[s0 + c];
+            else if (c < 26) x = obs[s1 + (c - 16)];
+            else if (c < 36) x = obs[s2 + (c - 26)];
+            else if (c < 38) x = obs[s1 + (c - 26)];   // past_action of the previous row: columns 10, 11
+        }
+        v[j] = x;
+        if (++c == DO) {
+            c = 0;
+            ++q;
+            if (q < n_rows) locate(q);
+        }
+    }
+    if (k0 + V <= total) {
+        *reinterpret_cast<uint4*>(out + k0) = *reinterpret_cast<const uint4*>(v);
+    } else {
+        for (int j = 0; j < V; ++j)
+            if (k0 + j < total) out[k0 + j] = v[j];
+    }
 }
 
 // ---------------------------------------------------------------- return scan (PPO.compute_rtgs)
@@ -3491,6 +3746,29 @@ int navsim_rollout_mlp64(navsim_t* h, const float* actor_params_dev, void* obs_b
     return NAVSIM_OK;
 }
 
+int navsim_rollout_mlp64_hist(navsim_t* h, const float* actor_params_dev, void* obs_buf_dev, float* act_buf_dev,
+                              float* logp_buf_dev, float* reward_dev, uint8_t* done_dev, uint8_t* arrive_dev, uint8_t* ended_dev,
+                              float* ep_return_dev, int32_t* ep_length_dev, float* ep_path_dev, const float* var_dev,
+                              uint64_t act_seed, const uint32_t* step_base_dev, int32_t n_steps, void* stream) {
+    RolloutArgs R;
+    const int rc = rollout_args(h, "navsim_rollout_mlp64_hist", [](int b) { return b == 10; },
+                                "the scan-history policy stacks 10-beam scans (n_beams must be 10)", R, actor_params_dev, obs_buf_dev,
+                                act_buf_dev, logp_buf_dev, reward_dev, done_dev, arrive_dev, ended_dev, ep_return_dev, ep_length_dev,
+                                ep_path_dev, var_dev, act_seed, step_base_dev, n_steps);
+    if (rc != NAVSIM_OK || n_steps == 0) return rc;
+    // always 16 envs on 8 waves, whatever navsim_set_shape says: beyond 4096 envs the workgroups run in rounds
+    const dim3 grid((h->P.N + 15) / 16), block(64 * 8);
+    auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)stream, h->P, R); };
+    with_flag(sens_on(h), [&](auto S) {
+        with_flag(h->P.tile_box != nullptr, [&](auto BOXES) {
+            if (h->P.mov_tape) go(rollout_hist_mov_kernel<BOXES>);
+            else go(rollout_hist_kernel<S, BOXES>);
+        });
+    });
+    HIP_TRY(hipGetLastError());
+    return NAVSIM_OK;
+}
+
 int navsim_rollout_resmlp512(navsim_t* h, const float* actor_params_dev, void* obs_buf_dev, float* act_buf_dev, float* logp_buf_dev,
                              float* reward_dev, uint8_t* done_dev, uint8_t* arrive_dev, uint8_t* ended_dev, float* ep_return_dev,
                              int32_t* ep_length_dev, float* ep_path_dev, const float* var_dev, uint64_t act_seed,
@@ -3547,6 +3825,27 @@ int navsim_evaluate_mlp64(navsim_t* h, const float* actor_params_dev, const void
             if (h->P.mov_tape) go(evaluate_mov_kernel<BOXES>);   // (10 beams: navsim_set_movers)
             else if (h->P.B == 36) go(evaluate_kernel<36, S, BOXES>);
             else go(evaluate_kernel<10, S, BOXES>);
+        });
+    });
+    HIP_TRY(hipGetLastError());
+    return NAVSIM_OK;
+}
+
+int navsim_evaluate_mlp64_hist(navsim_t* h, const float* actor_params_dev, const void* obs0_dev, int32_t quota, int32_t n_steps,
+                               uint8_t* ep_flags_dev, int32_t* ep_length_dev, float* ep_return_dev, float* ep_path_dev,
+                               int32_t* count_dev, int32_t* steps_dev, void* stream) {
+    const int rc = eval_check(h, "navsim_evaluate_mlp64_hist", actor_params_dev, obs0_dev, quota, n_steps, ep_flags_dev, ep_length_dev,
+                              ep_return_dev, ep_path_dev, count_dev, steps_dev, [](int b) { return b == 10; },
+                              "the scan-history policy stacks 10-beam scans (n_beams must be 10)");
+    if (rc != NAVSIM_OK) return rc;
+    const EvalArgs R = {actor_params_dev, obs0_dev, ep_flags_dev, ep_length_dev, ep_return_dev, ep_path_dev, count_dev, steps_dev,
+                        quota, n_steps};
+    const dim3 grid((h->P.N + 15) / 16), block(64 * 8);
+    auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)stream, h->P, R); };
+    with_flag(sens_on(h), [&](auto S) {
+        with_flag(h->P.tile_box != nullptr, [&](auto BOXES) {
+            if (h->P.mov_tape) go(evaluate_hist_mov_kernel<BOXES>);
+            else go(evaluate_hist_kernel<S, BOXES>);
         });
     });
     HIP_TRY(hipGetLastError());
@@ -3732,6 +4031,27 @@ int navsim_gae_scan_trunc(const float* rew_dev, const uint8_t* ended_dev, const 
     else
         hipLaunchKernelGGL(gae_trunc_kernel_generic, dim3((N + 63) / 64), dim3(64), 0, (hipStream_t)stream, rew_dev, ended_dev, done_dev,
                            arrive_dev, value_dev, last_value_dev, T, N, gamma, lam, adv_dev, ret_dev);
+    HIP_TRY(hipGetLastError());
+    return NAVSIM_OK;
+}
+
+int navsim_stack_rows(const void* obs_dev, int32_t obs_f16, const uint8_t* ended_dev, int32_t R, int32_t N, void* out_dev,
+                      void* stream) {
+    if (R < 1 || N < 1) return fail(NAVSIM_E_ARG, "navsim_stack_rows: R and N must be at least 1");
+    if (!obs_dev || !out_dev) return fail(NAVSIM_E_ARG, "navsim_stack_rows: null buffer");
+    if (R > 1 && !ended_dev) return fail(NAVSIM_E_ARG, "navsim_stack_rows: ended_dev may be null only when R == 1");
+    if (((uintptr_t)obs_dev & 15) || ((uintptr_t)out_dev & 15))
+        return fail(NAVSIM_E_ARG, "navsim_stack_rows: obs_dev and out_dev must be 16-byte aligned");
+    const size_t total = (size_t)R * (size_t)N * (size_t)kHistD;
+    const size_t per = obs_f16 ? 8 : 4;
+    const size_t blocks = ((total + per - 1) / per + 255) / 256;
+    if (blocks > 0x7fffffffull) return fail(NAVSIM_E_ARG, "navsim_stack_rows: too many rows for one launch");
+    if (obs_f16)
+        hipLaunchKernelGGL(stack_rows_kernel<__half>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
+                           reinterpret_cast<const __half*>(obs_dev), ended_dev, R, N, reinterpret_cast<__half*>(out_dev));
+    else
+        hipLaunchKernelGGL(stack_rows_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
+                           reinterpret_cast<const float*>(obs_dev), ended_dev, R, N, reinterpret_cast<float*>(out_dev));
     HIP_TRY(hipGetLastError());
     return NAVSIM_OK;
 }

@@ -20,7 +20,10 @@ import torch
 from . import maps as _maps
 from ._native import NavsimCfg, NavsimError, NavsimInfo, check, lib
 
-__all__ = ["NavSim", "VecEnv", "Env", "NavsimError", "rtg_scan", "gae_scan", "gae_scan_trunc", "truncated_returns_reference"]
+__all__ = ["NavSim", "VecEnv", "Env", "NavsimError", "rtg_scan", "gae_scan", "gae_scan_trunc", "truncated_returns_reference",
+           "stack_rows", "stack_rows_reference", "HistoryWindow", "HostHistoryWindow", "HIST_DIM"]
+
+HIST_DIM = 42   # columns of a scan-history row (navsim_stack_rows)
 
 
 def _ptr(t):
@@ -422,6 +425,129 @@ def truncated_returns_reference(rew, ended, done, arrive, value, gamma, lam, las
     return ret - V, ret
 
 
+def stack_rows_reference(obs, ended=None):
+    """Host mirror of navsim_stack_rows, numpy -- the statement of the scan-history rule.  obs [R, N, 16] (float32 or float16) are
+    ordinary rows (10 beams / 3.5, past_action, 4 goal columns), ended [R - 1, N] (non-zero = the step between rows t and t + 1 ended
+    the episode; None allowed when R == 1).  Returns [R, N, 42] of obs's dtype, every entry a copy:
+        out[t, :,  0:16] = obs[t]                  the ordinary row
+        out[t, :, 16:26] = obs[i1, :, 0:10]        the previous scan,          i1 = max(t - 1, r(t))
+        out[t, :, 26:36] = obs[i2, :, 0:10]        the scan before it,         i2 = max(t - 2, r(t))
+        out[t, :, 36:38] = obs[i1, :, 10:12]       the action between the two older scans
+        out[t, :, 38:42] = 0
+    r(t) = the latest s <= t with s == 0 or ended[s - 1] != 0: frames never reach across an episode's first row, and row 0 of the
+    buffer always counts as one."""
+    obs = np.asarray(obs)
+    if obs.ndim != 3 or obs.shape[2] != 16:
+        raise ValueError(f"stack_rows_reference: obs must be [R, N, 16], got {obs.shape}")
+    R, N, _ = obs.shape
+    if R < 1 or N < 1:
+        raise ValueError("stack_rows_reference: R and N must be at least 1")
+    if ended is None:
+        if R > 1:
+            raise ValueError("stack_rows_reference: ended may be None only when R == 1")
+        end = np.zeros((0, N), dtype=bool)
+    else:
+        end = np.asarray(ended).reshape(R - 1, N) != 0
+    out = np.zeros((R, N, HIST_DIM), dtype=obs.dtype)
+    cols = np.arange(N)
+    start = np.zeros(N, dtype=np.int64)   # r(t) per env
+    for t in range(R):
+        if t > 0:
+            start = np.where(end[t - 1], t, start)
+        i1, i2 = np.maximum(t - 1, start), np.maximum(t - 2, start)
+        out[t, :, 0:16] = obs[t]
+        out[t, :, 16:26] = obs[i1, cols, 0:10]
+        out[t, :, 26:36] = obs[i2, cols, 0:10]
+        out[t, :, 36:38] = obs[i1, cols, 10:12]
+    return out
+
+
+def stack_rows(obs, ended=None, out=None):
+    """navsim_stack_rows on device tensors: obs [R, N, 16] float32 or float16, ended [R - 1, N] uint8 (None allowed when R == 1)
+    -> [R, N, 42] of obs's dtype (``out`` if given); stack_rows_reference states the rule.  Asynchronous on the current stream."""
+    if not torch.is_tensor(obs) or not obs.is_cuda:
+        raise NavsimError("stack_rows needs device tensors; there is no CPU path (stack_rows_reference is the host mirror)")
+    if obs.dim() != 3 or obs.shape[2] != 16 or obs.dtype not in (torch.float32, torch.float16) or not obs.is_contiguous():
+        raise NavsimError(f"stack_rows: obs must be contiguous [R, N, 16] float32 or float16 rows, got {obs.dtype} {tuple(obs.shape)}")
+    R, N = int(obs.shape[0]), int(obs.shape[1])
+    if ended is not None and (not torch.is_tensor(ended) or ended.device != obs.device or ended.dtype != torch.uint8
+                              or ended.numel() != (R - 1) * N or not ended.is_contiguous()):
+        raise NavsimError(f"stack_rows: ended must be {(R - 1) * N} contiguous uint8 values on {obs.device}")
+    if ended is not None and R == 1:
+        ended = None
+    if out is None:
+        out = torch.empty((R, N, HIST_DIM), dtype=obs.dtype, device=obs.device)
+    elif (not torch.is_tensor(out) or out.device != obs.device or out.dtype != obs.dtype or out.numel() != R * N * HIST_DIM
+          or not out.is_contiguous()):
+        raise NavsimError(f"stack_rows: out must be {R * N * HIST_DIM} contiguous {obs.dtype} values on {obs.device}")
+    with torch.cuda.device(obs.device):
+        check(lib().navsim_stack_rows(_ptr(obs), int(obs.dtype == torch.float16), _ptr(ended), R, N, _ptr(out), _stream()),
+              "navsim_stack_rows")
+    return out
+
+
+class HistoryWindow:
+    """The last three ordinary rows and the flags between them, for a loop that steps the envs itself: ``reset(obs)`` starts every
+    env's episode, ``push(obs, ended)`` adds the row a step left (``ended`` [N] uint8: that step's flag); both return the current
+    [N, 42] history row -- the last row navsim_stack_rows makes of the window, which is exact whatever lies in front of it."""
+
+    def __init__(self, n_envs, device, dtype=torch.float32):
+        self.N = int(n_envs)
+        self.rows = torch.zeros((3, self.N, 16), dtype=dtype, device=device)
+        self.flags = torch.zeros((2, self.N), dtype=torch.uint8, device=device)
+        # one output per window length, each an allocation of its own (a tail of a [3, N, 42] buffer is 16-byte aligned for even N only)
+        self.out = [torch.zeros((R, self.N, HIST_DIM), dtype=dtype, device=device) for R in (1, 2, 3)]
+        self.row = torch.zeros((self.N, HIST_DIM), dtype=dtype, device=device)   # the current history row
+        self.count = 0
+
+    def reset(self, obs):
+        self.count = 0
+        return self.push(obs)
+
+    def push(self, obs, ended=None):
+        if self.count and ended is None:
+            raise NavsimError("HistoryWindow.push: the flag of the step that produced the row is required")
+        if self.count:
+            self.rows[0].copy_(self.rows[1])
+            self.rows[1].copy_(self.rows[2])
+            self.flags[0].copy_(self.flags[1])
+            self.flags[1].copy_(ended.reshape(self.N))
+        self.rows[2].copy_(obs.reshape(self.N, 16))
+        self.count = min(self.count + 1, 3)
+        R = self.count
+        out = self.out[R - 1]
+        stack_rows(self.rows[3 - R:], self.flags[3 - R:] if R > 1 else None, out=out)
+        self.row.copy_(out[R - 1])   # (an allocation of its own: aligned for every N, as the act entry points want their rows)
+        return self.row
+
+
+class HostHistoryWindow:
+    """HistoryWindow for ONE env on the host (Env(scan_history=True)): a three-row deque of 16-vectors and the flags between them,
+    the rule applied through stack_rows_reference.  reset(row) / push(row, ended) return the 42-vector in the rows' dtype."""
+
+    def __init__(self):
+        import collections
+        self.rows, self.flags = collections.deque(maxlen=3), collections.deque(maxlen=2)
+
+    def reset(self, row):
+        self.rows.clear()
+        self.flags.clear()
+        return self._row(row)
+
+    def push(self, row, ended):
+        if not self.rows:
+            raise ValueError("HostHistoryWindow.push before reset")
+        self.flags.append(bool(ended))
+        return self._row(row)
+
+    def _row(self, row):
+        self.rows.append(np.array(row).reshape(16))
+        obs = np.stack(self.rows)[:, None, :]
+        flags = list(self.flags)[-(len(self.rows) - 1):] if len(self.rows) > 1 else None
+        end = None if flags is None else np.array(flags, dtype=np.uint8).reshape(-1, 1)
+        return stack_rows_reference(obs, end)[-1, 0]
+
+
 class VecEnv:
     """N environments stepped by one kernel launch; tensors stay on the GPU.
 
@@ -508,20 +634,25 @@ class VecEnv:
         return out
 
 
-    def rollout_mlp64(self, actor_params, n_steps, var, seed=0, step_base=0, obs0=None):
+    def rollout_mlp64(self, actor_params, n_steps, var, seed=0, step_base=0, obs0=None, history=False):
         """PPO.rollout's hot loop (ppo.py:505-594) for the (B + 6)-64-64 policy in ONE launch (navsim_rollout_mlp64): per step
         PPO.get_action (ppo.py:673-706) on the observation the previous step left on chip, then the env step.
         actor_params: flat float32 device tensor [5378] (10 beams) / [7042] (36 beams) in nn.Module.named_parameters order
         (include/navppo.h); var: exploration variance (float or device scalar); action noise = Philox(seed, global env id,
         step_base + t).  obs0 [N, B + 6]: the observations to start from (default: a fresh reset).  Returns a namespace: obs
         [T + 1, N, B + 6] (row 0 = obs0; float16 on an obs_f16 env), act [T, N, 2], logp / reward / done / arrive / ended /
-        ep_return / ep_length / ep_path [T, N] -- bit-identical to T pairs of navppo_mlp64_act / step calls."""
+        ep_return / ep_length / ep_path [T, N] -- bit-identical to T pairs of navppo_mlp64_act / step calls.
+        history=True (10 beams): navsim_rollout_mlp64_hist -- actor_params is the [7042] 42-64-64 actor, which reads the scan-history
+        row of every step (stack_rows_reference); every returned buffer keeps its shape, obs stays [T + 1, N, 16]."""
         import ctypes as C
         from ._native import check, lib
         if self.B not in (10, 36):
             raise NavsimError("rollout_mlp64 needs 10 or 36 beams")
+        if history and self.B != 10:
+            raise NavsimError("rollout_mlp64(history=True) needs 10 beams: the history row stacks 10-beam scans")
         T, N, D, dev = int(n_steps), self.N, self.D, self.device
-        n_actor = 64 * D + 64 + 64 * 64 + 64 + 2 * (64 + 1)
+        n_actor = 64 * (HIST_DIM if history else D) + 64 + 64 * 64 + 64 + 2 * (64 + 1)
+        entry = "navsim_rollout_mlp64_hist" if history else "navsim_rollout_mlp64"
         prm = actor_params.to(device=dev, dtype=torch.float32).contiguous()
         if prm.numel() != n_actor or prm.data_ptr() % 16:
             raise NavsimError(f"actor_params: {n_actor} float32 values, 16-byte aligned")
@@ -541,16 +672,16 @@ class VecEnv:
         base_t = torch.tensor(int(step_base), dtype=torch.int32, device=dev)
         p = lambda x: C.c_void_p(x.data_ptr())
         with torch.cuda.device(dev):
-            check(lib().navsim_rollout_mlp64(self.sim._h, p(prm), p(out.obs), p(out.act), p(out.logp), p(out.reward), p(out.done),
-                                             p(out.arrive), p(out.ended), p(out.ep_return), p(out.ep_length), p(out.ep_path), p(var_t),
-                                             int(seed) & 0xFFFFFFFFFFFFFFFF, p(base_t), T,
-                                             C.c_void_p(torch.cuda.current_stream().cuda_stream)), "navsim_rollout_mlp64")
+            check(getattr(lib(), entry)(self.sim._h, p(prm), p(out.obs), p(out.act), p(out.logp), p(out.reward), p(out.done),
+                                        p(out.arrive), p(out.ended), p(out.ep_return), p(out.ep_length), p(out.ep_path), p(var_t),
+                                        int(seed) & 0xFFFFFFFFFFFFFFFF, p(base_t), T,
+                                        C.c_void_p(torch.cuda.current_stream().cuda_stream)), entry)
             torch.cuda.current_stream().synchronize()   # var_t / base_t / prm may be temporaries of this call
         return out
 
     EVAL_POLICIES = {"mlp64x2": "navsim_evaluate_mlp64", "resmlp512": "navsim_evaluate_resmlp512"}
 
-    def evaluate_policy(self, actor_params, quota, n_steps=None, policy="mlp64x2", fill=0):
+    def evaluate_policy(self, actor_params, quota, n_steps=None, policy="mlp64x2", fill=0, history=False):
         """The evaluation loop (main.py:135-252) in ONE launch (navsim_evaluate_mlp64 / navsim_evaluate_resmlp512): a fresh
         reset, then every env plays whole episodes back to back with the DETERMINISTIC action (the clamped mean of the actor,
         main.py:197-199) and records its first ``quota`` of them; a workgroup of 16 envs stops once all of its envs are done,
@@ -559,9 +690,13 @@ class VecEnv:
         ("resmlp512", 10 beams).  Returns a namespace: flags [quota, N] uint8 (1 success, 2 collision, 4 timeout), length
         [quota, N] int32, ret / path [quota, N] float32, count [N] int32 (episodes recorded), steps [ceil(N / 16)] int32 (steps
         each workgroup executed); slots that were not reached hold ``fill``.  The env state afterwards is unspecified (the envs
-        ran on past their quota): reset before stepping this env again."""
+        ran on past their quota): reset before stepping this env again.
+        history=True (policy "mlp64x2", 10 beams): navsim_evaluate_mlp64_hist -- the [7042] 42-64-64 actor on scan-history rows."""
         import ctypes as C
         from ._native import check, lib
+        if history and (policy != "mlp64x2" or self.B != 10):
+            raise ValueError("evaluate_policy(history=True): the scan-history evaluation runs the 42-64-64 actor (policy 'mlp64x2') "
+                             f"on 10 beams, not policy {policy!r} on {self.B} beams")
         if policy not in self.EVAL_POLICIES:
             raise ValueError(f"evaluate_policy: no evaluation kernel for policy {policy!r} (have {sorted(self.EVAL_POLICIES)})")
         if policy == "resmlp512" and self.B != 10:
@@ -572,7 +707,8 @@ class VecEnv:
         N, D, dev, sim = self.N, self.D, self.device, self.sim
         quota = int(quota)
         n_steps = quota * int(sim.cfg.max_episode_steps) if n_steps is None else int(n_steps)
-        n_actor = 50290 if policy == "resmlp512" else 64 * D + 64 + 64 * 64 + 64 + 2 * (64 + 1)
+        n_actor = 50290 if policy == "resmlp512" else 64 * (HIST_DIM if history else D) + 64 + 64 * 64 + 64 + 2 * (64 + 1)
+        entry = "navsim_evaluate_mlp64_hist" if history else self.EVAL_POLICIES[policy]
         if not torch.is_tensor(actor_params):
             raise NavsimError("evaluate_policy: actor_params: expected a tensor")
         prm = actor_params.detach().to(device=dev, dtype=torch.float32).contiguous()
@@ -595,9 +731,9 @@ class VecEnv:
         sim.reset(obs0)
         p = lambda x: C.c_void_p(x.data_ptr())
         with torch.cuda.device(dev):
-            check(getattr(lib(), self.EVAL_POLICIES[policy])(
+            check(getattr(lib(), entry)(
                 sim._h, p(prm), p(obs0), quota, n_steps, p(out.flags), p(out.length), p(out.ret), p(out.path), p(out.count),
-                p(out.steps), C.c_void_p(torch.cuda.current_stream().cuda_stream)), self.EVAL_POLICIES[policy])
+                p(out.steps), C.c_void_p(torch.cuda.current_stream().cuda_stream)), entry)
             if prm.data_ptr() != actor_params.data_ptr():
                 torch.cuda.current_stream().synchronize()   # prm is a temporary of this call
         return out
@@ -653,12 +789,19 @@ class Env:
     resets, and on arrival it re-spawns the goal like ``setReward`` does (environment_new.py:245-267).
     """
 
-    def __init__(self, is_training, use_vision=False, vision_dim=64, map="stage_1", seed=0, device=None, movers=None):
+    def __init__(self, is_training, use_vision=False, vision_dim=64, map="stage_1", seed=0, device=None, movers=None,
+                 scan_history=False):
         """movers: moving obstacles (an extension, NavSim.set_movers; resolve_env_movers: a scene name, a tape [P, M, 4] or
         dict(tape=... | name=..., phase=int)).  The scan of a step sees tape[(k + 1 + phase) mod P], k = the steps taken since the last
-        reset(); the reset observation sees tape[phase].  None: the static world, exactly as without the keyword."""
+        reset(); the reset observation sees tape[phase].  None: the static world, exactly as without the keyword.
+        scan_history: reset() / step() return the 42-vector of stack_rows_reference (the last three scans, cut where the step's
+        `ended` flag -- collision or arrival here -- was set and at every reset()) instead of the 16-vector.  Host code only."""
         if use_vision:
             raise NotImplementedError("camera modality is outside the LiDAR hot path (SURVEY.md 2a)")
+        if not isinstance(scan_history, bool):
+            raise ValueError(f"scan_history {scan_history!r}: True or False")
+        self.scan_history = scan_history
+        self._hist = HostHistoryWindow() if scan_history else None
         self.use_vision = False
         self.vision_dim = vision_dim
         self.threshold_arrive = 0.2 if is_training else 0.4
@@ -777,6 +920,8 @@ class Env:
         self._call(self._lib.navsim_reset, self._reset_args, "navsim_reset")
         self._wait_results(obs_only=True)
         self._state = None
+        if self._hist is not None:
+            return self._hist.reset(self._pin_np[16:32]).astype(np.float64)
         return self._pin_np[16:32].astype(np.float64)
 
     def step(self, action, past_action):
@@ -790,6 +935,9 @@ class Env:
         self._call(self._lib.navsim_step, self._step_args, "navsim_step")
         self._wait_results()
         self._state = None
+        if self._hist is not None:
+            return (self._hist.push(self._pin_np[16:32], self._pin_u8_np[2]).astype(np.float64), float(self._pin_np[32]),
+                    bool(self._pin_u8_np[0]), bool(self._pin_u8_np[1]))
         return (self._pin_np[16:32].astype(np.float64), float(self._pin_np[32]), bool(self._pin_u8_np[0]),
                 bool(self._pin_u8_np[1]))
 

@@ -38,6 +38,12 @@ def load_actor(path, device):
     return actor.to(device).eval(), policy
 
 
+def reads_scan_history(actor, n_beams=10):
+    """True for a 42-input mlp64x2 actor on a 10-beam env: a checkpoint trained with PPOConfig.scan_history, whose rows are the
+    scan-history rows of env.stack_rows_reference (on 36 beams the same width is the ordinary row)."""
+    return isinstance(actor, nets.MLP64Actor) and actor.layer1.weight.shape[1] == 42 and n_beams == 10
+
+
 def persistent_policy(actor, n_beams=10):
     """(policy name, flat float32 actor in the layout of include/navppo.h) for VecEnv.evaluate_policy; ValueError if the actor
     or the beam count has no evaluation kernel -- ``evaluate(persistent=True)`` never falls back to the stepping loop."""
@@ -49,6 +55,8 @@ def persistent_policy(actor, n_beams=10):
         raise ValueError(f"evaluate(persistent=True): no evaluation kernel for an actor of type {type(actor).__name__} "
                          "(navsim_evaluate_mlp64 runs nets.MLP64Actor, navsim_evaluate_resmlp512 nets.ResMLPActor)")
     in_dim = (actor.rb1.fc1.weight if policy == "resmlp512" else actor.layer1.weight).shape[1]
+    if reads_scan_history(actor, n_beams):   # navsim_evaluate_mlp64_hist: the 42-64-64 actor on 10 beams
+        return policy, nets.flat_actor_params(actor)
     if n_beams not in beams or in_dim != n_beams + 6:
         raise ValueError(f"evaluate(persistent=True): no evaluation kernel for policy {policy} with {in_dim}-wide observations on "
                          f"{n_beams} beams (instantiated for {' / '.join(str(b) for b in beams)} beams)")
@@ -73,6 +81,7 @@ def evaluate(actor, num_episodes=100, max_timesteps_per_episode=500, map="stage_
     of the stepping alone) and ``steps`` (env steps behind it)."""
     n_par = int(n_parallel or min(num_episodes, 1024))
     quota = -(-int(num_episodes) // n_par)
+    history = reads_scan_history(actor)   # a scan_history checkpoint: both forms feed it the history rows (the env has 10 beams)
     if persistent:
         policy, flat_actor = persistent_policy(actor)
     env = VecEnv(n_par, map=map, max_episode_steps=max_timesteps_per_episode, auto_reset=True, is_training=False, seed=seed,
@@ -85,7 +94,7 @@ def evaluate(actor, num_episodes=100, max_timesteps_per_episode=500, map="stage_
         flat_actor = flat_actor.to(dev)
         torch.cuda.synchronize(dev)
         t0 = time.time()
-        tab = env.evaluate_policy(flat_actor, quota, policy=policy)
+        tab = env.evaluate_policy(flat_actor, quota, policy=policy, history=history)
         torch.cuda.synchronize(dev)
         seconds = time.time() - t0
         if int(tab.count.min()) < quota:
@@ -98,6 +107,11 @@ def evaluate(actor, num_episodes=100, max_timesteps_per_episode=500, map="stage_
         return _report(res, quota, n_par, num_episodes, seconds, steps, output_dir, method_name, log, timing, tape_id, n_tapes)
     actor = actor.to(dev).eval()
     obs = env.reset()
+    window = None
+    if history:
+        from .env import HistoryWindow
+        window = HistoryWindow(n_par, dev, obs.dtype)
+        obs = window.reset(obs)
     count = torch.zeros(n_par, dtype=torch.int64, device=dev)
     res = torch.zeros((quota, n_par, 6), dtype=torch.float64, device=dev)   # success, collision, timeout, length, return, path
     env_ids = torch.arange(n_par, device=dev)
@@ -107,6 +121,8 @@ def evaluate(actor, num_episodes=100, max_timesteps_per_episode=500, map="stage_
         action = actor(obs.float())                                   # deterministic mean action, main.py:197-199
         obs, rew, done, arrive = env.step(action)
         io = env.io
+        if window is not None:
+            obs = window.push(obs, io.ended)
         take = io.ended.bool() & (count < quota)
         a, d = arrive.bool(), done.bool()
         ln = io.ep_length.double()

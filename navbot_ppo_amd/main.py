@@ -17,7 +17,8 @@ exceeds 1.5 x the target), --minibatch_size M / --minibatch_shuffle MODE (K = ce
 batch, shuffled on the device), --norm_reward / --clip_reward C (rewards scaled by the running standard deviation of the discounted
 return and clipped to +-C before the return scan), --lr_schedule adaptive|linear with --desired_kl / --lr_min / --lr_max (the KL-adaptive
 step size decided on the device after every optimiser step, or a linear decay over --max_timesteps), --bootstrap_truncated (time-outs
-bootstrap with gamma V of their own row and the batch end with V of the next observation instead of counting as terminal), --movers NAME / --movers_period P (moving obstacles beside the static map, training and evaluation; NAME random:K with --movers_seed or bank:a,b,... is a bank of scenarios, one per env), --eval_movers NAME / --eval_movers_seed (held-out scenarios for --eval_every).  Vision flags are accepted and refused (the camera
+bootstrap with gamma V of their own row and the batch end with V of the next observation instead of counting as terminal), --movers NAME / --movers_period P (moving obstacles beside the static map, training and evaluation; NAME random:K with --movers_seed or bank:a,b,... is a bank of scenarios, one per env), --eval_movers NAME / --eval_movers_seed (held-out scenarios for --eval_every), --scan_history (the mlp64x2 policy reads the last three
+scans).  Vision flags are accepted and refused (the camera
 modality is outside the LiDAR hot path); --mode test maps to --eval (the reference's test path is broken).
 """
 import argparse
@@ -90,6 +91,9 @@ def get_args(argv=None):
                    help="training with --eval_every: the movers of the EVALUATION envs only, e.g. random:32 with another "
                         "--eval_movers_seed -- a held-out set of scenarios; default: the training world's")
     p.add_argument("--eval_movers_seed", type=int, default=1, help="the seed of --eval_movers random:K")
+    p.add_argument("--scan_history", action="store_true", default=False,
+                   help="the mlp64x2 policy reads the last three LiDAR scans and the action between them (a 42-column row assembled on "
+                        "the device, never across an episode start) instead of one scan; needs --policy mlp64x2; default: off")
     args = p.parse_args(argv)
     if args.output_dir is None:
         args.output_dir = os.path.join(os.getcwd(), "runs")
@@ -122,7 +126,7 @@ def config_of(args, rollout):
                          target_kl=args.target_kl, minibatch_size=args.minibatch_size, minibatch_shuffle=args.minibatch_shuffle,
                          norm_reward=args.norm_reward, clip_reward=args.clip_reward, lr_schedule=args.lr_schedule,
                          desired_kl=args.desired_kl, lr_min=args.lr_min, lr_max=args.lr_max,
-                         bootstrap_truncated=args.bootstrap_truncated,
+                         bootstrap_truncated=args.bootstrap_truncated, scan_history=args.scan_history,
                          eval_movers=movers_of(args.eval_movers, args.movers_period, args.eval_movers_seed))
 
 

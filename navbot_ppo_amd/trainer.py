@@ -8,7 +8,7 @@ import torch
 
 from . import nets
 from ._native import _navppo, _ptr, check, lib
-from .config import PPOConfig, check_bootstrap_config, check_reward_norm_config
+from .config import PPOConfig, check_bootstrap_config, check_reward_norm_config, check_scan_history_config
 from .distributed import as_ctx
 from .lr_schedule import linear_lr
 from .reward_norm import RET_RMS_INIT, return_moments, reward_scale
@@ -24,11 +24,23 @@ class PPOTrainer:
         self.device = env.device
         cfg = self.cfg
         N, T, D = env.N, cfg.rollout_len, env.D
+        check_scan_history_config(cfg)
+        self.scan_history = cfg.scan_history
+        if self.scan_history:
+            from .env import HIST_DIM
+            if env.B != 10:
+                raise ValueError(f"scan_history needs n_beams == 10 (the history row stacks 10-beam scans), not {env.B}")
+            if self.device.type != "cuda":
+                raise ValueError("scan_history runs on the GPU only: the history rows are built by HIP kernels")
+        # the width of the rows the nets read: the env's rows, or the scan-history rows built from them
+        self.net_dim = HIST_DIM if self.scan_history else D
         torch.manual_seed(cfg.seed)  # same initial weights on every rank (then broadcast anyway)
-        self.actor, self.critic = nets.make_policy(cfg.policy, D, 2)
+        self.actor, self.critic = nets.make_policy(cfg.policy, self.net_dim, 2)
         self.actor.to(self.device)
         self.critic.to(self.device)
         self.updater = PPOUpdater(self.actor, self.critic, cfg, ctx, self.device)
+        if self.scan_history and not (self.updater.fused_mlp64 and self.uses_persistent_rollout):
+            raise ValueError("scan_history needs the persistent rollout and the fused update of policy 'mlp64x2' on the GPU")
         torch.manual_seed(cfg.seed * 1000003 + 17 + ctx.rank)  # exploration noise differs per shard
         dev = self.device
         f32, u8 = torch.float32, torch.uint8
@@ -36,6 +48,9 @@ class PPOTrainer:
         # are read directly by the fused kernels of both policies (round 6: the 512-wide ones too), a PyTorch policy widens them
         self.obs_buf = torch.zeros((T + 1, N, D), dtype=env.sim.obs_dtype, device=dev)
         self._half_obs = env.sim.obs_dtype == torch.float16
+        # scan_history: the rows the nets read, built from obs_buf and ended_buf behind every rollout (navsim_stack_rows); obs_buf
+        # stays what the simulator writes, 16 columns wide
+        self.hist_buf = torch.zeros((T + 1, N, self.net_dim), dtype=env.sim.obs_dtype, device=dev) if self.scan_history else None
         self.act_buf = torch.zeros((T, N, 2), dtype=f32, device=dev)
         self.logp_buf = torch.zeros((T, N), dtype=f32, device=dev)
         self.rew_buf = torch.zeros((T, N), dtype=f32, device=dev)
@@ -132,7 +147,7 @@ class PPOTrainer:
         """ppo.py:505-594 in ONE launch (csrc/navsim.hip: rollout_kernel): policy step and env step alternate inside the
         kernel; same device functions and Philox keys as the per-step path, so the buffers come out bit-identical."""
         sim = self.env.sim
-        name = "navsim_rollout_" + ("resmlp512" if self.updater.fused_resmlp512 else "mlp64")
+        name = "navsim_rollout_" + ("resmlp512" if self.updater.fused_resmlp512 else "mlp64_hist" if self.scan_history else "mlp64")
         with torch.cuda.device(self.device):
             check(getattr(lib(), name)(sim._h, _ptr(self.updater.fp.flat), _ptr(self.obs_buf), _ptr(self.act_buf), _ptr(self.logp_buf),
                                        _ptr(self.rew_buf), _ptr(self.done_buf), _ptr(self.arrive_buf), _ptr(self.ended_buf),
@@ -153,6 +168,11 @@ class PPOTrainer:
         hipGraph of per-step launches."""
         return bool(self.cfg.persistent_rollout and ((self.updater.fused_mlp64 and self.env.B in (10, 36)) or
                                                      (self.updater.fused_resmlp512 and self.env.B == 10)))
+
+    @property
+    def net_obs(self):
+        """[T + 1, N, .]: the rows the nets read -- obs_buf, or with scan_history the history rows built from it"""
+        return self.hist_buf if self.scan_history else self.obs_buf
 
     @torch.no_grad()
     def rollout(self):
@@ -187,6 +207,10 @@ class PPOTrainer:
         else:
             self._rollout_body()
         from .env import gae_scan, gae_scan_trunc, rtg_scan
+        if self.scan_history:   # the batch the nets read, [T + 1, N, 42]: one bandwidth kernel per iteration
+            from .env import stack_rows
+            self.updater.invalidate_prepared()   # hist_buf is rewritten behind torch's version counter too
+            stack_rows(self.obs_buf, self.ended_buf, out=self.hist_buf)
         self._gae = None
         rew = self._normalise_rewards() if cfg.norm_reward else self.rew_buf   # (the scans below are the same either way)
         trunc, lam = cfg.bootstrap_truncated, cfg.gae_lambda
@@ -200,10 +224,10 @@ class PPOTrainer:
             # adds gamma V of its own observation (the terminal observation is gone: the step kernels store the reset one), the envs still
             # running on the last row bootstrap with V(obs_buf[T]) (ended[T-1] cuts that for an env that ended there) -- for every
             # lambda; None runs as 1: the reference's A = R - V on truncation-aware returns.  rew is in the critic's units either way.
-            T, N, D = cfg.rollout_len, self.env.N, self.env.D
+            T, N, D = cfg.rollout_len, self.env.N, self.net_dim
             lam = 1.0 if lam is None else lam
             boot = trunc or lam < 1.0   # V(obs_buf[T]) bootstraps the last row
-            Vall = self.updater.value(self.obs_buf[:T + 1 if boot else T].reshape(-1, D)).reshape(-1, N)
+            Vall = self.updater.value(self.net_obs[:T + 1 if boot else T].reshape(-1, D)).reshape(-1, N)
             V = Vall[:T].contiguous()
             last = Vall[T] if boot else None
             if trunc:
@@ -255,7 +279,7 @@ class PPOTrainer:
         the host waits once, at the end; rollout / update times come from events on the stream (wall clock on CPU)."""
         cfg = self.cfg
         cuda = self.device.type == "cuda"
-        T, N, D = cfg.rollout_len, self.env.N, self.env.D
+        T, N, D = cfg.rollout_len, self.env.N, self.net_dim
         t0 = time.time()
         if cuda:
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
@@ -265,7 +289,7 @@ class PPOTrainer:
             ev[1].record()
         t1 = time.time()
         m = self._rollout_metrics_dev()
-        stats = self.updater.update(self.obs_buf[:T].reshape(T * N, D), self.act_buf.reshape(T * N, 2),
+        stats = self.updater.update(self.net_obs[:T].reshape(T * N, D), self.act_buf.reshape(T * N, 2),
                                     self.logp_buf.reshape(T * N), self.rtg_buf.reshape(T * N),
                                     self.var_host if self.updater.fused else self.var,
                                     **({} if self._gae is None else dict(adv_raw=self._gae[0], V0=self._gae[1])))
@@ -391,7 +415,8 @@ class PPOTrainer:
         n_ep = int(cfg.eval_episodes)
         quota = -(-n_ep // env.N)
         t0 = time.time()
-        tab = env.evaluate_policy(self.updater.fp.flat, quota, policy="resmlp512" if self.updater.fused_resmlp512 else "mlp64x2")
+        tab = env.evaluate_policy(self.updater.fp.flat, quota, policy="resmlp512" if self.updater.fused_resmlp512 else "mlp64x2",
+                                  history=self.scan_history)
         cut = lambda x: x.reshape(-1)[:n_ep]
         fl = cut(tab.flags)
         sums = torch.stack([(fl & 1).sum().double(), ((fl >> 1) & 1).sum().double(), ((fl >> 2) & 1).sum().double(),
