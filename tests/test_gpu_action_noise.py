@@ -189,15 +189,19 @@ def test_act_step_counter(family, d):
 
 # ---------------------------------------------------------------------------------------------- persistent rollouts
 def launch_rollout(entry, n, beams, T, act_seed, env_id_base, step_base, leg):
-    """One persistent rollout (navsim_rollout_mlp64 / navsim_rollout_resmlp512) of T steps on stage_1 with a zero actor.
+    """One persistent rollout (navsim_rollout_mlp64 / navsim_rollout_mlp64_hist / navsim_rollout_resmlp512) of T steps on stage_1
+    with a zero actor (the scan-history entry: the 42-wide one, on the same 16-column buffers).
     Returns (act [T, n, 2], logp [T, n], info) as numpy / dict."""
     from navbot_ppo_amd._native import check, lib
-    from navbot_ppo_amd.env import VecEnv
+    from navbot_ppo_amd.env import HIST_DIM, VecEnv
     d = beams + 6
     env = VecEnv(n, map="stage_1", n_beams=beams, max_episode_steps=30, seed=3, env_id_base=env_id_base)
     try:
         sim, dev = env.sim, env.device
-        flat = _actor("mlp64" if entry == "navsim_rollout_mlp64" else "resmlp512", d, leg)
+        if entry == "navsim_rollout_mlp64_hist":
+            flat = _actor("mlp64", HIST_DIM, leg)
+        else:
+            flat = _actor("mlp64" if entry == "navsim_rollout_mlp64" else "resmlp512", d, leg)
         obs = torch.zeros((T + 1, n, d), device=dev)
         act, logp, rew = torch.full((T, n, 2), 7.0, device=dev), torch.zeros((T, n), device=dev), torch.zeros((T, n), device=dev)
         flags = [torch.zeros((T, n), dtype=torch.uint8, device=dev) for _ in range(3)]
@@ -216,7 +220,8 @@ ROLLOUT_SEED = 0x9E3779B97F4A7C15 * 5 + 0xAC7 & 0xFFFFFFFFFFFFFFFF    # the trai
 
 @pytest.mark.parametrize("env_id_base,step_base", [(0, 11), ((1 << 32) - 20, 0xFFFFFFFE)])
 @pytest.mark.parametrize("entry,n,beams,epb", [("navsim_rollout_mlp64", 37, 10, None), ("navsim_rollout_mlp64", 37, 36, None),
-                                               ("navsim_rollout_mlp64", 73, 10, "64"), ("navsim_rollout_resmlp512", 37, 10, None)])
+                                               ("navsim_rollout_mlp64", 73, 10, "64"), ("navsim_rollout_resmlp512", 37, 10, None),
+                                               ("navsim_rollout_mlp64_hist", 37, 10, None)])
 def test_persistent_rollout_draws_match_the_reference(entry, n, beams, epb, env_id_base, step_base, monkeypatch):
     """act_buf[t, i] of a persistent rollout is the reference draw of (act_seed, env_id_base + i, *step_base + t) for every t and i:
     the 16-env workgroups of both families (two full ones and a ragged one) and the forced 64-env shape (one full workgroup and a
@@ -240,23 +245,30 @@ def test_persistent_rollout_draws_match_the_reference(entry, n, beams, epb, env_
 
 
 # ---------------------------------------------------------------------------------------------- the trainer's three rollout paths
-@pytest.mark.parametrize("path", ["persistent", "graph", "eager"])
-@pytest.mark.parametrize("seed", [0, 0xDEADBEEF])
-@pytest.mark.parametrize("policy", ["mlp64x2", "resmlp512"])
+# (one list with the ids pytest gave the three stacked lists, policy-seed-path; scan_history exists on mlp64x2's persistent path only)
+TRAINER_CASES = [(po, s, pa) for pa in ("persistent", "graph", "eager") for s in (0, 0xDEADBEEF) for po in ("mlp64x2", "resmlp512")]  \
+    + [("mlp64x2", s, "persistent+history") for s in (0, 0xDEADBEEF)]
+
+
+@pytest.mark.parametrize("policy,seed,path", TRAINER_CASES, ids=[f"{po}-{s}-{pa}" for po, s, pa in TRAINER_CASES])
 def test_trainer_rollouts_advance_the_noise_counter(policy, seed, path):
     """PPOTrainer.rollout called three times: after call k the actions are the reference draws of (tr._act_seed, tr._env_id_base + i,
     (k - 1) T + t) -- on the persistent path, on the hipGraph of per-step launches (warm-up, capture and replay must each advance
     the counter exactly once per executed rollout: `_step_base += T` lives inside the captured graph) and on the eager per-step path.
-    No iteration repeats another's noise."""
+    No iteration repeats another's noise.  "persistent+history": PPOConfig.scan_history, navsim_rollout_mlp64_hist with the 42-wide
+    actor."""
+    history = path.endswith("+history")
+    path = path.split("+")[0]
     from navbot_ppo_amd import ppo
     from navbot_ppo_amd.env import VecEnv
     N, T = 48, 4
     env = VecEnv(N, map="stage_1", max_episode_steps=30, seed=1, env_id_base=0 if seed == 0 else (1 << 32) - 20)
     try:
         cfg = ppo.PPOConfig(rollout_len=T, max_episode_steps=30, n_updates_per_iteration=1, policy=policy, seed=seed, init_var=2 ** -8,
-                            persistent_rollout=path == "persistent", use_graph=path == "graph")
+                            persistent_rollout=path == "persistent", use_graph=path == "graph", scan_history=history)
         tr = ppo.PPOTrainer(env, cfg)
         assert tr.updater.fused and tr.uses_persistent_rollout is (path == "persistent")
+        assert tr.scan_history is history and (not history or tr.updater.fp.module_numel[0] == MLP64_PA(42) == 7042)
         assert tr._act_seed == (seed * 0x9E3779B97F4A7C15 + 0xAC7) & 0xFFFFFFFFFFFFFFFF and tr._env_id_base == env.sim.cfg.env_id_base
         tr.updater.fp.flat[:tr.updater.fp.module_numel[0]].zero_()   # the actor slice of the flat buffer: what the kernels read
         gids = [tr._env_id_base + i for i in range(N)]
@@ -276,6 +288,6 @@ def test_trainer_rollouts_advance_the_noise_counter(policy, seed, path):
         for i in range(3):
             for j in range(i + 1, 3):
                 assert differ(seen[i], seen[j])
-        _report(f"PPOTrainer.rollout {policy} {path} seed={seed:#x}", worst)
+        _report(f"PPOTrainer.rollout {policy} {path}{'+history' if history else ''} seed={seed:#x}", worst)
     finally:
         env.close()

@@ -8,7 +8,13 @@ of the two persistent kernels is written HERE from the per-step entry points: na
 The common world: 40 envs (two full 16-env workgroups and one of 8), 48 steps, episodes capped at 7 steps and -- set_state behind the
 reset -- started at step count env mod 7, so that time-outs fall on row 0, on row 1 and on consecutive rows of neighbouring envs; the
 robot starts 0.24 m in front of stage_2's inner wall with goals drawn in a 1 m box next to it (arrival threshold 0.4), so that
-collisions and arrivals end episodes one or two steps after a reset."""
+collisions and arrivals end episodes one or two steps after a reset.
+
+Beside the bit-for-bit comparisons one check stands on its own feet (4b): the rollout kernel's actions and log-probs against a float64
+actor on stack_rows_reference rows of the kernel's own observation buffer, with the draws of tests/_noise.py.  Placement (2b): an env's
+trajectory depends on its global id alone -- one handle against two shards, the id carry inside a workgroup, a grid beyond one round
+of workgroups.  The trainer (8): the update consumes exactly the rows the rule prescribes, under every update option."""
+import copy
 import ctypes as C
 import functools
 import math
@@ -17,6 +23,7 @@ import numpy as np
 import pytest
 import torch
 
+import _noise
 from _guards import run_both
 from navbot_ppo_amd import evaluate as ev, maps, nets, ppo
 from navbot_ppo_amd._native import lib
@@ -74,36 +81,53 @@ KINDS = {   # name -> (map, NavSim options, movers)
     "orbit4": ("stage_1", {}, "orbit4"),
     "orbit4-boxes": ("stage_2", {}, "orbit4"),
     "bank3-respawn": ("stage_2", dict(respawn_on_arrive=True), "bank3"),
+    # the kMovSens instantiations with the sensor options on, float16 rows under them, per-env maps, and the episode rules off
+    "orbit4-noise-gazebo": ("stage_1", dict(lidar_noise_sigma=0.02, lidar_below_min="gazebo"), "orbit4"),
+    "bank3-noise-f16": ("stage_2", dict(respawn_on_arrive=True, lidar_noise_sigma=0.02, obs_f16=True), "bank3"),
+    "noise-f16": ("stage_2", dict(lidar_noise_sigma=0.02, lidar_below_min="gazebo", obs_f16=True), None),
+    "per-env": ("stage_2:per-env", {}, None),     # every env its own jittered, re-ordered copy of the 128 segments
+    "no-reset": ("stage_2", dict(auto_reset=False), None),   # an ended env keeps its row: hist_next_entry's sm.obs branch on a cut
+    "no-reset-respawn": ("stage_2", dict(auto_reset=False, respawn_on_arrive=True), None),
+    "no-cap": ("stage_2", dict(max_episode_steps=0), None),  # collisions and arrivals alone end episodes
 }
 
 
-def make_sim(kind, n=N, seed=11):
-    m, kw, movers = KINDS[kind]
+def world_of(kind):
+    return {**WORLD, **KINDS[kind][1]}
+
+
+def make_sim(kind, n=N, seed=11, env_id_base=0):
+    """the world `kind` for the envs env_id_base .. env_id_base + n - 1: mover phases and tape ids follow the global env id"""
+    m, _, movers = KINDS[kind]
+    m, _, per_env = m.partition(":")
+    w = world_of(kind)
     if m == "house_base":
-        w = {k: v for k, v in WORLD.items() if k not in ("spawn", "goal_box")}
-        s = NavSim(n, seed=seed, device=DEV, **w, **kw)
+        w = {k: v for k, v in w.items() if k not in ("spawn", "goal_box")}
+        s = NavSim(n, seed=seed, env_id_base=env_id_base, device=DEV, **w)
         s.set_map(maps.by_name(m))
         s.set_spawn_sampler(*maps.spawn_tables("small_house", min_dist=0.3, max_dist=6.0))
     else:
-        s = NavSim(n, seed=seed, device=DEV, **WORLD, **kw)
+        s = NavSim(n, seed=seed, env_id_base=env_id_base, device=DEV, **w)
         rr, rs = maps.goal_rects(m)
         s.set_goal_rects(0, rr)
         s.set_goal_rects(1, rs)
-        s.set_map(maps.by_name(m))
+        seg = maps.by_name(m)
+        s.set_map(maps.replicate_per_env(seg, n, seed=0) if per_env else seg)
     if movers == "orbit4":
         tape = maps.movers_by_name("orbit4", 16)
-        s.set_movers(tape, maps.mover_phases(tape.shape[0], n, map_seed=2))
+        s.set_movers(tape, maps.mover_phases(tape.shape[0], n, map_seed=2, env_id_base=env_id_base))
     elif movers == "bank3":
         bank, periods, _ = _bank3()
-        ids = maps.mover_tape_ids(3, n, map_seed=2)
-        s.set_mover_bank(bank, periods, ids, maps.mover_bank_phases(periods[ids], map_seed=2))
+        ids = maps.mover_tape_ids(3, n, map_seed=2, env_id_base=env_id_base)
+        s.set_mover_bank(bank, periods, ids, maps.mover_bank_phases(periods[ids], map_seed=2, env_id_base=env_id_base))
     return s
 
 
 def start(sim, obs0):
-    """the start of every closed-loop case: a reset, then staggered step counts (env i has taken i mod 7 steps of its episode)"""
+    """the start of every closed-loop case: a reset, then staggered step counts (the env with global id g has taken g mod 7 steps of
+    its episode)"""
     sim.reset(obs0)
-    sim.set_state(ep_step=(np.arange(sim.N) % CAP).astype(np.int32))
+    sim.set_state(ep_step=((int(sim.cfg.env_id_base) + np.arange(sim.N)) % CAP).astype(np.int32))
 
 
 def _buffers(sim, n_steps):
@@ -156,8 +180,8 @@ def stepping_rollout(sim, flat, n_steps):
 
 
 @functools.lru_cache(maxsize=None)
-def _stepping_of(kind, n=N, n_steps=T):
-    s = make_sim(kind, n)
+def _stepping_of(kind, n=N, n_steps=T, env_id_base=0):
+    s = make_sim(kind, n, env_id_base=env_id_base)
     try:
         return stepping_rollout(s, _actor()[1], n_steps)
     finally:
@@ -165,8 +189,8 @@ def _stepping_of(kind, n=N, n_steps=T):
 
 
 @functools.lru_cache(maxsize=None)
-def _kernel_of(kind, n=N, n_steps=T):
-    s = make_sim(kind, n)
+def _kernel_of(kind, n=N, n_steps=T, env_id_base=0):
+    s = make_sim(kind, n, env_id_base=env_id_base)
     try:
         return kernel_rollout(s, _actor()[1], n_steps)
     finally:
@@ -180,6 +204,46 @@ def assert_cuts_cover_the_edges(ended):
     assert e[:2].any(), "no env has a cut on row 0 or 1"
     close = (e[:-1] & e[1:]).any() or (e[:-2] & e[2:]).any()
     assert close, "no env has two cuts less than three rows apart"
+
+
+def longest_run(ended):
+    """the longest run of consecutive rows with `ended` set, over all envs"""
+    e = ended.cpu().numpy() != 0
+    run, best = np.zeros(e.shape[1], np.int64), 0
+    for t in range(e.shape[0]):
+        run = np.where(e[t], run + 1, 0)
+        best = max(best, int(run.max()))
+    return best
+
+
+def cut_facts(b):
+    """the figures a closed-loop case prints: how often the stepping loop (the reference) cut, and where"""
+    e = b["ended"].cpu().numpy() != 0
+    close = (e[:-1] & e[1:]).sum() + (e[:-2] & e[2:]).sum() if e.shape[0] > 2 else 0
+    return (f"ended {int(e.sum())} done {int(b['done'].sum())} arrive {int(b['arrive'].sum())}; cuts on rows 0-1: {int(e[:2].sum())}, "
+            f"pairs of cuts less than three rows apart: {int(close)}, longest run of ended rows: {longest_run(b['ended'])}")
+
+
+def assert_the_world_exercises_the_cuts(kind, b):
+    """Conditions on the stepping loop's rollout, per world.  auto_reset: assert_cuts_cover_the_edges.  Without it an env that timed
+    out or collided keeps ending (its step count stays past the cap, it stays at the wall): some env must have three consecutive
+    ended rows, so that rows start an episode back to back from the row the step left.  Without a cap: a collision or an arrival
+    must cut, there is nothing else that does."""
+    w = world_of(kind)
+    if w["auto_reset"]:
+        assert_cuts_cover_the_edges(b["ended"])
+    else:
+        assert longest_run(b["ended"]) >= 3, "no env has three consecutive ended rows"
+    if w["max_episode_steps"] == 0:
+        assert int(((b["done"] != 0) | (b["arrive"] != 0)).sum()) >= 1, "no collision or arrival cut"
+
+
+def assert_same_rollout(got, got_state, want, want_state, what):
+    for f in FIELDS:
+        assert same(got[f], want[f]), f"{what}: {f} (first differing row "  \
+            f"{int((bits(got[f]).reshape(got[f].shape[0], -1) != bits(want[f]).reshape(want[f].shape[0], -1)).any(1).nonzero()[0])})"
+    for k in want_state:
+        assert np.array_equal(got_state[k], want_state[k]), f"{what}: state {k}"
 
 
 # ---------------------------------------------------------------- 1. navsim_stack_rows against the reference
@@ -214,22 +278,73 @@ def test_history_window_is_the_last_row_of_the_full_stack():
 
 
 # ---------------------------------------------------------------- 2. the rollout kernel against the stepping loop
-ROLLOUT_CASES = [(k, N, T) for k in KINDS] + [("plain", 5, T), ("plain", N, 1), ("bank3-respawn", 5, 3)]
+# 4117 envs: 258 workgroups -- more than the 256 CUs hold at once, so the grid runs in rounds -- the last one with 5 envs
+N_BIG, T_BIG = 4117, 12
+ROLLOUT_CASES = [(k, N, T) for k in KINDS] + [("plain", 5, T), ("plain", N, 1), ("bank3-respawn", 5, 3)]  \
+    + [("plain", N_BIG, T_BIG), ("orbit4", N_BIG, T_BIG)]
 
 
 @pytest.mark.parametrize("kind,n,n_steps", ROLLOUT_CASES, ids=lambda v: str(v))
 def test_rollout_hist_equals_the_stepping_loop(kind, n, n_steps):
     want, want_state = _stepping_of(kind, n, n_steps)
-    if n == N and n_steps == T:
-        assert_cuts_cover_the_edges(want["ended"])
+    print(f"{kind} N={n} T={n_steps}: {cut_facts(want)}")
+    if (n, n_steps) in ((N, T), (N_BIG, T_BIG)):
+        assert_the_world_exercises_the_cuts(kind, want)
     got, got_state = _kernel_of(kind, n, n_steps)
-    e = want["ended"]
-    print(f"{kind} N={n} T={n_steps}: ended {int(e.sum())} done {int(want['done'].sum())} arrive {int(want['arrive'].sum())}")
+    assert_same_rollout(got, got_state, want, want_state, kind)
+
+
+# ---------------------------------------------------------------- 2b. placement and keys
+SHARDS = ((0, 24), (24, 16))   # (env_id_base, envs): env 24 is lane 8 of workgroup 1 in the whole run, lane 0 of workgroup 0 in its shard
+
+
+@pytest.mark.parametrize("kind", ["plain", "bank3-noise-f16"])
+def test_rollout_hist_does_not_depend_on_the_placement(kind):
+    """One handle of 40 envs against two of 24 and 16 with env_id_base 0 and 24, the same seeds: an env's trajectory depends on its
+    global id alone, not on the lane or the workgroup that holds it (the `hist` block in LDS is indexed by the local env)."""
+    whole, whole_state = _kernel_of(kind)
+    parts = [_kernel_of(kind, n, T, base) for base, n in SHARDS]
+    assert not same(parts[1][0]["act"], whole["act"][:, :16])   # (the second shard is not the first 16 envs again)
     for f in FIELDS:
-        assert same(got[f], want[f]), f"{kind}: {f} (first differing row "  \
-            f"{int((bits(got[f]).reshape(got[f].shape[0], -1) != bits(want[f]).reshape(want[f].shape[0], -1)).any(1).nonzero()[0])})"
-    for k in want_state:
-        assert np.array_equal(got_state[k], want_state[k]), f"{kind}: state {k}"
+        assert same(torch.cat([p[0][f] for p in parts], dim=1), whole[f]), f"{kind}: {f}"
+    for k in whole_state:
+        assert np.array_equal(np.concatenate([p[1][k] for p in parts]), whole_state[k]), f"{kind}: state {k}"
+
+
+def test_rollout_hist_with_the_env_id_carry_inside_a_workgroup():
+    """env_id_base = 2^32 - 20: envs 20 .. 39 have counter word 1 = 1, the carry falls inside workgroup 1 (envs 16 .. 31)"""
+    base = (1 << 32) - 20
+    want, want_state = _stepping_of("plain", N, T, base)
+    print(f"plain env_id_base=2^32-20: {cut_facts(want)}")
+    assert_the_world_exercises_the_cuts("plain", want)
+    got, got_state = _kernel_of("plain", N, T, base)
+    assert_same_rollout(got, got_state, want, want_state, "plain, env_id_base = 2^32 - 20")
+    assert not same(got["act"], _kernel_of("plain")[0]["act"])
+
+
+def test_rollout_hist_of_zero_steps_touches_nothing():
+    s = make_sim("plain")
+    try:
+        b = _buffers(s, T)
+        for f in FIELDS:
+            b[f].fill_(7)
+        start(s, b["obs"][0])
+        torch.cuda.synchronize()
+        before, state = {f: b[f].clone() for f in FIELDS}, s.get_state()
+        var = torch.tensor(VAR, device=DEV)
+        base = torch.tensor(STEP_BASE, dtype=torch.int32, device=DEV)
+        rc = lib().navsim_rollout_mlp64_hist(s._h, P(_actor()[1]), P(b["obs"]), P(b["act"]), P(b["logp"]), P(b["reward"]), P(b["done"]),
+                                             P(b["arrive"]), P(b["ended"]), P(b["ep_return"]), P(b["ep_length"]), P(b["ep_path"]), P(var),
+                                             ACT_SEED, P(base), 0, _st())
+        assert rc == 0, lib().navsim_last_error().decode()
+        torch.cuda.synchronize()
+        after = s.get_state()
+    finally:
+        s.close()
+    for f in FIELDS:
+        assert same(b[f], before[f]), f
+    for k in state:
+        assert np.array_equal(after[k], state[k]), k
 
 
 # ---------------------------------------------------------------- 3. the env side is untouched
@@ -315,6 +430,81 @@ def test_the_two_older_frames_are_read():
     assert float((x["act"][2][keep] - y["act"][2][keep]).abs().max()) > 1e-3
 
 
+# ---------------------------------------------------------------- 4b. the rollout kernel against a float64 actor, closed loop
+REL = 16 * 2.0 ** -24       # a draw against the float64 Philox / Box-Muller reference, per max(1, rad): test_gpu_action_noise.REL
+LOG_2PI = 1.8378770664093453
+
+
+@functools.lru_cache(maxsize=None)
+def _host_actors():
+    """the actor of the closed-loop cases as torch's float32 module on the host, and its float64 copy"""
+    a = copy.deepcopy(_actor()[0]).cpu()
+    return a, copy.deepcopy(a).double()
+
+
+def closed_loop_ratios(kind, swap_older_frames=False):
+    """Every action and log-prob of the cached kernel rollout `kind` against a reference that runs no kernel of the project: the rows
+    are stack_rows_reference of the kernel's own obs / ended buffers, the mean is the float64 actor on them (float16 rows widen
+    exactly), the draws are tests/_noise.py's.  expected action = clamp(mean64 + sqrt(var) e), var the float32 the kernel is handed.
+    Bound per entry, from what the project already asserts elsewhere:
+        |mean32 - mean64|              torch's float32 actor against its float64 copy on the same rows: a reference-only quantity
+      + 1e-5 |mean64| + 2e-6           navppo_mlp64_act against torch's float32 actor (test_fused_act_and_value_on_wide_and_half_rows)
+      + sqrt(var) REL max(1, rad)      the draws (test_gpu_action_noise.REL)
+    and the clamp is 1-Lipschitz, so no entry is left out.  logp: the float64 formula on the kernel's own action and mean64 at
+    check_logp's rtol 1e-4, atol 2e-5, plus what the mean's bound m moves the formula by: sum_j (|a_j - mean_j| m_j + m_j^2 / 2) / var.
+    Returns (error / bound of the actions [T, N, 2], of logp [T, N], steps into the episode of every row [T, N])."""
+    b, _ = _kernel_of(kind)
+    obs, ended = b["obs"].cpu().numpy(), b["ended"].cpu().numpy()
+    rows = stack_rows_reference(obs, ended)[:T]
+    if swap_older_frames:
+        sw = rows.copy()
+        sw[..., 16:26], sw[..., 26:36] = rows[..., 26:36], rows[..., 16:26]
+        rows = sw
+    a32, a64 = _host_actors()
+    x = torch.from_numpy(rows.astype(np.float32).reshape(T * N, HIST_DIM))
+    with torch.no_grad():
+        m32, m64 = a32(x).double().numpy(), a64(x.double()).numpy()
+    var = float(np.float32(VAR))
+    sd = math.sqrt(var)
+    e, rad = np.empty((T, N, 2)), np.empty((T, N))
+    for t in range(T):
+        _, u1, _, e[t, :, 0], e[t, :, 1] = _noise.action_noise(ACT_SEED, list(range(N)), STEP_BASE + t)
+        rad[t] = _noise.rad_of(u1)
+    raw = m64 + sd * e.reshape(T * N, 2)
+    want = np.stack([raw[:, 0].clip(0.0, 1.0), raw[:, 1].clip(-1.0, 1.0)], 1)
+    m_bound = np.abs(m32 - m64) + 1e-5 * np.abs(m64) + 2e-6
+    bound = m_bound + sd * REL * np.maximum(1.0, rad).reshape(T * N, 1)
+    act = b["act"].cpu().numpy().astype(np.float64).reshape(T * N, 2)
+    r_act = np.abs(act - want) / bound
+    lp_want = -0.5 * ((act - m64) ** 2).sum(1) / var - LOG_2PI - math.log(var)
+    lp_bound = 2e-5 + 1e-4 * np.abs(lp_want) + ((np.abs(act - m64) * m_bound + 0.5 * m_bound ** 2).sum(1)) / var
+    r_lp = np.abs(b["logp"].cpu().numpy().astype(np.float64).reshape(-1) - lp_want) / lp_bound
+    first = np.zeros(N, np.int64)   # r(t) of stack_rows_reference
+    depth = np.empty((T, N), np.int64)
+    for t in range(T):
+        if t > 0:
+            first = np.where(ended[t - 1] != 0, t, first)
+        depth[t] = t - first
+    return r_act.reshape(T, N, 2), r_lp.reshape(T, N), depth
+
+
+@pytest.mark.parametrize("kind", ["plain", "f16", "bank3-respawn"])
+def test_rollout_hist_against_a_float64_actor_on_reference_rows(kind):
+    r_act, r_lp, depth = closed_loop_ratios(kind)
+    print(f"{kind}: worst error / bound: actions {r_act.max():.3f}, logp {r_lp.max():.3f}")
+    assert (r_act <= 1.0).all(), (kind, float(r_act.max()), np.argwhere(r_act > 1.0)[:4].tolist())
+    assert (r_lp <= 1.0).all(), (kind, float(r_lp.max()), np.argwhere(r_lp > 1.0)[:4].tolist())
+    # the check sees the order of the two older frames: with them swapped in the reference rows it fails on most rows on which
+    # they can differ (rows at least two steps into an episode; on every other row both are the same scan)
+    s_act, _, _ = closed_loop_ratios(kind, swap_older_frames=True)
+    deep = depth >= 2
+    failed = (s_act > 1.0).any(-1)
+    print(f"{kind}: rows at least two steps into an episode {int(deep.sum())}, of which the swapped check fails {int((failed & deep).sum())}")
+    assert int(deep.sum()) >= N
+    assert int((failed & deep).sum()) > int(deep.sum()) // 2
+    assert not failed[depth == 0].any()   # (an episode's first row holds its own scan three times)
+
+
 # ---------------------------------------------------------------- 5. the evaluation kernel
 def reference_table_hist(sim, flat, quota, n_steps, fill=77):
     """evaluate()'s quota rule (tests/test_gpu_evaluate.reference_table) over the stepping loop with zero noise"""
@@ -368,7 +558,7 @@ def kernel_table_hist(sim, flat, quota, n_steps, fill=77):
     return {k: v.cpu().numpy() for k, v in out.items()}
 
 
-@pytest.mark.parametrize("kind", ["plain", "bank3-respawn", "f16", "stage_1"])
+@pytest.mark.parametrize("kind", ["plain", "bank3-respawn", "f16", "stage_1", "orbit4-noise-gazebo", "bank3-noise-f16", "noise-f16", "per-env"])
 def test_evaluate_hist_equals_the_stepping_loop(kind):
     quota = 3
     flat = _actor()[1]
@@ -386,6 +576,46 @@ def test_evaluate_hist_equals_the_stepping_loop(kind):
         np.testing.assert_array_equal(got[k], want[k], err_msg=f"{kind}: {k}")
     for k in ("ret", "path"):
         np.testing.assert_array_equal(got[k].view(np.uint32), want[k].view(np.uint32), err_msg=f"{kind}: {k}")
+
+
+@pytest.mark.parametrize("kind", ["plain", "bank3-noise-f16"])
+def test_evaluate_hist_does_not_depend_on_the_placement(kind):
+    """test_rollout_hist_does_not_depend_on_the_placement through navsim_evaluate_mlp64_hist: every env records its first three
+    episodes whichever workgroup it plays in (`steps` is per workgroup and left out)"""
+    quota = 3
+    flat = _actor()[1]
+    tabs = []
+    for base, n in ((0, N),) + SHARDS:
+        s = make_sim(kind, n, seed=21, env_id_base=base)
+        try:
+            tabs.append(kernel_table_hist(s, flat, quota, quota * CAP))
+        finally:
+            s.close()
+    whole, parts = tabs[0], tabs[1:]
+    assert (whole["count"] == quota).all() and len(set(np.unique(whole["flags"]).tolist())) >= 2
+    for k in ("count", "flags", "length", "ret", "path"):
+        got = np.concatenate([p[k] for p in parts], axis=-1)
+        np.testing.assert_array_equal(got.view(np.uint32) if got.dtype == np.float32 else got,
+                                      whole[k].view(np.uint32) if got.dtype == np.float32 else whole[k], err_msg=f"{kind}: {k}")
+    assert not np.array_equal(parts[1]["ret"], whole["ret"][:, :16])
+
+
+def test_evaluate_hist_refuses_more_than_4096_envs():
+    n, fill = 4097, 77
+    s = make_sim("plain", n)
+    try:
+        obs0 = torch.empty((n, 16), device=DEV)
+        s.reset(obs0)
+        tab = [torch.full((1, n), fill, dtype=dt, device=DEV) for dt in (torch.uint8, torch.int32, torch.float32, torch.float32)]
+        cnt = torch.full((n,), fill, dtype=torch.int32, device=DEV)
+        stp = torch.full(((n + 15) // 16,), fill, dtype=torch.int32, device=DEV)
+        rc = lib().navsim_evaluate_mlp64_hist(s._h, P(_actor()[1]), P(obs0), 1, CAP, *[P(x) for x in tab], P(cnt), P(stp), _st())
+        assert rc == -1 and b"navsim_evaluate_mlp64_hist" in lib().navsim_last_error() and b"4096" in lib().navsim_last_error()
+        torch.cuda.synchronize()
+        for x in tab + [cnt, stp]:
+            assert bool((x == fill).all())
+    finally:
+        s.close()
 
 
 # ---------------------------------------------------------------- 6. refusals
@@ -454,7 +684,7 @@ def test_refusals_launch_nothing():
 
 
 # ---------------------------------------------------------------- 7. guarded allocations
-@pytest.mark.parametrize("kind", ["plain", "f16", "bank3-respawn"])
+@pytest.mark.parametrize("kind", ["plain", "f16", "bank3-respawn", "orbit4-noise-gazebo", "bank3-noise-f16"])
 def test_rollout_hist_outputs_guarded(kind):
     """every argument of navsim_rollout_mlp64_hist inside a guarded allocation, at a 256-byte boundary and at the minimum alignment:
     guards intact, every row written, outputs identical between the placements and equal to the plain run's"""
@@ -489,7 +719,7 @@ def test_rollout_hist_outputs_guarded(kind):
         assert same(got[f], want[f]), f
 
 
-@pytest.mark.parametrize("kind", ["plain", "f16", "bank3-respawn"])
+@pytest.mark.parametrize("kind", ["plain", "f16", "bank3-respawn", "orbit4-noise-gazebo", "bank3-noise-f16"])
 def test_evaluate_hist_outputs_guarded(kind):
     flat = _actor()[1]
     quota = 2
@@ -571,3 +801,69 @@ def test_trainer_with_scan_history(tmp_path):
     assert sp["episodes"] == sl["episodes"] == 8
     assert [r[1:5] for r in sp["rows"]] == [r[1:5] for r in sl["rows"]]     # success, collision, timeout, length
     np.testing.assert_allclose([r[5] for r in sp["rows"]], [r[5] for r in sl["rows"]], rtol=1e-4, atol=1e-3)
+
+
+UPDATE_CASES = {   # name -> (PPOConfig options, VecEnv options)
+    "defaults": ({}, {}),                                  # bf16x3 on the prepared pieces of the batch
+    "f32": (dict(update_arith="f32"), {}),
+    "minibatch": (dict(minibatch_size=96, minibatch_shuffle="epoch", max_grad_norm=0.5), {}),
+    "f16-returns": (dict(bootstrap_truncated=True, gae_lambda=0.95, norm_reward=True), dict(obs_f16=True)),
+    "adaptive-lr": (dict(lr_schedule="adaptive"), {}),
+    "target-kl": (dict(target_kl=0.01), {}),
+}
+
+
+@pytest.mark.parametrize("case", list(UPDATE_CASES))
+def test_the_update_reads_the_rows_the_rule_prescribes(case):
+    """Two trainers built alike.  A runs iteration() twice.  B runs it once, then rollout() -- the same buffers as A's second
+    rollout, bit for bit -- and then the update as iteration() calls it, but on a freshly allocated tensor holding
+    stack_rows_reference of its obs_buf / ended_buf.  The fused paths are deterministic, so parameters and Adam's moments come out
+    bit-identical if and only if A's second update consumed exactly those rows -- not the first iteration's, which lie behind the
+    same pointer, shape and version counter (hist_buf[:T] is a view of a buffer the kernels rewrite every iteration)."""
+    cfg_kw, env_kw = UPDATE_CASES[case]
+    n, t_len = 64, 32
+    trainers = []
+    for _ in range(2):
+        env = VecEnv(n, map="stage_1", max_episode_steps=20, seed=1, movers="random:4", **env_kw)
+        cfg = ppo.PPOConfig(policy="mlp64x2", scan_history=True, rollout_len=t_len, max_episode_steps=20, n_updates_per_iteration=3, seed=2,
+                            **cfg_kw)
+        trainers.append(ppo.PPOTrainer(env, cfg))
+    A, B = trainers
+    names = ("obs_buf", "act_buf", "logp_buf", "ended_buf", "rtg_buf")
+    try:
+        assert A.scan_history and A.updater.obs_dim == HIST_DIM and same(A.updater.fp.flat, B.updater.fp.flat)
+        A.iteration()
+        snap = {}
+        rollout = A.rollout
+
+        def recording_rollout():
+            rollout()
+            snap.update({k: getattr(A, k).clone() for k in names})
+            snap["flat"] = A.updater.fp.flat.clone()
+
+        A.rollout = recording_rollout
+        A.iteration()
+        B.iteration()
+        B.rollout()
+        torch.cuda.synchronize()
+        for k in names:
+            assert same(getattr(B, k), snap[k]), f"{case}: {k} of the second rollout"
+        assert same(B.updater.fp.flat, snap["flat"])
+        n_ends = int(B.ended_buf.sum())
+        print(f"{case}: episode ends in the second rollout: {n_ends}")
+        assert n_ends >= n   # the cuts matter: rows that start an episode all over the batch
+        rows = torch.from_numpy(stack_rows_reference(B.obs_buf.cpu().numpy(), B.ended_buf.cpu().numpy()))[:t_len]
+        rows = rows.reshape(t_len * n, HIST_DIM).to(DEV)
+        assert rows.data_ptr() != B.hist_buf.data_ptr() and rows.dtype == B.hist_buf.dtype
+        B.updater.update(rows, B.act_buf.reshape(t_len * n, 2), B.logp_buf.reshape(t_len * n), B.rtg_buf.reshape(t_len * n), B.var_host,
+                         **({} if B._gae is None else dict(adv_raw=B._gae[0], V0=B._gae[1])))
+        torch.cuda.synchronize()
+        assert (B._gae is not None) == (case == "f16-returns")
+        assert not same(A.updater.fp.flat, snap["flat"])   # the update moved the parameters
+        assert same(A.updater.fp.flat, B.updater.fp.flat), f"{case}: parameters"
+        assert same(A.updater._adam_m, B.updater._adam_m), f"{case}: Adam's first moment"
+        assert same(A.updater._adam_v, B.updater._adam_v), f"{case}: Adam's second moment"
+        assert A.updater._adam_t == B.updater._adam_t > 0
+    finally:
+        A.env.close()
+        B.env.close()

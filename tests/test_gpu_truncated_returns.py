@@ -138,22 +138,37 @@ def _trainer(policy, **cfg):
     return ppo.PPOTrainer(env, ppo.PPOConfig(rollout_len=48, max_episode_steps=20, n_updates_per_iteration=1, policy=policy, seed=2, **cfg))
 
 
+def assert_net_rows_are_the_rule(tr):
+    """PPOConfig.scan_history: the rows the nets read -- all T + 1 of them, the last one bootstraps the batch end -- are
+    stack_rows_reference of the trainer's own obs_buf / ended_buf, bit for bit; without it they are obs_buf itself"""
+    if not tr.scan_history:
+        assert tr.net_obs is tr.obs_buf and tr.net_dim == tr.env.D
+        return
+    from navbot_ppo_amd.env import HIST_DIM, stack_rows_reference
+    want = torch.from_numpy(stack_rows_reference(tr.obs_buf.cpu().numpy(), tr.ended_buf.cpu().numpy()))
+    assert tr.net_obs is tr.hist_buf and tr.net_dim == HIST_DIM and tr.hist_buf.shape == want.shape
+    assert tr.hist_buf.dtype == want.dtype and torch.equal(tr.hist_buf.cpu().view(torch.uint8), want.view(torch.uint8))
+
+
+# (scan_history rides on the policy: it exists for mlp64x2 only)
 @pytest.mark.parametrize("norm_reward", [False, True])
 @pytest.mark.parametrize("gae_lambda", [None, 0.95])
-@pytest.mark.parametrize("policy", ["mlp64x2", "resmlp512"])
-def test_trainer_targets_are_the_mirror_of_its_own_buffers(policy, gae_lambda, norm_reward):
+@pytest.mark.parametrize("policy,scan_history", [("mlp64x2", False), ("resmlp512", False), ("mlp64x2", True)],
+                         ids=["mlp64x2", "resmlp512", "mlp64x2+history"])
+def test_trainer_targets_are_the_mirror_of_its_own_buffers(policy, scan_history, gae_lambda, norm_reward):
     """A fresh policy drives at most 0.25 m/s x 0.2 s x 20 steps = 1 m per episode, so nearly every episode of the 20-step limit is cut
     by it (the CPU oracle counts 127-128 truncated rows in 64 x 48 for random actions): two time-outs per env, and the batch end cuts
-    the third episode of every env."""
+    the third episode of every env.  With scan_history V is taken on the T + 1 history rows."""
     T, N = 48, 64
-    tr = _trainer(policy, bootstrap_truncated=True, gae_lambda=gae_lambda, norm_reward=norm_reward)
+    tr = _trainer(policy, bootstrap_truncated=True, gae_lambda=gae_lambda, norm_reward=norm_reward, scan_history=scan_history)
     tr.rollout()
     ended, done, arrive = (t.cpu().numpy() for t in (tr.ended_buf, tr.done_buf, tr.arrive_buf))
     n_trunc = int(truncated_rows(ended, done, arrive).sum())
     assert n_trunc >= N, n_trunc                      # what keeps the test honest: the rule is exercised ...
     assert int((ended[T - 1] == 0).sum()) >= 1        # ... and so is the bootstrap of the batch end
     rew = tr.rew_scaled_buf if norm_reward else tr.rew_buf
-    Vall = tr.updater.value(tr.obs_buf.reshape(-1, tr.env.D)).reshape(T + 1, N)
+    assert_net_rows_are_the_rule(tr)
+    Vall = tr.updater.value(tr.net_obs.reshape(-1, tr.net_dim)).reshape(T + 1, N)
     want_adv, want_ret = truncated_returns_reference(rew.cpu().numpy(), ended, done, arrive, Vall[:T].cpu().numpy(), tr.cfg.gamma,
                                                      1.0 if gae_lambda is None else gae_lambda, last_value=Vall[T].cpu().numpy())
     want_ret = torch.from_numpy(want_ret).to(DEV)
@@ -170,17 +185,19 @@ def test_trainer_targets_are_the_mirror_of_its_own_buffers(policy, gae_lambda, n
 
 
 @pytest.mark.parametrize("norm_reward", [False, True])
-@pytest.mark.parametrize("gae_lambda", [None, 0.95])
-def test_trainer_with_the_option_off_is_todays(gae_lambda, norm_reward):
+@pytest.mark.parametrize("gae_lambda,scan_history", [(None, False), (0.95, False), (None, True), (0.95, True)],
+                         ids=["None", "0.95", "None+history", "0.95+history"])
+def test_trainer_with_the_option_off_is_todays(gae_lambda, scan_history, norm_reward):
     T, N = 48, 64
-    tr = _trainer("mlp64x2", gae_lambda=gae_lambda, norm_reward=norm_reward)
+    tr = _trainer("mlp64x2", gae_lambda=gae_lambda, norm_reward=norm_reward, scan_history=scan_history)
     assert tr.cfg.bootstrap_truncated is False
     tr.rollout()
     rew = tr.rew_scaled_buf if norm_reward else tr.rew_buf
+    assert_net_rows_are_the_rule(tr)
     if gae_lambda is None:
         assert tr._gae is None and torch.equal(tr.rtg_buf, rtg_scan(rew, tr.ended_buf, tr.cfg.gamma))
     else:
-        Vall = tr.updater.value(tr.obs_buf.reshape(-1, tr.env.D)).reshape(T + 1, N)
+        Vall = tr.updater.value(tr.net_obs.reshape(-1, tr.net_dim)).reshape(T + 1, N)
         adv, ret = gae_scan(rew, tr.ended_buf, Vall[:T].contiguous(), tr.cfg.gamma, gae_lambda, last_value=Vall[T])
         assert torch.equal(tr.rtg_buf, ret) and torch.equal(tr._gae[0], adv.reshape(-1))
     lg = tr.iteration()
