@@ -12,6 +12,10 @@ SRCS = [os.path.join(HERE, "csrc", f) for f in ("navsim.hip", "ppo_mlp64.hip", "
                                                    "ppo_reward_norm.hip")]   # navppo_return_moments, navppo_reward_scale (norm_reward)
 HDRS = ["navsim.h", "navppo.h"]
 INC = os.path.join(REPO, "include")
+# what every object depends on besides its own source: the public headers, the csrc headers and the two sources the *_kl twins include
+HDR_DEPS = [os.path.join(INC, h) for h in HDRS] + [os.path.join(HERE, "csrc", h) for h in (
+    "navsim_select.h", "mlp64_policy.h", "navppo_internal.h", "resmlp_policy.h", "bf16x3.h", "ppo_mlp64_x3s.h", "ppo_resmlp512_bwd2s.h",
+    "ppo_mlp64.hip", "ppo_resmlp512.hip")]
 LIB = os.path.join(HERE, "libnavsim.so")
 
 # -ffp-contract=off: the arithmetic contract writes every fused multiply-add explicitly
@@ -32,7 +36,7 @@ def needs_build():
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = SRCS + [os.path.join(INC, h) for h in HDRS] + [os.path.join(HERE, "csrc", h) for h in ("mlp64_policy.h", "navppo_internal.h", "resmlp_policy.h", "bf16x3.h", "ppo_mlp64_x3s.h", "ppo_resmlp512_bwd2s.h", "ppo_mlp64.hip", "ppo_resmlp512.hip")]
+    deps = SRCS + HDR_DEPS
     return any(os.path.getmtime(p) > t for p in deps)
 
 
@@ -96,7 +100,6 @@ def build_native(force=False, verbose=False, navsim_src=None, out=None, extra=()
     procs, objs = [], []
     srcs = SRCS if navsim_src is None else [navsim_src] + SRCS[1:]
     lib_out = LIB if out is None else out
-    hdrs = [os.path.join(INC, h) for h in HDRS] + [os.path.join(HERE, "csrc", h) for h in ("mlp64_policy.h", "navppo_internal.h", "resmlp_policy.h", "bf16x3.h", "ppo_mlp64_x3s.h", "ppo_resmlp512_bwd2s.h", "ppo_mlp64.hip", "ppo_resmlp512.hip")]
     for k, src in enumerate(srcs):   # the sources compile side by side
         obj = os.path.join(objdir, os.path.basename(SRCS[k]) + ".o")
         per_src = per_source_flags(os.path.basename(SRCS[k]))
@@ -106,7 +109,7 @@ def build_native(force=False, verbose=False, navsim_src=None, out=None, extra=()
         # incremental: an object newer than its source, the headers and this file, built by the same command line, is kept
         stamp = obj + ".cmd"
         fresh = (not force and os.path.exists(obj) and os.path.exists(stamp) and open(stamp).read() == " ".join(cmd) and
-                 all(os.path.getmtime(d) < os.path.getmtime(obj) for d in [src, os.path.abspath(__file__)] + hdrs))
+                 all(os.path.getmtime(d) < os.path.getmtime(obj) for d in [src, os.path.abspath(__file__)] + HDR_DEPS))
         if fresh:
             continue
         if verbose:

@@ -2481,7 +2481,7 @@ __global__ __launch_bounds__(64 * 8) void steps_mov_kernel(SeqKArgs) {
 
 // ---------------------------------------------------------------- the persistent rollout at the big shard shapes
 // navsim_rollout_mlp64 for shards beyond 4096 envs: steps_kernel's workgroup (64 envs on 16 waves, one per CU, the cast at its
-// vector-issue bound, the cast variants of launch_step) with a policy phase in front of every step -- the closed-loop form of the
+// vector-issue bound, the cast variants of the step kernel) with a policy phase in front of every step -- the closed-loop form of the
 // tape kernel: the action of step t is PPO.get_action (ppo.py:673-706) of the observation tile step t - 1 left in LDS.
 // The phase is bound by the SIMDs' MFMA pipes (64 envs x 10.2 kFLOP at the f32 MFMA rate of 64 FLOP per cycle and SIMD = 2560
 // cycles), so each of the EPB / 16 policy tiles of 16 envs belongs to ONE wave -- the waves of a workgroup land on the SIMDs round
@@ -2987,204 +2987,191 @@ __global__ void gae_trunc_kernel_generic(const float* __restrict__ rew, const ui
 }  // namespace
 
 // ==================================================================== host side / C ABI
+#include "navsim_select.h"   // which instantiation runs for a handle: the rule, its thresholds and the measurements behind them
+namespace sel = navsim_select;
+static_assert(kMovSens == sel::kMovTwinsSens, "the 16-env mover twins are built in the form the rule picks");
+
+// A hipMalloc allocation and its owner (move-only): freed by reset(), by the next alloc() and with the owner
+template <class T>
+class DevBuf {
+    T* p_ = nullptr;
+
+public:
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+    ~DevBuf() { (void)reset(); }
+    hipError_t alloc(size_t n) {   // n elements
+        (void)reset();
+        return hipMalloc(&p_, sizeof(T) * n);
+    }
+    hipError_t reset() {
+        const hipError_t e = hipFree(p_);
+        p_ = nullptr;
+        return e;
+    }
+    T* get() const { return p_; }
+};
+
 struct navsim {
     navsim_cfg cfg;
     Params P;
-    void* state_block = nullptr;   // one allocation for all per-env state
-    double* beam_cs_dev = nullptr;
-    Rects* rects_dev = nullptr;
+    DevBuf<unsigned char> state_block;   // one allocation for all per-env state
+    DevBuf<double> beam_cs_dev;
+    DevBuf<Rects> rects_dev;
     Rects rects_host;
-    float4* seg_sorted_dev = nullptr;   // shared maps of 65..4096 segments: the handle's own Morton-ordered copy
-    float4* tile_box_dev = nullptr;
-    float* spawn_scan_dev = nullptr;
-    float* spawn_obs_dev = nullptr;
-    double* starts_dev = nullptr;   // [K][3]
-    double* starts_sc_dev = nullptr;  // [K]
-    double* goals_dev = nullptr;    // [G][2]
-    const float* seg_dev = nullptr;
-    int32_t* mov_phase0_dev = nullptr;   // navsim_set_movers: the handle's copy of the per-env phase offsets
-    uint2* mov_bp_dev = nullptr;         // navsim_set_mover_bank: (base row, period), the tape id and the tapes' goal rectangles
-    int32_t* mov_tid_dev = nullptr;
-    double* mov_rects_dev = nullptr;
+    DevBuf<float4> seg_sorted_dev;   // shared maps of 65..4096 segments: the handle's own Morton-ordered copy
+    DevBuf<float4> tile_box_dev;
+    DevBuf<float> spawn_scan_dev;
+    DevBuf<float> spawn_obs_dev;
+    DevBuf<double> starts_dev;   // [K][3]
+    DevBuf<double> starts_sc_dev;  // [K]
+    DevBuf<double> goals_dev;    // [G][2]
+    DevBuf<int32_t> mov_phase0_dev;   // navsim_set_movers: the handle's copy of the per-env phase offsets
+    DevBuf<uint2> mov_bp_dev;         // navsim_set_mover_bank: (base row, period), the tape id and the tapes' goal rectangles
+    DevBuf<int32_t> mov_tid_dev;
+    DevBuf<double> mov_rects_dev;
     bool has_map = false;
-    // kernel-shape overrides of THIS handle (navsim_set_shape; tests and A/B timing): envs per workgroup, 0 = the rule of pick_epb
-    // below; pair_cast false = 64-segment passes for every map
+    // kernel-shape overrides of THIS handle (navsim_set_shape; tests and A/B timing): envs per workgroup, 0 = the rule of
+    // navsim_select::pick_epb; pair_cast false = 64-segment passes for every map
     int force_epb = 0;
     bool pair_cast = true;
     int pair_cast_request = -1;   // what navsim_set_shape was given (-1 = the rule): reported by navsim_get_info
 };
 
-// Envs per workgroup.  Bigger workgroups make the float64 lanes of the geometry / rules phases denser (a wave instruction
-// costs the same with 16 or 64 active lanes) and start fewer workgroups, but need N / EPB >= the number of CUs to fill the
-// chip: measured (tools/time_step.py) 16384 envs: 18.5 / 16.7 / 15.9 us with 16 / 32 / 64; 8192: 69.8 / 64.8 / 73.9; 4096: 8.9 / 8.6 / 9.8.
-// Round 4 swept shard size x shape x beam count on shared maps (tools/epb_sweep.py, profiles/r04_epb_sweep.txt), us per step,
-// shapes 8 / 16 / 32:
-//   36 beams, tape form    1024 envs 6.3 / 10.0 / 9.9   2048: 6.5 / 10.1 / 9.8   4096: 7.0 / 10.2 / 9.9   8192: 13.0 / 11.0 / 10.0
-//   36 beams, one launch   1024: 10.5 / 12.9 / 12.7     2048: 11.0 / 13.1 / 12.9  4096: 11.9 / 13.5 / 13.1  8192: 13.9 / 14.6 / 13.5
-//   10 beams, tape form    1024:  4.45 / 5.06 / 4.72    2048: 4.49 / 5.09 / 4.70  4096: 4.94 / 5.27 / 4.81
-//   10 beams, one launch   1024:  8.6 / 7.6 / 7.2       2048: 8.8 / 7.8 / 7.3     4096: 9.2 / 8.0 / 7.6
-// With 36 beams a workgroup's chain is long (36 beam directions per env in the pose phase, stage B per beam group) and eight envs
-// on four waves, two to four workgroups per CU, overlap their chains: up to 4096 envs the 8-env shape; small 10-beam shards take it
-// in the tape form only (a launch per step pays for 4 x as many workgroups to start) and the 32-env shape otherwise.
-// The 36-beam 8-env shape then went from four to eight waves (one env's beam groups per wave; min_waves_per_simd keeps two
-// workgroups on a CU): tape form 1024 / 2048 / 4096 envs 6.3 / 6.5 / 7.0 -> 5.2 / 5.4 / 6.3 us per step, a launch per step
-// unchanged (10.4 / 11.0 / 12.0); with 10 beams eight waves gain 2-3 % at 1024-2048 envs and nothing at 4096: four stay.
-// The same on the shared 2048-segment house map (tile boxes; EPB_MAP=house): 8 / 32 envs per workgroup, tape form 1024-4096 envs
-// 18.5-20.2 / 29.1-29.8 us per step, 8192: 25.0 / 30.7; one launch per step 1024-4096: 20.8-22.6 / 31.3-32.2, 8192: 38.2 / 32.6;
-// 16384 envs: the 64-env shape (35 / 37 us) ahead of every smaller one.
-// Per-env stage_2 maps (EPB_MAP=per_env), 8 / 32: tape 1024-2048 envs 5.6 / 7.2, 4096: 6.2 / 7.3, 8192: 11.5 / 7.7; a launch per step 9.2-10.2 / 9.2-9.4.
-// Waves of the 8-env workgroup.  Eight (one env per wave) halve each wave's cast chain: on the house map (tile boxes) the tape runs
-// 18.4 / 18.7 / 20.2 -> 12.1 / 12.6 / 15.0 us per step at 1024 / 2048 / 4096 envs and a launch per step 20.7 / 21.2 / 22.4 -> 14.8 /
-// 15.4 / 18.0; per-env stage_2 maps as a tape 5.5 / 5.6 / 6.1 -> 4.6 / 4.7 / 5.6; 36 beams see the comment above.  Two such
-// workgroups fit a CU (128 VGPRs each: min_waves_per_simd), so beyond 4096 envs the shape runs in rounds and is not chosen.
-// The 16-env workgroup went from four to eight waves the same way (two envs per wave; us per step, the rule before / 16 envs on eight waves):
-//   stage_1, 10 beams, tape form   1024: 4.30 / 3.90   2048: 4.36 / 3.91   4096: 4.80 / 4.09   8192: 4.97 / 4.97   (a launch per step: equal)
-//   per-env maps, a launch per step 1024: 9.13 / 7.86   2048: 9.24 / 8.18   4096: 9.42 / 8.47   8192: 10.5 / 10.0   (tape: the 8-env shape stays)
-//   36 beams, a launch per step    1024: 10.3 / 9.3    2048: 11.0 / 9.7    4096: 12.1 / 10.1   8192: 13.6 / 11.8   16384: 25.0 / 21.3
-//   house map, tape form           8192: 24.6 (8 envs on four waves) / 23.6 -- the last user of a four-wave shape, which is gone
-// With the 128-VGPR bound on the 16-env instantiations that need it (min_waves_per_simd), the rule before / 16 envs: 36 beams, tape
-// 8192: 9.95 / 8.16   16384: 19.7 / 16.0; house map, a launch per step 8192: 32.7 / 25.8; per-env maps, tape 8192: 7.58 / 6.89;
-// stage_1, a launch per step 1024: 7.17 / 6.77   4096: 7.59 / 7.23   8192: 7.96 / 8.00.
-static int pick_epb(const navsim* h, int n_envs, int n_beams, bool tape, bool boxes, bool per_env) {
-    if (h->force_epb >= 8) return h->force_epb;
-    if (n_beams > 16) return (tape && n_envs <= 4096) ? 8 : (n_envs <= 16384 ? 16 : 32);
-    if (boxes && n_envs <= 8192) return n_envs <= 4096 ? 8 : 16;
-    if (per_env && tape && n_envs <= 8192) return n_envs <= 4096 ? 8 : 16;
-    if (per_env && !tape && n_envs <= 8192) return 16;
-    if (n_envs >= 16384) return 64;
-    if (!boxes && !per_env && n_envs <= 4096) return 16;
-    return 32;
+// What entry point `e` launches for this handle (navsim_select.h holds the rule)
+static sel::Pick pick_for(const navsim* h, sel::Entry e) {
+    return sel::pick(e, sel::Facts{h->P.N, h->P.B, h->P.S, (h->P.per_env & 1) != 0, h->P.mov_tape != nullptr,
+                                   sel::sens_on(h->P.sigma, h->P.below_min_mode), h->force_epb, h->pair_cast});
 }
 
-// The instantiation navsim_step (tape = false) / navsim_step_seq (tape = true) launches for this handle: envs and waves per
-// workgroup and the cast variant -- 0 = 64-segment passes, 1 = 128-segment passes (maps of 65+ segments without tile boxes:
-// per-env maps, shared maps beyond 4096 segments), 2 = the same with non-temporal loads (the stream does not fit the caches,
-// navsim_set_map; exists for the big 10-beam shapes), 3 = tile bounding boxes (shared maps of 65..4096 segments).
-struct ShapePick {
-    int epb, waves, cast;
+// ---- pick -> kernel.  One resolve function per kernel signature: it spells out the instantiations that are built and answers null
+// for every other pick (launch() below turns that into an error: nothing is ever launched in a missing kernel's place).  The envs
+// and waves per workgroup of a resolved kernel are the pick's.
+
+// step_kernel | steps_kernel behind one name each, so that one ladder serves both
+struct StepK {
+    using Fn = void (*)(StepKArgs);
+    template <int NB, int EPB, bool S, int NW, bool BX, int PAIR> static Fn of() { return step_kernel<NB, EPB, S, NW, BX, PAIR>; }
+    template <bool BX> static Fn mov() { return step_mov_kernel<BX>; }
 };
-static ShapePick pick_shape(const navsim* h, bool tape) {
-    const int NB = h->P.B;
-    const bool boxes = h->P.tile_box != nullptr;
-    if (h->P.mov_tape) return ShapePick{16, 8, boxes ? 3 : 0};   // movers: the one shape that has the MOV form (navsim_set_movers)
-    const int want = pick_epb(h, h->P.N, NB, tape, boxes, h->P.per_env != 0);
-    ShapePick sp;
-    if (want == 8) sp.epb = 8, sp.waves = 8;                                    // eight waves: one env per wave
-    else if (want == 32 || (want == 64 && NB > 10)) sp.epb = 32, sp.waves = 8;  // float64 geometry / rules lanes twice as dense
-    else if (want == 64) sp.epb = 64, sp.waves = 16;                            // (10 beams: the 36-beam tile does not fit the LDS)
-    else sp.epb = 16, sp.waves = 8;                                             // two envs per wave
-    const bool pair = h->pair_cast && !boxes && h->P.S > 64 && h->P.seg_pack_log2 == 6;
-    const bool nt = (h->P.per_env & (tape ? 2 : 4)) != 0;   // navsim_set_map: the per-env stream does not fit the L2s / the Infinity Cache
-    sp.cast = boxes ? 3 : (pair ? ((nt && NB == 10 && sp.epb >= 32) ? 2 : 1) : 0);
-    return sp;
-}
-
-// Run-time choices -> template arguments: f(std::true_type) or f(std::false_type), so that f's body can name an instantiation
-// with the flag (`kernel<..., S, ...>`, `if constexpr (S)`).  Nested calls combine flags.
-template <class F>
-static void with_flag(const bool b, F&& f) {
-    if (b) f(std::true_type{});
-    else f(std::false_type{});
-}
-
-// The SENS flag of a handle's instantiations: the sensor-fidelity options (range noise, -inf below range_min) are on
-static bool sens_on(const navsim* h) { return h->P.sigma > 0.f || h->P.below_min_mode != 0; }
-
-// KERNEL: step_kernel | steps_kernel; `go(kernel, epb, waves)` launches
-#define NAVSIM_DISPATCH_CAST(KERNEL, EPB_, NW_)                                                                            \
-    with_flag(sens_on(h), [&](auto S) {                                                                                    \
-        if (sp.cast == 3) go(KERNEL<NB, EPB_, S, NW_, true>, EPB_, NW_);                                                   \
-        else if (sp.cast == 2) /* the streaming variant exists for the big shapes */                                       \
-            go(KERNEL<NB, EPB_, S, NW_, false, (NB == 10 && EPB_ >= 32) ? 2 : 1>, EPB_, NW_);                              \
-        else if (sp.cast == 1) go(KERNEL<NB, EPB_, S, NW_, false, 1>, EPB_, NW_);                                          \
-        else go(KERNEL<NB, EPB_, S, NW_, false>, EPB_, NW_);                                                               \
-    })
-#define NAVSIM_DISPATCH_SHAPE(KERNEL)                                              \
-    do {                                                                           \
-        if (sp.epb == 8) NAVSIM_DISPATCH_CAST(KERNEL, 8, 8);                       \
-        else if (sp.epb == 32) NAVSIM_DISPATCH_CAST(KERNEL, 32, 8);                \
-        else if (sp.epb == 64) {                                                   \
-            if constexpr (NB == 10) NAVSIM_DISPATCH_CAST(KERNEL, 64, 16);          \
-        } else NAVSIM_DISPATCH_CAST(KERNEL, 16, 8);                                \
-    } while (0)
-
-// `query` non-null: the selected instantiation is not launched, its resources (registers, scratch = spilled registers, LDS) are read
-// into *query (navsim_get_info: the run-time check that what the rule picks fits the way the rule assumes)
-template <int NB>
-static void launch_step(const navsim* h, const float* action, const float* past, void* obs, float* reward, uint8_t* done,
-                        uint8_t* arrive, uint8_t* ended, float* ep_ret, int32_t* ep_len, float* ep_path, hipStream_t st,
-                        hipFuncAttributes* query = nullptr) {
-    const StepKArgs ka = {h->P, StepIO{(const float2*)action, (const float2*)past, obs, reward, done, arrive, ended, ep_ret, ep_len,
-                                       ep_path}};
-    auto go = [&](auto kernel, int epb, int nw) {
-        if (query) (void)hipFuncGetAttributes(query, reinterpret_cast<const void*>(kernel));
-        else hipLaunchKernelGGL(kernel, dim3((h->P.N + epb - 1) / epb), dim3(64 * nw), 0, st, ka);
-    };
-    const ShapePick sp = pick_shape(h, false);
-    if constexpr (NB == 10) {
-        if (h->P.mov_tape) {
-            with_flag(sp.cast == 3, [&](auto BX) { go(step_mov_kernel<BX>, 16, 8); });
-            return;
-        }
-    }
-    NAVSIM_DISPATCH_SHAPE(step_kernel);
-}
-
-// navsim_step_seq: the same shapes and cast variants, all steps of the tape in one launch
-template <int NB>
-static void launch_steps(const navsim* h, const SeqArgs& R, hipStream_t st, hipFuncAttributes* query = nullptr) {
-    const SeqKArgs ka = {h->P, R};
-    auto go = [&](auto kernel, int epb, int nw) {
-        if (query) (void)hipFuncGetAttributes(query, reinterpret_cast<const void*>(kernel));
-        else hipLaunchKernelGGL(kernel, dim3((h->P.N + epb - 1) / epb), dim3(64 * nw), 0, st, ka);
-    };
-    const ShapePick sp = pick_shape(h, true);
-    if constexpr (NB == 10) {
-        if (h->P.mov_tape) {
-            with_flag(sp.cast == 3, [&](auto BX) { go(steps_mov_kernel<BX>, 16, 8); });
-            return;
-        }
-    }
-    NAVSIM_DISPATCH_SHAPE(steps_kernel);
-}
-#undef NAVSIM_DISPATCH_SHAPE
-#undef NAVSIM_DISPATCH_CAST
-
-// navsim_rollout_mlp64's kernel for this handle: kind 0 = unavailable, 1 = rollout_kernel (EPB envs on 8 waves, any beam
-// count), 2 = rollout_big_kernel (64 envs on 16 waves, 10 beams, the cast variants of the step kernel).
-// A 16-env workgroup is ONE latency chain per step whatever its size: measured (tools/time_rollout.py, 512 steps) 4096 / 2048 /
-// 1024 / 512 envs take 2.92 / 2.90 / 2.89 / 2.97 ms with 16 envs per workgroup, 3.05-3.06 ms with 8 and 2.96 ms with 4 wherever the
-// grid still fits one round of 256 CUs (a second round doubles the time: 256 registers x 8 waves fill a CU) -- spreading a small
-// shard over more CUs buys nothing.  Beyond 4096 envs (10 beams): the tape kernel's 64-env workgroup with the policy phase inside
-// every step -- the 16-env shape needs a second round of workgroups there (measured, us per step, 16-env / 64-env shape: 4608 envs
-// 10.6 / 7.3, 8192 10.5 / 7.4, 12288 15.5 / 7.4, 16384 20.5 / 7.6; 4096: 5.3 / 7.5), while a 64-env workgroup costs the same
-// 7.3-7.6 us whether 72 or 256 CUs hold one.  36 beams: the 16-env shape at every size (the 64-env tile does not fit the LDS).
-struct RolloutPick {
-    int kind, epb, waves, cast;
+struct SeqK {
+    using Fn = void (*)(SeqKArgs);
+    template <int NB, int EPB, bool S, int NW, bool BX, int PAIR> static Fn of() { return steps_kernel<NB, EPB, S, NW, BX, PAIR>; }
+    template <bool BX> static Fn mov() { return steps_mov_kernel<BX>; }
 };
-static RolloutPick pick_rollout(const navsim* h) {
-    RolloutPick rp = {0, 0, 0, 0};
-    if (h->P.B != 10 && h->P.B != 36) return rp;
-    const bool boxes = h->P.tile_box != nullptr;
-    const bool pair = h->pair_cast && !boxes && h->P.S > 64 && h->P.seg_pack_log2 == 6;
-    // movers: rollout_big_mov_kernel under the same rule (the tape needs a shared map: cast 0 or 3), else rollout_mov_kernel.
-    // Measured (profiles/movers_big_rollout.txt; orbit_movers M = 32, 512 steps, ms per rollout, the 16-env twin / the big twin):
-    // stage_1 8192 envs 6.66 / 5.25, 16384 envs 13.29 / 5.30; the 2048-segment house map (tile boxes, 32 envs on 8 waves) 8192 envs
-    // 17.36 / 14.95 -- each far outside the spread of the blocks (0.01-0.06 ms), so the rule is the one without movers.
-    if (h->P.B == 10 && (h->force_epb == 64 || h->force_epb == 32 || (h->force_epb == 0 && h->P.N > 16 * 256))) {
-        rp.kind = 2; rp.epb = 64; rp.waves = 16;
-        // tile-box maps (the 2048-segment house map: a vector-issue-bound cast) on 4097..8192 envs: 64-env workgroups would leave half
-        // the CUs empty (8192 envs: 35.4 us per step) -- 32 envs on 8 waves, one workgroup on every CU
-        if (h->force_epb == 32 || (h->force_epb == 0 && boxes && h->P.N <= 32 * 256)) rp.epb = 32, rp.waves = 8;
-        rp.cast = boxes ? 3 : (pair ? ((h->P.per_env & 2) ? 2 : 1) : 0);   // 2: one step's per-env stream exceeds 1.25 x the Infinity Cache
-        if ((rp.epb == 32 || h->P.mov_tape) && rp.cast != 3) rp.cast = 0;   // (the forced 32-env shape, and every shape with movers, exists with 64-segment passes and with tile boxes)
-        return rp;
+// the cast variants of one shape: tile boxes, 64-segment passes, 128-segment passes and (the big 10-beam shapes) their streaming form
+template <class K, int NB, int EPB, int NW, bool S>
+static typename K::Fn step_cast(const int cast) {
+    if (cast == 3) return K::template of<NB, EPB, S, NW, true, 0>();
+    if (cast == 0) return K::template of<NB, EPB, S, NW, false, 0>();
+    if (cast == 1) return K::template of<NB, EPB, S, NW, false, 1>();
+    if constexpr (NB == 10 && EPB >= 32)
+        if (cast == 2) return K::template of<NB, EPB, S, NW, false, 2>();
+    return nullptr;
+}
+template <class K, int NB, bool S>
+static typename K::Fn step_shape(const sel::Pick& p) {
+    if (p.epb == 8 && p.waves == 8) return step_cast<K, NB, 8, 8, S>(p.cast);
+    if (p.epb == 16 && p.waves == 8) return step_cast<K, NB, 16, 8, S>(p.cast);
+    if (p.epb == 32 && p.waves == 8) return step_cast<K, NB, 32, 8, S>(p.cast);
+    if constexpr (NB == 10)   // (the 36-beam tile does not fit the LDS at 64 envs)
+        if (p.epb == 64 && p.waves == 16) return step_cast<K, NB, 64, 16, S>(p.cast);
+    return nullptr;
+}
+template <class K>   // K: StepK (navsim_step) | SeqK (navsim_step_seq)
+static typename K::Fn resolve_step(const sel::Pick& p) {
+    if (p.family != sel::kSmall || p.hist || sel::policy_of(p.entry) >= 0) return nullptr;
+    if (p.mov)   // 10 beams, 16 envs on 8 waves, a shared map
+        return !(p.beams == 10 && p.epb == 16 && p.waves == 8 && p.sens == kMovSens) ? nullptr
+               : p.cast == 3 ? K::template mov<true>() : p.cast == 0 ? K::template mov<false>() : nullptr;
+    if (p.beams == 10) return p.sens ? step_shape<K, 10, true>(p) : step_shape<K, 10, false>(p);
+    if (p.beams == 36) return p.sens ? step_shape<K, 36, true>(p) : step_shape<K, 36, false>(p);
+    return nullptr;
+}
+
+// the rollout_* | evaluate_* kernels of the 16-env workgroup on 8 waves behind one set of names, as StepK / SeqK
+struct RolloutK {
+    using Fn = void (*)(Params, RolloutArgs);
+    static constexpr bool kEval = false;
+    template <int NB, bool S, bool BX> static Fn mlp64() { return rollout_kernel<NB, 16, S, 8, BX>; }
+    template <int EPB, bool S> static Fn narrow() { return rollout_kernel<10, EPB, S, 8>; }   // navsim_set_shape: 4 | 8 envs
+    template <bool BX> static Fn mlp64_mov() { return rollout_mov_kernel<BX>; }
+    template <bool S, bool BX> static Fn hist() { return rollout_hist_kernel<S, BX>; }
+    template <bool BX> static Fn hist_mov() { return rollout_hist_mov_kernel<BX>; }
+    template <bool S> static Fn resmlp() { return rollout_resmlp_kernel<S>; }
+    static Fn resmlp_mov() { return rollout_resmlp_mov_kernel; }
+};
+struct EvalK {
+    using Fn = void (*)(Params, EvalArgs);
+    static constexpr bool kEval = true;
+    template <int NB, bool S, bool BX> static Fn mlp64() { return evaluate_kernel<NB, S, BX>; }
+    template <bool BX> static Fn mlp64_mov() { return evaluate_mov_kernel<BX>; }
+    template <bool S, bool BX> static Fn hist() { return evaluate_hist_kernel<S, BX>; }
+    template <bool BX> static Fn hist_mov() { return evaluate_hist_mov_kernel<BX>; }
+    template <bool S> static Fn resmlp() { return evaluate_resmlp_kernel<S>; }
+    static Fn resmlp_mov() { return evaluate_resmlp_mov_kernel; }
+};
+template <class K, bool S, bool BX>
+static typename K::Fn policy_fn(const sel::Pick& p) {   // the mover twins: 10 beams, one form whatever S says (kMovSens)
+    switch (sel::policy_of(p.entry)) {
+        case 0: return p.mov ? K::template mlp64_mov<BX>() : p.beams == 36 ? K::template mlp64<36, S, BX>() : K::template mlp64<10, S, BX>();
+        case 1: return p.mov ? K::template hist_mov<BX>() : K::template hist<S, BX>();
+        case 2: return BX ? nullptr : p.mov ? K::resmlp_mov() : K::template resmlp<S>();   // (64-segment passes on every map)
     }
-    rp.kind = 1; rp.waves = 8;
-    if (h->P.mov_tape) return RolloutPick{1, 16, 8, boxes ? 3 : 0};   // (movers: the 16-env shape is the only small one with the MOV form)
-    rp.epb = (h->P.B == 10 && !boxes && (h->force_epb == 4 || h->force_epb == 8)) ? h->force_epb : 16;
-    rp.cast = boxes ? 3 : 0;   // (round 5: the 16-env shape has the tile-box cast too -- the house map on shards up to 4096 envs)
-    return rp;
+    return nullptr;
+}
+template <class K>   // K: RolloutK (navsim_rollout_*, the small family) | EvalK (navsim_evaluate_*)
+static typename K::Fn resolve_policy(const sel::Pick& p) {
+    const int pol = sel::policy_of(p.entry);
+    const bool BX = p.cast == 3, S = p.sens;
+    if (pol < 0 || K::kEval != (p.entry >= sel::kEvaluateMlp64) || p.family != sel::kSmall || p.hist != (pol == 1)) return nullptr;
+    if (p.waves != 8 || (p.cast != 0 && !BX)) return nullptr;
+    if (p.mov ? !(p.beams == 10 && S == kMovSens) : !(p.beams == 10 || (p.beams == 36 && pol == 0))) return nullptr;
+    if constexpr (!K::kEval)
+        if ((p.epb == 4 || p.epb == 8) && pol == 0 && p.beams == 10 && !p.mov && !BX)
+            return p.epb == 4 ? (S ? K::template narrow<4, true>() : K::template narrow<4, false>())
+                              : (S ? K::template narrow<8, true>() : K::template narrow<8, false>());
+    if (p.epb != 16) return nullptr;
+    return BX ? (S ? policy_fn<K, true, true>(p) : policy_fn<K, false, true>(p))
+              : (S ? policy_fn<K, true, false>(p) : policy_fn<K, false, false>(p));
+}
+
+// navsim_rollout_mlp64's big family: 64 envs on 16 waves with the cast variants of the step kernel, or 32 envs on 8 waves (tile
+// boxes; forced: any map without the 128-segment passes); with movers a shared map, cast 0 or 3
+using BigFn = void (*)(BigKArgs);
+template <bool S>
+static BigFn big_fn(const sel::Pick& p) {
+    const bool BX = p.cast == 3;
+    if (p.epb == 32 && p.waves == 8 && (p.cast == 0 || BX)) {
+        if (p.mov) return BX ? rollout_big_mov_kernel<32, S, 8, true> : rollout_big_mov_kernel<32, S, 8, false>;
+        return BX ? rollout_big_kernel<32, S, 8, true, 0> : rollout_big_kernel<32, S, 8, false, 0>;
+    }
+    if (p.epb != 64 || p.waves != 16) return nullptr;
+    if (p.mov) return BX ? rollout_big_mov_kernel<64, S, 16, true> : p.cast == 0 ? rollout_big_mov_kernel<64, S, 16, false> : nullptr;
+    if (BX) return rollout_big_kernel<64, S, 16, true, 0>;
+    if (p.cast == 2) return rollout_big_kernel<64, S, 16, false, 2>;
+    if (p.cast == 1) return rollout_big_kernel<64, S, 16, false, 1>;
+    return p.cast == 0 ? rollout_big_kernel<64, S, 16, false, 0> : nullptr;
+}
+static BigFn resolve_big(const sel::Pick& p) {
+    if (p.family != sel::kBig || p.entry != sel::kRolloutMlp64 || p.beams != 10 || p.hist) return nullptr;
+    return p.sens ? big_fn<true>(p) : big_fn<false>(p);
+}
+
+// The one launch of a stepping entry point `who`: the grid covers n_envs with the pick's envs per workgroup.  A pick without a
+// kernel is an error that names the pick.
+template <class... A>
+static int launch(const char* who, const sel::Pick& p, void (*kernel)(A...), const int n_envs, hipStream_t st, const A&... args) {
+    if (p.not_built) return fail(NAVSIM_E_STATE, std::string(who) + ": " + p.not_built);
+    if (!kernel) {
+        char s[160];
+        std::snprintf(s, sizeof(s), ": no kernel is built for the pick {%s family, %d beams, %d envs on %d waves, cast %d, sens %d, mov %d, hist %d}",
+                      p.family == sel::kBig ? "big" : "small", p.beams, p.epb, p.waves, p.cast, (int)p.sens, (int)p.mov, (int)p.hist);
+        return fail(NAVSIM_E_STATE, std::string(who) + s);
+    }
+    hipLaunchKernelGGL(kernel, dim3((n_envs + p.epb - 1) / p.epb), dim3(64 * p.waves), 0, st, args...);
+    HIP_TRY(hipGetLastError());
+    return NAVSIM_OK;
 }
 
 static int invalidate_records(navsim* h, hipStream_t st) {
@@ -3195,16 +3182,15 @@ static int invalidate_records(navsim* h, hipStream_t st) {
 
 // Uploads the start-pose table [K][3] and tabulates its half-angle (cos, sin) on the device.
 static int upload_starts(navsim* h, const double* starts_host, int K, hipStream_t st) {
-    (void)hipFree(h->starts_dev);
-    (void)hipFree(h->starts_sc_dev);
-    h->starts_dev = h->starts_sc_dev = nullptr;
-    HIP_TRY(hipMalloc(&h->starts_dev, sizeof(double) * 3 * K));
-    HIP_TRY(hipMalloc(&h->starts_sc_dev, sizeof(double) * K));
-    HIP_TRY(hipMemcpy(h->starts_dev, starts_host, sizeof(double) * 3 * K, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(starts_sc_kernel, dim3((K + 63) / 64), dim3(64), 0, st, h->starts_dev, K, h->starts_sc_dev);
+    (void)h->starts_dev.reset();
+    (void)h->starts_sc_dev.reset();
+    HIP_TRY(h->starts_dev.alloc(3 * (size_t)K));
+    HIP_TRY(h->starts_sc_dev.alloc((size_t)K));
+    HIP_TRY(hipMemcpy(h->starts_dev.get(), starts_host, sizeof(double) * 3 * K, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(starts_sc_kernel, dim3((K + 63) / 64), dim3(64), 0, st, h->starts_dev.get(), K, h->starts_sc_dev.get());
     HIP_TRY(hipGetLastError());
-    h->P.starts = h->starts_dev;
-    h->P.starts_sc = h->starts_sc_dev;
+    h->P.starts = h->starts_dev.get();
+    h->P.starts_sc = h->starts_sc_dev.get();
     h->P.K = K;
     return NAVSIM_OK;
 }
@@ -3222,11 +3208,11 @@ static int init_handle(navsim* h, const navsim_cfg* cfg) {
     // one block: 8 f64 state arrays + 6 + 2 f64 record arrays, 2 float4, float2 past_action, 2 uint2, i32 ep_step, 2 u32
     const size_t bytes = N * (16 * sizeof(double) + 2 * sizeof(float4) + sizeof(float2) + 2 * sizeof(uint2) +
                               sizeof(int32_t) + 2 * sizeof(uint32_t));
-    HIP_TRY(hipMalloc(&h->state_block, bytes));
-    HIP_TRY(hipMemset(h->state_block, 0, bytes));
+    HIP_TRY(h->state_block.alloc(bytes));
+    HIP_TRY(hipMemset(h->state_block.get(), 0, bytes));
     Params& P = h->P;
     std::memset(&P, 0, sizeof(P));
-    double* d = reinterpret_cast<double*>(h->state_block);
+    double* d = reinterpret_cast<double*>(h->state_block.get());
     P.x = d; P.y = d + N; P.th = d + 2 * N; P.gx = d + 3 * N; P.gy = d + 4 * N;
     P.past_dist = d + 5 * N; P.ep_ret = d + 6 * N; P.ep_path = d + 7 * N;
     P.rec_g = d + 8 * N; P.rsp_g = d + 14 * N;
@@ -3260,17 +3246,17 @@ static int init_handle(navsim* h, const navsim_cfg* cfg) {
         cs[i] = std::cos(phi);
         cs[B + i] = std::sin(phi);
     }
-    HIP_TRY(hipMalloc(&h->beam_cs_dev, sizeof(double) * 2 * B));
-    HIP_TRY(hipMemcpy(h->beam_cs_dev, cs, sizeof(double) * 2 * B, hipMemcpyHostToDevice));
-    P.beam_cs = h->beam_cs_dev;
+    HIP_TRY(h->beam_cs_dev.alloc(2 * (size_t)B));
+    HIP_TRY(hipMemcpy(h->beam_cs_dev.get(), cs, sizeof(double) * 2 * B, hipMemcpyHostToDevice));
+    P.beam_cs = h->beam_cs_dev.get();
 
     std::memset(&h->rects_host, 0, sizeof(Rects));
     std::memcpy(h->rects_host.r[0], kResetRects, sizeof(kResetRects));
     std::memcpy(h->rects_host.r[1], kRespawnRects, sizeof(kRespawnRects));
     h->rects_host.n[0] = h->rects_host.n[1] = 4;
-    HIP_TRY(hipMalloc(&h->rects_dev, sizeof(Rects)));
-    HIP_TRY(hipMemcpy(h->rects_dev, &h->rects_host, sizeof(Rects), hipMemcpyHostToDevice));
-    P.rects = h->rects_dev;
+    HIP_TRY(h->rects_dev.alloc(1));
+    HIP_TRY(hipMemcpy(h->rects_dev.get(), &h->rects_host, sizeof(Rects), hipMemcpyHostToDevice));
+    P.rects = h->rects_dev.get();
 
     // start-pose table: K = 1, the cfg spawn pose (turtlebot3_stage_1.launch:3-5) until navsim_set_spawn_sampler
     {
@@ -3282,12 +3268,6 @@ static int init_handle(navsim* h, const navsim_cfg* cfg) {
     }
     return NAVSIM_OK;
 }
-
-// what navsim_set_movers (and a navsim_set_map behind it) refuses; the same sentence stands in include/navsim.h.  (What IS built
-// beside the 16-env twins: the big shapes of navsim_rollout_mlp64, rollout_big_mov_kernel; every other stepping entry point keeps 16
-// envs on 8 waves whatever navsim_set_shape says.)
-static const char* const kMoversNotBuilt =
-    "movers need 10 beams and a shared static map: movers with 36 beams or with a per-env static map are not built";
 
 #pragma GCC visibility push(default)
 extern "C" {
@@ -3321,31 +3301,14 @@ int navsim_create(const navsim_cfg* cfg, navsim_t** out) {
     navsim* h = new navsim();
     const int rc = init_handle(h, cfg);
     if (rc != NAVSIM_OK) {
-        navsim_destroy(h);   // frees whatever was allocated before the failure
+        delete h;   // frees whatever was allocated before the failure
         return rc;
     }
     *out = h;
     return NAVSIM_OK;
 }
 
-void navsim_destroy(navsim_t* h) {
-    if (!h) return;
-    (void)hipFree(h->state_block);
-    (void)hipFree(h->beam_cs_dev);
-    (void)hipFree(h->rects_dev);
-    (void)hipFree(h->spawn_scan_dev);
-    (void)hipFree(h->spawn_obs_dev);
-    (void)hipFree(h->seg_sorted_dev);
-    (void)hipFree(h->tile_box_dev);
-    (void)hipFree(h->starts_dev);
-    (void)hipFree(h->starts_sc_dev);
-    (void)hipFree(h->goals_dev);
-    (void)hipFree(h->mov_phase0_dev);
-    (void)hipFree(h->mov_bp_dev);
-    (void)hipFree(h->mov_tid_dev);
-    (void)hipFree(h->mov_rects_dev);
-    delete h;
-}
+void navsim_destroy(navsim_t* h) { delete h; }
 
 int navsim_set_shape(navsim_t* h, int32_t envs_per_workgroup, int32_t pair_cast) {
     if (!h) return fail(NAVSIM_E_ARG, "navsim_set_shape: null handle");
@@ -3367,21 +3330,19 @@ int navsim_get_info(navsim_t* h, navsim_info* out) {
     out->has_map = h->has_map;
     out->forced_epb = h->force_epb; out->forced_pair_cast = h->pair_cast_request;
     if (h->has_map) {
-        const ShapePick a = pick_shape(h, false), b = pick_shape(h, true);
+        const sel::Pick a = pick_for(h, sel::kStep), b = pick_for(h, sel::kStepSeq), r = pick_for(h, sel::kRolloutMlp64);
         out->step_epb = a.epb; out->step_waves = a.waves; out->step_cast = a.cast;
         out->seq_epb = b.epb; out->seq_waves = b.waves; out->seq_cast = b.cast;
-        const RolloutPick r = pick_rollout(h);
-        out->rollout_kind = r.kind; out->rollout_epb = r.epb; out->rollout_waves = r.waves; out->rollout_cast = r.cast;
+        out->rollout_kind = r.not_built ? 0 : (r.family == sel::kBig ? 2 : 1);
+        out->rollout_epb = r.epb; out->rollout_waves = r.waves; out->rollout_cast = r.cast;
+        // the resources (registers, scratch = spilled registers, LDS) of what the rule picks: the run-time check that it fits the
+        // way the rule assumes
         hipFuncAttributes fa;
         std::memset(&fa, 0, sizeof(fa));
-        if (h->P.B == 10) launch_step<10>(h, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &fa);
-        else launch_step<36>(h, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &fa);
+        if (const auto k = resolve_step<StepK>(a)) (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(k));
         out->step_vgprs = fa.numRegs; out->step_scratch_bytes = (int32_t)fa.localSizeBytes; out->step_lds_bytes = (int32_t)fa.sharedSizeBytes;
         std::memset(&fa, 0, sizeof(fa));
-        SeqArgs sr;
-        std::memset(&sr, 0, sizeof(sr));
-        if (h->P.B == 10) launch_steps<10>(h, sr, nullptr, &fa);
-        else launch_steps<36>(h, sr, nullptr, &fa);
+        if (const auto k = resolve_step<SeqK>(b)) (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(k));
         out->seq_vgprs = fa.numRegs; out->seq_scratch_bytes = (int32_t)fa.localSizeBytes; out->seq_lds_bytes = (int32_t)fa.sharedSizeBytes;
     }
     return NAVSIM_OK;
@@ -3393,7 +3354,7 @@ int navsim_set_goal_rects(navsim_t* h, int32_t which, const double* rects_host, 
     HIP_TRY(hipDeviceSynchronize());
     std::memcpy(h->rects_host.r[which], rects_host, sizeof(double) * 4 * n_rects);
     h->rects_host.n[which] = n_rects;
-    HIP_TRY(hipMemcpy(h->rects_dev, &h->rects_host, sizeof(Rects), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h->rects_dev.get(), &h->rects_host, sizeof(Rects), hipMemcpyHostToDevice));
     const int rc = invalidate_records(h, nullptr);
     if (rc != NAVSIM_OK) return rc;
     HIP_TRY(hipDeviceSynchronize());
@@ -3404,20 +3365,19 @@ static int rebuild_spawn_scans(navsim* h, hipStream_t st) {
     Params& P = h->P;
     P.spawn_per_env = (P.per_env || (P.mov_tape && (P.mov_phase0 || P.mov_bp))) ? 1 : 0;   // movers with phase offsets or tape ids: every env resets into its own row
     const size_t n_poses = (size_t)(P.spawn_per_env ? P.N : 1) * P.K;
-    if (h->spawn_scan_dev) {
+    if (h->spawn_scan_dev.get()) {
         HIP_TRY(hipStreamSynchronize(st));
-        HIP_TRY(hipFree(h->spawn_scan_dev));
-        HIP_TRY(hipFree(h->spawn_obs_dev));
-        h->spawn_scan_dev = h->spawn_obs_dev = nullptr;
+        HIP_TRY(h->spawn_scan_dev.reset());
+        HIP_TRY(h->spawn_obs_dev.reset());
     }
-    HIP_TRY(hipMalloc(&h->spawn_scan_dev, n_poses * P.B * sizeof(float)));
-    HIP_TRY(hipMalloc(&h->spawn_obs_dev, n_poses * P.B * sizeof(float)));
-    P.spawn_scan = h->spawn_scan_dev;
-    P.spawn_obs = h->spawn_obs_dev;
-    hipLaunchKernelGGL(raycast_kernel, dim3((unsigned)((n_poses + 63) / 64)), dim3(64), 0, st, P, h->starts_dev, P.K, 1,
-                       (int)n_poses, 1, h->spawn_scan_dev);
-    hipLaunchKernelGGL(spawn_obs_kernel, dim3((unsigned)((n_poses * P.B + 255) / 256)), dim3(256), 0, st, h->spawn_scan_dev,
-                       (int)(n_poses * P.B), P.below_min_mode, h->spawn_obs_dev);
+    HIP_TRY(h->spawn_scan_dev.alloc(n_poses * P.B));
+    HIP_TRY(h->spawn_obs_dev.alloc(n_poses * P.B));
+    P.spawn_scan = h->spawn_scan_dev.get();
+    P.spawn_obs = h->spawn_obs_dev.get();
+    hipLaunchKernelGGL(raycast_kernel, dim3((unsigned)((n_poses + 63) / 64)), dim3(64), 0, st, P, h->starts_dev.get(), P.K, 1,
+                       (int)n_poses, 1, h->spawn_scan_dev.get());
+    hipLaunchKernelGGL(spawn_obs_kernel, dim3((unsigned)((n_poses * P.B + 255) / 256)), dim3(256), 0, st, h->spawn_scan_dev.get(),
+                       (int)(n_poses * P.B), P.below_min_mode, h->spawn_obs_dev.get());
     HIP_TRY(hipGetLastError());
     return NAVSIM_OK;
 }
@@ -3425,25 +3385,20 @@ static int rebuild_spawn_scans(navsim* h, hipStream_t st) {
 int navsim_set_map(navsim_t* h, const float* seg_dev, int32_t n_segments, int32_t per_env, void* stream) {
     if (!h || !seg_dev || n_segments < 1) return fail(NAVSIM_E_ARG, "navsim_set_map: bad argument");
     if (h->P.mov_tape && per_env)
-        return fail(NAVSIM_E_ARG, "navsim_set_map: movers are set and " + std::string(kMoversNotBuilt));
+        return fail(NAVSIM_E_ARG, "navsim_set_map: movers are set and " + std::string(sel::kMoversNotBuilt));
     Params& P = h->P;
     P.seg = reinterpret_cast<const float4*>(seg_dev);
     P.S = n_segments;
-    P.per_env = per_env ? 1 : 0;
-    // bit 1: the per-env segment stream of one step (N x S x 16 B) exceeds 1.25 x the 256 MiB Infinity Cache -> the persistent
-    // kernels load it non-temporally too (the PAIR == 2 instantiations)
-    if (per_env && (size_t)P.N * (size_t)n_segments * sizeof(float4) >= (size_t)320 << 20) P.per_env |= 2;
-    // bit 2: it does not fit the 8 x 4 MiB of L2 -> the one-launch-per-step kernel loads it non-temporally
-    if (per_env && (size_t)P.N * (size_t)n_segments * sizeof(float4) >= (size_t)32 << 20) P.per_env |= 4;
-    P.seg_pack_log2 = 6;
+    const sel::MapFacts mf = sel::map_facts(P.N, n_segments, per_env != 0);   // the bits of per_env, tile boxes or not, the packing
+    P.per_env = mf.per_env;
+    P.seg_pack_log2 = mf.seg_pack_log2;
     P.tile_box = nullptr;
-    if (h->seg_sorted_dev || h->tile_box_dev) {
+    if (h->seg_sorted_dev.get() || h->tile_box_dev.get()) {
         HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-        (void)hipFree(h->seg_sorted_dev);
-        (void)hipFree(h->tile_box_dev);
-        h->seg_sorted_dev = h->tile_box_dev = nullptr;
+        (void)h->seg_sorted_dev.reset();
+        (void)h->tile_box_dev.reset();
     }
-    if (!per_env && n_segments > 64 && n_segments <= 4096) {
+    if (mf.tile_boxes) {
         // A shared map big enough to tile: keep an own copy in Morton order of the segment midpoints, so that a 64-segment
         // tile is a compact patch of the map, with the bounding box of every tile.  The order of the segments does not
         // change the scan (the nearest hit is a min).
@@ -3489,17 +3444,12 @@ int navsim_set_map(navsim_t* h, const float* seg_dev, int32_t n_segments, int32_
             }
             box[t] = b;
         }
-        HIP_TRY(hipMalloc(&h->seg_sorted_dev, sizeof(float4) * S));
-        HIP_TRY(hipMalloc(&h->tile_box_dev, sizeof(float4) * nt));
-        HIP_TRY(hipMemcpy(h->seg_sorted_dev, sorted.data(), sizeof(float4) * S, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(h->tile_box_dev, box.data(), sizeof(float4) * nt, hipMemcpyHostToDevice));
-        P.seg = h->seg_sorted_dev;
-        P.tile_box = h->tile_box_dev;
-    }
-    if (n_segments <= 32) {   // several envs share one 64-lane pass of the cast
-        int lg = 0;
-        while ((1 << lg) < n_segments) ++lg;
-        P.seg_pack_log2 = lg;
+        HIP_TRY(h->seg_sorted_dev.alloc((size_t)S));
+        HIP_TRY(h->tile_box_dev.alloc((size_t)nt));
+        HIP_TRY(hipMemcpy(h->seg_sorted_dev.get(), sorted.data(), sizeof(float4) * S, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(h->tile_box_dev.get(), box.data(), sizeof(float4) * nt, hipMemcpyHostToDevice));
+        P.seg = h->seg_sorted_dev.get();
+        P.tile_box = h->tile_box_dev.get();
     }
     const int rc = rebuild_spawn_scans(h, (hipStream_t)stream);
     if (rc != NAVSIM_OK) return rc;
@@ -3539,13 +3489,10 @@ static int set_mover_bank_impl(navsim* h, const char* fn, const float* bank_dev,
         }
     }
     const bool had_rects = P.mov_rects != nullptr;
-    (void)hipFree(h->mov_phase0_dev);
-    (void)hipFree(h->mov_bp_dev);
-    (void)hipFree(h->mov_tid_dev);
-    (void)hipFree(h->mov_rects_dev);
-    h->mov_phase0_dev = h->mov_tid_dev = nullptr;
-    h->mov_bp_dev = nullptr;
-    h->mov_rects_dev = nullptr;
+    (void)h->mov_phase0_dev.reset();
+    (void)h->mov_bp_dev.reset();
+    (void)h->mov_tid_dev.reset();
+    (void)h->mov_rects_dev.reset();
     P.mov_tape = nullptr;
     P.mov_phase0 = nullptr;
     P.mov_bp = nullptr;
@@ -3554,25 +3501,25 @@ static int set_mover_bank_impl(navsim* h, const char* fn, const float* bank_dev,
     P.mov_P = P.mov_M = P.mov_pack_log2 = P.mov_n_rects = 0;
     if (bank_dev) {
         if (!ph0.empty()) {
-            HIP_TRY(hipMalloc(&h->mov_phase0_dev, sizeof(int32_t) * P.N));
-            HIP_TRY(hipMemcpy(h->mov_phase0_dev, ph0.data(), sizeof(int32_t) * P.N, hipMemcpyHostToDevice));
+            HIP_TRY(h->mov_phase0_dev.alloc((size_t)P.N));
+            HIP_TRY(hipMemcpy(h->mov_phase0_dev.get(), ph0.data(), sizeof(int32_t) * P.N, hipMemcpyHostToDevice));
         }
         if (!tid.empty()) {
-            HIP_TRY(hipMalloc(&h->mov_tid_dev, sizeof(int32_t) * P.N));
-            HIP_TRY(hipMemcpy(h->mov_tid_dev, tid.data(), sizeof(int32_t) * P.N, hipMemcpyHostToDevice));
-            HIP_TRY(hipMalloc(&h->mov_bp_dev, sizeof(uint2) * P.N));
-            HIP_TRY(hipMemcpy(h->mov_bp_dev, bp.data(), sizeof(uint2) * P.N, hipMemcpyHostToDevice));
+            HIP_TRY(h->mov_tid_dev.alloc((size_t)P.N));
+            HIP_TRY(hipMemcpy(h->mov_tid_dev.get(), tid.data(), sizeof(int32_t) * P.N, hipMemcpyHostToDevice));
+            HIP_TRY(h->mov_bp_dev.alloc((size_t)P.N));
+            HIP_TRY(hipMemcpy(h->mov_bp_dev.get(), bp.data(), sizeof(uint2) * P.N, hipMemcpyHostToDevice));
         }
         if (rects_host && n_rects > 0) {
-            HIP_TRY(hipMalloc(&h->mov_rects_dev, sizeof(double) * 4 * (size_t)n_rects * (size_t)K));
-            HIP_TRY(hipMemcpy(h->mov_rects_dev, rects_host, sizeof(double) * 4 * (size_t)n_rects * (size_t)K, hipMemcpyHostToDevice));
-            P.mov_rects = h->mov_rects_dev;
+            HIP_TRY(h->mov_rects_dev.alloc(4 * (size_t)n_rects * (size_t)K));
+            HIP_TRY(hipMemcpy(h->mov_rects_dev.get(), rects_host, sizeof(double) * 4 * (size_t)n_rects * (size_t)K, hipMemcpyHostToDevice));
+            P.mov_rects = h->mov_rects_dev.get();
             P.mov_n_rects = n_rects;
         }
         P.mov_tape = reinterpret_cast<const float4*>(bank_dev);
-        P.mov_phase0 = h->mov_phase0_dev;
-        P.mov_bp = h->mov_bp_dev;
-        P.mov_tid = h->mov_tid_dev;
+        P.mov_phase0 = h->mov_phase0_dev.get();
+        P.mov_bp = h->mov_bp_dev.get();
+        P.mov_tid = h->mov_tid_dev.get();
         P.mov_P = period_host[0];
         P.mov_M = M;
         int lg = 0;
@@ -3597,7 +3544,7 @@ int navsim_set_movers(navsim_t* h, const float* tape_dev, int32_t period, int32_
         if (period < 1 || period > 65536 || n_segments < 1 || n_segments > 64)
             return fail(NAVSIM_E_ARG, "navsim_set_movers: 1 <= period <= 65536 and 1 <= n_segments <= 64");
         if ((uintptr_t)tape_dev & 15) return fail(NAVSIM_E_ARG, "navsim_set_movers: the tape must be 16-byte aligned");
-        if (h->P.B != 10 || (h->P.per_env & 1)) return fail(NAVSIM_E_ARG, std::string("navsim_set_movers: ") + kMoversNotBuilt);
+        if (const char* why = sel::movers_not_built(h->P.B, (h->P.per_env & 1) != 0)) return fail(NAVSIM_E_ARG, std::string("navsim_set_movers: ") + why);
     }
     // the bank with one tape, ids 0 and no rectangles
     return set_mover_bank_impl(h, "navsim_set_movers", tape_dev, 1, period, n_segments, &period, nullptr, phase0_dev, nullptr, 0,
@@ -3618,7 +3565,7 @@ int navsim_set_mover_bank(navsim_t* h, const float* bank_dev, int32_t n_tapes, i
         if ((uintptr_t)bank_dev & 15) return fail(NAVSIM_E_ARG, "navsim_set_mover_bank: the bank must be 16-byte aligned");
         if (n_rects < 0 || n_rects > 8) return fail(NAVSIM_E_ARG, "navsim_set_mover_bank: 0 <= n_rects <= 8");
         if (n_rects > 0 && !goal_rects_host) return fail(NAVSIM_E_ARG, "navsim_set_mover_bank: n_rects > 0 without rectangles");
-        if (h->P.B != 10 || (h->P.per_env & 1)) return fail(NAVSIM_E_ARG, std::string("navsim_set_mover_bank: ") + kMoversNotBuilt);
+        if (const char* why = sel::movers_not_built(h->P.B, (h->P.per_env & 1) != 0)) return fail(NAVSIM_E_ARG, std::string("navsim_set_mover_bank: ") + why);
     }
     return set_mover_bank_impl(h, "navsim_set_mover_bank", bank_dev, n_tapes, max_period, n_segments, period_host, tape_id_dev,
                                phase0_dev, goal_rects_host, n_rects, (hipStream_t)stream);
@@ -3631,17 +3578,16 @@ int navsim_set_spawn_sampler(navsim_t* h, const double* starts_host, int32_t n_s
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(hipStreamSynchronize(st));
     Params& P = h->P;
-    (void)hipFree(h->goals_dev);
-    h->goals_dev = nullptr;
+    (void)h->goals_dev.reset();
     {
         const int rc = upload_starts(h, starts_host, n_starts, st);
         if (rc != NAVSIM_OK) return rc;
     }
     if (n_goals > 0) {
-        HIP_TRY(hipMalloc(&h->goals_dev, sizeof(double) * 2 * n_goals));
-        HIP_TRY(hipMemcpy(h->goals_dev, goals_host, sizeof(double) * 2 * n_goals, hipMemcpyHostToDevice));
+        HIP_TRY(h->goals_dev.alloc(2 * (size_t)n_goals));
+        HIP_TRY(hipMemcpy(h->goals_dev.get(), goals_host, sizeof(double) * 2 * n_goals, hipMemcpyHostToDevice));
     }
-    P.goals = h->goals_dev;
+    P.goals = h->goals_dev.get();
     P.G = n_goals;
     P.min_dist = min_dist;
     P.max_dist = max_dist;
@@ -3668,130 +3614,67 @@ int navsim_step(navsim_t* h, const float* action_dev, const float* past_action_d
     if (!h || !action_dev || !obs_dev || !reward_dev || !done_dev || !arrive_dev)
         return fail(NAVSIM_E_ARG, "navsim_step: null required buffer");
     if (!h->has_map) return fail(NAVSIM_E_STATE, "navsim_step: call navsim_set_map first");
-    hipStream_t st = (hipStream_t)stream;
-    if (h->P.B == 10)
-        launch_step<10>(h, action_dev, past_action_dev, obs_dev, reward_dev, done_dev, arrive_dev, ended_dev,
-                        ep_return_dev, ep_length_dev, ep_path_dev, st);
-    else
-        launch_step<36>(h, action_dev, past_action_dev, obs_dev, reward_dev, done_dev, arrive_dev, ended_dev,
-                        ep_return_dev, ep_length_dev, ep_path_dev, st);
-    HIP_TRY(hipGetLastError());
-    return NAVSIM_OK;
+    const StepKArgs ka = {h->P, StepIO{(const float2*)action_dev, (const float2*)past_action_dev, obs_dev, reward_dev, done_dev,
+                                       arrive_dev, ended_dev, ep_return_dev, ep_length_dev, ep_path_dev}};
+    const sel::Pick p = pick_for(h, sel::kStep);
+    return launch("navsim_step", p, resolve_step<StepK>(p), h->P.N, (hipStream_t)stream, ka);
 }
 
-// what both rollout entry points check before anything is launched, and the RolloutArgs they pass; `beams_ok`: the policy has an
-// instantiation for P.B.  NAVSIM_OK with n_steps == 0: nothing to launch.
-static int rollout_args(const navsim* h, const char* fn, bool (*beams_ok)(int), const char* beams_msg, RolloutArgs& R,
-                        const float* params, void* obs_buf, float* act_buf, float* logp_buf, float* reward, uint8_t* done,
-                        uint8_t* arrive, uint8_t* ended, float* ep_return, int32_t* ep_length, float* ep_path, const float* var,
-                        uint64_t seed, const uint32_t* step_base, int32_t n_steps) {
+// The one body of the three rollout entry points: what they check before anything is launched, the RolloutArgs they pass, the
+// pick of entry point `e` and its launch.  NAVSIM_OK with n_steps == 0: nothing to launch.
+static int rollout_entry(const sel::Entry e, const char* fn, const navsim* h, const float* params, void* obs_buf, float* act_buf,
+                         float* logp_buf, float* reward, uint8_t* done, uint8_t* arrive, uint8_t* ended, float* ep_return,
+                         int32_t* ep_length, float* ep_path, const float* var, uint64_t seed, const uint32_t* step_base,
+                         int32_t n_steps, void* stream) {
     const std::string f = std::string(fn) + ": ";
     if (!h || !params || !obs_buf || !act_buf || !logp_buf || !reward || !done || !arrive || !ended || !var || n_steps < 0)
         return fail(NAVSIM_E_ARG, f + "bad argument");
     if (!h->has_map) return fail(NAVSIM_E_STATE, f + "call navsim_set_map first");
-    if (!beams_ok(h->P.B)) return fail(NAVSIM_E_ARG, f + beams_msg);
+    if (const char* why = sel::beams_not_built(e, h->P.B)) return fail(NAVSIM_E_ARG, f + why);
     if (((uintptr_t)params & 15) || ((uintptr_t)act_buf & 7) || ((uintptr_t)obs_buf & 15))
         return fail(NAVSIM_E_ARG, f + "params and obs must be 16-byte, act 8-byte aligned");
-    R = RolloutArgs{params, obs_buf, act_buf, logp_buf, reward, done, arrive, ended, ep_return, ep_length, ep_path, var, step_base,
-                    seed, n_steps};
-    return NAVSIM_OK;
+    if (n_steps == 0) return NAVSIM_OK;
+    const RolloutArgs R = {params, obs_buf, act_buf, logp_buf, reward, done, arrive, ended, ep_return, ep_length, ep_path, var,
+                           step_base, seed, n_steps};
+    const sel::Pick p = pick_for(h, e);
+    if (p.family == sel::kBig) {
+        const BigKArgs ka = {h->P, R, rollout_io(R, (size_t)h->P.N, (size_t)h->P.B + 6, 0, h->P.obs_f16 != 0)};
+        return launch(fn, p, resolve_big(p), h->P.N, (hipStream_t)stream, ka);
+    }
+    return launch(fn, p, resolve_policy<RolloutK>(p), h->P.N, (hipStream_t)stream, h->P, R);
 }
 
 int navsim_rollout_mlp64(navsim_t* h, const float* actor_params_dev, void* obs_buf_dev, float* act_buf_dev,
                          float* logp_buf_dev, float* reward_dev, uint8_t* done_dev, uint8_t* arrive_dev, uint8_t* ended_dev,
                          float* ep_return_dev, int32_t* ep_length_dev, float* ep_path_dev, const float* var_dev,
                          uint64_t act_seed, const uint32_t* step_base_dev, int32_t n_steps, void* stream) {
-    RolloutArgs R;
-    const int rc = rollout_args(h, "navsim_rollout_mlp64", [](int b) { return b == 10 || b == 36; },
-                                "the (B + 6)-64-64 policy needs 10 or 36 beams", R, actor_params_dev, obs_buf_dev, act_buf_dev,
-                                logp_buf_dev, reward_dev, done_dev, arrive_dev, ended_dev, ep_return_dev, ep_length_dev, ep_path_dev,
-                                var_dev, act_seed, step_base_dev, n_steps);
-    if (rc != NAVSIM_OK || n_steps == 0) return rc;
-    const RolloutPick rp = pick_rollout(h);
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((h->P.N + rp.epb - 1) / rp.epb), block(64 * rp.waves);
-    if (rp.kind == 2) {   // 64 envs on 16 waves, the cast variants of launch_step (see pick_rollout)
-        const BigKArgs ka = {h->P, R, rollout_io(R, (size_t)h->P.N, (size_t)h->P.B + 6, 0, h->P.obs_f16 != 0)};
-        auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, st, ka); };
-        with_flag(sens_on(h), [&](auto S) {
-            if (h->P.mov_tape) {   // (a shared map: cast 0 or 3)
-                with_flag(rp.cast == 3, [&](auto BX) {
-                    if (rp.epb == 32) go(rollout_big_mov_kernel<32, S, 8, BX>);
-                    else go(rollout_big_mov_kernel<64, S, 16, BX>);
-                });
-            } else if (rp.epb == 32) {   // (tile boxes; forced: any map without the 128-segment passes)
-                if (rp.cast == 3) go(rollout_big_kernel<32, S, 8, true, 0>);
-                else go(rollout_big_kernel<32, S, 8, false, 0>);
-            } else if (rp.cast == 3) go(rollout_big_kernel<64, S, 16, true, 0>);
-            else if (rp.cast == 2) go(rollout_big_kernel<64, S, 16, false, 2>);
-            else if (rp.cast == 1) go(rollout_big_kernel<64, S, 16, false, 1>);
-            else go(rollout_big_kernel<64, S, 16, false, 0>);
-        });
-    } else {   // 8 waves per workgroup (pick_rollout): more ray waves shorten the cast
-        constexpr int kRollWaves = 8;
-        auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, st, h->P, R); };
-        with_flag(sens_on(h), [&](auto S) {
-            if (h->P.mov_tape) {   // (10 beams: navsim_set_movers)
-                with_flag(rp.cast == 3, [&](auto BX) { go(rollout_mov_kernel<BX>); });
-            } else if (h->P.B == 36) {
-                if (rp.cast == 3) go(rollout_kernel<36, 16, S, kRollWaves, true>);
-                else go(rollout_kernel<36, 16, S, kRollWaves>);
-            } else if (rp.cast == 3) go(rollout_kernel<10, 16, S, kRollWaves, true>);
-            else if (rp.epb == 4) go(rollout_kernel<10, 4, S, kRollWaves>);
-            else if (rp.epb == 8) go(rollout_kernel<10, 8, S, kRollWaves>);
-            else go(rollout_kernel<10, 16, S, kRollWaves>);
-        });
-    }
-    HIP_TRY(hipGetLastError());
-    return NAVSIM_OK;
+    return rollout_entry(sel::kRolloutMlp64, "navsim_rollout_mlp64", h, actor_params_dev, obs_buf_dev, act_buf_dev, logp_buf_dev,
+                         reward_dev, done_dev, arrive_dev, ended_dev, ep_return_dev, ep_length_dev, ep_path_dev, var_dev, act_seed,
+                         step_base_dev, n_steps, stream);
 }
 
 int navsim_rollout_mlp64_hist(navsim_t* h, const float* actor_params_dev, void* obs_buf_dev, float* act_buf_dev,
                               float* logp_buf_dev, float* reward_dev, uint8_t* done_dev, uint8_t* arrive_dev, uint8_t* ended_dev,
                               float* ep_return_dev, int32_t* ep_length_dev, float* ep_path_dev, const float* var_dev,
                               uint64_t act_seed, const uint32_t* step_base_dev, int32_t n_steps, void* stream) {
-    RolloutArgs R;
-    const int rc = rollout_args(h, "navsim_rollout_mlp64_hist", [](int b) { return b == 10; },
-                                "the scan-history policy stacks 10-beam scans (n_beams must be 10)", R, actor_params_dev, obs_buf_dev,
-                                act_buf_dev, logp_buf_dev, reward_dev, done_dev, arrive_dev, ended_dev, ep_return_dev, ep_length_dev,
-                                ep_path_dev, var_dev, act_seed, step_base_dev, n_steps);
-    if (rc != NAVSIM_OK || n_steps == 0) return rc;
-    // always 16 envs on 8 waves, whatever navsim_set_shape says: beyond 4096 envs the workgroups run in rounds
-    const dim3 grid((h->P.N + 15) / 16), block(64 * 8);
-    auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)stream, h->P, R); };
-    with_flag(sens_on(h), [&](auto S) {
-        with_flag(h->P.tile_box != nullptr, [&](auto BOXES) {
-            if (h->P.mov_tape) go(rollout_hist_mov_kernel<BOXES>);
-            else go(rollout_hist_kernel<S, BOXES>);
-        });
-    });
-    HIP_TRY(hipGetLastError());
-    return NAVSIM_OK;
+    return rollout_entry(sel::kRolloutMlp64Hist, "navsim_rollout_mlp64_hist", h, actor_params_dev, obs_buf_dev, act_buf_dev,
+                         logp_buf_dev, reward_dev, done_dev, arrive_dev, ended_dev, ep_return_dev, ep_length_dev, ep_path_dev, var_dev,
+                         act_seed, step_base_dev, n_steps, stream);
 }
 
 int navsim_rollout_resmlp512(navsim_t* h, const float* actor_params_dev, void* obs_buf_dev, float* act_buf_dev, float* logp_buf_dev,
                              float* reward_dev, uint8_t* done_dev, uint8_t* arrive_dev, uint8_t* ended_dev, float* ep_return_dev,
                              int32_t* ep_length_dev, float* ep_path_dev, const float* var_dev, uint64_t act_seed,
                              const uint32_t* step_base_dev, int32_t n_steps, void* stream) {
-    RolloutArgs R;
-    const int rc = rollout_args(h, "navsim_rollout_resmlp512", [](int b) { return b == 10; },
-                                "the reference's nets read 16-wide observations (10 beams)", R, actor_params_dev, obs_buf_dev,
-                                act_buf_dev, logp_buf_dev, reward_dev, done_dev, arrive_dev, ended_dev, ep_return_dev, ep_length_dev,
-                                ep_path_dev, var_dev, act_seed, step_base_dev, n_steps);
-    if (rc != NAVSIM_OK || n_steps == 0) return rc;
-    const dim3 grid((h->P.N + 15) / 16), block(64 * 8);
-    with_flag(sens_on(h), [&](auto S) {
-        if (h->P.mov_tape) hipLaunchKernelGGL(rollout_resmlp_mov_kernel, grid, block, 0, (hipStream_t)stream, h->P, R);
-        else hipLaunchKernelGGL(rollout_resmlp_kernel<S>, grid, block, 0, (hipStream_t)stream, h->P, R);
-    });
-    HIP_TRY(hipGetLastError());
-    return NAVSIM_OK;
+    return rollout_entry(sel::kRolloutResmlp512, "navsim_rollout_resmlp512", h, actor_params_dev, obs_buf_dev, act_buf_dev,
+                         logp_buf_dev, reward_dev, done_dev, arrive_dev, ended_dev, ep_return_dev, ep_length_dev, ep_path_dev, var_dev,
+                         act_seed, step_base_dev, n_steps, stream);
 }
 
-// what both evaluation entry points check before anything is launched; `beams_ok`: the policy has an instantiation for P.B
-static int eval_check(const navsim* h, const char* fn, const float* params, const void* obs0, int32_t quota, int32_t n_steps,
-                      const void* flags, const void* length, const void* ret, const void* path, const void* count, const void* steps,
-                      bool (*beams_ok)(int), const char* beams_msg) {
+// The one body of the three evaluation entry points, as rollout_entry
+static int evaluate_entry(const sel::Entry e, const char* fn, const navsim* h, const float* params, const void* obs0, int32_t quota,
+                          int32_t n_steps, uint8_t* flags, int32_t* length, float* ret, float* path, int32_t* count, int32_t* steps,
+                          void* stream) {
     const std::string f = std::string(fn) + ": ";
     if (!h) return fail(NAVSIM_E_ARG, f + "null handle");
     if (!params || !obs0 || !flags || !length || !ret || !path || !count || !steps) return fail(NAVSIM_E_ARG, f + "null pointer");
@@ -3801,73 +3684,35 @@ static int eval_check(const navsim* h, const char* fn, const float* params, cons
     if (h->P.max_ep_steps <= 0) return fail(NAVSIM_E_ARG, f + "max_episode_steps == 0: an episode could never end");
     if (h->P.N > 16 * 256)
         return fail(NAVSIM_E_ARG, f + "more than 4096 envs (only the 16-env workgroup shape has an evaluation form)");
-    if (!beams_ok(h->P.B)) return fail(NAVSIM_E_ARG, f + beams_msg);
+    if (const char* why = sel::beams_not_built(e, h->P.B)) return fail(NAVSIM_E_ARG, f + why);
     if (((uintptr_t)params & 15) || ((uintptr_t)obs0 & 15)) return fail(NAVSIM_E_ARG, f + "params and obs0 must be 16-byte aligned");
     if (((uintptr_t)length & 3) || ((uintptr_t)ret & 3) || ((uintptr_t)path & 3) || ((uintptr_t)count & 3) || ((uintptr_t)steps & 3))
         return fail(NAVSIM_E_ARG, f + "ep_length, ep_return, ep_path, count and steps must be 4-byte aligned");
     if (!h->has_map) return fail(NAVSIM_E_STATE, f + "call navsim_set_map first");
-    return NAVSIM_OK;
+    const EvalArgs R = {params, obs0, flags, length, ret, path, count, steps, quota, n_steps};
+    const sel::Pick p = pick_for(h, e);
+    return launch(fn, p, resolve_policy<EvalK>(p), h->P.N, (hipStream_t)stream, h->P, R);
 }
 
 int navsim_evaluate_mlp64(navsim_t* h, const float* actor_params_dev, const void* obs0_dev, int32_t quota, int32_t n_steps,
                           uint8_t* ep_flags_dev, int32_t* ep_length_dev, float* ep_return_dev, float* ep_path_dev,
                           int32_t* count_dev, int32_t* steps_dev, void* stream) {
-    const int rc = eval_check(h, "navsim_evaluate_mlp64", actor_params_dev, obs0_dev, quota, n_steps, ep_flags_dev, ep_length_dev,
-                              ep_return_dev, ep_path_dev, count_dev, steps_dev, [](int b) { return b == 10 || b == 36; },
-                              "the (B + 6)-64-64 policy needs 10 or 36 beams");
-    if (rc != NAVSIM_OK) return rc;
-    const EvalArgs R = {actor_params_dev, obs0_dev, ep_flags_dev, ep_length_dev, ep_return_dev, ep_path_dev, count_dev, steps_dev,
-                        quota, n_steps};
-    const dim3 grid((h->P.N + 15) / 16), block(64 * 8);
-    auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)stream, h->P, R); };
-    with_flag(sens_on(h), [&](auto S) {
-        with_flag(h->P.tile_box != nullptr, [&](auto BOXES) {
-            if (h->P.mov_tape) go(evaluate_mov_kernel<BOXES>);   // (10 beams: navsim_set_movers)
-            else if (h->P.B == 36) go(evaluate_kernel<36, S, BOXES>);
-            else go(evaluate_kernel<10, S, BOXES>);
-        });
-    });
-    HIP_TRY(hipGetLastError());
-    return NAVSIM_OK;
+    return evaluate_entry(sel::kEvaluateMlp64, "navsim_evaluate_mlp64", h, actor_params_dev, obs0_dev, quota, n_steps, ep_flags_dev,
+                          ep_length_dev, ep_return_dev, ep_path_dev, count_dev, steps_dev, stream);
 }
 
 int navsim_evaluate_mlp64_hist(navsim_t* h, const float* actor_params_dev, const void* obs0_dev, int32_t quota, int32_t n_steps,
                                uint8_t* ep_flags_dev, int32_t* ep_length_dev, float* ep_return_dev, float* ep_path_dev,
                                int32_t* count_dev, int32_t* steps_dev, void* stream) {
-    const int rc = eval_check(h, "navsim_evaluate_mlp64_hist", actor_params_dev, obs0_dev, quota, n_steps, ep_flags_dev, ep_length_dev,
-                              ep_return_dev, ep_path_dev, count_dev, steps_dev, [](int b) { return b == 10; },
-                              "the scan-history policy stacks 10-beam scans (n_beams must be 10)");
-    if (rc != NAVSIM_OK) return rc;
-    const EvalArgs R = {actor_params_dev, obs0_dev, ep_flags_dev, ep_length_dev, ep_return_dev, ep_path_dev, count_dev, steps_dev,
-                        quota, n_steps};
-    const dim3 grid((h->P.N + 15) / 16), block(64 * 8);
-    auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)stream, h->P, R); };
-    with_flag(sens_on(h), [&](auto S) {
-        with_flag(h->P.tile_box != nullptr, [&](auto BOXES) {
-            if (h->P.mov_tape) go(evaluate_hist_mov_kernel<BOXES>);
-            else go(evaluate_hist_kernel<S, BOXES>);
-        });
-    });
-    HIP_TRY(hipGetLastError());
-    return NAVSIM_OK;
+    return evaluate_entry(sel::kEvaluateMlp64Hist, "navsim_evaluate_mlp64_hist", h, actor_params_dev, obs0_dev, quota, n_steps,
+                          ep_flags_dev, ep_length_dev, ep_return_dev, ep_path_dev, count_dev, steps_dev, stream);
 }
 
 int navsim_evaluate_resmlp512(navsim_t* h, const float* actor_params_dev, const void* obs0_dev, int32_t quota, int32_t n_steps,
                               uint8_t* ep_flags_dev, int32_t* ep_length_dev, float* ep_return_dev, float* ep_path_dev,
                               int32_t* count_dev, int32_t* steps_dev, void* stream) {
-    const int rc = eval_check(h, "navsim_evaluate_resmlp512", actor_params_dev, obs0_dev, quota, n_steps, ep_flags_dev,
-                              ep_length_dev, ep_return_dev, ep_path_dev, count_dev, steps_dev, [](int b) { return b == 10; },
-                              "the reference's nets read 16-wide observations (10 beams)");
-    if (rc != NAVSIM_OK) return rc;
-    const EvalArgs R = {actor_params_dev, obs0_dev, ep_flags_dev, ep_length_dev, ep_return_dev, ep_path_dev, count_dev, steps_dev,
-                        quota, n_steps};
-    const dim3 grid((h->P.N + 15) / 16), block(64 * 8);
-    with_flag(sens_on(h), [&](auto S) {
-        if (h->P.mov_tape) hipLaunchKernelGGL(evaluate_resmlp_mov_kernel, grid, block, 0, (hipStream_t)stream, h->P, R);
-        else hipLaunchKernelGGL(evaluate_resmlp_kernel<S>, grid, block, 0, (hipStream_t)stream, h->P, R);
-    });
-    HIP_TRY(hipGetLastError());
-    return NAVSIM_OK;
+    return evaluate_entry(sel::kEvaluateResmlp512, "navsim_evaluate_resmlp512", h, actor_params_dev, obs0_dev, quota, n_steps,
+                          ep_flags_dev, ep_length_dev, ep_return_dev, ep_path_dev, count_dev, steps_dev, stream);
 }
 
 int navsim_step_seq(navsim_t* h, const float* actions_dev, int32_t n_steps, void* obs_dev, float* reward_dev, uint8_t* done_dev,
@@ -3882,10 +3727,9 @@ int navsim_step_seq(navsim_t* h, const float* actions_dev, int32_t n_steps, void
     R.io = StepIO{reinterpret_cast<const float2*>(actions_dev), nullptr, obs_dev, reward_dev, done_dev, arrive_dev, ended_dev,
                   ep_return_dev, ep_length_dev, ep_path_dev};
     R.T = n_steps;
-    if (h->P.B == 10) launch_steps<10>(h, R, (hipStream_t)stream);
-    else launch_steps<36>(h, R, (hipStream_t)stream);
-    HIP_TRY(hipGetLastError());
-    return NAVSIM_OK;
+    const SeqKArgs ka = {h->P, R};
+    const sel::Pick p = pick_for(h, sel::kStepSeq);
+    return launch("navsim_step_seq", p, resolve_step<SeqK>(p), h->P.N, (hipStream_t)stream, ka);
 }
 
 int navsim_odometry(int32_t n, const double* x_dev, const double* y_dev, const double* quat_dev, const double* goal_dev,
@@ -3915,27 +3759,21 @@ int navsim_get_state(navsim_t* h, double* pose, double* goal, double* past_dist,
     const size_t N = (size_t)h->P.N;
     const Params& P = h->P;
     if (pose) {
-        double* tmp = new double[3 * N];
-        hipError_t e = hipMemcpy(tmp, P.x, sizeof(double) * 3 * N, hipMemcpyDeviceToHost);  // x,y,th are adjacent
-        if (e == hipSuccess)
-            for (size_t i = 0; i < N; ++i) {
-                pose[3 * i] = tmp[i];
-                pose[3 * i + 1] = tmp[N + i];
-                pose[3 * i + 2] = tmp[2 * N + i];
-            }
-        delete[] tmp;
-        HIP_TRY(e);
+        std::vector<double> tmp(3 * N);
+        HIP_TRY(hipMemcpy(tmp.data(), P.x, sizeof(double) * 3 * N, hipMemcpyDeviceToHost));  // x,y,th are adjacent
+        for (size_t i = 0; i < N; ++i) {
+            pose[3 * i] = tmp[i];
+            pose[3 * i + 1] = tmp[N + i];
+            pose[3 * i + 2] = tmp[2 * N + i];
+        }
     }
     if (goal) {
-        double* tmp = new double[2 * N];
-        hipError_t e = hipMemcpy(tmp, P.gx, sizeof(double) * 2 * N, hipMemcpyDeviceToHost);
-        if (e == hipSuccess)
-            for (size_t i = 0; i < N; ++i) {
-                goal[2 * i] = tmp[i];
-                goal[2 * i + 1] = tmp[N + i];
-            }
-        delete[] tmp;
-        HIP_TRY(e);
+        std::vector<double> tmp(2 * N);
+        HIP_TRY(hipMemcpy(tmp.data(), P.gx, sizeof(double) * 2 * N, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < N; ++i) {
+            goal[2 * i] = tmp[i];
+            goal[2 * i + 1] = tmp[N + i];
+        }
     }
     if (past_dist) HIP_TRY(hipMemcpy(past_dist, P.past_dist, sizeof(double) * N, hipMemcpyDeviceToHost));
     if (past_action) HIP_TRY(hipMemcpy(past_action, P.past_action, sizeof(float2) * N, hipMemcpyDeviceToHost));
@@ -3954,25 +3792,21 @@ int navsim_set_state(navsim_t* h, const double* pose, const double* goal, const 
     const size_t N = (size_t)h->P.N;
     const Params& P = h->P;
     if (pose) {
-        double* tmp = new double[3 * N];
+        std::vector<double> tmp(3 * N);
         for (size_t i = 0; i < N; ++i) {
             tmp[i] = pose[3 * i];
             tmp[N + i] = pose[3 * i + 1];
             tmp[2 * N + i] = pose[3 * i + 2];
         }
-        hipError_t e = hipMemcpy(P.x, tmp, sizeof(double) * 3 * N, hipMemcpyHostToDevice);
-        delete[] tmp;
-        HIP_TRY(e);
+        HIP_TRY(hipMemcpy(P.x, tmp.data(), sizeof(double) * 3 * N, hipMemcpyHostToDevice));
     }
     if (goal) {
-        double* tmp = new double[2 * N];
+        std::vector<double> tmp(2 * N);
         for (size_t i = 0; i < N; ++i) {
             tmp[i] = goal[2 * i];
             tmp[N + i] = goal[2 * i + 1];
         }
-        hipError_t e = hipMemcpy(P.gx, tmp, sizeof(double) * 2 * N, hipMemcpyHostToDevice);
-        delete[] tmp;
-        HIP_TRY(e);
+        HIP_TRY(hipMemcpy(P.gx, tmp.data(), sizeof(double) * 2 * N, hipMemcpyHostToDevice));
     }
     if (past_dist) HIP_TRY(hipMemcpy(P.past_dist, past_dist, sizeof(double) * N, hipMemcpyHostToDevice));
     if (past_action) HIP_TRY(hipMemcpy(P.past_action, past_action, sizeof(float2) * N, hipMemcpyHostToDevice));

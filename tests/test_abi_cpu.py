@@ -71,7 +71,7 @@ def test_library_reads_no_shape_knobs_from_the_environment():
     """The workgroup-shape overrides are per-handle state (navsim_set_shape, reported by navsim_get_info): nothing in
     navsim_create -- or anywhere else in the library -- may read NAVSIM_EPB / NAVSIM_PAIR_CAST from the process environment
     (a later handle's environment used to change the kernel shape of every earlier handle)."""
-    src = open(os.path.join(REPO, "navbot_ppo_amd", "csrc", "navsim.hip")).read()
+    src = "".join(open(os.path.join(REPO, "navbot_ppo_amd", "csrc", f)).read() for f in ("navsim.hip", "navsim_select.h"))   # (the rule)
     code = re.sub(r"//[^\n]*", "", src)
     assert "NAVSIM_EPB" not in code and "NAVSIM_PAIR_CAST" not in code
     assert not re.search(r"\bg_epb\b|\bg_pair_cast\b", code)
