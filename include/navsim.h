@@ -407,9 +407,10 @@ int navsim_evaluate_resmlp512(navsim_t* h, const float* actor_params_dev, const 
  *     38..41  0
  * The episode cut: with r(t) the latest row index s <= t such that s == 0 or ended[s-1] != 0, row_{t-j} means
  * row_{max(t-j, r(t))}.  On an episode's first row all three frames are that row's scan and columns 36..37 its past_action (zeros
- * after a reset); a zero-filled frame would read as "obstacle at distance 0" in this normalisation.  Row 0 of a buffer always counts
- * as an episode start: a caller that continues episodes across launches loses two frames at the seam.  With float16 rows every
- * copy is a copy of the half value.  Nothing is recomputed, so everything below is exact.
+ * after a reset); a zero-filled frame would read as "obstacle at distance 0" in this normalisation.  Row 0 of a buffer counts as an
+ * episode start for navsim_stack_rows, navsim_rollout_mlp64_hist and navsim_evaluate_mlp64_hist; a caller that continues episodes
+ * across launches hands the history over the seam with the *_cont entry points below (the HISTORY CARRY) and loses nothing.  With
+ * float16 rows every copy is a copy of the half value.  Nothing is recomputed, so everything below is exact.
  *
  * navsim_stack_rows builds the history rows of a whole buffer; it takes no handle.
  *   obs_dev   [R, N, 16] f32 (f16 if obs_f16 != 0)   rows as navsim_rollout_mlp64's obs_buf_dev holds them
@@ -436,6 +437,36 @@ int navsim_rollout_mlp64_hist(navsim_t* h, const float* actor_params_dev, void* 
                               float* logp_buf_dev, float* reward_dev, uint8_t* done_dev, uint8_t* arrive_dev, uint8_t* ended_dev,
                               float* ep_return_dev, int32_t* ep_length_dev, float* ep_path_dev, const float* var_dev,
                               uint64_t act_seed, const uint32_t* step_base_dev, int32_t n_steps, void* stream);
+
+/*
+ * Continuing across launches.  The HISTORY CARRY of a row is [N, 22] f32, 16-byte aligned: columns 16..37 of the row's history row,
+ *     0..9    the scan of row t-1        10..19  the scan of row t-2        20..21  past_action of row t-1
+ * each already clamped to the episode's first row by the rule above (on an episode's first row: the row's own scan, twice, and its
+ * own past_action), with float16 rows the half values held as float.  The cut is inside the values, so whoever consumes a carry needs
+ * no "did row 0 start an episode" flag.  k launches of T steps chained through carries (row T of one launch's obs_buf copied to row 0
+ * of the next, step_base advanced by T, the handle untouched in between) write the bits ONE launch of k T steps writes.
+ *
+ * navsim_rollout_mlp64_hist_cont: navsim_rollout_mlp64_hist plus
+ *   hist_in_dev   nullable: the carry of obs_buf_dev's row 0 (NULL = row 0 starts every env's episode, as navsim_rollout_mlp64_hist)
+ *   hist_out_dev  nullable: receives the carry of row n_steps (the row behind the last step)
+ * The two may be one buffer: a workgroup reads its envs' entries before its first step and writes them after its last.  Both NULL:
+ * the bits of navsim_rollout_mlp64_hist.  NAVSIM_E_ARG, before anything is launched: whatever navsim_rollout_mlp64_hist refuses, a
+ * carry that is not 16-byte aligned, and n_steps == 0 with a hist_out_dev that is not hist_in_dev (no row to write a carry for).
+ *
+ * navsim_stack_rows_cont: navsim_stack_rows plus
+ *   carry_in_dev   nullable: the carry of obs_dev's row 0.  Output row 0's columns 16..37 are the carry; row 1 takes its oldest frame
+ *                  (columns 26..35) from the carry's entries 0..9 unless ended_dev[0] is set; rows 2.. are navsim_stack_rows's.
+ *   carry_out_dev  nullable: receives columns 16..37 of output row R - 1 as float -- the carry of that row, i.e. of row 0 of the
+ *                  buffer that continues there (written by a second, N x 22-element launch behind the first: may be carry_in_dev)
+ * Both NULL: the bits of navsim_stack_rows.  NAVSIM_E_ARG: whatever navsim_stack_rows refuses, a carry that is not 16-byte aligned.
+ */
+int navsim_rollout_mlp64_hist_cont(navsim_t* h, const float* actor_params_dev, void* obs_buf_dev, float* act_buf_dev,
+                                   float* logp_buf_dev, float* reward_dev, uint8_t* done_dev, uint8_t* arrive_dev, uint8_t* ended_dev,
+                                   float* ep_return_dev, int32_t* ep_length_dev, float* ep_path_dev, const float* var_dev,
+                                   uint64_t act_seed, const uint32_t* step_base_dev, int32_t n_steps, const float* hist_in_dev,
+                                   float* hist_out_dev, void* stream);
+int navsim_stack_rows_cont(const void* obs_dev, int32_t obs_f16, const uint8_t* ended_dev, int32_t R, int32_t N, void* out_dev,
+                           const float* carry_in_dev, float* carry_out_dev, void* stream);
 
 /*
  * navsim_evaluate_mlp64 with the 42-64-64 actor on history rows, as navsim_rollout_mlp64_hist: obs0_dev stays [N, 16] and counts as

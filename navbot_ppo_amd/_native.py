@@ -79,6 +79,9 @@ SYMBOLS = [
     ("navsim_stack_rows", C.c_int, [_vp, _i32, _vp, _i32, _i32, _vp, _vp]),
     ("navsim_rollout_mlp64_hist", C.c_int, [_vp] * 13 + [C.c_uint64, _vp, _i32, _vp]),
     ("navsim_evaluate_mlp64_hist", C.c_int, [_vp, _vp, _vp, _i32, _i32] + [_vp] * 7),
+    # ... continued across launches: the same two with a history carry in and out
+    ("navsim_rollout_mlp64_hist_cont", C.c_int, [_vp] * 13 + [C.c_uint64, _vp, _i32, _vp, _vp, _vp]),
+    ("navsim_stack_rows_cont", C.c_int, [_vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     # include/navppo.h
     ("navppo_last_error", C.c_char_p, []),
     ("navppo_mlp64_workspace_bytes", C.c_size_t, [_i32]),

@@ -96,6 +96,14 @@ class PPOConfig:
     # it and the action between them, never reaching across an episode's first row (env.stack_rows_reference).  The rollout assembles
     # the rows on chip (navsim_rollout_mlp64_hist); the update's batch comes from navsim_stack_rows, once per iteration.
     scan_history: bool = False
+    # False = the reference: every rollout starts from a reset of all envs (ppo.py:486), so no training step ever sees an episode step
+    # at or beyond rollout_len.  True: only the first rollout resets; every later one goes on where the last one stopped (the handle
+    # holds the env state, row T of the observation buffer becomes row 0, with scan_history the history carry crosses the seam too:
+    # navsim_rollout_mlp64_hist_cont / navsim_stack_rows_cont, with norm_reward the running return does) -- the regime of short
+    # rollouts on many envs (rsl_rl, Stable-Baselines3 n_steps).  The envs are reset again when the world changes (set_map, set_movers,
+    # the spawn sampler, ...), after load_checkpoint and on PPOTrainer.reset_envs().  Needs a batch end that is not terminal:
+    # bootstrap_truncated=True or gae_lambda < 1.
+    continue_rollouts: bool = False
 
     def __post_init__(self):
         check_minibatch_config(self)
@@ -103,6 +111,19 @@ class PPOConfig:
         check_lr_schedule_config(self)
         check_bootstrap_config(self)
         check_scan_history_config(self)
+        check_continue_config(self)
+
+
+def check_continue_config(cfg):
+    """PPOConfig.continue_rollouts, at the construction of the config and again of the trainer (a config is mutable)."""
+    if not isinstance(cfg.continue_rollouts, bool):
+        raise ValueError(f"continue_rollouts {cfg.continue_rollouts!r}: True or False")
+    if not cfg.continue_rollouts:
+        return
+    lam = cfg.gae_lambda
+    if not (cfg.bootstrap_truncated is True or (lam is not None and float(lam) < 1.0)):
+        raise ValueError("continue_rollouts=True needs bootstrap_truncated=True or gae_lambda < 1: the reference's convention treats "
+                         "the batch end as terminal, which would cut every env's running episode in every iteration")
 
 
 def check_scan_history_config(cfg):

@@ -1672,6 +1672,10 @@ struct RolloutArgs {
     const uint32_t* step_base;   // device scalar, nullable: rollout steps taken before this launch (noise counter)
     uint64_t seed;
     int T;
+    // navsim_rollout_mlp64_hist_cont: the [N, kHistLen] history carry of row 0 (null = row 0 starts every env's episode) and where
+    // to leave the carry of row T (null = nowhere); may be one buffer.  Read by the scan-history kernels alone.
+    const float* hist_in;
+    float* hist_out;
 };
 
 // ---- what the persistent kernels (rollout_kernel, rollout_resmlp_kernel, evaluate_kernel, evaluate_resmlp_kernel, steps_kernel,
@@ -1785,8 +1789,8 @@ __device__ __forceinline__ float hist_next_entry(PRef P, const StepSmem<NB, EPB,
 }
 // The input of lane (env e, kk) of the 42-column policy tile: columns 11 kk .. 11 kk + 10 of the stacked row (44 padded features).
 // Columns 0..15 are mlp64_obs_row's of the 16-column policy (next_obs_n / sm.obs); columns 16..37 come from `hist`, or -- on a row
-// that starts an episode (row 0 of the launch: !IN_STEP; a row behind an ended step) -- are copies of the row's own scan and
-// past_action; 38..43 are 0.  Every value rounded to half when the buffers are (idempotent on what hist already holds).
+// behind an ended step -- are copies of the row's own scan and past_action; 38..43 are 0.  Row 0 of the launch (!IN_STEP) reads
+// `hist` as it was filled: by hist_init with those same copies (the row starts an episode), or from the caller's carry.  Every value rounded to half when the buffers are (idempotent on what hist already holds).
 template <int NB, int EPB, int NW, bool SENS, bool IN_STEP, class PRef>
 __device__ __forceinline__ ObsRow<11> hist_obs_row(PRef P, const StepSmem<NB, EPB, NW>& sm, const float* hist, const int e, const int kk,
                                                    const int nloc, const bool half_rows, const float sigma, const int below_min) {
@@ -1796,7 +1800,7 @@ __device__ __forceinline__ ObsRow<11> hist_obs_row(PRef P, const StepSmem<NB, EP
     const int el = min(e, nloc - 1);
     ObsRow<KS> r;
     float (&xs)[KS] = r.x;
-    bool ends = true;
+    bool ends = false;
     if constexpr (IN_STEP) {
         next_obs_n<NB, EPB, NW, SENS, KS, PRef>(P, sm, el, KS * kk, sigma, below_min, xs);   // (columns past 15: 0)
         ends = hist_step_ends<NB, EPB, NW, SENS, PRef>(P, sm, el);
@@ -1808,10 +1812,9 @@ __device__ __forceinline__ ObsRow<11> hist_obs_row(PRef P, const StepSmem<NB, EP
     for (int j = 0; j < KS; ++j) {
         const int f = KS * kk + j;
         if (f >= D && f < D + kHistLen) {
-            float v;
+            float v = 0.f;
             if (ends) {
                 if constexpr (IN_STEP) v = hist_next_entry<NB, EPB, NW, SENS, PRef>(P, sm, el, hist_src_col(f), true, sigma, below_min);
-                else v = sm.obs[el * DP + hist_src_col(f)];
             } else {
                 v = hist[el * kHistStride + (f - D)];
             }
@@ -1839,6 +1842,51 @@ __device__ __forceinline__ void hist_init(float* hist, const void* obs, const in
         hist[e * kHistStride + c] = half_rows ? __half2float(reinterpret_cast<const __half*>(obs)[src])
                                               : reinterpret_cast<const float*>(obs)[src];
     }
+}
+// Between the steps `hist` is one row ahead of a history row's columns: in front of step t it holds (scan of row t, scan of row
+// t - 1, past_action of row t) -- what row t + 1 reads unless step t ends the episode -- while columns 16..37 of row t, the CARRY of
+// row t (include/navsim.h), are (scan of row t - 1, scan of row t - 2, past_action of row t - 1).  So a launch that continues from a
+// caller's carry ([N, kHistLen] f32) fills `hist` with the carry itself, which the policy of row 0 reads as its columns 16..37
+// (hist_obs_row, !IN_STEP), and then moves it one row on (hist_enter); the episode cut is inside the carry's values, so nothing
+// here asks whether row 0 starts an episode.
+template <int NW>
+__device__ __forceinline__ void hist_load(float* hist, const float* carry, const int base, const int nloc) {
+    for (int k = threadIdx.x; k < nloc * kHistLen; k += 64 * NW)
+        hist[(k / kHistLen) * kHistStride + (k % kHistLen)] = carry[(size_t)base * kHistLen + k];
+}
+// lane = env e, behind the policy of row 0 and in front of step 0: the carry of row 0 -> the block in front of step 0.  Row 0's own
+// scan and past_action come from the observation tile (float16 rows: the half values, as load_obs_tile widened them).
+template <int NB, int EPB, int NW>
+__device__ __forceinline__ void hist_enter(const StepSmem<NB, EPB, NW>& sm, float* hist, const int e) {
+    constexpr int DP = NB + 7;
+    float* h = hist + e * kHistStride;
+    for (int c = 0; c < NB; ++c) {
+        h[NB + c] = h[c];
+        h[c] = sm.obs[e * DP + c];
+    }
+    h[2 * NB] = sm.obs[e * DP + NB];
+    h[2 * NB + 1] = sm.obs[e * DP + NB + 1];
+}
+// lane = env e, behind the launch's LAST step (no policy ran in it: the block is as the shift of the step before left it; the
+// observation tile holds the row the step left, the reset observation where it ended an episode): the carry of that row.  The
+// block IS its columns 16..37 unless the step ended the episode (`ended`: the flag this lane stored for the step); then they are
+// copies of the new row's own scan and past_action.  8 bytes per store (rows of 88 bytes in a 16-byte aligned buffer).
+template <int NB, int EPB, int NW>
+__device__ __forceinline__ void hist_leave(const StepSmem<NB, EPB, NW>& sm, float* hist, float* carry, const int base, const int e,
+                                           const bool ended, const bool half_rows) {
+    constexpr int DP = NB + 7;
+    float* h = hist + e * kHistStride;
+    if (ended) {
+        for (int c = 0; c < NB + 2; ++c) {
+            float v = sm.obs[e * DP + c];
+            if (half_rows) v = __half2float(__float2half_rn(v));
+            if (c < NB) h[c] = v;
+            h[NB + c] = v;
+        }
+    }
+    float2* o = reinterpret_cast<float2*>(carry + (size_t)(base + e) * kHistLen);
+#pragma unroll
+    for (int c = 0; c < kHistLen / 2; ++c) o[c] = make_float2(h[2 * c], h[2 * c + 1]);
 }
 // The shift, lane = env, by the wave that arrives last at the in-step policy (last_arrival: the four tile waves have read `hist`,
 // and the next read is behind barrier B2 of the next step, which no wave reaches before this wave has passed barrier C):
@@ -1934,7 +1982,10 @@ __device__ __forceinline__ void rollout_body(const Params& P, const RolloutArgs&
     load_obs_tile<NB, EPB, NW>(sm, R.obs_buf, base, nloc, half_rows);
     load_tables<NB, EPB, NW, const Params&>(P, sm);
     if constexpr (MOV) load_mover_phase0<NB, EPB, NW, const Params&>(P, sm, base, nloc);
-    if constexpr (HIST) hist_init<NB, NW>(hist, R.obs_buf, base, nloc, half_rows);
+    if constexpr (HIST) {
+        if (R.hist_in) hist_load<NW>(hist, R.hist_in, base, nloc);
+        else hist_init<NB, NW>(hist, R.obs_buf, base, nloc, half_rows);
+    }
     const uint32_t step0 = R.step_base ? *R.step_base : 0u;
     const float var = *R.var_ptr;
     if (tid == 0) pol_cnt = 0u;
@@ -1987,6 +2038,9 @@ __device__ __forceinline__ void rollout_body(const Params& P, const RolloutArgs&
     else if (wave == 4 && lane < nloc) draw_noise(step0);
     __syncthreads();
     if (wave == 0 && lane < nloc) finish(0);
+    if constexpr (HIST) {   // (the tile waves have read the carry as row 0's columns: now the block in front of step 0)
+        if (wave == 1 && lane < nloc && R.hist_in) hist_enter<NB, EPB, NW>(sm, hist, lane);
+    }
     __syncthreads();
     for (int t = 0; t < R.T; ++t) {
         const size_t tn = (size_t)t * N;
@@ -2018,6 +2072,10 @@ __device__ __forceinline__ void rollout_body(const Params& P, const RolloutArgs&
         step_body<NB, EPB, SENS, true, NW, BOXES, 0, const Params&, const StepIO&, decltype(hook), MOV>(P, sm, next_env, io,
                                                                                                       t == R.T - 1, 0, hook);
         // the observation tile of step t + 1 is in sm.obs (its store only reads it), its action in sm.act_l
+    }
+    if constexpr (HIST) {   // the carry of row T, by the lanes that wrote the last step's flags (wave 0, lane = env)
+        if (R.hist_out && wave == 0 && lane < nloc)
+            hist_leave<NB, EPB, NW>(sm, hist, R.hist_out, base, lane, R.ended[(size_t)(R.T - 1) * N + base + lane] != 0, half_rows);
     }
 }
 template <int NB, int EPB, bool SENS, int NW, bool BOXES = false>
@@ -2755,9 +2813,13 @@ __global__ void spawn_obs_kernel(const float* __restrict__ best, int n, int belo
 // array, a thread owns 16 bytes of it (4 floats / 8 halves, crossing a row boundary where they do) and stores them at once;
 // neighbouring threads read neighbouring entries of the same three source rows, which the caches serve (each input row is read
 // three times, the output written once: 3.6 x the input's bytes in all).
-template <class T>
+// CONT (navsim_stack_rows_cont with a carry-in): row 0 does not start the episodes -- its columns 16..37 ARE the carry ([N, kHistLen]
+// f32: the two scans and the action pair in front of row 0, the episode cut already inside), and row 1, unless ended[0] cuts it off,
+// takes its oldest frame from the carry's first scan.  From row 2 on nothing looks in front of row 0.
+template <class T, bool CONT = false>
 __global__ __launch_bounds__(256) void stack_rows_kernel(const T* __restrict__ obs, const uint8_t* __restrict__ ended, const int R,
-                                                         const int N, T* __restrict__ out) {
+                                                         const int N, T* __restrict__ out,
+                                                         [[maybe_unused]] const float* __restrict__ carry = nullptr) {
     constexpr int V = 16 / (int)sizeof(T), DI = 16, DO = kHistD;
     const size_t total = (size_t)R * (size_t)N * DO;
     const size_t k0 = ((size_t)blockIdx.x * 256 + threadIdx.x) * V;
@@ -2766,6 +2828,8 @@ __global__ __launch_bounds__(256) void stack_rows_kernel(const T* __restrict__ o
     int c = (int)(k0 - q * DO);
     const size_t n_rows = (size_t)R * (size_t)N;
     size_t s0 = 0, s1 = 0, s2 = 0;   // element offsets of the rows frames 0, 1, 2 are copied from
+    [[maybe_unused]] const float* cr = nullptr;   // CONT: the env's carry row
+    [[maybe_unused]] bool c1 = false, c2 = false;   // CONT: columns 16..25 and 36..37 / columns 26..35 come from the carry
     auto locate = [&](const size_t row) {
         const size_t r = row / (size_t)N;
         const bool cut0 = (r == 0) || (ended[row - (size_t)N] != 0);                  // row r starts an episode
@@ -2773,6 +2837,11 @@ __global__ __launch_bounds__(256) void stack_rows_kernel(const T* __restrict__ o
         s0 = row * DI;
         s1 = cut0 ? s0 : s0 - (size_t)N * DI;
         s2 = cut0 ? s0 : (cut1 ? s1 : s1 - (size_t)N * DI);
+        if constexpr (CONT) {
+            cr = carry + (row - r * (size_t)N) * kHistLen;
+            c1 = r == 0;
+            c2 = c1 || (r == 1 && !cut0);
+        }
     };
     locate(q);
     alignas(16) T v[V];
@@ -2780,10 +2849,17 @@ __global__ __launch_bounds__(256) void stack_rows_kernel(const T* __restrict__ o
     for (int j = 0; j < V; ++j) {
         T x = T(0.f);
         if (q < n_rows) {
+            if constexpr (CONT) {   // (the carry holds the rows' own values as float: the conversion back is exact)
+                if (c < DI) x = obs[s0 + c];
+                else if (c < 26) x = c1 ? T(cr[c - 16]) : obs[s1 + (c - 16)];
+                else if (c < 36) x = c2 ? T(cr[c1 ? c - 16 : c - 26]) : obs[s2 + (c - 26)];
+                else if (c < 38) x = c1 ? T(cr[c - 16]) : obs[s1 + (c - 26)];
+            } else {
             if (c < DI) x = obs[s0 + c];
             else if (c < 26) x = obs[s1 + (c - 16)];
             else if (c < 36) x = obs[s2 + (c - 26)];
             else if (c < 38) x = obs[s1 + (c - 26)];   // past_action of the previous row: columns 10, 11
+            }
         }
         v[j] = x;
         if (++c == DO) {
@@ -2798,6 +2874,15 @@ __global__ __launch_bounds__(256) void stack_rows_kernel(const T* __restrict__ o
         for (int j = 0; j < V; ++j)
             if (k0 + j < total) out[k0 + j] = v[j];
     }
+}
+
+// navsim_stack_rows_cont's carry-out: columns 16..37 of the last output row as float, [N, kHistLen].  Launched behind the kernel
+// above, so a caller may hand in the buffer the carry-in came from.
+template <class T>
+__global__ __launch_bounds__(256) void stack_rows_carry_kernel(const T* __restrict__ last_row, const int N, float* __restrict__ carry) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= N * kHistLen) return;
+    carry[k] = (float)last_row[(size_t)(k / kHistLen) * kHistD + 16 + (k % kHistLen)];
 }
 
 // ---------------------------------------------------------------- return scan (PPO.compute_rtgs)
@@ -3625,17 +3710,20 @@ int navsim_step(navsim_t* h, const float* action_dev, const float* past_action_d
 static int rollout_entry(const sel::Entry e, const char* fn, const navsim* h, const float* params, void* obs_buf, float* act_buf,
                          float* logp_buf, float* reward, uint8_t* done, uint8_t* arrive, uint8_t* ended, float* ep_return,
                          int32_t* ep_length, float* ep_path, const float* var, uint64_t seed, const uint32_t* step_base,
-                         int32_t n_steps, void* stream) {
+                         int32_t n_steps, void* stream, const float* hist_in = nullptr, float* hist_out = nullptr) {
     const std::string f = std::string(fn) + ": ";
     if (!h || !params || !obs_buf || !act_buf || !logp_buf || !reward || !done || !arrive || !ended || !var || n_steps < 0)
         return fail(NAVSIM_E_ARG, f + "bad argument");
+    if (((uintptr_t)hist_in & 15) || ((uintptr_t)hist_out & 15)) return fail(NAVSIM_E_ARG, f + "the history carries must be 16-byte aligned");
+    if (n_steps == 0 && hist_out && hist_out != hist_in)
+        return fail(NAVSIM_E_ARG, f + "n_steps == 0 leaves no row to write a carry for (pass hist_out = hist_in, or none)");
     if (!h->has_map) return fail(NAVSIM_E_STATE, f + "call navsim_set_map first");
     if (const char* why = sel::beams_not_built(e, h->P.B)) return fail(NAVSIM_E_ARG, f + why);
     if (((uintptr_t)params & 15) || ((uintptr_t)act_buf & 7) || ((uintptr_t)obs_buf & 15))
         return fail(NAVSIM_E_ARG, f + "params and obs must be 16-byte, act 8-byte aligned");
     if (n_steps == 0) return NAVSIM_OK;
     const RolloutArgs R = {params, obs_buf, act_buf, logp_buf, reward, done, arrive, ended, ep_return, ep_length, ep_path, var,
-                           step_base, seed, n_steps};
+                           step_base, seed, n_steps, hist_in, hist_out};
     const sel::Pick p = pick_for(h, e);
     if (p.family == sel::kBig) {
         const BigKArgs ka = {h->P, R, rollout_io(R, (size_t)h->P.N, (size_t)h->P.B + 6, 0, h->P.obs_f16 != 0)};
@@ -3660,6 +3748,16 @@ int navsim_rollout_mlp64_hist(navsim_t* h, const float* actor_params_dev, void* 
     return rollout_entry(sel::kRolloutMlp64Hist, "navsim_rollout_mlp64_hist", h, actor_params_dev, obs_buf_dev, act_buf_dev,
                          logp_buf_dev, reward_dev, done_dev, arrive_dev, ended_dev, ep_return_dev, ep_length_dev, ep_path_dev, var_dev,
                          act_seed, step_base_dev, n_steps, stream);
+}
+
+int navsim_rollout_mlp64_hist_cont(navsim_t* h, const float* actor_params_dev, void* obs_buf_dev, float* act_buf_dev,
+                                   float* logp_buf_dev, float* reward_dev, uint8_t* done_dev, uint8_t* arrive_dev, uint8_t* ended_dev,
+                                   float* ep_return_dev, int32_t* ep_length_dev, float* ep_path_dev, const float* var_dev,
+                                   uint64_t act_seed, const uint32_t* step_base_dev, int32_t n_steps, const float* hist_in_dev,
+                                   float* hist_out_dev, void* stream) {
+    return rollout_entry(sel::kRolloutMlp64Hist, "navsim_rollout_mlp64_hist_cont", h, actor_params_dev, obs_buf_dev, act_buf_dev,
+                         logp_buf_dev, reward_dev, done_dev, arrive_dev, ended_dev, ep_return_dev, ep_length_dev, ep_path_dev, var_dev,
+                         act_seed, step_base_dev, n_steps, stream, hist_in_dev, hist_out_dev);
 }
 
 int navsim_rollout_resmlp512(navsim_t* h, const float* actor_params_dev, void* obs_buf_dev, float* act_buf_dev, float* logp_buf_dev,
@@ -3869,25 +3967,51 @@ int navsim_gae_scan_trunc(const float* rew_dev, const uint8_t* ended_dev, const 
     return NAVSIM_OK;
 }
 
-int navsim_stack_rows(const void* obs_dev, int32_t obs_f16, const uint8_t* ended_dev, int32_t R, int32_t N, void* out_dev,
-                      void* stream) {
-    if (R < 1 || N < 1) return fail(NAVSIM_E_ARG, "navsim_stack_rows: R and N must be at least 1");
-    if (!obs_dev || !out_dev) return fail(NAVSIM_E_ARG, "navsim_stack_rows: null buffer");
-    if (R > 1 && !ended_dev) return fail(NAVSIM_E_ARG, "navsim_stack_rows: ended_dev may be null only when R == 1");
+// The one body of navsim_stack_rows and navsim_stack_rows_cont
+static int stack_rows_entry(const char* fn, const void* obs_dev, int32_t obs_f16, const uint8_t* ended_dev, int32_t R, int32_t N,
+                            void* out_dev, const float* carry_in, float* carry_out, void* stream) {
+    const std::string f = std::string(fn) + ": ";
+    if (R < 1 || N < 1) return fail(NAVSIM_E_ARG, f + "R and N must be at least 1");
+    if (!obs_dev || !out_dev) return fail(NAVSIM_E_ARG, f + "null buffer");
+    if (R > 1 && !ended_dev) return fail(NAVSIM_E_ARG, f + "ended_dev may be null only when R == 1");
     if (((uintptr_t)obs_dev & 15) || ((uintptr_t)out_dev & 15))
-        return fail(NAVSIM_E_ARG, "navsim_stack_rows: obs_dev and out_dev must be 16-byte aligned");
+        return fail(NAVSIM_E_ARG, f + "obs_dev and out_dev must be 16-byte aligned");
+    if (((uintptr_t)carry_in & 15) || ((uintptr_t)carry_out & 15)) return fail(NAVSIM_E_ARG, f + "the carries must be 16-byte aligned");
+    if (carry_out && (int64_t)N * kHistLen > 0x7fffffffll) return fail(NAVSIM_E_ARG, f + "too many envs for a carry");
     const size_t total = (size_t)R * (size_t)N * (size_t)kHistD;
     const size_t per = obs_f16 ? 8 : 4;
     const size_t blocks = ((total + per - 1) / per + 255) / 256;
-    if (blocks > 0x7fffffffull) return fail(NAVSIM_E_ARG, "navsim_stack_rows: too many rows for one launch");
-    if (obs_f16)
-        hipLaunchKernelGGL(stack_rows_kernel<__half>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
-                           reinterpret_cast<const __half*>(obs_dev), ended_dev, R, N, reinterpret_cast<__half*>(out_dev));
-    else
-        hipLaunchKernelGGL(stack_rows_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
-                           reinterpret_cast<const float*>(obs_dev), ended_dev, R, N, reinterpret_cast<float*>(out_dev));
+    if (blocks > 0x7fffffffull) return fail(NAVSIM_E_ARG, f + "too many rows for one launch");
+    const hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)blocks), cgrid((unsigned)(((size_t)N * kHistLen + 255) / 256));
+    const size_t last = (size_t)(R - 1) * (size_t)N * (size_t)kHistD;
+    if (obs_f16) {
+        const __half* obs = reinterpret_cast<const __half*>(obs_dev);
+        __half* out = reinterpret_cast<__half*>(out_dev);
+        if (carry_in) hipLaunchKernelGGL(HIP_KERNEL_NAME(stack_rows_kernel<__half, true>), grid, dim3(256), 0, st, obs, ended_dev, R, N, out, carry_in);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(stack_rows_kernel<__half, false>), grid, dim3(256), 0, st, obs, ended_dev, R, N, out, nullptr);
+        HIP_TRY(hipGetLastError());
+        if (carry_out) hipLaunchKernelGGL(stack_rows_carry_kernel<__half>, cgrid, dim3(256), 0, st, out + last, N, carry_out);
+    } else {
+        const float* obs = reinterpret_cast<const float*>(obs_dev);
+        float* out = reinterpret_cast<float*>(out_dev);
+        if (carry_in) hipLaunchKernelGGL(HIP_KERNEL_NAME(stack_rows_kernel<float, true>), grid, dim3(256), 0, st, obs, ended_dev, R, N, out, carry_in);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(stack_rows_kernel<float, false>), grid, dim3(256), 0, st, obs, ended_dev, R, N, out, nullptr);
+        HIP_TRY(hipGetLastError());
+        if (carry_out) hipLaunchKernelGGL(stack_rows_carry_kernel<float>, cgrid, dim3(256), 0, st, out + last, N, carry_out);
+    }
     HIP_TRY(hipGetLastError());
     return NAVSIM_OK;
+}
+
+int navsim_stack_rows(const void* obs_dev, int32_t obs_f16, const uint8_t* ended_dev, int32_t R, int32_t N, void* out_dev,
+                      void* stream) {
+    return stack_rows_entry("navsim_stack_rows", obs_dev, obs_f16, ended_dev, R, N, out_dev, nullptr, nullptr, stream);
+}
+
+int navsim_stack_rows_cont(const void* obs_dev, int32_t obs_f16, const uint8_t* ended_dev, int32_t R, int32_t N, void* out_dev,
+                           const float* carry_in_dev, float* carry_out_dev, void* stream) {
+    return stack_rows_entry("navsim_stack_rows_cont", obs_dev, obs_f16, ended_dev, R, N, out_dev, carry_in_dev, carry_out_dev, stream);
 }
 
 }  // extern "C"

@@ -21,9 +21,20 @@ from . import maps as _maps
 from ._native import NavsimCfg, NavsimError, NavsimInfo, check, lib
 
 __all__ = ["NavSim", "VecEnv", "Env", "NavsimError", "rtg_scan", "gae_scan", "gae_scan_trunc", "truncated_returns_reference",
-           "stack_rows", "stack_rows_reference", "HistoryWindow", "HostHistoryWindow", "HIST_DIM"]
+           "stack_rows", "stack_rows_reference", "HistoryWindow", "HostHistoryWindow", "HIST_DIM", "HIST_CARRY"]
 
 HIST_DIM = 42   # columns of a scan-history row (navsim_stack_rows)
+HIST_CARRY = 22   # floats per env of a history carry: columns 16..37 of a history row (include/navsim.h)
+
+
+def _chk_carry(what, t, n_envs, device):
+    """a history carry before its pointer crosses the ABI: [N, 22] contiguous float32 on `device`, 16-byte aligned (None passes)"""
+    if t is None:
+        return
+    if (not torch.is_tensor(t) or t.device != device or t.dtype != torch.float32 or tuple(t.shape) != (n_envs, HIST_CARRY)
+            or not t.is_contiguous() or t.data_ptr() % 16):
+        raise NavsimError(f"{what}: a contiguous, 16-byte aligned float32 tensor [{n_envs}, {HIST_CARRY}] on {device}, got "
+                          f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
 
 
 def _ptr(t):
@@ -425,8 +436,8 @@ def truncated_returns_reference(rew, ended, done, arrive, value, gamma, lam, las
     return ret - V, ret
 
 
-def stack_rows_reference(obs, ended=None):
-    """Host mirror of navsim_stack_rows, numpy -- the statement of the scan-history rule.  obs [R, N, 16] (float32 or float16) are
+def stack_rows_reference(obs, ended=None, carry=None):
+    """Host mirror of navsim_stack_rows / navsim_stack_rows_cont, numpy -- the statement of the scan-history rule.  obs [R, N, 16] (float32 or float16) are
     ordinary rows (10 beams / 3.5, past_action, 4 goal columns), ended [R - 1, N] (non-zero = the step between rows t and t + 1 ended
     the episode; None allowed when R == 1).  Returns [R, N, 42] of obs's dtype, every entry a copy:
         out[t, :,  0:16] = obs[t]                  the ordinary row
@@ -435,7 +446,11 @@ def stack_rows_reference(obs, ended=None):
         out[t, :, 36:38] = obs[i1, :, 10:12]       the action between the two older scans
         out[t, :, 38:42] = 0
     r(t) = the latest s <= t with s == 0 or ended[s - 1] != 0: frames never reach across an episode's first row, and row 0 of the
-    buffer always counts as one."""
+    buffer counts as one -- unless ``carry`` [N, 22] (float32; None = no carry) says what lay in front of it: columns 16..37 of row
+    0's history row (the scan of row -1, the scan of row -2, past_action of row -1, each already clamped to the episode's first row).
+    Then the call returns (rows, carry_out), carry_out [N, 22] float32 = columns 16..37 of the last row: the carry of that row,
+    wherever it is row 0 of the next buffer.  The pieces of a buffer cut at row s (obs[:s + 1], ended[:s] | obs[s:], ended[s:]),
+    chained through the carry, give the rows of the whole."""
     obs = np.asarray(obs)
     if obs.ndim != 3 or obs.shape[2] != 16:
         raise ValueError(f"stack_rows_reference: obs must be [R, N, 16], got {obs.shape}")
@@ -459,12 +474,23 @@ def stack_rows_reference(obs, ended=None):
         out[t, :, 16:26] = obs[i1, cols, 0:10]
         out[t, :, 26:36] = obs[i2, cols, 0:10]
         out[t, :, 36:38] = obs[i1, cols, 10:12]
-    return out
+    if carry is None:
+        return out
+    carry = np.asarray(carry, dtype=np.float32)
+    if carry.shape != (N, HIST_CARRY):
+        raise ValueError(f"stack_rows_reference: carry must be [{N}, {HIST_CARRY}], got {carry.shape}")
+    out[0, :, 16:38] = carry.astype(obs.dtype)          # row 0: what lay in front of it
+    if R > 1:                                           # row 1, unless it starts an episode: its oldest frame is row -1's scan
+        keep = ~end[0]
+        out[1, keep, 26:36] = carry[keep, 0:10].astype(obs.dtype)
+    return out, out[R - 1, :, 16:38].astype(np.float32)
 
 
-def stack_rows(obs, ended=None, out=None):
+def stack_rows(obs, ended=None, out=None, carry_in=None, carry_out=None):
     """navsim_stack_rows on device tensors: obs [R, N, 16] float32 or float16, ended [R - 1, N] uint8 (None allowed when R == 1)
-    -> [R, N, 42] of obs's dtype (``out`` if given); stack_rows_reference states the rule.  Asynchronous on the current stream."""
+    -> [R, N, 42] of obs's dtype (``out`` if given); stack_rows_reference states the rule.  Asynchronous on the current stream.
+    carry_in / carry_out ([N, 22] float32, either may be None, both may be one tensor): navsim_stack_rows_cont -- row 0 continues
+    from carry_in instead of starting the episodes, carry_out receives the carry of the last row."""
     if not torch.is_tensor(obs) or not obs.is_cuda:
         raise NavsimError("stack_rows needs device tensors; there is no CPU path (stack_rows_reference is the host mirror)")
     if obs.dim() != 3 or obs.shape[2] != 16 or obs.dtype not in (torch.float32, torch.float16) or not obs.is_contiguous():
@@ -480,9 +506,15 @@ def stack_rows(obs, ended=None, out=None):
     elif (not torch.is_tensor(out) or out.device != obs.device or out.dtype != obs.dtype or out.numel() != R * N * HIST_DIM
           or not out.is_contiguous()):
         raise NavsimError(f"stack_rows: out must be {R * N * HIST_DIM} contiguous {obs.dtype} values on {obs.device}")
+    _chk_carry("stack_rows: carry_in", carry_in, N, obs.device)
+    _chk_carry("stack_rows: carry_out", carry_out, N, obs.device)
     with torch.cuda.device(obs.device):
-        check(lib().navsim_stack_rows(_ptr(obs), int(obs.dtype == torch.float16), _ptr(ended), R, N, _ptr(out), _stream()),
-              "navsim_stack_rows")
+        if carry_in is None and carry_out is None:
+            check(lib().navsim_stack_rows(_ptr(obs), int(obs.dtype == torch.float16), _ptr(ended), R, N, _ptr(out), _stream()),
+                  "navsim_stack_rows")
+        else:
+            check(lib().navsim_stack_rows_cont(_ptr(obs), int(obs.dtype == torch.float16), _ptr(ended), R, N, _ptr(out),
+                                               _ptr(carry_in), _ptr(carry_out), _stream()), "navsim_stack_rows_cont")
     return out
 
 
@@ -634,7 +666,7 @@ class VecEnv:
         return out
 
 
-    def rollout_mlp64(self, actor_params, n_steps, var, seed=0, step_base=0, obs0=None, history=False):
+    def rollout_mlp64(self, actor_params, n_steps, var, seed=0, step_base=0, obs0=None, history=False, hist_in=None, hist_out=None):
         """PPO.rollout's hot loop (ppo.py:505-594) for the (B + 6)-64-64 policy in ONE launch (navsim_rollout_mlp64): per step
         PPO.get_action (ppo.py:673-706) on the observation the previous step left on chip, then the env step.
         actor_params: flat float32 device tensor [5378] (10 beams) / [7042] (36 beams) in nn.Module.named_parameters order
@@ -643,7 +675,11 @@ class VecEnv:
         [T + 1, N, B + 6] (row 0 = obs0; float16 on an obs_f16 env), act [T, N, 2], logp / reward / done / arrive / ended /
         ep_return / ep_length / ep_path [T, N] -- bit-identical to T pairs of navppo_mlp64_act / step calls.
         history=True (10 beams): navsim_rollout_mlp64_hist -- actor_params is the [7042] 42-64-64 actor, which reads the scan-history
-        row of every step (stack_rows_reference); every returned buffer keeps its shape, obs stays [T + 1, N, 16]."""
+        row of every step (stack_rows_reference); every returned buffer keeps its shape, obs stays [T + 1, N, 16].
+        hist_in / hist_out (history=True; [N, 22] float32, either may be None, both may be one tensor): navsim_rollout_mlp64_hist_cont
+        -- obs0 continues the envs' episodes with the history carry hist_in (None: obs0 starts them), hist_out receives the carry of
+        row T.  A rollout cut in pieces (obs0 = the previous piece's last row, step_base advanced, the carry handed on) writes the
+        bits of the whole."""
         import ctypes as C
         from ._native import check, lib
         if self.B not in (10, 36):
@@ -652,7 +688,12 @@ class VecEnv:
             raise NavsimError("rollout_mlp64(history=True) needs 10 beams: the history row stacks 10-beam scans")
         T, N, D, dev = int(n_steps), self.N, self.D, self.device
         n_actor = 64 * (HIST_DIM if history else D) + 64 + 64 * 64 + 64 + 2 * (64 + 1)
-        entry = "navsim_rollout_mlp64_hist" if history else "navsim_rollout_mlp64"
+        cont = hist_in is not None or hist_out is not None
+        if cont and not history:
+            raise NavsimError("rollout_mlp64: hist_in / hist_out need history=True")
+        _chk_carry("rollout_mlp64: hist_in", hist_in, N, dev)
+        _chk_carry("rollout_mlp64: hist_out", hist_out, N, dev)
+        entry = ("navsim_rollout_mlp64_hist_cont" if cont else "navsim_rollout_mlp64_hist") if history else "navsim_rollout_mlp64"
         prm = actor_params.to(device=dev, dtype=torch.float32).contiguous()
         if prm.numel() != n_actor or prm.data_ptr() % 16:
             raise NavsimError(f"actor_params: {n_actor} float32 values, 16-byte aligned")
@@ -674,7 +715,7 @@ class VecEnv:
         with torch.cuda.device(dev):
             check(getattr(lib(), entry)(self.sim._h, p(prm), p(out.obs), p(out.act), p(out.logp), p(out.reward), p(out.done),
                                         p(out.arrive), p(out.ended), p(out.ep_return), p(out.ep_length), p(out.ep_path), p(var_t),
-                                        int(seed) & 0xFFFFFFFFFFFFFFFF, p(base_t), T,
+                                        int(seed) & 0xFFFFFFFFFFFFFFFF, p(base_t), T, *((_ptr(hist_in), _ptr(hist_out)) if cont else ()),
                                         C.c_void_p(torch.cuda.current_stream().cuda_stream)), entry)
             torch.cuda.current_stream().synchronize()   # var_t / base_t / prm may be temporaries of this call
         return out

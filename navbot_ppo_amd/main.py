@@ -18,7 +18,7 @@ batch, shuffled on the device), --norm_reward / --clip_reward C (rewards scaled 
 return and clipped to +-C before the return scan), --lr_schedule adaptive|linear with --desired_kl / --lr_min / --lr_max (the KL-adaptive
 step size decided on the device after every optimiser step, or a linear decay over --max_timesteps), --bootstrap_truncated (time-outs
 bootstrap with gamma V of their own row and the batch end with V of the next observation instead of counting as terminal), --movers NAME / --movers_period P (moving obstacles beside the static map, training and evaluation; NAME random:K with --movers_seed or bank:a,b,... is a bank of scenarios, one per env), --eval_movers NAME / --eval_movers_seed (held-out scenarios for --eval_every), --scan_history (the mlp64x2 policy reads the last three
-scans).  Vision flags are accepted and refused (the camera
+scans), --continue_rollouts (only the first rollout resets the envs; later ones go on where the last stopped).  Vision flags are accepted and refused (the camera
 modality is outside the LiDAR hot path); --mode test maps to --eval (the reference's test path is broken).
 """
 import argparse
@@ -94,6 +94,9 @@ def get_args(argv=None):
     p.add_argument("--scan_history", action="store_true", default=False,
                    help="the mlp64x2 policy reads the last three LiDAR scans and the action between them (a 42-column row assembled on "
                         "the device, never across an episode start) instead of one scan; needs --policy mlp64x2; default: off")
+    p.add_argument("--continue_rollouts", action="store_true", default=False,
+                   help="only the first rollout starts from a reset: every later one continues the envs' episodes across the iteration "
+                        "boundary (short rollouts on many envs); needs --bootstrap_truncated; default: off, as in the reference")
     args = p.parse_args(argv)
     if args.output_dir is None:
         args.output_dir = os.path.join(os.getcwd(), "runs")
@@ -105,9 +108,10 @@ def get_args(argv=None):
 
 
 def schedule(args, world=1):
-    """(n_envs_total, rollout_len): steps_per_iteration timesteps per batch spread over the envs.  Every rollout starts from a
-    reset (ppo.py:486), so a rollout shorter than the episode cap could never finish a timed-out episode: by default the
-    env count is chosen so that rollout_len >= timesteps_per_episode (5000/500 -> 10 envs x 500 steps; 2 M/500 -> 4096 x 512)."""
+    """(n_envs_total, rollout_len): steps_per_iteration timesteps per batch spread over the envs.  By default every rollout starts
+    from a reset (ppo.py:486), so a rollout shorter than the episode cap could never finish a timed-out episode: the env count is
+    chosen so that rollout_len >= timesteps_per_episode (5000/500 -> 10 envs x 500 steps; 2 M/500 -> 4096 x 512).  With
+    --continue_rollouts the episodes run on across the batches and --n_envs may make the rollout as short as it likes."""
     if args.n_envs:
         n_envs = args.n_envs
     else:
@@ -127,6 +131,7 @@ def config_of(args, rollout):
                          norm_reward=args.norm_reward, clip_reward=args.clip_reward, lr_schedule=args.lr_schedule,
                          desired_kl=args.desired_kl, lr_min=args.lr_min, lr_max=args.lr_max,
                          bootstrap_truncated=args.bootstrap_truncated, scan_history=args.scan_history,
+                         continue_rollouts=args.continue_rollouts,
                          eval_movers=movers_of(args.eval_movers, args.movers_period, args.eval_movers_seed))
 
 

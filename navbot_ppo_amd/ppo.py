@@ -33,8 +33,8 @@ lr_schedule.py, the ranks in distributed.py.
 """
 import torch.distributed as dist  # noqa: F401
 
-from .config import (LR_SCHEDULES, MINIBATCH_SHUFFLES, PPOConfig, check_bootstrap_config, check_lr_schedule_config,  # noqa: F401
-                     check_minibatch_config, check_reward_norm_config, check_scan_history_config, check_update_config)
+from .config import (LR_SCHEDULES, MINIBATCH_SHUFFLES, PPOConfig, check_bootstrap_config, check_continue_config,  # noqa: F401
+                     check_lr_schedule_config, check_minibatch_config, check_reward_norm_config, check_scan_history_config, check_update_config)
 from .distributed import DistCtx, SingleProcessCtx, as_ctx, global_mean  # noqa: F401
 from .lr_schedule import LR_FACTOR, adaptive_lr_direction, adaptive_lr_reference, linear_lr  # noqa: F401
 from .minibatch import batch_permutation, minibatch_counter, minibatch_key  # noqa: F401

@@ -8,7 +8,7 @@ import torch
 
 from . import nets
 from ._native import _navppo, _ptr, check, lib
-from .config import PPOConfig, check_bootstrap_config, check_reward_norm_config, check_scan_history_config
+from .config import PPOConfig, check_bootstrap_config, check_continue_config, check_reward_norm_config, check_scan_history_config
 from .distributed import as_ctx
 from .lr_schedule import linear_lr
 from .reward_norm import RET_RMS_INIT, return_moments, reward_scale
@@ -63,6 +63,18 @@ class PPOTrainer:
         self.rtg_buf = torch.zeros((T, N), dtype=f32, device=dev)
         check_reward_norm_config(cfg)
         check_bootstrap_config(cfg)
+        check_continue_config(cfg)
+        # continue_rollouts (off: not one tensor or launch more than before): whether the next rollout must reset, the generation of
+        # the world the envs were last reset in, with scan_history the two history carries that take turns -- [0] belongs to row 0 of
+        # the batch at hand, [1] receives row T's -- and with norm_reward the running return behind the last row (SB3's self.returns)
+        self.continue_rollouts = cfg.continue_rollouts
+        self._reset_pending, self._reset_gen, self._did_reset = True, None, True
+        if self.continue_rollouts:
+            if self.scan_history:
+                from .env import HIST_CARRY
+                self._hist_carry = [torch.zeros((N, HIST_CARRY), dtype=f32, device=dev) for _ in range(2)]
+            if cfg.norm_reward:
+                self._ret_carry = torch.zeros(N, dtype=torch.float64, device=dev)
         if cfg.norm_reward:   # (off: not one tensor, launch or read-back more than before)
             self._init_ret_rms(dev)
             self.rew_scaled_buf = torch.zeros((T, N), dtype=f32, device=dev)   # what the scans read; rew_buf keeps the raw rewards
@@ -103,14 +115,16 @@ class PPOTrainer:
 
     def _normalise_rewards(self):
         """Behind the rollout, in front of the return scan: this rank's (n, mean, M2) of the rollout's running returns (carry-in 0:
-        every rollout starts from a reset), every rank's row gathered by ONE all-reduce of a zero-filled [world, 3] tensor (adding
+        the rollout starts from a reset -- or, with continue_rollouts, the running return the last rollout left, zeroed whenever the
+        envs are reset), every rank's row gathered by ONE all-reduce of a zero-filled [world, 3] tensor (adding
         zeros is exact), all rows merged in rank order on every rank -- bit-identical statistics -- and the rollout scaled by them.
         Two entry points, no host round trip."""
         cfg, ctx = self.cfg, self.ctx
         rows = self._ret_rows
         if ctx.enabled and rows.shape[0] > 1:
             rows.zero_()
-        return_moments(self.rew_buf, self.ended_buf, cfg.gamma, out=rows[ctx.rank])
+        carry = getattr(self, "_ret_carry", None)   # (there with continue_rollouts alone)
+        return_moments(self.rew_buf, self.ended_buf, cfg.gamma, carry=carry, out=rows[ctx.rank])
         ctx.all_reduce_sum(rows)
         return reward_scale(self.ret_rms, rows, self.rew_buf, clip=cfg.clip_reward, eps=cfg.norm_reward_eps, out=self.rew_scaled_buf)
 
@@ -148,11 +162,15 @@ class PPOTrainer:
         kernel; same device functions and Philox keys as the per-step path, so the buffers come out bit-identical."""
         sim = self.env.sim
         name = "navsim_rollout_" + ("resmlp512" if self.updater.fused_resmlp512 else "mlp64_hist" if self.scan_history else "mlp64")
+        carries = ()
+        if self.scan_history and self.continue_rollouts:   # the carry of row 0 in (none behind a reset), the carry of row T out
+            name += "_cont"
+            carries = (None if self._did_reset else _ptr(self._hist_carry[0]), _ptr(self._hist_carry[1]))
         with torch.cuda.device(self.device):
             check(getattr(lib(), name)(sim._h, _ptr(self.updater.fp.flat), _ptr(self.obs_buf), _ptr(self.act_buf), _ptr(self.logp_buf),
                                        _ptr(self.rew_buf), _ptr(self.done_buf), _ptr(self.arrive_buf), _ptr(self.ended_buf),
                                        _ptr(self.epret_buf), _ptr(self.eplen_buf), _ptr(self.eppath_buf), _ptr(self.var), self._act_seed,
-                                       _ptr(self._step_base), self.cfg.rollout_len,
+                                       _ptr(self._step_base), self.cfg.rollout_len, *carries,
                                        C.c_void_p(torch.cuda.current_stream().cuda_stream)), name)
         self._step_base += self.cfg.rollout_len
 
@@ -181,14 +199,15 @@ class PPOTrainer:
         self.epret_buf.zero_()
         self.eplen_buf.zero_()
         self.updater.invalidate_prepared()   # the kernels below rewrite obs_buf behind torch's version counter
-        self.env.sim.reset(self.obs_buf[0])  # ppo.py:486: every batch starts from a reset
+        graph_path = not self.uses_persistent_rollout and cfg.use_graph and self.device.type == "cuda"
+        if graph_path and self._graph is not None and self._graph_gen != self.env.sim.generation:
+            self._graph = None   # set_map / set_spawn_sampler / set_goal_rects re-allocated what the capture froze
+        self._begin_rollout(capturing=graph_path and self._graph is None)
         # (round 5: both rollout kernels have the tile-box cast of shared 65..4096-segment maps; until then shards up to 4096 envs on
         # such a map took the hipGraph of per-step launches)
         if self.uses_persistent_rollout:
             self._persistent_rollout()
-        elif cfg.use_graph and self.device.type == "cuda":
-            if self._graph is not None and self._graph_gen != self.env.sim.generation:
-                self._graph = None   # set_map / set_spawn_sampler / set_goal_rects re-allocated what the capture froze
+        elif graph_path:
             if self._graph is None:
                 self._graph_gen = self.env.sim.generation
                 s = torch.cuda.Stream(self.device)
@@ -197,7 +216,7 @@ class PPOTrainer:
                     self._rollout_step(0)
                 torch.cuda.current_stream().wait_stream(s)
                 torch.cuda.synchronize()
-                self.env.sim.reset(self.obs_buf[0])
+                self.env.sim.reset(self.obs_buf[0])   # (the warm-up stepped the envs; _begin_rollout made this a rollout that resets)
                 self._graph = torch.cuda.CUDAGraph()
                 # thread_local: other threads (the RCCL watchdog of torch.distributed) may touch the HIP runtime while
                 # this thread captures; the default global mode would turn that into a capture error on multi-GPU runs
@@ -210,7 +229,11 @@ class PPOTrainer:
         if self.scan_history:   # the batch the nets read, [T + 1, N, 42]: one bandwidth kernel per iteration
             from .env import stack_rows
             self.updater.invalidate_prepared()   # hist_buf is rewritten behind torch's version counter too
-            stack_rows(self.obs_buf, self.ended_buf, out=self.hist_buf)
+            if self.continue_rollouts:   # row 0 continues from its carry, so hist_buf[T] is the exact row the value bootstrap reads
+                stack_rows(self.obs_buf, self.ended_buf, out=self.hist_buf, carry_in=None if self._did_reset else self._hist_carry[0])
+                self._hist_carry.reverse()   # what the launch wrote for row T is the next batch's row 0's
+            else:
+                stack_rows(self.obs_buf, self.ended_buf, out=self.hist_buf)
         self._gae = None
         rew = self._normalise_rewards() if cfg.norm_reward else self.rew_buf   # (the scans below are the same either way)
         trunc, lam = cfg.bootstrap_truncated, cfg.gae_lambda
@@ -237,6 +260,27 @@ class PPOTrainer:
             self.rtg_buf.copy_(ret)
             self._gae = (adv.reshape(T * N), V.reshape(T * N))
         self.env_steps += cfg.rollout_len * self.env.N
+
+    def reset_envs(self):
+        """continue_rollouts: the next rollout starts from a reset of all envs (as the first one does, and the one behind a change of
+        the world or load_checkpoint).  Without the option every rollout does anyway."""
+        self._reset_pending = True
+
+    def _begin_rollout(self, capturing=False):
+        """Row 0 of the batch.  ppo.py:486: every batch starts from a reset -- the rule unless continue_rollouts, and then still the
+        rule of the first rollout, of one behind reset_envs() / load_checkpoint, of one in a world whose generation changed and of
+        one that captures its graph (the warm-up steps the envs).  Otherwise the envs go on: the handle holds their state, and the
+        observations they stopped at, row T of the last batch, become row 0."""
+        sim = self.env.sim
+        self._did_reset = (not self.continue_rollouts or self._reset_pending or capturing or self._reset_gen != sim.generation)
+        if self._did_reset:
+            sim.reset(self.obs_buf[0])
+            if self.continue_rollouts:
+                self._reset_pending, self._reset_gen = False, sim.generation
+                if self.cfg.norm_reward:
+                    self._ret_carry.zero_()
+        else:
+            self.obs_buf[0].copy_(self.obs_buf[self.cfg.rollout_len])
 
     def _decay_exploration(self):
         """ppo.py:694-695 multiplies the covariance by 0.995 at every episode start once t_so_far > 50000 while
@@ -269,7 +313,7 @@ class PPOTrainer:
     def _rollout_metrics(self, m=None):
         m = self._rollout_metrics_dev() if m is None else m   # (a tensor, or the six figures already on the host)
         ep, succ, coll, tmo, steps, ret = [float(x) for x in (m.tolist() if torch.is_tensor(m) else m)]
-        self.episode_starts = ep / self.ctx.world + self.env.N
+        self.episode_starts = ep / self.ctx.world + (self.env.N if getattr(self, "_did_reset", True) else 0)   # (the reset started N episodes)
         return dict(episodes=int(ep), successes=int(succ), collisions=int(coll), timeouts=int(tmo),
                     completed_steps=int(steps), avg_ep_rews=(ret / ep if ep else 0.0),       # ppo.py:833
                     avg_ep_lens=(steps / ep if ep else 0.0), success_rate=(succ / ep if ep else 0.0))
@@ -628,6 +672,7 @@ class PPOTrainer:
         """main.py:52-89: state_dicts only (optimiser state and covariance are not part of a checkpoint).  With norm_reward the return
         statistics come from retnorm_<tag>.pth beside the actor's file; without that file: one warning line and fresh statistics.
         With lr_schedule="adaptive" the learning rate comes from lrsched_<tag>.pth; without that file: one warning line and cfg.lr."""
+        self.reset_envs()   # (continue_rollouts: the episodes under way were the old weights')
         if self.cfg.lr_schedule == "adaptive":
             s = self._load_sidecar("lrsched", actor_path,
                                    "lr_schedule='adaptive': {} not found -- the learning rate starts at lr = " + str(self.cfg.lr))
