@@ -83,6 +83,26 @@ int navppo_adam_step(float* params_dev, const float* grad_dev, float* adam_m_dev
 int navppo_episode_sums(const uint8_t* ended_dev, const uint8_t* arrive_dev, const uint8_t* done_dev, const int32_t* ep_length_dev,
                         const float* ep_return_dev, int64_t n, double* sums_dev, void* workspace_dev, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------------
+ * Per-group episode sums (csrc/ppo_group_sums.hip): navppo_episode_sums per GROUP of envs -- the scenario an env plays, its tape id
+ * of a mover bank -- over the [T, N] buffers a rollout fills.  group_dev [N] i32: the group of every env.  sums_dev [K][8] f64, row k
+ * over the columns n with group[n] == k:
+ *   0 episodes (ended)   1 successes (arrive and ended)   2 collisions (done, not arrive, ended)   3 time-outs (ended, neither)
+ *   4 sum of ep_length over all entries   5 sum of ep_return over ended entries   (entry by entry navppo_episode_sums' figures)
+ *   6 sum of |adv| over all entries (adv_dev [T, N] f32, nullable: then 0)        7 rows: T x the number of envs of the group
+ * A group without envs gives a zero row; an id outside [0, K) is counted in no row (and indexes nothing).  1 <= K <= 1024, T, N >= 1.
+ * Columns 0..4 and 7 are exact integers; summed over k, columns 0..5 are navppo_episode_sums' (5 up to the summation order).
+ * No atomics: every column's partial sums per chunk of T are stored to the workspace, then one workgroup per group adds its columns'
+ * partials in ascending env order and a fixed tree -- two calls on the same buffers give the same bits.
+ * ep_length / ep_return / adv / group 4-byte, sums / workspace 8-byte aligned.  workspace_dev: navppo_group_sums_ws_bytes(T, N, K)
+ * bytes (0 = sizes the entry point refuses).  Null required pointers, bad sizes, a null workspace: -1 and navppo_last_error().
+ */
+#define NAVPPO_GROUP_SUMS_COLS 8
+size_t navppo_group_sums_ws_bytes(int32_t T, int32_t N, int32_t K);
+int navppo_group_sums(const uint8_t* ended_dev, const uint8_t* arrive_dev, const uint8_t* done_dev, const int32_t* ep_length_dev,
+                      const float* ep_return_dev, const float* adv_dev, const int32_t* group_dev, int32_t T, int32_t N, int32_t K,
+                      double* sums_dev, void* workspace_dev, void* stream);
+
 /* V = critic(obs).squeeze() (ppo.py:275, :724) for n rows: the forward half of the critic's fused pass.  value_dev [n] f32. */
 int navppo_mlp64_value(const float* critic_params_dev, const void* obs_dev, int32_t obs_dim, int32_t obs_f16, int64_t n_samples,
                        float* value_dev, void* stream);

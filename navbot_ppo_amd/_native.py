@@ -127,6 +127,8 @@ SYMBOLS = [
     ("navppo_shuffle_batch", C.c_int, [_vp, _i32, _i32] + [_vp] * 4 + [C.c_int64, C.c_uint64, C.c_uint64] + [_vp] * 7),
     ("navppo_return_moments", C.c_int, [_vp, _vp, _i32, _i32, _d, _vp, _vp, _vp]),
     ("navppo_reward_scale", C.c_int, [_vp, _vp, _i32, _vp, _vp, C.c_int64, _d, _d, _vp]),
+    ("navppo_group_sums_ws_bytes", C.c_size_t, [_i32, _i32, _i32]),
+    ("navppo_group_sums", C.c_int, [_vp] * 7 + [_i32, _i32, _i32, _vp, _vp, _vp]),
     ("navppo_resmlp512_value", C.c_int, [_vp, _vp, _i32, C.c_int64, _vp, _vp, _vp]),
     ("navppo_resmlp512_act", C.c_int, [_vp, _vp, _i32, _vp, C.c_int64, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint32, _vp, _vp, _vp, _vp]),
 ]

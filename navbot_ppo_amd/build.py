@@ -9,7 +9,8 @@ REPO = os.path.dirname(HERE)
 # (csrc/navppo_internal.h, NAVPPO_KL_TU), in a translation unit of its own so that the ungated kernels' listings stay what they were
 SRCS = [os.path.join(HERE, "csrc", f) for f in ("navsim.hip", "ppo_mlp64.hip", "ppo_resmlp512.hip", "ppo_mlp64_kl.hip", "ppo_resmlp512_kl.hip",
                                                    "ppo_shuffle.hip",    # ppo_shuffle.hip: navppo_shuffle_batch (minibatch updates)
-                                                   "ppo_reward_norm.hip")]   # navppo_return_moments, navppo_reward_scale (norm_reward)
+                                                   "ppo_reward_norm.hip",    # navppo_return_moments, navppo_reward_scale (norm_reward)
+                                                   "ppo_group_sums.hip")]    # navppo_group_sums (scenario_stats / scenario_priority)
 HDRS = ["navsim.h", "navppo.h"]
 INC = os.path.join(REPO, "include")
 # what every object depends on besides its own source: the public headers, the csrc headers and the two sources the *_kl twins include

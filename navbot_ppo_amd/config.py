@@ -5,6 +5,7 @@ import math
 
 MINIBATCH_SHUFFLES = ("epoch", "update", "none")
 LR_SCHEDULES = (None, "adaptive", "linear")
+SCENARIO_PRIORITIES = (None, "failure", "abs_adv")
 
 
 @dataclasses.dataclass
@@ -104,6 +105,20 @@ class PPOConfig:
     # the spawn sampler, ...), after load_checkpoint and on PPOTrainer.reset_envs().  Needs a batch end that is not terminal:
     # bootstrap_truncated=True or gae_lambda < 1.
     continue_rollouts: bool = False
+    # Training on a bank of mover tapes (VecEnv movers="random:K", "bank:...", dict(bank=...); at least 2 tapes).  scenario_stats: one
+    # navppo_group_sums launch per iteration sums the rollout per scenario on the device; its [K, 8] table rides on the iteration's one
+    # all-reduce and one read-back, the log gains train_scenario_success_min / _mean and rank 0 appends <method>_train_scenarios.csv.
+    # scenario_priority (implies the statistics): every scenario_resample_every iterations the envs are re-assigned to the scenarios by
+    # rank-prioritised level replay (scenarios.ScenarioSampler) on a score per scenario -- "failure": 1 - success rate, "abs_adv": the
+    # mean |advantage| (needs gae_lambda or bootstrap_truncated) -- an exponential average with weight scenario_score_alpha on the newest
+    # iteration; weights (1 / rank)^(1 / scenario_temperature), mixed with the uniform distribution by scenario_uniform_mix.  A
+    # re-assignment changes the world: with continue_rollouts the next rollout resets.  Both off: nothing differs.
+    scenario_stats: bool = False
+    scenario_priority: str = None
+    scenario_resample_every: int = 1
+    scenario_score_alpha: float = 0.5
+    scenario_temperature: float = 0.3
+    scenario_uniform_mix: float = 0.25
 
     def __post_init__(self):
         check_minibatch_config(self)
@@ -112,6 +127,29 @@ class PPOConfig:
         check_bootstrap_config(self)
         check_scan_history_config(self)
         check_continue_config(self)
+        check_scenario_config(self)
+
+
+def check_scenario_config(cfg):
+    """PPOConfig.scenario_stats / scenario_priority and their parameters, at the construction of the config and again of the trainer
+    (a config is mutable).  What needs the env -- a bank of at least 2 tapes -- is checked by the trainer."""
+    if not isinstance(cfg.scenario_stats, bool):
+        raise ValueError(f"scenario_stats {cfg.scenario_stats!r}: True or False")
+    if cfg.scenario_priority not in SCENARIO_PRIORITIES:
+        raise ValueError(f"scenario_priority {cfg.scenario_priority!r}: one of {SCENARIO_PRIORITIES}")
+    every = cfg.scenario_resample_every
+    if isinstance(every, bool) or not isinstance(every, int) or every < 1:
+        raise ValueError(f"scenario_resample_every {every!r}: an integer >= 1")
+    for name in ("scenario_score_alpha", "scenario_uniform_mix"):
+        v = getattr(cfg, name)
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0.0 <= v <= 1.0:   # (NaN fails the comparison too)
+            raise ValueError(f"{name} {v!r}: a number in [0, 1]")
+    b = cfg.scenario_temperature
+    if isinstance(b, bool) or not isinstance(b, (int, float)) or not (0.0 < b < float("inf")):
+        raise ValueError(f"scenario_temperature {b!r}: a finite number > 0")
+    if cfg.scenario_priority == "abs_adv" and cfg.gae_lambda is None and not cfg.bootstrap_truncated:
+        raise ValueError("scenario_priority='abs_adv' needs the raw advantages in the trainer: set gae_lambda or bootstrap_truncated "
+                         "(the reference's A = rtg - V is formed inside the update)")
 
 
 def check_continue_config(cfg):

@@ -77,6 +77,7 @@ class NavSim:
             check(lib().navsim_create(C.byref(self.cfg), C.byref(self._h)), "navsim_create")
         self._seg = None  # keeps the map tensor alive: the handle only borrows the pointer
         self._mov_tape = self._mov_phase0 = None   # the same for the mover tape (set_movers)
+        self._mov_bank = None   # set_mover_bank's host arrays (periods, rectangles), for set_mover_assignment
         self.movers_period = self.movers_segments = 0
         self.movers_tapes, self.movers_tape_id = 0, None   # set_mover_bank: tapes in the bank, the envs' tape ids (None = all 0)
         self.generation = 0  # bumped whenever device pointers / scalars a captured hipGraph would have frozen change
@@ -146,7 +147,7 @@ class NavSim:
         if tape is None:
             with torch.cuda.device(self.device):
                 check(lib().navsim_set_movers(self._h, None, 0, 0, None, _stream()), "navsim_set_movers")
-            self._mov_tape = self._mov_phase0 = None
+            self._mov_tape = self._mov_phase0 = self._mov_bank = None
             self.movers_period = self.movers_segments = 0
             self.movers_tapes, self.movers_tape_id = 0, None
             self.generation += 1
@@ -167,7 +168,7 @@ class NavSim:
         with torch.cuda.device(self.device):
             check(lib().navsim_set_movers(self._h, _ptr(tape), int(tape.shape[0]), int(tape.shape[1]), _ptr(phase0), _stream()),
                   "navsim_set_movers")
-        self._mov_tape, self._mov_phase0 = tape, phase0
+        self._mov_tape, self._mov_phase0, self._mov_bank = tape, phase0, None
         self.movers_period, self.movers_segments = int(tape.shape[0]), int(tape.shape[1])
         self.movers_tapes, self.movers_tape_id = 1, None
         self.generation += 1
@@ -217,9 +218,22 @@ class NavSim:
             check(lib().navsim_set_mover_bank(self._h, _ptr(bank), K, Pmax, M, _np_ptr(per), _ptr(tape_id), _ptr(phase0),
                                               _np_ptr(rects), n_rects, _stream()), "navsim_set_mover_bank")
         self._mov_tape, self._mov_phase0 = bank, phase0
+        self._mov_bank = (per, rects, n_rects)   # what set_mover_assignment hands in again (host copies)
         self.movers_period, self.movers_segments = Pmax, M
         self.movers_tapes, self.movers_tape_id = K, tape_id
         self.generation += 1
+
+    def set_mover_assignment(self, tape_id, phase0=None):
+        """Re-points the envs at the tapes of the bank the handle already holds: tape_id [N] integers in [0, K), phase0 [N] integers in
+        [0, periods[tape_id[i]]) (None: all 0).  The bank on the device, the periods and the goal rectangles stay what set_mover_bank
+        was given (the same navsim_set_mover_bank entry point with the same bank pointer: no upload of the bank); the per-env spawn
+        scans are rebuilt for the new tapes and phases.  The world changed: ``generation`` is bumped.  Waits for the stream."""
+        if self._mov_bank is None:
+            raise NavsimError("set_mover_assignment: the handle holds no bank of tapes (call set_mover_bank first)")
+        if tape_id is None:
+            raise NavsimError("set_mover_assignment: tape_id: required")
+        per, rects, _ = self._mov_bank
+        self.set_mover_bank(self._mov_tape, per, tape_id, phase0, rects)
 
     def set_goal_rects(self, which, rects):
         r = np.ascontiguousarray(rects, dtype=np.float64).reshape(-1, 4)
@@ -625,9 +639,12 @@ class VecEnv:
             if isinstance(sampler, str):
                 sampler = _maps.spawn_tables(sampler)
             self.sim.set_spawn_sampler(*sampler)
+        self.mover_bank = None   # the resolved bank of tapes, if the movers are one (assign_scenarios)
+        self._mover_phase, self._map_seed, self._env_id_base = "random", map_seed, env_id_base
         if movers is not None:
             tape, phase = _maps.resolve_movers(movers)
             if isinstance(tape, _maps.MoverBank):   # one scenario per env: ids and phases from (map_seed, global env id) only
+                self.mover_bank, self._mover_phase = tape, phase
                 ids = tape.tape_ids(self.N, map_seed=map_seed, env_id_base=env_id_base)
                 phase0 = None if phase == "zero" else _maps.mover_bank_phases(tape.periods[ids], map_seed=map_seed, env_id_base=env_id_base)
                 self.sim.set_mover_bank(tape.bank, tape.periods, ids, phase0, tape.rects)
@@ -638,6 +655,22 @@ class VecEnv:
 
     def close(self):
         self.sim.close()
+
+    def assign_scenarios(self, ids):
+        """Gives every env another tape of the bank (NavSim.set_mover_assignment): ids [N] integers in [0, K), the phases redrawn by
+        the constructor's rule -- maps.mover_bank_phases of the new tapes' periods from (map_seed, global env id), or none for
+        phase="zero" -- so a shard still gives a global env what the single-GPU run gives it.  The envs keep their state; reset them
+        before stepping on (PPOTrainer does: the handle's generation changed)."""
+        if self.mover_bank is None:
+            raise NavsimError("assign_scenarios: the env's movers are not a bank of tapes")
+        K = len(self.mover_bank.periods)
+        ids = np.asarray(ids.cpu() if torch.is_tensor(ids) else ids)
+        if ids.shape != (self.N,) or not np.issubdtype(ids.dtype, np.integer) or ids.min() < 0 or ids.max() >= K:
+            raise NavsimError(f"assign_scenarios: {self.N} tape ids in [0, {K})")
+        ids = ids.astype(np.int32)
+        phase0 = None if self._mover_phase == "zero" else _maps.mover_bank_phases(
+            np.asarray(self.mover_bank.periods)[ids], map_seed=self._map_seed, env_id_base=self._env_id_base)
+        self.sim.set_mover_assignment(ids, phase0)
 
     def reset(self, mask=None):
         return self.sim.reset(self.io.obs, mask)

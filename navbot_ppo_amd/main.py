@@ -18,7 +18,10 @@ batch, shuffled on the device), --norm_reward / --clip_reward C (rewards scaled 
 return and clipped to +-C before the return scan), --lr_schedule adaptive|linear with --desired_kl / --lr_min / --lr_max (the KL-adaptive
 step size decided on the device after every optimiser step, or a linear decay over --max_timesteps), --bootstrap_truncated (time-outs
 bootstrap with gamma V of their own row and the batch end with V of the next observation instead of counting as terminal), --movers NAME / --movers_period P (moving obstacles beside the static map, training and evaluation; NAME random:K with --movers_seed or bank:a,b,... is a bank of scenarios, one per env), --eval_movers NAME / --eval_movers_seed (held-out scenarios for --eval_every), --scan_history (the mlp64x2 policy reads the last three
-scans), --continue_rollouts (only the first rollout resets the envs; later ones go on where the last stopped).  Vision flags are accepted and refused (the camera
+scans), --continue_rollouts (only the first rollout resets the envs; later ones go on where the last stopped), --scenario_stats /
+--scenario_priority failure|abs_adv with --scenario_resample_every / --scenario_score_alpha / --scenario_temperature /
+--scenario_uniform_mix (on a bank of scenarios: per-scenario training statistics from the device, and the envs re-assigned towards the
+scenarios that score worst).  Vision flags are accepted and refused (the camera
 modality is outside the LiDAR hot path); --mode test maps to --eval (the reference's test path is broken).
 """
 import argparse
@@ -97,6 +100,20 @@ def get_args(argv=None):
     p.add_argument("--continue_rollouts", action="store_true", default=False,
                    help="only the first rollout starts from a reset: every later one continues the envs' episodes across the iteration "
                         "boundary (short rollouts on many envs); needs --bootstrap_truncated; default: off, as in the reference")
+    p.add_argument("--scenario_stats", action="store_true", default=False,
+                   help="with a bank of scenarios (--movers random:K | bank:...): sum every rollout per scenario on the device, log the "
+                        "worst and the mean scenario's success rate and append <method>_train_scenarios.csv; default: off")
+    p.add_argument("--scenario_priority", type=str, default=None, choices=["failure", "abs_adv"],
+                   help="re-assign the envs to the scenarios of the bank by rank-prioritised level replay on a score per scenario: "
+                        "failure = 1 - success rate, abs_adv = mean |advantage| (needs --bootstrap_truncated); implies the statistics; "
+                        "default: off, every env keeps the scenario it was given")
+    p.add_argument("--scenario_resample_every", type=int, default=1, help="with --scenario_priority: iterations between re-assignments")
+    p.add_argument("--scenario_score_alpha", type=float, default=0.5,
+                   help="with --scenario_priority: the weight of the newest iteration in a scenario's running score, in [0, 1]")
+    p.add_argument("--scenario_temperature", type=float, default=0.3,
+                   help="with --scenario_priority: beta of the rank weights (1 / rank)^(1 / beta); smaller = sharper")
+    p.add_argument("--scenario_uniform_mix", type=float, default=0.25,
+                   help="with --scenario_priority: the share of the envs spread uniformly over the scenarios, in [0, 1]")
     args = p.parse_args(argv)
     if args.output_dir is None:
         args.output_dir = os.path.join(os.getcwd(), "runs")
@@ -131,7 +148,10 @@ def config_of(args, rollout):
                          norm_reward=args.norm_reward, clip_reward=args.clip_reward, lr_schedule=args.lr_schedule,
                          desired_kl=args.desired_kl, lr_min=args.lr_min, lr_max=args.lr_max,
                          bootstrap_truncated=args.bootstrap_truncated, scan_history=args.scan_history,
-                         continue_rollouts=args.continue_rollouts,
+                         continue_rollouts=args.continue_rollouts, scenario_stats=args.scenario_stats,
+                         scenario_priority=args.scenario_priority, scenario_resample_every=args.scenario_resample_every,
+                         scenario_score_alpha=args.scenario_score_alpha, scenario_temperature=args.scenario_temperature,
+                         scenario_uniform_mix=args.scenario_uniform_mix,
                          eval_movers=movers_of(args.eval_movers, args.movers_period, args.eval_movers_seed))
 
 

@@ -20,6 +20,9 @@ Follows ``project_ppo/src/ppo.py`` of the reference function by function, vector
                                     PPOConfig.lr_schedule: "adaptive" = the learning rate follows every step's approx_kl, decided
                                     on the device (navppo_*_update_epoch_lr; host mirror: adaptive_lr_reference); "linear" = decay
                                     over learn()'s budget, set per iteration
+                                    PPOConfig.scenario_stats / scenario_priority: on a bank of mover tapes the rollout is summed per
+                                    scenario on the device (navppo_group_sums; host mirror: group_sums_reference) and the envs are
+                                    re-assigned to the scenarios by rank-prioritised level replay (scenarios.ScenarioSampler)
   learn            ppo.py:218-461   iteration loop, timing, checkpoints (actor_iter%04d_step%08d.pth)
 
 Multi-GPU (absent in the reference): one process per GPU, each owns a contiguous shard
@@ -29,15 +32,17 @@ flat gradient buffer holding actor+critic; the advantage mean/std come from all-
 
 This module is the import surface and holds no code of its own: rollout, learn and the logging live in trainer.py (PPOTrainer), update
 and evaluate in updater.py (PPOUpdater), the options and their checks in config.py, the host mirrors in minibatch.py, reward_norm.py and
-lr_schedule.py, the ranks in distributed.py.
+lr_schedule.py, the per-scenario sums and the scenario sampler in scenarios.py, the ranks in distributed.py.
 """
 import torch.distributed as dist  # noqa: F401
 
-from .config import (LR_SCHEDULES, MINIBATCH_SHUFFLES, PPOConfig, check_bootstrap_config, check_continue_config,  # noqa: F401
-                     check_lr_schedule_config, check_minibatch_config, check_reward_norm_config, check_scan_history_config, check_update_config)
+from .config import (LR_SCHEDULES, MINIBATCH_SHUFFLES, SCENARIO_PRIORITIES, PPOConfig, check_bootstrap_config,  # noqa: F401
+                     check_continue_config, check_lr_schedule_config, check_minibatch_config, check_reward_norm_config,
+                     check_scan_history_config, check_scenario_config, check_update_config)
 from .distributed import DistCtx, SingleProcessCtx, as_ctx, global_mean  # noqa: F401
 from .lr_schedule import LR_FACTOR, adaptive_lr_direction, adaptive_lr_reference, linear_lr  # noqa: F401
 from .minibatch import batch_permutation, minibatch_counter, minibatch_key  # noqa: F401
 from .reward_norm import RET_RMS_INIT, merge_return_moments, return_moments, reward_norm_reference, reward_scale  # noqa: F401
+from .scenarios import GROUP_SUMS_COLS, ScenarioSampler, group_sums, group_sums_reference  # noqa: F401
 from .trainer import PPOTrainer  # noqa: F401
 from .updater import ADAM_HYPER, LOG_2PI, FlatParams, PPOUpdater, gaussian_log_prob, normalise_advantages, ppo_losses  # noqa: F401

@@ -8,7 +8,8 @@ import torch
 
 from . import nets
 from ._native import _navppo, _ptr, check, lib
-from .config import PPOConfig, check_bootstrap_config, check_continue_config, check_reward_norm_config, check_scan_history_config
+from .config import (PPOConfig, check_bootstrap_config, check_continue_config, check_reward_norm_config, check_scan_history_config,
+                     check_scenario_config)
 from .distributed import as_ctx
 from .lr_schedule import linear_lr
 from .reward_norm import RET_RMS_INIT, return_moments, reward_scale
@@ -17,6 +18,8 @@ from .updater import LOG_2PI, PPOUpdater, gaussian_log_prob
 
 class PPOTrainer:
     """PPO.learn for a ``VecEnv`` shard.  Construct one per process (= per GPU)."""
+
+    scenarios = None   # the ScenarioSampler of scenario_stats / scenario_priority (None: both off)
 
     def __init__(self, env, cfg=None, ctx=None):
         self.env, self.cfg = env, cfg or PPOConfig()
@@ -87,6 +90,10 @@ class PPOTrainer:
         self._step_base = torch.zeros((), dtype=torch.int32, device=dev)  # rollout steps taken so far (noise counter)
         self._act_seed = (cfg.seed * 0x9E3779B97F4A7C15 + 0xAC7) & 0xFFFFFFFFFFFFFFFF
         self._env_id_base = int(env.sim.cfg.env_id_base)
+        check_scenario_config(cfg)
+        self.scenarios = None   # (both options off: not one tensor, launch, collective or log key more than before)
+        if cfg.scenario_stats or cfg.scenario_priority is not None:
+            self._init_scenarios()
         self.t_so_far = 0     # completed-episode steps, as the reference counts (ppo.py:258)
         self.env_steps = 0    # all simulated steps
         self.i_so_far = 0
@@ -135,6 +142,88 @@ class PPOTrainer:
         tgt, v0 = self.rtg_buf.reshape(-1).double(), self.updater._last_V0.reshape(-1).double()
         ev = 1.0 - (tgt - v0).var(unbiased=False) / tgt.var(unbiased=False)
         return torch.cat([self.ret_rms, ev.reshape(1)])
+
+    # ---- PPOConfig.scenario_stats / scenario_priority: the rollout summed per scenario, and the envs re-assigned by what it shows
+    def _init_scenarios(self):
+        from .scenarios import GROUP_SUMS_COLS, ScenarioSampler
+        cfg, env, sim = self.cfg, self.env, self.env.sim
+        K = int(getattr(sim, "movers_tapes", 0) or 0)
+        if getattr(env, "mover_bank", None) is None or K < 2:
+            raise ValueError("scenario_stats / scenario_priority need an env whose movers are a bank of at least 2 tapes "
+                             "(VecEnv movers='random:K', 'bank:a,b,...' or dict(bank=...))")
+        if self.device.type != "cuda":
+            raise ValueError("scenario_stats / scenario_priority run on the GPU only: the sums are a HIP kernel's")
+        self._n_global = env.N * self.ctx.world   # (DistCtx.shard cuts the global envs into equal shards)
+        if self._env_id_base + env.N > self._n_global:
+            raise ValueError("scenario_stats / scenario_priority: the shards of the run must hold the same number of envs")
+        # stats alone: the score the table shows is the failure rate, and nothing is ever re-assigned
+        self.scenarios = ScenarioSampler(K, mode=cfg.scenario_priority or "failure", alpha=cfg.scenario_score_alpha,
+                                         temperature=cfg.scenario_temperature, uniform_mix=cfg.scenario_uniform_mix, seed=cfg.seed)
+        self._scen_K, self._scen_cols = K, GROUP_SUMS_COLS
+        self._scen_ws = torch.empty(int(lib().navppo_group_sums_ws_bytes(cfg.rollout_len, env.N, K)), dtype=torch.uint8, device=self.device)
+        self._scen_ids_host = None   # every rank's ids, on the host (filled when the table first needs them)
+
+    def _scenario_envs(self):
+        """[K] envs per scenario over ALL ranks (the table's column): from the sampler's last assignment, or -- nothing re-assigned yet
+        -- from the constructor's rule for every global env"""
+        import numpy as np
+        if self._scen_ids_host is None:
+            bank, env = self.env.mover_bank, self.env
+            if isinstance(bank.assign, str):
+                self._scen_ids_host = bank.tape_ids(self._n_global, map_seed=env._map_seed, env_id_base=0)
+            else:   # explicit ids: this rank's alone are known
+                self._scen_ids_host = env.sim.movers_tape_id.cpu().numpy()
+        return np.bincount(np.asarray(self._scen_ids_host), minlength=self._scen_K)
+
+    def _scenario_sums_dev(self):
+        """navppo_group_sums behind navppo_episode_sums: this rank's [K, 8] table, flat (the caller all-reduces it with the six sums)"""
+        from .scenarios import group_sums
+        T, N = self.cfg.rollout_len, self.env.N
+        adv = self._gae[0].reshape(T, N) if (self.cfg.scenario_priority == "abs_adv" and self._gae is not None) else None
+        return group_sums(self.ended_buf, self.arrive_buf, self.done_buf, self.eplen_buf, self.epret_buf, self.env.sim.movers_tape_id,
+                          self._scen_K, adv=adv, workspace=self._scen_ws).reshape(-1)
+
+    def _scenario_step(self, G):
+        """After the read-back (i_so_far already counts the iteration): the scores take in the iteration's global [K, 8] sums, the log
+        and the table are written, and -- with scenario_priority, every scenario_resample_every iterations -- the envs get their next
+        scenarios (the stream is idle)."""
+        import numpy as np
+        cfg, smp = self.cfg, self.scenarios
+        G = np.asarray(G, dtype=np.float64).reshape(self._scen_K, self._scen_cols)
+        smp.observe(G)
+        played = G[:, 0] > 0
+        rate = G[played, 1] / G[played, 0]
+        out = dict(train_scenario_success_min=float(rate.min()) if rate.size else float("nan"),
+                   train_scenario_success_mean=float(rate.mean()) if rate.size else float("nan"))
+        self.scenario_table = self.scenario_rows(G)
+        if cfg.output_dir and self.writes_files:
+            import csv
+            from .scenarios import SCENARIO_CSV_HEADER
+            os.makedirs(self.log_dir(), exist_ok=True)
+            path = os.path.join(self.log_dir(), f"{cfg.method_name}_train_scenarios.csv")
+            new = not os.path.exists(path)
+            with open(path, "a", newline="") as f:
+                w = csv.writer(f)
+                if new:
+                    w.writerow(SCENARIO_CSV_HEADER)
+                w.writerows([[r[h] for h in SCENARIO_CSV_HEADER] for r in self.scenario_table])
+        if cfg.scenario_priority is not None and self.i_so_far % cfg.scenario_resample_every == 0:
+            ids = smp.assign(self._n_global)
+            self._scen_ids_host = ids
+            self.env.assign_scenarios(ids[self._env_id_base:self._env_id_base + self.env.N])   # bumps sim.generation
+        return out
+
+    def scenario_rows(self, G):
+        """One dict per scenario for <method>_train_scenarios.csv: evaluate.scenario_report's fields (scenario, episodes and the success,
+        collision and time-out rate, NaN where no episode ended) plus iteration, envs, score and weight, from the global [K, 8] sums."""
+        envs, w, nan = self._scenario_envs(), self.scenarios.weights(), float("nan")
+        rows = []
+        for k in range(self._scen_K):
+            ep = G[k, 0]
+            rows.append(dict(iteration=self.i_so_far, scenario=k, envs=int(envs[k]), episodes=int(ep),
+                             success_rate=float(G[k, 1] / ep) if ep else nan, collision_rate=float(G[k, 2] / ep) if ep else nan,
+                             timeout_rate=float(G[k, 3] / ep) if ep else nan, score=float(self.scenarios.score[k]), weight=float(w[k])))
+        return rows
 
     def _fused_act(self, t, noise=None):
         """PPO.get_action for all envs in ONE launch (csrc/ppo_mlp64.hip: mlp64_act, csrc/ppo_resmlp512.hip: resmlp_act)."""
@@ -300,13 +389,16 @@ class PPOTrainer:
 
     def _rollout_metrics_dev(self):
         """The six sums behind the iteration's episode metrics as ONE device tensor (all-reduced over the ranks); nothing
-        here waits for the GPU, so the update can be queued behind it."""
+        here waits for the GPU, so the update can be queued behind it.  With scenario_stats / scenario_priority the [K, 8] sums per
+        scenario follow the six in the same tensor: one more launch, the same ONE collective."""
         if getattr(self, "_sums_ws", None) is None:
             self._sums_ws = torch.empty(256 * 6, dtype=torch.float64, device=self.device)
         m = torch.empty(6, dtype=torch.float64, device=self.device)
         with torch.cuda.device(self.device):
             _navppo("navppo_episode_sums", _ptr(self.ended_buf), _ptr(self.arrive_buf), _ptr(self.done_buf), _ptr(self.eplen_buf),
                     _ptr(self.epret_buf), self.ended_buf.numel(), _ptr(m), _ptr(self._sums_ws))
+        if self.scenarios is not None:
+            m = torch.cat([m, self._scenario_sums_dev()])
         self.ctx.all_reduce_sum(m)
         return m
 
@@ -339,6 +431,7 @@ class PPOTrainer:
                                     **({} if self._gae is None else dict(adv_raw=self._gae[0], V0=self._gae[1])))
         if cuda:
             ev[2].record()
+        n_scen = 0 if self.scenarios is None else self._scen_K * self._scen_cols   # (the per-scenario sums sit behind the six)
         if cfg.norm_reward:   # the option's figures ride on the episode sums' read-back below: one tensor, one copy
             m = torch.cat([m, self._reward_norm_figures_dev()])
         if cuda:
@@ -347,9 +440,10 @@ class PPOTrainer:
         if cuda:   # the host ran ahead of the stream: split the wall clock of the iteration by the stream's own stamps
             r_ms, u_ms = ev[0].elapsed_time(ev[1]), ev[1].elapsed_time(ev[2])
             t1 = t0 + (t2 - t0) * r_ms / max(r_ms + u_ms, 1e-9)
+        if n_scen or cfg.norm_reward:
+            m = m.tolist()   # the one read-back
+            scen, rn, m = m[6:6 + n_scen], m[6 + n_scen:], m[:6]
         if cfg.norm_reward:
-            m = m.tolist()
-            rn, m = m[6:], m[:6]
             stats = dict(stats, reward_scale=rn[3], ret_rms_mean=rn[0], ret_rms_std=math.sqrt(max(rn[1], 0.0)), explained_variance=rn[4])
         metrics = self._rollout_metrics(m)
         world = self.ctx.world
@@ -357,6 +451,8 @@ class PPOTrainer:
             stats = dict(stats, bootstrapped_frac=metrics["timeouts"] / max(T * N * world, 1))
         self.t_so_far += metrics["completed_steps"]
         self.i_so_far += 1
+        if n_scen:
+            stats = dict(stats, **self._scenario_step(scen))
         self._grad_guard(stats)
         self.logger = dict(metrics, **stats, iteration=self.i_so_far, t_so_far=self.t_so_far,
                            rollout_time=t1 - t0, update_time=t2 - t1, iter_time=t2 - t0,
@@ -561,6 +657,9 @@ class PPOTrainer:
                 **({"ppo/" + k: lg[k] for k in ("reward_scale", "ret_rms_mean", "ret_rms_std", "explained_variance")}
                    if "reward_scale" in lg else {}),                                                    # (norm_reward)
                 **({"ppo/bootstrapped_frac": lg["bootstrapped_frac"]} if "bootstrapped_frac" in lg else {}),   # (bootstrap_truncated)
+                **({"scenarios/train_success_min": lg["train_scenario_success_min"],
+                    "scenarios/train_success_mean": lg["train_scenario_success_mean"]}
+                   if "train_scenario_success_min" in lg else {}),                                      # (scenario_stats / _priority)
                 **({"eval/success_rate": lg["eval_success"], "eval/collision_rate": lg["eval_collision"],
                     "eval/timeout_rate": lg["eval_timeout"], "eval/mean_return": lg["eval_return"],
                     "eval/mean_ep_length": lg["eval_length"], "time/eval": lg["eval_time"]} if "eval_success" in lg else {})}
@@ -619,6 +718,8 @@ class PPOTrainer:
                     + (f" lr={lg['lr']:.3e}" if "lr" in lg else "")
                     + (f" lr_ups={lg['lr_ups']} lr_downs={lg['lr_downs']}" if "lr_ups" in lg else "")
                     + (f" bootstrapped_frac={lg['bootstrapped_frac']:.4f}" if "bootstrapped_frac" in lg else "")
+                    + (f" train scenarios: min={lg['train_scenario_success_min']:.3f} mean={lg['train_scenario_success_mean']:.3f}"
+                       if "train_scenario_success_min" in lg else "")
                     + (f" eval: succ={lg['eval_success']:.3f} coll={lg['eval_collision']:.3f} tmo={lg['eval_timeout']:.3f} "
                        f"ret={lg['eval_return']:.2f} len={lg['eval_length']:.1f} ({lg['eval_time']:.3f}s)"
                        if "eval_success" in lg else "")
@@ -642,6 +743,10 @@ class PPOTrainer:
             torch.save({"mean": mean, "var": var, "count": count}, os.path.join(d, "retnorm_" + tag))
         if self.cfg.lr_schedule == "adaptive":   # the rate the next step starts from (on the host since the last update's read-back)
             torch.save({"lr": float(self.updater.lr_value)}, os.path.join(d, "lrsched_" + tag))
+        if self.scenarios is not None:   # the scores and the re-assignment counter (the next assignment is drawn from them)
+            st = self.scenarios.state_dict()
+            torch.save({"score": [float(v) for v in st["score"]], "counter": st["counter"], "mode": st["mode"]},
+                       os.path.join(d, "scenarios_" + tag))
         return pa, pc
 
     @staticmethod
@@ -671,12 +776,18 @@ class PPOTrainer:
     def load_checkpoint(self, actor_path, critic_path):
         """main.py:52-89: state_dicts only (optimiser state and covariance are not part of a checkpoint).  With norm_reward the return
         statistics come from retnorm_<tag>.pth beside the actor's file; without that file: one warning line and fresh statistics.
-        With lr_schedule="adaptive" the learning rate comes from lrsched_<tag>.pth; without that file: one warning line and cfg.lr."""
+        With lr_schedule="adaptive" the learning rate comes from lrsched_<tag>.pth; without that file: one warning line and cfg.lr.
+        With scenario_stats / scenario_priority the scores and the re-assignment counter come from scenarios_<tag>.pth; without that
+        file: one warning line and fresh state."""
         self.reset_envs()   # (continue_rollouts: the episodes under way were the old weights')
         if self.cfg.lr_schedule == "adaptive":
             s = self._load_sidecar("lrsched", actor_path,
                                    "lr_schedule='adaptive': {} not found -- the learning rate starts at lr = " + str(self.cfg.lr))
             self.updater.set_lr(float(s["lr"] if s else self.cfg.lr))
+        if self.scenarios is not None:
+            s = self._load_sidecar("scenarios", actor_path,
+                                   "scenario_stats / scenario_priority: {} not found -- the scenario scores start fresh")
+            self.scenarios.load_state_dict(s or {"score": [float("nan")] * self._scen_K, "counter": 0})
         if self.cfg.norm_reward:
             s = self._load_sidecar("retnorm", actor_path,
                                    "norm_reward: {} not found -- the return statistics start fresh; the critic's units are off until they settle")
