@@ -4,7 +4,12 @@ PPOConfig.continue_rollouts.
 Nothing is recomputed at a seam -- a history carry is 22 copies, the env state lives in the handle, the noise counter is a device
 scalar -- so every comparison is bit for bit: k launches chained through row T -> row 0, step_base and the carry against ONE launch
 of the whole length.  The common world: 40 envs (two full 16-env workgroups and one of 8) on stage_1, 24 steps, episodes capped at 7
-steps, so that time-outs put an episode's first row on rows 7, 14 and 21."""
+steps, so that time-outs put an episode's first row on rows 7, 14 and 21.
+
+The further worlds (SEAM_KINDS) are those of tests/test_gpu_scan_history.py, built by its make_sim and started by its start(): stage_2
+with the robot in front of the inner wall, episodes capped at 7 steps and started at step count env mod 7, so that collisions,
+arrivals and time-outs end episodes on every row.  Beside the comparison with ONE launch the final carry is held against
+stack_rows_reference of the one-launch buffers on the host -- an expected value that no kernel of the project computed."""
 import ctypes as C
 import functools
 
@@ -12,7 +17,9 @@ import numpy as np
 import pytest
 import torch
 
+import test_gpu_scan_history as SH
 from _guards import run_both
+from _ranks import spawn_ranks
 from navbot_ppo_amd import maps, nets, ppo
 from navbot_ppo_amd._native import lib
 from navbot_ppo_amd.env import HIST_CARRY, HIST_DIM, NavSim, NavsimError, VecEnv, stack_rows, stack_rows_reference
@@ -58,9 +65,12 @@ def _actor(policy="hist", seed=3, scale=2.0):
     return nets.flat_actor_params(a).to(DEV)
 
 
-def make_sim(kind="plain", n=N, **kw):
+def make_sim(kind="plain", n=N, cap=CAP, **kw):
+    if kind not in KINDS:   # a world of tests/test_gpu_scan_history.py (its cap is this file's)
+        assert kind in SH.KINDS and cap == CAP == SH.CAP
+        return SH.make_sim(kind, n, **kw)
     opts, movers = KINDS[kind]
-    s = NavSim(n, n_beams=10, max_episode_steps=CAP, auto_reset=True, seed=11, device=DEV, **opts, **kw)
+    s = NavSim(n, n_beams=10, max_episode_steps=cap, auto_reset=True, seed=11, device=DEV, **opts, **kw)
     rr, rs = maps.goal_rects("stage_1")
     s.set_goal_rects(0, rr)
     s.set_goal_rects(1, rs)
@@ -91,7 +101,12 @@ def launch(entry, sim, flat, b, n_steps, step_base, carries=None):
     torch.cuda.synchronize()
 
 
-def chained(entry, sim, flat, cuts, n_steps=T, cont=False, inplace=True):
+def start_of(kind):
+    """how a rollout in the world `kind` begins: a reset, in the worlds of the scan-history file its start() (staggered step counts)"""
+    return (lambda sim, obs0: sim.reset(obs0)) if kind in KINDS else SH.start
+
+
+def chained(entry, sim, flat, cuts, n_steps=T, cont=False, inplace=True, start=start_of("plain")):
     """the rollout in pieces cut at the rows `cuts`: a reset, then per piece a launch on buffers of its own whose row 0 is a copy of
     the piece before's last row, step_base advanced by the steps taken, the carry handed on (cont).  Returns the concatenation -- the
     seam rows once -- and the last carry."""
@@ -102,7 +117,7 @@ def chained(entry, sim, flat, cuts, n_steps=T, cont=False, inplace=True):
     for k, (a, e) in enumerate(zip(edges[:-1], edges[1:])):
         b = _buffers(sim, e - a)
         if prev is None:
-            sim.reset(b["obs"][0])
+            start(sim, b["obs"][0])
         else:
             b["obs"][0].copy_(prev["obs"][-1])
         cs = None
@@ -118,16 +133,37 @@ def chained(entry, sim, flat, cuts, n_steps=T, cont=False, inplace=True):
 
 
 @functools.lru_cache(maxsize=None)
-def _whole(kind):
+def _whole(kind, n=N, n_steps=T, cap=CAP, env_id_base=0):
     """ONE launch of T steps of navsim_rollout_mlp64_hist_cont (no carry in), its carry-out, and the history rows of its buffer"""
-    s = make_sim(kind)
+    s = make_sim(kind, n, cap, env_id_base=env_id_base)
     try:
-        b, carry = chained("navsim_rollout_mlp64_hist_cont", s, _actor(), [], cont=True)
+        b, carry = chained("navsim_rollout_mlp64_hist_cont", s, _actor(), [], n_steps, cont=True, start=start_of(kind))
     finally:
         s.close()
     hist = stack_rows(b["obs"], b["ended"])
     torch.cuda.synchronize()
     return b, carry, hist
+
+
+def mirror_carry(b):
+    """the carry of the last row of a rollout's buffers by the host mirror: columns 16..37 of its last history row, as float32"""
+    rows = stack_rows_reference(b["obs"].cpu().numpy(), b["ended"].cpu().numpy())
+    return torch.from_numpy(rows[-1, :, 16:38].astype(np.float32)).to(DEV)
+
+
+def assert_chain_is_one_launch(kind, cuts, inplace=True, n=N, n_steps=T, cap=CAP, env_id_base=0):
+    """the launches chained at `cuts` write the bits of ONE launch, carry included, and that carry is the host mirror's; returns the
+    chain's buffers and carry"""
+    want, carry, _ = _whole(kind, n, n_steps, cap, env_id_base)
+    s = make_sim(kind, n, cap, env_id_base=env_id_base)
+    try:
+        got, c = chained("navsim_rollout_mlp64_hist_cont", s, _actor(), cuts, n_steps, cont=True, inplace=inplace, start=start_of(kind))
+    finally:
+        s.close()
+    _assert_same_rollout(got, want, (kind, cuts, inplace, n))
+    assert same(c, carry), (kind, cuts, inplace, n)
+    assert same(carry, mirror_carry(want)), (kind, n)
+    return got, c
 
 
 def _assert_same_rollout(got, want, what):
@@ -229,6 +265,127 @@ def test_misaligned_carries_are_refused_before_any_launch():
         s.close()
 
 
+# ---------------------------------------------------------------- 1b. seams in the further worlds, on every row, in every placement
+SEAM_KINDS = {   # a world of tests/test_gpu_scan_history.py -> the row it is cut at
+    "bank3-respawn": 9,      # three tapes with per-env ids, goal rectangles, respawn on arrival (sp_scan[1])
+    "noise-gazebo": 10,      # range noise with the below-minimum mode (sm.neg)
+    "noise-f16": 11,         # ... on float16 rows
+    "per-env": 9,            # every env its own copy of stage_2
+    "house-boxes": 10,       # the tile-box cast of a 256-segment shared map
+    "no-reset": 4,           # auto_reset off: an ended env keeps its row, hist_leave copies it
+}
+
+
+def seam_facts(b, s):
+    """what the one-launch rollout holds around a cut at row s, per env: the step in front of the cut ended an episode (row s is an
+    episode's first row); row s lies two rows and more into an episode (both older frames are real rows of it); the env ended
+    before the cut and is still ended behind it; an arrival lies in front of the cut"""
+    e, a = b["ended"].cpu().numpy() != 0, b["arrive"].cpu().numpy() != 0
+    return dict(first=e[s - 1], deep=~e[s - 3] & ~e[s - 2] & ~e[s - 1], stays=e[s - 2] & e[s - 1] & e[s], arrived=a[:s].any(axis=0))
+
+
+@pytest.mark.parametrize("kind", list(SEAM_KINDS))
+def test_one_cut_in_the_further_worlds(kind):
+    s = SEAM_KINDS[kind]
+    want = _whole(kind)[0]
+    f = seam_facts(want, s)
+    print(f"{kind}, cut {s}: {SH.cut_facts(want)}; at the cut: " + ", ".join(f"{k} {int(v.sum())}" for k, v in f.items()))
+    assert 3 <= s < T and f["first"].any() and f["deep"].any()       # the case means something: else it fails, it does not pass empty
+    w = SH.world_of(kind)
+    if not w["auto_reset"]:
+        assert f["stays"].any()
+    if w.get("respawn_on_arrive"):
+        assert f["arrived"].any()
+    if w.get("obs_f16"):
+        assert want["obs"].dtype == torch.float16
+    assert 0 < int(want["ended"].sum()) < want["ended"].numel()
+    assert_chain_is_one_launch(kind, [s])
+
+
+@pytest.mark.parametrize("inplace", [True, False], ids=["in-place", "two-buffers"])
+@pytest.mark.parametrize("kind", ["plain", "bank3-respawn", "noise-f16"])
+def test_every_row_a_seam(kind, inplace):
+    """T launches of ONE step: hist_shift never runs (no step is followed by another), hist_enter and hist_leave alone move the carry"""
+    assert_chain_is_one_launch(kind, list(range(1, T)), inplace)
+
+
+PLACED = {"plain": (5, 7), "bank3-noise-f16": (11,)}    # kind -> the cuts, one per chain (this file's plain world ends episodes by
+# its cap alone, all envs at once: row 7 is an episode's first row, row 5 lies five rows into one)
+
+
+@pytest.mark.parametrize("kind", list(PLACED))
+def test_shards_with_carries_concatenate_to_the_whole(kind):
+    """one handle of 40 envs against two of 24 and 16 (env_id_base 0 and 24), each chained over one cut with a carry of its own"""
+    want, carry, _ = _whole(kind)
+    facts = [seam_facts(want, s) for s in PLACED[kind]]
+    assert any(f["first"].any() for f in facts) and any(f["deep"].any() for f in facts)
+    for s in PLACED[kind]:
+        parts = [assert_chain_is_one_launch(kind, [s], n=n, env_id_base=base) for base, n in SH.SHARDS]
+        assert not same(parts[1][0]["act"], want["act"][:, :16])     # (the second shard is not the first 16 envs again)
+        for fld in FIELDS:
+            assert same(torch.cat([p[0][fld] for p in parts], dim=1), want[fld]), (kind, s, fld)
+        assert same(torch.cat([p[1] for p in parts]), carry), (kind, s)
+
+
+@pytest.mark.parametrize("n", [1, 5, 17])
+@pytest.mark.parametrize("kind", list(PLACED))
+def test_one_handle_of_1_5_and_17_envs(kind, n):
+    for s in PLACED[kind]:
+        assert_chain_is_one_launch(kind, [s], n=n)
+        assert_chain_is_one_launch(kind, [s], inplace=False, n=n)
+
+
+def test_more_workgroups_than_one_round_with_carries():
+    """4117 envs: 258 workgroups -- the grid runs in rounds -- the last one of 5 envs; episodes capped at 3 steps, one cut at row 3"""
+    n, steps, cap = 4117, 6, 3
+    want = _whole("plain", n, steps, cap)[0]
+    e = want["ended"].cpu().numpy() != 0
+    print(f"N = {n}, cap {cap}: episode ends per row {e.sum(axis=1).tolist()}")
+    assert e[2].any() and e[2, -5:].any() and not e[0].all()     # the cap makes row 3 an episode's first row, in the last workgroup too
+    assert_chain_is_one_launch("plain", [3], n=n, n_steps=steps, cap=cap)
+
+
+def _zero_step_call(s, b, cin, cout):
+    var, base = torch.tensor(VAR, device=DEV), torch.tensor(STEP_BASE, dtype=torch.int32, device=DEV)
+    rc = lib().navsim_rollout_mlp64_hist_cont(s._h, P(_actor()), P(b["obs"]), P(b["act"]), P(b["logp"]), P(b["reward"]), P(b["done"]),
+                                              P(b["arrive"]), P(b["ended"]), P(b["ep_return"]), P(b["ep_length"]), P(b["ep_path"]), P(var),
+                                              ACT_SEED, P(base), 0, P(cin), P(cout), _st())
+    torch.cuda.synchronize()
+    return rc
+
+
+def test_zero_steps_with_carries():
+    s = make_sim("plain")
+    try:
+        b = _buffers(s, 2)
+        s.reset(b["obs"][0])
+        for f in FIELDS[1:]:
+            b[f].fill_(7)
+        torch.cuda.synchronize()
+        before, state = {f: b[f].clone() for f in FIELDS}, s.get_state()
+        carry = torch.randn((N, HIST_CARRY), device=DEV)
+        kept = carry.clone()
+        # one buffer in and out: accepted, nothing moves
+        assert _zero_step_call(s, b, carry, carry) == 0, lib().navsim_last_error().decode()
+        assert same(carry, kept)
+        # a carry in alone: accepted as well
+        assert _zero_step_call(s, b, carry, None) == 0, lib().navsim_last_error().decode()
+        # two buffers (both 16-byte aligned): no row to write a carry for -- refused by name, nothing launched
+        other = torch.full((N, HIST_CARRY), 7.0, device=DEV)
+        assert carry.data_ptr() % 16 == 0 and other.data_ptr() % 16 == 0 and other.data_ptr() != carry.data_ptr()
+        assert _zero_step_call(s, b, carry, other) == -1
+        err = lib().navsim_last_error().decode()
+        assert err.startswith("navsim_rollout_mlp64_hist_cont: ") and "n_steps == 0" in err
+        assert _zero_step_call(s, b, None, other) == -1 and b"navsim_rollout_mlp64_hist_cont" in lib().navsim_last_error()
+        assert bool((other == 7.0).all()) and same(carry, kept)
+        after = s.get_state()
+        assert all(np.array_equal(state[k], after[k]) for k in state)
+        for f in FIELDS:
+            assert same(b[f], before[f]), f
+    finally:
+        s.close()
+
+
 # ---------------------------------------------------------------- 2. navsim_stack_rows_cont
 @pytest.mark.parametrize("kind", ["plain", "f16"])
 def test_stack_rows_cont_against_the_host_mirror(kind):
@@ -262,6 +419,42 @@ def test_stack_rows_cont_with_null_carries_is_stack_rows(kind):
     assert rc == 0, lib().navsim_last_error().decode()
     torch.cuda.synchronize()
     assert same(out, hist)
+
+
+@pytest.mark.parametrize("f16", [False, True], ids=["f32", "f16"])
+@pytest.mark.parametrize("R,n", [(1, 37), (2, 37), (3, 1), (3, 37), (3, 4099)])
+def test_stack_rows_cont_at_its_sizes_inside_guards(R, n, f16):
+    """R = 1: no step at all -- ended_dev is NULL, row 0's columns 16..37 ARE the carry and the carry goes out as it came in; R = 2:
+    the one flag decides, per env, whether row 1 reads its oldest frame from the carry; R = 3 with 1, 37 and 4099 envs.  Against
+    stack_rows_reference, with separate carries and with one buffer for both."""
+    rng = np.random.default_rng(100 * R + n)
+    dt = np.float16 if f16 else np.float32
+    obs = rng.standard_normal((R, n, 16)).astype(dt)
+    carry = rng.standard_normal((n, HIST_CARRY)).astype(dt).astype(np.float32)     # (values the rows' dtype holds)
+    ended = (rng.random((R - 1, n)) < 0.4).astype(np.uint8) if R > 1 else None
+    if R == 2:
+        assert ended[0].any() and not ended[0].all()
+    want, want_carry = stack_rows_reference(obs, ended, carry=carry)
+    tdt = torch.float16 if f16 else torch.float32
+
+    def call(g, inplace):
+        o = g.inp(torch.from_numpy(obs), 16)
+        e = g.inp(torch.from_numpy(ended), 1) if R > 1 else None
+        cin = g.io(torch.from_numpy(carry), 16) if inplace else g.inp(torch.from_numpy(carry), 16)
+        cout = cin if inplace else g.out((n, HIST_CARRY), torch.float32, 16)
+        out = g.out((R, n, HIST_DIM), tdt, 16)
+        rc = lib().navsim_stack_rows_cont(P(o), int(f16), P(e), R, n, P(out), P(cin), P(cout), _st())
+        assert rc == 0, lib().navsim_last_error().decode()
+        torch.cuda.synchronize()
+        return out.clone(), cout.clone()
+
+    for inplace in (False, True):
+        out, cout = run_both(DEV, lambda g: call(g, inplace), f"navsim_stack_rows_cont R={R} N={n} f16={f16} inplace={inplace}")
+        assert np.array_equal(out.cpu().numpy().view(np.uint8), want.view(np.uint8)), (R, n, f16, inplace)
+        assert np.array_equal(cout.cpu().numpy().view(np.uint8), want_carry.view(np.uint8)), (R, n, f16, inplace)
+        if R == 1:
+            assert np.array_equal(out.cpu().numpy()[0, :, 16:38].astype(np.float32).view(np.uint8), carry.view(np.uint8))
+            assert np.array_equal(cout.cpu().numpy().view(np.uint8), carry.view(np.uint8))
 
 
 # ---------------------------------------------------------------- 3. the carries inside guarded allocations
@@ -339,8 +532,11 @@ TR = dict(policy="mlp64x2", scan_history=True, rollout_len=8, max_episode_steps=
           bootstrap_truncated=True)
 
 
-def _trainer(**cfg):
-    env = VecEnv(40, map="stage_1", max_episode_steps=20, seed=1, device=DEV)
+ENV = dict(map="stage_1", max_episode_steps=20, seed=1, device=DEV)
+
+
+def _trainer(env_kw=None, **cfg):
+    env = VecEnv(40, **{**ENV, **(env_kw or {})})
     return ppo.PPOTrainer(env, ppo.PPOConfig(**{**TR, **cfg}))
 
 
@@ -349,19 +545,24 @@ def _run(tr, iters):
     for _ in range(iters):
         lg = tr.iteration()
         torch.cuda.synchronize()
-        snaps.append({k: getattr(tr, k + "_buf").clone() for k in ("obs", "act", "rew", "ended", "hist", "eplen")})
+        snaps.append({k: getattr(tr, k + "_buf").clone() for k in ("obs", "act", "rew", "ended", "hist", "eplen")
+                      if getattr(tr, k + "_buf") is not None})
         snaps[-1]["log"] = dict(lg)
         snaps[-1]["starts"] = tr.episode_starts
+        snaps[-1]["did_reset"] = tr._did_reset
     return snaps
 
 
-def _replay(actions_per_reset):
-    """the observations and flags of a fresh env of the trainer's world under recorded actions: a reset in front of every tape"""
-    env = VecEnv(40, map="stage_1", max_episode_steps=20, seed=1, device=DEV)
+def _replay(actions_per_reset, env_kw=None, state=None):
+    """the observations and flags of a fresh env of the trainer's world under recorded actions: a reset in front of every tape
+    (state: the envs' state behind it -- NavSim.get_state -- where the trainer's envs did more than reset before the tape)"""
+    env = VecEnv(40, **{**ENV, **(env_kw or {})})
     try:
         out = []
         for act in actions_per_reset:
             obs0 = env.reset().clone()
+            if state is not None:
+                env.sim.set_state(**state)
             r = env.step_seq(act)
             torch.cuda.synchronize()
             out.append((torch.cat([obs0[None], r.obs]), r.ended))
@@ -447,3 +648,116 @@ def test_option_off_every_rollout_starts_from_a_reset():
         assert np.array_equal(s["hist"].cpu().numpy(), stack_rows_reference(s["obs"].cpu().numpy(), s["ended"].cpu().numpy())), k
         assert int(s["eplen"].max()) <= Tr
         assert s["starts"] == int(s["ended"].sum()) + 40
+
+
+CONT_CASES = {   # name -> (PPOConfig options over TR + continue_rollouts, VecEnv options)
+    "mlp64x2-16-columns": (dict(scan_history=False), {}),
+    "resmlp512": (dict(policy="resmlp512", scan_history=False), {}),
+    "history-float16": (dict(), dict(obs_f16=True)),
+    "graph": (dict(scan_history=False, persistent_rollout=False), {}),
+    "per-step": (dict(scan_history=False, persistent_rollout=False, use_graph=False), {}),
+}
+
+
+@pytest.mark.parametrize("case", list(CONT_CASES))
+def test_trainer_continues_on_every_rollout_path(case):
+    """test_trainer_continues_across_iterations' trajectory check for the other nets, row formats and rollout paths: three iterations
+    are ONE trajectory.  On the hipGraph path the first rollout captures -- the warm-up steps the envs, so it resets a second time --
+    and the two behind it replay the graph and continue; the replay of that case starts from the state the envs had behind that
+    second reset (a fresh env's reset alone is not where they stood)."""
+    cfg_kw, env_kw = CONT_CASES[case]
+    tr = _trainer(env_kw, continue_rollouts=True, **cfg_kw)
+    states = []
+    try:
+        reset = tr.env.sim.reset
+
+        def recording_reset(obs, mask=None):
+            out = reset(obs, mask)
+            torch.cuda.synchronize()
+            states.append(tr.env.sim.get_state())
+            return out
+
+        tr.env.sim.reset = recording_reset
+        persistent, graph = tr.uses_persistent_rollout, tr._graph
+        snaps = _run(tr, 3)
+        graph_after = tr._graph
+    finally:
+        tr.env.close()
+    Tr = TR["rollout_len"]
+    on_graph = case == "graph"
+    assert persistent == (case not in ("graph", "per-step")) and graph is None and (graph_after is not None) == on_graph
+    assert [s["did_reset"] for s in snaps] == [True, False, False]
+    assert len(states) == (2 if on_graph else 1)
+    for a, b in zip(snaps[:-1], snaps[1:]):
+        assert same(b["obs"][0], a["obs"][Tr])   # row 0 is the row the last rollout stopped at
+    (obs, ended), = _replay([torch.cat([s["act"] for s in snaps])], env_kw, state=states[-1] if on_graph else None)
+    if on_graph:   # (row 0 is the second reset's; the replaying env wrote its own first one)
+        assert same(obs[1:], torch.cat([s["obs"][1:] for s in snaps]))
+    else:
+        assert same(obs, torch.cat([snaps[0]["obs"]] + [s["obs"][1:] for s in snaps[1:]]))
+    assert same(ended, torch.cat([s["ended"] for s in snaps]))
+    assert max(int(s["eplen"].max()) for s in snaps) > Tr     # episodes longer than a rollout end
+    assert 0 < int(ended.sum()) < ended.numel()
+    if case == "history-float16":
+        assert snaps[0]["obs"].dtype == torch.float16 and snaps[0]["hist"].dtype == torch.float16
+        full = stack_rows_reference(obs.cpu().numpy(), ended.cpu().numpy())
+        for k, s in enumerate(snaps):
+            assert np.array_equal(s["hist"].cpu().numpy().view(np.uint16), full[k * Tr:(k + 1) * Tr + 1].view(np.uint16)), k
+    else:
+        assert "hist" not in snaps[0]
+    eps = [int(s["ended"].sum()) for s in snaps]
+    assert [s["starts"] for s in snaps] == [eps[0] + 40, eps[1], eps[2]]
+
+
+def test_history_off_the_persistent_rollout_is_refused():
+    """scan_history lives in the persistent rollout kernel alone: with continue_rollouts as without, the other paths refuse it"""
+    for kw in (dict(persistent_rollout=False), dict(persistent_rollout=False, use_graph=False), dict(fused_update=False)):
+        with pytest.raises(ValueError, match="scan_history needs persistent_rollout=True and fused_update=True"):
+            ppo.PPOConfig(**{**TR, **kw}, continue_rollouts=True)
+    with pytest.raises(ValueError, match="scan_history with policy='resmlp512'"):
+        ppo.PPOConfig(**{**TR, "policy": "resmlp512"}, continue_rollouts=True)
+
+
+# ---------------------------------------------------------------- 6. two ranks
+RANKS_CAP = 12   # two iterations are 16 steps: under the cap of 20 no episode would time out, under this one every env's does on row 11
+
+
+def _cont_rank_worker(rank, world, port, path):
+    import os
+    os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
+                      NAVBOT_DIST_BACKEND="gloo")   # RCCL refuses two ranks on one device: gloo carries the all-reduce here
+    ctx = ppo.DistCtx(device="cuda:0")
+    lo, hi = ctx.shard(40)
+    env = VecEnv(hi - lo, **{**ENV, "max_episode_steps": RANKS_CAP}, env_id_base=lo)
+    tr = ppo.PPOTrainer(env, ppo.PPOConfig(**{**TR, "max_episode_steps": RANKS_CAP}, continue_rollouts=True), ctx)
+    try:
+        snaps = _run(tr, 2)
+        torch.save({"snaps": [{k: v.cpu() if torch.is_tensor(v) else v for k, v in s.items()} for s in snaps],
+                    "flat": tr.updater.fp.flat.cpu(), "base": tr._env_id_base}, f"{path}.{rank}")
+    finally:
+        env.close()
+    ctx.barrier()
+    torch.distributed.destroy_process_group()
+
+
+def test_two_ranks_continue_like_one_process_that_plays_both(tmp_path):
+    """Shards of 20 + 20 envs with scan_history, two iterations: every rank's rows, flags and history rows are those of ONE env of
+    all 40 under the recorded actions -- a single reset -- and the ranks hold the same weights."""
+    path = str(tmp_path / "cont")
+    spawn_ranks(_cont_rank_worker, 2, lambda port: (2, port, path))
+    ranks = [torch.load(f"{path}.{r}", weights_only=False) for r in range(2)]
+    assert [r["base"] for r in ranks] == [0, 20]
+    assert same(ranks[0]["flat"], ranks[1]["flat"])
+    Tr = TR["rollout_len"]
+    cat = lambda k, it: torch.cat([r["snaps"][it][k] for r in ranks], dim=1)
+    (obs, ended), = _replay([torch.cat([cat("act", 0), cat("act", 1)]).to(DEV)], dict(max_episode_steps=RANKS_CAP))
+    obs, ended = obs.cpu(), ended.cpu()
+    assert bool(ended[RANKS_CAP - 1].any()) and 0 < int(ended.sum()) < ended.numel()
+    full = stack_rows_reference(obs.numpy(), ended.numpy())
+    for it in range(2):
+        assert [r["snaps"][it]["did_reset"] for r in ranks] == [it == 0] * 2
+        assert same(cat("obs", it), obs[it * Tr:(it + 1) * Tr + 1]), it
+        assert same(cat("ended", it), ended[it * Tr:(it + 1) * Tr]), it
+        assert np.array_equal(cat("hist", it).numpy().view(np.uint32), full[it * Tr:(it + 1) * Tr + 1].view(np.uint32)), it
+    assert not np.array_equal(full[Tr:], stack_rows_reference(obs.numpy()[Tr:], ended.numpy()[Tr:]))   # the carry mattered
+    assert max(int(cat("eplen", it).max()) for it in range(2)) == RANKS_CAP > Tr     # an episode longer than a rollout ended

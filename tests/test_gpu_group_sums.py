@@ -4,7 +4,15 @@ Shapes (T, N, K): (1, 1, 1) the smallest; (3, 17, 4) with one empty group; (37, 
 (40, 4112, 32) more columns than one workgroup of lanes per row (17 workgroups along N, the last one 16 columns wide) and several
 chunks of T.  Each with and without advantages, the ids in no order.  Columns 0-4 and 7 are integers and must be exact; columns 5 and 6
 are float64 sums of float32 terms in an order of the kernel's own, so |got - ref| <= n 2^-53 sum|x| with n the number of summands --
-the bound that holds for any summation order in float64.  Every buffer of every call sits inside guarded allocations."""
+the bound that holds for any summation order in float64.  Every buffer of every call sits inside guarded allocations.
+
+CHUNKS: the shapes that exist for the way T is cut (gs_cut in the kernel's file: the rows of a chunk and the chunk count, which the
+workspace size and both launches share).  group_sums_final gives wave w of its 16 the chunks w, w + 16, ...; each case names the
+count it needs -- read back from navppo_group_sums_ws_bytes -- so that another cut fails the case instead of hollowing it out.
+(137, 40, 3): 18 chunks, waves 0 and 1 take two, the last chunk is one row; (300, 40, 3): 38, waves 0..5 take three; (2049, 5, 2):
+256 aimed for, 9 rows each, so 228 with a last one of 6 rows; (2048, 17, 2): 256, the maximum, 16 per wave.  The 4096-column tile of
+group_sums_final: N = 4096 (one tile exactly), 4097 (a second tile of one column: every other id load of it is clamped to N - 1),
+8200 (three tiles, the last one 8 columns).  K = 1024, the maximum (at most 48 groups hold an env), and K = 1."""
 import ctypes as C
 import functools
 
@@ -21,8 +29,18 @@ from navbot_ppo_amd.env import VecEnv
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda")
 F64 = torch.float64
-SHAPES = [(1, 1, 1), (3, 17, 4), (37, 40, 3), (64, 129, 5), (40, 4112, 32)]
+CHUNKS = {(137, 40, 3): 18, (300, 40, 3): 38, (2049, 5, 2): 228, (2048, 17, 2): 256, (9, 4096, 4): 2, (9, 4097, 4): 2, (9, 8200, 7): 2,
+          (24, 48, 1024): 3, (24, 48, 1): 3}
+SHAPES = [(1, 1, 1), (3, 17, 4), (37, 40, 3), (64, 129, 5), (40, 4112, 32)] + list(CHUNKS)
 U = 2.0 ** -53
+NAN_BYTE = 0xFF      # eight of them: a NaN double (sign, exponent and mantissa all ones)
+
+
+def n_chunks(T, N, K):
+    """how many chunks the entry point cuts T into: its workspace is [chunks][7][N] float64"""
+    nbytes = int(lib().navppo_group_sums_ws_bytes(T, N, K))
+    assert nbytes > 0 and nbytes % (7 * N * 8) == 0
+    return nbytes // (7 * N * 8)
 
 
 @functools.lru_cache(maxsize=None)
@@ -72,10 +90,13 @@ def _assert_sums(got, want, bounds, what):
     assert (err <= bounds).all(), f"{what}: {err} > {bounds}"
 
 
-def _guarded_call(b, T, N, K, with_adv, twice=False):
+def _guarded_call(b, T, N, K, with_adv, twice=False, ws_fill=None):
+    """ws_fill: the byte the workspace holds before the call (default: the guards' canary)"""
     def call(g):
         t = {k: g.inp(torch.from_numpy(np.array(v)), 4 if v.dtype.itemsize == 4 else 1) for k, v in b.items() if k != "adv" or with_adv}
         ws = g.scratch(int(lib().navppo_group_sums_ws_bytes(T, N, K)), 8)
+        if ws_fill is not None:
+            ws.fill_(ws_fill)
         out = g.out((K, 8), F64, 8)
         args = (t["ended"], t["arrive"], t["done"], t["ep_length"], t["ep_return"], t["group"], K)
         ppo.group_sums(*args, adv=t.get("adv"), out=out, workspace=ws)
@@ -100,6 +121,107 @@ def test_against_the_host_mirror_inside_guards(T, N, K, with_adv):
     if not with_adv:
         assert not got[:, 6].cpu().numpy().any()
     assert want[:, 7].sum() == T * N
+    if (T, N, K) in CHUNKS:     # the case reaches what it is here for
+        c = n_chunks(T, N, K)
+        assert c == CHUNKS[(T, N, K)], (c, CHUNKS[(T, N, K)])
+        if T >= 137:
+            assert c > 16       # some wave of group_sums_final takes a second chunk
+        if (T, N, K) == (2049, 5, 2):
+            assert c < 256      # fewer chunks than the 256 aimed for
+        if K == 1024:
+            assert 1 < (want[:, 7] > 0).sum() <= N and not got.cpu().numpy()[want[:, 7] == 0].any()
+        if K == 1:
+            assert want[0, 7] == T * N
+
+
+def _bits(x):
+    return (x.cpu().numpy() if torch.is_tensor(x) else x).view(np.int64)
+
+
+# ---------------------------------------------------------------- what the contract allows the buffers and the workspace to hold
+@pytest.mark.parametrize("T, N, K", [(37, 40, 3), (137, 40, 3), (9, 4097, 4)])
+def test_garbage_where_no_episode_ended_is_not_read(T, N, K):
+    """ep_return is written only where an episode ended (include/navppo.h): everywhere else a real buffer holds whatever it held.
+    NaN, +inf, -inf and -0.0 there, with arrive and done set as well: the sums are the clean buffers' -- the mirror's within the
+    file's bounds, and bit for bit the kernel's own on the clean buffers (it masks the return's bits, so a not-ended entry adds +0.0
+    either way, in the same order)."""
+    b = _case(T, N, K)
+    quiet = b["ended"] == 0
+    dirty = dict(b)
+    junk = np.array([np.nan, np.inf, -np.inf, -0.0], dtype=np.float32)[(np.arange(T)[:, None] + np.arange(N)[None, :]) % 4]
+    dirty["ep_return"] = np.where(quiet, junk, b["ep_return"]).astype(np.float32)
+    dirty["arrive"] = np.where(quiet, 0xFF, b["arrive"]).astype(np.uint8)
+    dirty["done"] = np.where(quiet, 1, b["done"]).astype(np.uint8)
+    for k in range(K):      # every group holds each of the four values on an entry that did not end
+        col = b["group"] == k
+        if col.any():
+            q = quiet[:, col]
+            x = dirty["ep_return"][:, col][q]
+            assert np.isnan(x).any() and (x == np.inf).any() and (x == -np.inf).any() and (np.signbit(x) & (x == 0)).any(), k
+    want = _reference(T, N, K, True)
+    assert np.isfinite(want).all()
+    got = _guarded_call(dirty, T, N, K, True)
+    _assert_sums(got, want, _bounds(b, K, True), f"garbage on not-ended entries {(T, N, K)}")
+    clean = _guarded_call(b, T, N, K, True)
+    assert np.array_equal(_bits(got), _bits(clean))
+    # (the mirror states the same rule)
+    mirror = ppo.group_sums_reference(dirty["ended"], dirty["arrive"], dirty["done"], dirty["ep_length"], dirty["ep_return"],
+                                      dirty["group"], K, adv=dirty["adv"])
+    assert np.array_equal(_bits(mirror), _bits(want))
+
+
+@pytest.mark.parametrize("T, N, K", [(37, 40, 3), (300, 40, 3)])
+def test_a_non_finite_advantage_stays_in_its_group(T, N, K):
+    b = _case(T, N, K)
+    clean = _guarded_call(b, T, N, K, True).cpu().numpy()
+    n = N - 3                     # (a column of the ragged last wave)
+    k = int(b["group"][n])
+    adv = np.array(b["adv"])
+    adv[T - 1, n] = np.nan        # the last row: at T = 300 the one chunk of wave 5's third trip
+    bad = dict(b, adv=adv)
+    want = ppo.group_sums_reference(bad["ended"], bad["arrive"], bad["done"], bad["ep_length"], bad["ep_return"], bad["group"], K, adv=adv)
+    assert np.isnan(want[k, 6]) and np.isnan(want).sum() == 1
+    got = _guarded_call(bad, T, N, K, True).cpu().numpy()
+    assert np.isnan(got[k, 6])
+    others = np.arange(K) != k
+    assert np.array_equal(_bits(got[others]), _bits(clean[others]))                       # no other group sees it
+    assert np.array_equal(_bits(got[k, [0, 1, 2, 3, 4, 5, 7]]), _bits(clean[k, [0, 1, 2, 3, 4, 5, 7]]))   # and no count changes
+
+
+@pytest.mark.parametrize("with_adv", [False, True], ids=["noadv", "adv"])
+@pytest.mark.parametrize("T, N, K", [(37, 40, 3), (300, 40, 3)])
+def test_a_stale_workspace_does_not_leak(T, N, K, with_adv):
+    """The trainer keeps one workspace for the whole run.  Every double of it a NaN before the call: the sums are the bits of a call
+    on a zeroed workspace -- also without advantages, where figure 6 of the workspace is neither written nor read."""
+    b = _case(T, N, K)
+    zeroed = _guarded_call(b, T, N, K, with_adv, ws_fill=0)
+    stale = _guarded_call(b, T, N, K, with_adv, ws_fill=NAN_BYTE, twice=True)
+    assert np.array_equal(_bits(stale), _bits(zeroed))
+    assert np.isfinite(stale.cpu().numpy()).all()
+    _assert_sums(stale, _reference(T, N, K, with_adv), _bounds(b, K, with_adv), f"stale workspace {(T, N, K)} adv={with_adv}")
+    if not with_adv:
+        assert np.array_equal(_bits(stale[:, 6]), np.zeros(K, np.int64))      # +0.0 exactly
+
+
+@pytest.mark.parametrize("T, N, K", [(37, 40, 3), (300, 40, 3)])
+def test_one_workspace_with_and_then_without_advantages(T, N, K):
+    """with adv the call fills figure 6 of the workspace; the next call without adv must not pick it up"""
+    b = _case(T, N, K)
+    fresh = _guarded_call(b, T, N, K, False)
+
+    def call(g):
+        t = {k: g.inp(torch.from_numpy(np.array(v)), 4 if v.dtype.itemsize == 4 else 1) for k, v in b.items()}
+        ws = g.scratch(int(lib().navppo_group_sums_ws_bytes(T, N, K)), 8)
+        first, second = g.out((K, 8), F64, 8), g.out((K, 8), F64, 8)
+        args = (t["ended"], t["arrive"], t["done"], t["ep_length"], t["ep_return"], t["group"], K)
+        ppo.group_sums(*args, adv=t["adv"], out=first, workspace=ws)
+        ppo.group_sums(*args, adv=None, out=second, workspace=ws)
+        torch.cuda.synchronize()
+        assert bool((first[:, 6] > 0).all())
+        return second
+    second = run_both(DEV, call, f"navppo_group_sums {(T, N, K)} adv, then none, one workspace")
+    assert np.array_equal(_bits(second), _bits(fresh))
+    assert np.array_equal(_bits(second[:, 6]), np.zeros(K, np.int64))
 
 
 @pytest.mark.parametrize("T, N, K", SHAPES)

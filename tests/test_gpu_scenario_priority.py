@@ -7,8 +7,11 @@ import numpy as np
 import pytest
 import torch
 
+import test_gpu_group_sums as GS
 from _movers import blade_tape
+from _ranks import spawn_ranks
 from navbot_ppo_amd import maps, ppo
+from navbot_ppo_amd._native import lib
 from navbot_ppo_amd.env import NavsimError, VecEnv
 
 pytestmark = pytest.mark.gpu
@@ -19,9 +22,10 @@ TR = dict(policy="mlp64x2", rollout_len=T, max_episode_steps=CAP, n_updates_per_
 BUFS = ("obs", "act", "logp", "rew", "done", "arrive", "ended", "epret", "eplen", "eppath", "rtg")
 
 
-def _env(assign="random"):
+def _env(assign="random", n=N, env_id_base=0):
     bank, periods, _ = maps.mover_bank([blade_tape(P, M, radius=r) for P, M, r in SPECS])
-    return VecEnv(N, map="stage_1", max_episode_steps=CAP, seed=1, device=DEV, movers=dict(bank=bank, periods=periods, assign=assign))
+    return VecEnv(n, map="stage_1", max_episode_steps=CAP, seed=1, device=DEV, env_id_base=env_id_base,
+                  movers=dict(bank=bank, periods=periods, assign=assign))
 
 
 def _trainer(assign="random", **cfg):
@@ -220,3 +224,116 @@ def test_refused_without_a_bank():
                 env.assign_scenarios(bad)
     finally:
         env.close()
+
+
+# ---------------------------------------------------------------- (g) the table at an odd shape
+def test_stats_table_against_the_mirror_at_an_odd_shape(tmp_path):
+    """40 envs (the last rollout workgroup holds 8) and a rollout of 137 rows, which navppo_group_sums cuts into 18 chunks -- two
+    waves of its second kernel take two -- the last one a single row: the CSV's figures are the host mirror's of the trainer's own
+    buffers"""
+    n, t_len = 40, 137
+    assert int(lib().navppo_group_sums_ws_bytes(t_len, n, K)) // (7 * n * 8) == 18
+    env = _env(n=n)
+    tr = ppo.PPOTrainer(env, ppo.PPOConfig(**{**TR, "rollout_len": t_len}, scenario_stats=True, output_dir=str(tmp_path), method_name="m",
+                                           save_freq=1000, episode_csv_rows=0, tb_episode_rows=0))
+    try:
+        ids = _ids(tr)
+        lg = tr.iteration()
+        h = {k: getattr(tr, k + "_buf").cpu().numpy() for k in ("ended", "arrive", "done", "eplen", "epret")}
+        assert tr._scen_ws.numel() == 18 * 7 * n * 8
+    finally:
+        env.close()
+    G = ppo.group_sums_reference(h["ended"], h["arrive"], h["done"], h["eplen"], h["epret"], ids, K)
+    assert (G[:, 0] > 0).all() and G[:, 7].sum() == t_len * n and np.array_equal(G[:, 7], t_len * np.bincount(ids, minlength=K))
+    assert (lg["episodes"], lg["successes"], lg["collisions"], lg["timeouts"]) == tuple(int(v) for v in G[:, :4].sum(axis=0))
+    assert lg["train_scenario_success_min"] == (G[:, 1] / G[:, 0]).min()
+    with open(os.path.join(str(tmp_path), "m", "logs", "m_train_scenarios.csv")) as f:
+        rows = list(csv.DictReader(f))
+    assert len(rows) == K
+    host = ppo.ScenarioSampler(K, seed=TR["seed"])
+    host.observe(G)
+    for k, r in enumerate(rows):
+        assert (int(r["iteration"]), int(r["scenario"]), int(r["envs"]), int(r["episodes"])) == (1, k, (ids == k).sum(), G[k, 0])
+        assert float(r["success_rate"]) == G[k, 1] / G[k, 0] and float(r["collision_rate"]) == G[k, 2] / G[k, 0]
+        assert float(r["timeout_rate"]) == G[k, 3] / G[k, 0] and float(r["score"]) == host.score[k]
+
+
+# ---------------------------------------------------------------- (h) two ranks
+ROLLOUT = ("ended", "arrive", "done", "eplen", "epret")
+
+
+def _scen_rank_worker(rank, world, port, path, mode):
+    os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
+                      NAVBOT_DIST_BACKEND="gloo")   # RCCL refuses two ranks on one device: gloo carries the all-reduce here
+    ctx = ppo.DistCtx(device="cuda:0")
+    lo, hi = ctx.shard(N)
+    env = _env(n=hi - lo, env_id_base=lo)
+    tr = ppo.PPOTrainer(env, ppo.PPOConfig(**TR, scenario_priority=mode), ctx)
+    tables, its = [], []
+    step = tr._scenario_step
+
+    def recording_step(G):      # the global table, as the iteration read it back behind its one all-reduce
+        tables.append(np.array(G, dtype=np.float64).reshape(K, 8))
+        return step(G)
+
+    tr._scenario_step = recording_step
+    try:
+        first = _ids(tr)
+        for _ in range(2):
+            ids = _ids(tr)
+            tr.iteration()
+            torch.cuda.synchronize()
+            it = {k: getattr(tr, k + "_buf").cpu().numpy() for k in ROLLOUT}
+            it.update(ids=ids, adv=tr._gae[0].reshape(T, hi - lo).cpu().numpy() if mode == "abs_adv" else None, after=_ids(tr),
+                      host=np.array(tr._scen_ids_host), score=tr.scenarios.score.copy(), counter=tr.scenarios.counter)
+            its.append(it)
+        torch.save(dict(first=first, its=its, tables=tables, base=tr._env_id_base, flat=tr.updater.fp.flat.cpu()), f"{path}.{rank}")
+    finally:
+        env.close()
+    ctx.barrier()
+    torch.distributed.destroy_process_group()
+
+
+@pytest.mark.parametrize("mode", ["failure", "abs_adv"])
+def test_two_ranks_equal_one_process_that_plays_both(tmp_path, mode):
+    """Shards of 24 + 24 envs: the ranks hold one score, one counter and one global assignment, each rank's device ids are its
+    slice of it, and the table behind the all-reduce is the host mirror's over both ranks' buffers side by side.  The single run of
+    48 envs starts from the same weights, so its first rollout, its first table's counts and its first re-assignment are the same."""
+    path = str(tmp_path / "scen")
+    spawn_ranks(_scen_rank_worker, 2, lambda port: (2, port, path, mode))
+    ranks = [torch.load(f"{path}.{r}", weights_only=False) for r in range(2)]
+    half = N // 2
+    assert [r["base"] for r in ranks] == [0, half] and torch.equal(ranks[0]["flat"], ranks[1]["flat"])
+    assert np.array_equal(np.concatenate([r["first"] for r in ranks]), maps.mover_tape_ids(K, N))
+    with_adv = mode == "abs_adv"
+    for it in range(2):
+        a, b = (r["its"][it] for r in ranks)
+        assert np.array_equal(a["score"], b["score"]) and a["counter"] == b["counter"] == it + 1
+        assert np.array_equal(a["host"], b["host"]) and a["host"].shape == (N,)
+        assert np.array_equal(a["after"], a["host"][:half]) and np.array_equal(b["after"], a["host"][half:])
+        assert np.array_equal(np.bincount(a["host"], minlength=K) >= 1, [True] * K)
+        h = {k: np.concatenate([a[k], b[k]], axis=1) for k in ROLLOUT}
+        ids = np.concatenate([a["ids"], b["ids"]])
+        adv = np.concatenate([a["adv"], b["adv"]], axis=1) if with_adv else None
+        want = ppo.group_sums_reference(h["ended"], h["arrive"], h["done"], h["eplen"], h["epret"], ids, K, adv=adv)
+        bounds = GS._bounds(dict(ended=h["ended"], ep_return=h["epret"], adv=adv, group=ids), K, with_adv)
+        for r in ranks:
+            GS._assert_sums(r["tables"][it], want, bounds, f"{mode}, iteration {it + 1}, rank {r['base'] // half}")
+        assert np.array_equal(ranks[0]["tables"][it].view(np.int64), ranks[1]["tables"][it].view(np.int64))
+        assert (want[:, 0] > 0).all() and with_adv == bool(want[:, 6].any())
+    assert not np.array_equal(ranks[0]["its"][0]["host"], maps.mover_tape_ids(K, N))      # the envs did move
+    # the single run
+    tr = _trainer(scenario_priority=mode)
+    try:
+        assert np.array_equal(_ids(tr), maps.mover_tape_ids(K, N))
+        tr.iteration()
+        G = _host_sums(tr, maps.mover_tape_ids(K, N), with_adv)
+        exact = [0, 1, 2, 3, 4, 7]
+        assert np.array_equal(ranks[0]["tables"][0][:, exact], G[:, exact])
+        if mode == "failure":     # the score reads the counts alone
+            assert np.array_equal(tr.scenarios.score, ranks[0]["its"][0]["score"])
+        else:
+            np.testing.assert_allclose(tr.scenarios.score, ranks[0]["its"][0]["score"], rtol=1e-12, atol=0)
+        assert np.array_equal(_ids(tr), ranks[0]["its"][0]["host"])
+    finally:
+        tr.env.close()

@@ -111,6 +111,47 @@ def test_uniform_mix_one_gives_counts_that_differ_by_at_most_one():
         assert (np.diff(c) <= 0).all()       # the spare envs go to the lower ids
 
 
+def test_without_the_uniform_floor_a_tie_goes_to_the_lower_id():
+    """uniform_mix = 0: the weights are the rank weights alone -- nothing lifts the tail.  Scenarios 2 and 3 tie at .5: the lower id
+    ranks first and, wherever the weights give the two a different count, gets the larger one; every scenario still plays."""
+    s = _scored(uniform_mix=0.0)
+    assert s.score[2] == s.score[3] and s.ranks()[2] + 1 == s.ranks()[3]
+    p = (1.0 / s.ranks()) ** (1 / 0.3)
+    np.testing.assert_allclose(s.weights(), p / p.sum(), rtol=1e-14)
+    assert abs(s.weights().sum() - 1) < 1e-12 and s.weights().min() < 0.25 / 7
+    for n in (7, 8, 48, 4096):
+        c = s.counts(n)
+        assert c.sum() == n and c.min() >= 1, (n, c)
+        assert (np.diff(c[np.argsort(s.ranks())]) <= 0).all(), (n, c)
+        assert c[2] >= c[3], (n, c)
+    assert s.counts(4096)[2] > s.counts(4096)[3]
+    assert np.array_equal(np.bincount(s.assign(48), minlength=7), _scored(uniform_mix=0.0).counts(48))
+    # every score the same: the ranks are the ids, the counts fall with the id
+    t = ScenarioSampler(5, uniform_mix=0.0)
+    t.observe(_sums(5, 10, 5))
+    assert t.ranks().tolist() == [1, 2, 3, 4, 5]
+    for n in (5, 6, 33, 1000):
+        c = t.counts(n)
+        assert c.sum() == n and c.min() >= 1 and (np.diff(c) <= 0).all(), (n, c)
+    # ... and with the floor alone nobody is preferred beyond the spare envs
+    u = ScenarioSampler(5, uniform_mix=1.0)
+    u.observe(_sums(5, 10, 5))
+    assert u.counts(33).tolist() == [7, 7, 7, 6, 6]
+
+
+def test_more_scenarios_than_envs_are_refused_not_left_without_an_env():
+    """K > N: some scenario would get no env, and its statistics would never be measured again: assign refuses -- for the whole run
+    and for a shard alike -- and counts nothing; K == N is one env each"""
+    s = _scored()
+    for kw in (dict(), dict(env_id_base=0, n_envs=3), dict(env_id_base=3, n_envs=3)):
+        with pytest.raises(ValueError, match="6 envs cannot play 7 scenarios"):
+            s.assign(6, **kw)
+    assert s.counter == 0
+    ids = s.assign(7)
+    assert sorted(ids.tolist()) == list(range(7)) and s.counter == 1
+    assert _scored(uniform_mix=0.0).counts(7).tolist() == [1] * 7
+
+
 def test_first_sight_then_the_exponential_average_and_unobserved_scores_stay():
     s = ScenarioSampler(3, alpha=0.25)
     assert np.isnan(s.score).all()
