@@ -713,8 +713,6 @@ class VecEnv:
         -- obs0 continues the envs' episodes with the history carry hist_in (None: obs0 starts them), hist_out receives the carry of
         row T.  A rollout cut in pieces (obs0 = the previous piece's last row, step_base advanced, the carry handed on) writes the
         bits of the whole."""
-        import ctypes as C
-        from ._native import check, lib
         if self.B not in (10, 36):
             raise NavsimError("rollout_mlp64 needs 10 or 36 beams")
         if history and self.B != 10:
@@ -766,8 +764,6 @@ class VecEnv:
         each workgroup executed); slots that were not reached hold ``fill``.  The env state afterwards is unspecified (the envs
         ran on past their quota): reset before stepping this env again.
         history=True (policy "mlp64x2", 10 beams): navsim_evaluate_mlp64_hist -- the [7042] 42-64-64 actor on scan-history rows."""
-        import ctypes as C
-        from ._native import check, lib
         if history and (policy != "mlp64x2" or self.B != 10):
             raise ValueError("evaluate_policy(history=True): the scan-history evaluation runs the 42-64-64 actor (policy 'mlp64x2') "
                              f"on 10 beams, not policy {policy!r} on {self.B} beams")

@@ -142,6 +142,56 @@ def evaluate(actor, num_episodes=100, max_timesteps_per_episode=500, map="stage_
     return _report(res, quota, n_par, num_episodes, seconds, steps, output_dir, method_name, log, timing, tape_id, n_tapes)
 
 
+def make_eval_env(train_env, cfg, device):
+    """The evaluation envs of PPOConfig.eval_every: the training env's world (VecEnv.world_args; movers: cfg.eval_movers if set),
+    min(eval_episodes, 1024) envs with the evaluation arrival threshold and a goal / spawn stream of their own."""
+    w = dict(getattr(train_env, "world_args", None) or {})   # (any env with N, B, D and a sim can train; only a VecEnv says this)
+    if not w:
+        raise ValueError("PPOConfig.eval_every: the training env does not describe its world (VecEnv.world_args)")
+    if torch.is_tensor(w["map"]) and w["map"].dim() == 3:
+        raise ValueError("PPOConfig.eval_every: a per-env segment tensor cannot be reused for the evaluation envs; pass a map "
+                         "name or a shared [S, 4] map (per_env_map=True replicates it)")
+    n_par = min(int(cfg.eval_episodes), 1024)
+    if n_par < 1:
+        raise ValueError("PPOConfig.eval_episodes must be at least 1")
+    seed = (int(cfg.seed) * 1000003 + 7919) & 0xFFFFFFFF   # its own goal / spawn stream, derived from cfg.seed
+    if cfg.eval_movers is not None:   # the held-out set: resolved like VecEnv's movers, given to the evaluation env only
+        w["movers"] = cfg.eval_movers
+    return VecEnv(n_par, max_episode_steps=cfg.max_episode_steps, auto_reset=True, is_training=False, seed=seed, device=device, **w)
+
+
+def evaluate_params(env, flat_params, policy, history, eval_episodes):
+    """eval_episodes episodes of the actor in the flat parameter buffer in ONE launch on env: the deterministic mean action, a fixed
+    quota of whole episodes per env, rows cut slot-major to eval_episodes as evaluate() does.  The sums are taken on the device and
+    read with one synchronisation.  Returns the eval_* figures of PPOTrainer.evaluate_now."""
+    n_ep = int(eval_episodes)
+    quota = -(-n_ep // env.N)
+    t0 = time.time()
+    tab = env.evaluate_policy(flat_params, quota, policy=policy, history=history)
+    cut = lambda x: x.reshape(-1)[:n_ep]
+    fl = cut(tab.flags)
+    sums = torch.stack([(fl & 1).sum().double(), ((fl >> 1) & 1).sum().double(), ((fl >> 2) & 1).sum().double(),
+                        cut(tab.length).double().sum(), cut(tab.ret).double().sum(), cut(tab.path).double().sum(),
+                        tab.count.min().double(), tab.steps.max().double()])
+    n_tapes = env.sim.movers_tapes if env.sim.movers_tape_id is not None else 0
+    if n_tapes:   # a bank of tapes: episodes and successes per scenario (row r of the table was played by env r mod N)
+        ids = cut(env.sim.movers_tape_id.long().repeat(quota))
+        sums = torch.cat([sums, torch.bincount(ids, minlength=n_tapes).double(),
+                          torch.bincount(ids, weights=(fl & 1).double(), minlength=n_tapes)])
+    sums = sums.cpu().numpy()   # the one host sync
+    per_tape = sums[8:].reshape(2, -1)
+    if int(sums[6]) < quota:
+        raise RuntimeError("evaluate_now: an env did not finish its quota of episodes")
+    sums = [float(v) for v in sums]
+    out = dict(eval_episodes=n_ep, eval_success=sums[0] / n_ep, eval_collision=sums[1] / n_ep, eval_timeout=sums[2] / n_ep,
+               eval_length=sums[3] / n_ep, eval_return=sums[4] / n_ep, eval_path_length=sums[5] / n_ep,
+               eval_steps=int(sums[7]), eval_time=time.time() - t0)
+    if n_tapes:
+        rate = per_tape[1][per_tape[0] > 0] / per_tape[0][per_tape[0] > 0]   # (scenarios that played at least one episode)
+        out.update(eval_scenario_success_min=float(rate.min()), eval_scenario_success_mean=float(rate.mean()))
+    return out
+
+
 def scenario_report(rows, tape_id, n_tapes):
     """The episode table grouped by scenario: rows = evaluate()'s rows in their slot-major order (row r was played by env
     r mod len(tape_id)), tape_id [n_par] the tape of each env -> one dict per tape of the bank: scenario, episodes and the success,

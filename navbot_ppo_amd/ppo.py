@@ -14,7 +14,7 @@ Follows ``project_ppo/src/ppo.py`` of the reference function by function, vector
                                     epochs of clipped surrogate + MSE critic, Adam(lr 3e-4), no entropy
                                     term, no value clip, no gradient clipping (PPOConfig.max_grad_norm
                                     turns on per-net clipping + a non-finite guard; the gradient-norm
-                                    check of ppo.py:356-379,414-416 is PPOTrainer._grad_guard)
+                                    check of ppo.py:356-379,414-416 is train_log.grad_guard)
                                     PPOConfig.minibatch_size: K optimiser steps per epoch on slices of the batch, shuffled
                                     on the device (navppo_shuffle_batch; host mirror: batch_permutation)
                                     PPOConfig.lr_schedule: "adaptive" = the learning rate follows every step's approx_kl, decided
@@ -30,9 +30,12 @@ of env ids; after each backward ONE all-reduce (RCCL over xGMI; gloo on CPU for 
 flat gradient buffer holding actor+critic; the advantage mean/std come from all-reduced
 (sum, sum of squares, count) so they equal the single-process values of ppo.py:284.
 
-This module is the import surface and holds no code of its own: rollout, learn and the logging live in trainer.py (PPOTrainer), update
+This module is the import surface and holds no code of its own: rollout, iteration and learn live in trainer.py (PPOTrainer), update
 and evaluate in updater.py (PPOUpdater), the options and their checks in config.py, the host mirrors in minibatch.py, reward_norm.py and
-lr_schedule.py, the per-scenario sums and the scenario sampler in scenarios.py, the ranks in distributed.py.
+lr_schedule.py, the per-scenario sums, the scenario sampler and the scenario table in scenarios.py, the ranks in distributed.py.
+  train_log.py    what an iteration writes: progress line, scalars.jsonl, TensorBoard, episode CSV, grad_diagnostics.txt (RunLog)
+  checkpoint.py   the two reference-named state_dict files and the <kind>_<tag>.pth sidecars beside them
+  evaluate.py     main.evaluate, and the periodic evaluation of PPOConfig.eval_every (make_eval_env, evaluate_params)
 """
 import torch.distributed as dist  # noqa: F401
 

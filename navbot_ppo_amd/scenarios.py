@@ -86,6 +86,20 @@ def group_sums(ended, arrive, done, ep_length, ep_return, group, K, adv=None, ou
     return out
 
 
+def scenario_rows(G, envs_per_scenario, sampler, iteration):
+    """One dict per scenario for <method>_train_scenarios.csv (SCENARIO_CSV_HEADER): evaluate.scenario_report's fields (scenario,
+    episodes and the success, collision and time-out rate, NaN where no episode ended) plus iteration, envs, score and weight, from the
+    global [K, 8] sums G, the [K] envs per scenario over all ranks and the sampler's scores."""
+    w, nan = sampler.weights(), float("nan")
+    rows = []
+    for k in range(sampler.K):
+        ep = G[k, 0]
+        rows.append(dict(iteration=iteration, scenario=k, envs=int(envs_per_scenario[k]), episodes=int(ep),
+                         success_rate=float(G[k, 1] / ep) if ep else nan, collision_rate=float(G[k, 2] / ep) if ep else nan,
+                         timeout_rate=float(G[k, 3] / ep) if ep else nan, score=float(sampler.score[k]), weight=float(w[k])))
+    return rows
+
+
 class ScenarioSampler:
     """Scores per scenario from the [K, 8] sums of navppo_group_sums, and the assignment of envs to scenarios they lead to.  Pure
     numpy, deterministic, no generator streams: the same on every rank and under every numpy version.

@@ -1,25 +1,35 @@
-"""PPO.learn for a VecEnv shard (ppo.py:218-461): rollout, return scan, update, logging and checkpoints."""
+"""PPO.learn for a VecEnv shard (ppo.py:218-461): the loop -- rollout, return scan, update -- and the device state it runs on.  What
+an iteration writes is train_log.py's, the checkpoint files are checkpoint.py's, the periodic evaluation is evaluate.py's."""
 import ctypes as C
+import functools
 import math
 import os
 import time
 
+import numpy as np
 import torch
 
-from . import nets
+from . import checkpoint, nets, train_log
 from ._native import _navppo, _ptr, check, lib
 from .config import (PPOConfig, check_bootstrap_config, check_continue_config, check_reward_norm_config, check_scan_history_config,
                      check_scenario_config)
 from .distributed import as_ctx
+from .env import HIST_CARRY, HIST_DIM, gae_scan, gae_scan_trunc, rtg_scan, stack_rows
+from .evaluate import evaluate_params, make_eval_env
 from .lr_schedule import linear_lr
 from .reward_norm import RET_RMS_INIT, return_moments, reward_scale
-from .updater import LOG_2PI, PPOUpdater, gaussian_log_prob
+from .scenarios import GROUP_SUMS_COLS, SCENARIO_CSV_HEADER, ScenarioSampler, group_sums, scenario_rows
+from .updater import PPOUpdater, gaussian_log_prob
 
 
 class PPOTrainer:
     """PPO.learn for a ``VecEnv`` shard.  Construct one per process (= per GPU)."""
 
+    # Class-level defaults.  __init__ sets every attribute a trainer reads; these two are ALSO there on a trainer that never ran it:
+    # the CPU tests build bare trainers (PPOTrainer.__new__, cfg and a few attributes, one method), and the methods they call --
+    # save_checkpoint / load_checkpoint, tb_scalars, _grad_guard, learn -- read nothing else beyond the state of an option cfg has on.
     scenarios = None   # the ScenarioSampler of scenario_stats / scenario_priority (None: both off)
+    _log = None        # the RunLog of the run's files, created at the first write (_run_log)
 
     def __init__(self, env, cfg=None, ctx=None):
         self.env, self.cfg = env, cfg or PPOConfig()
@@ -30,7 +40,6 @@ class PPOTrainer:
         check_scan_history_config(cfg)
         self.scan_history = cfg.scan_history
         if self.scan_history:
-            from .env import HIST_DIM
             if env.B != 10:
                 raise ValueError(f"scan_history needs n_beams == 10 (the history row stacks 10-beam scans), not {env.B}")
             if self.device.type != "cuda":
@@ -74,7 +83,6 @@ class PPOTrainer:
         self._reset_pending, self._reset_gen, self._did_reset = True, None, True
         if self.continue_rollouts:
             if self.scan_history:
-                from .env import HIST_CARRY
                 self._hist_carry = [torch.zeros((N, HIST_CARRY), dtype=f32, device=dev) for _ in range(2)]
             if cfg.norm_reward:
                 self._ret_carry = torch.zeros(N, dtype=torch.float64, device=dev)
@@ -86,7 +94,10 @@ class PPOTrainer:
         self.var_host = float(cfg.init_var)   # host mirror, refreshed at every rollout start
         self._lo = torch.tensor([0.0, -1.0], device=dev)
         self._hi = torch.tensor([1.0, 1.0], device=dev)
-        self._graph = None
+        self._graph = self._graph_gen = None   # the captured hipGraph of per-step launches, and the generation of the world it froze
+        self._gae = None        # (raw advantages, V) of the last rollout where a GAE scan ran
+        self._sums_ws = None    # navppo_episode_sums' workspace, allocated by the first _rollout_metrics_dev
+        self._eval_env = None   # the evaluation envs of eval_every, created by the first evaluate_now
         self._step_base = torch.zeros((), dtype=torch.int32, device=dev)  # rollout steps taken so far (noise counter)
         self._act_seed = (cfg.seed * 0x9E3779B97F4A7C15 + 0xAC7) & 0xFFFFFFFFFFFFFFFF
         self._env_id_base = int(env.sim.cfg.env_id_base)
@@ -130,7 +141,7 @@ class PPOTrainer:
         rows = self._ret_rows
         if ctx.enabled and rows.shape[0] > 1:
             rows.zero_()
-        carry = getattr(self, "_ret_carry", None)   # (there with continue_rollouts alone)
+        carry = self._ret_carry if cfg.continue_rollouts else None   # (the tensor is there with the option alone)
         return_moments(self.rew_buf, self.ended_buf, cfg.gamma, carry=carry, out=rows[ctx.rank])
         ctx.all_reduce_sum(rows)
         return reward_scale(self.ret_rms, rows, self.rew_buf, clip=cfg.clip_reward, eps=cfg.norm_reward_eps, out=self.rew_scaled_buf)
@@ -145,7 +156,6 @@ class PPOTrainer:
 
     # ---- PPOConfig.scenario_stats / scenario_priority: the rollout summed per scenario, and the envs re-assigned by what it shows
     def _init_scenarios(self):
-        from .scenarios import GROUP_SUMS_COLS, ScenarioSampler
         cfg, env, sim = self.cfg, self.env, self.env.sim
         K = int(getattr(sim, "movers_tapes", 0) or 0)
         if getattr(env, "mover_bank", None) is None or K < 2:
@@ -166,7 +176,6 @@ class PPOTrainer:
     def _scenario_envs(self):
         """[K] envs per scenario over ALL ranks (the table's column): from the sampler's last assignment, or -- nothing re-assigned yet
         -- from the constructor's rule for every global env"""
-        import numpy as np
         if self._scen_ids_host is None:
             bank, env = self.env.mover_bank, self.env
             if isinstance(bank.assign, str):
@@ -177,7 +186,6 @@ class PPOTrainer:
 
     def _scenario_sums_dev(self):
         """navppo_group_sums behind navppo_episode_sums: this rank's [K, 8] table, flat (the caller all-reduces it with the six sums)"""
-        from .scenarios import group_sums
         T, N = self.cfg.rollout_len, self.env.N
         adv = self._gae[0].reshape(T, N) if (self.cfg.scenario_priority == "abs_adv" and self._gae is not None) else None
         return group_sums(self.ended_buf, self.arrive_buf, self.done_buf, self.eplen_buf, self.epret_buf, self.env.sim.movers_tape_id,
@@ -187,7 +195,6 @@ class PPOTrainer:
         """After the read-back (i_so_far already counts the iteration): the scores take in the iteration's global [K, 8] sums, the log
         and the table are written, and -- with scenario_priority, every scenario_resample_every iterations -- the envs get their next
         scenarios (the stream is idle)."""
-        import numpy as np
         cfg, smp = self.cfg, self.scenarios
         G = np.asarray(G, dtype=np.float64).reshape(self._scen_K, self._scen_cols)
         smp.observe(G)
@@ -197,16 +204,8 @@ class PPOTrainer:
                    train_scenario_success_mean=float(rate.mean()) if rate.size else float("nan"))
         self.scenario_table = self.scenario_rows(G)
         if cfg.output_dir and self.writes_files:
-            import csv
-            from .scenarios import SCENARIO_CSV_HEADER
-            os.makedirs(self.log_dir(), exist_ok=True)
-            path = os.path.join(self.log_dir(), f"{cfg.method_name}_train_scenarios.csv")
-            new = not os.path.exists(path)
-            with open(path, "a", newline="") as f:
-                w = csv.writer(f)
-                if new:
-                    w.writerow(SCENARIO_CSV_HEADER)
-                w.writerows([[r[h] for h in SCENARIO_CSV_HEADER] for r in self.scenario_table])
+            train_log.append_rows(self._run_log().path("train_scenarios.csv"), SCENARIO_CSV_HEADER,
+                                  [[r[h] for h in SCENARIO_CSV_HEADER] for r in self.scenario_table])
         if cfg.scenario_priority is not None and self.i_so_far % cfg.scenario_resample_every == 0:
             ids = smp.assign(self._n_global)
             self._scen_ids_host = ids
@@ -214,16 +213,8 @@ class PPOTrainer:
         return out
 
     def scenario_rows(self, G):
-        """One dict per scenario for <method>_train_scenarios.csv: evaluate.scenario_report's fields (scenario, episodes and the success,
-        collision and time-out rate, NaN where no episode ended) plus iteration, envs, score and weight, from the global [K, 8] sums."""
-        envs, w, nan = self._scenario_envs(), self.scenarios.weights(), float("nan")
-        rows = []
-        for k in range(self._scen_K):
-            ep = G[k, 0]
-            rows.append(dict(iteration=self.i_so_far, scenario=k, envs=int(envs[k]), episodes=int(ep),
-                             success_rate=float(G[k, 1] / ep) if ep else nan, collision_rate=float(G[k, 2] / ep) if ep else nan,
-                             timeout_rate=float(G[k, 3] / ep) if ep else nan, score=float(self.scenarios.score[k]), weight=float(w[k])))
-        return rows
+        """the rows of <method>_train_scenarios.csv from the global [K, 8] sums of an iteration (scenarios.scenario_rows)"""
+        return scenario_rows(G, self._scenario_envs(), self.scenarios, self.i_so_far)
 
     def _fused_act(self, t, noise=None):
         """PPO.get_action for all envs in ONE launch (csrc/ppo_mlp64.hip: mlp64_act, csrc/ppo_resmlp512.hip: resmlp_act)."""
@@ -283,6 +274,15 @@ class PPOTrainer:
 
     @torch.no_grad()
     def rollout(self):
+        self._collect()
+        if self.scan_history:
+            self._stack_history()
+        self._compute_returns()
+        self.env_steps += self.cfg.rollout_len * self.env.N
+
+    def _collect(self):
+        """T steps of all envs into the [T, N] buffers: ONE persistent launch, the replay of the captured hipGraph of per-step launches
+        (captured here, behind a warm-up step, the first time and after a change of the world), or the per-step launches themselves."""
         cfg = self.cfg
         self._decay_exploration()
         self.epret_buf.zero_()
@@ -314,41 +314,46 @@ class PPOTrainer:
             self._graph.replay()
         else:
             self._rollout_body()
-        from .env import gae_scan, gae_scan_trunc, rtg_scan
-        if self.scan_history:   # the batch the nets read, [T + 1, N, 42]: one bandwidth kernel per iteration
-            from .env import stack_rows
-            self.updater.invalidate_prepared()   # hist_buf is rewritten behind torch's version counter too
-            if self.continue_rollouts:   # row 0 continues from its carry, so hist_buf[T] is the exact row the value bootstrap reads
-                stack_rows(self.obs_buf, self.ended_buf, out=self.hist_buf, carry_in=None if self._did_reset else self._hist_carry[0])
-                self._hist_carry.reverse()   # what the launch wrote for row T is the next batch's row 0's
-            else:
-                stack_rows(self.obs_buf, self.ended_buf, out=self.hist_buf)
+
+    def _stack_history(self):
+        """scan_history: the batch the nets read, [T + 1, N, 42], from obs_buf and ended_buf: one bandwidth kernel per iteration"""
+        self.updater.invalidate_prepared()   # hist_buf is rewritten behind torch's version counter too
+        if self.continue_rollouts:   # row 0 continues from its carry, so hist_buf[T] is the exact row the value bootstrap reads
+            stack_rows(self.obs_buf, self.ended_buf, out=self.hist_buf, carry_in=None if self._did_reset else self._hist_carry[0])
+            self._hist_carry.reverse()   # what the launch wrote for row T is the next batch's row 0's
+        else:
+            stack_rows(self.obs_buf, self.ended_buf, out=self.hist_buf)
+
+    def _compute_returns(self):
+        """rtg_buf, the critic's targets, from the rewards (norm_reward: scaled first; the scans are the same either way), and
+        _gae = (raw advantages, V) where a GAE scan ran -- None behind the reference's reward-to-go (ppo.py:619 -> 643-671).
+        gae_lambda alone, lambda < 1: the envs still running at the batch end are bootstrapped with V(obs_buf[T]), the observation
+        behind the last row (an env that ended on the last row has ended[T-1] set, which cuts the bootstrap).  lambda = 1 keeps the
+        reference's convention -- the batch end is terminal, ppo.py:601,658-666 -- and stays bit-identical to compute_rtgs.
+        bootstrap_truncated: neither a time-out nor the batch end is the end of the robot.  V of all T + 1 stored rows; a time-out row
+        adds gamma V of its own observation (the terminal observation is gone: the step kernels store the reset one), the envs still
+        running on the last row bootstrap with V(obs_buf[T]) (ended[T-1] cuts that for an env that ended there) -- for every
+        lambda; None runs as 1: the reference's A = R - V on truncation-aware returns.  rew is in the critic's units either way."""
+        cfg = self.cfg
         self._gae = None
-        rew = self._normalise_rewards() if cfg.norm_reward else self.rew_buf   # (the scans below are the same either way)
+        rew = self._normalise_rewards() if cfg.norm_reward else self.rew_buf
         trunc, lam = cfg.bootstrap_truncated, cfg.gae_lambda
         if not trunc and lam is None:
-            rtg_scan(rew, self.ended_buf, cfg.gamma, out=self.rtg_buf)  # ppo.py:619 -> 643-671
-        else:   # extension: the critic's values of the stored observations -> lambda-returns (critic targets) and advantages
-            # gae_lambda alone, lambda < 1: the envs still running at the batch end are bootstrapped with V(obs_buf[T]), the observation
-            # behind the last row (an env that ended on the last row has ended[T-1] set, which cuts the bootstrap).  lambda = 1 keeps the
-            # reference's convention -- the batch end is terminal, ppo.py:601,658-666 -- and stays bit-identical to compute_rtgs.
-            # bootstrap_truncated: neither a time-out nor the batch end is the end of the robot.  V of all T + 1 stored rows; a time-out row
-            # adds gamma V of its own observation (the terminal observation is gone: the step kernels store the reset one), the envs still
-            # running on the last row bootstrap with V(obs_buf[T]) (ended[T-1] cuts that for an env that ended there) -- for every
-            # lambda; None runs as 1: the reference's A = R - V on truncation-aware returns.  rew is in the critic's units either way.
-            T, N, D = cfg.rollout_len, self.env.N, self.net_dim
-            lam = 1.0 if lam is None else lam
-            boot = trunc or lam < 1.0   # V(obs_buf[T]) bootstraps the last row
-            Vall = self.updater.value(self.net_obs[:T + 1 if boot else T].reshape(-1, D)).reshape(-1, N)
-            V = Vall[:T].contiguous()
-            last = Vall[T] if boot else None
-            if trunc:
-                adv, ret = gae_scan_trunc(rew, self.ended_buf, self.done_buf, self.arrive_buf, V, cfg.gamma, lam, last_value=last)
-            else:
-                adv, ret = gae_scan(rew, self.ended_buf, V, cfg.gamma, lam, last_value=last)
-            self.rtg_buf.copy_(ret)
-            self._gae = (adv.reshape(T * N), V.reshape(T * N))
-        self.env_steps += cfg.rollout_len * self.env.N
+            rtg_scan(rew, self.ended_buf, cfg.gamma, out=self.rtg_buf)
+            return
+        # extension: the critic's values of the stored observations -> lambda-returns (critic targets) and advantages
+        T, N, D = cfg.rollout_len, self.env.N, self.net_dim
+        lam = 1.0 if lam is None else lam
+        boot = trunc or lam < 1.0   # V(obs_buf[T]) bootstraps the last row
+        Vall = self.updater.value(self.net_obs[:T + 1 if boot else T].reshape(-1, D)).reshape(-1, N)
+        V = Vall[:T].contiguous()
+        last = Vall[T] if boot else None
+        if trunc:
+            adv, ret = gae_scan_trunc(rew, self.ended_buf, self.done_buf, self.arrive_buf, V, cfg.gamma, lam, last_value=last)
+        else:
+            adv, ret = gae_scan(rew, self.ended_buf, V, cfg.gamma, lam, last_value=last)
+        self.rtg_buf.copy_(ret)
+        self._gae = (adv.reshape(T * N), V.reshape(T * N))
 
     def reset_envs(self):
         """continue_rollouts: the next rollout starts from a reset of all envs (as the first one does, and the one behind a change of
@@ -390,22 +395,22 @@ class PPOTrainer:
     def _rollout_metrics_dev(self):
         """The six sums behind the iteration's episode metrics as ONE device tensor (all-reduced over the ranks); nothing
         here waits for the GPU, so the update can be queued behind it.  With scenario_stats / scenario_priority the [K, 8] sums per
-        scenario follow the six in the same tensor: one more launch, the same ONE collective."""
-        if getattr(self, "_sums_ws", None) is None:
+        scenario follow the six in the same tensor: one more launch, the same ONE collective.  Returns (tensor, its sections as
+        train_log.join_sections names them: "episodes", then "scenarios")."""
+        if self._sums_ws is None:
             self._sums_ws = torch.empty(256 * 6, dtype=torch.float64, device=self.device)
         m = torch.empty(6, dtype=torch.float64, device=self.device)
         with torch.cuda.device(self.device):
             _navppo("navppo_episode_sums", _ptr(self.ended_buf), _ptr(self.arrive_buf), _ptr(self.done_buf), _ptr(self.eplen_buf),
                     _ptr(self.epret_buf), self.ended_buf.numel(), _ptr(m), _ptr(self._sums_ws))
-        if self.scenarios is not None:
-            m = torch.cat([m, self._scenario_sums_dev()])
+        m, sections = train_log.join_sections([("episodes", m)] + ([] if self.scenarios is None else [("scenarios", self._scenario_sums_dev())]))
         self.ctx.all_reduce_sum(m)
-        return m
+        return m, sections
 
     def _rollout_metrics(self, m=None):
-        m = self._rollout_metrics_dev() if m is None else m   # (a tensor, or the six figures already on the host)
+        m = self._rollout_metrics_dev()[0] if m is None else m   # (a tensor, or the six figures already on the host)
         ep, succ, coll, tmo, steps, ret = [float(x) for x in (m.tolist() if torch.is_tensor(m) else m)]
-        self.episode_starts = ep / self.ctx.world + (self.env.N if getattr(self, "_did_reset", True) else 0)   # (the reset started N episodes)
+        self.episode_starts = ep / self.ctx.world + (self.env.N if self._did_reset else 0)   # (the reset started N episodes)
         return dict(episodes=int(ep), successes=int(succ), collisions=int(coll), timeouts=int(tmo),
                     completed_steps=int(steps), avg_ep_rews=(ret / ep if ep else 0.0),       # ppo.py:833
                     avg_ep_lens=(steps / ep if ep else 0.0), success_rate=(succ / ep if ep else 0.0))
@@ -424,35 +429,34 @@ class PPOTrainer:
         if cuda:
             ev[1].record()
         t1 = time.time()
-        m = self._rollout_metrics_dev()
+        m, sections = self._rollout_metrics_dev()
         stats = self.updater.update(self.net_obs[:T].reshape(T * N, D), self.act_buf.reshape(T * N, 2),
                                     self.logp_buf.reshape(T * N), self.rtg_buf.reshape(T * N),
                                     self.var_host if self.updater.fused else self.var,
                                     **({} if self._gae is None else dict(adv_raw=self._gae[0], V0=self._gae[1])))
         if cuda:
             ev[2].record()
-        n_scen = 0 if self.scenarios is None else self._scen_K * self._scen_cols   # (the per-scenario sums sit behind the six)
         if cfg.norm_reward:   # the option's figures ride on the episode sums' read-back below: one tensor, one copy
-            m = torch.cat([m, self._reward_norm_figures_dev()])
+            rn = self._reward_norm_figures_dev()   # (behind the collective: every rank's own figures)
+            m, sections = torch.cat([m, rn]), sections + [("reward_norm", rn.numel())]
         if cuda:
             torch.cuda.synchronize(self.device)
         t2 = time.time()
         if cuda:   # the host ran ahead of the stream: split the wall clock of the iteration by the stream's own stamps
             r_ms, u_ms = ev[0].elapsed_time(ev[1]), ev[1].elapsed_time(ev[2])
             t1 = t0 + (t2 - t0) * r_ms / max(r_ms + u_ms, 1e-9)
-        if n_scen or cfg.norm_reward:
-            m = m.tolist()   # the one read-back
-            scen, rn, m = m[6:6 + n_scen], m[6 + n_scen:], m[:6]
+        back = train_log.split_sections(m, sections)   # the one read-back (the six alone: still the tensor, read by _rollout_metrics)
         if cfg.norm_reward:
-            stats = dict(stats, reward_scale=rn[3], ret_rms_mean=rn[0], ret_rms_std=math.sqrt(max(rn[1], 0.0)), explained_variance=rn[4])
-        metrics = self._rollout_metrics(m)
+            mean, var, _, scale, expl = back["reward_norm"]   # (_reward_norm_figures_dev)
+            stats = dict(stats, reward_scale=scale, ret_rms_mean=mean, ret_rms_std=math.sqrt(max(var, 0.0)), explained_variance=expl)
+        metrics = self._rollout_metrics(back["episodes"])
         world = self.ctx.world
         if cfg.bootstrap_truncated:   # the share of rows the scan bootstrapped as time-outs: the episode sums' figure, nothing launched
             stats = dict(stats, bootstrapped_frac=metrics["timeouts"] / max(T * N * world, 1))
         self.t_so_far += metrics["completed_steps"]
         self.i_so_far += 1
-        if n_scen:
-            stats = dict(stats, **self._scenario_step(scen))
+        if "scenarios" in back:
+            stats = dict(stats, **self._scenario_step(back["scenarios"]))
         self._grad_guard(stats)
         self.logger = dict(metrics, **stats, iteration=self.i_so_far, t_so_far=self.t_so_far,
                            rollout_time=t1 - t0, update_time=t2 - t1, iter_time=t2 - t0,
@@ -463,240 +467,17 @@ class PPOTrainer:
         if cfg.output_dir and self.writes_files:
             if self.i_so_far % cfg.save_freq == 0:
                 self.save_checkpoint()
-            import json
-            os.makedirs(self.log_dir(), exist_ok=True)
-            with open(os.path.join(self.log_dir(), "scalars.jsonl"), "a") as f:
-                f.write(json.dumps(dict(self.tb_scalars(), iteration=self.i_so_far, t_so_far=self.t_so_far)) + "\n")
+            train_log.append_json_line(os.path.join(self.log_dir(), "scalars.jsonl"),
+                                       dict(self.tb_scalars(), iteration=self.i_so_far, t_so_far=self.t_so_far))
             if cfg.episode_csv_rows:
                 self.write_episode_csv(cfg.episode_csv_rows)
             self.write_tensorboard()
         return self.logger
 
-    # ---- the gradient check of the reference (ppo.py:356-379, 414-416), once per iteration on figures that are already on the host
-    def _grad_guard(self, stats, log=print):
-        """A per-net mean gradient norm that is <= 0 or not finite, a loss that is not finite, or a skipped step (max_grad_norm):
-        the reference's warning line, and a block in <output_dir>/grad_diagnostics.txt.  No launch and no sync unless it triggers
-        (then a few reductions over the advantages for the file); it reports only -- what happens to the weights is decided by
-        PPOConfig.max_grad_norm inside the update -- and never raises.  Returns the nets that triggered."""
-        cfg = self.cfg
-        if cfg.n_updates_per_iteration < 1:
-            return []
-        hit = []
-        for net in ("actor", "critic"):
-            gn, loss, sk = stats.get(net + "_grad_norm", 0.0), stats.get(net + "_loss", 0.0), stats.get("skipped_steps_" + net, 0)
-            if gn <= 0 or not math.isfinite(gn) or not math.isfinite(loss) or sk > 0:
-                hit.append((net, gn, loss, sk))
-        if not hit or not self.writes_files:
-            return [h[0] for h in hit]
-        try:
-            for net, gn, loss, sk in hit:
-                if log:
-                    log(f"[WARNING] {net.capitalize()} grad norm invalid: {gn:.6f} at iteration {self.i_so_far}. Check grad_diagnostics.txt"
-                        + (f" ({sk} of {cfg.n_updates_per_iteration} steps skipped)" if sk else ""), flush=True)
-            if cfg.output_dir:
-                adv = getattr(self.updater, "_last_adv", None)
-                a = [float("nan")] * 4 if adv is None else [float(x) for x in (adv.mean(), adv.std(), adv.min(), adv.max())]
-                os.makedirs(cfg.output_dir, exist_ok=True)
-                with open(os.path.join(cfg.output_dir, "grad_diagnostics.txt"), "a") as f:
-                    for net, gn, loss, sk in hit:
-                        f.write(f"\n[{net.upper()} GRAD ISSUE] Iteration {self.i_so_far}\n")
-                        f.write(f"  Net: {net}\n")
-                        f.write(f"  {net.capitalize()} grad norm: {gn}\n")
-                        f.write(f"  {net.capitalize()} loss: {loss}\n")
-                        f.write(f"  Skipped steps: {sk} of {cfg.n_updates_per_iteration}\n")
-                        f.write(f"  Advantage stats: mean={a[0]:.4f}, std={a[1]:.4f}, min={a[2]:.4f}, max={a[3]:.4f}\n")
-                        f.write(f"  Clip fraction: {stats.get('clip_frac', 0.0):.4f}\n")
-        except Exception as e:   # a diagnostics file must never end a run
-            try:
-                print(f"[WARNING] grad diagnostics not written: {e}", flush=True)
-            except Exception:
-                pass
-        return [h[0] for h in hit]
-
-    # ---- periodic evaluation (PPOConfig.eval_every)
-    EVAL_HISTORY_HEADER = ["iteration", "timesteps", "episodes", "success_rate", "collision_rate", "timeout_rate", "mean_length",
-                           "mean_return", "mean_path_length"]
-
     @property
     def stats(self):
         """the last iteration's figures (what iteration() returned)"""
         return self.logger
-
-    def _make_eval_env(self):
-        from .env import VecEnv
-        w = dict(getattr(self.env, "world_args", None) or {})
-        if not w:
-            raise ValueError("PPOConfig.eval_every: the training env does not describe its world (VecEnv.world_args)")
-        if torch.is_tensor(w["map"]) and w["map"].dim() == 3:
-            raise ValueError("PPOConfig.eval_every: a per-env segment tensor cannot be reused for the evaluation envs; pass a map "
-                             "name or a shared [S, 4] map (per_env_map=True replicates it)")
-        n_par = min(int(self.cfg.eval_episodes), 1024)
-        if n_par < 1:
-            raise ValueError("PPOConfig.eval_episodes must be at least 1")
-        seed = (int(self.cfg.seed) * 1000003 + 7919) & 0xFFFFFFFF   # its own goal / spawn stream, derived from cfg.seed
-        if self.cfg.eval_movers is not None:   # the held-out set: resolved like VecEnv's movers, given to the evaluation env only
-            w["movers"] = self.cfg.eval_movers
-        return VecEnv(n_par, max_episode_steps=self.cfg.max_episode_steps, auto_reset=True, is_training=False, seed=seed,
-                      device=self.device, **w)
-
-    def evaluate_now(self):
-        """eval_episodes episodes of the current actor in ONE launch on the evaluation envs (created at the first call): the
-        deterministic mean action, arrival threshold 0.4, a fixed quota of whole episodes per env, rows cut slot-major to
-        eval_episodes as evaluate() does.  Reads the flat parameter buffer the update writes and nothing of the training env
-        (its state, RNG counters, the noise counter and the captured graph are untouched).  Returns the eval_* figures and
-        appends one row to <method>_eval_history.csv."""
-        cfg = self.cfg
-        if not (self.updater.fused_mlp64 or self.updater.fused_resmlp512):
-            raise ValueError(f"PPOConfig.eval_every: no evaluation kernel for policy {cfg.policy!r} on this update path "
-                             "(it needs the fused HIP update's flat parameter layout)")
-        if getattr(self, "_eval_env", None) is None:
-            self._eval_env = self._make_eval_env()
-        env = self._eval_env
-        n_ep = int(cfg.eval_episodes)
-        quota = -(-n_ep // env.N)
-        t0 = time.time()
-        tab = env.evaluate_policy(self.updater.fp.flat, quota, policy="resmlp512" if self.updater.fused_resmlp512 else "mlp64x2",
-                                  history=self.scan_history)
-        cut = lambda x: x.reshape(-1)[:n_ep]
-        fl = cut(tab.flags)
-        sums = torch.stack([(fl & 1).sum().double(), ((fl >> 1) & 1).sum().double(), ((fl >> 2) & 1).sum().double(),
-                            cut(tab.length).double().sum(), cut(tab.ret).double().sum(), cut(tab.path).double().sum(),
-                            tab.count.min().double(), tab.steps.max().double()])
-        n_tapes = env.sim.movers_tapes if env.sim.movers_tape_id is not None else 0
-        if n_tapes:   # a bank of tapes: episodes and successes per scenario (row r of the table was played by env r mod N)
-            ids = cut(env.sim.movers_tape_id.long().repeat(quota))
-            sums = torch.cat([sums, torch.bincount(ids, minlength=n_tapes).double(),
-                              torch.bincount(ids, weights=(fl & 1).double(), minlength=n_tapes)])
-        sums = sums.cpu().numpy()   # the one host sync
-        per_tape = sums[8:].reshape(2, -1)
-        if int(sums[6]) < quota:
-            raise RuntimeError("evaluate_now: an env did not finish its quota of episodes")
-        sums = [float(v) for v in sums]
-        out = dict(eval_episodes=n_ep, eval_success=sums[0] / n_ep, eval_collision=sums[1] / n_ep, eval_timeout=sums[2] / n_ep,
-                   eval_length=sums[3] / n_ep, eval_return=sums[4] / n_ep, eval_path_length=sums[5] / n_ep,
-                   eval_steps=int(sums[7]), eval_time=time.time() - t0)
-        if n_tapes:
-            rate = per_tape[1][per_tape[0] > 0] / per_tape[0][per_tape[0] > 0]   # (scenarios that played at least one episode)
-            out.update(eval_scenario_success_min=float(rate.min()), eval_scenario_success_mean=float(rate.mean()))
-        if cfg.output_dir:
-            import csv
-            os.makedirs(self.log_dir(), exist_ok=True)
-            path = os.path.join(self.log_dir(), f"{cfg.method_name}_eval_history.csv")
-            new = not os.path.exists(path)
-            with open(path, "a", newline="") as f:
-                w = csv.writer(f)
-                if new:
-                    w.writerow(self.EVAL_HISTORY_HEADER)
-                w.writerow([self.i_so_far, self.t_so_far, n_ep, out["eval_success"], out["eval_collision"], out["eval_timeout"],
-                            out["eval_length"], out["eval_return"], out["eval_path_length"]])
-        return out
-
-    # ---- logging surface of the reference: per-episode CSV (ppo.py:159-163,739-746) and the TensorBoard scalar names
-    #      (ppo.py:892-939) written as one JSON object per iteration (tensorboardX is not a dependency here)
-    EPISODE_CSV_HEADER = ["episode", "timestep", "success", "collision", "timeout", "length", "return", "path_length", "time"]
-
-    def log_dir(self):
-        return os.path.join(self.cfg.output_dir, self.cfg.method_name, "logs")
-
-    def write_episode_csv(self, max_rows=None):
-        """Appends the episodes finished in the last rollout, in (step, env) order (ppo.py:739-746).  path_length is the
-        simulator's per-episode accumulator (ppo.py:533-537 semantics: the final step's displacement is not part of it);
-        time is the episode's share of the rollout wall clock, length x (rollout_time / T): the envs advance in lock
-        step, so an episode of L steps occupied L / T of the rollout."""
-        import csv
-        os.makedirs(self.log_dir(), exist_ok=True)
-        path = os.path.join(self.log_dir(), f"{self.cfg.method_name}_train_episodes.csv")
-        new = not os.path.exists(path)
-        ended = self.ended_buf.bool()
-        t_idx, n_idx = torch.nonzero(ended, as_tuple=True)
-        if max_rows is not None:
-            t_idx, n_idx = t_idx[:max_rows], n_idx[:max_rows]
-        d = self.done_buf[t_idx, n_idx].cpu().numpy()
-        a = self.arrive_buf[t_idx, n_idx].cpu().numpy()
-        ln = self.eplen_buf[t_idx, n_idx].cpu().numpy()
-        rt = self.epret_buf[t_idx, n_idx].cpu().numpy()
-        pl = self.eppath_buf[t_idx, n_idx].cpu().numpy()
-        tt = t_idx.cpu().numpy()
-        sec_per_step = float(self.logger.get("rollout_time", 0.0)) / max(self.cfg.rollout_len, 1)
-        base = getattr(self, "_episode_count", 0)
-        with open(path, "a", newline="") as f:
-            w = csv.writer(f)
-            if new:
-                w.writerow(self.EPISODE_CSV_HEADER)
-            for k in range(len(tt)):
-                succ = int(a[k]); coll = int(d[k] and not a[k]); tmo = int(not d[k] and not a[k])  # ppo.py:558-560
-                w.writerow([base + k, self.env_steps - (self.cfg.rollout_len - int(tt[k]) - 1) * self.env.N, succ, coll, tmo,
-                            int(ln[k]), float(rt[k]), float(pl[k]), float(ln[k]) * sec_per_step])
-        self._episode_count = base + len(tt)
-        return path
-
-    def tb_scalars(self):
-        """The scalars the reference hands to SummaryWriter.add_scalar once per iteration, under its tag names
-        (ppo.py:892-918), for the last iteration."""
-        lg = self.logger
-        ep = max(lg.get("episodes", 0), 1)
-        n_ep = self.cfg.n_updates_per_iteration
-        var = float(lg.get("var", self.cfg.init_var))
-        sec_per_step = float(lg.get("rollout_time", 0.0)) / max(self.cfg.rollout_len, 1)
-        return {"train/success_rate": lg.get("success_rate"), "train/collision_rate": lg.get("collisions", 0) / ep,
-                "train/timeout_rate": lg.get("timeouts", 0) / ep, "train/mean_return": lg.get("avg_ep_rews"),
-                "train/mean_ep_length": lg.get("avg_ep_lens"), "train/mean_ep_time": lg.get("avg_ep_lens", 0.0) * sec_per_step,
-                "loss/actor": lg.get("actor_loss"), "loss/critic": lg.get("critic_loss"), "train/timesteps": lg.get("t_so_far"),
-                "time/rollout": lg.get("rollout_time"), "time/update": lg.get("update_time"), "time/iteration": lg.get("iter_time"),
-                "perf/steps_per_sec": lg.get("steps_per_sec"), "perf/actor_grad_steps": n_ep, "perf/critic_grad_steps": n_ep,
-                "ppo/approx_kl": lg.get("approx_kl"),
-                "ppo/entropy": 1.0 + LOG_2PI + math.log(max(var, 1e-30)),   # MultivariateNormal(mean, var I).entropy(), 2-D
-                "ppo/clip_frac": lg.get("clip_frac"), "ppo/actor_grad_norm": lg.get("actor_grad_norm"),
-                "ppo/critic_grad_norm": lg.get("critic_grad_norm"), "ppo/actor_param_delta": lg.get("actor_param_delta"),
-                "ppo/critic_param_delta": lg.get("critic_param_delta"),
-                "ppo/grad_clip_frac_actor": lg.get("grad_clip_frac_actor"), "ppo/grad_clip_frac_critic": lg.get("grad_clip_frac_critic"),
-                "ppo/skipped_steps_actor": lg.get("skipped_steps_actor"), "ppo/skipped_steps_critic": lg.get("skipped_steps_critic"),
-                "ppo/kl_stop_epoch": lg.get("kl_stop_epoch"), "ppo/kl_stopped": lg.get("kl_stopped"),   # (target_kl set)
-                **({"ppo/kl_stop_step": lg["kl_stop_step"]} if "kl_stop_step" in lg else {}),           # (target_kl and minibatches)
-                **({"ppo/" + k: lg[k] for k in ("lr", "lr_ups", "lr_downs") if k in lg}),               # (lr_schedule set)
-                **({"ppo/" + k: lg[k] for k in ("reward_scale", "ret_rms_mean", "ret_rms_std", "explained_variance")}
-                   if "reward_scale" in lg else {}),                                                    # (norm_reward)
-                **({"ppo/bootstrapped_frac": lg["bootstrapped_frac"]} if "bootstrapped_frac" in lg else {}),   # (bootstrap_truncated)
-                **({"scenarios/train_success_min": lg["train_scenario_success_min"],
-                    "scenarios/train_success_mean": lg["train_scenario_success_mean"]}
-                   if "train_scenario_success_min" in lg else {}),                                      # (scenario_stats / _priority)
-                **({"eval/success_rate": lg["eval_success"], "eval/collision_rate": lg["eval_collision"],
-                    "eval/timeout_rate": lg["eval_timeout"], "eval/mean_return": lg["eval_return"],
-                    "eval/mean_ep_length": lg["eval_length"], "time/eval": lg["eval_time"]} if "eval_success" in lg else {})}
-
-    def tb_dir(self):
-        return os.path.join(self.cfg.output_dir, self.cfg.method_name, "tb")   # ppo.py:66
-
-    def write_tensorboard(self):
-        """The reference's TensorBoard stream (ppo.py:892-939): per-iteration scalars at step i_so_far, the per-epoch
-        Actor_loss/train and Critic_loss/train series, Episode_Rewards/train (return / length of every finished episode,
-        ppo.py:586, capped per iteration like the CSV) and avg_ep_rews/train."""
-        from .tb_writer import SummaryWriter
-        if getattr(self, "_tb", None) is None:
-            self._tb = SummaryWriter(self.tb_dir())
-            self._tb_loss_steps = self._tb_ep_steps = 0
-        w, it = self._tb, self.i_so_far
-        t0 = time.time()
-        recs = [(k, float(v), it) for k, v in self.tb_scalars().items() if v is not None]
-        hist = self.updater.loss_history.detach().cpu().numpy()
-        hist = hist[:int(self.updater.stats.get("kl_stop_epoch", hist.shape[0])) + int(self.updater.stats.get("kl_stopped", 0))]   # (rows of epochs that ran)
-        for k in range(hist.shape[0]):
-            recs.append(("Actor_loss/train", float(hist[k, 0]), self._tb_loss_steps + k))
-            recs.append(("Critic_loss/train", float(hist[k, 1]), self._tb_loss_steps + k))
-        self._tb_loss_steps += hist.shape[0]
-        cap = int(self.cfg.tb_episode_rows or 0)
-        if cap:   # own cap, independent of the CSV's: with 4096 envs an iteration finishes ~1e5 episodes
-            ended = self.ended_buf.bool()
-            t_idx, n_idx = torch.nonzero(ended, as_tuple=True)
-            t_idx, n_idx = t_idx[:cap], n_idx[:cap]
-            per_step = (self.epret_buf[t_idx, n_idx] / self.eplen_buf[t_idx, n_idx].clamp(min=1)).cpu().numpy()
-            recs.extend(("Episode_Rewards/train", float(r), self._tb_ep_steps + k) for k, r in enumerate(per_step))
-            self._tb_ep_steps += len(per_step)
-        recs.append(("avg_ep_rews/train", float(self.logger.get("avg_ep_rews", 0.0)), it))
-        recs.append(("time/log", float(getattr(self, "_last_log_time", 0.0)), it))   # the previous iteration's logging cost
-        w.add_scalars(recs)   # one TFRecord per point; CRCs vectorised over the records (tb_writer._masked_crc_many)
-        w.flush()
-        self._last_log_time = time.time() - t0
 
     def learn(self, total_timesteps, log=print):
         # The reference counts only COMPLETED episodes toward the budget (ppo.py:258); if a configuration never completes
@@ -709,96 +490,95 @@ class PPOTrainer:
                 self.updater.set_lr(linear_lr(self.cfg.lr, self.t_so_far, total_timesteps))
             lg = self.iteration()
             if log and self.writes_files:
-                log(f"[iter {lg['iteration']:4d}] t={lg['t_so_far']:>10d} mean_ep_rew={lg['avg_ep_rews']:8.2f} "
-                    f"succ={lg['success_rate']:.3f} ep_len={lg['avg_ep_lens']:6.1f} a_loss={lg['actor_loss']:.4f} "
-                    f"c_loss={lg['critic_loss']:.2f} kl={lg['approx_kl']:.4f} steps/s={lg['steps_per_sec']:.0f} "
-                    f"(rollout {lg['rollout_time']:.3f}s update {lg['update_time']:.3f}s)"
-                    + (f" kl_stop_epoch={lg['kl_stop_epoch']} kl_stopped={lg['kl_stopped']}" if "kl_stop_epoch" in lg else "")
-                    + (f" kl_stop_step={lg['kl_stop_step']}" if "kl_stop_step" in lg else "")
-                    + (f" lr={lg['lr']:.3e}" if "lr" in lg else "")
-                    + (f" lr_ups={lg['lr_ups']} lr_downs={lg['lr_downs']}" if "lr_ups" in lg else "")
-                    + (f" bootstrapped_frac={lg['bootstrapped_frac']:.4f}" if "bootstrapped_frac" in lg else "")
-                    + (f" train scenarios: min={lg['train_scenario_success_min']:.3f} mean={lg['train_scenario_success_mean']:.3f}"
-                       if "train_scenario_success_min" in lg else "")
-                    + (f" eval: succ={lg['eval_success']:.3f} coll={lg['eval_collision']:.3f} tmo={lg['eval_timeout']:.3f} "
-                       f"ret={lg['eval_return']:.2f} len={lg['eval_length']:.1f} ({lg['eval_time']:.3f}s)"
-                       if "eval_success" in lg else "")
-                    + (f" scenarios: min={lg['eval_scenario_success_min']:.3f} mean={lg['eval_scenario_success_mean']:.3f}"
-                       if "eval_scenario_success_min" in lg else ""))
+                log(train_log.progress_line(lg))
         return self.logger
 
-    # ---- ppo.py:452-457 file naming; state_dict keys match the reference's nets for policy resmlp512
+    # ---- periodic evaluation (PPOConfig.eval_every)
+    def evaluate_now(self):
+        """evaluate.evaluate_params on the evaluation envs (created at the first call).  Reads the flat parameter buffer the update
+        writes and nothing of the training env (its state, RNG counters, the noise counter and the captured graph are untouched).
+        Returns the eval_* figures and appends one row to <method>_eval_history.csv."""
+        cfg, up = self.cfg, self.updater
+        if not (up.fused_mlp64 or up.fused_resmlp512):
+            raise ValueError(f"PPOConfig.eval_every: no evaluation kernel for policy {cfg.policy!r} on this update path "
+                             "(it needs the fused HIP update's flat parameter layout)")
+        if self._eval_env is None:
+            self._eval_env = make_eval_env(self.env, cfg, self.device)
+        out = evaluate_params(self._eval_env, up.fp.flat, "resmlp512" if up.fused_resmlp512 else "mlp64x2", self.scan_history,
+                              cfg.eval_episodes)
+        if cfg.output_dir:
+            figures = ("episodes", "success", "collision", "timeout", "length", "return", "path_length")
+            train_log.append_rows(self._run_log().path("eval_history.csv"), self.EVAL_HISTORY_HEADER,
+                                  [[self.i_so_far, self.t_so_far] + [out["eval_" + k] for k in figures]])
+        return out
+
+    # ---- the run's files: forwards to train_log.py, under the names the tests and tools/ call
+    EPISODE_CSV_HEADER, EVAL_HISTORY_HEADER = train_log.EPISODE_CSV_HEADER, train_log.EVAL_HISTORY_HEADER
+
+    def _run_log(self):
+        if self._log is None:
+            self._log = train_log.RunLog(self.cfg)
+        return self._log
+
+    def log_dir(self):
+        return self._run_log().log_dir
+
+    def tb_dir(self):
+        return self._run_log().tb_dir
+
+    def tb_scalars(self):
+        return train_log.tb_scalars(self.logger, self.cfg)
+
+    def _grad_guard(self, stats, log=print):
+        return train_log.grad_guard(stats, self.cfg, self.i_so_far, self.updater._last_adv, self.writes_files, log)
+
+    def write_episode_csv(self, max_rows=None):
+        return self._run_log().write_episode_csv(self.ended_buf, self.done_buf, self.arrive_buf, self.eplen_buf, self.epret_buf,
+                                                 self.eppath_buf, self.env_steps, self.logger.get("rollout_time", 0.0), max_rows)
+
+    def write_tensorboard(self):
+        self._run_log().write_tensorboard(self.i_so_far, self.logger, self.updater.loss_history, self.updater.stats, self.ended_buf,
+                                          self.epret_buf, self.eplen_buf)
+
+    # ---- checkpoints: the two reference-named files (checkpoint.py) and, beside them, one sidecar per option with state of its own
+    sidecar_path = staticmethod(checkpoint.sidecar_path)
+
+    retnorm_path = staticmethod(functools.partial(checkpoint.sidecar_path, "retnorm"))
+    lrsched_path = staticmethod(functools.partial(checkpoint.sidecar_path, "lrsched"))
+
     def checkpoint_dir(self):
         return os.path.join(self.cfg.output_dir, self.cfg.method_name, "checkpoints")
 
+    def _sidecars(self):
+        """One row per sidecar, in the order load_checkpoint() reads them: (kind, the option is on, the payload to store, what takes
+        the stored payload -- None: no such file --, the ONE warning line of a missing file with the path in its {}).  A row whose
+        option is off is not touched: its two callables may read state that only the option creates."""
+        cfg = self.cfg
+        return (("lrsched", cfg.lr_schedule == "adaptive",   # the rate the next step starts from (on the host since the last read-back)
+                 lambda: {"lr": float(self.updater.lr_value)}, lambda s: self.updater.set_lr(float(s["lr"] if s else cfg.lr)),
+                 "lr_schedule='adaptive': {} not found -- the learning rate starts at lr = " + str(cfg.lr)),
+                ("scenarios", self.scenarios is not None,   # the scores and the re-assignment counter (the next assignment is drawn from them)
+                 lambda: dict(self.scenarios.state_dict(), score=[float(v) for v in self.scenarios.score]),
+                 lambda s: self.scenarios.load_state_dict(s or {"score": [float("nan")] * self._scen_K, "counter": 0}),
+                 "scenario_stats / scenario_priority: {} not found -- the scenario scores start fresh"),
+                ("retnorm", cfg.norm_reward,   # the critic's units
+                 lambda: dict(zip(("mean", "var", "count"), self.ret_rms[:3].tolist())),
+                 lambda s: self._init_ret_rms(self.ret_rms.device, *((s["mean"], s["var"], s["count"]) if s else ())),
+                 "norm_reward: {} not found -- the return statistics start fresh; the critic's units are off until they settle"))
+
     def save_checkpoint(self):
-        d = self.checkpoint_dir()
-        os.makedirs(d, exist_ok=True)
-        tag = f"iter{self.i_so_far:04d}_step{self.t_so_far:08d}.pth"
-        pa, pc = os.path.join(d, "actor_" + tag), os.path.join(d, "critic_" + tag)
-        torch.save({k: v.detach().cpu().clone() for k, v in self.actor.state_dict().items()}, pa)
-        torch.save({k: v.detach().cpu().clone() for k, v in self.critic.state_dict().items()}, pc)
-        if self.cfg.norm_reward:   # a third file beside the two reference-named ones: the critic's units
-            mean, var, count = self.ret_rms[:3].tolist()
-            torch.save({"mean": mean, "var": var, "count": count}, os.path.join(d, "retnorm_" + tag))
-        if self.cfg.lr_schedule == "adaptive":   # the rate the next step starts from (on the host since the last update's read-back)
-            torch.save({"lr": float(self.updater.lr_value)}, os.path.join(d, "lrsched_" + tag))
-        if self.scenarios is not None:   # the scores and the re-assignment counter (the next assignment is drawn from them)
-            st = self.scenarios.state_dict()
-            torch.save({"score": [float(v) for v in st["score"]], "counter": st["counter"], "mode": st["mode"]},
-                       os.path.join(d, "scenarios_" + tag))
+        pa, pc = checkpoint.save_nets(self.checkpoint_dir(), f"iter{self.i_so_far:04d}_step{self.t_so_far:08d}.pth", self.actor, self.critic)
+        for kind, on, state, _, _ in self._sidecars():
+            if on:
+                checkpoint.save_sidecar(kind, pa, state())
         return pa, pc
 
-    @staticmethod
-    def sidecar_path(kind, actor_path):
-        """<kind>_<tag>.pth beside actor_<tag>.pth: the files save_checkpoint() writes beside the two reference-named ones"""
-        d, base = os.path.split(actor_path)
-        return os.path.join(d, kind + "_" + (base[len("actor_"):] if base.startswith("actor_") else base))
-
-    @staticmethod
-    def retnorm_path(actor_path):
-        return PPOTrainer.sidecar_path("retnorm", actor_path)
-
-    @staticmethod
-    def lrsched_path(actor_path):
-        return PPOTrainer.sidecar_path("lrsched", actor_path)
-
-    def _load_sidecar(self, kind, actor_path, missing):
-        """What save_checkpoint() stored in the `kind` file beside the actor's, or -- no such file -- None after ONE warning line:
-        `missing` with the file's path in its {}."""
-        path = self.sidecar_path(kind, actor_path)
-        if os.path.exists(path):
-            return torch.load(path, map_location="cpu")
-        import warnings
-        warnings.warn(missing.format(path))
-        return None
-
     def load_checkpoint(self, actor_path, critic_path):
-        """main.py:52-89: state_dicts only (optimiser state and covariance are not part of a checkpoint).  With norm_reward the return
-        statistics come from retnorm_<tag>.pth beside the actor's file; without that file: one warning line and fresh statistics.
-        With lr_schedule="adaptive" the learning rate comes from lrsched_<tag>.pth; without that file: one warning line and cfg.lr.
-        With scenario_stats / scenario_priority the scores and the re-assignment counter come from scenarios_<tag>.pth; without that
-        file: one warning line and fresh state."""
+        """main.py:52-89: state_dicts only (optimiser state and covariance are not part of a checkpoint).  An option with a sidecar
+        (_sidecars) takes its state from <kind>_<tag>.pth beside the actor's file; without that file: one warning line and the
+        state of a fresh run (the learning rate: cfg.lr)."""
         self.reset_envs()   # (continue_rollouts: the episodes under way were the old weights')
-        if self.cfg.lr_schedule == "adaptive":
-            s = self._load_sidecar("lrsched", actor_path,
-                                   "lr_schedule='adaptive': {} not found -- the learning rate starts at lr = " + str(self.cfg.lr))
-            self.updater.set_lr(float(s["lr"] if s else self.cfg.lr))
-        if self.scenarios is not None:
-            s = self._load_sidecar("scenarios", actor_path,
-                                   "scenario_stats / scenario_priority: {} not found -- the scenario scores start fresh")
-            self.scenarios.load_state_dict(s or {"score": [float("nan")] * self._scen_K, "counter": 0})
-        if self.cfg.norm_reward:
-            s = self._load_sidecar("retnorm", actor_path,
-                                   "norm_reward: {} not found -- the return statistics start fresh; the critic's units are off until they settle")
-            self._init_ret_rms(self.ret_rms.device, *((s["mean"], s["var"], s["count"]) if s else ()))
-        sa = torch.load(actor_path, map_location="cpu")
-        sc = torch.load(critic_path, map_location="cpu")
-        with torch.no_grad():
-            for mod, sd in ((self.actor, sa), (self.critic, sc)):
-                own = mod.state_dict()
-                missing = set(own) - set(sd)
-                if missing:
-                    raise KeyError(f"checkpoint lacks keys {sorted(missing)}")
-                for k, v in own.items():
-                    v.copy_(sd[k])  # in place: parameters stay views of the flat buffer
+        for kind, on, _, load, missing in self._sidecars():
+            if on:
+                load(checkpoint.load_sidecar(kind, actor_path, missing))
+        checkpoint.load_nets(self.actor, self.critic, actor_path, critic_path)

@@ -117,6 +117,7 @@ class PPOUpdater:
         fused = self.device.type == "cuda"
         self.opt = torch.optim.Adam([self.fp.proxy], lr=cfg.lr, betas=ADAM_HYPER[:2], eps=ADAM_HYPER[2], fused=fused)  # == ppo.py:116-117
         self.stats = {}
+        self._last_adv = self._last_V0 = None   # the last update()'s normalised advantages, and with norm_reward its V0 (the trainer's logs)
         # HIP paths: fused f32-MFMA kernels instead of ~40 (mlp64x2) / ~120 (resmlp512) PyTorch kernels per epoch
         on_gpu = self.device.type == "cuda" and cfg.fused_update
         # the D-64-64 heads: D = 16 (10 beams) or 42 (36 beams), rows float32 or float16 (obs_f16 envs) -- include/navppo.h
