@@ -249,6 +249,45 @@ int navppo_adam_step_lr(float* params_dev, float* grad_dev, float* adam_m_dev, f
                         const float* kl_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------------
+ * Learned exploration variance ON THE DEVICE (the state-independent log-std of Stable-Baselines3 / rsl_rl / rl_games / CleanRL, steered
+ * by an entropy coefficient).  The policy stays MVN(mean, var I) with ONE variance; theta = log var becomes a parameter of the actor
+ * that is stepped after every optimiser step of the nets, so the variance cannot be a by-value argument: it lives in var_state_dev.
+ * navppo_mlp64_update_epoch_var, navppo_mlp64_bf16x3_update_epoch_var and navppo_resmlp512_update_epoch_var take the arguments of their
+ * *_lr twins WITHOUT the by-value `var` and with `ent_coef, var_min, var_max, var_state_dev` in front of `stream`.
+ *   lr_state_dev  may be NULL: the epoch is then that of *_clipped at the constant `lr` (kl_target .. adapt are not read); else that of *_lr.
+ *   max_norm      = +inf means "no clipping", as above.
+ *   var_state_dev [8] f32, 16-byte aligned; the caller starts it as (log v0, v0, 0, 0, 0, 0, 0, 0), afterwards only the library writes it:
+ *                 [0] theta   [1] var -- what the passes read and what a caller hands to every rollout / *_act kernel as var_dev
+ *                 [2] Adam's m   [3] Adam's v   [4] the gradient of the last step taken, after the coefficient
+ *                 [5] steps taken   [6] steps skipped   [7] the entropy H = 1 + log 2 pi + theta after the last step taken
+ *   ent_coef      >= 0 and finite;  var_min > 0;  var_max >= var_min, both finite;  var_state_dev not NULL and 16-byte aligned -- else -1
+ *                 and nothing is launched.  The checks of *_clipped (lr_state_dev NULL) / *_lr are unchanged.
+ * With lp = -1/2 (d0^2 + d1^2) / var - log 2 pi - log var (d measured from the clamped action) the actor's loss is L - ent_coef H and
+ *   d/d theta = sum_i dL_dlp_i (1/2 (d0^2 + d1^2)_i / var - 1) - ent_coef,   dL_dlp_i the factor of the nets' gradient, 1 / n included.
+ * Per call:
+ *   1. the pass twins read var = var_state[1] at their entry and compute lp as ... - logf(var) from it: parameters, moments, grad_dev,
+ *      clip_stats_dev and stats_dev[0..2], [4] are bit for bit those of *_clipped / *_lr called with that var by value.  The per-sample
+ *      terms of the sum above are added per workgroup, then over the workgroups in one fixed order (two calls on the same buffers give
+ *      the same bits); the sum is stored to stats_dev[3] ([7] stays unspecified).
+ *   2. behind the nets' step launch one more launch steps theta: g = (sum - ent_coef) * clip_stats[2] -- theta follows the ACTOR's clip
+ *      coefficient of this step but is not counted in the actor's norm (a deviation from Stable-Baselines3, where log_std lies inside
+ *      the one clipped parameter set).  Coefficient 0 (the actor's step was skipped for a non-finite norm) or g not finite: nothing is
+ *      written but [6] += 1.
+ *   3. else Adam with the call's beta1, beta2, eps and the bias corrections of `step`, the expressions of the nets' step, at the rate
+ *      the nets stepped with (`lr`, or the adaptive rule's rate of this step); theta is clamped to [log var_min, log var_max] (the
+ *      logarithms taken in double and rounded once), var = expf(theta), and [2] .. [5], [7] are written.
+ * Every launch of the NEXT call -- and every rollout queued behind this one on the same stream -- reads the new variance.
+ * navbot_ppo_amd.ppo.learned_var_reference is the host mirror of steps 2 and 3.  Not combined with the *_kl entry points.  Workspaces
+ * are those of the existing entry points.  The multi-GPU form (*_loss_grad twins, the scalar riding on the all-reduce) is not built.
+ */
+int navppo_mlp64_update_epoch_var(float* params_dev, const void* obs_dev, int32_t obs_dim, int32_t obs_f16, const float* act_dev,
+                                  const float* logp_old_dev, const float* rtg_dev, const float* adv_dev, int64_t n_samples, float clip,
+                                  float lr, float beta1, float beta2, float eps, int32_t step, float* adam_m_dev, float* adam_v_dev,
+                                  float* grad_dev, float* stats_dev, void* workspace_dev, float max_norm, float* clip_stats_dev,
+                                  float kl_target, float lr_min, float lr_max, int32_t adapt, float* lr_state_dev, float ent_coef,
+                                  float var_min, float var_max, float* var_state_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------------
  * The same update (ppo.py:305-397; 16- or 42-column rows, float32 or float16) with every matrix product evaluated on the bf16 MFMA from operands split into
  * three bf16 pieces -- "bf16x3": a = a0 + a1 + a2 exactly (8 + 8 + 8 significand bits), a b ~ the six leading piece products,
  * each exact in float32, float32 accumulation, small terms first.  float32-equivalent by measurement (against float64 the
@@ -297,6 +336,14 @@ int navppo_mlp64_bf16x3_update_epoch_lr(float* params_dev, const void* prep_dev,
                                         float* adam_v_dev, float* grad_dev, float* stats_dev, void* workspace_dev, float max_norm,
                                         float* clip_stats_dev, float kl_target, float lr_min, float lr_max, int32_t adapt,
                                         float* lr_state_dev, void* stream);
+
+/* navppo_mlp64_bf16x3_update_epoch_clipped / _lr with the learned exploration variance: see navppo_mlp64_update_epoch_var */
+int navppo_mlp64_bf16x3_update_epoch_var(float* params_dev, const void* prep_dev, int32_t obs_dim, const float* act_dev,
+                                         const float* logp_old_dev, const float* rtg_dev, const float* adv_dev, int64_t n_samples, float clip,
+                                         float lr, float beta1, float beta2, float eps, int32_t step, float* adam_m_dev, float* adam_v_dev,
+                                         float* grad_dev, float* stats_dev, void* workspace_dev, float max_norm, float* clip_stats_dev,
+                                         float kl_target, float lr_min, float lr_max, int32_t adapt, float* lr_state_dev, float ent_coef,
+                                         float var_min, float var_max, float* var_state_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------------
  * Minibatch updates.  Every *_loss_grad / *_update_epoch[_clipped | _kl] entry point takes pointers and n_samples, so one optimiser
@@ -434,6 +481,14 @@ int navppo_resmlp512_update_epoch_lr(float* params_dev, const void* obs_dev, int
                                      float beta1, float beta2, float eps, int32_t step, float* adam_m_dev, float* adam_v_dev,
                                      float* grad_dev, float* stats_dev, void* workspace_dev, float max_norm, float* clip_stats_dev,
                                      float kl_target, float lr_min, float lr_max, int32_t adapt, float* lr_state_dev, void* stream);
+
+/* navppo_resmlp512_update_epoch_clipped / _lr with the learned exploration variance: see navppo_mlp64_update_epoch_var */
+int navppo_resmlp512_update_epoch_var(float* params_dev, const void* obs_dev, int32_t obs_f16, const float* act_dev, const float* logp_old_dev,
+                                      const float* rtg_dev, const float* adv_dev, int64_t n_samples, float clip, float lr, float beta1,
+                                      float beta2, float eps, int32_t step, float* adam_m_dev, float* adam_v_dev, float* grad_dev,
+                                      float* stats_dev, void* workspace_dev, float max_norm, float* clip_stats_dev, float kl_target,
+                                      float lr_min, float lr_max, int32_t adapt, float* lr_state_dev, float ent_coef, float var_min,
+                                      float var_max, float* var_state_dev, void* stream);
 
 /* V = critic(obs).squeeze() (ppo.py:275, :724); critic_params_dev [50257] (8-byte aligned suffices), value_dev [n] */
 int navppo_resmlp512_value(const float* critic_params_dev, const void* obs_dev, int32_t obs_f16, int64_t n_samples, float* value_dev,

@@ -124,6 +124,16 @@ SYMBOLS = [
      [_vp, _vp, _i32] + [_vp] * 4 + [C.c_int64] + [C.c_float] * 6 + [_i32] + [_vp] * 5 + [C.c_float, _vp] + [C.c_float] * 3 + [_i32, _vp, _vp]),
     ("navppo_adam_step_lr", C.c_int,
      [_vp, _vp, _vp, _vp, C.c_int64, C.c_int64] + [C.c_float] * 6 + [_i32, _vp] + [C.c_float] * 3 + [_i32, _vp, _vp, _vp]),
+    # the *_lr prototypes without the by-value var and with ent_coef, var_min, var_max and var_state_dev in front of stream
+    ("navppo_mlp64_update_epoch_var", C.c_int,
+     [_vp, _vp, _i32, _i32] + [_vp] * 4 + [C.c_int64] + [C.c_float] * 5 + [_i32] + [_vp] * 5 + [C.c_float, _vp] + [C.c_float] * 3 +
+     [_i32, _vp] + [C.c_float] * 3 + [_vp, _vp]),
+    ("navppo_mlp64_bf16x3_update_epoch_var", C.c_int,
+     [_vp, _vp, _i32] + [_vp] * 4 + [C.c_int64] + [C.c_float] * 5 + [_i32] + [_vp] * 5 + [C.c_float, _vp] + [C.c_float] * 3 +
+     [_i32, _vp] + [C.c_float] * 3 + [_vp, _vp]),
+    ("navppo_resmlp512_update_epoch_var", C.c_int,
+     [_vp, _vp, _i32] + [_vp] * 4 + [C.c_int64] + [C.c_float] * 5 + [_i32] + [_vp] * 5 + [C.c_float, _vp] + [C.c_float] * 3 +
+     [_i32, _vp] + [C.c_float] * 3 + [_vp, _vp]),
     ("navppo_shuffle_batch", C.c_int, [_vp, _i32, _i32] + [_vp] * 4 + [C.c_int64, C.c_uint64, C.c_uint64] + [_vp] * 7),
     ("navppo_return_moments", C.c_int, [_vp, _vp, _i32, _i32, _d, _vp, _vp, _vp]),
     ("navppo_reward_scale", C.c_int, [_vp, _vp, _i32, _vp, _vp, C.c_int64, _d, _d, _vp]),

@@ -10,7 +10,10 @@ REPO = os.path.dirname(HERE)
 SRCS = [os.path.join(HERE, "csrc", f) for f in ("navsim.hip", "ppo_mlp64.hip", "ppo_resmlp512.hip", "ppo_mlp64_kl.hip", "ppo_resmlp512_kl.hip",
                                                    "ppo_shuffle.hip",    # ppo_shuffle.hip: navppo_shuffle_batch (minibatch updates)
                                                    "ppo_reward_norm.hip",    # navppo_return_moments, navppo_reward_scale (norm_reward)
-                                                   "ppo_group_sums.hip")]    # navppo_group_sums (scenario_stats / scenario_priority)
+                                                   "ppo_group_sums.hip",    # navppo_group_sums (scenario_stats / scenario_priority)
+                                                   # the *_var twins (learn_var): the partner sources compiled a third time
+                                                   # (NAVPPO_VAR_TU), and the launch that steps log var
+                                                   "ppo_mlp64_var.hip", "ppo_resmlp512_var.hip", "ppo_learned_var.hip")]
 HDRS = ["navsim.h", "navppo.h"]
 INC = os.path.join(REPO, "include")
 # what every object depends on besides its own source: the public headers, the csrc headers and the two sources the *_kl twins include
@@ -51,11 +54,13 @@ def needs_build():
 # first it does neither.  (The other kernels of the file: same registers, no spills either way.)
 EXTRA_FLAGS = {"navsim.hip": ["-mllvm", "-disable-machine-licm"],
                "ppo_resmlp512.hip": ["-mllvm", "-greedy-regclass-priority-trumps-globalness=1"],
-               "ppo_resmlp512_kl.hip": ["-mllvm", "-greedy-regclass-priority-trumps-globalness=1"]}   # (resmlp_bwd2s_kl: the same stream)
+               "ppo_resmlp512_kl.hip": ["-mllvm", "-greedy-regclass-priority-trumps-globalness=1"],   # (resmlp_bwd2s_kl: the same stream)
+               "ppo_resmlp512_var.hip": ["-mllvm", "-greedy-regclass-priority-trumps-globalness=1"]}   # (resmlp_bwd2s_var likewise)
 # what a source is built with INSTEAD when hipcc rejects (or NAVSIM_NO_EXTRA_FLAGS=1 drops) its EXTRA_FLAGS: a flag that only buys speed
 # has no entry; resmlp_bwd2s without its allocation flag carries a hazard the compiler cannot see, so the file then launches the
 # compiler-scheduled resmlp_bwd<32, 2, 4> (same arithmetic, 4.3 instead of 3.2 ms per epoch)
-FALLBACK_FLAGS = {"ppo_resmlp512.hip": ["-DRESMLP_BWD2S=0"], "ppo_resmlp512_kl.hip": ["-DRESMLP_BWD2S=0"]}
+FALLBACK_FLAGS = {"ppo_resmlp512.hip": ["-DRESMLP_BWD2S=0"], "ppo_resmlp512_kl.hip": ["-DRESMLP_BWD2S=0"],
+                  "ppo_resmlp512_var.hip": ["-DRESMLP_BWD2S=0"]}
 
 _flag_ok = {}
 

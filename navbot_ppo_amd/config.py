@@ -29,6 +29,16 @@ class PPOConfig:
     var_decay: float = 0.995               # ppo.py:695
     var_floor: float = 0.1                 # ppo.py:694
     var_decay_after: int = 50000           # ppo.py:694
+    # False = the reference: the variance follows the fixed schedule above and the update cannot change it.  True: theta = log var is a
+    # parameter of the actor (the state-independent log-std of Stable-Baselines3 / rsl_rl / rl_games / CleanRL, one isotropic variance
+    # as in the reference), stepped by Adam after every optimiser step of the nets -- at their rate, scaled by the actor's clip
+    # coefficient -- on the gradient of actor_loss - ent_coef * entropy, clamped to [var_min, var_max]; it starts at init_var and the
+    # schedule is off.  On one GPU the step is taken on the device (navppo_*_update_epoch_var; host mirror: learned_var_reference) and
+    # every rollout reads the variance from the same device state.  Not with target_kl, overlap_allreduce or several ranks.
+    learn_var: bool = False
+    ent_coef: float = 0.0                  # learn_var: the entropy bonus' coefficient (0 = none)
+    var_min: float = 1e-3                  # learn_var: the clamps of the variance
+    var_max: float = 1.0
     save_freq: int = 2                     # ppo.py:774
     seed: int = 0
     use_graph: bool = True                 # capture the T-step rollout in one hipGraph
@@ -128,6 +138,34 @@ class PPOConfig:
         check_scan_history_config(self)
         check_continue_config(self)
         check_scenario_config(self)
+        check_learn_var_config(self)
+
+
+def check_learn_var_config(cfg, world=1):
+    """PPOConfig.learn_var / ent_coef / var_min / var_max, at the construction of the config and again of the updater and the trainer
+    (a config is mutable).  world: the number of ranks (the updater and the trainer know it)."""
+    if not isinstance(cfg.learn_var, bool):
+        raise ValueError(f"learn_var {cfg.learn_var!r}: True or False")
+    num = lambda v: not isinstance(v, bool) and isinstance(v, (int, float)) and math.isfinite(v)
+    e, lo, hi = cfg.ent_coef, cfg.var_min, cfg.var_max
+    if not num(e) or e < 0:
+        raise ValueError(f"ent_coef {e!r}: a finite number >= 0")
+    if not num(lo) or not lo > 0:
+        raise ValueError(f"var_min {lo!r}: a finite number > 0")
+    if not num(hi) or hi < lo:
+        raise ValueError(f"var_max {hi!r}: a finite number >= var_min = {lo!r}")
+    if not cfg.learn_var:
+        if e != 0:
+            raise ValueError(f"ent_coef {e!r} without learn_var: a fixed variance has no gradient for the entropy bonus to act on")
+        return
+    if not num(cfg.init_var) or not lo <= cfg.init_var <= hi:
+        raise ValueError(f"init_var {cfg.init_var!r} outside [var_min, var_max] = [{lo!r}, {hi!r}]")
+    if cfg.target_kl is not None:
+        raise ValueError("learn_var with target_kl: the gated kernels are not combined with the learned variance's")
+    if cfg.overlap_allreduce:
+        raise ValueError("learn_var with overlap_allreduce=True: the per-net pipeline has no place for the variance's step")
+    if world > 1:
+        raise ValueError(f"learn_var on {world} ranks: the multi-GPU form is not built (one rank only)")
 
 
 def check_scenario_config(cfg):

@@ -51,7 +51,24 @@ struct NavppoStep {
     float kl_limit; float* kl_state;     // kClipKl
     float kl_target, lr_min, lr_max;     // kClipLr: the desired KL and the clamps of the learning rate
     int32_t adapt; float* lr_state;      // kClipLr: 0 = keep the rate, 1 = apply the rule; [4] (two rate slots, raises, lowerings)
+    float* var_state;                    // the *_var entry points (kClip / kClipLr of their translation units): [8], see NavppoVar
 };
+
+// the *_var entry points' own arguments (include/navppo.h "Learned exploration variance"): the entropy coefficient, the clamps of the
+// variance and the state -- (theta, var, m, v, gradient, steps taken, steps skipped, entropy)
+struct NavppoVar {
+    float ent_coef, var_min, var_max;
+    float* state;
+    bool ok() const {   // (a NaN fails each comparison)
+        return ent_coef >= 0.f && std::isfinite(ent_coef) && var_min > 0.f && var_max >= var_min && std::isfinite(var_max) && state &&
+               ((uintptr_t)state & 15) == 0;
+    }
+};
+inline int navppo_check_var(const char* who, const NavppoVar& v) {
+    return v.ok() ? 0
+                  : navppo_bad_args(who, "ent_coef >= 0 and finite, 0 < var_min <= var_max, both finite, and var_state_dev [8] not null, "
+                                         "16-byte aligned");
+}
 
 // max_norm of the *_clipped entry points, kl_limit of the *_kl entry points: a positive number, +inf included (NaN fails)
 inline bool navppo_max_norm_ok(float max_norm) { return max_norm > 0.f; }
@@ -130,8 +147,29 @@ __device__ __forceinline__ bool navppo_kl_stopped(const float* __restrict__ kl_s
 // (Twins in the SAME translation unit changed the ungated kernels' listings: a helper that is not force-inlined then has two callers
 // and the inliner decides differently -- mlp64_pass_both_x3s went from 491 to 486 registers, mlp64_pass_both_x3<16> from 268 to 192
 // bytes of scratch -- and a hand-placed stream's listing is exactly what tests/test_isa_*.py pin: profiles/kl_gate_resources.txt.)
-#ifdef NAVPPO_KL_TU
-constexpr bool kNavppoKlTu = true;
+//
+// A THIRD compilation of the same text gives the twins of the *_var entry points (ppo_mlp64_var.hip / ppo_resmlp512_var.hip define
+// NAVPPO_VAR_TU, and NAVPPO_KL_TU with it so that the same code is compiled out): every kernel is then `name_var` and takes var_state
+// as its last argument; there is no gate; the kernels that hold a loss block start with NAVPPO_VAR_READ(var) -- var = var_state[1], the
+// by-value argument is ignored -- and, under `if constexpr (kNavppoVarTu)`, add the per-sample term of d/d(log var) into one more
+// per-lane sum that leaves through the workgroup's statistics row (column 3).  The modes of those units are kClip and kClipLr.
+#if defined(NAVPPO_VAR_TU)
+#ifndef NAVPPO_KL_TU
+#error "NAVPPO_VAR_TU is defined together with NAVPPO_KL_TU (the twins' translation units compile the same code out)"
+#endif
+constexpr bool kNavppoKlTu = false, kNavppoVarTu = true;
+#define NAVPPO_KL_KERNEL(name) name##_var
+#define NAVPPO_KL_PARAM , const float* __restrict__ var_state
+#define NAVPPO_KL_ARG(var_state) , (const float*)(var_state)
+#define NAVPPO_KL_GATE() \
+    do {                 \
+    } while (0)
+#define NAVPPO_VAR_READ(var) \
+    do {                     \
+        var = var_state[1];  \
+    } while (0)
+#elif defined(NAVPPO_KL_TU)
+constexpr bool kNavppoKlTu = true, kNavppoVarTu = false;
 #define NAVPPO_KL_KERNEL(name) name##_kl
 #define NAVPPO_KL_PARAM , const float* __restrict__ kl_state
 #define NAVPPO_KL_ARG(kl_state) , (const float*)(kl_state)
@@ -139,12 +177,33 @@ constexpr bool kNavppoKlTu = true;
     do {                 \
         if (navppo_kl_stopped(kl_state)) return; \
     } while (0)
+#define NAVPPO_VAR_READ(var) \
+    do {                     \
+    } while (0)
 #else
-constexpr bool kNavppoKlTu = false;
+constexpr bool kNavppoKlTu = false, kNavppoVarTu = false;
 #define NAVPPO_KL_KERNEL(name) name
 #define NAVPPO_KL_PARAM
 #define NAVPPO_KL_ARG(kl_state)
 #define NAVPPO_KL_GATE() \
     do {                 \
     } while (0)
+#define NAVPPO_VAR_READ(var) \
+    do {                     \
+    } while (0)
 #endif
+
+// the state pointer the twins' launches pass behind the last argument: kl_state (the gated twins) or var_state (the *_var twins)
+inline const float* navppo_twin_state(const NavppoStep& s) { return kNavppoVarTu ? s.var_state : s.kl_state; }
+
+// the per-sample term of d(actor loss)/d(log var), the log-probability being -1/2 (d0^2 + d1^2) / var - log 2 pi - log var:
+// dL_dlp (1/2 (d0^2 + d1^2) / var - 1), the quotient written as the loss blocks write it
+__device__ __forceinline__ float navppo_dlogvar_term(float dL_dlp, float d0, float d1, float var) {
+    return dL_dlp * (0.5f * ((d0 * d0 + d1 * d1) / var) - 1.0f);
+}
+
+// The launch behind a *_var epoch's step launch (var_step_kernel, ppo_learned_var.hip): ONE workgroup adds column 0 of `n_rows` rows of
+// pitch `row_pitch` at `col` (the workgroups' sums of the term above) in one fixed order, writes the sum to *sum_out, and steps
+// log var with Adam (include/navppo.h has the rule).  lr_state: NULL, or the *_lr state whose slot (step + 1) & 1 the step launch wrote.
+void navppo_launch_var_step(const float* col, int n_rows, int row_pitch, const NavppoStep& s, const NavppoVar& v, float* sum_out,
+                            void* stream);

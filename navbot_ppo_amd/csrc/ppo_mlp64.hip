@@ -249,6 +249,8 @@ __device__ __forceinline__ void pass_body(SmemW<IN>& sm, const float* __restrict
         for (int c = 0; c < NC; ++c) aW1[u][c] = f32x4{0.f, 0.f, 0.f, 0.f};
     float adb2[2] = {0.f, 0.f}, adw3[2] = {0.f, 0.f}, adw4[2] = {0.f, 0.f}, adb1[4] = {0.f, 0.f, 0.f, 0.f};
     float adb3 = 0.f, adb4 = 0.f, st0 = 0.f, st1 = 0.f, st2 = 0.f, st3 = 0.f;
+    float stv = 0.f;   // (the *_var twins: the sum of navppo_dlogvar_term, column 3 of the workgroup's statistics row)
+    (void)stv;
 
     const long long n_tiles = (M + 31) / 32;
     const long long gw = (long long)blockIdx.x * NW + wave, stride = (long long)gridDim.x * NW;
@@ -403,6 +405,7 @@ __device__ __forceinline__ void pass_body(SmemW<IN>& sm, const float* __restrict
                     const bool inside = (ratio >= 1.0f - clip) && (ratio <= 1.0f + clip);
                     const float dL_dratio = (inside || s1 < s2) ? -A : 0.f;
                     const float dL_dlp = dL_dratio * ratio * inv_n;
+                    if constexpr (kNavppoVarTu) stv += own * navppo_dlogvar_term(dL_dlp, d0, d1, var);
                     g3 = dL_dlp * (d0 / var) * (mu0 * (1.0f - mu0));
                     g4 = dL_dlp * (d1 / var) * (1.0f - mu1 * mu1);
                 } else {
@@ -597,6 +600,13 @@ __device__ __forceinline__ void pass_body(SmemW<IN>& sm, const float* __restrict
         s3 += __shfl_xor(s3, o, 64); s4 += __shfl_xor(s4, o, 64);
         sA += __shfl_xor(sA, o, 64); sB += __shfl_xor(sB, o, 64); sC += __shfl_xor(sC, o, 64);
     }
+    constexpr int kStatCols = (kNavppoVarTu && ACTOR) ? 4 : 3;   // (RP has room for the actor's fourth column, not for the critic's)
+    static_assert(P + kStatCols <= RP, "the statistics fit the row");
+    float sV = stv;
+    if constexpr (kStatCols == 4) {
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) sV += __shfl_xor(sV, o, 64);
+    }
     float hb2[2], hw3[2], hw4[2], qb1[4];
 #pragma unroll
     for (int t2 = 0; t2 < 2; ++t2) {
@@ -644,6 +654,7 @@ __device__ __forceinline__ void pass_body(SmemW<IN>& sm, const float* __restrict
                 put(P + 0, sA);
                 put(P + 1, sB);
                 put(P + 2, sC);
+                if constexpr (kStatCols == 4) put(P + 3, sV);
             }
         }
         __syncthreads();
@@ -651,7 +662,7 @@ __device__ __forceinline__ void pass_body(SmemW<IN>& sm, const float* __restrict
     float* out = partial + (size_t)blockIdx.x * P;
     const float* red = red_base;
     for (int k = tid; k < P; k += NT) out[k] = (red[k] + red[RP + k]) + (red[2 * RP + k] + red[3 * RP + k]);
-    if (tid < 3) stats_partial[blockIdx.x * 4 + tid] = (red[P + tid] + red[RP + P + tid]) + (red[2 * RP + P + tid] + red[3 * RP + P + tid]);
+    if (tid < kStatCols) stats_partial[blockIdx.x * 4 + tid] = (red[P + tid] + red[RP + P + tid]) + (red[2 * RP + P + tid] + red[3 * RP + P + tid]);
 }
 
 template <bool ACTOR, bool FWD, int IN, bool F16>
@@ -678,6 +689,7 @@ __global__ __launch_bounds__(64 * Pad<IN>::NW) void NAVPPO_KL_KERNEL(mlp64_pass_
                                                              float* __restrict__ grad, float* __restrict__ stats NAVPPO_KL_PARAM) {
     __shared__ __attribute__((aligned(16))) SmemW<IN> sm;
     NAVPPO_KL_GATE();
+    NAVPPO_VAR_READ(var);
     pass_body<true, false, IN, F16>(sm, params, obs, act, logp_old, rtg, adv, M, var, clip, inv_n, partial_a, stats_partial_a, grad,
                                     stats);
     __syncthreads();
@@ -915,6 +927,8 @@ __device__ __forceinline__ void pass_body_x3(SmemX<IN>& sm, const float* __restr
         for (int u = 0; u < 4; ++u) aW1[c][u] = f32x4{0.f, 0.f, 0.f, 0.f};
     float adb2[2] = {0.f, 0.f}, adw3[2] = {0.f, 0.f}, adw4[2] = {0.f, 0.f}, adb1[4] = {0.f, 0.f, 0.f, 0.f};
     float adb3 = 0.f, adb4 = 0.f, st0 = 0.f, st1 = 0.f, st2 = 0.f, st3 = 0.f;
+    float stv = 0.f;   // (the *_var twins: the sum of navppo_dlogvar_term, column 3 of the workgroup's statistics row)
+    (void)stv;
 
     const long long n_tiles = (M + 31) / 32;
     const long long gw = (long long)blockIdx.x * kXWaves + wave, stride = (long long)gridDim.x * kXWaves;
@@ -1057,6 +1071,7 @@ __device__ __forceinline__ void pass_body_x3(SmemX<IN>& sm, const float* __restr
                     const bool inside = (ratio >= 1.0f - clip) && (ratio <= 1.0f + clip);
                     const float dL_dratio = (inside || s1 < s2) ? -A : 0.f;
                     const float dL_dlp = dL_dratio * ratio * inv_n;
+                    if constexpr (kNavppoVarTu) stv += own * navppo_dlogvar_term(dL_dlp, d0, d1, var);
                     g3 = dL_dlp * (d0 / var) * (mu0 * (1.0f - mu0));
                     g4 = dL_dlp * (d1 / var) * (1.0f - mu1 * mu1);
                 } else {
@@ -1204,6 +1219,13 @@ __device__ __forceinline__ void pass_body_x3(SmemX<IN>& sm, const float* __restr
         s3 += __shfl_xor(s3, o, 64); s4 += __shfl_xor(s4, o, 64);
         sA += __shfl_xor(sA, o, 64); sB += __shfl_xor(sB, o, 64); sC += __shfl_xor(sC, o, 64);
     }
+    constexpr int kStatCols = (kNavppoVarTu && ACTOR) ? 4 : 3;   // (RP has room for the actor's fourth column, not for the critic's)
+    static_assert(P + kStatCols <= RP, "the statistics fit the row");
+    float sV = stv;
+    if constexpr (kStatCols == 4) {
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) sV += __shfl_xor(sV, o, 64);
+    }
     float hb2[2], hw3[2], hw4[2], qb1[4];
 #pragma unroll
     for (int t2 = 0; t2 < 2; ++t2) {
@@ -1252,6 +1274,7 @@ __device__ __forceinline__ void pass_body_x3(SmemX<IN>& sm, const float* __restr
                 put(P + 0, sA);
                 put(P + 1, sB);
                 put(P + 2, sC);
+                if constexpr (kStatCols == 4) put(P + 3, sV);
             }
         }
         __syncthreads();
@@ -1259,7 +1282,7 @@ __device__ __forceinline__ void pass_body_x3(SmemX<IN>& sm, const float* __restr
     float* out = partial + (size_t)blockIdx.x * P;
     const float* red = red0;
     for (int k = tid; k < P; k += NT) out[k] = (red[k] + red[RP + k]) + (red[2 * RP + k] + red[3 * RP + k]);
-    if (tid < 3) stats_partial[blockIdx.x * 4 + tid] = (red[P + tid] + red[RP + P + tid]) + (red[2 * RP + P + tid] + red[3 * RP + P + tid]);
+    if (tid < kStatCols) stats_partial[blockIdx.x * 4 + tid] = (red[P + tid] + red[RP + P + tid]) + (red[2 * RP + P + tid] + red[3 * RP + P + tid]);
 }
 
 // both nets of one epoch in one launch; net_mask: bit 0 = actor, bit 1 = critic (the one-net launches of the multi-GPU pipeline)
@@ -1272,6 +1295,7 @@ __global__ __launch_bounds__(64 * XPad<IN>::NW) void NAVPPO_KL_KERNEL(mlp64_pass
                                                                 float* __restrict__ partial_c, float* __restrict__ stats_partial_c NAVPPO_KL_PARAM) {
     __shared__ __attribute__((aligned(16))) SmemX<IN> sm;
     NAVPPO_KL_GATE();
+    NAVPPO_VAR_READ(var);
     if (net_mask & 1) pass_body_x3<true, IN>(sm, params, prep, act, logp_old, rtg, adv, M, var, clip, inv_n, partial_a, stats_partial_a);
     if (net_mask == 3) __syncthreads();
     if (net_mask & 2) pass_body_x3<false, IN>(sm, params + Layout<IN>::P_ACTOR, prep, act, logp_old, rtg, adv, M, var, clip, inv_n, partial_c, stats_partial_c);
@@ -1741,8 +1765,12 @@ struct Mlp64Rows {
 // net_mask 3: both nets; 1 / 2 (kGrad only): the actor's / the critic's pass and its slice of the reduction.
 template <NavppoMode MODE>
 int mlp64_epoch(const char* who, float* params, const Mlp64Rows& x, const NavppoBatch& b, int net_mask, const NavppoStep& s, float* grad,
-                float* stats, void* workspace, void* stream) {
+                float* stats, void* workspace, void* stream, const NavppoVar* lv = nullptr) {
     static_assert((MODE == NavppoMode::kClipKl) == kNavppoKlTu, "the gated mode is the twins' translation unit's, the others are not");
+    static_assert(!kNavppoVarTu || MODE == NavppoMode::kClip || MODE == NavppoMode::kClipLr, "the *_var twins' unit: the clipped modes");
+    if constexpr (kNavppoVarTu) {   // (lv: the *_var entry points' arguments, checked in front of everything else -- nothing is launched)
+        if (const int rc = navppo_check_var(who, *lv)) return rc;
+    }
     if (net_mask < 1 || net_mask > 3 || (MODE != NavppoMode::kGrad && net_mask != 3)) return navppo_bad_args(who, "net is 0 (actor) or 1 (critic)");
     if (!params || !x.data || !b.ok() || !grad || !stats || !workspace || (x.dim != 16 && x.dim != 42))
         return navppo_bad_args(who, "bad argument (obs_dim is 16 or 42)");
@@ -1757,7 +1785,7 @@ int mlp64_epoch(const char* who, float* params, const Mlp64Rows& x, const Navppo
         const unsigned char* const prep = reinterpret_cast<const unsigned char*>(x.data);
         auto pass = [&](auto kernel, int waves) {
             hipLaunchKernelGGL(kernel, dim3(pl.blocks), dim3(64 * waves), 0, st, w, prep, b.act, b.logp_old, b.rtg, b.adv, n, b.var, b.clip, pl.inv_n,
-                               net_mask, pl.partial, pl.stats_partial, pl.partial_c, pl.stats_partial_c NAVPPO_KL_ARG(s.kl_state));
+                               net_mask, pl.partial, pl.stats_partial, pl.partial_c, pl.stats_partial_c NAVPPO_KL_ARG(navppo_twin_state(s)));
         };
         if (x.dim == 16 && X3_SCHED) pass(NAVPPO_KL_KERNEL(mlp64_pass_both_x3s), x3s::SW);
         else if (x.dim == 16) pass(NAVPPO_KL_KERNEL(mlp64_pass_both_x3)<16>, XPad<16>::NW);
@@ -1769,7 +1797,7 @@ int mlp64_epoch(const char* who, float* params, const Mlp64Rows& x, const Navppo
             const dim3 grid(pl.blocks), block(64 * Pad<IN>::NW);
             if (net_mask == 3)
                 hipLaunchKernelGGL((NAVPPO_KL_KERNEL(mlp64_pass_both)<IN, F16>), grid, block, 0, st, w, x.data, b.act, b.logp_old, b.rtg, b.adv, n, b.var,
-                                   b.clip, pl.inv_n, pl.partial, pl.stats_partial, pl.partial_c, pl.stats_partial_c, grad, stats NAVPPO_KL_ARG(s.kl_state));
+                                   b.clip, pl.inv_n, pl.partial, pl.stats_partial, pl.partial_c, pl.stats_partial_c, grad, stats NAVPPO_KL_ARG(navppo_twin_state(s)));
             else if constexpr (MODE == NavppoMode::kGrad) {
                 if (net_mask == 1)
                     hipLaunchKernelGGL((mlp64_pass_w<true, false, IN, F16>), grid, block, 0, st, w, x.data, b.act, b.logp_old, b.rtg, b.adv, n, b.var,
@@ -1791,10 +1819,12 @@ int mlp64_epoch(const char* who, float* params, const Mlp64Rows& x, const Navppo
     const int parity = kClip ? 0 : (kAdam && net_mask == 3) ? (int)(s.step & 1) : -1;
     hipLaunchKernelGGL((NAVPPO_KL_KERNEL(reduce_adam)<kAdam>), dim3(rblocks), dim3(64 * kRedGroups), 0, st, pl.partial, pl.stats_partial, pl.partial_c,
                        pl.stats_partial_c, pl.blocks, pl.inv_n, grad, stats, kAdam ? params : nullptr, r.m, r.v, r.lr, r.beta1, r.beta2, r.eps, bc.bc1,
-                       bc.bc2_sqrt, pl.pa, pl.pc, q0, q1, parity >= 0 ? pl.gn : nullptr, parity NAVPPO_KL_ARG(s.kl_state));
+                       bc.bc2_sqrt, pl.pa, pl.pc, q0, q1, parity >= 0 ? pl.gn : nullptr, parity NAVPPO_KL_ARG(navppo_twin_state(s)));
     if constexpr (kClip)
         navppo_launch_clip_adam(params, grad, pl.pa + pl.pc, pl.pa, 1.0f, s, pl.gn, rblocks, kGnSlots, 8, stream,
                                 MODE == NavppoMode::kClipKl || kLr ? stats + 1 : nullptr, kLr);
+    // the *_var epochs: column 3 of the actor's statistics rows -> stats[3], and the step of log var behind the nets' step
+    if constexpr (kNavppoVarTu) navppo_launch_var_step(pl.stats_partial + 3, pl.blocks, 4, s, *lv, stats + 3, stream);
     return navppo_launched(who);
 }
 

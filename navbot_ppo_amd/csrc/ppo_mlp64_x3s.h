@@ -291,6 +291,8 @@ __device__ __forceinline__ void pass_body(SmemS& sm, const float* __restrict__ p
 #pragma unroll
         for (int r = 0; r < 16; ++r) pb2[t][r] = pw3[t][r] = pw4[t][r] = zf;
     float adb3 = zf, adb4 = zf, st0 = zf, st1 = zf, st2 = zf, st3 = zf;
+    float stv = zf;   // (the *_var twin: the sum of navppo_dlogvar_term, column 3 of the workgroup's statistics row)
+    (void)stv;
     // (no instruction: a use of dW2's accumulators in the middle of the phases that do not touch them, so that the register allocator
     // does not park them elsewhere for those phases and fetch them back for G2 -- 96 copies per tile; dW1's likewise: moved aside over
     // F2 and back in front of G1, one copy right in front of its MFMA)
@@ -612,6 +614,7 @@ __device__ __forceinline__ void pass_body(SmemS& sm, const float* __restrict__ p
                     const bool inside = (ratio >= 1.0f - clip) && (ratio <= 1.0f + clip);
                     const float dL_dratio = (inside || s1 < s2) ? -A : 0.f;
                     const float dL_dlp = dL_dratio * ratio * inv_n;
+                    if constexpr (kNavppoVarTu) stv += own * navppo_dlogvar_term(dL_dlp, d0, d1, var);
                     g3 = dL_dlp * (d0 / var) * (mu0 * (1.0f - mu0));
                     g4 = dL_dlp * (d1 / var) * (1.0f - mu1 * mu1);
                 } else {
@@ -827,6 +830,13 @@ __device__ __forceinline__ void pass_body(SmemS& sm, const float* __restrict__ p
         s3 += __shfl_xor(s3, o, 64); s4 += __shfl_xor(s4, o, 64);
         sA += __shfl_xor(sA, o, 64); sB += __shfl_xor(sB, o, 64); sC += __shfl_xor(sC, o, 64);
     }
+    constexpr int kStatCols = (kNavppoVarTu && ACTOR) ? 4 : 3;   // (RP has room for the actor's fourth column, not for the critic's)
+    static_assert(P + kStatCols <= RP, "the statistics fit the row");
+    float sV = stv;
+    if constexpr (kStatCols == 4) {
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) sV += __shfl_xor(sV, o, 64);
+    }
     float* const red0 = reinterpret_cast<float*>(&sm.img[0][0][0]);
     float* const rowp = red0 + wave * RP;
     {
@@ -856,13 +866,14 @@ __device__ __forceinline__ void pass_body(SmemS& sm, const float* __restrict__ p
             put(P + 0, sA);
             put(P + 1, sB);
             put(P + 2, sC);
+            if constexpr (kStatCols == 4) put(P + 3, sV);
         }
     }
     __syncthreads();
     float* out = partial + (size_t)block * P;
     const float* red = red0;
     for (int k = tid; k < P; k += NT) out[k] = (red[k] + red[RP + k]) + (red[2 * RP + k] + red[3 * RP + k]);
-    if (tid < 3) stats_partial[block * 4 + tid] = (red[P + tid] + red[RP + P + tid]) + (red[2 * RP + P + tid] + red[3 * RP + P + tid]);
+    if (tid < kStatCols) stats_partial[block * 4 + tid] = (red[P + tid] + red[RP + P + tid]) + (red[2 * RP + P + tid] + red[3 * RP + P + tid]);
 }
 
 }  // namespace x3s
@@ -888,6 +899,7 @@ __global__ __launch_bounds__(64 * x3s::SW) void NAVPPO_KL_KERNEL(mlp64_pass_both
                                                                     float* __restrict__ partial_c, float* __restrict__ stats_partial_c NAVPPO_KL_PARAM) {
     __shared__ __attribute__((aligned(128))) x3s::SmemS sm;
     NAVPPO_KL_GATE();
+    NAVPPO_VAR_READ(var);
 #if X3S_PAIR
     // paired: both nets and whole pair groups only (single-net launches, small and odd grids keep the order below on their own block).
     // The critic's pass is always the partner's block: a workgroup with the pair bit clear runs actor(b), critic(b ^ X3S_PAIR), one with

@@ -914,8 +914,10 @@ __global__ __launch_bounds__(kEThreads) void NAVPPO_KL_KERNEL(resmlp_e2)(const f
                                                        const float* __restrict__ rtg, const float* __restrict__ adv, long long n,
                                                        float var, float clip, float inv_n, float* __restrict__ dy2,
                                                        float* __restrict__ epart, float* __restrict__ v_out, int obs_f16 NAVPPO_KL_PARAM) {
-    __shared__ float red[(kEThreads / 64) * 8 * 17];
+    constexpr int NV = kNavppoVarTu ? 18 : 17;   // (the *_var twin: one more sum, navppo_dlogvar_term, in column EC_STAT + 3)
+    __shared__ float red[(kEThreads / 64) * 8 * NV];
     NAVPPO_KL_GATE();
+    NAVPPO_VAR_READ(var);
     const int net_i = blockIdx.y, net = net_base + net_i;
     const bool actor = net == 0;
     const float* __restrict__ pn = params + (net ? rp::P_ACTOR : 0);
@@ -929,10 +931,10 @@ __global__ __launch_bounds__(kEThreads) void NAVPPO_KL_KERNEL(resmlp_e2)(const f
     const float bo1 = pn[rp::BO1], bo2 = actor ? pn[rp::BO2] : 0.f;
     const float* __restrict__ pp = p2 + (size_t)net_i * NSLF * n * 32;   // (obs / h1buf: no longer read here -- pair 0's partial carries them)
     float* __restrict__ dyo = HEAD_ONLY ? nullptr : dy2 + (size_t)net_i * n * 32;
-    // accumulators: db2b[4] dwo1[4] dwo2[4] dbo1 dbo2 st0 st1 st2   (17 values)
-    float acc[17];
+    // accumulators: db2b[4] dwo1[4] dwo2[4] dbo1 dbo2 st0 st1 st2   (17 values; the *_var twin: + the sum of the d/d(log var) terms)
+    float acc[NV];
 #pragma unroll
-    for (int v = 0; v < 17; ++v) acc[v] = 0.f;
+    for (int v = 0; v < NV; ++v) acc[v] = 0.f;
     const long long total = n * 8, step = (long long)gridDim.x * kEThreads;
     for (long long g = (long long)blockIdx.x * kEThreads + threadIdx.x; g < total; g += step) {
         const long long s = g >> 3, o = g * 4;   // o == s * 32 + 4 * og
@@ -982,6 +984,7 @@ __global__ __launch_bounds__(kEThreads) void NAVPPO_KL_KERNEL(resmlp_e2)(const f
             const bool inside = (ratio >= 1.0f - clip) && (ratio <= 1.0f + clip);
             const float dL_dratio = (inside || s1 < s2) ? -A : 0.f;
             const float dL_dlp = dL_dratio * ratio * inv_n;
+            if constexpr (kNavppoVarTu) acc[NV - 1] += own * navppo_dlogvar_term(dL_dlp, d0, d1, var);
             g3 = dL_dlp * (d0 / var) * (mu0 * (1.0f - mu0));
             g4 = dL_dlp * (d1 / var) * (1.0f - mu1 * mu1);
         } else {
@@ -1003,9 +1006,9 @@ __global__ __launch_bounds__(kEThreads) void NAVPPO_KL_KERNEL(resmlp_e2)(const f
     }
     if (HEAD_ONLY) return;
     // value v of unit group og -> column cols[v] + og * strides[v]
-    __shared__ int cols[17], strides[17];
-    __shared__ bool og0[17];
-    if (threadIdx.x < 17) {
+    __shared__ int cols[NV], strides[NV];
+    __shared__ bool og0[NV];
+    if (threadIdx.x < NV) {
         const int v = threadIdx.x;
         const int c = v < 4 ? EC_B2B + v : v < 8 ? EC_WO1 + (v - 4) : v < 12 ? EC_WO2 + (v - 8)
                       : v == 12 ? EC_BO1 : v == 13 ? EC_BO2 : EC_STAT + (v - 14);
@@ -1014,7 +1017,7 @@ __global__ __launch_bounds__(kEThreads) void NAVPPO_KL_KERNEL(resmlp_e2)(const f
         og0[v] = v >= 12;
     }
     __syncthreads();
-    block_sum_to_row<8, 17>(acc, red, epart + ((size_t)net_i * gridDim.x + blockIdx.x) * EP, cols, strides, og0);
+    block_sum_to_row<8, NV>(acc, red, epart + ((size_t)net_i * gridDim.x + blockIdx.x) * EP, cols, strides, og0);
 }
 
 // ---------------------------------------------------------------- partial rows -> gradient (-> Adam)
@@ -1183,8 +1186,12 @@ void launch_forward(const Plan& p, const float* params, int net_base, int n_nets
 // compiled in ppo_resmlp512_kl.hip, every kernel its twin -- navppo_internal.h)
 template <NavppoMode MODE>
 int loss_grad_impl(const char* name, float* params, const void* obs, int32_t obs_f16, const NavppoBatch& b, const NavppoStep& s, float* grad,
-                   float* stats, void* ws, void* stream) {
+                   float* stats, void* ws, void* stream, const NavppoVar* lv = nullptr) {
     static_assert((MODE == NavppoMode::kClipKl) == kNavppoKlTu, "the gated mode is the twins' translation unit's, the others are not");
+    static_assert(!kNavppoVarTu || MODE == NavppoMode::kClip || MODE == NavppoMode::kClipLr, "the *_var twins' unit: the clipped modes");
+    if constexpr (kNavppoVarTu) {   // (lv: the *_var entry point's arguments, checked in front of everything else -- nothing is launched)
+        if (const int rc = navppo_check_var(name, *lv)) return rc;
+    }
     if (!params || !obs || !b.ok() || !grad || !stats || !ws) return navppo_bad_args(name, "bad argument");
     if (((uintptr_t)obs & 15) || ((uintptr_t)b.act & 7)) return navppo_bad_args(name, "obs must be 16-byte and act 8-byte aligned");
     if (const int rc = navppo_check_step(name, MODE, s)) return rc;
@@ -1194,21 +1201,21 @@ int loss_grad_impl(const char* name, float* params, const void* obs, int32_t obs
     const int f16 = obs_f16 != 0;
     const long long n = b.n;
     const float *const w = params, *const h1 = p.h1, *const dy2 = p.dy2;
-    launch_forward(p, w, 0, 2, obs, f16, n, st, s.kl_state);
+    launch_forward(p, w, 0, 2, obs, f16, n, st, navppo_twin_state(s));
     hipLaunchKernelGGL(NAVPPO_KL_KERNEL(resmlp_e2)<false>, dim3(p.e_blocks, 2), dim3(kEThreads), 0, st, w, 0, obs, h1, (const float*)p.p2, b.act,
-                       b.logp_old, b.rtg, b.adv, n, b.var, b.clip, inv_n, p.dy2, p.epart, (float*)nullptr, f16 NAVPPO_KL_ARG(s.kl_state));
+                       b.logp_old, b.rtg, b.adv, n, b.var, b.clip, inv_n, p.dy2, p.epart, (float*)nullptr, f16 NAVPPO_KL_ARG(navppo_twin_state(s)));
     if constexpr (RESMLP_BWD2S && kBwd2Waves == b2s::SW) {
         if (f16)
             hipLaunchKernelGGL(NAVPPO_KL_KERNEL(resmlp_bwd2s)<true>, dim3(p.wgs), dim3(64 * b2s::SW), 0, st, w, 2, obs, h1, dy2, n, p.groups, p.wpart,
-                               p.qb NAVPPO_KL_ARG(s.kl_state));
+                               p.qb NAVPPO_KL_ARG(navppo_twin_state(s)));
         else
             hipLaunchKernelGGL(NAVPPO_KL_KERNEL(resmlp_bwd2s)<false>, dim3(p.wgs), dim3(64 * b2s::SW), 0, st, w, 2, obs, h1, dy2, n, p.groups, p.wpart,
-                               p.qb NAVPPO_KL_ARG(s.kl_state));
+                               p.qb NAVPPO_KL_ARG(navppo_twin_state(s)));
     } else
         hipLaunchKernelGGL((NAVPPO_KL_KERNEL(resmlp_bwd)<32, 2, kBwd2Waves>), dim3(p.wgs), dim3(64 * kBwd2Waves), 0, st, w, 2, obs, h1, dy2, n, p.groups,
-                           p.wpart, p.qb, (const float*)nullptr, f16 NAVPPO_KL_ARG(s.kl_state));
+                           p.wpart, p.qb, (const float*)nullptr, f16 NAVPPO_KL_ARG(navppo_twin_state(s)));
     hipLaunchKernelGGL((NAVPPO_KL_KERNEL(resmlp_bwd)<16, 2, kBwd1Waves>), dim3(p.wgs), dim3(64 * kBwd1Waves), 0, st, w, 2, obs, h1, dy2, n, p.groups,
-                       p.wpart, (float*)nullptr, (const float*)p.qb, f16 NAVPPO_KL_ARG(s.kl_state));
+                       p.wpart, (float*)nullptr, (const float*)p.qb, f16 NAVPPO_KL_ARG(navppo_twin_state(s)));
     // the reduction.  kAdam: Adam in the same launch, its blocks' squared-norm slots in parity step & 1 for the logged means.
     // kClip / kClipKl / kClipLr: the reduction alone, the slots in parity 0; then the norms, the KL decision (kClipKl) or the learning
     // rate (kClipLr) from stats[1], the clip and Adam
@@ -1220,10 +1227,12 @@ int loss_grad_impl(const char* name, float* params, const void* obs, int32_t obs
     const int parity = kClip ? 0 : kAdam ? (int)(s.step & 1) : -1;
     hipLaunchKernelGGL(NAVPPO_KL_KERNEL(resmlp_reduce)<kAdam>, dim3(rblocks), dim3(64 * kRedGroups), 0, st, (const float*)p.wpart, p.groups * kBwd1Waves,
                        p.groups * kBwd2Waves, (const float*)p.epart, p.e_blocks, inv_n, grad, stats, kAdam ? params : nullptr, r.m, r.v, r.lr, r.beta1,
-                       r.beta2, r.eps, bc.bc1, bc.bc2_sqrt, parity >= 0 ? p.epart : nullptr, parity NAVPPO_KL_ARG(s.kl_state));
+                       r.beta2, r.eps, bc.bc1, bc.bc2_sqrt, parity >= 0 ? p.epart : nullptr, parity NAVPPO_KL_ARG(navppo_twin_state(s)));
     if constexpr (kClip)
         navppo_launch_clip_adam(params, grad, rp::P_ACTOR + rp::P_CRITIC, rp::P_ACTOR, 1.0f, s, p.epart, rblocks, kGnSlotsR, EP, stream,
                                 MODE == NavppoMode::kClipKl || kLr ? stats + 1 : nullptr, kLr);
+    // the *_var epoch: column EC_STAT + 3 of the actor's streaming rows -> stats[3], and the step of log var behind the nets' step
+    if constexpr (kNavppoVarTu) navppo_launch_var_step(p.epart + EC_STAT + 3, p.e_blocks, EP, s, *lv, stats + 3, stream);
     return navppo_launched(name);
 }
 

@@ -16,7 +16,8 @@ stepping loop), --eval_every K (training: a persistent evaluation of --eval_epis
 exceeds 1.5 x the target), --minibatch_size M / --minibatch_shuffle MODE (K = ceil(batch / M) optimiser steps per epoch on slices of the
 batch, shuffled on the device), --norm_reward / --clip_reward C (rewards scaled by the running standard deviation of the discounted
 return and clipped to +-C before the return scan), --lr_schedule adaptive|linear with --desired_kl / --lr_min / --lr_max (the KL-adaptive
-step size decided on the device after every optimiser step, or a linear decay over --max_timesteps), --bootstrap_truncated (time-outs
+step size decided on the device after every optimiser step, or a linear decay over --max_timesteps), --learn_var with --ent_coef /
+--var_min / --var_max (the exploration variance learned by the update, with an entropy bonus, stepped on the device), --bootstrap_truncated (time-outs
 bootstrap with gamma V of their own row and the batch end with V of the next observation instead of counting as terminal), --movers NAME / --movers_period P (moving obstacles beside the static map, training and evaluation; NAME random:K with --movers_seed or bank:a,b,... is a bank of scenarios, one per env), --eval_movers NAME / --eval_movers_seed (held-out scenarios for --eval_every), --scan_history (the mlp64x2 policy reads the last three
 scans), --continue_rollouts (only the first rollout resets the envs; later ones go on where the last stopped), --scenario_stats /
 --scenario_priority failure|abs_adv with --scenario_resample_every / --scenario_score_alpha / --scenario_temperature /
@@ -81,6 +82,13 @@ def get_args(argv=None):
     p.add_argument("--desired_kl", type=float, default=0.01, help="with --lr_schedule adaptive: the KL per optimiser step the rule steers towards")
     p.add_argument("--lr_min", type=float, default=1e-5, help="with --lr_schedule adaptive: the lower clamp of the learning rate")
     p.add_argument("--lr_max", type=float, default=1e-2, help="with --lr_schedule adaptive: the upper clamp of the learning rate")
+    p.add_argument("--learn_var", action="store_true", default=False,
+                   help="the exploration variance is a parameter of the actor (one isotropic log-variance, as Stable-Baselines3's "
+                        "log_std), stepped on the device after every optimiser step, instead of the reference's fixed decay schedule; "
+                        "not with --target_kl; one GPU only; default: off")
+    p.add_argument("--ent_coef", type=float, default=0.0, help="with --learn_var: the coefficient of the entropy bonus in the actor's loss")
+    p.add_argument("--var_min", type=float, default=1e-3, help="with --learn_var: the lower clamp of the variance")
+    p.add_argument("--var_max", type=float, default=1.0, help="with --learn_var: the upper clamp of the variance")
     p.add_argument("--bootstrap_truncated", action="store_true", default=False,
                    help="partial-episode bootstrapping: an episode cut by --timesteps_per_episode adds gamma V of its last stored "
                         "observation (rsl_rl's rule) and the envs still running at the batch end bootstrap with V of the next one, for "
@@ -147,6 +155,7 @@ def config_of(args, rollout):
                          target_kl=args.target_kl, minibatch_size=args.minibatch_size, minibatch_shuffle=args.minibatch_shuffle,
                          norm_reward=args.norm_reward, clip_reward=args.clip_reward, lr_schedule=args.lr_schedule,
                          desired_kl=args.desired_kl, lr_min=args.lr_min, lr_max=args.lr_max,
+                         learn_var=args.learn_var, ent_coef=args.ent_coef, var_min=args.var_min, var_max=args.var_max,
                          bootstrap_truncated=args.bootstrap_truncated, scan_history=args.scan_history,
                          continue_rollouts=args.continue_rollouts, scenario_stats=args.scenario_stats,
                          scenario_priority=args.scenario_priority, scenario_resample_every=args.scenario_resample_every,

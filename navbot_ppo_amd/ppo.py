@@ -20,6 +20,9 @@ Follows ``project_ppo/src/ppo.py`` of the reference function by function, vector
                                     PPOConfig.lr_schedule: "adaptive" = the learning rate follows every step's approx_kl, decided
                                     on the device (navppo_*_update_epoch_lr; host mirror: adaptive_lr_reference); "linear" = decay
                                     over learn()'s budget, set per iteration
+                                    PPOConfig.learn_var: log var is a parameter of the actor, stepped on the device after every
+                                    optimiser step, with an entropy bonus ent_coef (navppo_*_update_epoch_var; host mirror:
+                                    learned_var_reference); the fixed decay schedule is off
                                     PPOConfig.scenario_stats / scenario_priority: on a bank of mover tapes the rollout is summed per
                                     scenario on the device (navppo_group_sums; host mirror: group_sums_reference) and the envs are
                                     re-assigned to the scenarios by rank-prioritised level replay (scenarios.ScenarioSampler)
@@ -40,9 +43,10 @@ lr_schedule.py, the per-scenario sums, the scenario sampler and the scenario tab
 import torch.distributed as dist  # noqa: F401
 
 from .config import (LR_SCHEDULES, MINIBATCH_SHUFFLES, SCENARIO_PRIORITIES, PPOConfig, check_bootstrap_config,  # noqa: F401
-                     check_continue_config, check_lr_schedule_config, check_minibatch_config, check_reward_norm_config,
-                     check_scan_history_config, check_scenario_config, check_update_config)
+                     check_continue_config, check_learn_var_config, check_lr_schedule_config, check_minibatch_config,
+                     check_reward_norm_config, check_scan_history_config, check_scenario_config, check_update_config)
 from .distributed import DistCtx, SingleProcessCtx, as_ctx, global_mean  # noqa: F401
+from .explore_var import VAR_STATE_LEN, learned_var_reference, var_state_init  # noqa: F401
 from .lr_schedule import LR_FACTOR, adaptive_lr_direction, adaptive_lr_reference, linear_lr  # noqa: F401
 from .minibatch import batch_permutation, minibatch_counter, minibatch_key  # noqa: F401
 from .reward_norm import RET_RMS_INIT, merge_return_moments, return_moments, reward_norm_reference, reward_scale  # noqa: F401

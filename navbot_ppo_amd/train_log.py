@@ -79,6 +79,7 @@ def tb_scalars(lg, cfg):
             **({"ppo/" + k: lg[k] for k in ("reward_scale", "ret_rms_mean", "ret_rms_std", "explained_variance")}
                if "reward_scale" in lg else {}),                                                    # (norm_reward)
             **({"ppo/bootstrapped_frac": lg["bootstrapped_frac"]} if "bootstrapped_frac" in lg else {}),   # (bootstrap_truncated)
+            **({"ppo/" + k: lg[k] for k in ("var", "std", "var_grad", "var_steps_skipped")} if "var_grad" in lg else {}),   # (learn_var)
             **({"scenarios/train_success_min": lg["train_scenario_success_min"],
                 "scenarios/train_success_mean": lg["train_scenario_success_mean"]}
                if "train_scenario_success_min" in lg else {}),                                      # (scenario_stats / _priority)
@@ -98,6 +99,8 @@ def progress_line(lg):
             + (f" lr={lg['lr']:.3e}" if "lr" in lg else "")
             + (f" lr_ups={lg['lr_ups']} lr_downs={lg['lr_downs']}" if "lr_ups" in lg else "")
             + (f" bootstrapped_frac={lg['bootstrapped_frac']:.4f}" if "bootstrapped_frac" in lg else "")
+            + (f" var={lg['var']:.4f} std={lg['std']:.4f} entropy={lg['entropy']:.4f} var_grad={lg['var_grad']:.3e} "
+               f"var_steps_skipped={lg['var_steps_skipped']}" if "var_grad" in lg else "")
             + (f" train scenarios: min={lg['train_scenario_success_min']:.3f} mean={lg['train_scenario_success_mean']:.3f}"
                if "train_scenario_success_min" in lg else "")
             + (f" eval: succ={lg['eval_success']:.3f} coll={lg['eval_collision']:.3f} tmo={lg['eval_timeout']:.3f} "

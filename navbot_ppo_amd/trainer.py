@@ -11,8 +11,8 @@ import torch
 
 from . import checkpoint, nets, train_log
 from ._native import _navppo, _ptr, check, lib
-from .config import (PPOConfig, check_bootstrap_config, check_continue_config, check_reward_norm_config, check_scan_history_config,
-                     check_scenario_config)
+from .config import (PPOConfig, check_bootstrap_config, check_continue_config, check_learn_var_config, check_reward_norm_config,
+                     check_scan_history_config, check_scenario_config)
 from .distributed import as_ctx
 from .env import HIST_CARRY, HIST_DIM, gae_scan, gae_scan_trunc, rtg_scan, stack_rows
 from .evaluate import evaluate_params, make_eval_env
@@ -91,6 +91,9 @@ class PPOTrainer:
             self.rew_scaled_buf = torch.zeros((T, N), dtype=f32, device=dev)   # what the scans read; rew_buf keeps the raw rewards
             self._ret_rows = torch.zeros((ctx.world, 3), dtype=torch.float64, device=dev)   # one row per rank
         self.var = torch.full((), cfg.init_var, dtype=f32, device=dev)  # ppo.py:123-124 (0.8 * I)
+        check_learn_var_config(cfg, ctx.world)
+        if cfg.learn_var:   # a view of the updater's state: every rollout path reads the variance the last optimiser step left
+            self.var = self.updater.var_state[1]
         self.var_host = float(cfg.init_var)   # host mirror, refreshed at every rollout start
         self._lo = torch.tensor([0.0, -1.0], device=dev)
         self._hi = torch.tensor([1.0, 1.0], device=dev)
@@ -383,7 +386,9 @@ class PPOTrainer:
         up to being applied at the rollout boundary; documented deviation."""
         cfg = self.cfg
         v = float(self.var)   # the one read-back of the iteration, at its start (the stream is idle here)
-        if self.t_so_far > cfg.var_decay_after:
+        if cfg.learn_var:   # the update steps the variance; the schedule is off
+            pass
+        elif self.t_so_far > cfg.var_decay_after:
             k = int(round(self.episode_starts / max(self.env.N, 1)))
             for _ in range(k):
                 if v >= cfg.var_floor:
@@ -461,7 +466,9 @@ class PPOTrainer:
         self.logger = dict(metrics, **stats, iteration=self.i_so_far, t_so_far=self.t_so_far,
                            rollout_time=t1 - t0, update_time=t2 - t1, iter_time=t2 - t0,
                            steps_per_sec=T * N * world / (t2 - t0),                      # ppo.py:855
-                           rollout_steps_per_sec=T * N * world / (t1 - t0), var=self.var_host)
+                           rollout_steps_per_sec=T * N * world / (t1 - t0),
+                           # (learn_var: `var` is the update's figure -- what it ended on, what the next rollout draws with)
+                           **(dict(rollout_var=self.var_host) if cfg.learn_var else dict(var=self.var_host)))
         if cfg.eval_every > 0 and self.i_so_far % cfg.eval_every == 0 and self.writes_files:
             self.logger.update(self.evaluate_now())   # rank 0 alone, no collective: the other ranks go on to their next rollout
         if cfg.output_dir and self.writes_files:
@@ -557,6 +564,9 @@ class PPOTrainer:
         return (("lrsched", cfg.lr_schedule == "adaptive",   # the rate the next step starts from (on the host since the last read-back)
                  lambda: {"lr": float(self.updater.lr_value)}, lambda s: self.updater.set_lr(float(s["lr"] if s else cfg.lr)),
                  "lr_schedule='adaptive': {} not found -- the learning rate starts at lr = " + str(cfg.lr)),
+                ("explore", cfg.learn_var,   # theta, its Adam moments and the steps taken
+                 lambda: self.updater.var_state_dict(), lambda s: self.updater.load_var_state(s),
+                 "learn_var: {} not found -- the exploration variance starts at init_var = " + str(cfg.init_var)),
                 ("scenarios", self.scenarios is not None,   # the scores and the re-assignment counter (the next assignment is drawn from them)
                  lambda: dict(self.scenarios.state_dict(), score=[float(v) for v in self.scenarios.score]),
                  lambda s: self.scenarios.load_state_dict(s or {"score": [float("nan")] * self._scen_K, "counter": 0}),

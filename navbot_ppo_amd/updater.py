@@ -9,8 +9,10 @@ import torch.distributed as dist
 
 from . import nets
 from ._native import _navppo, _ptr, lib
-from .config import check_lr_schedule_config, check_minibatch_config, check_update_config
+from .config import check_learn_var_config, check_lr_schedule_config, check_minibatch_config, check_update_config
 from .distributed import as_ctx, global_mean
+from .explore_var import (ADAM_M, ADAM_V, ENTROPY_AT_ZERO, GRAD, SKIPPED, STEPS, THETA, VAR, VAR_STATE_LEN, learned_var_reference,
+                          var_state_init)
 from .lr_schedule import adaptive_lr_direction, adaptive_lr_reference
 from .minibatch import batch_permutation, minibatch_counter, minibatch_key
 
@@ -23,6 +25,9 @@ ADAM_HYPER = (0.9, 0.999, 1e-8)   # Adam's (beta1, beta2, eps), torch's defaults
 # PPOUpdater._mode_args holds the arguments a mode adds.  Every mode but the plain one runs the clipped machinery and fills clip_stats:
 # target_kl or the adaptive rate without max_grad_norm clip at max_norm = +inf, the unclipped epochs' bits.
 PLAIN, CLIP, KL_STOP, ADAPTIVE_LR = "", "_clipped", "_kl", "_lr"
+# PPOConfig.learn_var (one rank only): the *_var entry points -- the clipped machinery, or with lr_schedule="adaptive" the adaptive
+# rate's, with the passes reading the variance from the device state and one more launch that steps it
+LEARN_VAR = "_var"
 
 
 class FlatParams:
@@ -127,6 +132,7 @@ class PPOUpdater:
         check_update_config(cfg)
         check_minibatch_config(cfg)
         check_lr_schedule_config(cfg)
+        check_learn_var_config(cfg, self.ctx.world)
         self.max_norm = None if cfg.max_grad_norm is None else float(cfg.max_grad_norm)
         self.kl_limit = None if cfg.target_kl is None else 1.5 * float(cfg.target_kl)   # Stable-Baselines3's factor
         # lr_schedule: lr_adaptive = the rule runs after every optimiser step; lr_value = the rate the next step starts from (adaptive),
@@ -137,6 +143,15 @@ class PPOUpdater:
         self.lr_counts = (0, 0)  # adaptive: raises and lowerings since construction
         self.kl_steps = None     # adaptive: [steps] the approx_kl (global, on several ranks) of every optimiser step of the last update()
         self.mode = ADAPTIVE_LR if self.lr_adaptive else KL_STOP if self.kl_limit is not None else CLIP if self.max_norm is not None else PLAIN
+        # learn_var: [8] (theta, var, m, v, gradient, steps taken, steps skipped, entropy), on the updater's device; after this only the
+        # *_var entry points (fused) or the mirror's step (PyTorch) write it.  The trainer's variance is a view of slot 1.
+        self.learn_var = bool(cfg.learn_var)
+        self.var_state = None
+        if self.learn_var:
+            self.mode = LEARN_VAR
+            self.var_state = torch.tensor(var_state_init(cfg.init_var), dtype=torch.float32, device=self.device)
+            self._var_t = 0   # (the PyTorch path: optimiser steps so far, Adam's count for the mirror)
+            self._var_skipped0 = 0   # the skipped steps the last summary saw (the state counts since its initialisation)
         self._clipping = self.mode != PLAIN   # the clipped machinery runs and fills clip_stats
         self.update_index = 0    # updates run so far: the high word of the shuffle's counter
         self._mb_key = minibatch_key(cfg.seed, self.ctx.rank)
@@ -198,13 +213,16 @@ class PPOUpdater:
             args += (self.kl_limit, _ptr(self.kl_state))
         elif self.mode == ADAPTIVE_LR:
             args += (float(cfg.desired_kl), float(cfg.lr_min), float(cfg.lr_max), int(adapt), _ptr(self.lr_state))
+        elif self.mode == LEARN_VAR:   # (lr_state None: the constant rate, the adaptive rule's arguments are not read)
+            args += (float(cfg.desired_kl), float(cfg.lr_min), float(cfg.lr_max), int(adapt), _ptr(self.lr_state),
+                     float(cfg.ent_coef), float(cfg.var_min), float(cfg.var_max), _ptr(self.var_state))
         return args
 
     def _step_kw(self, plan, st):
         """What a step's launches get beside today's positional arguments, as two keyword dictionaries: where a slice starts in the
         prepared batch (minibatches), and whether the adaptive rate adapts -- on every step but the first of an update.  Both empty on
         whole-batch epochs of the other modes."""
-        return ({"first_row": st.first_row} if plan.K > 1 else {}), ({"adapt": st.index > 0} if self.mode == ADAPTIVE_LR else {})
+        return ({"first_row": st.first_row} if plan.K > 1 else {}), ({"adapt": st.index > 0} if self.lr_adaptive else {})
 
     def _workspace(self, n):
         """Scratch of the fused kernels: fixed for the 2x64 heads, per-sample partial block outputs for the 512-wide nets."""
@@ -345,7 +363,9 @@ class PPOUpdater:
         clipped launches with a step launch that derives its rate on the device.  first_row: _batch_args; adapt: _mode_args."""
         mode = self._mode_args(cstats, adapt)
         self._adam_t += 1
-        fam, batch = self._batch_args(obs, acts, logp_old, rtg, adv, var, first_row)
+        fam, batch = self._batch_args(obs, acts, logp_old, rtg, adv, 0.0 if self.learn_var else var, first_row)
+        if self.learn_var:   # the *_var entry points have no by-value variance: (..., n, clip)
+            batch = batch[:-2] + batch[-1:]
         _navppo(fam + "_update_epoch" + self.mode, _ptr(self.fp.flat), *batch, self._lr(), *ADAM_HYPER, int(self._adam_t),
                 _ptr(self._adam_m), _ptr(self._adam_v), _ptr(self.fp.grad), _ptr(stats), _ptr(self._workspace(obs.shape[0])), *mode)
 
@@ -454,6 +474,30 @@ class PPOUpdater:
         g_a, g_c = self.fp.grad[:self._n_actor], self.fp.grad[self._n_actor:]
         self.clip_stats[ep] = torch.stack([(g_a * g_a).sum(), (g_c * g_c).sum(), g_a.new_full((), c), g_a.new_full((), c)])
 
+    def _var_step_host(self, grad_sum, coef):
+        """learn_var on the PyTorch path: the step of log var through the kernel's host mirror, at the rate the nets just stepped with"""
+        cfg = self.cfg
+        self._var_t += 1
+        new = learned_var_reference(self.var_state.tolist(), grad_sum, coef, cfg.ent_coef, self.opt.param_groups[0]["lr"], ADAM_HYPER[:2],
+                                    ADAM_HYPER[2], self._var_t, cfg.var_min, cfg.var_max)
+        self.var_state.copy_(torch.tensor(new, dtype=torch.float32))
+
+    def var_state_dict(self):
+        """learn_var: what a checkpoint keeps of the state -- theta, Adam's moments and the steps taken"""
+        st = self.var_state.tolist()
+        return {"theta": st[THETA], "m": st[ADAM_M], "v": st[ADAM_V], "steps": st[STEPS]}
+
+    def load_var_state(self, d=None):
+        """learn_var: the state of a checkpoint (var_state_dict), or -- None -- a fresh one from init_var.  Written IN PLACE: the
+        trainer's variance is a view of slot 1, and captured graphs hold its address."""
+        st = var_state_init(self.cfg.init_var)
+        if d is not None:
+            theta = torch.tensor(float(d["theta"]), dtype=torch.float32)
+            st = [float(theta), float(torch.exp(theta)), float(d["m"]), float(d["v"]), 0.0, float(d["steps"]), 0.0, float(theta + ENTROPY_AT_ZERO)]
+            self._var_t = int(d["steps"])
+        self.var_state.copy_(torch.tensor(st, dtype=torch.float32))
+        self._var_skipped0 = 0
+
     def _fused_record(self, plan, V0, r0, gn_sum=None, net_gn=None):
         """What every fused runner ends with: ONE synchronisation (kl_state) after the last epoch, then the record from the first k rows
         of _fhist.  gn_sum / net_gn: the runner's own sums of norms; the single-GPU epochs have none and take them from the rows."""
@@ -534,6 +578,9 @@ class PPOUpdater:
         acc, net_gn = torch.zeros(6, device=batch[0].device), None  # sums over steps of the diagnostics and of the per-net gradient norms
         kls = []   # adaptive lr: every step's (global) approx_kl, float32
         for ep, _, _, (obs, acts, logp_old, rtg, adv) in self._steps(plan, batch):   # ppo.py:305 (ep: the step -- an epoch, or a slice of one)
+            if self.learn_var:   # theta = log var as a leaf: autograd gives d(actor loss)/d theta, the entropy term is the mirror's
+                log_var = self.var_state[THETA].detach().clone().requires_grad_(True)
+                var = torch.exp(log_var)
             a_loss, c_loss, ratios, logp, _ = ppo_losses(self.actor, self.critic, obs, acts, logp_old, rtg, adv, var, self.cfg.clip)
             self.fp.grad.zero_()
             (a_loss + c_loss).backward()                       # disjoint nets: same grads as the two backward()s of :349,:386
@@ -541,7 +588,7 @@ class PPOUpdater:
                 ctx.all_reduce_sum(self.fp.grad)
                 self.fp.grad.div_(ctx.world)
             ratios, lr_, trip = ratios.detach(), logp.detach() - logp_old, False
-            if self.mode in (KL_STOP, ADAPTIVE_LR):   # both act before the step, on the global approx_kl (weighted by the ranks' batch sizes)
+            if self.kl_limit is not None or self.lr_adaptive:   # both act before the step, on the global approx_kl (weighted by the ranks' batch sizes)
                 kl = float(global_mean(ctx, ((ratios - 1) - lr_).sum(), float(lr_.numel())))
             if self.kl_limit is not None:   # a NaN trips
                 trip = not (kl <= self.kl_limit)
@@ -560,6 +607,8 @@ class PPOUpdater:
                 self.opt.step()                                # ppo.py:381,392
                 if self._clipping:   # (target_kl without max_grad_norm: the norms of every epoch, coefficient 1)
                     self._clip_row(ep, 1.0)
+            if self.learn_var:   # theta follows the actor: its coefficient and rate of this step, Adam's count as torch's (steps so far)
+                self._var_step_host(float(log_var.grad), float(self.clip_stats[ep, 2]))
             with torch.no_grad():                              # ppo.py:323-336
                 losses[ep] = torch.stack([a_loss.detach(), c_loss.detach()])
                 acc += torch.stack([a_loss.detach(), c_loss.detach(), ((ratios - 1) - lr_).mean(),
@@ -606,7 +655,10 @@ class PPOUpdater:
                 "actor_param_delta", "critic_param_delta",
                 "grad_clip_frac_actor", "grad_clip_frac_critic", "skipped_steps_actor", "skipped_steps_critic"]
         lr_cols = [self.lr_state] if self.lr_state is not None else []   # (adaptive lr, fused: the state rides on this read-back)
-        vals = [float(v) for v in torch.cat([acc, extra] + (clip_cols if self.max_norm is not None else []) + lr_cols).tolist()]
+        var_cols = [self.var_state.to(acc.device)] if self.learn_var else []   # (learn_var: the state rides on this read-back too)
+        vals = [float(v) for v in torch.cat([acc, extra] + (clip_cols if self.max_norm is not None else []) + lr_cols + var_cols).tolist()]
+        if var_cols:
+            vals, vs = vals[:-VAR_STATE_LEN], vals[-VAR_STATE_LEN:]
         if lr_cols:   # the slot the last step wrote; the counts are cumulative
             vals, st = vals[:-4], vals[-4:]
             if plan.n_steps > 0:
@@ -620,6 +672,10 @@ class PPOUpdater:
             self.lr_counts = (ups, downs)
         elif self.lr_value is not None:   # ("linear": the rate this update ran with)
             stats["lr"] = self.lr_value
+        if var_cols:   # the variance the NEXT rollout draws its noise with, the gradient of the last step taken, the steps skipped in this update
+            stats.update(var=vs[VAR], std=math.sqrt(vs[VAR]), entropy=1.0 + LOG_2PI + vs[THETA], var_grad=vs[GRAD],
+                         var_steps_skipped=int(vs[SKIPPED]) - self._var_skipped0)
+            self._var_skipped0 = int(vs[SKIPPED])
         if self.kl_limit is not None:   # steps taken (n_ep if the update never stopped) and whether it stopped; identical on every rank
             # (minibatches: kl_stop_step counts the steps, kl_stop_epoch the whole epochs completed)
             stats["kl_stop_epoch"], stats["kl_stopped"] = r.steps // r.K, r.stopped
@@ -661,7 +717,8 @@ class PPOUpdater:
             self._last_V0 = V0      # (the trainer's explained_variance: the critic before this update)
         runner = (self._run_pytorch if not self.fused else self._run_fused_single if not multi else
                   self._run_fused_pipelined if self.fused_mlp64 and cfg.overlap_allreduce else self._run_fused_multi)
-        run = runner(plan, batch, float(var) if self.fused else var, V0, r0)
+        # (learn_var: `var` is not read -- the variance is the state's, on the device -- and must not cost a synchronisation here)
+        run = runner(plan, batch, None if self.learn_var else float(var) if self.fused else var, V0, r0)
         self.stats = self._summarise(run, plan, flat_before)
         self.loss_history = run.losses   # per-epoch (actor, critic) loss, ppo.py:396-397; NaN rows behind an early stop
         last = (run.k - 1) // run.K      # the last epoch a step of which ran
