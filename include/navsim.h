@@ -113,9 +113,35 @@ typedef struct navsim_info {
        vector registers per lane, scratch bytes per lane (= spilled registers x 4; 0 = none), static LDS bytes per workgroup */
     int32_t step_vgprs, step_scratch_bytes, step_lds_bytes;
     int32_t seq_vgprs, seq_scratch_bytes, seq_lds_bytes;
-    int32_t reserved[6];
+    int32_t reserved[6];   /* reserved[0]: scan_pool (navsim_set_scan_pool; 1 = off) */
 } navsim_info;
 int navsim_get_info(navsim_t* h, navsim_info* out);
+
+/*
+ * Sector LiDAR -- an EXTENSION built on the reference's unused down-sampler (pick_laser.Pick(scan, len_batch): the minimum of
+ * consecutive chunks of a denser scan).  scan_pool = k in 1..4, 1 = off (the default: today's behaviour, kernels and bits).  With
+ * k > 1 on a 10-beam handle:
+ *   dense fan     10 k rays, phi_i = A_min + i (A_max - A_min) / (10 k - 1): the beam angles of a handle with n_beams = 10 k.
+ *   per ray       each dense ray goes through the sensor model on its own -- range limits, lidar_below_min, lidar_noise_sigma with
+ *                 the noise keyed by the dense ray index i exactly as a 10 k-beam handle keys beam i (Gazebo's sensor, samples = 10 k).
+ *   column c      min over the sanitised readings of rays k c .. k c + k - 1, divided by 3.5; a -inf reading (lidar_below_min) wins.
+ *   collision     0 < min < 0.2 over all 10 k rays, i.e. over the 10 pooled columns.
+ * So the pooled env IS the 10 k-beam env -- pose, goal draws, reward, flags, episode sums and RNG counters -- with its rows passed
+ * through Pick(., k); columns 10..15, every row shape, net, history row and checkpoint are unchanged.  The pooled world is harder:
+ * an obstacle that sat between two of the 10 beams (and was neither seen nor hit) is now seen, and hit.
+ * Callable before or after navsim_set_map / navsim_set_movers / navsim_set_mover_bank, in any order, with the same resulting bits;
+ * rebuilds the dense beam table and re-casts the cached spawn scans where a map is set; synchronises the device; takes effect from
+ * the next launch (set it BEFORE a step is captured into a graph).  k = 1 restores exactly the kernels and bits of a fresh handle.
+ * On a pooled handle every stepping entry point runs the pooled twin of the mover kernels' shape -- 16 envs on 8 waves, in rounds of
+ * workgroups beyond 4096 envs, 64-segment passes or tile boxes; navsim_set_shape is accepted and has no effect; navsim_raycast
+ * returns [N, 10] pooled noise-free scan values; navsim_get_info reports scan_pool in reserved[0], 16 / 8 / cast 0 | 3,
+ * rollout_kind = 1 and the pooled twin's resources.
+ * NAVSIM_E_ARG: k outside 1..4 (more than 4 rays per column is not built), and with k > 1: scan_pool > 1 needs n_beams == 10:
+ * pooling a 36-beam scan is not built; scan_pool > 1 needs a shared static map: pooling over per-env maps is not built (a later
+ * navsim_set_map(per_env = 1) on a pooled handle is refused likewise).  navsim_rollout_resmlp512 / navsim_evaluate_resmlp512 on a
+ * pooled handle fail with NAVSIM_E_STATE: not built.
+ */
+int navsim_set_scan_pool(navsim_t* h, int32_t k);
 
 /*
  * The static world the reference gets from Gazebo (worlds/train_world_new.world:85-416):

@@ -56,6 +56,7 @@ SYMBOLS = [
     ("navsim_destroy", None, [_vp]),
     ("navsim_set_shape", C.c_int, [_vp, _i32, _i32]),
     ("navsim_get_info", C.c_int, [_vp, C.POINTER(NavsimInfo)]),
+    ("navsim_set_scan_pool", C.c_int, [_vp, _i32]),   # sector LiDAR: k rays min-pooled into each scan column
     ("navsim_set_map", C.c_int, [_vp, _vp, _i32, _i32, _vp]),
     ("navsim_set_movers", C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp]),
     ("navsim_set_mover_bank", C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp]),

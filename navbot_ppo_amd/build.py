@@ -13,13 +13,16 @@ SRCS = [os.path.join(HERE, "csrc", f) for f in ("navsim.hip", "ppo_mlp64.hip", "
                                                    "ppo_group_sums.hip",    # navppo_group_sums (scenario_stats / scenario_priority)
                                                    # the *_var twins (learn_var): the partner sources compiled a third time
                                                    # (NAVPPO_VAR_TU), and the launch that steps log var
-                                                   "ppo_mlp64_var.hip", "ppo_resmlp512_var.hip", "ppo_learned_var.hip")]
+                                                   "ppo_mlp64_var.hip", "ppo_resmlp512_var.hip", "ppo_learned_var.hip",
+                                                   # the sector-LiDAR twins (scan_pool): navsim.hip's step body compiled a second time
+                                                   # (NAVSIM_POOL_TU), beside it instead of inside it
+                                                   "navsim_pool.hip")]
 HDRS = ["navsim.h", "navppo.h"]
 INC = os.path.join(REPO, "include")
 # what every object depends on besides its own source: the public headers, the csrc headers and the two sources the *_kl twins include
 HDR_DEPS = [os.path.join(INC, h) for h in HDRS] + [os.path.join(HERE, "csrc", h) for h in (
-    "navsim_select.h", "mlp64_policy.h", "navppo_internal.h", "resmlp_policy.h", "bf16x3.h", "ppo_mlp64_x3s.h", "ppo_resmlp512_bwd2s.h",
-    "ppo_mlp64.hip", "ppo_resmlp512.hip")]
+    "navsim_select.h", "navsim_pool.h", "mlp64_policy.h", "navppo_internal.h", "resmlp_policy.h", "bf16x3.h", "ppo_mlp64_x3s.h",
+    "ppo_resmlp512_bwd2s.h", "ppo_mlp64.hip", "ppo_resmlp512.hip", "navsim.hip")]
 LIB = os.path.join(HERE, "libnavsim.so")
 
 # -ffp-contract=off: the arithmetic contract writes every fused multiply-add explicitly
@@ -53,6 +56,7 @@ def needs_build():
 # asm: tools/verify/mfma_hazard_lint.py, tests/test_isa_lint_cpu.py) and copies 8 more registers per tile; with register-class priority
 # first it does neither.  (The other kernels of the file: same registers, no spills either way.)
 EXTRA_FLAGS = {"navsim.hip": ["-mllvm", "-disable-machine-licm"],
+               "navsim_pool.hip": ["-mllvm", "-disable-machine-licm"],   # (the same persistent kernels, pooled)
                "ppo_resmlp512.hip": ["-mllvm", "-greedy-regclass-priority-trumps-globalness=1"],
                "ppo_resmlp512_kl.hip": ["-mllvm", "-greedy-regclass-priority-trumps-globalness=1"],   # (resmlp_bwd2s_kl: the same stream)
                "ppo_resmlp512_var.hip": ["-mllvm", "-greedy-regclass-priority-trumps-globalness=1"]}   # (resmlp_bwd2s_var likewise)

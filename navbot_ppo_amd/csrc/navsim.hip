@@ -121,6 +121,10 @@ struct Params {
     const int32_t* mov_tid;      // [N] tape id per env (the goal rectangles' index), the handle's; null = all zero
     const double* mov_rects;     // [K][mov_n_rects][4] per-tape goal rejection rectangles (a NaN row is absent), the handle's; null = none
     int mov_n_rects;
+    // ---- sector LiDAR (navsim_set_scan_pool), in what was the struct's tail padding.  Read by the pooled twins (navsim_pool.hip) only:
+    // they cast B * pool rays and min-pool `pool` consecutive ones into each of the B scan columns; beam_cs is then [2][B * pool] and
+    // the rows of spawn_scan / spawn_obs hold B * pool entries.  1 = off.
+    int pool;
 };
 static_assert(offsetof(Params, max_ep_steps) == 128, "the hot head of Params");
 
@@ -353,14 +357,19 @@ __device__ __forceinline__ void sample_episode(PRef P, const Rects& R, int i, ui
 constexpr uint32_t kRecValid = 0x40000000u;   // bit of the ep_step word: the cached next-episode records of this env are current
 constexpr uint32_t kStepMask = 0x3FFFFFFFu;
 
-template <int NB, int EPB, int NW = 4>
+// POOL (the sector-LiDAR twins, navsim_pool.hip): the block casts NB * Params::pool rays (pool <= kMaxPool) and writes NB scan
+// columns, so everything indexed by ray -- dir, rng, noise, sp_scan, pe, beam -- is sized for NR = kMaxPool * NB rays and everything
+// indexed by column keeps NB.  Off, NR == NB: the block is what it was.
+constexpr int kMaxPool = 4;
+template <int NB, int EPB, int NW = 4, bool POOL = false>
 struct StepSmem {
+    static constexpr int NR = POOL ? kMaxPool * NB : NB;   // rays the arrays hold
     float2 org[EPB];             // sensor origin per env
     float2 hd[EPB];              // heading (cos, sin) as float32: the cull only (never the ranges)
-    float2 dir[NB * EPB];        // [beam][env] unit direction
-    unsigned rng[NB * EPB];      // [beam][env] nearest hit as float bits (non-negative floats order like uints)
+    float2 dir[NR * EPB];        // [beam][env] unit direction
+    unsigned rng[NR * EPB];      // [beam][env] nearest hit as float bits (non-negative floats order like uints)
     float obs[EPB * (NB + 7)];   // [env][B+6 (+1 pad: odd row stride, conflict-free)] the block's output tile
-    float noise[NB * EPB];       // [beam][env] standard-normal draws for the range noise (only written when sigma > 0)
+    float noise[NR * EPB];       // [beam][env] standard-normal draws for the range noise (only written when sigma > 0)
     // env state parked by the part-1 lanes for the part-2/3 lanes
     double sv_d[13][EPB];        // x, y, th, gx, gy, past_dist, dist, (7-9 unused), ep_ret, step displacement, ep_path
     float2 sv_act[EPB], sv_pact[EPB];
@@ -374,7 +383,7 @@ struct StepSmem {
     int sp_k[2][EPB];
     double sp_rg[2][EPB];        // the arrival re-spawn goal (environment_new.py:245-253) and the draw counter after it
     uint32_t sp_rctr[EPB];
-    float sp_scan[2][EPB][NB];   // lidar entries of the reset observation (SENS: the raw nearest hits at the start pose)
+    float sp_scan[2][EPB][NR];   // lidar entries of the reset observation (SENS: the raw nearest hits at the start pose)
     unsigned mn_bits[EPB];       // min over the sanitised scan as float bits, and whether a reading is negative (-inf, SENS)
     unsigned neg[EPB];
     // cast: per-wave queue of the segments that survive the cull (ring of 128)
@@ -382,11 +391,11 @@ struct StepSmem {
     unsigned qe[NW][128];
     float4 r4[NW][128];          // ... and of those whose angular extent holds at least one beam
     unsigned re[NW][128];        //     env | first beam of that extent << 8 | number of beams << 16
-    unsigned pe[NW][(NB > 16) ? 128 : 1];   // 36 beams: stage-B work entries: r4 slot | first beam << 8 | beams to test << 16
+    unsigned pe[NW][(POOL || NB > 16) ? 128 : 1];   // 36 beams: stage-B work entries: r4 slot | first beam << 8 | beams to test << 16
     float4 tbox[64];             // Params::tile_box, staged once per launch (BOXES)
     Rects rects;                 // Params::rects, staged by the ray waves before barrier A (the spec lanes' goal rejection test)
     float2 act_l[EPB];           // persistent rollout: the action the policy phase chose for this step
-    double beam[2 * NB];         // Params::beam_cs, staged by the pose waves (persistent rollout: once)
+    double beam[2 * NR];         // Params::beam_cs, staged by the pose waves (persistent rollout: once)
     // persistent rollout: the envs' state lives here between the steps (HBM sees it before the first and after the last)
     double st_d[8][EPB];         // x, y, th, gx, gy, past_dist, ep_ret, ep_path
     float2 st_pact[EPB];
@@ -394,8 +403,8 @@ struct StepSmem {
 };
 // What the MOV instantiations (moving obstacles, Params::mov_tape) keep in LDS on top of it: a kernel with movers declares this
 // one, step_body takes the base and reaches the rest through a cast that only its MOV branches contain.
-template <int NB, int EPB, int NW = 4>
-struct StepSmemMov : StepSmem<NB, EPB, NW> {
+template <int NB, int EPB, int NW = 4, bool POOL = false>
+struct StepSmemMov : StepSmem<NB, EPB, NW, POOL> {
     uint32_t mv_phase[EPB];      // the tape row each env's scan sees this step, published by the pose lanes before barrier A
     uint32_t mv_phase0[EPB];     // persistent kernels: Params::mov_phase0 of the workgroup's envs, staged once per launch
     uint2 mv_bp[EPB];            // ... and their tapes' (base row, period) (Params::mov_bp)
@@ -472,6 +481,25 @@ __device__ __forceinline__ float write_lidar(float* row, const float* best, int 
     return mn;
 }
 
+// the same for a sector-LiDAR row: column c is the minimum over the sanitised readings of rays pool c .. pool c + pool - 1 (`best`:
+// the raw hits of all B pool rays, stride 1; `noise` per ray)
+__device__ __forceinline__ float write_lidar_pool(float* row, const float* best, const float* noise, int nstride, float sigma,
+                                                  int below_min_mode, int B, int pool) {
+    float mn_all = INFINITY;
+    for (int c = 0; c < B; ++c) {
+        float mn = INFINITY;
+        for (int j = 0; j < pool; ++j) {
+            const int k = pool * c + j;
+            float r = sensor_value(best[k], sigma, noise ? noise[k * nstride] : 0.f, below_min_mode);
+            if (r == INFINITY) r = 3.5f;
+            mn = r < mn ? r : mn;
+        }
+        mn_all = mn < mn_all ? mn : mn_all;
+        row[c] = mn / 3.5f;
+    }
+    return mn_all;
+}
+
 // ---------------------------------------------------------------- the step kernel
 // One workgroup = 4 waves = EPB consecutive envs (EPB = 16: waves 0-1 are the "pose waves", 2-3 the "ray waves").
 //   part 1   pose waves, 8 lanes per env: state loads, float64 motion, the 8 sincos of the step one per lane -> LDS
@@ -537,11 +565,19 @@ struct EvalIO : StepIO {
 struct NoHook {
     __device__ __forceinline__ void operator()(int, int) const {}
 };
+// POOL (sector LiDAR, navsim_set_scan_pool; the twins of navsim_pool.hip): NB stays the number of scan COLUMNS -- the observation
+// tile, the policies' rows, the history rows and every output keep their shape -- while the rays the body casts become NC = NB *
+// Params::pool, a run-time count (one instantiation serves pool = 2, 3, 4; StepSmem holds kMaxPool * NB rays).  Pose lanes, noise,
+// cull, stage A2 and stage B (the entries of the 36-beam path: kPairB) work on the NC rays exactly as an NB = NC instantiation would;
+// between barriers B and B2 lane (column, env) takes the minimum of its `pool` consecutive sanitised readings.  Off, NC == NB is a
+// constant and nothing of it is compiled.
 template <int NB, int EPB, bool SENS, bool PERSIST, int NW = 4, bool BOXES = false, int PAIR = 0, class PRef = const Params&,
-          class IORef = const StepIO&, class Hook = NoHook, bool MOV = false>
-__device__ __forceinline__ void step_body(PRef P, StepSmem<NB, EPB, NW>& sm, int& next_env, IORef io, const bool last_step = true,
+          class IORef = const StepIO&, class Hook = NoHook, bool MOV = false, bool POOL = false>
+__device__ __forceinline__ void step_body(PRef P, StepSmem<NB, EPB, NW, POOL>& sm, int& next_env, IORef io, const bool last_step = true,
                                           const size_t row0 = 0, Hook hook = Hook()) {
     static_assert(EPB <= 64 && EPB >= 4 && NB % 2 == 0, "EPB / NB");
+    static_assert(!POOL || (MOV && SENS && NB == 10 && EPB == 16 && NW == 8 && PAIR == 0),
+                  "sector LiDAR: the sensor-options form of the 16-env mover twins");
     static_assert(!(PAIR && BOXES), "tile boxes describe 64-segment tiles");
     static_assert(!MOV || (NB == 10 && PAIR == 0 && ((EPB == 16 && NW == 8) || (EPB == 32 && NW == 8) || (EPB == 64 && NW == 16))),
                   "movers: 10 beams without the 128-segment passes, on 16 or 32 envs and 8 waves or on 64 envs and 16 waves");
@@ -558,6 +594,8 @@ __device__ __forceinline__ void step_body(PRef P, StepSmem<NB, EPB, NW>& sm, int
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int base = blockIdx.x * EPB;
     constexpr int B = NB;       // host dispatch guarantees P.B == NB
+    [[maybe_unused]] const int pool = POOL ? P.pool : 1;   // rays per scan column
+    const int NC = POOL ? NB * pool : NB;                   // rays cast (a constant unless POOL)
     constexpr int D = B + 6;
     constexpr int DP = D + 1;   // padded LDS row stride
     const int nloc = min(EPB, P.N - base);  // envs in this block
@@ -670,7 +708,7 @@ __device__ __forceinline__ void step_body(PRef P, StepSmem<NB, EPB, NW>& sm, int
     // pose waves: the beam table goes through LDS (lane k requests entry k here, right behind the state; written to LDS behind the
     // sincos, read back per beam): held in registers per lane it
     // cost 4 NB / LPE VGPRs from here to the end of part 1.  (The persistent rollout stages it once, before its first step.)
-    constexpr int kBeamLd = (2 * NB + 63) / 64;
+    constexpr int kBeamLd = (2 * StepSmem<NB, EPB, NW, POOL>::NR + 63) / 64;
     double beam_ld[kBeamLd];
     if (wave < PWP) {
         if (!PERSIST && pose_lane && el_pose < nloc) {
@@ -692,7 +730,7 @@ __device__ __forceinline__ void step_body(PRef P, StepSmem<NB, EPB, NW>& sm, int
         }
         if (!PERSIST) {
 #pragma unroll
-            for (int q = 0; q < kBeamLd; ++q) beam_ld[q] = P.beam_cs[min(lane + 64 * q, 2 * NB - 1)];
+            for (int q = 0; q < kBeamLd; ++q) beam_ld[q] = P.beam_cs[min(lane + 64 * q, 2 * NC - 1)];
         }
     }
 
@@ -753,8 +791,8 @@ __device__ __forceinline__ void step_body(PRef P, StepSmem<NB, EPB, NW>& sm, int
                 ctr = sm.st_ctr[e];
                 stepw = sm.st_step[e];
                 if constexpr (MOV) {
-                    mv_ph0 = static_cast<StepSmemMov<NB, EPB, NW>&>(sm).mv_phase0[e];
-                    mv_bp = static_cast<StepSmemMov<NB, EPB, NW>&>(sm).mv_bp[e];
+                    mv_ph0 = static_cast<StepSmemMov<NB, EPB, NW, POOL>&>(sm).mv_phase0[e];
+                    mv_bp = static_cast<StepSmemMov<NB, EPB, NW, POOL>&>(sm).mv_bp[e];
                 }
                 if (rr == 0) {
                     x = sm.st_d[0][e]; y = sm.st_d[1][e];
@@ -782,7 +820,7 @@ __device__ __forceinline__ void step_body(PRef P, StepSmem<NB, EPB, NW>& sm, int
             // the step -- integer work that issues under the latency of the float64 chain above
             if constexpr (MOV) {
                 if (rr == 0)
-                    static_cast<StepSmemMov<NB, EPB, NW>&>(sm).mv_phase[el_pose] = mover_row(mv_bp, (stepw & kStepMask) + 1u, mv_ph0);
+                    static_cast<StepSmemMov<NB, EPB, NW, POOL>&>(sm).mv_phase[el_pose] = mover_row(mv_bp, (stepw & kStepMask) + 1u, mv_ph0);
             }
         }
         // spec lanes that share wave 0 with the pose lanes (small shapes): behind the wheel arithmetic -- the wait for the state
@@ -838,12 +876,21 @@ __device__ __forceinline__ void step_body(PRef P, StepSmem<NB, EPB, NW>& sm, int
         if (!PERSIST && wave < PWP) {
 #pragma unroll
             for (int q = 0; q < kBeamLd; ++q)
-                if (lane + 64 * q < 2 * NB) sm.beam[lane + 64 * q] = beam_ld[q];
+                if (lane + 64 * q < 2 * NC) sm.beam[lane + 64 * q] = beam_ld[q];
         }
         if (pose_lane) {
             // the table entries just written by this wave (LDS operations of a wave complete in order)
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
+            if constexpr (POOL) {   // up to 40 rays: a loop (the table in registers would be 40 VGPRs beside the persistent kernels' policy)
+#pragma unroll 2
+                for (int b = rr; b < NC; b += LPE) {
+                    const double bc = sm.beam[b], bs = sm.beam[NC + b];
+                    const double c = cth * bc - sth * bs;
+                    const double s = sth * bc + cth * bs;
+                    sm.dir[b * EPB + el_pose] = make_float2((float)c, (float)s);
+                }
+            } else {
             constexpr int kBeamIt = (NB + LPE - 1) / LPE;
             double bc[kBeamIt], bs[kBeamIt];
 #pragma unroll
@@ -861,13 +908,14 @@ __device__ __forceinline__ void step_body(PRef P, StepSmem<NB, EPB, NW>& sm, int
                     sm.dir[b * EPB + el_pose] = make_float2((float)c, (float)s);
                 }
             }
+            }
         }
         // the ray waves' first three tiles are pre-assigned (requested before barrier A): 1, 2 or 3 items per ray wave
         if (tid == 0) next_env = (NW - PW) * (ntl == 1 ? 3 : (ntl == 2 ? 2 : 1));
     }
     if (wave >= PW) {
         // ---------------- other waves, part 1 (their tile requests went out at the top): LDS traffic under that round trip
-        for (int k = tid - 64 * PW; k < NB * EPB; k += kThreads - 64 * PW) sm.rng[k] = kInfBits;
+        for (int k = tid - 64 * PW; k < NC * EPB; k += kThreads - 64 * PW) sm.rng[k] = kInfBits;
         if (tid - 64 * PW < EPB) {
             sm.mn_bits[tid - 64 * PW] = kInfBits;
             sm.neg[tid - 64 * PW] = 0u;
@@ -896,7 +944,7 @@ __device__ __forceinline__ void step_body(PRef P, StepSmem<NB, EPB, NW>& sm, int
 
     if (sigma > 0.f && pose_lane && el_pose < nloc) {
         // range noise for this step: lane rr draws beams rr, rr + 2, ... (off the critical path: the others ray-cast)
-        for (int b = rr; b < B; b += LPE)
+        for (int b = rr; b < NC; b += LPE)   // (POOL: keyed by the dense ray index, as a handle with NC beams keys its beams)
             sm.noise[b * EPB + el_pose] = lidar_noise(P.key0, P.key1, P.env_id_base + (uint64_t)i, ctr, stepw & kStepMask, b);
     }
     // ---------------- part 2 (the other waves are already ray-casting): goal geometry.
@@ -940,12 +988,19 @@ __device__ __forceinline__ void step_body(PRef P, StepSmem<NB, EPB, NW>& sm, int
             int sk = 0;
             // the scan every reset at start pose k observes: rows of NB floats are 8-byte aligned (NB even), all NB / 2 requests
             // go out before the first is awaited (one memory latency instead of NB / 2)
-            float2 row[NB / 2];
+            // (POOL: the raw hits of all NC rays -- the noise is per ray; the row goes to LDS in a loop where it is stored below, not
+            // through NC / 2 registers)
+            float2 row[POOL ? 1 : NB / 2];
+            [[maybe_unused]] const float2* row_src = nullptr;
             auto request_row = [&](const int k) __attribute__((always_inline)) {
                 const float2* sp = reinterpret_cast<const float2*>((SENS ? P.spawn_scan : P.spawn_obs) +
-                                                                   (((MOV ? P.spawn_per_env : P.per_env) ? (size_t)ie * P.K : 0) + k) * B);
+                                                                   (((MOV ? P.spawn_per_env : P.per_env) ? (size_t)ie * P.K : 0) + k) * NC);
+                if constexpr (POOL) {
+                    row_src = sp;
+                } else {
 #pragma unroll
                 for (int b = 0; b < NB / 2; ++b) row[b] = sp[b];
+                }
             };
             const bool current = (sm.sv_step[e] & kRecValid) != 0;
             if (PERSIST && current) prefetch_records();
@@ -984,10 +1039,19 @@ __device__ __forceinline__ void step_body(PRef P, StepSmem<NB, EPB, NW>& sm, int
                 }
             }
             if (P.auto_reset) {
+                if constexpr (POOL) {
+#pragma unroll 5
+                    for (int b = 0; b < NC / 2; ++b) {
+                        const float2 v = row_src[b];
+                        sm.sp_scan[c][e][2 * b] = v.x;
+                        sm.sp_scan[c][e][2 * b + 1] = v.y;
+                    }
+                } else {
 #pragma unroll
                 for (int b = 0; b < NB / 2; ++b) {
                     sm.sp_scan[c][e][2 * b] = row[b].x;
                     sm.sp_scan[c][e][2 * b + 1] = row[b].y;
+                }
                 }
             }
             sm.sp_d[c][0][e] = px; sm.sp_d[c][1][e] = py; sm.sp_d[c][2][e] = pth; sm.sp_d[c][3][e] = tgx;
@@ -1017,11 +1081,11 @@ __device__ __forceinline__ void step_body(PRef P, StepSmem<NB, EPB, NW>& sm, int
         // Measured (tools/time_step.py, same box): BASELINE configs[3]'s shard (4096 envs, stage_4, 36 beams) 15.8 -> 12.5 us per
         // launch, tape form 12.7 -> 9.8 us per step.  At 10 beams the expansion costs more than it saves -- a wave of a configs[2]
         // workgroup queues only ~40 segments per step, one partial pass either way: 12.96 -> 13.19 us -- so it stays off there.
-        constexpr bool kPairB = NB > 16;
+        constexpr bool kPairB = POOL || NB > 16;   // (POOL: 20..40 rays, the entries of the 36-beam path)
         // (Rejected, profiles/r04_stage_b_pool_ablation.txt: pooling what the 16 waves' stage-B queues hold at the end of a step --
         // a wave queues ~40 segments per step, so its one pass runs with 60 % of its lanes -- removes 6.5 of 16 passes per
         // workgroup and step and is 14-17 % SLOWER: the passes land on the tail of the slowest wave, behind dependent LDS atomics.)
-        constexpr int kBeamsPerEntry = (NB > 16) ? 4 : 2;
+        constexpr int kBeamsPerEntry = kPairB ? 4 : 2;
         auto exact_tests = [&](const bool on, const float4 g, const unsigned el, const int b_first, const int n_b, auto n_max)
                                __attribute__((always_inline)) {
             constexpr int kMaxB = decltype(n_max)::value;
@@ -1036,7 +1100,7 @@ __device__ __forceinline__ void step_body(PRef P, StepSmem<NB, EPB, NW>& sm, int
                 // the empty volatile asm keeps this a real (wave-uniform) branch the compiler cannot speculate
                 asm volatile("; degenerate-segment pass" ::: "memory");
                 for (int u = 0; u < kMaxB; ++u) {
-                    const int b = min(b_first + u, NB - 1);
+                    const int b = min(b_first + u, NC - 1);
                     const float2 d = sm.dir[b * EPB + el];
                     const unsigned bits = __float_as_uint(ray_seg(rx, ry, ex, ey, k, d.x, d.y)) & 0x7fffffffu;
                     if (on && u < n_b && bits < kInfBits) atomicMin(&sm.rng[b * EPB + el], bits);
@@ -1044,7 +1108,7 @@ __device__ __forceinline__ void step_body(PRef P, StepSmem<NB, EPB, NW>& sm, int
             } else {
 #pragma unroll
                 for (int u = 0; u < kMaxB; ++u) {
-                    const int b = (kMaxB == NB) ? u : min(b_first + u, NB - 1);
+                    const int b = (kMaxB == NB) ? u : min(b_first + u, NC - 1);
                     const float2 d = sm.dir[b * EPB + el];
                     const unsigned bits = ray_seg_bits(rx, ry, ex, ey, k, d.x, d.y);
                     // hits only: same-address LDS atomics of a wave serialise, and most lanes miss
@@ -1106,7 +1170,11 @@ __device__ __forceinline__ void step_body(PRef P, StepSmem<NB, EPB, NW>& sm, int
         };
         // stage A2, dense over up to 64 survivors of the range / behind cull: does the arc the segment subtends, as seen
         // from the sensor, hold a beam at all -- and which?  (Beams are 20 degrees apart, a pillar facet at 2 m subtends 2.)
-        constexpr float kInvDelta = (float)((NB - 1) / (2.0 * kAngleMax)), kBeamMargin = 0.02f;
+        constexpr float kInvDeltaNB = (float)((NB - 1) / (2.0 * kAngleMax)), kBeamMargin = 0.02f;
+        // (POOL: the constant an NB = 20 | 30 | 40 instantiation folds)
+        const float kInvDelta = !POOL ? kInvDeltaNB
+                                      : pool == 2 ? (float)((2 * NB - 1) / (2.0 * kAngleMax))
+                                      : pool == 3 ? (float)((3 * NB - 1) / (2.0 * kAngleMax)) : (float)((4 * NB - 1) / (2.0 * kAngleMax));
         auto flushA2 = [&](int n) __attribute__((always_inline)) {
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
@@ -1128,16 +1196,16 @@ __device__ __forceinline__ void step_body(PRef P, StepSmem<NB, EPB, NW>& sm, int
             const bool wrap = (ya * yb < 0.f) && (kl * ey < 0.f);
             const bool through = kl * kl <= 1e-6f * fmaf(ex, ex, ey * ey);   // the line passes within 1 mm of the sensor
             const float ce = ceilf(lo - kBeamMargin), fl = floorf(hi + kBeamMargin);
-            const bool inside = (fl >= ce) && (fl >= 0.f) && (ce <= (float)(NB - 1));
-            const bool outside = (lo + kBeamMargin >= 0.f) || (hi - kBeamMargin <= (float)(NB - 1));
+            const bool inside = (fl >= ce) && (fl >= 0.f) && (ce <= (float)(NC - 1));
+            const bool outside = (lo + kBeamMargin >= 0.f) || (hi - kBeamMargin <= (float)(NC - 1));
             // an arc whose beam extent cannot be trusted (an endpoint next to the sensor or straight behind it, a line through the
             // sensor, an arc through straight-behind) keeps the segment for every beam
             const bool all = bad_a || bad_b || through || wrap;
             const bool keep = on && (all ? (bad_a || bad_b || through || outside) : inside);
             unsigned ext = 0u;
             if constexpr (kPairB) {   // beams ce .. fl of the fan (v_med3 clamps; a NaN coordinate has set `bad`)
-                const float b_lo = __builtin_amdgcn_fmed3f(ce, 0.f, (float)(NB - 1)), b_hi = __builtin_amdgcn_fmed3f(fl, 0.f, (float)(NB - 1));
-                ext = all ? ((unsigned)NB << 16) : (((unsigned)(int)b_lo << 8) | ((unsigned)((int)(b_hi - b_lo) + 1) << 16));
+                const float b_lo = __builtin_amdgcn_fmed3f(ce, 0.f, (float)(NC - 1)), b_hi = __builtin_amdgcn_fmed3f(fl, 0.f, (float)(NC - 1));
+                ext = all ? ((unsigned)NC << 16) : (((unsigned)(int)b_lo << 8) | ((unsigned)((int)(b_hi - b_lo) + 1) << 16));
             }
             qhead += n;
             const unsigned long long bal = __ballot(keep);
@@ -1268,7 +1336,7 @@ __device__ __forceinline__ void step_body(PRef P, StepSmem<NB, EPB, NW>& sm, int
         [[maybe_unused]] int m_el[kMovPasses];
         [[maybe_unused]] bool m_v[kMovPasses];
         if constexpr (MOV && !kMovRot) {
-            const StepSmemMov<NB, EPB, NW>& ms = static_cast<const StepSmemMov<NB, EPB, NW>&>(sm);
+            const StepSmemMov<NB, EPB, NW, POOL>& ms = static_cast<const StepSmemMov<NB, EPB, NW, POOL>&>(sm);
             const int mspl = P.mov_pack_log2, M = P.mov_M;
             const int mepp = 64 >> mspl, msub = lane >> mspl, mj = lane & ((1 << mspl) - 1);
             const float4* const tape = P.mov_tape;
@@ -1310,7 +1378,7 @@ __device__ __forceinline__ void step_body(PRef P, StepSmem<NB, EPB, NW>& sm, int
             bool present;
             const int el = mov_el(p, present);
             v = present && (mj < mv_M);
-            g = mv_tape[(size_t)static_cast<const StepSmemMov<NB, EPB, NW>&>(sm).mv_phase[el] * (size_t)mv_M + (size_t)min(mj, mv_M - 1)];
+            g = mv_tape[(size_t)static_cast<const StepSmemMov<NB, EPB, NW, POOL>&>(sm).mv_phase[el] * (size_t)mv_M + (size_t)min(mj, mv_M - 1)];
         };
         auto request_m = [&](const Pos p, float4& ga, bool& va, float4& gb, bool& vb) __attribute__((always_inline)) {
             if constexpr (kMovRot) {
@@ -1411,6 +1479,27 @@ __device__ __forceinline__ void step_body(PRef P, StepSmem<NB, EPB, NW>& sm, int
 
     // ---------------- scan -> observation entries, lane = (beam, env): sanitise (environment_new.py:192-198), / 3.5 (:289),
     // and min(scan) for the collision rule (:200).  Nearest hits are uint bit patterns of non-negative floats (inf = none).
+    if constexpr (POOL) {
+        // lane = (column, env): the nearest of the column's `pool` consecutive rays, each through the sensor model on its own.  A -inf
+        // reading wins the minimum.  (The minimum commutes with the division by 3.5: the quotient of the nearest reading.)
+        for (int idx = tid; idx < NB * EPB; idx += kThreads) {
+            const int c = idx / EPB, e = idx % EPB;
+            if (e < nloc) {
+                float mn = INFINITY;
+                for (int j = 0; j < pool; ++j) {
+                    const int k = (pool * c + j) * EPB + e;
+                    float r = sensor_value(__uint_as_float(sm.rng[k]), sigma, (sigma > 0.f) ? sm.noise[k] : 0.f, below_min);
+                    if (r == INFINITY) r = 3.5f;
+                    mn = r < mn ? r : mn;
+                }
+                sm.obs[e * DP + c] = mn / 3.5f;
+                if (mn < 0.f)
+                    atomicOr(&sm.neg[e], 1u);
+                else
+                    atomicMin(&sm.mn_bits[e], __float_as_uint(mn));
+            }
+        }
+    } else
     for (int idx = tid; idx < NB * EPB; idx += kThreads) {
         const int b = idx / EPB, e = idx % EPB;
         if (e < nloc) {
@@ -1495,7 +1584,9 @@ __device__ __forceinline__ void step_body(PRef P, StepSmem<NB, EPB, NW>& sm, int
             moved_stream = true;
             next_pact = make_float2(0.f, 0.f);
             pdist = dist;  // getGoalDistace, :116-120,:359
-            if (SENS) {
+            if constexpr (POOL) {
+                write_lidar_pool(row, sm.sp_scan[c][e], noise, EPB, sigma, below_min, B, pool);
+            } else if (SENS) {
                 write_lidar(row, sm.sp_scan[c][e], 1, noise, EPB, sigma, below_min, B);
             } else {
 #pragma unroll 2
@@ -1539,14 +1630,29 @@ __device__ __forceinline__ void step_body(PRef P, StepSmem<NB, EPB, NW>& sm, int
     }
 }
 
+// write_lidar_pool's entry for column `col` of the reset observation of record c, env e: the start pose's raw hits through this
+// step's range noise, ray by ray, then the minimum
+template <int NB, int EPB, int NW>
+__device__ __forceinline__ float pool_reset_entry(const StepSmem<NB, EPB, NW, true>& sm, const int c, const int e, const int col,
+                                                  const int pool, const float sigma, const int below_min) {
+    float mn = INFINITY;
+    for (int j = 0; j < pool; ++j) {
+        const int k = pool * col + j;
+        float r = sensor_value(sm.sp_scan[c][e][k], sigma, (sigma > 0.f) ? sm.noise[k * EPB + e] : 0.f, below_min);
+        if (r == INFINITY) r = 3.5f;
+        mn = r < mn ? r : mn;
+    }
+    return mn / 3.5f;
+}
+
 // Entries f0 .. f0 + KS - 1 of the observation env `e` (local) will hold when this step is over (entries past the row: 0), readable
 // from barrier B2 on -- i.e. BEFORE the rules lane of part 3 has run: the row in sm.obs as it stands, unless the step ends the
 // episode and auto_reset replaces it by the reset observation (ppo.py:582-593).  Whether it does follows from three values that are
 // final at barrier B2 -- the minimum of the scan (collision, environment_new.py:200), the goal distance (arrival, :204), the step
 // count (time-out, ppo.py:552) -- and the reset observation is the record the spec lanes staged in part 2.  The same expressions as
 // part 3 on the same operands, so the policy that reads its input through here sees exactly the row part 3 leaves in sm.obs.
-template <int NB, int EPB, int NW, bool SENS, int KS, class PRef>
-__device__ __forceinline__ void next_obs_n(PRef P, const StepSmem<NB, EPB, NW>& sm, const int e, const int f0, const float sigma,
+template <int NB, int EPB, int NW, bool SENS, int KS, class PRef, bool POOL = false>
+__device__ __forceinline__ void next_obs_n(PRef P, const StepSmem<NB, EPB, NW, POOL>& sm, const int e, const int f0, const float sigma,
                                            const int below_min, float (&x)[KS]) {
     constexpr int D = NB + 6, DP = NB + 7;
     const float* row = sm.obs + e * DP;
@@ -1565,11 +1671,15 @@ __device__ __forceinline__ void next_obs_n(PRef P, const StepSmem<NB, EPB, NW>& 
             const int idx = f0 + j;
             float val;
             if (idx < NB) {
+                if constexpr (POOL) {
+                    val = pool_reset_entry<NB, EPB, NW>(sm, c, e, min(idx, NB - 1), P.pool, sigma, below_min);
+                } else {
                 val = sm.sp_scan[c][e][min(idx, NB - 1)];
                 if (SENS) {   // write_lidar's entry: the start pose's nearest hit through this step's range noise
                     float r = sensor_value(val, sigma, (sigma > 0.f) ? sm.noise[min(idx, NB - 1) * EPB + e] : 0.f, below_min);
                     if (r == INFINITY) r = 3.5f;
                     val = r / 3.5f;
+                }
                 }
             } else if (idx < NB + 2) {
                 val = 0.f;                                                                       // environment_new.py:372-373
@@ -1620,8 +1730,8 @@ __global__ __launch_bounds__(64 * NW, min_waves_per_simd(NB, EPB, NW, PAIR, fals
 }
 
 // The shared-memory block of a kernel: with movers the extended one (StepSmemMov)
-template <int NB, int EPB, int NW, bool MOV>
-using StepSmemFor = typename std::conditional<MOV, StepSmemMov<NB, EPB, NW>, StepSmem<NB, EPB, NW>>::type;
+template <int NB, int EPB, int NW, bool MOV, bool POOL = false>
+using StepSmemFor = typename std::conditional<MOV, StepSmemMov<NB, EPB, NW, POOL>, StepSmem<NB, EPB, NW, POOL>>::type;
 
 // Movers (navsim_set_movers): every entry point takes the 16-env, 8-wave shape with 10 beams; navsim_rollout_mlp64 alone also has
 // the big shapes (rollout_big_mov_kernel below).  The MOV kernels are twins of their
@@ -1642,8 +1752,8 @@ __global__ __launch_bounds__(64 * 8) void step_mov_kernel(StepKArgs) {
 }
 
 // persistent kernels with movers: the phase offsets of the workgroup's envs -> LDS, once per launch
-template <int NB, int EPB, int NW, class PRef>
-__device__ __forceinline__ void load_mover_phase0(PRef P, StepSmemMov<NB, EPB, NW>& sm, const int base, const int nloc) {
+template <int NB, int EPB, int NW, class PRef, bool POOL = false>
+__device__ __forceinline__ void load_mover_phase0(PRef P, StepSmemMov<NB, EPB, NW, POOL>& sm, const int base, const int nloc) {
     const int32_t* const ph0 = P.mov_phase0;
     if ((int)threadIdx.x < nloc) {
         sm.mv_phase0[threadIdx.x] = ph0 ? (uint32_t)ph0[base + threadIdx.x] : 0u;
@@ -1682,16 +1792,16 @@ struct RolloutArgs {
 // rollout_big_kernel) do around step_body.  A workgroup owns envs base .. base + nloc - 1; PRef as in step_body.
 
 // The state of env i (local e) between HBM (Params) and LDS (sm.st_*): in before the first step, out after the last.
-template <int NB, int EPB, int NW, class PRef>
-__device__ __forceinline__ void load_state(PRef P, StepSmem<NB, EPB, NW>& sm, const int e, const int i) {
+template <int NB, int EPB, int NW, class PRef, bool POOL = false>
+__device__ __forceinline__ void load_state(PRef P, StepSmem<NB, EPB, NW, POOL>& sm, const int e, const int i) {
     sm.st_d[0][e] = P.x[i]; sm.st_d[1][e] = P.y[i]; sm.st_d[2][e] = P.th[i]; sm.st_d[3][e] = P.gx[i]; sm.st_d[4][e] = P.gy[i];
     sm.st_d[5][e] = P.past_dist[i]; sm.st_d[6][e] = P.ep_ret[i]; sm.st_d[7][e] = P.ep_path[i];
     sm.st_pact[e] = P.past_action[i];
     sm.st_step[e] = (uint32_t)P.ep_step[i];
     sm.st_ctr[e] = P.rng_ctr[i];
 }
-template <int NB, int EPB, int NW>
-__device__ __forceinline__ void store_state(const Params& P, const StepSmem<NB, EPB, NW>& sm, const int e, const int i) {
+template <int NB, int EPB, int NW, bool POOL = false>
+__device__ __forceinline__ void store_state(const Params& P, const StepSmem<NB, EPB, NW, POOL>& sm, const int e, const int i) {
     P.x[i] = sm.st_d[0][e]; P.y[i] = sm.st_d[1][e]; P.th[i] = sm.st_d[2][e]; P.gx[i] = sm.st_d[3][e]; P.gy[i] = sm.st_d[4][e];
     P.past_dist[i] = sm.st_d[5][e]; P.ep_ret[i] = sm.st_d[6][e]; P.ep_path[i] = sm.st_d[7][e];
     P.past_action[i] = sm.st_pact[e];
@@ -1700,8 +1810,8 @@ __device__ __forceinline__ void store_state(const Params& P, const StepSmem<NB, 
 }
 
 // The workgroup's rows of an [N, B + 6] observation buffer (f32; f16 if half_rows) -> the observation tile sm.obs
-template <int NB, int EPB, int NW>
-__device__ __forceinline__ void load_obs_tile(StepSmem<NB, EPB, NW>& sm, const void* obs, const int base, const int nloc,
+template <int NB, int EPB, int NW, bool POOL = false>
+__device__ __forceinline__ void load_obs_tile(StepSmem<NB, EPB, NW, POOL>& sm, const void* obs, const int base, const int nloc,
                                               const bool half_rows) {
     constexpr int D = NB + 6, DP = D + 1;
     for (int k = threadIdx.x; k < nloc * D; k += 64 * NW)
@@ -1710,9 +1820,10 @@ __device__ __forceinline__ void load_obs_tile(StepSmem<NB, EPB, NW>& sm, const v
 }
 
 // The beam table and the goal rejection rectangles -> LDS, once for all steps of the launch
-template <int NB, int EPB, int NW, class PRef>
-__device__ __forceinline__ void load_tables(PRef P, StepSmem<NB, EPB, NW>& sm) {
-    for (int k = threadIdx.x; k < 2 * NB; k += 64 * NW) sm.beam[k] = P.beam_cs[k];
+template <int NB, int EPB, int NW, class PRef, bool POOL = false>
+__device__ __forceinline__ void load_tables(PRef P, StepSmem<NB, EPB, NW, POOL>& sm) {
+    const int n_beam = POOL ? 2 * NB * P.pool : 2 * NB;   // (POOL: the dense fan's table)
+    for (int k = threadIdx.x; k < n_beam; k += 64 * NW) sm.beam[k] = P.beam_cs[k];
     for (int k = threadIdx.x; k < (int)(sizeof(Rects) / 8); k += 64 * NW)
         reinterpret_cast<uint64_t*>(&sm.rects)[k] = reinterpret_cast<const uint64_t*>(P.rects)[k];
 }
@@ -1725,8 +1836,8 @@ struct ObsRow {
 // barrier B2, the row the step will leave (next_obs_n), rounded as the f16 buffer holds it; else the row in sm.obs (policy_row).
 // An absent env (e >= nloc) feeds zeros.  (Returned by value: with the row as an output argument instead, rollout_kernel<10, 4 | 8,
 // false, 8> took 169 VGPRs, one SIMD occupancy step below the 167 of the row written out in the kernel.)
-template <int NB, int EPB, int NW, bool SENS, bool IN_STEP, class PRef>
-__device__ __forceinline__ ObsRow<mlp64::Layout<NB + 6>::KS> mlp64_obs_row(PRef P, const StepSmem<NB, EPB, NW>& sm, const int e,
+template <int NB, int EPB, int NW, bool SENS, bool IN_STEP, class PRef, bool POOL = false>
+__device__ __forceinline__ ObsRow<mlp64::Layout<NB + 6>::KS> mlp64_obs_row(PRef P, const StepSmem<NB, EPB, NW, POOL>& sm, const int e,
                                                                         const int kk, const int nloc, const bool half_rows,
                                                                         const float sigma, const int below_min) {
     using PL = mlp64::Layout<NB + 6>;
@@ -1760,8 +1871,8 @@ __device__ __forceinline__ int hist_src_col(const int f) { return f < 26 ? f - 1
 
 // Whether step t ends env e's episode, from the three values that are final at barrier B2: the predicate under which part 3 of
 // step_body writes `ended` (d || a || timeout there; next_obs_n evaluates the same three).
-template <int NB, int EPB, int NW, bool SENS, class PRef>
-__device__ __forceinline__ bool hist_step_ends(PRef P, const StepSmem<NB, EPB, NW>& sm, const int e) {
+template <int NB, int EPB, int NW, bool SENS, class PRef, bool POOL = false>
+__device__ __forceinline__ bool hist_step_ends(PRef P, const StepSmem<NB, EPB, NW, POOL>& sm, const int e) {
     const float mn = (SENS && sm.neg[e]) ? -INFINITY : __uint_as_float(sm.mn_bits[e]);
     const bool d = (0.2 > (double)mn) && ((double)mn > 0);                                        // environment_new.py:200
     const bool a = sm.sv_d[6][e] <= P.thr;                                                       // :204
@@ -1772,13 +1883,14 @@ __device__ __forceinline__ bool hist_step_ends(PRef P, const StepSmem<NB, EPB, N
 // Entry idx (0..11: the scan and past_action) of the row the step will leave for env e, behind barrier B2: next_obs_n's value for
 // one run-time column (`ends`: hist_step_ends).  With auto_reset the reset observation's entry -- its scan through THIS step's range
 // noise under SENS, past_action 0 -- else the row in sm.obs (which part 3 then leaves alone).
-template <int NB, int EPB, int NW, bool SENS, class PRef>
-__device__ __forceinline__ float hist_next_entry(PRef P, const StepSmem<NB, EPB, NW>& sm, const int e, const int idx, const bool ends,
+template <int NB, int EPB, int NW, bool SENS, class PRef, bool POOL = false>
+__device__ __forceinline__ float hist_next_entry(PRef P, const StepSmem<NB, EPB, NW, POOL>& sm, const int e, const int idx, const bool ends,
                                                  const float sigma, const int below_min) {
     constexpr int DP = NB + 7;
     if (!(ends && P.auto_reset)) return sm.obs[e * DP + idx];
     if (idx >= NB) return 0.f;                                                                   // environment_new.py:372-373
     const int c = ((sm.sv_d[6][e] <= P.thr) && P.respawn) ? 1 : 0;
+    if constexpr (POOL) return pool_reset_entry<NB, EPB, NW>(sm, c, e, idx, P.pool, sigma, below_min);
     float val = sm.sp_scan[c][e][idx];
     if (SENS) {
         float r = sensor_value(val, sigma, (sigma > 0.f) ? sm.noise[idx * EPB + e] : 0.f, below_min);
@@ -1791,8 +1903,8 @@ __device__ __forceinline__ float hist_next_entry(PRef P, const StepSmem<NB, EPB,
 // Columns 0..15 are mlp64_obs_row's of the 16-column policy (next_obs_n / sm.obs); columns 16..37 come from `hist`, or -- on a row
 // behind an ended step -- are copies of the row's own scan and past_action; 38..43 are 0.  Row 0 of the launch (!IN_STEP) reads
 // `hist` as it was filled: by hist_init with those same copies (the row starts an episode), or from the caller's carry.  Every value rounded to half when the buffers are (idempotent on what hist already holds).
-template <int NB, int EPB, int NW, bool SENS, bool IN_STEP, class PRef>
-__device__ __forceinline__ ObsRow<11> hist_obs_row(PRef P, const StepSmem<NB, EPB, NW>& sm, const float* hist, const int e, const int kk,
+template <int NB, int EPB, int NW, bool SENS, bool IN_STEP, class PRef, bool POOL = false>
+__device__ __forceinline__ ObsRow<11> hist_obs_row(PRef P, const StepSmem<NB, EPB, NW, POOL>& sm, const float* hist, const int e, const int kk,
                                                    const int nloc, const bool half_rows, const float sigma, const int below_min) {
     static_assert(NB == 10, "the history row stacks 10-beam scans");
     constexpr int KS = 11, D = NB + 6, DP = NB + 7;
@@ -1856,8 +1968,8 @@ __device__ __forceinline__ void hist_load(float* hist, const float* carry, const
 }
 // lane = env e, behind the policy of row 0 and in front of step 0: the carry of row 0 -> the block in front of step 0.  Row 0's own
 // scan and past_action come from the observation tile (float16 rows: the half values, as load_obs_tile widened them).
-template <int NB, int EPB, int NW>
-__device__ __forceinline__ void hist_enter(const StepSmem<NB, EPB, NW>& sm, float* hist, const int e) {
+template <int NB, int EPB, int NW, bool POOL = false>
+__device__ __forceinline__ void hist_enter(const StepSmem<NB, EPB, NW, POOL>& sm, float* hist, const int e) {
     constexpr int DP = NB + 7;
     float* h = hist + e * kHistStride;
     for (int c = 0; c < NB; ++c) {
@@ -1871,8 +1983,8 @@ __device__ __forceinline__ void hist_enter(const StepSmem<NB, EPB, NW>& sm, floa
 // observation tile holds the row the step left, the reset observation where it ended an episode): the carry of that row.  The
 // block IS its columns 16..37 unless the step ended the episode (`ended`: the flag this lane stored for the step); then they are
 // copies of the new row's own scan and past_action.  8 bytes per store (rows of 88 bytes in a 16-byte aligned buffer).
-template <int NB, int EPB, int NW>
-__device__ __forceinline__ void hist_leave(const StepSmem<NB, EPB, NW>& sm, float* hist, float* carry, const int base, const int e,
+template <int NB, int EPB, int NW, bool POOL = false>
+__device__ __forceinline__ void hist_leave(const StepSmem<NB, EPB, NW, POOL>& sm, float* hist, float* carry, const int base, const int e,
                                            const bool ended, const bool half_rows) {
     constexpr int DP = NB + 7;
     float* h = hist + e * kHistStride;
@@ -1891,8 +2003,8 @@ __device__ __forceinline__ void hist_leave(const StepSmem<NB, EPB, NW>& sm, floa
 // The shift, lane = env, by the wave that arrives last at the in-step policy (last_arrival: the four tile waves have read `hist`,
 // and the next read is behind barrier B2 of the next step, which no wave reaches before this wave has passed barrier C):
 // the row the step leaves becomes the previous row.  On a row that starts an episode both frames become its scan.
-template <int NB, int EPB, int NW, bool SENS, class PRef>
-__device__ __forceinline__ void hist_shift(PRef P, const StepSmem<NB, EPB, NW>& sm, float* hist, const int e, const bool half_rows,
+template <int NB, int EPB, int NW, bool SENS, class PRef, bool POOL = false>
+__device__ __forceinline__ void hist_shift(PRef P, const StepSmem<NB, EPB, NW, POOL>& sm, float* hist, const int e, const bool half_rows,
                                            const float sigma, const int below_min) {
     const bool ends = hist_step_ends<NB, EPB, NW, SENS, PRef>(P, sm, e);
     float* h = hist + e * kHistStride;
@@ -1963,8 +2075,8 @@ __host__ __device__ __forceinline__ StepIO rollout_io(const RolloutArgs& R, cons
 // HIST (navsim_rollout_mlp64_hist): the policy is the 42-64-64 one on the stacked row of the last three 10-beam scans (hist_obs_row;
 // `hist`: the workgroup's [16][kHistStride] LDS block); the env side and every buffer are those of the 16-column form.  Off, nothing
 // of it is compiled.
-template <int NB, int EPB, bool SENS, int NW, bool BOXES, bool MOV, bool HIST = false>
-__device__ __forceinline__ void rollout_body(const Params& P, const RolloutArgs& R, StepSmemFor<NB, EPB, NW, MOV>& sm, int& next_env,
+template <int NB, int EPB, bool SENS, int NW, bool BOXES, bool MOV, bool HIST = false, bool POOL = false>   // POOL: as in step_body
+__device__ __forceinline__ void rollout_body(const Params& P, const RolloutArgs& R, StepSmemFor<NB, EPB, NW, MOV, POOL>& sm, int& next_env,
                                              float* const wts, float2 (&pol_z)[4][16], float2 (&pol_eps)[16], unsigned& pol_cnt,
                                              [[maybe_unused]] float* const hist = nullptr) {
     constexpr int D = NB + 6, kThreads = 64 * NW;
@@ -2069,8 +2181,8 @@ __device__ __forceinline__ void rollout_body(const Params& P, const RolloutArgs&
                 });
             }
         };
-        step_body<NB, EPB, SENS, true, NW, BOXES, 0, const Params&, const StepIO&, decltype(hook), MOV>(P, sm, next_env, io,
-                                                                                                      t == R.T - 1, 0, hook);
+        step_body<NB, EPB, SENS, true, NW, BOXES, 0, const Params&, const StepIO&, decltype(hook), MOV, POOL>(P, sm, next_env, io,
+                                                                                                            t == R.T - 1, 0, hook);
         // the observation tile of step t + 1 is in sm.obs (its store only reads it), its action in sm.act_l
     }
     if constexpr (HIST) {   // the carry of row T, by the lanes that wrote the last step's flags (wave 0, lane = env)
@@ -2211,6 +2323,7 @@ __global__ __launch_bounds__(64 * 8) void rollout_resmlp_kernel(Params P, Rollou
     __shared__ float2 pol_eps[EPB];   // the action noise of the next policy step (drawn inside the env step in front of it)
     rollout_resmlp_body<SENS, false>(P, R, sm, next_env, ps, bs, pol_eps);
 }
+#ifndef NAVSIM_POOL_TU   // (a kernel that is no template: not compiled a second time in the sector-LiDAR twins' translation unit)
 __global__ __launch_bounds__(64 * 8) void rollout_resmlp_mov_kernel(Params P, RolloutArgs R) {
     __shared__ StepSmemMov<10, 16, 8> sm;
     __shared__ int next_env;
@@ -2219,6 +2332,7 @@ __global__ __launch_bounds__(64 * 8) void rollout_resmlp_mov_kernel(Params P, Ro
     __shared__ float2 pol_eps[16];
     rollout_resmlp_body<kMovSens, true>(P, R, sm, next_env, ps, bs, pol_eps);
 }
+#endif   // NAVSIM_POOL_TU
 
 // ---------------------------------------------------------------- the evaluation form of the two persistent rollouts
 // main.evaluate (main.py:135-252) in ONE launch: rollout_kernel's / rollout_resmlp_kernel's workgroup (16 envs on 8 waves, env
@@ -2256,8 +2370,8 @@ __device__ __forceinline__ bool eval_quota_met(const int* ep_cnt, const int lane
     return __builtin_amdgcn_ballot_w64(ep_cnt[lane & (EPB - 1)] < quota) == 0ull;
 }
 
-template <int NB, bool SENS, bool BOXES, bool MOV, bool HIST = false>   // HIST: as in rollout_body (navsim_evaluate_mlp64_hist)
-__device__ __forceinline__ void evaluate_body(const Params& P, const EvalArgs& R, StepSmemFor<NB, 16, 8, MOV>& sm, int& next_env,
+template <int NB, bool SENS, bool BOXES, bool MOV, bool HIST = false, bool POOL = false>   // HIST: as in rollout_body (navsim_evaluate_mlp64_hist)
+__device__ __forceinline__ void evaluate_body(const Params& P, const EvalArgs& R, StepSmemFor<NB, 16, 8, MOV, POOL>& sm, int& next_env,
                                               float* const wts, float2 (&pol_z)[4][16], unsigned& pol_cnt, int (&ep_cnt)[16],
                                               [[maybe_unused]] float* const hist = nullptr) {
     constexpr int EPB = 16, NW = 8, D = NB + 6, kThreads = 64 * NW;
@@ -2330,7 +2444,7 @@ __device__ __forceinline__ void evaluate_body(const Params& P, const EvalArgs& R
                 });
             }
         };
-        step_body<NB, EPB, SENS, true, NW, BOXES, 0, const Params&, const EvalIO&, decltype(hook), MOV>(P, sm, next_env, io, false, 0, hook);
+        step_body<NB, EPB, SENS, true, NW, BOXES, 0, const Params&, const EvalIO&, decltype(hook), MOV, POOL>(P, sm, next_env, io, false, 0, hook);
         n_done = t + 1;
         if (eval_quota_met<EPB>(ep_cnt, lane, R.quota)) break;   // behind barrier C: workgroup-uniform (see above)
     }
@@ -2460,6 +2574,7 @@ __global__ __launch_bounds__(64 * 8) void evaluate_resmlp_kernel(Params P, EvalA
     __shared__ int ep_cnt[EPB];       // episodes recorded per env
     evaluate_resmlp_body<SENS, false>(P, R, sm, next_env, ps, bs, ep_cnt);
 }
+#ifndef NAVSIM_POOL_TU
 __global__ __launch_bounds__(64 * 8) void evaluate_resmlp_mov_kernel(Params P, EvalArgs R) {
     __shared__ StepSmemMov<10, 16, 8> sm;
     __shared__ int next_env;
@@ -2468,6 +2583,7 @@ __global__ __launch_bounds__(64 * 8) void evaluate_resmlp_mov_kernel(Params P, E
     __shared__ int ep_cnt[16];
     evaluate_resmlp_body<kMovSens, true>(P, R, sm, next_env, ps, bs, ep_cnt);
 }
+#endif   // NAVSIM_POOL_TU
 
 // ---------------------------------------------------------------- n steps of an action tape in ONE launch (navsim_step_seq)
 // The step loop of PPO.rollout / the evaluation loop (ppo.py:505-594, main.py:176-235) when the actions are already known -- a
@@ -2492,8 +2608,8 @@ typedef const SeqKArgs __attribute__((address_space(4))) * SeqKArgsPtr;
 
 static_assert(std::is_trivially_copyable<SeqKArgs>::value && offsetof(SeqKArgs, P) == 0, "kernarg mirror of steps_kernel");
 
-template <int NB, int EPB, bool SENS, int NW, bool BOXES, int PAIR, bool MOV>
-__device__ __forceinline__ void steps_body(StepSmemFor<NB, EPB, NW, MOV>& sm, int& next_env) {
+template <int NB, int EPB, bool SENS, int NW, bool BOXES, int PAIR, bool MOV, bool POOL = false>
+__device__ __forceinline__ void steps_body(StepSmemFor<NB, EPB, NW, MOV, POOL>& sm, int& next_env) {
     // parameters through the kernarg segment pointer, as in step_kernel (scalar loads at each use, no spilled SGPRs)
     SeqKArgsPtr A = (SeqKArgsPtr)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(A));
@@ -2520,7 +2636,7 @@ __device__ __forceinline__ void steps_body(StepSmemFor<NB, EPB, NW, MOV>& sm, in
             if (t + 1 < T) a_next = R.io.action[tn + N + base + tid];   // lands under this step
         }
         __syncthreads();
-        step_body<NB, EPB, SENS, true, NW, BOXES, PAIR, PRef, const StepIO __attribute__((address_space(4)))&, NoHook, MOV>(
+        step_body<NB, EPB, SENS, true, NW, BOXES, PAIR, PRef, const StepIO __attribute__((address_space(4)))&, NoHook, MOV, POOL>(
             P, sm, next_env, R.io, t == T - 1, tn);
     }
 }
@@ -2690,6 +2806,8 @@ __global__ __launch_bounds__(64 * NW) void rollout_big_mov_kernel(BigKArgs) {
     rollout_big_body<EPB, SENS, NW, BOXES, 0, true>();
 }
 
+#ifndef NAVSIM_POOL_TU   // (down to the end of the file: the small kernels, the scans and the host side / C ABI are navsim.hip's own;
+                         // navsim_pool.hip compiles the step body and what stands around it, above, a second time)
 // Env.getOdometry (environment_new.py:138-181) for n independent (position, orientation quaternion, goal) triples
 __global__ void odometry_kernel(int n, const double* __restrict__ px, const double* __restrict__ py, const double* __restrict__ q,
                                 const double* __restrict__ goal, double* __restrict__ out) {
@@ -3069,12 +3187,16 @@ __global__ void gae_trunc_kernel_generic(const float* __restrict__ rew, const ui
     }
 }
 
+#endif   // NAVSIM_POOL_TU
 }  // namespace
 
+#ifndef NAVSIM_POOL_TU
 // ==================================================================== host side / C ABI
 #include "navsim_select.h"   // which instantiation runs for a handle: the rule, its thresholds and the measurements behind them
+#include "navsim_pool.h"     // the sector-LiDAR twins: kernels of a translation unit of their own (navsim_pool.hip)
 namespace sel = navsim_select;
 static_assert(kMovSens == sel::kMovTwinsSens, "the 16-env mover twins are built in the form the rule picks");
+static_assert(kMaxPool == sel::kMaxScanPool, "the pooled twins hold the rays of the largest scan_pool the rule admits");
 
 // A hipMalloc allocation and its owner (move-only): freed by reset(), by the next alloc() and with the owner
 template <class T>
@@ -3121,12 +3243,29 @@ struct navsim {
     int force_epb = 0;
     bool pair_cast = true;
     int pair_cast_request = -1;   // what navsim_set_shape was given (-1 = the rule): reported by navsim_get_info
+    // sector LiDAR (navsim_set_scan_pool): rays per scan column, mirrored in P.pool; the pooled twins are mover kernels, and a handle
+    // without a tape hands them this one-row tape of one absent (NaN) segment (launch_params)
+    int scan_pool = 1;
+    DevBuf<float4> pool_tape_dev;
 };
+
+// The parameter block a stepping launch passes: the handle's, and on a pooled handle without movers the one-row tape of one absent
+// segment (period 1, no phase offsets), which the cull of the mover pass drops -- the scan is that of the static map alone.
+static Params launch_params(const navsim* h) {
+    Params P = h->P;
+    if (h->scan_pool > 1 && !P.mov_tape) {
+        P.mov_tape = h->pool_tape_dev.get();
+        P.mov_P = 1;
+        P.mov_M = 1;
+        P.mov_pack_log2 = 0;
+    }
+    return P;
+}
 
 // What entry point `e` launches for this handle (navsim_select.h holds the rule)
 static sel::Pick pick_for(const navsim* h, sel::Entry e) {
     return sel::pick(e, sel::Facts{h->P.N, h->P.B, h->P.S, (h->P.per_env & 1) != 0, h->P.mov_tape != nullptr,
-                                   sel::sens_on(h->P.sigma, h->P.below_min_mode), h->force_epb, h->pair_cast});
+                                   sel::sens_on(h->P.sigma, h->P.below_min_mode), h->force_epb, h->pair_cast, h->scan_pool});
 }
 
 // ---- pick -> kernel.  One resolve function per kernel signature: it spells out the instantiations that are built and answers null
@@ -3138,11 +3277,13 @@ struct StepK {
     using Fn = void (*)(StepKArgs);
     template <int NB, int EPB, bool S, int NW, bool BX, int PAIR> static Fn of() { return step_kernel<NB, EPB, S, NW, BX, PAIR>; }
     template <bool BX> static Fn mov() { return step_mov_kernel<BX>; }
+    static Fn pool(bool bx) { return reinterpret_cast<Fn>(const_cast<void*>(navsim_pool::resolve(navsim_pool::kStep, bx))); }
 };
 struct SeqK {
     using Fn = void (*)(SeqKArgs);
     template <int NB, int EPB, bool S, int NW, bool BX, int PAIR> static Fn of() { return steps_kernel<NB, EPB, S, NW, BX, PAIR>; }
     template <bool BX> static Fn mov() { return steps_mov_kernel<BX>; }
+    static Fn pool(bool bx) { return reinterpret_cast<Fn>(const_cast<void*>(navsim_pool::resolve(navsim_pool::kSteps, bx))); }
 };
 // the cast variants of one shape: tile boxes, 64-segment passes, 128-segment passes and (the big 10-beam shapes) their streaming form
 template <class K, int NB, int EPB, int NW, bool S>
@@ -3166,6 +3307,8 @@ static typename K::Fn step_shape(const sel::Pick& p) {
 template <class K>   // K: StepK (navsim_step) | SeqK (navsim_step_seq)
 static typename K::Fn resolve_step(const sel::Pick& p) {
     if (p.family != sel::kSmall || p.hist || sel::policy_of(p.entry) >= 0) return nullptr;
+    if (p.pool > 1)   // the pooled twin: 10 columns, 16 envs on 8 waves, a shared map
+        return (p.beams == 10 && p.epb == 16 && p.waves == 8 && (p.cast == 0 || p.cast == 3)) ? K::pool(p.cast == 3) : nullptr;
     if (p.mov)   // 10 beams, 16 envs on 8 waves, a shared map
         return !(p.beams == 10 && p.epb == 16 && p.waves == 8 && p.sens == kMovSens) ? nullptr
                : p.cast == 3 ? K::template mov<true>() : p.cast == 0 ? K::template mov<false>() : nullptr;
@@ -3185,6 +3328,9 @@ struct RolloutK {
     template <bool BX> static Fn hist_mov() { return rollout_hist_mov_kernel<BX>; }
     template <bool S> static Fn resmlp() { return rollout_resmlp_kernel<S>; }
     static Fn resmlp_mov() { return rollout_resmlp_mov_kernel; }
+    static Fn pool(bool hist, bool bx) {
+        return reinterpret_cast<Fn>(const_cast<void*>(navsim_pool::resolve(hist ? navsim_pool::kRolloutHist : navsim_pool::kRollout, bx)));
+    }
 };
 struct EvalK {
     using Fn = void (*)(Params, EvalArgs);
@@ -3195,6 +3341,9 @@ struct EvalK {
     template <bool BX> static Fn hist_mov() { return evaluate_hist_mov_kernel<BX>; }
     template <bool S> static Fn resmlp() { return evaluate_resmlp_kernel<S>; }
     static Fn resmlp_mov() { return evaluate_resmlp_mov_kernel; }
+    static Fn pool(bool hist, bool bx) {
+        return reinterpret_cast<Fn>(const_cast<void*>(navsim_pool::resolve(hist ? navsim_pool::kEvaluateHist : navsim_pool::kEvaluate, bx)));
+    }
 };
 template <class K, bool S, bool BX>
 static typename K::Fn policy_fn(const sel::Pick& p) {   // the mover twins: 10 beams, one form whatever S says (kMovSens)
@@ -3211,6 +3360,7 @@ static typename K::Fn resolve_policy(const sel::Pick& p) {
     const bool BX = p.cast == 3, S = p.sens;
     if (pol < 0 || K::kEval != (p.entry >= sel::kEvaluateMlp64) || p.family != sel::kSmall || p.hist != (pol == 1)) return nullptr;
     if (p.waves != 8 || (p.cast != 0 && !BX)) return nullptr;
+    if (p.pool > 1) return (p.beams == 10 && p.epb == 16 && pol != 2) ? K::pool(pol == 1, BX) : nullptr;
     if (p.mov ? !(p.beams == 10 && S == kMovSens) : !(p.beams == 10 || (p.beams == 36 && pol == 0))) return nullptr;
     if constexpr (!K::kEval)
         if ((p.epb == 4 || p.epb == 8) && pol == 0 && p.beams == 10 && !p.mov && !BX)
@@ -3239,7 +3389,7 @@ static BigFn big_fn(const sel::Pick& p) {
     return p.cast == 0 ? rollout_big_kernel<64, S, 16, false, 0> : nullptr;
 }
 static BigFn resolve_big(const sel::Pick& p) {
-    if (p.family != sel::kBig || p.entry != sel::kRolloutMlp64 || p.beams != 10 || p.hist) return nullptr;
+    if (p.family != sel::kBig || p.entry != sel::kRolloutMlp64 || p.beams != 10 || p.hist || p.pool > 1) return nullptr;
     return p.sens ? big_fn<true>(p) : big_fn<false>(p);
 }
 
@@ -3250,8 +3400,8 @@ static int launch(const char* who, const sel::Pick& p, void (*kernel)(A...), con
     if (p.not_built) return fail(NAVSIM_E_STATE, std::string(who) + ": " + p.not_built);
     if (!kernel) {
         char s[160];
-        std::snprintf(s, sizeof(s), ": no kernel is built for the pick {%s family, %d beams, %d envs on %d waves, cast %d, sens %d, mov %d, hist %d}",
-                      p.family == sel::kBig ? "big" : "small", p.beams, p.epb, p.waves, p.cast, (int)p.sens, (int)p.mov, (int)p.hist);
+        std::snprintf(s, sizeof(s), ": no kernel is built for the pick {%s family, %d beams, %d envs on %d waves, cast %d, sens %d, mov %d, hist %d, pool %d}",
+                      p.family == sel::kBig ? "big" : "small", p.beams, p.epb, p.waves, p.cast, (int)p.sens, (int)p.mov, (int)p.hist, p.pool);
         return fail(NAVSIM_E_STATE, std::string(who) + s);
     }
     hipLaunchKernelGGL(kernel, dim3((n_envs + p.epb - 1) / p.epb), dim3(64 * p.waves), 0, st, args...);
@@ -3277,6 +3427,21 @@ static int upload_starts(navsim* h, const double* starts_host, int K, hipStream_
     h->P.starts = h->starts_dev.get();
     h->P.starts_sc = h->starts_sc_dev.get();
     h->P.K = K;
+    return NAVSIM_OK;
+}
+
+// beam table: n samples evenly over [min_angle, max_angle] (gazebo.xacro:110-115); n = n_beams, or n_beams * scan_pool: the dense
+// fan of a pooled handle IS the table of a handle with that many beams
+static int upload_beam_table(navsim* h, const int n) {
+    double cs[2 * 64];
+    for (int i = 0; i < n; ++i) {
+        const double phi = kAngleMin + (double)i * ((kAngleMax - kAngleMin) / (double)(n - 1));
+        cs[i] = std::cos(phi);
+        cs[n + i] = std::sin(phi);
+    }
+    HIP_TRY(h->beam_cs_dev.alloc(2 * (size_t)n));
+    HIP_TRY(hipMemcpy(h->beam_cs_dev.get(), cs, sizeof(double) * 2 * n, hipMemcpyHostToDevice));
+    h->P.beam_cs = h->beam_cs_dev.get();
     return NAVSIM_OK;
 }
 
@@ -3324,16 +3489,11 @@ static int init_handle(navsim* h, const navsim_cfg* cfg) {
     P.goal_lo = cfg->goal_lo; P.goal_hi = cfg->goal_hi;
     P.diag = std::sqrt(2.0) * (3.8 + 3.8);  // environment_new.py:21
 
-    // beam table: samples evenly over [min_angle, max_angle] (gazebo.xacro:110-115)
-    double cs[2 * 64];
-    for (int i = 0; i < B; ++i) {
-        const double phi = kAngleMin + (double)i * ((kAngleMax - kAngleMin) / (double)(B - 1));
-        cs[i] = std::cos(phi);
-        cs[B + i] = std::sin(phi);
+    P.pool = 1;
+    {
+        const int rc = upload_beam_table(h, B);
+        if (rc != NAVSIM_OK) return rc;
     }
-    HIP_TRY(h->beam_cs_dev.alloc(2 * (size_t)B));
-    HIP_TRY(hipMemcpy(h->beam_cs_dev.get(), cs, sizeof(double) * 2 * B, hipMemcpyHostToDevice));
-    P.beam_cs = h->beam_cs_dev.get();
 
     std::memset(&h->rects_host, 0, sizeof(Rects));
     std::memcpy(h->rects_host.r[0], kResetRects, sizeof(kResetRects));
@@ -3353,6 +3513,8 @@ static int init_handle(navsim* h, const navsim_cfg* cfg) {
     }
     return NAVSIM_OK;
 }
+
+static int rebuild_spawn_scans(navsim* h, hipStream_t st);   // (below, with navsim_set_map)
 
 #pragma GCC visibility push(default)
 extern "C" {
@@ -3406,6 +3568,43 @@ int navsim_set_shape(navsim_t* h, int32_t envs_per_workgroup, int32_t pair_cast)
     return NAVSIM_OK;
 }
 
+int navsim_set_scan_pool(navsim_t* h, int32_t k) {
+    if (!h) return fail(NAVSIM_E_ARG, "navsim_set_scan_pool: null handle");
+    if (k < 1 || k > sel::kMaxScanPool)
+        return fail(NAVSIM_E_ARG, "navsim_set_scan_pool: scan_pool must be 1, 2, 3 or 4 (more than 4 rays per column is not built)");
+    if (k > 1)
+        if (const char* why = sel::scan_pool_not_built(h->P.B, (h->P.per_env & 1) != 0))
+            return fail(NAVSIM_E_ARG, std::string("navsim_set_scan_pool: ") + why);
+    HIP_TRY(hipDeviceSynchronize());   // launches in flight read the old beam table / spawn scans
+    if (k > 1 && !h->pool_tape_dev.get()) {
+        const float nan4[4] = {NAN, NAN, NAN, NAN};
+        HIP_TRY(h->pool_tape_dev.alloc(1));
+        HIP_TRY(hipMemcpy(h->pool_tape_dev.get(), nan4, sizeof(nan4), hipMemcpyHostToDevice));
+    }
+    // k, the beam table and the spawn rows change together: a step that fails puts the old k back with its tables, so that no launch
+    // ever reads rows of another stride than its k
+    auto apply = [h](const int kk) -> int {
+        h->scan_pool = kk;
+        h->P.pool = kk;
+        const int rc = upload_beam_table(h, h->P.B * kk);   // the dense fan (k = 1: the table of a fresh handle)
+        if (rc != NAVSIM_OK) return rc;
+        if (h->has_map) {   // the cached spawn scans: the raw hits of the new fan
+            const int rs = rebuild_spawn_scans(h, nullptr);
+            if (rs != NAVSIM_OK) return rs;
+            HIP_TRY(hipDeviceSynchronize());
+        }
+        return NAVSIM_OK;
+    };
+    const int old = h->scan_pool;
+    const int rc = apply(k);
+    if (rc != NAVSIM_OK && old != k) {
+        const std::string why = g_err;
+        (void)apply(old);
+        g_err = why;
+    }
+    return rc;
+}
+
 int navsim_get_info(navsim_t* h, navsim_info* out) {
     if (!h || !out) return fail(NAVSIM_E_ARG, "navsim_get_info: null argument");
     std::memset(out, 0, sizeof(*out));
@@ -3414,6 +3613,7 @@ int navsim_get_info(navsim_t* h, navsim_info* out) {
     out->n_segments = h->P.S; out->per_env_map = h->P.per_env & 1; out->tile_boxes = h->P.tile_box != nullptr;
     out->has_map = h->has_map;
     out->forced_epb = h->force_epb; out->forced_pair_cast = h->pair_cast_request;
+    out->reserved[0] = h->scan_pool;
     if (h->has_map) {
         const sel::Pick a = pick_for(h, sel::kStep), b = pick_for(h, sel::kStepSeq), r = pick_for(h, sel::kRolloutMlp64);
         out->step_epb = a.epb; out->step_waves = a.waves; out->step_cast = a.cast;
@@ -3446,23 +3646,35 @@ int navsim_set_goal_rects(navsim_t* h, int32_t which, const double* rects_host, 
     return NAVSIM_OK;
 }
 
+// the pooled handle's reset / ray-cast kernels (navsim_pool.hip), under the signatures of reset_kernel / raycast_kernel
+using ResetFn = void (*)(Params, const uint8_t*, void*);
+using RaycastFn = void (*)(Params, const double*, int, int, int, int, float*);
+static ResetFn pool_reset_kernel() { return reinterpret_cast<ResetFn>(const_cast<void*>(navsim_pool::resolve(navsim_pool::kReset, false))); }
+static RaycastFn pool_raycast_kernel() { return reinterpret_cast<RaycastFn>(const_cast<void*>(navsim_pool::resolve(navsim_pool::kRaycast, false))); }
+
 static int rebuild_spawn_scans(navsim* h, hipStream_t st) {
     Params& P = h->P;
     P.spawn_per_env = (P.per_env || (P.mov_tape && (P.mov_phase0 || P.mov_bp))) ? 1 : 0;   // movers with phase offsets or tape ids: every env resets into its own row
     const size_t n_poses = (size_t)(P.spawn_per_env ? P.N : 1) * P.K;
+    const size_t n_rays = (size_t)P.B * (size_t)P.pool;   // entries of a row: on a pooled handle the raw hits of the dense fan
     if (h->spawn_scan_dev.get()) {
         HIP_TRY(hipStreamSynchronize(st));
         HIP_TRY(h->spawn_scan_dev.reset());
         HIP_TRY(h->spawn_obs_dev.reset());
     }
-    HIP_TRY(h->spawn_scan_dev.alloc(n_poses * P.B));
-    HIP_TRY(h->spawn_obs_dev.alloc(n_poses * P.B));
+    HIP_TRY(h->spawn_scan_dev.alloc(n_poses * n_rays));
     P.spawn_scan = h->spawn_scan_dev.get();
-    P.spawn_obs = h->spawn_obs_dev.get();
-    hipLaunchKernelGGL(raycast_kernel, dim3((unsigned)((n_poses + 63) / 64)), dim3(64), 0, st, P, h->starts_dev.get(), P.K, 1,
-                       (int)n_poses, 1, h->spawn_scan_dev.get());
-    hipLaunchKernelGGL(spawn_obs_kernel, dim3((unsigned)((n_poses * P.B + 255) / 256)), dim3(256), 0, st, h->spawn_scan_dev.get(),
-                       (int)(n_poses * P.B), P.below_min_mode, h->spawn_obs_dev.get());
+    P.spawn_obs = nullptr;
+    if (P.pool == 1) {   // (the pooled twins are sensor-options kernels: they read the raw hits, never the noise-free entries)
+        HIP_TRY(h->spawn_obs_dev.alloc(n_poses * n_rays));
+        P.spawn_obs = h->spawn_obs_dev.get();
+    }
+    const RaycastFn cast = P.pool > 1 ? pool_raycast_kernel() : raycast_kernel;
+    hipLaunchKernelGGL(cast, dim3((unsigned)((n_poses + 63) / 64)), dim3(64), 0, st, P, h->starts_dev.get(), P.K, 1, (int)n_poses, 1,
+                       h->spawn_scan_dev.get());
+    if (P.pool == 1)
+        hipLaunchKernelGGL(spawn_obs_kernel, dim3((unsigned)((n_poses * n_rays + 255) / 256)), dim3(256), 0, st, h->spawn_scan_dev.get(),
+                           (int)(n_poses * n_rays), P.below_min_mode, h->spawn_obs_dev.get());
     HIP_TRY(hipGetLastError());
     return NAVSIM_OK;
 }
@@ -3471,6 +3683,8 @@ int navsim_set_map(navsim_t* h, const float* seg_dev, int32_t n_segments, int32_
     if (!h || !seg_dev || n_segments < 1) return fail(NAVSIM_E_ARG, "navsim_set_map: bad argument");
     if (h->P.mov_tape && per_env)
         return fail(NAVSIM_E_ARG, "navsim_set_map: movers are set and " + std::string(sel::kMoversNotBuilt));
+    if (h->scan_pool > 1 && per_env)
+        return fail(NAVSIM_E_ARG, "navsim_set_map: scan_pool is set and " + std::string(sel::kPoolPerEnvNotBuilt));
     Params& P = h->P;
     P.seg = reinterpret_cast<const float4*>(seg_dev);
     P.S = n_segments;
@@ -3687,8 +3901,8 @@ int navsim_set_spawn_sampler(navsim_t* h, const double* starts_host, int32_t n_s
 int navsim_reset(navsim_t* h, const uint8_t* mask_dev, void* obs_dev, void* stream) {
     if (!h || !obs_dev) return fail(NAVSIM_E_ARG, "navsim_reset: bad argument");
     if (!h->has_map) return fail(NAVSIM_E_STATE, "navsim_reset: call navsim_set_map first");
-    hipLaunchKernelGGL(reset_kernel, dim3((h->P.N + 63) / 64), dim3(64), 0, (hipStream_t)stream, h->P, mask_dev,
-                       obs_dev);
+    const ResetFn reset = h->scan_pool > 1 ? pool_reset_kernel() : reset_kernel;
+    hipLaunchKernelGGL(reset, dim3((h->P.N + 63) / 64), dim3(64), 0, (hipStream_t)stream, h->P, mask_dev, obs_dev);
     HIP_TRY(hipGetLastError());
     return NAVSIM_OK;
 }
@@ -3699,7 +3913,7 @@ int navsim_step(navsim_t* h, const float* action_dev, const float* past_action_d
     if (!h || !action_dev || !obs_dev || !reward_dev || !done_dev || !arrive_dev)
         return fail(NAVSIM_E_ARG, "navsim_step: null required buffer");
     if (!h->has_map) return fail(NAVSIM_E_STATE, "navsim_step: call navsim_set_map first");
-    const StepKArgs ka = {h->P, StepIO{(const float2*)action_dev, (const float2*)past_action_dev, obs_dev, reward_dev, done_dev,
+    const StepKArgs ka = {launch_params(h), StepIO{(const float2*)action_dev, (const float2*)past_action_dev, obs_dev, reward_dev, done_dev,
                                        arrive_dev, ended_dev, ep_return_dev, ep_length_dev, ep_path_dev}};
     const sel::Pick p = pick_for(h, sel::kStep);
     return launch("navsim_step", p, resolve_step<StepK>(p), h->P.N, (hipStream_t)stream, ka);
@@ -3729,7 +3943,7 @@ static int rollout_entry(const sel::Entry e, const char* fn, const navsim* h, co
         const BigKArgs ka = {h->P, R, rollout_io(R, (size_t)h->P.N, (size_t)h->P.B + 6, 0, h->P.obs_f16 != 0)};
         return launch(fn, p, resolve_big(p), h->P.N, (hipStream_t)stream, ka);
     }
-    return launch(fn, p, resolve_policy<RolloutK>(p), h->P.N, (hipStream_t)stream, h->P, R);
+    return launch(fn, p, resolve_policy<RolloutK>(p), h->P.N, (hipStream_t)stream, launch_params(h), R);
 }
 
 int navsim_rollout_mlp64(navsim_t* h, const float* actor_params_dev, void* obs_buf_dev, float* act_buf_dev,
@@ -3789,7 +4003,7 @@ static int evaluate_entry(const sel::Entry e, const char* fn, const navsim* h, c
     if (!h->has_map) return fail(NAVSIM_E_STATE, f + "call navsim_set_map first");
     const EvalArgs R = {params, obs0, flags, length, ret, path, count, steps, quota, n_steps};
     const sel::Pick p = pick_for(h, e);
-    return launch(fn, p, resolve_policy<EvalK>(p), h->P.N, (hipStream_t)stream, h->P, R);
+    return launch(fn, p, resolve_policy<EvalK>(p), h->P.N, (hipStream_t)stream, launch_params(h), R);
 }
 
 int navsim_evaluate_mlp64(navsim_t* h, const float* actor_params_dev, const void* obs0_dev, int32_t quota, int32_t n_steps,
@@ -3825,7 +4039,7 @@ int navsim_step_seq(navsim_t* h, const float* actions_dev, int32_t n_steps, void
     R.io = StepIO{reinterpret_cast<const float2*>(actions_dev), nullptr, obs_dev, reward_dev, done_dev, arrive_dev, ended_dev,
                   ep_return_dev, ep_length_dev, ep_path_dev};
     R.T = n_steps;
-    const SeqKArgs ka = {h->P, R};
+    const SeqKArgs ka = {launch_params(h), R};
     const sel::Pick p = pick_for(h, sel::kStepSeq);
     return launch("navsim_step_seq", p, resolve_step<SeqK>(p), h->P.N, (hipStream_t)stream, ka);
 }
@@ -3844,8 +4058,8 @@ int navsim_odometry(int32_t n, const double* x_dev, const double* y_dev, const d
 int navsim_raycast(navsim_t* h, const double* pose_dev, float* ranges_dev, void* stream) {
     if (!h || !pose_dev || !ranges_dev) return fail(NAVSIM_E_ARG, "navsim_raycast: bad argument");
     if (!h->has_map) return fail(NAVSIM_E_STATE, "navsim_raycast: call navsim_set_map first");
-    hipLaunchKernelGGL(raycast_kernel, dim3((h->P.N + 63) / 64), dim3(64), 0, (hipStream_t)stream, h->P, pose_dev, 1, 0,
-                       h->P.N, 0, ranges_dev);
+    const RaycastFn cast = h->scan_pool > 1 ? pool_raycast_kernel() : raycast_kernel;
+    hipLaunchKernelGGL(cast, dim3((h->P.N + 63) / 64), dim3(64), 0, (hipStream_t)stream, h->P, pose_dev, 1, 0, h->P.N, 0, ranges_dev);
     HIP_TRY(hipGetLastError());
     return NAVSIM_OK;
 }
@@ -4016,3 +4230,4 @@ int navsim_stack_rows_cont(const void* obs_dev, int32_t obs_f16, const uint8_t* 
 
 }  // extern "C"
 #pragma GCC visibility pop
+#endif   // NAVSIM_POOL_TU

@@ -39,6 +39,7 @@ struct Facts {
     bool sens;        // sens_on()
     int force_epb;    // navsim_set_shape: envs per workgroup, 0 = the rule of pick_epb
     bool pair_cast;   // navsim_set_shape: false = 64-segment passes for every map
+    int scan_pool = 1;   // navsim_set_scan_pool: rays per scan column (sector LiDAR); 1 = off
 };
 
 // The SENS flag of a handle's instantiations: the sensor-fidelity options (range noise, -inf below range_min) are on
@@ -54,6 +55,18 @@ constexpr bool kMovTwinsSens = true;
 constexpr const char* kMoversNotBuilt =
     "movers need 10 beams and a shared static map: movers with 36 beams or with a per-env static map are not built";
 inline const char* movers_not_built(int n_beams, bool per_env) { return (n_beams != 10 || per_env) ? kMoversNotBuilt : nullptr; }
+
+// Sector LiDAR (navsim_set_scan_pool, k > 1): the pooled twins of navsim_pool.hip exist in ONE form -- 10 scan columns, 16 envs on 8
+// waves, a shared static map, the mover and sensor-options code compiled in (a handle without a tape or without the options runs it
+// and gets the same bits), 64-segment passes or tile boxes -- for navsim_step, navsim_step_seq and the two mlp64 policies' rollouts and
+// evaluations.  The sentences of the refusals; the same stand in include/navsim.h.
+constexpr int kMaxScanPool = 4;
+constexpr const char* kPoolBeamsNotBuilt = "scan_pool > 1 needs n_beams == 10: pooling a 36-beam scan is not built";
+constexpr const char* kPoolPerEnvNotBuilt = "scan_pool > 1 needs a shared static map: pooling over per-env maps is not built";
+constexpr const char* kPoolResmlpNotBuilt = "scan_pool > 1 with the 512-wide nets is not built (the pooled twins carry the mlp64 policies)";
+inline const char* scan_pool_not_built(int n_beams, bool per_env) {
+    return n_beams != 10 ? kPoolBeamsNotBuilt : per_env ? kPoolPerEnvNotBuilt : nullptr;
+}
 
 // The stepping entry points of the C ABI (policy_of() reads the order: step, step_seq, then the three policies twice)
 enum Entry {
@@ -128,6 +141,7 @@ struct Pick {
     Family family;
     int beams, epb, waves, cast;
     bool sens, mov, hist;   // the SENS, MOV and HIST template flags
+    int pool = 1;           // > 1: the pooled twin (navsim_pool.hip) casts 10 * pool rays; sens and mov are then its one form's (true)
 };
 
 // The instantiation navsim_step (tape = false) / navsim_step_seq (tape = true) launches for this handle: envs and waves per
@@ -188,6 +202,15 @@ inline Pick pick(Entry e, const Facts& f) {
     if ((p.not_built = beams_not_built(e, f.n_beams))) return p;
     if (f.movers && (p.not_built = movers_not_built(f.n_beams, f.per_env))) return p;
     const MapFacts m = map_facts(f.n_envs, f.n_segments, f.per_env);
+    if (f.scan_pool > 1) {
+        // the one pooled shape at every shard size and whatever navsim_set_shape says: beyond 4096 envs the workgroups run in rounds
+        p.pool = f.scan_pool;
+        if ((p.not_built = scan_pool_not_built(f.n_beams, f.per_env))) return p;
+        if (policy_of(e) == 2) p.not_built = kPoolResmlpNotBuilt;
+        p.epb = 16; p.waves = 8; p.cast = m.tile_boxes ? 3 : 0;
+        p.sens = true; p.mov = true;
+        return p;
+    }
     if (e == kStep || e == kStepSeq) pick_shape(f, m, e == kStepSeq, p);
     else if (e == kRolloutMlp64) pick_rollout(f, m, p);
     else {

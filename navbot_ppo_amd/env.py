@@ -21,7 +21,8 @@ from . import maps as _maps
 from ._native import NavsimCfg, NavsimError, NavsimInfo, check, lib
 
 __all__ = ["NavSim", "VecEnv", "Env", "NavsimError", "rtg_scan", "gae_scan", "gae_scan_trunc", "truncated_returns_reference",
-           "stack_rows", "stack_rows_reference", "HistoryWindow", "HostHistoryWindow", "HIST_DIM", "HIST_CARRY"]
+           "stack_rows", "stack_rows_reference", "HistoryWindow", "HostHistoryWindow", "HIST_DIM", "HIST_CARRY",
+           "pool_scan_reference", "check_scan_pool", "MAX_SCAN_POOL"]
 
 HIST_DIM = 42   # columns of a scan-history row (navsim_stack_rows)
 HIST_CARRY = 22   # floats per env of a history carry: columns 16..37 of a history row (include/navsim.h)
@@ -35,6 +36,39 @@ def _chk_carry(what, t, n_envs, device):
             or not t.is_contiguous() or t.data_ptr() % 16):
         raise NavsimError(f"{what}: a contiguous, 16-byte aligned float32 tensor [{n_envs}, {HIST_CARRY}] on {device}, got "
                           f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+
+
+MAX_SCAN_POOL = 4   # rays per scan column (navsim_set_scan_pool); more is not built
+
+
+def check_scan_pool(scan_pool, n_beams=10, per_env_map=False, policy=None):
+    """The refusals of ``scan_pool`` (sector LiDAR) that need no device, with the library's reasons: an int in 1..4; above 1 only
+    with 10 beams, a shared static map and a policy that is not the 512-wide one.  Returns the int."""
+    if isinstance(scan_pool, bool) or not isinstance(scan_pool, (int, np.integer)) or not 1 <= int(scan_pool) <= MAX_SCAN_POOL:
+        raise ValueError(f"scan_pool {scan_pool!r}: an int in 1..{MAX_SCAN_POOL} (1 = off; more than {MAX_SCAN_POOL} rays per "
+                         "column is not built)")
+    k = int(scan_pool)
+    if k > 1 and int(n_beams) != 10:
+        raise ValueError(f"scan_pool > 1 needs n_beams == 10, not {n_beams}: pooling a 36-beam scan is not built")
+    if k > 1 and per_env_map:
+        raise ValueError("scan_pool > 1 needs a shared static map: pooling over per-env maps is not built")
+    if k > 1 and policy == "resmlp512":
+        raise ValueError("scan_pool > 1 with policy='resmlp512' is not built (the pooled kernels carry the mlp64 policies); "
+                         "use policy='mlp64x2'")
+    return k
+
+
+def pool_scan_reference(rows_dense, k):
+    """The sector-LiDAR rule on the host, numpy -- its statement: rows_dense [..., 10 k + 6] are the rows of an env with 10 k beams
+    (scan / 3.5, then the six other columns); column c of the result [..., 16] is the minimum of dense columns k c .. k c + k - 1
+    (the reference's pick_laser.Pick(scan, k): -inf wins, ties are ties), columns 10..15 are the dense row's last six.  k = 1
+    returns the rows as they are."""
+    rows = np.asarray(rows_dense)
+    k = check_scan_pool(k)
+    if rows.shape[-1] != 10 * k + 6:
+        raise ValueError(f"pool_scan_reference: rows of {10 * k + 6} columns for k = {k}, got {rows.shape}")
+    scan = rows[..., :10 * k].reshape(rows.shape[:-1] + (10, k)).min(axis=-1)
+    return np.concatenate([scan, rows[..., 10 * k:]], axis=-1)
 
 
 def _ptr(t):
@@ -55,10 +89,12 @@ class NavSim:
     def __init__(self, n_envs, n_beams=10, max_episode_steps=0, auto_reset=False, respawn_on_arrive=False,
                  seed=0, env_id_base=0, threshold_arrive=0.2, spawn=(0.0, 0.0, 0.0), goal_box=(-3.6, 3.6),
                  obs_f16=False, device=None, lidar_below_min="clamp", lidar_noise_sigma=0.0, envs_per_workgroup=None,
-                 pair_cast=None):
+                 pair_cast=None, scan_pool=1):
         """envs_per_workgroup / pair_cast: kernel-shape overrides of THIS handle (navsim_set_shape; tests and A/B timing --
         results never depend on them).  None = the dev tools' NAVSIM_EPB / NAVSIM_PAIR_CAST environment variables if set
-        (read here, per handle; libnavsim itself reads nothing from the environment), else the built-in rule."""
+        (read here, per handle; libnavsim itself reads nothing from the environment), else the built-in rule.
+        scan_pool: sector LiDAR (set_scan_pool); 1 = off."""
+        scan_pool = check_scan_pool(scan_pool, n_beams)
         if not torch.cuda.is_available():
             raise NavsimError("navbot_ppo_amd needs a HIP device (MI355X); there is no CPU path")
         self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
@@ -92,6 +128,21 @@ class NavSim:
             pair_cast = knob("NAVSIM_PAIR_CAST") != 0
         if envs_per_workgroup is not None or pair_cast is not None:
             self.set_shape(envs_per_workgroup or 0, pair_cast)
+        self.scan_pool = 1
+        if scan_pool != 1:   # (off: not one call more than before)
+            self.set_scan_pool(scan_pool)
+
+    def set_scan_pool(self, k):
+        """Sector LiDAR (navsim_set_scan_pool): the simulator casts 10 k rays and each of the 10 scan columns is the nearest return
+        of k consecutive rays (pool_scan_reference states the rule; the env is that of 10 k beams, its rows pooled); k in 1..4, 1 =
+        off.  Before or after set_map / set_movers, in any order.  Rows, nets, history rows and checkpoints keep their shape.  The
+        pooled world is HARDER: obstacles the 10 beams passed by are seen, and hit.  Waits for the device; the world changed:
+        ``generation`` is bumped."""
+        k = check_scan_pool(k, self.B, getattr(self, "per_env", False))
+        with torch.cuda.device(self.device):
+            check(lib().navsim_set_scan_pool(self._h, k), "navsim_set_scan_pool")
+        self.scan_pool = k
+        self.generation += 1
 
     def set_shape(self, envs_per_workgroup=0, pair_cast=None):
         """navsim_set_shape: force the workgroup shape (0 = rule; 4 | 8 | 16 | 32 | 64) / the 128-segment passes of this handle."""
@@ -103,7 +154,9 @@ class NavSim:
         """navsim_get_info as a dict: handle facts + the (envs, waves, cast variant) each entry point launches right now."""
         inf = NavsimInfo()
         check(lib().navsim_get_info(self._h, C.byref(inf)), "navsim_get_info")
-        return {n: getattr(inf, n) for n, _ in NavsimInfo._fields_ if n != "reserved"}
+        d = {n: getattr(inf, n) for n, _ in NavsimInfo._fields_ if n != "reserved"}
+        d["scan_pool"] = int(inf.reserved[0])
+        return d
 
     def close(self):
         if getattr(self, "_h", None):
@@ -606,22 +659,26 @@ class VecEnv:
     def __init__(self, n_envs, map="stage_1", n_beams=10, max_episode_steps=500, auto_reset=True, is_training=True,
                  seed=0, env_id_base=0, per_env_map=False, map_seed=0, obs_f16=False, device=None, sampler=None,
                  lidar_below_min="clamp", lidar_noise_sigma=0.0, respawn_on_arrive=False, envs_per_workgroup=None, pair_cast=None,
-                 movers=None):
+                 movers=None, scan_pool=1):
         """movers: moving obstacles (NavSim.set_movers) -- a name of maps.movers_by_name ("orbit4"), a tape [P, M, 4], or a dict:
         tape=... or name=... (+ period=...), phase="random" (default: phase0[i] drawn from (map_seed, env_id_base + i) only, so
         the shards of a multi-GPU run and the single-GPU run give every global env the same phase) | "zero".
         A BANK of tapes, one scenario per env (NavSim.set_mover_bank, maps.resolve_movers): dict(bank=..., periods=..., rects=...,
         assign="random" (default: the tape id from the same hash) | "cycle" | [N] ids), "random:K" (dict(name="random:K", seed=...))
-        or "bank:orbit4,patrol2,..."."""
+        or "bank:orbit4,patrol2,...".
+        scan_pool: sector LiDAR (NavSim.set_scan_pool): k rays min-pooled into each of the 10 scan columns; 1 = off."""
+        scan_pool = check_scan_pool(scan_pool, n_beams, per_env_map or (torch.is_tensor(map) and map.dim() == 3) or
+                                    (not isinstance(map, str) and np.ndim(map) == 3))
         thr = 0.2 if is_training else 0.4  # environment_new.py:44-47
         # what a sibling env on the same world is built from (PPOTrainer's evaluation env: same map / beams / row type / sensor)
-        self.world_args = dict(map=map, n_beams=n_beams, per_env_map=per_env_map, map_seed=map_seed, obs_f16=obs_f16,
-                               sampler=sampler, lidar_below_min=lidar_below_min, lidar_noise_sigma=lidar_noise_sigma,
-                               respawn_on_arrive=respawn_on_arrive, movers=movers)
+        self._world_args = dict(map=map, n_beams=n_beams, per_env_map=per_env_map, map_seed=map_seed, obs_f16=obs_f16,
+                                sampler=sampler, lidar_below_min=lidar_below_min, lidar_noise_sigma=lidar_noise_sigma,
+                                respawn_on_arrive=respawn_on_arrive, movers=movers)
         self.sim = NavSim(n_envs, n_beams=n_beams, max_episode_steps=max_episode_steps, auto_reset=auto_reset,
                           respawn_on_arrive=respawn_on_arrive, seed=seed, env_id_base=env_id_base, threshold_arrive=thr,
                           obs_f16=obs_f16, device=device, lidar_below_min=lidar_below_min,
-                          lidar_noise_sigma=lidar_noise_sigma, envs_per_workgroup=envs_per_workgroup, pair_cast=pair_cast)
+                          lidar_noise_sigma=lidar_noise_sigma, envs_per_workgroup=envs_per_workgroup, pair_cast=pair_cast,
+                          scan_pool=scan_pool)
         self.N, self.B, self.D, self.device = self.sim.N, self.sim.B, self.sim.D, self.sim.device
         self.threshold_arrive = thr
         self.use_vision = False
@@ -655,6 +712,23 @@ class VecEnv:
 
     def close(self):
         self.sim.close()
+
+    @property
+    def scan_pool(self):
+        """the handle's scan_pool as it stands (NavSim.set_scan_pool may have changed it since the constructor)"""
+        return self.sim.scan_pool
+
+    @property
+    def world_args(self):
+        """the constructor's world, with the handle's current scan_pool when it is on (off: the dict is what it was)"""
+        w = dict(self._world_args)
+        if self.sim.scan_pool != 1:
+            w["scan_pool"] = self.sim.scan_pool
+        return w
+
+    def set_scan_pool(self, k):
+        """NavSim.set_scan_pool on the env's handle; scan_pool and world_args follow it"""
+        self.sim.set_scan_pool(k)
 
     def assign_scenarios(self, ids):
         """Gives every env another tape of the bank (NavSim.set_mover_assignment): ids [N] integers in [0, K), the phases redrawn by
@@ -860,12 +934,14 @@ class Env:
     """
 
     def __init__(self, is_training, use_vision=False, vision_dim=64, map="stage_1", seed=0, device=None, movers=None,
-                 scan_history=False):
+                 scan_history=False, scan_pool=1):
         """movers: moving obstacles (an extension, NavSim.set_movers; resolve_env_movers: a scene name, a tape [P, M, 4] or
         dict(tape=... | name=..., phase=int)).  The scan of a step sees tape[(k + 1 + phase) mod P], k = the steps taken since the last
         reset(); the reset observation sees tape[phase].  None: the static world, exactly as without the keyword.
         scan_history: reset() / step() return the 42-vector of stack_rows_reference (the last three scans, cut where the step's
-        `ended` flag -- collision or arrival here -- was set and at every reset()) instead of the 16-vector.  Host code only."""
+        `ended` flag -- collision or arrival here -- was set and at every reset()) instead of the 16-vector.  Host code only.
+        scan_pool: sector LiDAR (NavSim.set_scan_pool): 10 k rays min-pooled into the 10 scan entries; 1 = off."""
+        scan_pool = check_scan_pool(scan_pool)
         if use_vision:
             raise NotImplementedError("camera modality is outside the LiDAR hot path (SURVEY.md 2a)")
         if not isinstance(scan_history, bool):
@@ -876,7 +952,8 @@ class Env:
         self.vision_dim = vision_dim
         self.threshold_arrive = 0.2 if is_training else 0.4
         self._sim = NavSim(1, n_beams=10, max_episode_steps=0, auto_reset=False, respawn_on_arrive=True, seed=seed,
-                           threshold_arrive=self.threshold_arrive, device=device)
+                           threshold_arrive=self.threshold_arrive, device=device, scan_pool=scan_pool)
+        self.scan_pool = scan_pool
         if isinstance(map, str):
             seg = _maps.by_name(map)
             rr, rs = _maps.goal_rects(map)

@@ -65,7 +65,7 @@ def persistent_policy(actor, n_beams=10):
 
 @torch.no_grad()
 def evaluate(actor, num_episodes=100, max_timesteps_per_episode=500, map="stage_1", n_parallel=None, seed=0, device=None,
-             output_dir="", method_name="baseline", log=print, persistent=False, timing=None, movers=None):
+             output_dir="", method_name="baseline", log=print, persistent=False, timing=None, movers=None, scan_pool=1):
     """Every env plays a FIXED quota of q = ceil(num_episodes / n_parallel) whole episodes (its first q; later ones are
     ignored) and stepping continues until every env has met it, so which episodes are reported does not depend on how
     long they last -- taking "the first num_episodes to finish" would over-sample short episodes (early collisions) and
@@ -78,14 +78,15 @@ def evaluate(actor, num_episodes=100, max_timesteps_per_episode=500, map="stage_
     actor or beam count without an evaluation kernel raises ValueError.  movers: moving obstacles as for VecEnv; with a bank of
     tapes the result also holds ``scenarios`` (scenario_report: per tape id episodes and success / collision / time-out rate),
     ``scenario_success_min`` / ``_mean``, logged and, with an output_dir, written to ``<method>_eval_scenarios.csv``.  timing: a dict that receives ``seconds`` (wall clock
-    of the stepping alone) and ``steps`` (env steps behind it)."""
+    of the stepping alone) and ``steps`` (env steps behind it).  scan_pool: sector LiDAR as for VecEnv (the sensor world the policy is
+    judged in; a harder one than scan_pool=1 -- it detects the collisions with obstacles the 10 beams pass by)."""
     n_par = int(n_parallel or min(num_episodes, 1024))
     quota = -(-int(num_episodes) // n_par)
     history = reads_scan_history(actor)   # a scan_history checkpoint: both forms feed it the history rows (the env has 10 beams)
     if persistent:
         policy, flat_actor = persistent_policy(actor)
     env = VecEnv(n_par, map=map, max_episode_steps=max_timesteps_per_episode, auto_reset=True, is_training=False, seed=seed,
-                 device=device, movers=movers)
+                 device=device, movers=movers, scan_pool=scan_pool)
     dev = env.device
     # a bank of tapes (one scenario per env): the episode table is also grouped by the env's tape id, on the host
     tape_id = None if env.sim.movers_tape_id is None else env.sim.movers_tape_id.cpu().numpy()

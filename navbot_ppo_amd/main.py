@@ -105,6 +105,10 @@ def get_args(argv=None):
     p.add_argument("--scan_history", action="store_true", default=False,
                    help="the mlp64x2 policy reads the last three LiDAR scans and the action between them (a 42-column row assembled on "
                         "the device, never across an episode start) instead of one scan; needs --policy mlp64x2; default: off")
+    p.add_argument("--scan_pool", type=int, default=1, choices=[1, 2, 3, 4],
+                   help="sector LiDAR, training and --eval: the simulator casts 10 K rays and each of the 10 scan columns is the nearest "
+                        "return of K consecutive rays (thin obstacles between the 10 beams are seen -- and hit: a harder world); needs "
+                        "--policy mlp64x2; default 1: the reference's 10 beams")
     p.add_argument("--continue_rollouts", action="store_true", default=False,
                    help="only the first rollout starts from a reset: every later one continues the envs' episodes across the iteration "
                         "boundary (short rollouts on many envs); needs --bootstrap_truncated; default: off, as in the reference")
@@ -191,7 +195,7 @@ def main(argv=None):
         actor, _ = ev.load_actor(path, "cuda")
         s = ev.evaluate(actor, num_episodes=args.eval_episodes, max_timesteps_per_episode=args.timesteps_per_episode, map=args.map,
                         seed=args.seed, output_dir=args.output_dir, method_name=args.method_name, persistent=args.eval_persistent,
-                        movers=movers)
+                        movers=movers, scan_pool=args.scan_pool)
         return 0 if s["episodes"] == args.eval_episodes else 1
 
     ctx = ppo.DistCtx()
@@ -208,7 +212,7 @@ def main(argv=None):
                   flush=True)
         sampler = (st, g, dmin, dmax)
     env = VecEnv(hi - lo, map=args.map, max_episode_steps=args.timesteps_per_episode, auto_reset=True, is_training=True,
-                 seed=args.seed, env_id_base=lo, device=ctx.device, sampler=sampler, movers=movers)
+                 seed=args.seed, env_id_base=lo, device=ctx.device, sampler=sampler, movers=movers, scan_pool=args.scan_pool)
     cfg = config_of(args, rollout)
     trainer = ppo.PPOTrainer(env, cfg, ctx)
     if args.resume or args.actor_model:  # main.py:52-89

@@ -80,6 +80,7 @@ def tb_scalars(lg, cfg):
                if "reward_scale" in lg else {}),                                                    # (norm_reward)
             **({"ppo/bootstrapped_frac": lg["bootstrapped_frac"]} if "bootstrapped_frac" in lg else {}),   # (bootstrap_truncated)
             **({"ppo/" + k: lg[k] for k in ("var", "std", "var_grad", "var_steps_skipped")} if "var_grad" in lg else {}),   # (learn_var)
+            **({"env/scan_pool": lg["scan_pool"]} if "scan_pool" in lg else {}),                    # (sector LiDAR on)
             **({"scenarios/train_success_min": lg["train_scenario_success_min"],
                 "scenarios/train_success_mean": lg["train_scenario_success_mean"]}
                if "train_scenario_success_min" in lg else {}),                                      # (scenario_stats / _priority)
@@ -101,6 +102,7 @@ def progress_line(lg):
             + (f" bootstrapped_frac={lg['bootstrapped_frac']:.4f}" if "bootstrapped_frac" in lg else "")
             + (f" var={lg['var']:.4f} std={lg['std']:.4f} entropy={lg['entropy']:.4f} var_grad={lg['var_grad']:.3e} "
                f"var_steps_skipped={lg['var_steps_skipped']}" if "var_grad" in lg else "")
+            + (f" scan_pool={lg['scan_pool']}" if "scan_pool" in lg else "")
             + (f" train scenarios: min={lg['train_scenario_success_min']:.3f} mean={lg['train_scenario_success_mean']:.3f}"
                if "train_scenario_success_min" in lg else "")
             + (f" eval: succ={lg['eval_success']:.3f} coll={lg['eval_collision']:.3f} tmo={lg['eval_timeout']:.3f} "

@@ -14,7 +14,7 @@ from ._native import _navppo, _ptr, check, lib
 from .config import (PPOConfig, check_bootstrap_config, check_continue_config, check_learn_var_config, check_reward_norm_config,
                      check_scan_history_config, check_scenario_config)
 from .distributed import as_ctx
-from .env import HIST_CARRY, HIST_DIM, gae_scan, gae_scan_trunc, rtg_scan, stack_rows
+from .env import HIST_CARRY, HIST_DIM, check_scan_pool, gae_scan, gae_scan_trunc, rtg_scan, stack_rows
 from .evaluate import evaluate_params, make_eval_env
 from .lr_schedule import linear_lr
 from .reward_norm import RET_RMS_INIT, return_moments, reward_scale
@@ -31,6 +31,11 @@ class PPOTrainer:
     scenarios = None   # the ScenarioSampler of scenario_stats / scenario_priority (None: both off)
     _log = None        # the RunLog of the run's files, created at the first write (_run_log)
 
+    @property
+    def scan_pool(self):
+        """the env's scan_pool as it stands now (1 on an env without one)"""
+        return getattr(getattr(getattr(self, "env", None), "sim", None), "scan_pool", 1)
+
     def __init__(self, env, cfg=None, ctx=None):
         self.env, self.cfg = env, cfg or PPOConfig()
         self.ctx = ctx = as_ctx(ctx)
@@ -38,6 +43,8 @@ class PPOTrainer:
         cfg = self.cfg
         N, T, D = env.N, cfg.rollout_len, env.D
         check_scan_history_config(cfg)
+        # sector LiDAR is the env's option (VecEnv(scan_pool=k)): the trainer only refuses what its kernels lack and logs k
+        check_scan_pool(self.scan_pool, env.B, policy=cfg.policy)
         self.scan_history = cfg.scan_history
         if self.scan_history:
             if env.B != 10:
@@ -468,7 +475,8 @@ class PPOTrainer:
                            steps_per_sec=T * N * world / (t2 - t0),                      # ppo.py:855
                            rollout_steps_per_sec=T * N * world / (t1 - t0),
                            # (learn_var: `var` is the update's figure -- what it ended on, what the next rollout draws with)
-                           **(dict(rollout_var=self.var_host) if cfg.learn_var else dict(var=self.var_host)))
+                           **(dict(rollout_var=self.var_host) if cfg.learn_var else dict(var=self.var_host)),
+                           **(dict(scan_pool=self.scan_pool) if self.scan_pool != 1 else {}))   # (off: no key)
         if cfg.eval_every > 0 and self.i_so_far % cfg.eval_every == 0 and self.writes_files:
             self.logger.update(self.evaluate_now())   # rank 0 alone, no collective: the other ranks go on to their next rollout
         if cfg.output_dir and self.writes_files:
